@@ -28,6 +28,13 @@ and kills the child's process group at --launch-timeout.  --gpus 1 never starts 
 kernel_ms: {kernel: [device ms per STEP summed over its launches, launches per step]} from HIP events on the stream each kernel runs on
 (blsgpu_profile_*); "tail_stream_overlapped" runs beside the other kernels and is not additive.
 
+--dump-outputs DIR: after the timed steps of the measured config (before the other_configs ride along), what its LAST timed step
+returned to the caller goes to DIR/<name>.npy as float64 (status codes and indices are exact there): config 2 the per-item status
+vector (status.npy), configs 3 / 5 the one status, config 4 the status and blsgpu_aggregate_verify's two aux indices (aux.npy).
+Rank r > 0 of a multi-rank run writes <name>_rank<r>.npy.
+The inputs are a fixed function of the arguments, so two builds can be compared file by file.  At most 64 MB in all: a larger
+array is replaced by a fixed, seeded sample of its entries (<name>.npy) and their sorted positions (<name>_index.npy).
+
 Prints ONE JSON line on rank 0 (contract in the task description), including
   roofline      the dominant kernel's algorithmic HBM bytes / its HIP-event-measured duration vs 8 TB/s (and vs 6.29 TB/s)
   cpu_baseline  the oracle timed on a bounded sample of the same workload on this box's host cores (config 2, N = 1)
@@ -56,6 +63,8 @@ FPMUL_PEAK_G = 74.0                 # profiles/r03_ubench3_mad_rates.txt: the fu
                                     # (72-76 G multiplication-equivalents/s over runs and boxes; round 1 measured 66.6 with lazy signed limbs)
 FPMUL_MAD_ONLY_G = 85.0             # the same pipe with nothing but multiply-adds: 33.5 T lane-MAD/s / 392 per multiplication
 CONFIG_SIZES = {3: 1048576, 4: 262144, 5: 65536}
+DUMP_BYTES = 64 << 20               # --dump-outputs: at most this much in all (over all ranks)
+DUMP_SEED = 20250101                # --dump-outputs: the sample of an array too large to write whole
 VARIANTS = {'g1m': (1, 0, 'Bls12381G1Impl/Modern'), 'g2m': (2, 0, 'Bls12381G2Impl/Modern'), 'g2l': (2, 1, 'Bls12381G2Impl/Legacy')}
 
 
@@ -152,6 +161,7 @@ class Harness:
         from agora_blsful_amd import dist as bd
         self.bd = bd
         self.sh = bd.Sharded(self.ops, self.dist)
+        self.outputs = {}       # what the last timed step of the latest run_config* returned to its caller (--dump-outputs)
 
     def P(self, t):
         return ctypes.c_void_p(t.data_ptr())
@@ -232,6 +242,28 @@ def r6(x):
     return int(round(x)) if abs(x - round(x)) < 1e-9 * max(1.0, abs(x)) else float('%.6g' % x)
 
 
+def write_outputs(d, outputs, rank=0, world=1):
+    """--dump-outputs: {name: array} -> d/<name>[_rank<r>].npy as float64.  This rank's share of DUMP_BYTES is split evenly over
+    the arrays; one over its share is written as a seeded sample of its entries (the same positions in every run of the same
+    size) with those positions as d/<name>_index[_rank<r>].npy.  Returns {file name: entries written}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sfx = '_rank%d' % rank if rank else ''
+    share = DUMP_BYTES // max(1, world) // max(1, len(outputs)) - 2 * 4096     # room for the two files' .npy headers
+    written = {}
+    for name, a in outputs.items():
+        a = np.asarray(a).astype(np.float64).reshape(-1)
+        if a.nbytes > share:
+            k = max(1, share // 16)              # 8 bytes of value + 8 of position per sampled entry
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, k, replace=False))
+            np.save(os.path.join(d, name + '_index' + sfx + '.npy'), idx.astype(np.float64))
+            written[name + '_index' + sfx] = k
+            a = a[idx]
+        np.save(os.path.join(d, name + sfx + '.npy'), a)
+        written[name + sfx] = a.size
+    return written
+
+
 def kernel_ms(prof, steps):
     """{kernel: [device ms per step (all its launches), launches per step]}"""
     return {k: [round(v[0] / steps, 3), round(v[1] / steps, 2)] for k, v in prof.items() if v[1]}
@@ -287,6 +319,7 @@ def run_config3(h, steps, warmup, n_total=None, as_deserialised=False):
             res.append(sh.multi_verify(1, api.POP, d_pks, nl, agg, FIXED_MSG))
     dt, prof = h.timed(step, steps, warmup)
     assert all(r == api.OK for r in res)
+    h.outputs = {'status': [res[-1]]}
     out = {'metric': 'MultiSignature::verify public keys/s', 'value': r6(n * steps / dt),
            'unit': 'public keys/s', 'ms_per_step': r6(dt / steps * 1e3), 'scaling': 'strong',
            'config': {'workload': 'configs[2] MultiSignature<Bls12381G1Impl>::verify, G2 keys RAW_PROJ%s in HBM, one 32-byte message, PoP'
@@ -334,10 +367,14 @@ def run_config4(h, steps, warmup, n_total=None):
                                                      ctypes.cast(aux, ctypes.c_void_p)))
             res.append(stc.value)
     else:
+        aux = [None, None]
+
         def step():
-            res.append(sh.aggregate_verify(1, api.BASIC, d_pks, d_msgs, d_offs, nl, agg, lo, n_total=n)[0])
+            st, aux[:] = sh.aggregate_verify(1, api.BASIC, d_pks, d_msgs, d_offs, nl, agg, lo, n_total=n)
+            res.append(st)
     dt, prof = h.timed(step, steps, warmup)
     assert all(r == api.OK for r in res)
+    h.outputs = {'status': [res[-1]], 'aux': list(aux)}
     out = {'metric': 'AggregateSignature::verify (pk, msg) pairs/s', 'value': r6(n * steps / dt),
            'unit': 'pairs/s', 'ms_per_step': r6(dt / steps * 1e3), 'scaling': 'strong',
            'config': {'workload': 'configs[3] AggregateSignature<Bls12381G1Impl>::verify, distinct (pk, msg) pairs, Basic, 32-byte messages, RAW_PROJ in HBM',
@@ -377,6 +414,7 @@ def run_config5(h, steps, warmup, variant='g1m', n_total=None):
             res.append(sh.verify_secure(sg, api.BASIC, d_pks, nl, agg, FIXED_MSG, lo, mode, n_total=n))
     dt, prof = h.timed(step, steps, warmup)
     assert all(r == api.OK for r in res)
+    h.outputs = {'status': [res[-1]]}
     alg = (2 * (288 if pk_group == 2 else 144) + 64)
     out = {'metric': 'verify_secure public keys/s', 'value': r6(n * steps / dt), 'unit': 'public keys/s',
            'ms_per_step': r6(dt / steps * 1e3), 'scaling': 'strong', 'variant': name,
@@ -413,6 +451,7 @@ def run_config2_grouped(h, steps, warmup, n, tampered_every):
         assert torch.equal(d_status, expect), 'grouped verification: verdict vector differs from the expected one'
 
     dt, prof = h.timed(step, steps, warmup, after_warmup=check)
+    h.outputs = {'status': d_status.cpu().numpy()}
     check()
     return {'metric': 'BLS12-381 sig verifications/sec (batch, opt-in grouped mode)', 'value': r6(h.world * n * steps / dt), 'unit': 'verifications/s',
             'ms_per_step': r6(dt / steps * 1e3), 'scaling': 'weak',
@@ -449,6 +488,7 @@ def run_config2(h, args, sg=1, steps=None, warmup=None, headline=True):
         assert torch.equal(d_status, expect), 'verdict vector differs from the expected one'
 
     dt, prof = h.timed(step, steps, warmup, after_warmup=check)
+    h.outputs = {'status': d_status.cpu().numpy()}
     check()
     out = None
     if rank == 0:
@@ -567,22 +607,32 @@ def main(argv=None):
     ap.add_argument('--extras-timeout', type=int, default=90, help='seconds ONE other_configs entry may take (input signing included; scaled up with the rank count) before the headline line is printed without the rest')
     ap.add_argument('--launch-timeout', type=int, default=1500, help='--gpus N > 1 without a launcher: seconds the child launcher may run before its process group is killed')
     ap.add_argument('--fail-extra', default=None, metavar='NAME[:RANK]', help='test aid: make that other_configs entry raise on that rank (default 0) before its collectives')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB)')
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.gpus > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args, argv))
     h = Harness(args)
     common = {'n_gpus': h.world, 'steps': args.steps, 'warmup': args.warmup, 'higher_is_better': True, 'vs_baseline': None, 'dtype': 'u32',
               'data': 'synthetic'}
     exit_code = 0
+
+    def dump():
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, h.outputs, h.rank, h.world)
     if args.config == 2 and args.grouped is not None:
         out = run_config2_grouped(h, args.steps, args.warmup, args.n, args.grouped)
+        dump()
         out.update(common)
     elif args.config == 2 and args.impl == 'g2':
         out = run_config2(h, args, sg=2, headline=False)
+        dump()
         if out is not None:
             out['config']['note'] = 'NOT the headline: Bls12381G2Impl orientation of configs[1] (--impl g2)'
     elif args.config == 2:
         out = run_config2(h, args)
+        dump()                          # before the other configs replace h.outputs
         if not args.no_extras:
             # The other BASELINE configs ride along at every N: at N > 1 they are collectives over RCCL, so after each one the
             # ranks AGREE on its outcome through the rendezvous store (Harness.agree) before anybody enters the next collective.
@@ -663,6 +713,7 @@ def main(argv=None):
             out = run_config4(h, args.steps, args.warmup, args.size)
         else:
             out = run_config5(h, args.steps, args.warmup, args.variant, args.size)
+        dump()
         out.update(common)
         out['rccl_ranks'] = h.rccl_ranks()
     if h.rank == 0 and out is not None:

@@ -1,8 +1,13 @@
 """bench.py's result-line arithmetic on a synthetic kernel profile (CPU): kernel_ms is per STEP with a launch count, the roofline is
 per LAUNCH of the kernel with the largest per-step total on the main stream, and a chunked kernel's launch covers one chunk
-(config 4's line divided the whole call's bytes by one chunk's launch -- 4x too high)."""
+(config 4's line divided the whole call's bytes by one chunk's launch -- 4x too high); --dump-outputs and --steps."""
 import importlib.util
+import json
 import os
+import subprocess
+import sys
+
+import pytest
 
 import util
 
@@ -61,3 +66,53 @@ def test_self_launch_is_chosen_only_without_a_launcher(monkeypatch):
         except Stop:
             pass
         assert calls == []
+
+
+def test_dump_outputs_writes_float64_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float64 with its values exact; rank r > 0 adds _rank<r>; an array over its share
+    of the budget becomes a seeded sample (the same positions every run) plus those positions, and the files stay within the budget"""
+    import numpy as np
+    b = load_bench()
+    w = b.write_outputs(str(tmp_path / 'a'), {'status': np.array([0, 1, 2, -3], dtype=np.int32), 'aux': [3, (1 << 40) + 1]})
+    assert w == {'status': 4, 'aux': 2}
+    st, aux = np.load(tmp_path / 'a' / 'status.npy'), np.load(tmp_path / 'a' / 'aux.npy')
+    assert st.dtype == np.float64 and st.tolist() == [0, 1, 2, -3] and aux.tolist() == [3, (1 << 40) + 1]
+    monkeypatch.setattr(b, 'DUMP_BYTES', 2 * (16 * 1024 + 2 * 4096))
+    big = np.arange(100000, dtype=np.int32) * 3
+    runs = []
+    for d in ('b', 'c'):
+        w = b.write_outputs(str(tmp_path / d), {'status': big}, rank=1, world=2)
+        assert w == {'status_rank1': 1024, 'status_index_rank1': 1024}
+        idx, val = np.load(tmp_path / d / 'status_index_rank1.npy'), np.load(tmp_path / d / 'status_rank1.npy')
+        assert val.dtype == np.float64 and (np.diff(idx) > 0).all() and (val == 3 * idx).all()
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= b.DUMP_BYTES // 2
+        runs.append(idx)
+    assert (runs[0] == runs[1]).all()
+
+
+def test_steps_below_one_is_refused():
+    """ms_per_step divides by --steps: zero timed steps is an argument error, not a division by zero after the GPU work"""
+    b = load_bench()
+    with pytest.raises(SystemExit) as e:
+        b.main(['--steps', '0'])
+    assert e.value.code == 2
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_steps_statuses(pkg, tmp_path):
+    """`bench.py --dump-outputs DIR` on one GPU: status.npy is the status vector of the last timed step (the 1 % tampered items
+    INVALID_SIGNATURE, the rest OK) and the same for another number of steps; the line reports those steps and ms_per_step"""
+    import numpy as np
+    expect = np.zeros(1024)
+    expect[37::100] = pkg.api.INVALID_SIGNATURE
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    for steps in (1, 3):
+        d = tmp_path / ('steps%d' % steps)
+        r = subprocess.run([sys.executable, os.path.join(util.ROOT, 'bench.py'), '--items', '1024', '--steps', str(steps), '--warmup', '1',
+                            '--no-extras', '--cpu-sample', '64', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600, cwd=util.ROOT, env=env)
+        assert r.returncode == 0, r.stderr[-4000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == steps and line['ms_per_step'] > 0
+        assert sorted(os.listdir(d)) == ['status.npy']
+        st = np.load(d / 'status.npy')
+        assert st.dtype == np.float64 and (st == expect).all(), np.flatnonzero(st != expect)[:10]
