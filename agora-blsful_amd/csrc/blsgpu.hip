@@ -1327,18 +1327,24 @@ msm_plan msm_make_plan(size_t n, int G) {
   if (knobs().msm_ch) p.CH = (int)knobs().msm_ch;      // clamped to what the kernels assume
   if (p.c < 4) p.c = 4;
   if (p.c > 16) p.c = 16;
+  p.W = 255 / p.c;                      // scalars are < r < 2^255
+  p.clast = 255 - p.c * (p.W - 1);      // the last window takes the remainder: c <= clast < 2c ...
+  if (p.clast > 16) {                   // ... unless that is above 16 bits (c = 13, 14, 16: 21, 17, 31 bits, up to 2^31 buckets):
+    p.W++;                              // one more window, and the last one narrower than c (8, 3, 15 bits)
+    p.clast = 255 - p.c * (p.W - 1);
+  }
   if (p.CH < 1) p.CH = 1;
   while (p.CH & (p.CH - 1)) p.CH &= p.CH - 1;                       // a power of two, so that it divides 2^c and 2^clast
   if (p.CH > (1 << p.c)) p.CH = 1 << p.c;
-  p.W = 255 / p.c;                      // scalars are < r < 2^255
-  p.clast = 255 - p.c * (p.W - 1);      // the last window takes the remainder: c <= clast < 2c
+  if (p.CH > (1 << p.clast)) p.CH = 1 << p.clast;
   p.nb = ((size_t)(p.W - 1) << p.c) + ((size_t)1 << p.clast);
   p.nchunks = p.nb / p.CH;
   return p;
 }
 size_t msm2_ws_bytes(size_t n);
-size_t msm_ws_bytes(size_t n) {         // callers reserve for either group and either generation
+size_t msm_ws_bytes(size_t n) {         // callers reserve for either group and for the generation that runs
   size_t need = msm2_ws_bytes(n);
+  if (!msm_use_v1()) return need;       // the first generation's plan is sized only when BLSGPU_MSM_V1 selects it
   for (int G = 1; G <= 2; G++) {
     msm_plan p = msm_make_plan(n, G);
     size_t b = 3 * pad256(4 * p.nb) + pad256(4 * n * p.W) + pad256(4 * scan_tiles(p.nb)) + pad256(288 * p.nb) + pad256(288 * p.nchunks) + 4096;
