@@ -35,7 +35,7 @@ EXPORTS = [
     'blsgpu_aggregate_partial', 'blsgpu_fp12_product_is_one', 'blsgpu_core_verify', 'blsgpu_deserialize', 'blsgpu_pop_verify_batch', 'blsgpu_aggregate_secure',
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
-    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
 ]
 
 
@@ -141,6 +141,7 @@ def load_library(path=None):
         lib.blsgpu_core_verify_hashed.argtypes = [ci, vp, vp, vp, sz, i32p]
         lib.blsgpu_debug_wide_mul.argtypes = [u8p, u8p, sz, ci, u8p]
         lib.blsgpu_debug_wide_program.argtypes = [vp, sz, ci, u8p, u8p]
+        lib.blsgpu_debug_finalexp_batch.argtypes = [vp, sz, ci, sz, i32p]
         lib.blsgpu_verify_batch_grouped.argtypes = [ci, ci, vp, vp, u8p, vp, sz, ci, ctypes.c_uint64, i32p]
         lib.blsgpu_signatures_from_tagged.argtypes = [ci, u8p, sz, u8p, vp, i32p]
         lib.blsgpu_signatures_to_tagged.argtypes = [ci, u8p, vp, sz, ci, u8p]
@@ -469,6 +470,16 @@ def debug_wide_mul(a_list, b_list, reps=1):
     out = ctypes.create_string_buffer(48 * max(n, 1))
     _check(lib.blsgpu_debug_wide_mul(_ptr(b''.join(a_list)), _ptr(b''.join(b_list)), n, reps, ctypes.cast(out, ctypes.c_void_p)))
     return [out.raw[48 * i:48 * (i + 1)] for i in range(n)]
+
+
+def debug_finalexp_batch(records, form, chunk=0, status=None):
+    """Per-record verdicts (OK / INVALID_SIGNATURE) of the batch final exponentiation `form` (0: one kernel, 1: segments, 2: the
+    round-1/2 kernel) on 576-byte Fp12 records; entries of `status` that are not OK are skipped and returned unchanged."""
+    lib = init()
+    n = len(records)
+    st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
+    _check(lib.blsgpu_debug_finalexp_batch(_ptr(b''.join(records)), n, form, chunk, ctypes.cast(st, ctypes.c_void_p)))
+    return list(st[:n])
 
 
 _wide_defs = None

@@ -633,6 +633,24 @@ void trim_workspaces(Ctx* c) {
   }
 }
 
+// the final exponentiation and verdict of items [first, first + cnt) of the Fp12 workspace d_f (stride n), two lanes per item, with
+// the context's line workspace as the value store (FX_STORE_WORDS rows of row_stride(lanes_for(cnt)) words, reserved by the caller);
+// items whose status is not BLS_OK are skipped.  seg: in segments, the compressed squarings of each a^x on four lanes per item at four
+// waves per SIMD (k_cyc_run4) between them; otherwise one kernel (k_finalexp2s).
+void launch_finalexp_chunk(Ctx* c, size_t n, size_t first, size_t cnt, const uint32_t* d_f, int32_t* d_status, bool seg) {
+  const size_t nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
+  const dim3 grid((unsigned)(nlanes / BLS_BLOCK));
+  if (seg) {
+    const dim3 grid4(blocks_for(4 * cnt));
+    for (int s = 0; s <= 5; s++) {
+      KL(KID_FINALEXP, k_finalexp_seg, grid, dim3(BLS_BLOCK), s, n, first, cnt, d_f, c->lines_ws, lanes, d_status);
+      if (s < 5) KL(KID_CYCRUN, k_cyc_run4, grid4, dim3(BLS_BLOCK), cnt, c->lines_ws, lanes, (const int32_t*)d_status, first);
+    }
+  } else {
+    KL(KID_FINALEXP, k_finalexp2s, grid, dim3(BLS_BLOCK), n, first, cnt, d_f, c->lines_ws, lanes, d_status);
+  }
+}
+
 // the two-pair pairing check of every item whose status is still BLS_OK: status <- OK / INVALID_SIGNATURE.
 // fixed_g2: the second pair's G2 member is a constant with precomputed lines: 1 = -g2, 2 = -[c] g2 (csrc/g2neg_lines.cuh)
 int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2) {
@@ -675,16 +693,7 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
         }
         KL(KID_MILLER2, k_millerf2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const int32_t*)d_status, (const uint32_t*)c->lines_ws, lanes, d_f);
         // the chunk's line values are consumed: the same memory is the value store of the final exponentiation (3.4 KB per lane)
-        if (!finalexp_v1 && finalexp_seg) {
-          // in segments, the compressed squarings of each a^x on four lanes per item at four waves per SIMD (k_cyc_run4)
-          const dim3 grid4(blocks_for(4 * cnt));
-          for (int seg = 0; seg <= 5; seg++) {
-            KL(KID_FINALEXP, k_finalexp_seg, grid, dim3(BLS_BLOCK), seg, n, first, cnt, (const uint32_t*)d_f, c->lines_ws, lanes, d_status);
-            if (seg < 5) KL(KID_CYCRUN, k_cyc_run4, grid4, dim3(BLS_BLOCK), cnt, c->lines_ws, lanes, (const int32_t*)d_status, first);
-          }
-        } else if (!finalexp_v1) {
-          KL(KID_FINALEXP, k_finalexp2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_f, c->lines_ws, lanes, d_status);
-        }
+        if (!finalexp_v1) launch_finalexp_chunk(c, n, first, cnt, d_f, d_status, finalexp_seg);
       }
       if (finalexp_v1) KL(KID_FINALEXP_V1, k_finalexps, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_f, d_status);
     } else {
@@ -3261,6 +3270,41 @@ int blsgpu_debug_wide_program(const uint32_t* prog, size_t len, int reps, const 
   KL(KID_WIDE, k_wide_prog_test, dim3(1), dim3(WIDE_ENGINE_BLOCK), (const uint32_t*)d_prog, (int)len, reps, (const uint8_t*)d_in, d_out);
   HIPCK(hipGetLastError());
   if (d_out != t_out && (rc = copy_out(c, t_out, d_out, 576))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* Self-test hook of the batch final exponentiation + verdict (run_pairing2's two-lane forms) on caller-supplied Fp12 records (576
+ * bytes, the record format of blsgpu_fp12_product_is_one).  form 0: k_finalexp2s, 1: k_finalexp_seg + k_cyc_run4, both chunk by
+ * chunk through launch_finalexp_chunk with the line workspace as the value store, as the verify path runs them; 2: k_finalexps.
+ * chunk: items per chunk of forms 0 and 1 (0: the library's).  status is in/out: an entry that is not BLSGPU_OK on entry is
+ * skipped and left as it is. */
+int blsgpu_debug_finalexp_batch(const void* f12s, size_t n, int form, size_t chunk, int32_t* status) try {
+  if (!initialised()) return NOT_INIT();
+  if (n == 0) return 0;
+  if (!f12s || !status || form < 0 || form > 2) return fail(BLSGPU_E_ARG, "bad argument");
+  CTX_ACQUIRE(c);
+  int rc = arena_reserve(c, pad256(576 * n) + pad256(4 * n) + pad256((size_t)WS_F_WORDS * 4 * n) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_in, *d_st;
+  if ((rc = stage_in(c, f12s, 576 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  int32_t* d_status = (int32_t*)d_st;
+  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
+  if (!d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  KL(KID_F12_IO, k_f12_import, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_in, d_f, n);
+  if (form == 2) {
+    KL(KID_FINALEXP_V1, k_finalexps, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_f, d_status);
+  } else {
+    if (chunk == 0) chunk = miller_chunk_items() ? miller_chunk_items() : n;
+    if (chunk > n) chunk = n;
+    if (lines_reserve(c, (size_t)FX_STORE_WORDS * 4 * row_stride(lanes_for(chunk)))) return fail(BLSGPU_E_HIP, "no room for the value store");
+    for (size_t first = 0; first < n; first += chunk) launch_finalexp_chunk(c, n, first, n - first < chunk ? n - first : chunk, d_f, d_status, form == 1);
+  }
+  HIPCK(hipGetLastError());
+  if (d_status != status) return copy_out_and_sync(c, status, d_status, 4 * n);
   SYNC_FLUSH(c);
   return 0;
 }

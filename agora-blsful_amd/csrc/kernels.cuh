@@ -2352,10 +2352,10 @@ static __device__ __noinline__ int fx_is_one(lds_u32* sh) {
   sh_ld_f12(a, sh);
   return fp12_is_one(a) ? BLS_OK : BLS_ERR_INVALID_SIGNATURE;
 }
-// A == conj(V[slot]) ?
+// A == conj(V[slot]) and V[slot] != 0 ?  (a zero f passes the comparison: pairing.cuh final_exp_is_one)
 static __device__ __noinline__ int fx_eq_conj(lds_u32* sh, uint32_t* vp, size_t lanes, uint32_t t, int slot) {
   const vs_ref v = {vp, lanes, t};
-  bool eq = true;
+  bool eq = true, zero = true;
 #pragma unroll
   for (int j = 0; j < 6; j++) {
     hfp2 a, b;
@@ -2363,8 +2363,9 @@ static __device__ __noinline__ int fx_eq_conj(lds_u32* sh, uint32_t* vp, size_t 
     vs_ld(b.v, v, slot, j);
     if (j >= 3) fp2_neg(b, b);
     eq = fp2_eq(a, b) && eq;
+    zero = fp2_is_zero(b) && zero;
   }
-  return eq ? BLS_OK : BLS_ERR_INVALID_SIGNATURE;
+  return eq && !zero ? BLS_OK : BLS_ERR_INVALID_SIGNATURE;
 }
 // items [first, first + count) of the Fp12 workspace fws (stride n, as k_millerf2s / k_miller2s leave it)
 __global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES) __attribute__((disable_tail_calls))

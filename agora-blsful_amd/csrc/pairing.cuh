@@ -604,8 +604,9 @@ BLS_FN void final_exponentiation(fp12_t<F2>& r, const fp12_t<F2>& fin) {
   fp12_mul(u, u, f);  // f^3
   fp12_mul(r, t, u);
 }
-// the verdict only: t f^3 == 1  <=>  t f^2 == conj(f)  (f lies in the cyclotomic subgroup after the easy part: its conjugate is its
-// inverse) -- one Fp12 product less than forming the value (round 4)
+// the verdict only: t f^3 == 1  <=>  t f^2 == conj(f) and f != 0  (f lies in the cyclotomic subgroup after the easy part: its
+// conjugate is its inverse) -- one Fp12 product less than forming the value (round 4).  fin = 0 is not in Fp12*: the easy part then
+// leaves f = t = 0 (the inversion maps 0 to 0), which satisfies the comparison, so a zero f fails the check (f = 0 exactly when fin = 0).
 template <class F2>
 BLS_FN bool final_exp_is_one(const fp12_t<F2>& fin) {
   fp12_t<F2> f, t, u, c;
@@ -613,6 +614,8 @@ BLS_FN bool final_exp_is_one(const fp12_t<F2>& fin) {
   fp12_cyclotomic_sqr(u, f);
   fp12_mul(u, t, u);
   fp12_conj(c, f);
-  return fp2_eq(u.c0.a0, c.c0.a0) && fp2_eq(u.c0.a1, c.c0.a1) && fp2_eq(u.c0.a2, c.c0.a2) && fp2_eq(u.c1.a0, c.c1.a0) && fp2_eq(u.c1.a1, c.c1.a1) &&
-         fp2_eq(u.c1.a2, c.c1.a2);
+  const bool zero = fp2_is_zero(c.c0.a0) && fp2_is_zero(c.c0.a1) && fp2_is_zero(c.c0.a2) && fp2_is_zero(c.c1.a0) && fp2_is_zero(c.c1.a1) &&
+                    fp2_is_zero(c.c1.a2);
+  return !zero && fp2_eq(u.c0.a0, c.c0.a0) && fp2_eq(u.c0.a1, c.c0.a1) && fp2_eq(u.c0.a2, c.c0.a2) && fp2_eq(u.c1.a0, c.c1.a0) &&
+         fp2_eq(u.c1.a1, c.c1.a1) && fp2_eq(u.c1.a2, c.c1.a2);
 }

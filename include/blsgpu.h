@@ -280,6 +280,12 @@ int blsgpu_debug_wide_mul(const uint8_t* a, const uint8_t* b, size_t n, int reps
  * format of csrc/wide_tables.cuh, Fp12 operations on the arrays F, T, U, W, ACC only) `reps` times on one workgroup with
  * F = U = W = ACC = the Fp12 at f_in (twelve 48-byte Montgomery elements) and T = 0; t_out <- T.  prog: host memory. */
 int blsgpu_debug_wide_program(const uint32_t* prog, size_t len, int reps, const uint8_t* f_in, uint8_t* t_out);
+/* Self-test hook of the batch final exponentiation + verdict on caller-supplied Fp12 records (576 B, the record format of
+ * blsgpu_fp12_product_is_one).  form 0 = k_finalexp2s, 1 = k_finalexp_seg + k_cyc_run4, 2 = k_finalexps; chunk = items per chunk
+ * of the chunked forms (0: the library's).  status is in/out: an entry that is not BLSGPU_OK on entry is skipped and left as it
+ * is, as the verify path skips identity items; the others become BLSGPU_OK (fin^(3 (p^12 - 1) / r) == 1) or
+ * BLSGPU_ERR_INVALID_SIGNATURE. */
+int blsgpu_debug_finalexp_batch(const void* f12s, size_t n, int form, size_t chunk, int32_t* status);
 
 /* Sign side, provided so that benchmarks and tests can build inputs on the device:
  * pk[i] = sk[i] * g (SecretKey::public_key, src/secret_key.rs:342-344) and

@@ -454,6 +454,18 @@ int hs_pow_x_identity_check(void) {
   g_cyc_kara = keep;
   return ok;
 }
+// the verdict of the final exponentiation on a given Fp12 (6 fp2 in w-power order, Montgomery) through both tower instantiations:
+// pairing_verdict (what k_finalexps / k_finalexp_ones run); -100 - split verdict when the two disagree
+int hs_final_verdict(const uint32_t* a) {
+  fp12 x;
+  fp2* cx[6] = {&x.c0.a0, &x.c1.a0, &x.c0.a1, &x.c1.a1, &x.c0.a2, &x.c1.a2};
+  for (int k = 0; k < 6; k++) raw_fp2(*cx[k], a + 24 * k);
+  fp12_t<hfp2> xs;
+  hfp2* cs[6] = {&xs.c0.a0, &xs.c1.a0, &xs.c0.a1, &xs.c1.a1, &xs.c0.a2, &xs.c1.a2};
+  for (int k = 0; k < 6; k++) { cs[k]->c[0] = cx[k]->c0; cs[k]->c[1] = cx[k]->c1; }
+  const int v = pairing_verdict(x), vs = pairing_verdict(xs);
+  return v == vs ? v : -100 - vs;
+}
 // checked decompression: returns the status code; on success writes the re-compressed (modern) bytes
 int hs_decompress(int group, const uint8_t* in, int legacy, uint8_t* out) {
   if (group == 1) {

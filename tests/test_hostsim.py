@@ -333,6 +333,17 @@ def test_pairing_values(hs):
     assert hs.hs_miller_merged_matches(util.g1_aff_raw(P1), util.g2_aff_raw(Q1), util.g1_aff_raw(P2), util.g2_aff_raw(Q2)) == 1
 
 
+def test_final_verdict_fails_closed_on_zero(hs):
+    """pairing_verdict (k_finalexps, k_finalexp_ones) in both tower instantiations on crafted Fp12 values: 0 is not in Fp12* and
+    must be INVALID -- the comparison t f^2 == conj(f) alone holds for f = t = 0 -- and the other families agree with the oracle
+    (Fp2 / Fp6 elements run the declining compressed chains)."""
+    import finalexp_cases as fc
+    assert hs.hs_final_verdict(util.f12_raw((c.F2_ZERO,) * 6)) == fc.INVALID
+    pool = {name: v for name, _, v in fc.family_pool()}
+    for name in ('one', 'minus_one', 'fp2_0', 'fp6_0', 'y^r_0', 'y^r*s_0', 'y_0', 'y^r*z_0', 'miller_valid_0', 'miller_invalid_0'):
+        assert hs.hs_final_verdict(util.f12_raw(pool[name])) == fc.verdict(pool[name]), name
+
+
 def test_pairing_product_by_entries_and_horner_chain(hs):
     """The pairing product as run_miller_product_tree takes it (csrc/kernels.cuh k_linesp / k_line_quad / k_f12_fold4, engine program
     HORNER): per Miller entry the product over the items of their line values (four items merged two by two and multiplied, then folds
