@@ -25,6 +25,7 @@ MODERN, LEGACY = 0, 1
 OK, INVALID_SIGNATURE, SIG_IDENTITY, PK_IDENTITY, DUPLICATE_MESSAGE, INVALID_COEFFICIENT, BAD_LENGTH, BAD_ENCODING, \
     LEGACY_FORMAT = range(9)
 COMMITMENT_IDENTITY, PROOF_IDENTITY, ZERO_CHALLENGE = 9, 10, 11    # blsgpu_sig_proof_verify_batch only
+INVALID_SCHEME, VSSS_ERROR = 12, 13                                  # blsgpu_combine_shares only
 
 EXPORTS = [
     'blsgpu_init', 'blsgpu_shutdown', 'blsgpu_last_error', 'blsgpu_verify_batch', 'blsgpu_multi_verify',
@@ -36,6 +37,7 @@ EXPORTS = [
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
     'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_combine_shares',
 ]
 
 
@@ -80,6 +82,10 @@ def error_from_status(st, aux=(0, 0), aggregate=False):
         return BlsError('DeserializationError')
     if st == LEGACY_FORMAT:
         return BlsError('LegacyFormatError')
+    if st == INVALID_SCHEME:
+        return BlsError('InvalidSignatureScheme')
+    if st == VSSS_ERROR:
+        return BlsError('VsssError')
     return BlsError('Unknown', str(st))
 
 
@@ -145,6 +151,7 @@ def load_library(path=None):
         lib.blsgpu_verify_batch_grouped.argtypes = [ci, ci, vp, vp, u8p, vp, sz, ci, ctypes.c_uint64, i32p]
         lib.blsgpu_signatures_from_tagged.argtypes = [ci, u8p, sz, u8p, vp, i32p]
         lib.blsgpu_signatures_to_tagged.argtypes = [ci, u8p, vp, sz, ci, u8p]
+        lib.blsgpu_combine_shares.argtypes = [ci, u8p, vp, u8p, u64p, sz, ci, vp, i32p]
         _lib = lib
     return _lib
 
@@ -371,6 +378,35 @@ def aggregate_secure(sig_group, pks, sigs, ser_format=MODERN, fmt=FMT_RAW_PROJ):
     return st.value, out.raw
 
 
+def combine_shares(group, sets, fmt=FMT_RAW_PROJ):
+    """Threshold recovery of many independent sets in one call (blsgpu_combine_shares): `sets` is a list of lists of
+    (identifier: int, raw point, scheme or None).  Scheme tags are checked only when every share of the call carries one
+    (Signature::from_shares); None everywhere is PublicKey::from_shares.  Returns (RAW_PROJ points, statuses), one per set."""
+    lib = init()
+    n_sets = len(sets)
+    flat = [sh for st in sets for sh in st]
+    offs = (ctypes.c_uint64 * (n_sets + 1))()
+    t = 0
+    for s, st in enumerate(sets):
+        offs[s] = t
+        t += len(st)
+    offs[n_sets] = t
+    tagged = [sh[2] is not None for sh in flat]
+    if any(tagged) and not all(tagged):
+        raise ValueError('either every share carries a scheme or none does')
+    ids = b''.join(int(sh[0]).to_bytes(32, 'little') for sh in flat)
+    pts = b''.join(sh[1] for sh in flat)
+    sch = bytes(sh[2] for sh in flat) if flat and all(tagged) else None
+    osz = 144 if group == 1 else 288
+    out = ctypes.create_string_buffer(osz * max(n_sets, 1))
+    stv = (ctypes.c_int32 * max(n_sets, 1))()
+    _check(lib.blsgpu_combine_shares(group, _ptr(ids) if ids else None, _ptr(pts) if pts else None, _ptr(sch) if sch else None,
+                                     ctypes.cast(offs, ctypes.c_void_p), n_sets, fmt, ctypes.cast(out, ctypes.c_void_p),
+                                     ctypes.cast(stv, ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[osz * i:osz * (i + 1)] for i in range(n_sets)], list(stv)[:n_sets]
+
+
 def deserialize(group, blobs, legacy=False):
     """(RAW_PROJ points, statuses) from 48/96-byte encodings: checked decompression on the GPU."""
     lib = init()
@@ -580,6 +616,16 @@ class TensorOps:
             _check(fn(self._p(pts), self._p(scalars), n, FMT_RAW_PROJ, self._p(out)))
         return out
 
+    def combine_shares(self, group, ids, pts, schemes, offs, n_sets, fmt=FMT_RAW_PROJ):
+        """(RAW_PROJ points as one uint8 tensor of n_sets records, int32 statuses) from device-resident shares: ids (32 B each),
+        pts, schemes (uint8 or None) and offs (int64, n_sets + 1 entries).  The points can go straight into verify_batch."""
+        self._sync()
+        out = self.empty(max(n_sets, 1) * (144 if group == 1 else 288))
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        _check(self.lib.blsgpu_combine_shares(group, self._p(ids), self._p(pts), self._p(schemes), self._p(offs), n_sets, fmt, self._p(out),
+                                              self._p(st)))
+        return out[:n_sets * (144 if group == 1 else 288)], st[:n_sets]
+
     def multi_verify(self, sg, scheme, pks, n, sig, msg):
         self._sync()
         st = ctypes.c_int32(-99)
@@ -699,12 +745,57 @@ class PublicKey:
     def __init__(self, impl, raw):
         self.impl, self.raw = impl, bytes(raw)
 
+    @staticmethod
+    def from_shares(shares):
+        """reference src/public_key.rs:128-134: Lagrange interpolation at zero of the key shares, on the GPU."""
+        impl = shares[0].impl if shares else Bls12381G2Impl
+        out, st = combine_shares(2 if impl.sig_group == 1 else 1, [[(s.identifier, s.raw, None) for s in shares]])
+        e = error_from_status(st[0])
+        if e:
+            raise e
+        return PublicKey(impl, out[0])
+
+
+class PublicKeyShare:
+    """PublicKeyShare<C>: reference src/public_key_share.rs; `identifier` is the share's field element as an int."""
+
+    def __init__(self, impl, identifier, raw):
+        self.impl, self.identifier, self.raw = impl, int(identifier), bytes(raw)
+
+    def verify(self, sig, msg):
+        """reference src/public_key_share.rs:55-71: the share signature under this key share, with the share's scheme."""
+        st = verify_batch(self.impl.sig_group, sig.scheme, [self.raw], [sig.raw], [bytes(msg)])[0]
+        e = error_from_status(st)
+        if e:
+            raise e
+
+
+class SignatureShare:
+    """SignatureShare<C> {Basic, MessageAugmentation, ProofOfPossession}: reference src/signature_share.rs."""
+
+    def __init__(self, impl, scheme, identifier, raw):
+        self.impl, self.scheme, self.identifier, self.raw = impl, scheme, int(identifier), bytes(raw)
+
+    def verify(self, pks, msg):
+        """reference src/signature_share.rs:100-102."""
+        pks.verify(self, msg)
+
 
 class Signature:
     """Signature<C> {Basic, MessageAugmentation, ProofOfPossession}: reference src/signature.rs:25-44."""
 
     def __init__(self, impl, scheme, raw):
         self.impl, self.scheme, self.raw = impl, scheme, bytes(raw)
+
+    @staticmethod
+    def from_shares(shares):
+        """reference src/signature.rs:151-165: the scheme tags must agree, then Lagrange interpolation at zero, on the GPU."""
+        impl = shares[0].impl if shares else Bls12381G2Impl
+        out, st = combine_shares(impl.sig_group, [[(s.identifier, s.raw, s.scheme) for s in shares]])
+        e = error_from_status(st[0])
+        if e:
+            raise e
+        return Signature(impl, shares[0].scheme, out[0])
 
     def verify(self, pk, msg):
         """reference src/signature.rs:130-138; raises BlsError on failure, returns None on Ok(())."""

@@ -16,6 +16,7 @@
 
 #include "../../include/blsgpu.h"
 #include "kernels.cuh"
+#include "shares.cuh"
 #include "host_sha256.h"
 
 namespace {
@@ -31,12 +32,13 @@ enum {
   // round 4: one id per kernel on the paths bench.py reports (lumped ids made "the dominant kernel" meaningless)
   KID_MILLER2_V1, KID_FINALEXP_V1, KID_LINESP, KID_LINESP4, KID_LINE_QUAD, KID_F12_FOLD4, KID_F12_TREE, KID_HORNER, KID_MILLERFP, KID_PAIRING_POST, KID_PAIRING_PRE,
   KID_TAIL,        // everything launched on a context's tail stream: runs BESIDE the main stream's kernels, so its time is not additive
+  KID_SHARE_LAGRANGE, KID_SHARE_LADDER, KID_SHARE_FOLD, KID_SHARE_OUT,     // threshold recovery (blsgpu_combine_shares)
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
                                     "k_finalexp_one", "k_hash_to_point", "k_accumulate", "k_point_fold", "k_compress", "k_sign", "k_f12_io", "k_msm_sort", "k_msm_bucket", "k_msm_chunk", "k_decompress", "k_pairing_coop", "k_key_sort", "k_sha256_coeff", "k_duplicate_rule", "k_first_identity", "k_msm_prep", "k_normalize", "k_msm_merge", "k_wide", "k_lines2s", "k_cyc_run4",
                                     "k_miller2s", "k_finalexps", "k_linesp", "k_linesp4", "k_line_quad", "k_f12_fold4", "k_f12_tree_seg", "k_f12_horner_wide", "k_millerfp", "k_pairing_post", "k_pairing_pre",
-                                    "tail_stream_overlapped"};
+                                    "tail_stream_overlapped", "k_share_lagrange", "k_share_ladder", "k_share_fold", "k_share_out"};
 
 struct Ctx {
   int dev = -1;
@@ -157,6 +159,7 @@ struct Knobs {
   long stream_lines = 1;      // a check whose lines cannot be had early runs them BESIDE its Miller loop (k_pairing_stream; 0: two launches)
   long post_split = 3;        // the late part of a cut check runs its Miller loop on this many workgroups (k_pairing_post2: 3, 2; 0 or 1: one)
   long host_trace = 0, strict_env = 0, ab_knobs = 0;
+  long shares_msm_min = 1024; // blsgpu_combine_shares: a set of at least this many shares is summed by the bucket MSM, not per-share ladders
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
@@ -174,6 +177,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_WS_KEEP_MB", &Knobs::ws_keep_mb, 0, 1L << 20, false},        {"BLSGPU_MSM2_TABLES", &Knobs::msm2_tables, 0, 1, false},
     {"BLSGPU_STREAM_LINES", &Knobs::stream_lines, 0, 1, false},        {"BLSGPU_POST_SPLIT", &Knobs::post_split, 0, 3, false},
     {"BLSGPU_STRICT_ENV", &Knobs::strict_env, 0, 1, false},             {"BLSGPU_AB_KNOBS", &Knobs::ab_knobs, 0, 1, false},
+    {"BLSGPU_SHARES_MSM_MIN", &Knobs::shares_msm_min, 2, 1L << 32, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -3570,4 +3574,107 @@ int blsgpu_fp12_product_is_one(const void* f12s, size_t k, int32_t* is_one) try 
 }
 API_CATCH
 
+
+// ---- threshold recovery (shares.cuh): n_sets Lagrange interpolations at zero in one call
+int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const uint8_t* schemes, const uint64_t* set_offsets,
+                          size_t n_sets, int fmt, void* out, int32_t* status) try {
+  if (!initialised()) return NOT_INIT();
+  if (group != 1 && group != 2) return fail(BLSGPU_E_ARG, "group must be 1 (G1) or 2 (G2)");
+  if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE) return fail(BLSGPU_E_ARG, "fmt must be RAW_PROJ or RAW_AFFINE");
+  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
+  if (n_sets && (!out || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  CTX_ACQUIRE(c);
+  // the offsets decide every size of the call: read (and check) them on the host
+  std::vector<uint64_t> offs(n_sets + 1);
+  if (is_device_ptr(set_offsets)) HIPCK(hipMemcpy(offs.data(), set_offsets, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
+  else memcpy(offs.data(), set_offsets, 8 * (n_sets + 1));
+  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "set_offsets[0] must be 0");
+  uint64_t tmax = 0;
+  for (size_t s = 0; s < n_sets; s++) {
+    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "set_offsets must not decrease");
+    tmax = std::max(tmax, offs[s + 1] - offs[s]);
+  }
+  const size_t n = (size_t)offs[n_sets];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
+  if (n && (!ids || !pts)) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  const size_t psz = group == 1 ? g1_size(fmt) : g2_size(fmt), osz = group == 1 ? 144 : 288;
+  // plan: sets of at least BLSGPU_SHARES_MSM_MIN shares run as one bucket MSM each (k_msm2_*), all others as per-share ladders and a
+  // segmented tree sum; the coefficients of a large set are split over S workgroups per tile range (k_share_lagrange)
+  const uint64_t msm_min = (uint64_t)knobs().shares_msm_min;
+  std::vector<uint32_t> hflags(n_sets, 0);
+  uint64_t tmax_ladder = 0, tmax_msm = 0;
+  for (size_t s = 0; s < n_sets; s++) {
+    const uint64_t t = offs[s + 1] - offs[s];
+    if (t >= msm_min) {
+      hflags[s] = SHARE_F_MSM;
+      tmax_msm = std::max(tmax_msm, t);
+    } else {
+      tmax_ladder = std::max(tmax_ladder, t);
+    }
+  }
+  size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax / 256)));
+  S = std::max<size_t>(1, std::min(S, ((size_t)1 << 22) / std::max<size_t>(n, 1)));
+  const size_t msm_bytes = tmax_msm ? msm_ws_bytes(tmax_msm) + pad256(osz * accumulate_lanes(tmax_msm)) + pad256(osz * POINT_TREE_START) : 0;
+  int rc = arena_reserve(c, pad256(psz * n) + pad256(32 * n) + pad256(n) + pad256(8 * (n_sets + 1)) + pad256(32 * n) + pad256(4 * n) +
+                                pad256(64 * S * n) + pad256(osz * n) + pad256(4 * n_sets) + pad256(osz * n_sets) + pad256(4 * n_sets) + msm_bytes + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_pts, *d_ids, *d_sch = nullptr, *d_offs;
+  if ((rc = stage_in(c, pts, psz * n, &d_pts))) return rc;
+  if ((rc = stage_in(c, ids, 32 * n, &d_ids))) return rc;
+  if (schemes && n && (rc = stage_in(c, schemes, n, &d_sch))) return rc;
+  {
+    void* d = arena_take(c, 8 * (n_sets + 1));
+    if (!d) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    HIPCK(hipMemcpyAsync(d, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
+    d_offs = d;
+  }
+  uint8_t* d_lam = (uint8_t*)arena_take(c, 32 * n);
+  uint32_t* d_sid = (uint32_t*)arena_take(c, 4 * n);
+  uint32_t* d_nd = (uint32_t*)arena_take(c, 64 * S * n);
+  uint8_t* d_part = (uint8_t*)arena_take(c, osz * n);
+  uint32_t* d_flags = (uint32_t*)arena_take(c, 4 * n_sets);
+  uint8_t* d_out = is_device_ptr(out) ? (uint8_t*)out : (uint8_t*)arena_take(c, osz * n_sets);
+  int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
+  if (!d_lam || !d_sid || !d_nd || !d_part || !d_flags || !d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (tmax_msm) HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
+  else HIPCK(hipMemsetAsync(d_flags, 0, 4 * n_sets, c->stream));
+  const uint64_t* o = (const uint64_t*)d_offs;
+  if (n) {
+    KL(KID_SHARE_LAGRANGE, k_share_lagrange, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_ids, d_flags, d_nd, d_sid);
+    KL(KID_SHARE_LAGRANGE, k_share_lagrange_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (int)S, o, (const uint8_t*)d_ids, (const uint8_t*)d_sch,
+       (const uint32_t*)d_nd, (const uint32_t*)d_sid, d_flags, d_lam);
+    if (tmax_ladder >= 2) {
+      if (group == 1) KL(KID_SHARE_LADDER, k_share_ladder<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_lam,
+                         (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      else KL(KID_SHARE_LADDER, k_share_ladder<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_lam,
+              (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      for (uint64_t step = 1; step < tmax_ladder; step <<= 1) {
+        if (group == 1) KL(KID_SHARE_FOLD, k_share_fold<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+        else KL(KID_SHARE_FOLD, k_share_fold<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+      }
+    }
+    // the large sets: one MSM each over the set's points and coefficients, its (Z = 1) result into the set's first record.  A failed
+    // set computes a value nobody reads (k_share_out gives it the identity).  The MSM's workspace is reused from set to set.
+    const size_t mark = c->arena_off;
+    for (size_t s = 0; s < n_sets; s++) {
+      if (!(hflags[s] & SHARE_F_MSM)) continue;
+      const size_t lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]), T = accumulate_lanes(t);
+      c->arena_off = mark;
+      uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
+      if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
+      const uint8_t* sp = (const uint8_t*)d_pts + psz * lo;
+      if (group == 1) rc = run_point_sum<1>(c, sp, fmt, d_lam + 32 * lo, nullptr, t, d_msm, T);
+      else rc = run_point_sum<2>(c, sp, fmt, d_lam + 32 * lo, nullptr, t, d_msm, T);
+      if (rc) return rc;
+      HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
+    }
+  }
+  if (group == 1) KL(KID_SHARE_OUT, k_share_out<1>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
+  else KL(KID_SHARE_OUT, k_share_out<2>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
+  if (d_out != out && (rc = copy_out(c, out, d_out, osz * n_sets))) return rc;
+  return status_out_and_sync(c, status, d_st, n_sets);
+}
+API_CATCH
 }  // extern "C"

@@ -64,6 +64,9 @@ extern "C" {
 #define BLSGPU_COMMITMENT_IDENTITY 9 /* InvalidInputs("commitment is the identity point")        sig_proof.rs:110-114 */
 #define BLSGPU_PROOF_IDENTITY 10     /* InvalidInputs("proof is the identity point")             sig_proof.rs:115-119 */
 #define BLSGPU_ZERO_CHALLENGE 11     /* InvalidInputs("y is the zero")                           sig_proof.rs:125-127 */
+/* blsgpu_combine_shares only */
+#define BLSGPU_INVALID_SCHEME 12     /* BlsError::InvalidSignatureScheme       error.rs:19-20; signature.rs:152-154 */
+#define BLSGPU_VSSS_ERROR 13         /* BlsError::VsssError                    error.rs:25-26,60-64 */
 
 /* runtime failures (< 0): return codes.  One of them can also appear IN a status entry: BLSGPU_E_HIP when the device-side work of
  * that item failed (single-verdict checks run on workgroups that wait for each other with a bound; a wait that ran out is not a
@@ -293,6 +296,31 @@ int blsgpu_debug_finalexp_batch(const void* f12s, size_t n, int form, size_t chu
  * the public-key bytes, src/traits/sig_aug.rs:12-17).  sks: 32 B little-endian each; outputs RAW_PROJ. */
 int blsgpu_sign_batch(int sig_group, int scheme, const uint8_t* sks, const uint8_t* msgs, const uint64_t* msg_offsets,
                       size_t n, void* out_pks, void* out_sigs);
+
+/* Threshold recovery: Signature::from_shares (src/signature.rs:151-165) and PublicKey::from_shares (src/public_key.rs:128-134) ->
+ * core_combine_signature_shares / core_combine_public_key_shares (src/traits/sig_core.rs:92-105), for n_sets independent
+ * recoveries in one call.  Each is Lagrange interpolation at zero, as the dependency (vsss-rs) does it:
+ *     lambda_i = prod_{j != i} x_j / (x_j - x_i),   result = sum_i lambda_i P_i.
+ * group: the group the points live in, 1 = G1, 2 = G2.  For Bls12381G2Impl signatures are group 2 and public keys group 1; for
+ *     Bls12381G1Impl signatures are group 1 and public keys group 2.
+ * set_offsets: n_sets + 1 entries, set s is shares set_offsets[s] .. set_offsets[s + 1]; it starts at 0 and never decreases
+ *     (anything else: BLSGPU_E_ARG).  The total share count is set_offsets[n_sets].
+ * ids: one 32-byte little-endian identifier per share (IdentifierPrimeField<Scalar>): full 255-bit values are handled.
+ * pts: one point per share, BLSGPU_FMT_RAW_PROJ or BLSGPU_FMT_RAW_AFFINE (fmt); compressed input goes through blsgpu_deserialize
+ *     first (device pointers chain).
+ * schemes: NULL (PublicKey::from_shares: no scheme check) or one BLSGPU_SCHEME_* byte per share.
+ * out: n_sets RAW_PROJ points with Z = 1, or all-zero bytes for the identity; a set whose status is not OK gets the identity.
+ * status: one entry per set, the first of these that applies:
+ *     BLSGPU_BAD_ENCODING   an identifier >= r (the reference type cannot hold it: deserialisation fails before from_shares)
+ *     BLSGPU_INVALID_SCHEME the scheme tags differ within the set
+ *     BLSGPU_VSSS_ERROR     fewer than two shares (an empty set included), a zero identifier, or two equal identifiers
+ *     BLSGPU_OK
+ * The reference maps every error of the dependency to the one VsssError, so which of its checks fires first is not observable.
+ * Two assumptions of this library: at least two shares are required, and identity share values are accepted (they add
+ * nothing).  Fewer shares than the threshold is not an error: it yields a different point, as in the reference.
+ * Every pointer may be host or device memory; a device `out` feeds blsgpu_verify_batch without a host round trip. */
+int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const uint8_t* schemes, const uint64_t* set_offsets,
+                          size_t n_sets, int fmt, void* out, int32_t* status);
 
 #ifdef __cplusplus
 }
