@@ -17,6 +17,7 @@
 #include "../../include/blsgpu.h"
 #include "kernels.cuh"
 #include "shares.cuh"
+#include "secure.cuh"
 #include "host_sha256.h"
 
 namespace {
@@ -33,12 +34,14 @@ enum {
   KID_MILLER2_V1, KID_FINALEXP_V1, KID_LINESP, KID_LINESP4, KID_LINE_QUAD, KID_F12_FOLD4, KID_F12_TREE, KID_HORNER, KID_MILLERFP, KID_PAIRING_POST, KID_PAIRING_PRE,
   KID_TAIL,        // everything launched on a context's tail stream: runs BESIDE the main stream's kernels, so its time is not additive
   KID_SHARE_LAGRANGE, KID_SHARE_LADDER, KID_SHARE_FOLD, KID_SHARE_OUT,     // threshold recovery (blsgpu_combine_shares)
+  KID_SECURE_RANK, KID_SECURE_GATHER, KID_SECURE_DIGEST, KID_SECURE_COEFF, KID_SECURE_OUT, KID_SECURE_FIN,   // blsgpu_verify_secure_batch
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
                                     "k_finalexp_one", "k_hash_to_point", "k_accumulate", "k_point_fold", "k_compress", "k_sign", "k_f12_io", "k_msm_sort", "k_msm_bucket", "k_msm_chunk", "k_decompress", "k_pairing_coop", "k_key_sort", "k_sha256_coeff", "k_duplicate_rule", "k_first_identity", "k_msm_prep", "k_normalize", "k_msm_merge", "k_wide", "k_lines2s", "k_cyc_run4",
                                     "k_miller2s", "k_finalexps", "k_linesp", "k_linesp4", "k_line_quad", "k_f12_fold4", "k_f12_tree_seg", "k_f12_horner_wide", "k_millerfp", "k_pairing_post", "k_pairing_pre",
-                                    "tail_stream_overlapped", "k_share_lagrange", "k_share_ladder", "k_share_fold", "k_share_out"};
+                                    "tail_stream_overlapped", "k_share_lagrange", "k_share_ladder", "k_share_fold", "k_share_out",
+                                    "k_secure_rank", "k_secure_gather", "k_secure_digest", "k_secure_coeff", "k_secure_out", "k_secure_fin"};
 
 struct Ctx {
   int dev = -1;
@@ -160,6 +163,7 @@ struct Knobs {
   long post_split = 3;        // the late part of a cut check runs its Miller loop on this many workgroups (k_pairing_post2: 3, 2; 0 or 1: one)
   long host_trace = 0, strict_env = 0, ab_knobs = 0;
   long shares_msm_min = 1024; // blsgpu_combine_shares: a set of at least this many shares is summed by the bucket MSM, not per-share ladders
+  long secure_batch_max = 1024; // blsgpu_verify_secure_batch: a set of at least this many keys runs through blsgpu_verify_secure's machinery
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
@@ -178,6 +182,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_STREAM_LINES", &Knobs::stream_lines, 0, 1, false},        {"BLSGPU_POST_SPLIT", &Knobs::post_split, 0, 3, false},
     {"BLSGPU_STRICT_ENV", &Knobs::strict_env, 0, 1, false},             {"BLSGPU_AB_KNOBS", &Knobs::ab_knobs, 0, 1, false},
     {"BLSGPU_SHARES_MSM_MIN", &Knobs::shares_msm_min, 2, 1L << 32, false},
+    {"BLSGPU_SECURE_BATCH_MAX", &Knobs::secure_batch_max, 1, 1L << 32, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -3674,6 +3679,162 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
   if (group == 1) KL(KID_SHARE_OUT, k_share_out<1>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
   else KL(KID_SHARE_OUT, k_share_out<2>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
   if (d_out != out && (rc = copy_out(c, out, d_out, osz * n_sets))) return rc;
+  return status_out_and_sync(c, status, d_st, n_sets);
+}
+API_CATCH
+
+// ---- batched verify_secure (secure.cuh): n_sets independent Signature::verify_secure checks in one call
+int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
+                               const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt, int32_t* status) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc) return rc;
+  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
+  if (ser_format == 1 && sig_group != 2)
+    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
+  if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
+  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  // the offsets decide every size of the call: read (and check) them on the host
+  auto read_offsets = [&](const uint64_t* src, std::vector<uint64_t>& dst) -> int {
+    dst.resize(n_sets + 1);
+    if (is_device_ptr(src)) HIPCK(hipMemcpy(dst.data(), src, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
+    else memcpy(dst.data(), src, 8 * (n_sets + 1));
+    return 0;
+  };
+  std::vector<uint64_t> offs, moffs;
+  if ((rc = read_offsets(key_offsets, offs))) return rc;
+  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "key_offsets[0] must be 0");
+  for (size_t s = 0; s < n_sets; s++)
+    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "key_offsets must not decrease");
+  const size_t n = (size_t)offs[n_sets];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
+  if (n && !pks) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  if ((rc = read_offsets(msg_offsets, moffs))) return rc;
+  for (size_t s = 0; s < n_sets; s++)
+    if (moffs[s + 1] < moffs[s]) return fail(BLSGPU_E_ARG, "msg_offsets must not decrease");
+  if (moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  // plan: a set of at least BLSGPU_SECURE_BATCH_MAX keys runs one at a time through the machinery of blsgpu_verify_secure (device
+  // sort, host SHA-256 of the stream, k_sha256_coeff, bucket MSM); all others through the segmented kernels of secure.cuh and the
+  // per-key ladders of the threshold recovery.  One large set alone IS blsgpu_verify_secure (on one device: no sharding).
+  const uint64_t max_small = (uint64_t)knobs().secure_batch_max;
+  if (n_sets == 1 && n >= max_small) {
+    NestedScope ns;
+    return blsgpu_verify_secure(sig_group, scheme, pks, n, sigs, msgs + moffs[0], (size_t)(moffs[1] - moffs[0]), ser_format, fmt, status);
+  }
+  CTX_ACQUIRE(c);
+  const int pk_group = sig_group == 1 ? 2 : 1;
+  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = sig_group == 1 ? 96 : 48, osz = sig_group == 1 ? 288 : 144;
+  std::vector<uint32_t> hflags(n_sets, 0);
+  uint64_t tmax_small = 0, tmax_large = 0;
+  for (size_t s = 0; s < n_sets; s++) {
+    const uint64_t t = offs[s + 1] - offs[s];
+    if (t >= max_small) {
+      hflags[s] = SECURE_F_LARGE;
+      tmax_large = std::max(tmax_large, t);
+    } else {
+      tmax_small = std::max(tmax_small, t);
+    }
+  }
+  size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax_small / 256)));
+  const size_t mtotal = (size_t)moffs[n_sets];
+  const size_t large_bytes = tmax_large ? keysort_ws_bytes(tmax_large, width) + msm_ws_bytes(tmax_large) + pad256(osz * accumulate_lanes(tmax_large)) +
+                                              pad256(osz * POINT_TREE_START) + 4096
+                                        : 0;
+  rc = arena_reserve(c, pad256(psz * n) + 2 * pad256(width * n) + pad256(32 * n) + 2 * pad256(4 * n) + pad256(osz * n) + pad256(ssz * n_sets) +
+                            pad256(mtotal) + 2 * pad256(8 * (n_sets + 1)) + pad256(32 * n_sets) + 2 * pad256(4 * n_sets) + 2 * pad256(288 * n_sets) +
+                            pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) + pad256((size_t)WS_F_WORDS * 4 * n_sets) + large_bytes + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_pks = nullptr, *d_sigs, *d_msgs, *d_moffs;
+  if (n && (rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
+  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
+  uint64_t* d_offs = (uint64_t*)arena_take(c, 8 * (n_sets + 1));
+  uint8_t* d_bytes = (uint8_t*)arena_take(c, width * n);
+  uint8_t* d_sorted = (uint8_t*)arena_take(c, width * n);
+  uint8_t* d_scal = (uint8_t*)arena_take(c, 32 * n);
+  uint32_t* d_rank = (uint32_t*)arena_take(c, 4 * n);
+  uint32_t* d_sid = (uint32_t*)arena_take(c, 4 * n);
+  uint8_t* d_part = (uint8_t*)arena_take(c, osz * n);
+  uint8_t* d_H = (uint8_t*)arena_take(c, 32 * n_sets);
+  uint32_t* d_flags = (uint32_t*)arena_take(c, 4 * n_sets);
+  int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
+  uint8_t* d_sigp = (uint8_t*)arena_take(c, 288 * n_sets);
+  uint8_t* d_apk = (uint8_t*)arena_take(c, 288 * n_sets);
+  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n_sets);
+  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_sets);
+  if (!d_offs || !d_bytes || !d_sorted || !d_scal || !d_rank || !d_sid || !d_part || !d_H || !d_flags || !d_st || !d_sigp || !d_apk || !d_pairs || !d_f)
+    return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemcpyAsync(d_offs, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
+  const uint64_t* o = d_offs;
+  const uint8_t* kp = (const uint8_t*)d_pks;
+  if (n) {
+    // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:42,47,272-275)
+    if (pk_group == 2) KL(KID_COMPRESS, k_compress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes);
+    else KL(KID_COMPRESS, k_compress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes);
+    if (tmax_small) {
+      HIPCK(hipMemsetAsync(d_rank, 0, 4 * n, c->stream));
+      if (width == 96)
+        KL(KID_SECURE_RANK, k_secure_rank<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_flags, d_rank, d_sid);
+      else
+        KL(KID_SECURE_RANK, k_secure_rank<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_flags, d_rank, d_sid);
+      KL(KID_SECURE_GATHER, k_secure_gather, dim3(blocks_for(n * (width / 4))), dim3(BLS_BLOCK), n, width, o, (const uint8_t*)d_bytes,
+         (const uint32_t*)d_rank, (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_sorted);
+      KL(KID_SECURE_DIGEST, k_secure_digest, dim3((unsigned)n_sets), dim3(BLS_BLOCK), n_sets, width, o, (const uint8_t*)d_sorted,
+         (const uint32_t*)d_flags, d_H);
+      KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_rank, (const uint32_t*)d_sid,
+         (const uint8_t*)d_H, d_flags, d_scal);
+      // aggregated_pk = sum t_i pk_i per set (reference :201-204): one joint NAF ladder per key, then a segmented tree sum
+      if (pk_group == 1) KL(KID_SHARE_LADDER, k_share_ladder<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, (const uint8_t*)d_scal,
+                            (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      else KL(KID_SHARE_LADDER, k_share_ladder<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, (const uint8_t*)d_scal,
+              (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      for (uint64_t step = 1; step < tmax_small; step <<= 1) {
+        if (pk_group == 1) KL(KID_SHARE_FOLD, k_share_fold<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+        else KL(KID_SHARE_FOLD, k_share_fold<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+      }
+    }
+    // the large sets, one at a time as blsgpu_verify_secure runs them: device sort, host SHA-256 of the sorted stream, the
+    // coefficients, one MSM; its result goes to the set's first record (after the fold, which left the identity there).  The
+    // workspace is reused from set to set.
+    const size_t mark = c->arena_off;
+    for (size_t s = 0; s < n_sets; s++) {
+      if (!(hflags[s] & SECURE_F_LARGE)) continue;
+      const size_t lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]), T = accumulate_lanes(t);
+      c->arena_off = mark;
+      keysort_ws w;
+      if ((rc = keysort_ws_take(c, t, width, w))) return rc;
+      uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
+      if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
+      if ((rc = run_key_sort_to_host(c, d_bytes + width * lo, t, width, w, nullptr, nullptr))) return rc;
+      uint8_t H[32];
+      keys_digest_host(c->hpin, width * t, H);
+      HIPCK(hipMemcpy(d_H + 32 * s, H, 32, hipMemcpyHostToDevice));       // the stream is idle here (the sort synchronised)
+      if ((rc = run_coefficients(c, d_H + 32 * s, w.perm_a, t, 0, t, 0, d_scal + 32 * lo, (int32_t*)(d_flags + s)))) return rc;
+      if (pk_group == 1) rc = run_point_sum<1>(c, kp + psz * lo, fmt, d_scal + 32 * lo, nullptr, t, d_msm, T);
+      else rc = run_point_sum<2>(c, kp + psz * lo, fmt, d_scal + 32 * lo, nullptr, t, d_msm, T);
+      if (rc) return rc;
+      HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
+    }
+    c->arena_off = mark;
+  }
+  // every set's signature as RAW_PROJ, its key, its status so far; then ONE verification tail over all sets (core_verify with the
+  // scheme's DST and no key prefix, reference :236-246) that skips the sets already decided
+  if (sig_group == 1)
+    KL(KID_SECURE_OUT, k_secure_out<1>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, d_flags, (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt,
+       d_sigp, d_apk, d_st);
+  else
+    KL(KID_SECURE_OUT, k_secure_out<2>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, d_flags, (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt,
+       d_sigp, d_apk, d_st);
+  if ((rc = run_verify_items(c, sig_group, 0, d_apk, d_sigp, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msgs, (const uint64_t*)d_moffs, 0,
+                             scheme_dst(sig_group, scheme), n_sets, d_pairs, d_f, d_st, 1)))
+    return rc;
+  KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, d_st);
+  HIPCK(hipGetLastError());
   return status_out_and_sync(c, status, d_st, n_sets);
 }
 API_CATCH

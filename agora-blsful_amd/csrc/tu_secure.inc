@@ -1,0 +1,233 @@
+// Kernels of the batched verify_secure (blsgpu_verify_secure_batch, secure.cuh), included by tu_secure1.hip (BLS_TU_SECURE = 1:
+// the sort and the hashes) and tu_secure2.hip (BLS_TU_SECURE = 2: the point kernels).  Only the sets below
+// BLSGPU_SECURE_BATCH_MAX keys run here (SECURE_F_LARGE clear); the key sum between k_secure_coeff and k_secure_out is
+// k_share_ladder / k_share_fold of the threshold recovery (tu_shares.inc).
+//   k_secure_rank   : the key's position in its set under the stable byte-lexicographic order (reference src/secure_aggregation.rs:41-42)
+//   k_secure_gather : every set's keys as one contiguous sorted stream
+//   k_secure_digest : H_s = SHA-256 of set s's stream (:45-49), one wave per set
+//   k_secure_coeff  : t = SHA-256(BE32(position) || H_s) mod r into the key's input slot (:61-100); a zero flags the set
+//   k_secure_out    : the signature as RAW_PROJ, the set's summed key, the status the verification tail starts from
+//   k_secure_fin    : after the tail, the verdict of the empty sets (:189-195)
+#include "kernels.cuh"
+#include "secure.cuh"
+
+#if BLS_TU_SECURE == 1
+// the set of key i: the last s with offs[s] <= i (empty sets share their offset with the next one and are skipped)
+__device__ __forceinline__ uint32_t secure_set_of(const uint64_t* offs, size_t n_sets, size_t i) {
+  size_t lo = 0, hi = n_sets - 1;
+  while (lo < hi) {
+    const size_t mid = (lo + hi + 1) >> 1;
+    if (offs[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return (uint32_t)lo;
+}
+// key o sorts before key m: its big-endian words are smaller, or they are equal and o comes first in the input (tie)
+template <int WPK>
+__device__ __forceinline__ bool secure_key_less(const uint32_t* o, const uint32_t (&m)[WPK], bool tie) {
+#pragma unroll
+  for (int k = 0; k < WPK; k++)
+    if (o[k] != m[k]) return o[k] < m[k];
+  return tie;
+}
+// rank_i = #{ j in i's set : bytes_j < bytes_i, or bytes_j == bytes_i and j < i }: Rust's stable sort_by on to_bytes(), duplicates
+// included.  The n-body pattern of k_share_lagrange: the lanes of a workgroup are consecutive keys, the keys their sets hold are
+// one contiguous range, streamed through LDS in tiles of BLS_BLOCK keys (as big-endian words, converted once by the lane that
+// loads them); every lane compares its own key with those of its set.  A large range is split over gridDim.y workgroups (tile
+// k goes to y = k mod gridDim.y), whose counts meet in rank (zeroed by the caller) by atomicAdd.
+template <int WPK>
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_rank(size_t n, const uint64_t* offs, size_t n_sets, const uint8_t* kb, const uint32_t* flags,
+                                                         uint32_t* rank, uint32_t* sid) {
+  __shared__ uint32_t tile[BLS_BLOCK * WPK];
+  __shared__ unsigned long long range_lo, range_hi;
+  const size_t i = (size_t)blockIdx.x * BLS_BLOCK + threadIdx.x, S = gridDim.y;
+  const uint32_t* kw = (const uint32_t*)kb;
+  bool live = i < n;
+  size_t lo = 0, hi = 0;
+  uint32_t me[WPK];
+  if (threadIdx.x == 0) {
+    range_lo = ~0ull;
+    range_hi = 0;
+  }
+  __syncthreads();
+  if (live) {
+    const uint32_t s = secure_set_of(offs, n_sets, i);
+    if (blockIdx.y == 0) sid[i] = s;
+    live = !(flags[s] & SECURE_F_LARGE);
+    lo = offs[s];
+    hi = offs[s + 1];
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < WPK; k++) me[k] = __builtin_bswap32(kw[i * WPK + k]);
+    atomicMin(&range_lo, (unsigned long long)lo);
+    atomicMax(&range_hi, (unsigned long long)hi);
+  }
+  __syncthreads();
+  const size_t rlo = range_lo, rhi = range_hi;
+  if (rlo >= rhi) return;                     // no key of a small set here (uniform over the workgroup)
+  uint32_t cnt = 0;
+  for (size_t t0 = rlo + (size_t)blockIdx.y * BLS_BLOCK; t0 < rhi; t0 += S * BLS_BLOCK) {
+    const size_t j = t0 + threadIdx.x;
+    if (j < rhi) {
+#pragma unroll
+      for (int k = 0; k < WPK; k++) tile[threadIdx.x * WPK + k] = __builtin_bswap32(kw[j * WPK + k]);
+    }
+    __syncthreads();
+    if (live) {
+      const size_t a = t0 > lo ? t0 : lo, e = t0 + BLS_BLOCK < hi ? t0 + BLS_BLOCK : hi;
+      for (size_t j2 = a; j2 < e; j2++)
+        if (j2 != i && secure_key_less<WPK>(tile + (j2 - t0) * WPK, me, j2 < i)) cnt++;
+    }
+    __syncthreads();
+  }
+  if (live && cnt) atomicAdd(&rank[i], cnt);
+}
+// the keys of every small set at their sorted positions: sorted[offs[s] + rank_i] = key i, one 32-bit word per lane
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_gather(size_t n, size_t width, const uint64_t* offs, const uint8_t* kb, const uint32_t* rank,
+                                                           const uint32_t* sid, const uint32_t* flags, uint8_t* sorted) {
+  const size_t wpk = width / 4, t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * wpk) return;
+  const size_t i = t / wpk, w = t % wpk;
+  const uint32_t s = sid[i];
+  if (flags[s] & SECURE_F_LARGE) return;
+  ((uint32_t*)sorted)[(offs[s] + rank[i]) * wpk + w] = ((const uint32_t*)kb)[t];
+}
+// the wave-wide SHA-256 pieces of kernels.cuh (sha256_iv, sha256_block_from_lds: defined in the row-wide engine's unit only)
+__device__ __forceinline__ u32x8_t secure_sha256_iv() {
+  u32x8_t h;
+  h[0] = 0x6a09e667; h[1] = 0xbb67ae85; h[2] = 0x3c6ef372; h[3] = 0xa54ff53a;
+  h[4] = 0x510e527f; h[5] = 0x9b05688c; h[6] = 0x1f83d9ab; h[7] = 0x5be0cd19;
+  return h;
+}
+// the block that the lanes wrote byte by byte (stream order) -> sixteen big-endian words on every lane
+__device__ __forceinline__ u32x16_t secure_block_from_lds(uint8_t* blk) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  u32x16_t w;
+  const uint32_t* q = (const uint32_t*)blk;
+#pragma unroll
+  for (int j = 0; j < 16; j++) w[j] = __builtin_bswap32(q[j]);
+  __builtin_amdgcn_wave_barrier();
+  return w;
+}
+// H_s = SHA-256(set s's sorted stream): one wave per set walks the stream block by block (the pieces of kernels.cuh expand_message_xmd_wave: lane
+// L fetches byte L of the block, the block meets in LDS, every lane runs the compression on registers).  Sequential within a
+// set, parallel across sets.  H leaves as 32 big-endian bytes.
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_digest(size_t n_sets, size_t width, const uint64_t* offs, const uint8_t* sorted,
+                                                           const uint32_t* flags, uint8_t* H) {
+  __shared__ uint32_t blkw[16];
+  uint8_t* blk = (uint8_t*)blkw;
+  const size_t s = blockIdx.x;
+  const uint32_t L = threadIdx.x & 63u;
+  if (s >= n_sets) return;
+  const uint64_t lo = offs[s], cnt = offs[s + 1] - lo;
+  if (cnt == 0 || (flags[s] & SECURE_F_LARGE)) return;
+  const uint8_t* m = sorted + lo * width;
+  const uint64_t len = cnt * width, bits = len * 8;
+  const uint64_t nblk = (len + 9 + 63) >> 6;
+  u32x8_t h = secure_sha256_iv();
+  for (uint64_t b = 0; b < nblk; b++) {
+    const uint64_t pos = b * 64 + L;
+    uint32_t byte = 0;
+    if (pos < len) byte = m[pos];
+    else if (pos == len) byte = 0x80;
+    else if (b == nblk - 1 && L >= 56) byte = (uint32_t)(bits >> (8 * (63 - L))) & 255u;
+    blk[L] = (uint8_t)byte;
+    h = sha256_compress_v(h, secure_block_from_lds(blk));
+  }
+  if (L < 8) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) v = (uint32_t)j == L ? h[j] : v;
+    ((uint32_t*)(H + 32 * s))[L] = __builtin_bswap32(v);
+  }
+}
+// k_sha256_coeff's hash, per set: the key's sorted position within its set and that set's H; the scalar goes to the key's INPUT
+// slot, so the key sum needs no permutation
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_coeff(size_t n, const uint32_t* rank, const uint32_t* sid, const uint8_t* H, uint32_t* flags,
+                                                          uint8_t* scal) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = sid[i];
+  if (flags[s] & SECURE_F_LARGE) return;
+  const uint32_t* hw = (const uint32_t*)(H + 32 * (size_t)s);
+  uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  uint32_t w[16];
+  w[0] = rank[i];                                   // BE32(position)
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[1 + k] = __builtin_bswap32(hw[k]);
+  w[9] = 0x80000000u;
+#pragma unroll
+  for (int k = 10; k < 15; k++) w[k] = 0;
+  w[15] = 36 * 8;
+  sha256_compress(h, w);
+  uint32_t v[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) v[k] = h[7 - k];      // big-endian digest -> little-endian 32-bit words
+  u256_mod_r_le(v);
+  uint32_t nz = 0;
+  uint32_t* o = (uint32_t*)(scal + 32 * i);
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    nz |= v[k];
+    o[k] = v[k];
+  }
+  if (!nz) atomicOr(&flags[s], SECURE_F_ZERO);
+}
+// an empty set is Ok iff its signature is the identity (reference :189-195); the tail skipped it
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_fin(size_t n_sets, const uint64_t* offs, const uint32_t* flags, int32_t* status) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_sets || offs[s + 1] != offs[s]) return;
+  status[s] = (flags[s] & SECURE_F_IDSIG) ? BLS_OK : BLS_ERR_INVALID_SIGNATURE;
+}
+template __global__ void k_secure_rank<12>(size_t, const uint64_t*, size_t, const uint8_t*, const uint32_t*, uint32_t*, uint32_t*);
+template __global__ void k_secure_rank<24>(size_t, const uint64_t*, size_t, const uint8_t*, const uint32_t*, uint32_t*, uint32_t*);
+#endif
+
+#if BLS_TU_SECURE == 2
+template <int G>
+struct secure_pt;
+template <>
+struct secure_pt<1> {
+  typedef fp F;
+  enum { BYTES = 144 };
+  __device__ static void load(jac<F>& p, const uint8_t* b, size_t i, int fmt) { load_g1_pt(p, b, i, fmt); }
+  __device__ static void store(uint8_t* b, size_t i, const jac<F>& p) { store_g1_pt(b, i, p); }
+};
+template <>
+struct secure_pt<2> {
+  typedef fp2 F;
+  enum { BYTES = 288 };
+  __device__ static void load(jac<F>& p, const uint8_t* b, size_t i, int fmt) { load_g2_pt(p, b, i, fmt); }
+  __device__ static void store(uint8_t* b, size_t i, const jac<F>& p) { store_g2_pt(b, i, p); }
+};
+// SG: the signature group (the keys live in the other one).  part[offs[s]] holds set s's key sum (k_share_fold, or the large
+// set's MSM result copied there).  Status before the tail: INVALID_SIGNATURE stands in for an empty set (non-OK, so the tail
+// skips it; k_secure_fin decides), INVALID_COEFFICIENT comes before any verification (:97-100), OK lets the tail decide.
+template <int SG>
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_out(size_t n_sets, const uint64_t* offs, uint32_t* flags, const uint8_t* part,
+                                                        const uint8_t* sigs, int fmt, uint8_t* sig_proj, uint8_t* apk, int32_t* status) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_sets) return;
+  typedef secure_pt<SG> SP;
+  typedef secure_pt<3 - SG> KP;
+  jac<typename SP::F> sg;
+  SP::load(sg, sigs, s, fmt);
+  SP::store(sig_proj, s, sg);
+  uint32_t f = flags[s];
+  if (jac_is_inf(sg)) f |= SECURE_F_IDSIG;
+  flags[s] = f;
+  const uint64_t lo = offs[s], cnt = offs[s + 1] - lo;
+  uint32_t* w = (uint32_t*)(apk + s * KP::BYTES);
+  if (cnt) {
+    const uint32_t* src = (const uint32_t*)(part + lo * KP::BYTES);
+    for (int k = 0; k < KP::BYTES / 4; k++) w[k] = src[k];
+  } else {
+    for (int k = 0; k < KP::BYTES / 4; k++) w[k] = 0u;
+  }
+  status[s] = cnt == 0 ? BLS_ERR_INVALID_SIGNATURE : (f & SECURE_F_ZERO) ? BLS_ERR_INVALID_COEFFICIENT : BLS_OK;
+}
+template __global__ void k_secure_out<1>(size_t, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
+template __global__ void k_secure_out<2>(size_t, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
+#endif

@@ -42,6 +42,24 @@ __global__ void k_gather_rows(size_t cnt, const uint32_t* idx, const uint32_t* s
 __global__ void k_gather_ragged(size_t cnt, const uint32_t* idx, const uint64_t* offs_src, const uint64_t* offs_dst, const uint8_t* src, uint8_t* dst);
 __global__ void k_scatter_i32(size_t cnt, const uint32_t* idx, const int32_t* src, int32_t* dst);
 
+// v mod r for a 256-bit value v (little-endian words): k_sha256_coeff here, k_secure_coeff (tu_secure.inc)
+__device__ __forceinline__ void u256_mod_r_le(uint32_t v[8]) {
+  const uint32_t R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
+  for (int round = 0; round < 5; round++) {   // 2^256 < 4.5 r
+    uint32_t d[8];
+    uint64_t bw = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const uint64_t s = (uint64_t)v[i] - R[i] - bw;
+      d[i] = (uint32_t)s;
+      bw = (s >> 63) & 1;
+    }
+    if (!bw) {
+#pragma unroll
+      for (int i = 0; i < 8; i++) v[i] = d[i];
+    }
+  }
+}
 #if defined(BLS_TU_UTIL)
 // ---------------------------------------------------------------------------------------------------------------------
 // wave-level helpers (64 lanes, one wave per workgroup)
@@ -234,23 +252,6 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_run_first_index(size_t n, const u
 // t_p = int_BE(SHA-256(BE32(p) || H)) mod r for sorted position p (reference src/secure_aggregation.rs:61-100; the
 // reduction is SURVEY 8a A9's finding).  sorted_order != 0: out[p] = t_p.  Otherwise the scalar goes to the INPUT slot of
 // the key that sorted to p, restricted to the shard [base, base + count): out[perm[p] - base] = t_p.
-__device__ __forceinline__ void u256_mod_r_le(uint32_t v[8]) {
-  const uint32_t R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-  for (int round = 0; round < 5; round++) {   // 2^256 < 4.5 r
-    uint32_t d[8];
-    uint64_t bw = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const uint64_t s = (uint64_t)v[i] - R[i] - bw;
-      d[i] = (uint32_t)s;
-      bw = (s >> 63) & 1;
-    }
-    if (!bw) {
-#pragma unroll
-      for (int i = 0; i < 8; i++) v[i] = d[i];
-    }
-  }
-}
 __global__ void __launch_bounds__(BLS_BLOCK) k_sha256_coeff(size_t n, const uint8_t* H, const uint32_t* perm, size_t base, size_t count,
                                                          int sorted_order, uint8_t* out_scalars, int32_t* zero_flag) {
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

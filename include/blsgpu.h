@@ -322,6 +322,24 @@ int blsgpu_sign_batch(int sig_group, int scheme, const uint8_t* sks, const uint8
 int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const uint8_t* schemes, const uint64_t* set_offsets,
                           size_t n_sets, int fmt, void* out, int32_t* status);
 
+/* Batched verify_secure: Signature::verify_secure / verify_secure_with_mode (src/signature.rs:177-197,256-276 ->
+ * src/secure_aggregation.rs:182-205,236-246) for n_sets independent (keys, signature, message) sets in one call.
+ * key_offsets: n_sets + 1 entries; set s owns keys key_offsets[s] .. key_offsets[s + 1] of pks (it starts at 0 and never
+ *     decreases; anything else is BLSGPU_E_ARG).  The total key count must be below 2^32.
+ * sigs: one signature per set.  msgs / msg_offsets: one message per set (msg_offsets: n_sets + 1 entries).
+ * scheme, ser_format and fmt apply to every set and take the same values as in blsgpu_verify_secure (RAW_PROJ or RAW_AFFINE
+ *     points; Legacy only for sig_group 2).  MessageAugmentation only switches the DST: no key prefix (:236-246).
+ * status[s] equals what blsgpu_verify_secure returns for set s alone: an empty set is BLSGPU_OK iff its signature is the
+ *     identity, else BLSGPU_INVALID_SIGNATURE (:189-195); a zero coefficient is BLSGPU_INVALID_COEFFICIENT (:97-100); otherwise
+ *     the identity checks and the pairing check of core_verify (src/traits/sig_core.rs:126-140), in that order.
+ * Sets below BLSGPU_SECURE_BATCH_MAX keys are sorted, hashed and summed together on the device; larger ones run one at a time
+ *     through blsgpu_verify_secure's steps; every set shares one verification tail.  The knob changes the plan, never a status.
+ * Every pointer may be host or device memory; a device `status` stays on the device.  The call runs on one device even when
+ *     several are bound (whole sets are not sharded over devices). */
+int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets,
+                               const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt,
+                               int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
