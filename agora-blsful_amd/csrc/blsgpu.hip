@@ -11,6 +11,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -92,25 +93,14 @@ struct Lease {
   Lease() = default;
   Lease(Lease&&) = default;
   // An entry point that fails half-way returns without having synchronised: drain what it enqueued before the caller's
-  // buffers (and this context) are reused.  After a normal return both streams are idle and the queries cost nothing.
+  // buffers (and this context) are reused.  After a normal return every stream is idle and the queries cost nothing.
   ~Lease() {
     if (!c) return;
-    if (hipStreamQuery(c->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(c->stream);
-    }
-    if (c->side && hipStreamQuery(c->side) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(c->side);
-    }
-    if (c->side2 && hipStreamQuery(c->side2) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(c->side2);
-    }
-    if (c->tail && hipStreamQuery(c->tail) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(c->tail);
-    }
+    for (hipStream_t s : {c->stream, c->side, c->side2, c->tail})
+      if (s && hipStreamQuery(s) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(s);
+      }
     trim_workspaces(c);
   }
 };
@@ -335,6 +325,19 @@ int copy_out(Ctx* c, void* dst, const void* dsrc, size_t bytes) {
   HIPCK(hipMemcpyAsync(dst, dsrc, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   return 0;
 }
+// device view of an output buffer, the mirror of stage_in: a device pointer passes through, a host buffer gets arena bytes
+// (nullptr: the arena is too small) that stage_back copies to it after the kernels that write them
+template <class T>
+T* stage_out(Ctx* c, void* out, size_t bytes) {
+  return is_device_ptr(out) ? (T*)out : (T*)arena_take(c, bytes);
+}
+int stage_back(Ctx* c, void* out, const void* d, size_t bytes) { return d == out ? 0 : copy_out(c, out, d, bytes); }
+// a call's single verdict, decided on the host, to wherever the caller keeps it
+int put_i32(int32_t* dst, int32_t v) {
+  if (is_device_ptr(dst)) HIPCK(hipMemcpy(dst, &v, 4, hipMemcpyHostToDevice));
+  else *dst = v;
+  return 0;
+}
 
 // a call's verdicts: copy, then wait for the stream.  A few verdicts for host memory travel through the pinned record buffer (a
 // device-to-host copy into pageable memory makes the runtime stage and wait internally, ~10 us more on a 1.5 ms call).
@@ -366,10 +369,14 @@ int status_out_and_sync(Ctx* c, int32_t* status, const int32_t* d_status, size_t
   return 0;
 }
 
-size_t g1_size(int fmt) { return fmt == BLSGPU_FMT_RAW_PROJ ? 144 : fmt == BLSGPU_FMT_RAW_AFFINE ? 96 : 48; }
-size_t g2_size(int fmt) { return fmt == BLSGPU_FMT_RAW_PROJ ? 288 : fmt == BLSGPU_FMT_RAW_AFFINE ? 192 : 96; }
-size_t pk_size(int sg, int fmt) { return sg == 1 ? g2_size(fmt) : g1_size(fmt); }
-size_t sig_size(int sg, int fmt) { return sg == 1 ? g1_size(fmt) : g2_size(fmt); }
+// bytes of one point of `group` (1: G1, 2: G2, twice as wide) in a caller format; the two compressed formats are equally long.
+// This and key_group hold for group 1 or 2 only: every entry point checks its group argument before it gets here.
+size_t point_bytes(int group, int fmt) {
+  return (size_t)group * (fmt == BLSGPU_FMT_RAW_PROJ ? 144 : fmt == BLSGPU_FMT_RAW_AFFINE ? 96 : 48);
+}
+int key_group(int sig_group) { return 3 - sig_group; }   // the keys live in the group the signatures do not
+size_t pk_size(int sg, int fmt) { return point_bytes(key_group(sg), fmt); }
+size_t sig_size(int sg, int fmt) { return point_bytes(sg, fmt); }
 
 const char* DST_TABLE[2][3] = {
     {"BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_NUL_", "BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_AUG_",
@@ -458,6 +465,14 @@ void prof_flush(Ctx* c) {
     hipLaunchKernelGGL(kern, grid, block, 0, strm, __VA_ARGS__);                \
     prof_post(c, strm);                                                         \
   } while (0)
+// The run-time group as a compile-time one: f gets std::integral_constant<int, 1> or <int, 2>, so a generic lambda names
+// k_x<G()> / run_x<G()> once for both groups.  Returns what f returns: an rc, or nothing when f is a bare launch (KL needs `c`
+// in scope; HIPCK / fail return from the lambda, not from its caller, so they stay outside or travel as the rc).
+template <class F>
+auto with_group(int group, F&& f) {
+  if (group == 1) return f(std::integral_constant<int, 1>());
+  return f(std::integral_constant<int, 2>());
+}
 // one Miller loop per MILLER1_GROUP items: leaves ceil(cnt / MILLER1_GROUP) partial products at the start of the Fp12 workspace
 #define MILLER1_OUTPUTS(cnt) (((cnt) + MILLER1_GROUP - 1) / MILLER1_GROUP)
 #define MILLER1_LAUNCH(cnt, ...) KL(KID_MILLER1, k_miller1s, dim3(blocks_for(2 * MILLER1_OUTPUTS(cnt))), dim3(BLS_BLOCK), cnt, __VA_ARGS__)
@@ -1283,7 +1298,7 @@ int run_msm_pippenger(Ctx* c, const uint8_t* d_pts, int fmt, const uint8_t* d_sc
 const size_t POINT_TREE_START = 4096;
 template <int G>
 int run_point_fold(Ctx* c, uint8_t* d_partials, size_t m) {
-  const size_t psz = G == 1 ? 144 : 288;
+  const size_t psz = point_bytes(G, BLSGPU_FMT_RAW_PROJ);
   size_t cur = m;
   const bool wide = wide_max_items() >= 1;               // BLSGPU_WIDE_MAX=0 switches the row-wide engine off everywhere
   while (cur > (wide ? POINT_TREE_START : 1)) {
@@ -1478,7 +1493,7 @@ int run_msm2_rest(Ctx* c, const uint8_t* d_scalars, size_t n, msm2_ws& w, uint8_
   // pairing stages skips it
   if (normalize) KL(KID_MSM_NORM, k_normalize<G>, dim3(1), dim3(BLS_BLOCK), w.part);
   HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(d_out, w.part, G == 1 ? 144 : 288, hipMemcpyDeviceToDevice, c->stream));
+  HIPCK(hipMemcpyAsync(d_out, w.part, point_bytes(G, BLSGPU_FMT_RAW_PROJ), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 bool msm_use_v1() { return knobs().msm_v1 != 0; }   // A/B switch: the first-generation bucket method (unsigned digits, full additions)
@@ -1510,7 +1525,7 @@ int run_msm_pippenger(Ctx* c, const uint8_t* d_pts, int fmt, const uint8_t* d_sc
   if (int rc = run_point_fold<G>(c, d_part, p.nchunks)) return rc;
   KL(KID_MSM_NORM, k_normalize<G>, dim3(1), dim3(BLS_BLOCK), d_part);
   HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(d_out, d_part, G == 1 ? 144 : 288, hipMemcpyDeviceToDevice, c->stream));
+  HIPCK(hipMemcpyAsync(d_out, d_part, point_bytes(G, BLSGPU_FMT_RAW_PROJ), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -1924,17 +1939,14 @@ int blsgpu_verify_batch(int sig_group, int scheme, const void* pks, const void* 
     // test, reference src/public_key.rs:58-74,158-171, src/signature.rs:231-253, src/impls/legacy.rs:100-170.
     // A decode failure is the item's status (key first, then signature), exactly what a caller that deserialises
     // before verifying would have seen.
-    uint8_t* d_pk_raw = (uint8_t*)arena_take(c, (sig_group == 1 ? 288 : 144) * n);
-    uint8_t* d_sig_raw = (uint8_t*)arena_take(c, (sig_group == 1 ? 144 : 288) * n);
+    uint8_t* d_pk_raw = (uint8_t*)arena_take(c, pk_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n);
+    uint8_t* d_sig_raw = (uint8_t*)arena_take(c, sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n);
     if (!d_pk_raw || !d_sig_raw) return fail(BLSGPU_E_HIP, "internal: arena too small");
     const int legacy = fmt == BLSGPU_FMT_LEGACY;
-    if (sig_group == 1) {
-      KL(KID_DECOMPRESS, k_decompress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, legacy, d_pk_raw, d_status, 0);
-      KL(KID_DECOMPRESS, k_decompress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_sigs, legacy, d_sig_raw, d_status, 1);
-    } else {
-      KL(KID_DECOMPRESS, k_decompress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, legacy, d_pk_raw, d_status, 0);
-      KL(KID_DECOMPRESS, k_decompress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_sigs, legacy, d_sig_raw, d_status, 1);
-    }
+    with_group(key_group(sig_group), [&](auto KG) {
+      KL(KID_DECOMPRESS, k_decompress<KG()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, legacy, d_pk_raw, d_status, 0);
+      KL(KID_DECOMPRESS, k_decompress<3 - KG()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_sigs, legacy, d_sig_raw, d_status, 1);
+    });
     d_pks = d_pk_raw;
     d_sigs = d_sig_raw;
     pre = 1;
@@ -2061,12 +2073,12 @@ static int verify_one_tail(Ctx* c, int sig_group, int scheme, int aug_prefix, co
   if (!d_offs || !d_status || !d_pairs || !d_f || !d_sig_proj) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if ((rc = h2d_small(c, d_offs, offs_h, 16))) return rc;
   // normalise the signature to RAW_PROJ with a 1-point "sum"
-  if (sig_group == 1) rc = run_point_sum<1>(c, (const uint8_t*)d_sig_in, fmt, nullptr, nullptr, 1, d_sig_proj, 1);
-  else rc = run_point_sum<2>(c, (const uint8_t*)d_sig_in, fmt, nullptr, nullptr, 1, d_sig_proj, 1);
+  rc = with_group(sig_group, [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_sig_in, fmt, nullptr, nullptr, 1, d_sig_proj, 1); });
   if (rc) return rc;
   if (d_hash) {
-    if (sig_group == 1) KL(KID_PREPARE, k_prepare_hashed<1>, dim3(1), dim3(BLS_BLOCK), (size_t)1, d_pk_proj, (const uint8_t*)d_sig_proj, d_hash, d_pairs, d_status, 0);
-    else KL(KID_PREPARE, k_prepare_hashed<2>, dim3(1), dim3(BLS_BLOCK), (size_t)1, d_pk_proj, (const uint8_t*)d_sig_proj, d_hash, d_pairs, d_status, 0);
+    with_group(sig_group, [&](auto G) {
+      KL(KID_PREPARE, k_prepare_hashed<G()>, dim3(1), dim3(BLS_BLOCK), (size_t)1, d_pk_proj, (const uint8_t*)d_sig_proj, d_hash, d_pairs, d_status, 0);
+    });
     rc = run_pairing2(c, 1, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0);
   } else {
     rc = run_verify_items(c, sig_group, aug_prefix, d_pk_proj, d_sig_proj, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msg, d_offs, 1,
@@ -2175,7 +2187,7 @@ int blsgpu_multi_verify(int sig_group, int scheme, const void* pks, size_t n, co
   if (const size_t D = shard_devices(n, {pks, sig}); D > 1) {
     // per-device partial key sums (reference src/traits/pk_multi.rs:7-13 cut into ranges), then the fold and the one
     // verification on device 0: MultiSignature::verify over the D partial sums
-    const size_t psz = pk_size(sig_group, fmt), osz = sig_group == 1 ? 288 : 144;
+    const size_t psz = pk_size(sig_group, fmt), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
     std::vector<uint8_t> parts(osz * D), sig_proj(288);
     if ((rc = run_on_devices(D, [&](size_t d) {
           const size_t lo = n * d / D, hi = n * (d + 1) / D;
@@ -2219,8 +2231,7 @@ int blsgpu_multi_verify(int sig_group, int scheme, const void* pks, size_t n, co
     HIPCK(hipEventRecord(c->ev_join, c->side));
   }
   // MultiPublicKey::from_public_keys: the serial `g += key` of reference src/traits/pk_multi.rs:7-13 as a tree sum
-  if (sig_group == 1) rc = run_point_sum<2>(c, (const uint8_t*)d_pks, fmt, nullptr, nullptr, n, d_part, T);
-  else rc = run_point_sum<1>(c, (const uint8_t*)d_pks, fmt, nullptr, nullptr, n, d_part, T);
+  rc = with_group(key_group(sig_group), [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_pks, fmt, nullptr, nullptr, n, d_part, T); });
   if (use_cut) return cut_tail_finish(c, rc, d_part, cut, status);
   if (d_hash) {
     hipError_t e = hipStreamWaitEvent(c->stream, c->ev_join, 0);    // also on the error path: the side kernel reads the arena
@@ -2420,8 +2431,7 @@ int blsgpu_aggregate_verify(int sig_group, int scheme, const void* pks, const ui
         st = one ? BLSGPU_OK : BLSGPU_INVALID_SIGNATURE;
       }
     }
-    if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-    else *status = st;
+    if (int e = put_i32(status, st)) return e;
     if (aux) {
       if (is_device_ptr(aux)) HIPCK(hipMemcpy(aux, aux_h, 16, hipMemcpyHostToDevice));
       else memcpy(aux, aux_h, 16);
@@ -2502,8 +2512,7 @@ int blsgpu_aggregate_verify(int sig_group, int scheme, const void* pks, const ui
   } else {
     st = h->verdict;
   }
-  if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-  else *status = st;
+  if (int e = put_i32(status, st)) return e;
   if (aux) {
     if (is_device_ptr(aux)) HIPCK(hipMemcpy(aux, aux_h, 16, hipMemcpyHostToDevice));
     else memcpy(aux, aux_h, 16);
@@ -2520,12 +2529,11 @@ static int empty_list_verdict(Ctx* c, int sig_group, const void* sig, int fmt, i
   uint8_t* d_proj = (uint8_t*)arena_take(c, 288);
   uint8_t* h = (uint8_t*)hsmall_take(c, 288);
   if (!d_proj || !h) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if (sig_group == 1) rc = run_point_sum<1>(c, (const uint8_t*)d_sig, fmt, nullptr, nullptr, 1, d_proj, 1);
-  else rc = run_point_sum<2>(c, (const uint8_t*)d_sig, fmt, nullptr, nullptr, 1, d_proj, 1);
+  rc = with_group(sig_group, [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_sig, fmt, nullptr, nullptr, 1, d_proj, 1); });
   if (rc) return rc;
   HIPCK(hipMemcpyAsync(h, d_proj, 288, hipMemcpyDeviceToHost, c->stream));
   SYNC_FLUSH(c);
-  const size_t zoff = sig_group == 1 ? 96 : 192, zlen = sig_group == 1 ? 48 : 96;
+  const size_t zoff = sig_size(sig_group, BLSGPU_FMT_RAW_AFFINE), zlen = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) - zoff;   // Z follows X and Y
   bool inf = true;
   for (size_t k = 0; k < zlen; k++) inf = inf && h[zoff + k] == 0;
   *st = inf ? BLSGPU_OK : BLSGPU_INVALID_SIGNATURE;
@@ -2545,8 +2553,8 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
     // every device serialises its range of the keys; device 0 sorts all of them and a host core hashes the sorted stream
     // (the one sequential step, reference src/secure_aggregation.rs:45-59); every device derives the coefficients of its
     // own keys and adds up its share of sum t_i pk_i; device 0 folds the D partial sums and runs the one verification
-    const int pk_group = sig_group == 1 ? 2 : 1;
-    const size_t psz = pk_size(sig_group, fmt), width = sig_group == 1 ? 96 : 48, osz = sig_group == 1 ? 288 : 144;
+    const int pk_group = key_group(sig_group);
+    const size_t psz = pk_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
     std::vector<uint8_t> kb(width * n), parts(osz * D), apk(288), sig_proj(288), hm(288), digest(32);
     std::vector<uint32_t> perm(n);
     std::vector<int32_t> sts(D, 0);
@@ -2592,28 +2600,24 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
       if ((rc = (sig_group == 1 ? blsgpu_sum_g1 : blsgpu_sum_g2)(sig, 1, fmt, sig_proj.data()))) return rc;
       if ((rc = blsgpu_core_verify_hashed(sig_group, apk.data(), sig_proj.data(), hm.data(), 1, &st))) return rc;
     }
-    if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-    else *status = st;
-    return 0;
+    return put_i32(status, st);
   }
   CTX_ACQUIRE(c);
   const bool trace = knobs().host_trace != 0;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const size_t psz = pk_size(sig_group, fmt), width = sig_group == 1 ? 96 : 48, T = accumulate_lanes(n);
+  const size_t psz = pk_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), T = accumulate_lanes(n);
   // weighted MSM tables (csrc/kernels.cuh k_msm2_tables): built while the host hashes the key stream; BLSGPU_MSM2_TABLES=0 switches them off
   // (up to 262,144 keys: the tables are 4.5 KB per G2 key -- 1.2 GB there -- and stay in the context's arena; beyond that size the sum
   // is throughput-bound and its chunk lanes' latency no longer shows)
   const bool msm_tables = knobs().msm2_tables != 0 && msm_use_pippenger(n) && !msm_use_v1() && n <= ((size_t)1 << 18);
   size_t need = pad256(psz * n) + pad256(width * n) + pad256(32 * n) + pad256(288 * T) + pad256(msg_len) + 16384 + msm_ws_bytes(n) +
-                keysort_ws_bytes(n, width) + (msm_tables ? msm2_tables_bytes(n, sig_group == 1 ? 2 : 1) : 0);
+                keysort_ws_bytes(n, width) + (msm_tables ? msm2_tables_bytes(n, key_group(sig_group)) : 0);
   if ((rc = arena_reserve(c, need))) return rc;
   c->arena_off = 0;
   int32_t st = BLSGPU_OK;
   if (n == 0) {
     if ((rc = empty_list_verdict(c, sig_group, sig, fmt, &st))) return rc;
-    if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-    else *status = st;
-    return 0;
+    return put_i32(status, st);
   }
   const void* d_pks;
   if ((rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
@@ -2628,10 +2632,9 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
   if ((rc = keysort_ws_take(c, n, width, w))) return rc;
   const double t0 = now();
   // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:42,47; public_key.rs:146-151)
-  if (sig_group == 1)
-    KL(KID_COMPRESS, k_compress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
-  else
-    KL(KID_COMPRESS, k_compress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
+  with_group(key_group(sig_group), [&](auto G) {
+    KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
+  });
   HIPCK(hipGetLastError());
   // stable byte-lexicographic sort on the device; the sorted bytes travel to the host for the one sequential SHA-256
   if (!c->ev_host) HIPCK(hipEventCreateWithFlags(&c->ev_host, hipEventDisableTiming));
@@ -2666,9 +2669,8 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
   const bool msm2 = msm_use_pippenger(n) && !msm_use_v1();
   msm2_ws mw;
   if (msm2) {
-    if ((rc = msm2_ws_take(c, n, sig_group == 1 ? 2 : 1, mw, msm_tables))) return rc;
-    if (sig_group == 1) rc = run_msm2_prep<2>(c, (const uint8_t*)d_pks, fmt, nullptr, n, mw);
-    else rc = run_msm2_prep<1>(c, (const uint8_t*)d_pks, fmt, nullptr, n, mw);
+    if ((rc = msm2_ws_take(c, n, key_group(sig_group), mw, msm_tables))) return rc;
+    rc = with_group(key_group(sig_group), [&](auto G) { return run_msm2_prep<G()>(c, (const uint8_t*)d_pks, fmt, nullptr, n, mw); });
     if (rc) return rc;
   }
   if ((rc = run_key_sort_finish(c, d_bytes, n, width, w, c->ev_host, &full_sort))) return rc;
@@ -2683,11 +2685,9 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
   HIPCK(hipMemcpyAsync(h_zero, d_zero, 4, hipMemcpyDeviceToHost, c->stream));
   // aggregated_pk = sum t_i * pk_sorted[i]   (reference src/secure_aggregation.rs:201-204)
   if (msm2) {
-    if (sig_group == 1) rc = run_msm2_rest<2>(c, d_scal, n, mw, d_part, false);
-    else rc = run_msm2_rest<1>(c, d_scal, n, mw, d_part, false);
+    rc = with_group(key_group(sig_group), [&](auto G) { return run_msm2_rest<G()>(c, d_scal, n, mw, d_part, false); });
   } else {
-    if (sig_group == 1) rc = run_point_sum<2>(c, (const uint8_t*)d_pks, fmt, d_scal, nullptr, n, d_part, T);
-    else rc = run_point_sum<1>(c, (const uint8_t*)d_pks, fmt, d_scal, nullptr, n, d_part, T);
+    rc = with_group(key_group(sig_group), [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_pks, fmt, d_scal, nullptr, n, d_part, T); });
   }
   if (use_cut) {
     if ((rc = cut_tail_finish(c, rc, d_part, cut, status))) return rc;
@@ -2701,8 +2701,7 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
             n, full_sort ? " (full-width)" : "", t1 - t0, t2 - t1, now() - t2);
   if (*h_zero) {                   // a zero coefficient: BlsError::InvalidCoefficient before any verification (:97-100)
     st = BLSGPU_INVALID_COEFFICIENT;
-    if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-    else *status = st;
+    if (int e = put_i32(status, st)) return e;
   }
   return 0;
 }
@@ -2741,9 +2740,7 @@ int blsgpu_secure_coefficients(const uint8_t* key_bytes, size_t n, size_t width,
     SYNC_FLUSH(c);
     if (*h_zero) st = BLSGPU_INVALID_COEFFICIENT;
   }
-  if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-  else *status = st;
-  return 0;
+  return put_i32(status, st);
 }
 API_CATCH
 
@@ -2828,20 +2825,18 @@ int blsgpu_coefficients_for_range(const uint8_t* digest, const uint32_t* perm, s
     const void *d_perm, *d_H;
     if ((rc = stage_in(c, perm, 4 * n, &d_perm))) return rc;
     if ((rc = stage_in(c, digest, 32, &d_H))) return rc;
-    uint8_t* d_scal = is_device_ptr(out_scalars) ? out_scalars : (uint8_t*)arena_take(c, 32 * count);
+    uint8_t* d_scal = stage_out<uint8_t>(c, out_scalars, 32 * count);
     int32_t* d_zero = (int32_t*)arena_take(c, 64);
     int32_t* h_zero = (int32_t*)hsmall_take(c, 64);
     if ((count && !d_scal) || !d_zero || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
     HIPCK(hipMemsetAsync(d_zero, 0, 4, c->stream));
     if ((rc = run_coefficients(c, (const uint8_t*)d_H, (const uint32_t*)d_perm, n, base, count, 0, d_scal, d_zero))) return rc;
     HIPCK(hipMemcpyAsync(h_zero, d_zero, 4, hipMemcpyDeviceToHost, c->stream));
-    if (d_scal != out_scalars && (rc = copy_out(c, out_scalars, d_scal, 32 * count))) return rc;
+    if ((rc = stage_back(c, out_scalars, d_scal, 32 * count))) return rc;
     SYNC_FLUSH(c);
     if (*h_zero) st = BLSGPU_INVALID_COEFFICIENT;
   }
-  if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-  else *status = st;
-  return 0;
+  return put_i32(status, st);
 }
 API_CATCH
 
@@ -2862,13 +2857,13 @@ int blsgpu_first_occurrence(const uint8_t* key_bytes, const uint32_t* perm, size
   if ((rc = stage_in(c, perm, 4 * n, &d_perm))) return rc;
   uint32_t* d_start = (uint32_t*)arena_take(c, 4 * n);
   uint32_t* d_tiles = (uint32_t*)arena_take(c, 4 * scan_tiles(n));
-  uint32_t* d_idx = is_device_ptr(out_idx) ? out_idx : (uint32_t*)arena_take(c, 4 * n);
+  uint32_t* d_idx = stage_out<uint32_t>(c, out_idx, 4 * n);
   if (!d_start || !d_tiles || !d_idx) return fail(BLSGPU_E_HIP, "internal: arena too small");
   KL(KID_KEY_SORT, k_keys_run_start, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_kb, width, (const uint32_t*)d_perm, d_start);
   if ((rc = run_scan_max_u32(c, KID_KEY_SORT, n, d_start, d_tiles))) return rc;
   KL(KID_KEY_SORT, k_run_first_index, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_perm, (const uint32_t*)d_start, d_idx);
   HIPCK(hipGetLastError());
-  if (d_idx != out_idx && (rc = copy_out(c, out_idx, d_idx, 4 * n))) return rc;
+  if ((rc = stage_back(c, out_idx, d_idx, 4 * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -2906,14 +2901,14 @@ static int hash_to_group(int group, const uint8_t* msgs, const uint64_t* msg_off
   uint64_t total = 0;
   if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + n, 8, hipMemcpyDeviceToHost));
   else total = msg_offsets[n];
-  const size_t osz = group == 1 ? 144 : 288;
+  const size_t osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
   int rc = arena_reserve(c, pad256(total) + pad256(8 * (n + 1)) + pad256(osz * n) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
   const void *d_msgs, *d_offs;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
-  uint8_t* d_out = is_device_ptr(out) ? (uint8_t*)out : (uint8_t*)arena_take(c, osz * n);
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n);
   if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
   dst_arg d = make_dst(dst, dst_len);
   // two lanes per message: always for G2; for G1 up to the cooperative threshold (a full hash-only batch is faster with one lane per message)
@@ -2935,7 +2930,7 @@ static int hash_to_group(int group, const uint8_t* msgs, const uint64_t* msg_off
   } else
     KL(KID_HASH, k_hash_to_g2, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, d, d_out, two);
   HIPCK(hipGetLastError());
-  if (d_out != out && (rc = copy_out(c, out, d_out, osz * n))) return rc;
+  if ((rc = stage_back(c, out, d_out, osz * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -2953,7 +2948,7 @@ static int point_sum_entry(int group, const void* pts, const uint8_t* scalars, s
   if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE) return fail(BLSGPU_E_ARG, "fmt must be RAW_PROJ or RAW_AFFINE");
   if (!out || (n && !pts)) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  const size_t psz = group == 1 ? g1_size(fmt) : g2_size(fmt), osz = group == 1 ? 144 : 288, T = accumulate_lanes(n);
+  const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ), T = accumulate_lanes(n);
   int rc = arena_reserve(c, pad256(psz * n) + pad256(32 * n) + pad256(288 * T) + 4096 + (scalars ? msm_ws_bytes(n) : 0));
   if (rc) return rc;
   c->arena_off = 0;
@@ -2962,8 +2957,7 @@ static int point_sum_entry(int group, const void* pts, const uint8_t* scalars, s
   if (scalars && (rc = stage_in(c, scalars, 32 * n, &d_scal))) return rc;
   uint8_t* d_part = (uint8_t*)arena_take(c, 288 * T);
   if (!d_part) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if (group == 1) rc = run_point_sum<1>(c, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_scal, nullptr, n, d_part, T);
-  else rc = run_point_sum<2>(c, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_scal, nullptr, n, d_part, T);
+  rc = with_group(group, [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_scal, nullptr, n, d_part, T); });
   if (rc) return rc;
   if ((rc = copy_out(c, out, d_part, osz))) return rc;
   SYNC_FLUSH(c);
@@ -2989,12 +2983,12 @@ int blsgpu_pairing_product_is_one(const void* g1s, const void* g2s, size_t n, in
   int32_t verdict = BLSGPU_OK;
   if (n > 0) {
     CTX_ACQUIRE(c);
-    int rc = arena_reserve(c, pad256(g1_size(fmt) * n) + pad256(g2_size(fmt) * n) + pad256(4 * n) + 2 * pad256((size_t)WS_F_WORDS * 4 * n) + 4096);
+    int rc = arena_reserve(c, pad256(point_bytes(1, fmt) * n) + pad256(point_bytes(2, fmt) * n) + pad256(4 * n) + 2 * pad256((size_t)WS_F_WORDS * 4 * n) + 4096);
     if (rc) return rc;
     c->arena_off = 0;
     const void *d1, *d2;
-    if ((rc = stage_in(c, g1s, g1_size(fmt) * n, &d1))) return rc;
-    if ((rc = stage_in(c, g2s, g2_size(fmt) * n, &d2))) return rc;
+    if ((rc = stage_in(c, g1s, point_bytes(1, fmt) * n, &d1))) return rc;
+    if ((rc = stage_in(c, g2s, point_bytes(2, fmt) * n, &d2))) return rc;
     int32_t* d_skip = (int32_t*)arena_take(c, 4 * n + 4);
     uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIR1_WORDS * 4 * n);
     uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
@@ -3007,9 +3001,7 @@ int blsgpu_pairing_product_is_one(const void* g1s, const void* g2s, size_t n, in
     SYNC_FLUSH(c);
   }
   int32_t one = verdict == BLSGPU_OK ? 1 : 0;
-  if (is_device_ptr(is_one)) HIPCK(hipMemcpy(is_one, &one, 4, hipMemcpyHostToDevice));
-  else *is_one = one;
-  return 0;
+  return put_i32(is_one, one);
 }
 API_CATCH
 
@@ -3021,19 +3013,18 @@ int blsgpu_serialize(int group, const void* pts, size_t n, int fmt_in, int fmt_o
   if (n == 0) return 0;
   if (!pts || !out) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  const size_t psz = group == 1 ? g1_size(fmt_in) : g2_size(fmt_in), osz = group == 1 ? 48 : 96;
+  const size_t psz = point_bytes(group, fmt_in), osz = point_bytes(group, BLSGPU_FMT_COMPRESSED);
   int rc = arena_reserve(c, pad256(psz * n) + pad256(osz * n) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
   const void* d_pts;
   if ((rc = stage_in(c, pts, psz * n, &d_pts))) return rc;
-  uint8_t* d_out = is_device_ptr(out) ? (uint8_t*)out : (uint8_t*)arena_take(c, osz * n);
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n);
   if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
   int legacy = fmt_out == BLSGPU_FMT_LEGACY;
-  if (group == 1) KL(KID_COMPRESS, k_compress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt_in, legacy, d_out);
-  else KL(KID_COMPRESS, k_compress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt_in, legacy, d_out);
+  with_group(group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt_in, legacy, d_out); });
   HIPCK(hipGetLastError());
-  if (d_out != out && (rc = copy_out(c, out, d_out, osz * n))) return rc;
+  if ((rc = stage_back(c, out, d_out, osz * n))) return rc;
   SYNC_FLUSH(c);
   if (status) {
     std::vector<int32_t> z(n, 0);
@@ -3087,8 +3078,8 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
   if (ser_format == 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl");
   if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 keys");
   CTX_ACQUIRE(c);
-  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = sig_group == 1 ? 96 : 48, T = accumulate_lanes(n);
-  const size_t osz = sig_group == 1 ? 144 : 288;
+  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), T = accumulate_lanes(n);
+  const size_t osz = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ);
   size_t need = pad256(psz * n) + pad256(ssz * n) + pad256(width * n) + 2 * pad256(4 * n) + pad256(32 * n) + pad256(288 * T) + 8192 + msm_ws_bytes(n) +
                 keysort_ws_bytes(n, width) + pad256(4 * scan_tiles(n));
   if ((rc = arena_reserve(c, need))) return rc;
@@ -3099,8 +3090,7 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
   if (!d_part || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
   *h_zero = 0;
   if (n == 0) {
-    if (sig_group == 1) rc = run_point_sum<1>(c, nullptr, fmt, nullptr, nullptr, 0, d_part, T);
-    else rc = run_point_sum<2>(c, nullptr, fmt, nullptr, nullptr, 0, d_part, T);
+    rc = with_group(sig_group, [&](auto G) { return run_point_sum<G()>(c, nullptr, fmt, nullptr, nullptr, 0, d_part, T); });
     if (rc) return rc;
   } else {
     const void *d_pks, *d_sigs;
@@ -3116,8 +3106,9 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
     keysort_ws w;
     if (!d_bytes || !d_idx || !d_start || !d_tiles || !d_scal || !d_H || !d_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
     if ((rc = keysort_ws_take(c, n, width, w))) return rc;
-    if (sig_group == 1) KL(KID_COMPRESS, k_compress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
-    else KL(KID_COMPRESS, k_compress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
+    with_group(key_group(sig_group), [&](auto G) {
+      KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
+    });
     HIPCK(hipGetLastError());
     if ((rc = run_key_sort_to_host(c, d_bytes, n, width, w, nullptr, nullptr))) return rc;
     uint8_t H[32];
@@ -3132,8 +3123,7 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
     if ((rc = run_scan_max_u32(c, KID_KEY_SORT, n, d_start, d_tiles))) return rc;
     KL(KID_KEY_SORT, k_run_first_index, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)w.perm_a, (const uint32_t*)d_start, d_idx);
     HIPCK(hipGetLastError());
-    if (sig_group == 1) rc = run_point_sum<1>(c, (const uint8_t*)d_sigs, fmt, d_scal, d_idx, n, d_part, T);
-    else rc = run_point_sum<2>(c, (const uint8_t*)d_sigs, fmt, d_scal, d_idx, n, d_part, T);
+    rc = with_group(sig_group, [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_sigs, fmt, d_scal, d_idx, n, d_part, T); });
     if (rc) return rc;
   }
   SYNC_FLUSH(c);
@@ -3142,9 +3132,7 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
     if ((rc = copy_out(c, out_sig, d_part, osz))) return rc;
     SYNC_FLUSH(c);
   }
-  if (is_device_ptr(status)) HIPCK(hipMemcpy(status, &st, 4, hipMemcpyHostToDevice));
-  else *status = st;
-  return 0;
+  return put_i32(status, st);
 }
 API_CATCH
 
@@ -3155,21 +3143,20 @@ int blsgpu_deserialize(int group, const uint8_t* bytes, size_t n, int fmt_in, vo
   if (n == 0) return 0;
   if (!bytes || !out || !status) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  const size_t isz = group == 1 ? 48 : 96, osz = group == 1 ? 144 : 288;
+  const size_t isz = point_bytes(group, BLSGPU_FMT_COMPRESSED), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
   int rc = arena_reserve(c, pad256(isz * n) + pad256(osz * n) + pad256(4 * n) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
   const void* d_in;
   if ((rc = stage_in(c, bytes, isz * n, &d_in))) return rc;
-  uint8_t* d_out = is_device_ptr(out) ? (uint8_t*)out : (uint8_t*)arena_take(c, osz * n);
-  int32_t* d_st = is_device_ptr(status) ? status : (int32_t*)arena_take(c, 4 * n);
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n);
+  int32_t* d_st = stage_out<int32_t>(c, status, 4 * n);
   if (!d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
   const int legacy = fmt_in == BLSGPU_FMT_LEGACY;
-  if (group == 1) KL(KID_DECOMPRESS, k_decompress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_in, legacy, d_out, d_st, 0);
-  else KL(KID_DECOMPRESS, k_decompress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_in, legacy, d_out, d_st, 0);
+  with_group(group, [&](auto G) { KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_in, legacy, d_out, d_st, 0); });
   HIPCK(hipGetLastError());
-  if (d_out != out && (rc = copy_out(c, out, d_out, osz * n))) return rc;
-  if (d_st != status && (rc = copy_out(c, status, d_st, 4 * n))) return rc;
+  if ((rc = stage_back(c, out, d_out, osz * n))) return rc;
+  if ((rc = stage_back(c, status, d_st, 4 * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -3186,24 +3173,23 @@ int blsgpu_signatures_from_tagged(int sig_group, const uint8_t* bytes, size_t n,
   if (n == 0) return 0;
   if (!bytes || !out_schemes || !out || !status) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  const size_t width = sig_group == 1 ? 48 : 96, osz = sig_group == 1 ? 144 : 288;
+  const size_t width = sig_size(sig_group, BLSGPU_FMT_COMPRESSED), osz = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ);
   if ((rc = arena_reserve(c, pad256((width + 1) * n) + pad256(width * n) + pad256(n) + pad256(osz * n) + pad256(4 * n) + 4096))) return rc;
   c->arena_off = 0;
   const void* d_in;
   if ((rc = stage_in(c, bytes, (width + 1) * n, &d_in))) return rc;
   uint8_t* d_bytes = (uint8_t*)arena_take(c, width * n);
-  uint8_t* d_tags = is_device_ptr(out_schemes) ? out_schemes : (uint8_t*)arena_take(c, n);
-  uint8_t* d_out = is_device_ptr(out) ? (uint8_t*)out : (uint8_t*)arena_take(c, osz * n);
-  int32_t* d_st = is_device_ptr(status) ? status : (int32_t*)arena_take(c, 4 * n);
+  uint8_t* d_tags = stage_out<uint8_t>(c, out_schemes, n);
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n);
+  int32_t* d_st = stage_out<int32_t>(c, status, 4 * n);
   if (!d_bytes || !d_tags || !d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
   KL(KID_DECOMPRESS, k_untag, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, width, (const uint8_t*)d_in, d_bytes, d_tags, d_st);
   HIPCK(hipMemsetAsync(d_out, 0, osz * n, c->stream));      // records with a bad tag are not decoded: leave the identity encoding
-  if (sig_group == 1) KL(KID_DECOMPRESS, k_decompress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_bytes, 0, d_out, d_st, 1);
-  else KL(KID_DECOMPRESS, k_decompress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_bytes, 0, d_out, d_st, 1);
+  with_group(sig_group, [&](auto G) { KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_bytes, 0, d_out, d_st, 1); });
   HIPCK(hipGetLastError());
-  if (d_tags != out_schemes && (rc = copy_out(c, out_schemes, d_tags, n))) return rc;
-  if (d_out != out && (rc = copy_out(c, out, d_out, osz * n))) return rc;
-  if (d_st != status && (rc = copy_out(c, status, d_st, 4 * n))) return rc;
+  if ((rc = stage_back(c, out_schemes, d_tags, n))) return rc;
+  if ((rc = stage_back(c, out, d_out, osz * n))) return rc;
+  if ((rc = stage_back(c, status, d_st, 4 * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -3214,20 +3200,19 @@ int blsgpu_signatures_to_tagged(int sig_group, const uint8_t* schemes, const voi
   if (n == 0) return 0;
   if (!schemes || !sigs || !out) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  const size_t width = sig_group == 1 ? 48 : 96, psz = sig_size(sig_group, fmt);
+  const size_t width = sig_size(sig_group, BLSGPU_FMT_COMPRESSED), psz = sig_size(sig_group, fmt);
   if ((rc = arena_reserve(c, pad256(psz * n) + pad256(n) + pad256(width * n) + pad256((width + 1) * n) + 4096))) return rc;
   c->arena_off = 0;
   const void *d_pts, *d_tags;
   if ((rc = stage_in(c, sigs, psz * n, &d_pts))) return rc;
   if ((rc = stage_in(c, schemes, n, &d_tags))) return rc;
   uint8_t* d_bytes = (uint8_t*)arena_take(c, width * n);
-  uint8_t* d_out = is_device_ptr(out) ? out : (uint8_t*)arena_take(c, (width + 1) * n);
+  uint8_t* d_out = stage_out<uint8_t>(c, out, (width + 1) * n);
   if (!d_bytes || !d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if (sig_group == 1) KL(KID_COMPRESS, k_compress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, 0, d_bytes);
-  else KL(KID_COMPRESS, k_compress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, 0, d_bytes);
+  with_group(sig_group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, 0, d_bytes); });
   KL(KID_COMPRESS, k_tag, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, width, (const uint8_t*)d_tags, (const uint8_t*)d_bytes, d_out);
   HIPCK(hipGetLastError());
-  if (d_out != out && (rc = copy_out(c, out, d_out, (width + 1) * n))) return rc;
+  if ((rc = stage_back(c, out, d_out, (width + 1) * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -3247,13 +3232,13 @@ int blsgpu_debug_wide_mul(const uint8_t* a, const uint8_t* b, size_t n, int reps
   const void *d_a, *d_b;
   if ((rc = stage_in(c, a, 48 * n, &d_a))) return rc;
   if ((rc = stage_in(c, b, 48 * n, &d_b))) return rc;
-  uint8_t* d_out = is_device_ptr(out) ? out : (uint8_t*)arena_take(c, 48 * n);
+  uint8_t* d_out = stage_out<uint8_t>(c, out, 48 * n);
   if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
   // BLSGPU_WIDE_TEST_BLOCK=256: sixteen items per 256-thread workgroup (the engine's shape) instead of four per wave
   const unsigned tb = knobs().wide_test_block == 256 ? 256 : 64, per = tb / 16;
   KL(KID_WIDE, k_wide_mul_test, dim3((unsigned)((n + per - 1) / per)), dim3(tb), n, (const uint8_t*)d_a, (const uint8_t*)d_b, d_out, reps);
   HIPCK(hipGetLastError());
-  if (d_out != out && (rc = copy_out(c, out, d_out, 48 * n))) return rc;
+  if ((rc = stage_back(c, out, d_out, 48 * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -3274,11 +3259,11 @@ int blsgpu_debug_wide_program(const uint32_t* prog, size_t len, int reps, const 
   const void *d_prog, *d_in;
   if ((rc = stage_in(c, prog, 8 * len, &d_prog))) return rc;
   if ((rc = stage_in(c, f_in, 576, &d_in))) return rc;
-  uint8_t* d_out = is_device_ptr(t_out) ? t_out : (uint8_t*)arena_take(c, 576);
+  uint8_t* d_out = stage_out<uint8_t>(c, t_out, 576);
   if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
   KL(KID_WIDE, k_wide_prog_test, dim3(1), dim3(WIDE_ENGINE_BLOCK), (const uint32_t*)d_prog, (int)len, reps, (const uint8_t*)d_in, d_out);
   HIPCK(hipGetLastError());
-  if (d_out != t_out && (rc = copy_out(c, t_out, d_out, 576))) return rc;
+  if ((rc = stage_back(c, t_out, d_out, 576))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -3336,18 +3321,17 @@ int blsgpu_sign_batch(int sig_group, int scheme, const uint8_t* sks, const uint8
   if ((rc = stage_in(c, sks, 32 * n, &d_sks))) return rc;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
-  uint8_t* d_pks = is_device_ptr(out_pks) ? (uint8_t*)out_pks : (uint8_t*)arena_take(c, pkb);
-  uint8_t* d_sigs = is_device_ptr(out_sigs) ? (uint8_t*)out_sigs : (uint8_t*)arena_take(c, sgb);
+  uint8_t* d_pks = stage_out<uint8_t>(c, out_pks, pkb);
+  uint8_t* d_sigs = stage_out<uint8_t>(c, out_sigs, sgb);
   if (!d_pks || !d_sigs) return fail(BLSGPU_E_HIP, "internal: arena too small");
   dst_arg dst = scheme_dst(sig_group, scheme);
   int aug = scheme == BLSGPU_SCHEME_AUG;
-  if (sig_group == 1)
-    KL(KID_SIGN, k_sign<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_sks, aug, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, dst, d_pks, d_sigs);
-  else
-    KL(KID_SIGN, k_sign<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_sks, aug, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, dst, d_pks, d_sigs);
+  with_group(sig_group, [&](auto G) {
+    KL(KID_SIGN, k_sign<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_sks, aug, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, dst, d_pks, d_sigs);
+  });
   HIPCK(hipGetLastError());
-  if (d_pks != out_pks && (rc = copy_out(c, out_pks, d_pks, pkb))) return rc;
-  if (d_sigs != out_sigs && (rc = copy_out(c, out_sigs, d_sigs, sgb))) return rc;
+  if ((rc = stage_back(c, out_pks, d_pks, pkb))) return rc;
+  if ((rc = stage_back(c, out_sigs, d_sigs, sgb))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -3378,14 +3362,14 @@ int blsgpu_aggregate_partial(int sig_group, int scheme, const void* pks, const u
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * m, &d_offs))) return rc;
   // outputs may be device pointers (the sharded caller hands them to RCCL as they are): nothing crosses to the host then
-  uint8_t* d_rec = is_device_ptr(out_f12) ? (uint8_t*)out_f12 : (uint8_t*)arena_take(c, 576);
-  int64_t* d_first = is_device_ptr(first_bad) ? first_bad : (int64_t*)arena_take(c, 64);
+  uint8_t* d_rec = stage_out<uint8_t>(c, out_f12, 576);
+  int64_t* d_first = stage_out<int64_t>(c, first_bad, 64);
   if (!d_rec || !d_first) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if ((rc = aggregate_enqueue(c, sig_group, scheme, (const uint8_t*)d_pks, (const uint8_t*)d_sig, fmt, (const uint8_t*)d_msgs,
                               (const uint64_t*)d_offs, n, d_first, nullptr, d_rec)))
     return rc;
-  if (d_rec != out_f12 && (rc = copy_out(c, out_f12, d_rec, 576))) return rc;
-  if (d_first != first_bad && (rc = copy_out(c, first_bad, d_first, 8))) return rc;
+  if ((rc = stage_back(c, out_f12, d_rec, 576))) return rc;
+  if ((rc = stage_back(c, first_bad, d_first, 8))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }
@@ -3453,8 +3437,9 @@ int blsgpu_core_verify_hashed(int sig_group, const void* pks, const void* sigs, 
   uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
   uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
   if (!d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if (sig_group == 1) KL(KID_PREPARE, k_prepare_hashed<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, (const uint8_t*)d_h, d_pairs, d_status, 0);
-  else KL(KID_PREPARE, k_prepare_hashed<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, (const uint8_t*)d_h, d_pairs, d_status, 0);
+  with_group(sig_group, [&](auto G) {
+    KL(KID_PREPARE, k_prepare_hashed<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, (const uint8_t*)d_h, d_pairs, d_status, 0);
+  });
   if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0))) return rc;
   if ((rc = status_out_and_sync(c, status, d_status, n))) return rc;
   return 0;
@@ -3506,12 +3491,10 @@ int blsgpu_sig_proof_verify_batch(int sig_group, int scheme, const void* commitm
   uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
   if (!d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
   const dst_arg dst = scheme_dst(sig_group, scheme);
-  if (sig_group == 1)
-    KL(KID_PREPARE, k_prepare_proof<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, (const uint8_t*)d_v, (const uint8_t*)d_pks,
+  with_group(sig_group, [&](auto G) {
+    KL(KID_PREPARE, k_prepare_proof<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, (const uint8_t*)d_v, (const uint8_t*)d_pks,
        (const uint8_t*)d_ys, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, dst, d_pairs, d_status);
-  else
-    KL(KID_PREPARE, k_prepare_proof<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, (const uint8_t*)d_v, (const uint8_t*)d_pks,
-       (const uint8_t*)d_ys, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, dst, d_pairs, d_status);
+  });
   if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0))) return rc;
   if ((rc = status_out_and_sync(c, status, d_status, n))) return rc;
   return 0;
@@ -3529,7 +3512,7 @@ int blsgpu_pairing2_check_batch(const void* g1a, const void* g2a, const void* g1
   if (n == 0) return 0;
   if (!g1a || !g2a || !g1b || !g2b || !is_one) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  const size_t b1 = (fmt == BLSGPU_FMT_RAW_PROJ ? 144 : 96) * n, b2 = (fmt == BLSGPU_FMT_RAW_PROJ ? 288 : 192) * n;
+  const size_t b1 = point_bytes(1, fmt) * n, b2 = point_bytes(2, fmt) * n;
   size_t need = 2 * pad256(b1) + 2 * pad256(b2) + pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 4096;
   if ((rc = arena_reserve(c, need))) return rc;
   c->arena_off = 0;
@@ -3573,9 +3556,7 @@ int blsgpu_fp12_product_is_one(const void* f12s, size_t k, int32_t* is_one) try 
     SYNC_FLUSH(c);
   }
   int32_t one = verdict == BLSGPU_OK ? 1 : 0;
-  if (is_device_ptr(is_one)) HIPCK(hipMemcpy(is_one, &one, 4, hipMemcpyHostToDevice));
-  else *is_one = one;
-  return 0;
+  return put_i32(is_one, one);
 }
 API_CATCH
 
@@ -3603,7 +3584,7 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
   if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
   if (n && (!ids || !pts)) return fail(BLSGPU_E_ARG, "null argument");
   if (n_sets == 0) return 0;
-  const size_t psz = group == 1 ? g1_size(fmt) : g2_size(fmt), osz = group == 1 ? 144 : 288;
+  const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
   // plan: sets of at least BLSGPU_SHARES_MSM_MIN shares run as one bucket MSM each (k_msm2_*), all others as per-share ladders and a
   // segmented tree sum; the coefficients of a large set are split over S workgroups per tile range (k_share_lagrange)
   const uint64_t msm_min = (uint64_t)knobs().shares_msm_min;
@@ -3640,7 +3621,7 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
   uint32_t* d_nd = (uint32_t*)arena_take(c, 64 * S * n);
   uint8_t* d_part = (uint8_t*)arena_take(c, osz * n);
   uint32_t* d_flags = (uint32_t*)arena_take(c, 4 * n_sets);
-  uint8_t* d_out = is_device_ptr(out) ? (uint8_t*)out : (uint8_t*)arena_take(c, osz * n_sets);
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n_sets);
   int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
   if (!d_lam || !d_sid || !d_nd || !d_part || !d_flags || !d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if (tmax_msm) HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
@@ -3651,13 +3632,12 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
     KL(KID_SHARE_LAGRANGE, k_share_lagrange_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (int)S, o, (const uint8_t*)d_ids, (const uint8_t*)d_sch,
        (const uint32_t*)d_nd, (const uint32_t*)d_sid, d_flags, d_lam);
     if (tmax_ladder >= 2) {
-      if (group == 1) KL(KID_SHARE_LADDER, k_share_ladder<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_lam,
-                         (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
-      else KL(KID_SHARE_LADDER, k_share_ladder<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_lam,
-              (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      with_group(group, [&](auto G) {
+        KL(KID_SHARE_LADDER, k_share_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_lam,
+           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      });
       for (uint64_t step = 1; step < tmax_ladder; step <<= 1) {
-        if (group == 1) KL(KID_SHARE_FOLD, k_share_fold<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
-        else KL(KID_SHARE_FOLD, k_share_fold<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+        with_group(group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part); });
       }
     }
     // the large sets: one MSM each over the set's points and coefficients, its (Z = 1) result into the set's first record.  A failed
@@ -3670,15 +3650,15 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
       uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
       if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
       const uint8_t* sp = (const uint8_t*)d_pts + psz * lo;
-      if (group == 1) rc = run_point_sum<1>(c, sp, fmt, d_lam + 32 * lo, nullptr, t, d_msm, T);
-      else rc = run_point_sum<2>(c, sp, fmt, d_lam + 32 * lo, nullptr, t, d_msm, T);
+      rc = with_group(group, [&](auto G) { return run_point_sum<G()>(c, sp, fmt, d_lam + 32 * lo, nullptr, t, d_msm, T); });
       if (rc) return rc;
       HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
     }
   }
-  if (group == 1) KL(KID_SHARE_OUT, k_share_out<1>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
-  else KL(KID_SHARE_OUT, k_share_out<2>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
-  if (d_out != out && (rc = copy_out(c, out, d_out, osz * n_sets))) return rc;
+  with_group(group, [&](auto G) {
+    KL(KID_SHARE_OUT, k_share_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
+  });
+  if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
   return status_out_and_sync(c, status, d_st, n_sets);
 }
 API_CATCH
@@ -3722,8 +3702,8 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
     return blsgpu_verify_secure(sig_group, scheme, pks, n, sigs, msgs + moffs[0], (size_t)(moffs[1] - moffs[0]), ser_format, fmt, status);
   }
   CTX_ACQUIRE(c);
-  const int pk_group = sig_group == 1 ? 2 : 1;
-  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = sig_group == 1 ? 96 : 48, osz = sig_group == 1 ? 288 : 144;
+  const int pk_group = key_group(sig_group);
+  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
   std::vector<uint32_t> hflags(n_sets, 0);
   uint64_t tmax_small = 0, tmax_large = 0;
   for (size_t s = 0; s < n_sets; s++) {
@@ -3772,8 +3752,7 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
   const uint8_t* kp = (const uint8_t*)d_pks;
   if (n) {
     // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:42,47,272-275)
-    if (pk_group == 2) KL(KID_COMPRESS, k_compress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes);
-    else KL(KID_COMPRESS, k_compress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes);
+    with_group(pk_group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes); });
     if (tmax_small) {
       HIPCK(hipMemsetAsync(d_rank, 0, 4 * n, c->stream));
       if (width == 96)
@@ -3789,13 +3768,12 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
       KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_rank, (const uint32_t*)d_sid,
          (const uint8_t*)d_H, d_flags, d_scal);
       // aggregated_pk = sum t_i pk_i per set (reference :201-204): one joint NAF ladder per key, then a segmented tree sum
-      if (pk_group == 1) KL(KID_SHARE_LADDER, k_share_ladder<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, (const uint8_t*)d_scal,
-                            (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
-      else KL(KID_SHARE_LADDER, k_share_ladder<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, (const uint8_t*)d_scal,
-              (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      with_group(pk_group, [&](auto G) {
+        KL(KID_SHARE_LADDER, k_share_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, (const uint8_t*)d_scal,
+           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      });
       for (uint64_t step = 1; step < tmax_small; step <<= 1) {
-        if (pk_group == 1) KL(KID_SHARE_FOLD, k_share_fold<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
-        else KL(KID_SHARE_FOLD, k_share_fold<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+        with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part); });
       }
     }
     // the large sets, one at a time as blsgpu_verify_secure runs them: device sort, host SHA-256 of the sorted stream, the
@@ -3815,8 +3793,7 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
       keys_digest_host(c->hpin, width * t, H);
       HIPCK(hipMemcpy(d_H + 32 * s, H, 32, hipMemcpyHostToDevice));       // the stream is idle here (the sort synchronised)
       if ((rc = run_coefficients(c, d_H + 32 * s, w.perm_a, t, 0, t, 0, d_scal + 32 * lo, (int32_t*)(d_flags + s)))) return rc;
-      if (pk_group == 1) rc = run_point_sum<1>(c, kp + psz * lo, fmt, d_scal + 32 * lo, nullptr, t, d_msm, T);
-      else rc = run_point_sum<2>(c, kp + psz * lo, fmt, d_scal + 32 * lo, nullptr, t, d_msm, T);
+      rc = with_group(pk_group, [&](auto G) { return run_point_sum<G()>(c, kp + psz * lo, fmt, d_scal + 32 * lo, nullptr, t, d_msm, T); });
       if (rc) return rc;
       HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
     }
@@ -3824,12 +3801,10 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
   }
   // every set's signature as RAW_PROJ, its key, its status so far; then ONE verification tail over all sets (core_verify with the
   // scheme's DST and no key prefix, reference :236-246) that skips the sets already decided
-  if (sig_group == 1)
-    KL(KID_SECURE_OUT, k_secure_out<1>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, d_flags, (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt,
+  with_group(sig_group, [&](auto G) {
+    KL(KID_SECURE_OUT, k_secure_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, d_flags, (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt,
        d_sigp, d_apk, d_st);
-  else
-    KL(KID_SECURE_OUT, k_secure_out<2>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, d_flags, (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt,
-       d_sigp, d_apk, d_st);
+  });
   if ((rc = run_verify_items(c, sig_group, 0, d_apk, d_sigp, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msgs, (const uint64_t*)d_moffs, 0,
                              scheme_dst(sig_group, scheme), n_sets, d_pairs, d_f, d_st, 1)))
     return rc;

@@ -147,6 +147,25 @@ __device__ __noinline__ u32x8_t sha256_compress_v(u32x8_t hv, u32x16_t wv) {
   for (int i = 0; i < 8; i++) o[i] = h[i];
   return o;
 }
+// the pieces of a hash that a whole wave runs, one 64-byte block at a time (kernels.cuh expand_message_xmd_wave, tu_secure.inc
+// k_secure_digest): the initial state ...
+__device__ __forceinline__ u32x8_t sha256_iv() {
+  u32x8_t h;
+  h[0] = 0x6a09e667; h[1] = 0xbb67ae85; h[2] = 0x3c6ef372; h[3] = 0xa54ff53a;
+  h[4] = 0x510e527f; h[5] = 0x9b05688c; h[6] = 0x1f83d9ab; h[7] = 0x5be0cd19;
+  return h;
+}
+// ... and the block that the lanes wrote byte by byte (stream order) -> sixteen big-endian words on every lane
+__device__ __forceinline__ u32x16_t sha256_block_from_lds(uint8_t* blk) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  u32x16_t w;
+  const uint32_t* q = (const uint32_t*)blk;
+#pragma unroll
+  for (int j = 0; j < 16; j++) w[j] = __builtin_bswap32(q[j]);
+  __builtin_amdgcn_wave_barrier();
+  return w;
+}
 #endif
 struct sha_words {
   uint32_t h[8];

@@ -151,6 +151,32 @@ __device__ __forceinline__ void store_g2_pt(uint8_t* base, size_t i, const g2_ja
   fp2_to_raw(w + 24, p.y);
   fp2_to_raw(w + 48, p.z);
 }
+// ---- what a point's group implies, stated once (G = 1: G1 over Fp, G = 2: G2 over Fp2): the kernels that do the same on both
+// groups are written once over this trait
+template <int G>
+struct grp;
+template <>
+struct grp<1> {
+  typedef fp F;
+  typedef g1_jac jac_t;
+  typedef g1_aff aff_t;
+  enum { PROJ_BYTES = 144, COMP_BYTES = 48 };
+  __device__ static void load(g1_jac& p, const uint8_t* b, size_t i, int fmt) { load_g1_pt(p, b, i, fmt); }
+  __device__ static void store(uint8_t* b, size_t i, const g1_jac& p) { store_g1_pt(b, i, p); }
+  __device__ static void compress(uint8_t* out, const g1_aff& a, bool legacy) { g1_compress(out, a, legacy); }
+  __device__ static int decompress(g1_jac& p, const uint8_t* b, bool legacy) { return g1_decompress(p, b, legacy); }
+};
+template <>
+struct grp<2> {
+  typedef fp2 F;
+  typedef g2_jac jac_t;
+  typedef g2_aff aff_t;
+  enum { PROJ_BYTES = 288, COMP_BYTES = 96 };
+  __device__ static void load(g2_jac& p, const uint8_t* b, size_t i, int fmt) { load_g2_pt(p, b, i, fmt); }
+  __device__ static void store(uint8_t* b, size_t i, const g2_jac& p) { store_g2_pt(b, i, p); }
+  __device__ static void compress(uint8_t* out, const g2_aff& a, bool legacy) { g2_compress(out, a, legacy); }
+  __device__ static int decompress(g2_jac& p, const uint8_t* b, bool legacy) { return g2_decompress(p, b, legacy); }
+};
 
 // ---- lane-split G2 points (jac<hfp2>, tower_split.cuh): each lane of a pair converts and keeps its own component
 // (real / imaginary) of every coordinate of a caller-format point
@@ -930,38 +956,26 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_accumulate(size_t n, const uint8_
                                                         const uint32_t* perm, uint8_t* partials, size_t T) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
-  if (G == 1) {
-    g1_jac acc, p;
-    fp one;
-    fp_one(one);
-    jac_set_inf(acc);
-    for (size_t i = t; i < n; i += T) {
-      size_t src = perm ? perm[i] : i;
-      load_g1_pt(p, pts, src, fmt);
-      if (WITH_SCALARS) {
-        uint32_t k[8];
-        scalar_load_mod_r(k, scalars, i);
-        jac_mul_scalar(p, p, k);
-      }
-      if (!WITH_SCALARS && fp_eq(p.z, one)) jac_madd(acc, acc, p.x, p.y);     // Z = 1 (deserialised, RAW_AFF): the mixed addition
-      else jac_add(acc, acc, p);
+  typename grp<G>::jac_t acc, p;
+  jac_set_inf(acc);
+  for (size_t i = t; i < n; i += T) {
+    size_t src = perm ? perm[i] : i;
+    grp<G>::load(p, pts, src, fmt);
+    if (WITH_SCALARS) {
+      uint32_t k[8];
+      scalar_load_mod_r(k, scalars, i);
+      jac_mul_scalar(p, p, k);
     }
-    store_g1_pt(partials, t, acc);
-  } else {
-    g2_jac acc, p;
-    jac_set_inf(acc);
-    for (size_t i = t; i < n; i += T) {
-      size_t src = perm ? perm[i] : i;
-      load_g2_pt(p, pts, src, fmt);
-      if (WITH_SCALARS) {
-        uint32_t k[8];
-        scalar_load_mod_r(k, scalars, i);
-        jac_mul_scalar(p, p, k);
-      }
+    if constexpr (G == 1 && !WITH_SCALARS) {
+      fp one;
+      fp_one(one);
+      if (fp_eq(p.z, one)) jac_madd(acc, acc, p.x, p.y);     // Z = 1 (deserialised, RAW_AFF): the mixed addition
+      else jac_add(acc, acc, p);
+    } else {
       jac_add(acc, acc, p);
     }
-    store_g2_pt(partials, t, acc);
   }
+  grp<G>::store(partials, t, acc);
 }
 // The same for G2 without scalars on two lanes per accumulator (MultiPublicKey::from_public_keys over G2 keys).  A key that
 // comes from deserialisation has Z = 1 (so does every RAW_AFF input): it takes the mixed addition, 7M + 4S instead of 11M + 5S.
@@ -997,19 +1011,11 @@ template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_point_fold(size_t m, size_t half, uint8_t* partials) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i + half >= m || i >= half) return;
-  if (G == 1) {
-    g1_jac a, b;
-    load_g1_pt(a, partials, i, 0);
-    load_g1_pt(b, partials, i + half, 0);
-    jac_add_body(a, a, b);
-    store_g1_pt(partials, i, a);
-  } else {
-    g2_jac a, b;
-    load_g2_pt(a, partials, i, 0);
-    load_g2_pt(b, partials, i + half, 0);
-    jac_add_body(a, a, b);
-    store_g2_pt(partials, i, a);
-  }
+  typename grp<G>::jac_t a, b;
+  grp<G>::load(a, partials, i, 0);
+  grp<G>::load(b, partials, i + half, 0);
+  jac_add_body(a, a, b);
+  grp<G>::store(partials, i, a);
 }
 
 // grouped verification: the group's pair (sum_i r_i sig_i, -[c] g2) at slot c + 8 ng (the items' message points are uncleared:
@@ -1044,23 +1050,13 @@ template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_compress(size_t n, const uint8_t* pts, int fmt, int legacy, uint8_t* out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (G == 1) {
-    g1_jac p;
-    g1_aff a;
-    load_g1_pt(p, pts, i, fmt);
-    jac_to_aff(a, p);
-    uint8_t b[48];
-    g1_compress(b, a, legacy != 0);
-    for (int k = 0; k < 48; k++) out[i * 48 + k] = b[k];
-  } else {
-    g2_jac p;
-    g2_aff a;
-    load_g2_pt(p, pts, i, fmt);
-    jac_to_aff(a, p);
-    uint8_t b[96];
-    g2_compress(b, a, legacy != 0);
-    for (int k = 0; k < 96; k++) out[i * 96 + k] = b[k];
-  }
+  typename grp<G>::jac_t p;
+  typename grp<G>::aff_t a;
+  grp<G>::load(p, pts, i, fmt);
+  jac_to_aff(a, p);
+  uint8_t b[grp<G>::COMP_BYTES];
+  grp<G>::compress(b, a, legacy != 0);
+  for (int k = 0; k < grp<G>::COMP_BYTES; k++) out[i * grp<G>::COMP_BYTES + k] = b[k];
 }
 
 template __global__ void k_accumulate<1, 0>(size_t, const uint8_t*, int, const uint8_t*, const uint32_t*, uint8_t*, size_t);
@@ -2617,33 +2613,19 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_msm_fill(size_t n, const uint8_t*
 }
 #endif
 template <int G>
-struct msm_pt;
-template <>
-struct msm_pt<1> {
-  typedef g1_jac jac_t;
-  __device__ static void load(g1_jac& p, const uint8_t* b, size_t i, int fmt) { load_g1_pt(p, b, i, fmt); }
-  __device__ static void store(uint8_t* b, size_t i, const g1_jac& p) { store_g1_pt(b, i, p); }
-};
-template <>
-struct msm_pt<2> {
-  typedef g2_jac jac_t;
-  __device__ static void load(g2_jac& p, const uint8_t* b, size_t i, int fmt) { load_g2_pt(p, b, i, fmt); }
-  __device__ static void store(uint8_t* b, size_t i, const g2_jac& p) { store_g2_pt(b, i, p); }
-};
-template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_msm_bucket(size_t nb, const uint8_t* pts, int fmt, const uint32_t* perm, const uint32_t* cnt,
                                                         const uint32_t* off, const uint32_t* idx, uint8_t* sums) {
   size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= nb) return;
-  typename msm_pt<G>::jac_t acc, p;
+  typename grp<G>::jac_t acc, p;
   jac_set_inf(acc);
   const uint32_t n = cnt[b], o = off[b];
   for (uint32_t j = 0; j < n; j++) {
     uint32_t i = idx[o + j];
-    msm_pt<G>::load(p, pts, perm ? perm[i] : i, fmt);
+    grp<G>::load(p, pts, perm ? perm[i] : i, fmt);
     jac_add(acc, acc, p);
   }
-  msm_pt<G>::store(sums, b, acc);
+  grp<G>::store(sums, b, acc);
 }
 template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_msm_chunk(int c, int W, int clast, int CH, const uint8_t* sums, uint8_t* partials) {
@@ -2654,11 +2636,11 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_msm_chunk(int c, int W, int clast
   const int w = last ? W - 1 : (int)(t / cpw);
   const size_t lo = (last ? t - cpw * (W - 1) : t % cpw) * CH;
   const int wbits = last ? clast : c;
-  typename msm_pt<G>::jac_t run, acc, s;
+  typename grp<G>::jac_t run, acc, s;
   jac_set_inf(run);
   jac_set_inf(acc);
   for (int d = CH - 1; d >= 0; d--) {
-    msm_pt<G>::load(s, sums, ((size_t)w << c) + lo + d, 0);
+    grp<G>::load(s, sums, ((size_t)w << c) + lo + d, 0);
     jac_add(run, run, s);
     jac_add(acc, acc, run);   // acc = sum_d (d + 1) S_{lo + d}
   }
@@ -2675,18 +2657,18 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_msm_chunk(int c, int W, int clast
   }
   jac_add(acc, acc, s);
   for (int k = 0; k < c * w; k++) jac_dbl(acc, acc);   // weight 2^(c w)
-  msm_pt<G>::store(partials, t, acc);
+  grp<G>::store(partials, t, acc);
 }
 // Z = 1 (or the canonical identity) in place
 template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_normalize(uint8_t* pt) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  typename msm_pt<G>::jac_t p;
-  msm_pt<G>::load(p, pt, 0, 0);
+  typename grp<G>::jac_t p;
+  grp<G>::load(p, pt, 0, 0);
   if (jac_is_inf(p)) {
     jac_set_inf(p);
   } else {
-    decltype(p.x) zi, zi2;
+    typename grp<G>::F zi, zi2;
     fe_inv(zi, p.z);
     fe_sqr(zi2, zi);
     fe_mul(p.x, p.x, zi2);
@@ -2694,19 +2676,17 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_normalize(uint8_t* pt) {
     fe_mul(p.y, p.y, zi2);
     fe_one(p.z);
   }
-  msm_pt<G>::store(pt, 0, p);
+  grp<G>::store(pt, 0, p);
 }
 template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_decompress(size_t n, const uint8_t* bytes, int legacy, uint8_t* out, int32_t* status, int keep) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (keep && status[i] != BLS_OK) return;
-  typename msm_pt<G>::jac_t p;
-  int rc;
-  if (G == 1) rc = g1_decompress(*(g1_jac*)&p, bytes + 48 * i, legacy != 0);
-  else rc = g2_decompress(*(g2_jac*)&p, bytes + 96 * i, legacy != 0);
+  typename grp<G>::jac_t p;
+  const int rc = grp<G>::decompress(p, bytes + grp<G>::COMP_BYTES * i, legacy != 0);
   if (rc) jac_set_inf(p);
-  msm_pt<G>::store(out, i, p);
+  grp<G>::store(out, i, p);
   status[i] = rc;
 }
 
@@ -2722,47 +2702,7 @@ __device__ __forceinline__ void aff_ld_fp(fp& r, const uint32_t* e, int w0) {
 #pragma unroll
   for (int k = 0; k < FP_NL; k++) r.l[k] = (int32_t)e[w0 + k];
 }
-template <int G>
-__global__ void __launch_bounds__(BLS_BLOCK) k_msm2_prep(size_t n, const uint8_t* pts, int fmt, const uint32_t* perm, uint32_t* affws, uint8_t* inf) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const size_t src = perm ? perm[i] : i;
-  typename msm_pt<G>::jac_t p;
-  msm_pt<G>::load(p, pts, src, fmt);
-  const bool isinf = jac_is_inf(p);
-  inf[i] = isinf ? 1 : 0;
-  if (isinf) return;
-  uint32_t* e = affws + i * MSM2_E(G) * MSM2_AFF_WORDS(G);
-  if (G == 1) {
-    g1_aff a;
-    jac_to_aff(a, *(g1_jac*)&p);
-    fp qx[2], qy[2];
-    msm2_images_g1(qx, qy, a);
-    for (int j = 0; j < 2; j++) {
-      aff_st_fp(e + j * 2 * FP_NL, 0, qx[j]);
-      aff_st_fp(e + j * 2 * FP_NL, FP_NL, qy[j]);
-    }
-  } else {
-    g2_aff a;
-    jac_to_aff(a, *(g2_jac*)&p);
-    fp2 qx[4], qy[4];
-    msm2_images_g2(qx, qy, a);
-    for (int j = 0; j < 4; j++) {
-      uint32_t* q = e + j * 4 * FP_NL;
-      aff_st_fp(q, 0, qx[j].c0);
-      aff_st_fp(q, FP_NL, qx[j].c1);
-      aff_st_fp(q, 2 * FP_NL, qy[j].c0);
-      aff_st_fp(q, 3 * FP_NL, qy[j].c1);
-    }
-  }
-}
-// WEIGHTED TABLES (round 4; verify_secure only, where this runs while a host core still hashes the sorted key stream): for every key
-// the multiples 2^start(w) P of its windows w = 1 .. W - 1, affine, each with its endomorphism images -- entry ((i E + j) W + w) of
-// `tab` (entry w = 0: the images k_msm2_prep left).  A digit of window w then adds the ALREADY WEIGHTED point into its bucket, so the
-// chunk lanes -- the latency chain of the whole sum -- lose their start(w) doublings (up to 52 on G2, 116 on G1) and the windows' sums
-// are simply added.  Doubling commutes with the endomorphisms, so one chain of doublings per key serves all its images; the W - 1
-// Jacobian multiples wait in `jt` (X, Y, Z and the running product of the Z's, 4 coordinates per window) for ONE shared inversion.
-// Neither curve has a point of order two (both group orders are odd), so no multiple of a key is the identity and no Z vanishes.
+// one coordinate (Fp: FP_NL words, Fp2: c0 then c1)
 __device__ __forceinline__ void co_st(uint32_t* e, const fp& a) { aff_st_fp(e, 0, a); }
 __device__ __forceinline__ void co_st(uint32_t* e, const fp2& a) {
   aff_st_fp(e, 0, a.c0);
@@ -2773,12 +2713,46 @@ __device__ __forceinline__ void co_ld(fp2& r, const uint32_t* e) {
   aff_ld_fp(r.c0, e, 0);
   aff_ld_fp(r.c1, e, FP_NL);
 }
+// the E images of the affine point a (msm2.cuh) as workspace entries: image j goes to e + j * stride entries
+template <int G>
+__device__ __forceinline__ void msm2_store_images(uint32_t* e, size_t stride, const typename grp<G>::aff_t& a) {
+  constexpr int E = MSM2_E(G), AFFW = MSM2_AFF_WORDS(G), C = AFFW / 2;     // C: words per coordinate
+  typename grp<G>::F qx[E], qy[E];
+  if constexpr (G == 1) msm2_images_g1(qx, qy, a);
+  else msm2_images_g2(qx, qy, a);
+  for (int j = 0; j < E; j++) {
+    uint32_t* q = e + (size_t)j * stride * AFFW;
+    co_st(q, qx[j]);
+    co_st(q + C, qy[j]);
+  }
+}
+template <int G>
+__global__ void __launch_bounds__(BLS_BLOCK) k_msm2_prep(size_t n, const uint8_t* pts, int fmt, const uint32_t* perm, uint32_t* affws, uint8_t* inf) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t src = perm ? perm[i] : i;
+  typename grp<G>::jac_t p;
+  grp<G>::load(p, pts, src, fmt);
+  const bool isinf = jac_is_inf(p);
+  inf[i] = isinf ? 1 : 0;
+  if (isinf) return;
+  typename grp<G>::aff_t a;
+  jac_to_aff(a, p);
+  msm2_store_images<G>(affws + i * MSM2_E(G) * MSM2_AFF_WORDS(G), 1, a);
+}
+// WEIGHTED TABLES (round 4; verify_secure only, where this runs while a host core still hashes the sorted key stream): for every key
+// the multiples 2^start(w) P of its windows w = 1 .. W - 1, affine, each with its endomorphism images -- entry ((i E + j) W + w) of
+// `tab` (entry w = 0: the images k_msm2_prep left).  A digit of window w then adds the ALREADY WEIGHTED point into its bucket, so the
+// chunk lanes -- the latency chain of the whole sum -- lose their start(w) doublings (up to 52 on G2, 116 on G1) and the windows' sums
+// are simply added.  Doubling commutes with the endomorphisms, so one chain of doublings per key serves all its images; the W - 1
+// Jacobian multiples wait in `jt` (X, Y, Z and the running product of the Z's, 4 coordinates per window) for ONE shared inversion.
+// Neither curve has a point of order two (both group orders are odd), so no multiple of a key is the identity and no Z vanishes.
 template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_msm2_tables(size_t n, const uint32_t* affws, const uint8_t* inf, int W, uint32_t* tab, uint32_t* jt) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || inf[i]) return;
-  typedef typename msm_pt<G>::jac_t J;
-  typedef decltype(J().x) F;
+  typedef typename grp<G>::jac_t J;
+  typedef typename grp<G>::F F;
   constexpr int E = MSM2_E(G), AFFW = MSM2_AFF_WORDS(G), C = AFFW / 2;     // C: words per coordinate
   const msm2_layout L = msm2_make_layout(G == 1 ? 128 : 64, W);
   const uint32_t* e0 = affws + i * E * AFFW;
@@ -2822,33 +2796,11 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_msm2_tables(size_t n, const uint3
     fe_mul(t, t, zi);
     co_ld(y, r + C);
     fe_mul(y, y, t);
-    if (G == 1) {
-      g1_aff a;
-      a.x = *(fp*)&x;
-      a.y = *(fp*)&y;
-      a.inf = false;
-      fp qx[2], qy[2];
-      msm2_images_g1(qx, qy, a);
-      for (int j = 0; j < 2; j++) {
-        uint32_t* q = ti + ((size_t)j * W + w) * AFFW;
-        aff_st_fp(q, 0, qx[j]);
-        aff_st_fp(q, FP_NL, qy[j]);
-      }
-    } else {
-      g2_aff a;
-      a.x = *(fp2*)&x;
-      a.y = *(fp2*)&y;
-      a.inf = false;
-      fp2 qx[4], qy[4];
-      msm2_images_g2(qx, qy, a);
-      for (int j = 0; j < 4; j++) {
-        uint32_t* q = ti + ((size_t)j * W + w) * AFFW;
-        aff_st_fp(q, 0, qx[j].c0);
-        aff_st_fp(q, FP_NL, qx[j].c1);
-        aff_st_fp(q, 2 * FP_NL, qy[j].c0);
-        aff_st_fp(q, 3 * FP_NL, qy[j].c1);
-      }
-    }
+    typename grp<G>::aff_t a;
+    a.x = x;
+    a.y = y;
+    a.inf = false;
+    msm2_store_images<G>(ti + (size_t)w * AFFW, W, a);
   }
 }
 // scalar -> E sub-scalars (stored for k_msm2_fill) -> signed digits -> bucket sizes.  Bucket of digit magnitude m in
@@ -4013,25 +3965,6 @@ __device__ __noinline__ void jac_mul_u64_rows(jac<wf>& r, const jac<wf>& p, uint
 // the current 64-byte block straight from where it lives (zero pad, message, length / DST suffix, padding), the block meets in
 // LDS, and every lane runs the compression on registers (fully unrolled, the sixteen message words passed by value): ~5 us per
 // block, ~11 blocks.  All 64 lanes of the wave must call it; every lane returns the same words.
-typedef u32x8_t u32x8;      // (h2c.cuh: the compression with its operands by value, sha256_compress_v)
-typedef u32x16_t u32x16;
-__device__ __forceinline__ u32x8 sha256_iv() {
-  u32x8 h;
-  h[0] = 0x6a09e667; h[1] = 0xbb67ae85; h[2] = 0x3c6ef372; h[3] = 0xa54ff53a;
-  h[4] = 0x510e527f; h[5] = 0x9b05688c; h[6] = 0x1f83d9ab; h[7] = 0x5be0cd19;
-  return h;
-}
-// the block that the lanes wrote byte by byte (stream order) -> sixteen big-endian words on every lane
-__device__ __forceinline__ u32x16 sha256_block_from_lds(uint8_t* blk) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  u32x16 w;
-  const uint32_t* q = (const uint32_t*)blk;
-#pragma unroll
-  for (int j = 0; j < 16; j++) w[j] = __builtin_bswap32(q[j]);
-  __builtin_amdgcn_wave_barrier();
-  return w;
-}
 // out: NOUT / 4 big-endian words (word 0 = the first four bytes of the uniform bytes).  blk: 64 bytes of LDS owned by this wave.
 template <int NOUT>
 __device__ __forceinline__ void expand_message_xmd_wave(uint32_t* out, const uint8_t* m, uint32_t m_len, const dst_arg& dst, uint8_t* blk) {
@@ -4041,7 +3974,7 @@ __device__ __forceinline__ void expand_message_xmd_wave(uint32_t* out, const uin
   // the initial state is data-independent but is simply run (one block of eleven)
   const uint32_t total = 64 + m_len + 3 + dl + 1;
   const uint32_t nblk = (total + 9 + 63) >> 6;
-  u32x8 h = sha256_iv();
+  u32x8_t h = sha256_iv();
   for (uint32_t kb = 0; kb < nblk; kb++) {
     uint32_t pos = kb * 64 + L, byte = 0;
     if (pos >= 64 && pos < total) {
@@ -4064,13 +3997,13 @@ __device__ __forceinline__ void expand_message_xmd_wave(uint32_t* out, const uin
     blk[L] = (uint8_t)byte;
     h = sha256_compress_v(h, sha256_block_from_lds(blk));
   }
-  const u32x8 b0 = h;
-  u32x8 prev;
+  const u32x8_t b0 = h;
+  u32x8_t prev;
 #pragma unroll
   for (int j = 0; j < 8; j++) prev[j] = 0;
   const uint32_t total_i = 32 + 1 + dl + 1, nblk_i = (total_i + 9 + 63) >> 6;
   for (int bi = 1; bi <= NOUT / 32; bi++) {
-    u32x8 x;
+    u32x8_t x;
 #pragma unroll
     for (int j = 0; j < 8; j++) x[j] = b0[j] ^ prev[j];
     h = sha256_iv();

@@ -12,16 +12,6 @@
 #include "secure.cuh"
 
 #if BLS_TU_SECURE == 1
-// the set of key i: the last s with offs[s] <= i (empty sets share their offset with the next one and are skipped)
-__device__ __forceinline__ uint32_t secure_set_of(const uint64_t* offs, size_t n_sets, size_t i) {
-  size_t lo = 0, hi = n_sets - 1;
-  while (lo < hi) {
-    const size_t mid = (lo + hi + 1) >> 1;
-    if (offs[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return (uint32_t)lo;
-}
 // key o sorts before key m: its big-endian words are smaller, or they are equal and o comes first in the input (tie)
 template <int WPK>
 __device__ __forceinline__ bool secure_key_less(const uint32_t* o, const uint32_t (&m)[WPK], bool tie) {
@@ -51,7 +41,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_rank(size_t n, const uint6
   }
   __syncthreads();
   if (live) {
-    const uint32_t s = secure_set_of(offs, n_sets, i);
+    const uint32_t s = ragged_set_of(offs, n_sets, i);
     if (blockIdx.y == 0) sid[i] = s;
     live = !(flags[s] & SECURE_F_LARGE);
     lo = offs[s];
@@ -93,24 +83,6 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_gather(size_t n, size_t wi
   if (flags[s] & SECURE_F_LARGE) return;
   ((uint32_t*)sorted)[(offs[s] + rank[i]) * wpk + w] = ((const uint32_t*)kb)[t];
 }
-// the wave-wide SHA-256 pieces of kernels.cuh (sha256_iv, sha256_block_from_lds: defined in the row-wide engine's unit only)
-__device__ __forceinline__ u32x8_t secure_sha256_iv() {
-  u32x8_t h;
-  h[0] = 0x6a09e667; h[1] = 0xbb67ae85; h[2] = 0x3c6ef372; h[3] = 0xa54ff53a;
-  h[4] = 0x510e527f; h[5] = 0x9b05688c; h[6] = 0x1f83d9ab; h[7] = 0x5be0cd19;
-  return h;
-}
-// the block that the lanes wrote byte by byte (stream order) -> sixteen big-endian words on every lane
-__device__ __forceinline__ u32x16_t secure_block_from_lds(uint8_t* blk) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  u32x16_t w;
-  const uint32_t* q = (const uint32_t*)blk;
-#pragma unroll
-  for (int j = 0; j < 16; j++) w[j] = __builtin_bswap32(q[j]);
-  __builtin_amdgcn_wave_barrier();
-  return w;
-}
 // H_s = SHA-256(set s's sorted stream): one wave per set walks the stream block by block (the pieces of kernels.cuh expand_message_xmd_wave: lane
 // L fetches byte L of the block, the block meets in LDS, every lane runs the compression on registers).  Sequential within a
 // set, parallel across sets.  H leaves as 32 big-endian bytes.
@@ -126,7 +98,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_digest(size_t n_sets, size
   const uint8_t* m = sorted + lo * width;
   const uint64_t len = cnt * width, bits = len * 8;
   const uint64_t nblk = (len + 9 + 63) >> 6;
-  u32x8_t h = secure_sha256_iv();
+  u32x8_t h = sha256_iv();
   for (uint64_t b = 0; b < nblk; b++) {
     const uint64_t pos = b * 64 + L;
     uint32_t byte = 0;
@@ -134,7 +106,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_digest(size_t n_sets, size
     else if (pos == len) byte = 0x80;
     else if (b == nblk - 1 && L >= 56) byte = (uint32_t)(bits >> (8 * (63 - L))) & 255u;
     blk[L] = (uint8_t)byte;
-    h = sha256_compress_v(h, secure_block_from_lds(blk));
+    h = sha256_compress_v(h, sha256_block_from_lds(blk));
   }
   if (L < 8) {
     uint32_t v = 0;
@@ -143,7 +115,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_digest(size_t n_sets, size
     ((uint32_t*)(H + 32 * s))[L] = __builtin_bswap32(v);
   }
 }
-// k_sha256_coeff's hash, per set: the key's sorted position within its set and that set's H; the scalar goes to the key's INPUT
+// k_sha256_coeff's coefficient (sha256_coeff_mod_r), per set: the key's sorted position within its set and that set's H; the scalar goes to the key's INPUT
 // slot, so the key sum needs no permutation
 __global__ void __launch_bounds__(BLS_BLOCK) k_secure_coeff(size_t n, const uint32_t* rank, const uint32_t* sid, const uint8_t* H, uint32_t* flags,
                                                           uint8_t* scal) {
@@ -152,27 +124,13 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_coeff(size_t n, const uint
   const uint32_t s = sid[i];
   if (flags[s] & SECURE_F_LARGE) return;
   const uint32_t* hw = (const uint32_t*)(H + 32 * (size_t)s);
-  uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-  uint32_t w[16];
-  w[0] = rank[i];                                   // BE32(position)
+  uint32_t hb[8], v[8];
 #pragma unroll
-  for (int k = 0; k < 8; k++) w[1 + k] = __builtin_bswap32(hw[k]);
-  w[9] = 0x80000000u;
-#pragma unroll
-  for (int k = 10; k < 15; k++) w[k] = 0;
-  w[15] = 36 * 8;
-  sha256_compress(h, w);
-  uint32_t v[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) v[k] = h[7 - k];      // big-endian digest -> little-endian 32-bit words
-  u256_mod_r_le(v);
-  uint32_t nz = 0;
+  for (int k = 0; k < 8; k++) hb[k] = __builtin_bswap32(hw[k]);
+  const bool nz = sha256_coeff_mod_r(v, rank[i], hb);
   uint32_t* o = (uint32_t*)(scal + 32 * i);
 #pragma unroll
-  for (int k = 0; k < 8; k++) {
-    nz |= v[k];
-    o[k] = v[k];
-  }
+  for (int k = 0; k < 8; k++) o[k] = v[k];
   if (!nz) atomicOr(&flags[s], SECURE_F_ZERO);
 }
 // an empty set is Ok iff its signature is the identity (reference :189-195); the tail skipped it
@@ -186,22 +144,6 @@ template __global__ void k_secure_rank<24>(size_t, const uint64_t*, size_t, cons
 #endif
 
 #if BLS_TU_SECURE == 2
-template <int G>
-struct secure_pt;
-template <>
-struct secure_pt<1> {
-  typedef fp F;
-  enum { BYTES = 144 };
-  __device__ static void load(jac<F>& p, const uint8_t* b, size_t i, int fmt) { load_g1_pt(p, b, i, fmt); }
-  __device__ static void store(uint8_t* b, size_t i, const jac<F>& p) { store_g1_pt(b, i, p); }
-};
-template <>
-struct secure_pt<2> {
-  typedef fp2 F;
-  enum { BYTES = 288 };
-  __device__ static void load(jac<F>& p, const uint8_t* b, size_t i, int fmt) { load_g2_pt(p, b, i, fmt); }
-  __device__ static void store(uint8_t* b, size_t i, const jac<F>& p) { store_g2_pt(b, i, p); }
-};
 // SG: the signature group (the keys live in the other one).  part[offs[s]] holds set s's key sum (k_share_fold, or the large
 // set's MSM result copied there).  Status before the tail: INVALID_SIGNATURE stands in for an empty set (non-OK, so the tail
 // skips it; k_secure_fin decides), INVALID_COEFFICIENT comes before any verification (:97-100), OK lets the tail decide.
@@ -210,21 +152,21 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_out(size_t n_sets, const u
                                                         const uint8_t* sigs, int fmt, uint8_t* sig_proj, uint8_t* apk, int32_t* status) {
   const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_sets) return;
-  typedef secure_pt<SG> SP;
-  typedef secure_pt<3 - SG> KP;
-  jac<typename SP::F> sg;
+  typedef grp<SG> SP;
+  typedef grp<3 - SG> KP;
+  typename SP::jac_t sg;
   SP::load(sg, sigs, s, fmt);
   SP::store(sig_proj, s, sg);
   uint32_t f = flags[s];
   if (jac_is_inf(sg)) f |= SECURE_F_IDSIG;
   flags[s] = f;
   const uint64_t lo = offs[s], cnt = offs[s + 1] - lo;
-  uint32_t* w = (uint32_t*)(apk + s * KP::BYTES);
+  uint32_t* w = (uint32_t*)(apk + s * KP::PROJ_BYTES);
   if (cnt) {
-    const uint32_t* src = (const uint32_t*)(part + lo * KP::BYTES);
-    for (int k = 0; k < KP::BYTES / 4; k++) w[k] = src[k];
+    const uint32_t* src = (const uint32_t*)(part + lo * KP::PROJ_BYTES);
+    for (int k = 0; k < KP::PROJ_BYTES / 4; k++) w[k] = src[k];
   } else {
-    for (int k = 0; k < KP::BYTES / 4; k++) w[k] = 0u;
+    for (int k = 0; k < KP::PROJ_BYTES / 4; k++) w[k] = 0u;
   }
   status[s] = cnt == 0 ? BLS_ERR_INVALID_SIGNATURE : (f & SECURE_F_ZERO) ? BLS_ERR_INVALID_COEFFICIENT : BLS_OK;
 }

@@ -8,34 +8,7 @@
 #include "kernels.cuh"
 #include "shares.cuh"
 
-template <int G>
-struct share_pt;
-template <>
-struct share_pt<1> {
-  typedef fp F;
-  enum { BYTES = 144 };
-  __device__ static void load(jac<F>& p, const uint8_t* b, size_t i, int fmt) { load_g1_pt(p, b, i, fmt); }
-  __device__ static void store(uint8_t* b, size_t i, const jac<F>& p) { store_g1_pt(b, i, p); }
-};
-template <>
-struct share_pt<2> {
-  typedef fp2 F;
-  enum { BYTES = 288 };
-  __device__ static void load(jac<F>& p, const uint8_t* b, size_t i, int fmt) { load_g2_pt(p, b, i, fmt); }
-  __device__ static void store(uint8_t* b, size_t i, const jac<F>& p) { store_g2_pt(b, i, p); }
-};
-
 #if BLS_TU_SHARES == 1
-// the set of share i: the last s with offs[s] <= i (empty sets share their offset with the next one and are skipped)
-__device__ __forceinline__ uint32_t share_set_of(const uint64_t* offs, size_t n_sets, size_t i) {
-  size_t lo = 0, hi = n_sets - 1;
-  while (lo < hi) {
-    const size_t mid = (lo + hi + 1) >> 1;
-    if (offs[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return (uint32_t)lo;
-}
 // The lanes of a workgroup are consecutive shares of one or more sets, so the identifiers they need are ONE contiguous range
 // [offs[first set], offs[last set + 1]): the workgroup streams it through LDS in tiles of BLS_BLOCK identifiers (each converted to
 // Montgomery form once, by the lane that loads it), and every lane multiplies in those of its own set -- the n-body pattern:
@@ -47,7 +20,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_share_lagrange(size_t n, const ui
   __shared__ fr tile[BLS_BLOCK];
   const size_t b0 = (size_t)blockIdx.x * BLS_BLOCK, i = b0 + threadIdx.x, S = gridDim.y;
   const size_t blast = b0 + BLS_BLOCK - 1 < n ? b0 + BLS_BLOCK - 1 : n - 1;
-  const size_t range_lo = offs[share_set_of(offs, n_sets, b0)], range_hi = offs[share_set_of(offs, n_sets, blast) + 1];
+  const size_t range_lo = offs[ragged_set_of(offs, n_sets, b0)], range_hi = offs[ragged_set_of(offs, n_sets, blast) + 1];
   const bool live = i < n;
   uint32_t s = 0;
   size_t lo = 0, hi = 0;
@@ -55,7 +28,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_share_lagrange(size_t n, const ui
   share_lagrange L;
   share_lagrange_init(L);
   if (live) {
-    s = share_set_of(offs, n_sets, i);
+    s = ragged_set_of(offs, n_sets, i);
     lo = offs[s];
     hi = offs[s + 1];
     fr_to_mont(xi, (const uint32_t*)(ids + 32 * i));
@@ -117,18 +90,18 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_share_ladder(size_t n, const uint
                                                           const uint32_t* flags, uint8_t* part) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  typedef typename share_pt<G>::F F;
+  typedef typename grp<G>::F F;
   jac<F> p, acc;
   jac_set_inf(acc);
   if (!flags[sid[i]]) {            // a failed set's output is the identity, a large set runs as one MSM: no work here
-    share_pt<G>::load(p, pts, i, fmt);
+    grp<G>::load(p, pts, i, fmt);
     if (!jac_is_inf(p)) {
       aff<F> a;
       jac_to_aff(a, p);
       share_ladder<G>(acc, a, (const uint32_t*)(lam + 32 * i));
     }
   }
-  share_pt<G>::store(part, i, acc);
+  grp<G>::store(part, i, acc);
 }
 // level `step` (1, 2, 4, ...): the share at local index k (k a multiple of 2 step) adds in the one at k + step, if its set has it
 template <int G>
@@ -138,12 +111,12 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_share_fold(size_t n, uint64_t ste
   const uint32_t s = sid[i];
   const uint64_t k = i - offs[s];
   if ((k & (2 * step - 1)) != 0 || i + step >= offs[s + 1]) return;
-  typedef typename share_pt<G>::F F;
+  typedef typename grp<G>::F F;
   jac<F> a, b;
-  share_pt<G>::load(a, part, i, 0);
-  share_pt<G>::load(b, part, i + step, 0);
+  grp<G>::load(a, part, i, 0);
+  grp<G>::load(b, part, i + step, 0);
   jac_add(a, a, b);
-  share_pt<G>::store(part, i, a);
+  grp<G>::store(part, i, a);
 }
 template <int G>
 __global__ void __launch_bounds__(BLS_BLOCK) k_share_out(size_t n_sets, const uint64_t* offs, const uint32_t* flags, const uint8_t* part,
@@ -157,16 +130,16 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_share_out(size_t n_sets, const ui
   else if (f & SHARE_F_SCHEME) st = BLS_ERR_INVALID_SCHEME;
   else if ((f & SHARE_F_VSSS) || cnt < 2) st = BLS_ERR_VSSS;
   status[s] = st;
-  typedef typename share_pt<G>::F F;
+  typedef typename grp<G>::F F;
   jac<F> p;
   bool zero = st != BLS_OK;
   if (!zero) {
-    share_pt<G>::load(p, part, lo, 0);
+    grp<G>::load(p, part, lo, 0);
     zero = jac_is_inf(p);
   }
-  uint32_t* w = (uint32_t*)(out + s * share_pt<G>::BYTES);
+  uint32_t* w = (uint32_t*)(out + s * grp<G>::PROJ_BYTES);
   if (zero) {                      // the identity leaves as all-zero bytes: they depend on the group element only
-    for (int k = 0; k < share_pt<G>::BYTES / 4; k++) w[k] = 0;
+    for (int k = 0; k < grp<G>::PROJ_BYTES / 4; k++) w[k] = 0;
     return;
   }
   F zi, zi2;
@@ -176,7 +149,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_share_out(size_t n_sets, const ui
   fe_mul(zi2, zi2, zi);
   fe_mul(p.y, p.y, zi2);
   fe_one(p.z);
-  share_pt<G>::store(out, s, p);
+  grp<G>::store(out, s, p);
 }
 
 template __global__ void k_share_ladder<BLS_TU_SHARES>(size_t, const uint8_t*, int, const uint8_t*, const uint32_t*, const uint32_t*, uint8_t*);

@@ -42,7 +42,7 @@ __global__ void k_gather_rows(size_t cnt, const uint32_t* idx, const uint32_t* s
 __global__ void k_gather_ragged(size_t cnt, const uint32_t* idx, const uint64_t* offs_src, const uint64_t* offs_dst, const uint8_t* src, uint8_t* dst);
 __global__ void k_scatter_i32(size_t cnt, const uint32_t* idx, const int32_t* src, int32_t* dst);
 
-// v mod r for a 256-bit value v (little-endian words): k_sha256_coeff here, k_secure_coeff (tu_secure.inc)
+// v mod r for a 256-bit value v (little-endian words)
 __device__ __forceinline__ void u256_mod_r_le(uint32_t v[8]) {
   const uint32_t R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
   for (int round = 0; round < 5; round++) {   // 2^256 < 4.5 r
@@ -59,6 +59,37 @@ __device__ __forceinline__ void u256_mod_r_le(uint32_t v[8]) {
       for (int i = 0; i < 8; i++) v[i] = d[i];
     }
   }
+}
+// t = int_BE(SHA-256(BE32(pos) || H)) mod r (reference src/secure_aggregation.rs:61-100; the reduction is SURVEY 8a A9's
+// finding).  hw: H as eight big-endian words.  v: t as little-endian 32-bit words; returns whether t is non-zero
+__device__ __forceinline__ bool sha256_coeff_mod_r(uint32_t v[8], uint32_t pos, const uint32_t hw[8]) {
+  uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  uint32_t w[16];
+  w[0] = pos;                                       // BE32(pos): the word itself in SHA-256's big-endian word order
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[1 + k] = hw[k];
+  w[9] = 0x80000000u;
+#pragma unroll
+  for (int k = 10; k < 15; k++) w[k] = 0;
+  w[15] = 36 * 8;
+  sha256_compress(h, w);
+#pragma unroll
+  for (int k = 0; k < 8; k++) v[k] = h[7 - k];      // big-endian digest -> little-endian 32-bit words
+  u256_mod_r_le(v);
+  uint32_t nz = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) nz |= v[k];
+  return nz != 0;
+}
+// the set of item i of a ragged batch: the last s with offs[s] <= i (empty sets share their offset with the next one and are skipped)
+__device__ __forceinline__ uint32_t ragged_set_of(const uint64_t* offs, size_t n_sets, size_t i) {
+  size_t lo = 0, hi = n_sets - 1;
+  while (lo < hi) {
+    const size_t mid = (lo + hi + 1) >> 1;
+    if (offs[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return (uint32_t)lo;
 }
 #if defined(BLS_TU_UTIL)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -249,8 +280,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_run_first_index(size_t n, const u
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// t_p = int_BE(SHA-256(BE32(p) || H)) mod r for sorted position p (reference src/secure_aggregation.rs:61-100; the
-// reduction is SURVEY 8a A9's finding).  sorted_order != 0: out[p] = t_p.  Otherwise the scalar goes to the INPUT slot of
+// t_p = sha256_coeff_mod_r for sorted position p.  sorted_order != 0: out[p] = t_p.  Otherwise the scalar goes to the INPUT slot of
 // the key that sorted to p, restricted to the shard [base, base + count): out[perm[p] - base] = t_p.
 __global__ void __launch_bounds__(BLS_BLOCK) k_sha256_coeff(size_t n, const uint8_t* H, const uint32_t* perm, size_t base, size_t count,
                                                          int sorted_order, uint8_t* out_scalars, int32_t* zero_flag) {
@@ -262,27 +292,13 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_sha256_coeff(size_t n, const uint
     if (g < base || g >= base + count) return;
     slot = g - base;
   }
-  uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-  uint32_t w[16];
-  w[0] = (uint32_t)p;                               // BE32(i): the word itself in SHA-256's big-endian word order
+  uint32_t hw[8], v[8];
 #pragma unroll
-  for (int k = 0; k < 8; k++) w[1 + k] = ((uint32_t)H[4 * k] << 24) | ((uint32_t)H[4 * k + 1] << 16) | ((uint32_t)H[4 * k + 2] << 8) | H[4 * k + 3];
-  w[9] = 0x80000000u;
-#pragma unroll
-  for (int k = 10; k < 15; k++) w[k] = 0;
-  w[15] = 36 * 8;
-  sha256_compress(h, w);
-  uint32_t v[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) v[k] = h[7 - k];      // big-endian digest -> little-endian 32-bit words
-  u256_mod_r_le(v);
-  uint32_t nz = 0;
+  for (int k = 0; k < 8; k++) hw[k] = ((uint32_t)H[4 * k] << 24) | ((uint32_t)H[4 * k + 1] << 16) | ((uint32_t)H[4 * k + 2] << 8) | H[4 * k + 3];
+  const bool nz = sha256_coeff_mod_r(v, (uint32_t)p, hw);
   uint32_t* o = (uint32_t*)(out_scalars + 32 * slot);
 #pragma unroll
-  for (int k = 0; k < 8; k++) {
-    nz |= v[k];
-    o[k] = v[k];
-  }
+  for (int k = 0; k < 8; k++) o[k] = v[k];
   if (!nz) atomicOr((int*)zero_flag, 1);           // reference :97-100: a zero coefficient is InvalidCoefficient
 }
 
