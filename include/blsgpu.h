@@ -212,7 +212,9 @@ int blsgpu_verify_batch_grouped(int sig_group, int scheme, const void* pks, cons
  * (src/public_key.rs:58-74,158-171, src/signature.rs:231-253, src/impls/legacy.rs:39-82,100-126,144-170).
  * out: RAW_PROJ; status[i]: 0, BLSGPU_BAD_ENCODING or BLSGPU_LEGACY_FORMAT.  blsgpu_verify_batch also accepts
  * fmt = BLSGPU_FMT_COMPRESSED / BLSGPU_FMT_LEGACY directly (keys and signatures in the same format); a decode failure
- * becomes that item's status. */
+ * becomes that item's status.  The order per item is the one a caller who deserialises first would see: the key's decode
+ * status, then the signature's, and only for an item whose both decoded the identity checks (signature, then key) and the
+ * pairing -- so an infinity key beside an undecodable signature is that signature's BAD_ENCODING / LEGACY_FORMAT. */
 int blsgpu_deserialize(int group, const uint8_t* bytes, size_t n, int fmt_in, void* out, int32_t* status);
 
 /* Signature::<C>::try_from(&[u8]) and Vec<u8>::from(&Signature<C>) (src/signature.rs:112-126): the serde_bare form of the
