@@ -37,7 +37,7 @@ EXPORTS = [
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
     'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
-    'blsgpu_combine_shares', 'blsgpu_verify_secure_batch',
+    'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch',
 ]
 
 
@@ -153,6 +153,7 @@ def load_library(path=None):
         lib.blsgpu_signatures_to_tagged.argtypes = [ci, u8p, vp, sz, ci, u8p]
         lib.blsgpu_combine_shares.argtypes = [ci, u8p, vp, u8p, u64p, sz, ci, vp, i32p]
         lib.blsgpu_verify_secure_batch.argtypes = [ci, ci, vp, vp, sz, vp, vp, vp, ci, ci, vp]
+        lib.blsgpu_aggregate_verify_batch.argtypes = [ci, ci, vp, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
         _lib = lib
     return _lib
 
@@ -255,6 +256,28 @@ def aggregate_verify(sig_group, scheme, pks, msgs, sig, fmt=FMT_RAW_PROJ):
     _check(lib.blsgpu_aggregate_verify(sig_group, scheme, _ptr(pkb), _ptr(blob), ctypes.cast(offs, ctypes.c_void_p), len(pks), _ptr(sig), fmt,
                                        ctypes.byref(st), ctypes.cast(aux, ctypes.c_void_p)))
     return st.value, (aux[0], aux[1])
+
+
+def aggregate_verify_batch(sig_group, scheme, sets, fmt=FMT_RAW_PROJ):
+    """AggregateSignature::verify for many independent sets in one call (blsgpu_aggregate_verify_batch): `sets` is a list of
+    (pks, msgs, sig) with raw points in `fmt`.  Returns one (status, (aux0, aux1)) per set, each what aggregate_verify gives for
+    that set alone."""
+    lib = init()
+    n_sets = len(sets)
+    soffs = (ctypes.c_uint64 * (n_sets + 1))()
+    for s, (pks, msgs, _) in enumerate(sets):
+        if len(pks) != len(msgs):
+            raise ValueError('aggregate_verify_batch: set %d has %d keys and %d messages' % (s, len(pks), len(msgs)))
+        soffs[s + 1] = soffs[s] + len(pks)
+    pkb = b''.join(p for pks, _, _ in sets for p in pks)
+    moffs, mblob = _offsets([bytes(m) for _, msgs, _ in sets for m in msgs])
+    sgb = b''.join(sig for _, _, sig in sets)
+    stv = (ctypes.c_int32 * max(n_sets, 1))()
+    aux = (ctypes.c_uint64 * (2 * max(n_sets, 1)))()
+    _check(lib.blsgpu_aggregate_verify_batch(sig_group, scheme, _ptr(pkb), _ptr(mblob), ctypes.cast(moffs, ctypes.c_void_p),
+                                             ctypes.cast(soffs, ctypes.c_void_p), n_sets, _ptr(sgb), fmt, ctypes.cast(stv, ctypes.c_void_p),
+                                             ctypes.cast(aux, ctypes.c_void_p)))
+    return [(stv[s], (aux[2 * s], aux[2 * s + 1])) for s in range(n_sets)]
 
 
 def verify_secure(sig_group, scheme, pks, sig, msg, ser_format=MODERN, fmt=FMT_RAW_PROJ):
@@ -653,6 +676,17 @@ class TensorOps:
                                                    ser_format, FMT_RAW_PROJ, self._p(st)))
         return st[:n_sets]
 
+    def aggregate_verify_batch(self, sg, scheme, pks, msgs, msg_offs, set_offs, n_sets, sigs):
+        """(int32 statuses, int64 aux of shape (n_sets, 2)), both on the device, of n_sets aggregate_verify checks over
+        device-resident RAW_PROJ keys, one message per key (int64 offsets, one more entry than keys), the sets' int64 offsets into
+        the keys (n_sets + 1 entries) and one aggregate signature per set."""
+        self._sync()
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        aux = self.empty(2 * max(n_sets, 1), self.torch.int64)
+        _check(self.lib.blsgpu_aggregate_verify_batch(sg, scheme, self._p(pks), self._p(msgs), self._p(msg_offs), self._p(set_offs), n_sets,
+                                                      self._p(sigs), FMT_RAW_PROJ, self._p(st), self._p(aux)))
+        return st[:n_sets], aux[:2 * n_sets].view(n_sets, 2)
+
     def multi_verify(self, sg, scheme, pks, n, sig, msg):
         self._sync()
         st = ctypes.c_int32(-99)
@@ -771,6 +805,24 @@ def verify_secure_many(items, mode=MODERN):
         sts = verify_secure_batch(sg, scheme, [([p.raw for p in items[i][1]], items[i][0].raw, bytes(items[i][2])) for i in idx], mode)
         for i, st in zip(idx, sts):
             out[i] = error_from_status(st)
+    return out
+
+
+def aggregate_verify_many(items):
+    """AggregateSignature.verify over many items at once: `items` is a list of (AggregateSignature, [(PublicKey, msg)]) that
+    share one impl.  Items are grouped by scheme into at most three blsgpu_aggregate_verify_batch calls.  Returns one BlsError
+    (the one AggregateSignature.verify raises) or None per item, in order."""
+    if not items:
+        return []
+    sg = items[0][0].impl.sig_group
+    if any(sig.impl.sig_group != sg for sig, _ in items):
+        raise ValueError('aggregate_verify_many: every item must use the same impl')
+    out = [None] * len(items)
+    for scheme in sorted({sig.scheme for sig, _ in items}):
+        idx = [i for i, (sig, _) in enumerate(items) if sig.scheme == scheme]
+        res = aggregate_verify_batch(sg, scheme, [([p.raw for p, _ in items[i][1]], [bytes(m) for _, m in items[i][1]], items[i][0].raw) for i in idx])
+        for i, (st, aux) in zip(idx, res):
+            out[i] = error_from_status(st, aux, aggregate=True)
     return out
 
 

@@ -19,6 +19,7 @@
 #include "kernels.cuh"
 #include "shares.cuh"
 #include "secure.cuh"
+#include "agg_batch.cuh"
 #include "host_sha256.h"
 
 namespace {
@@ -36,13 +37,15 @@ enum {
   KID_TAIL,        // everything launched on a context's tail stream: runs BESIDE the main stream's kernels, so its time is not additive
   KID_SHARE_LAGRANGE, KID_SHARE_LADDER, KID_SHARE_FOLD, KID_SHARE_OUT,     // threshold recovery (blsgpu_combine_shares)
   KID_SECURE_RANK, KID_SECURE_GATHER, KID_SECURE_DIGEST, KID_SECURE_COEFF, KID_SECURE_OUT, KID_SECURE_FIN,   // blsgpu_verify_secure_batch
+  KID_AGG_SEG_INDEX, KID_AGG_SEG_FOLD, KID_AGG_SEG_FIN,   // blsgpu_aggregate_verify_batch (its prepare, Miller and final-exp kernels count under theirs)
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
                                     "k_finalexp_one", "k_hash_to_point", "k_accumulate", "k_point_fold", "k_compress", "k_sign", "k_f12_io", "k_msm_sort", "k_msm_bucket", "k_msm_chunk", "k_decompress", "k_pairing_coop", "k_key_sort", "k_sha256_coeff", "k_duplicate_rule", "k_first_identity", "k_msm_prep", "k_normalize", "k_msm_merge", "k_wide", "k_lines2s", "k_cyc_run4",
                                     "k_miller2s", "k_finalexps", "k_linesp", "k_linesp4", "k_line_quad", "k_f12_fold4", "k_f12_tree_seg", "k_f12_horner_wide", "k_millerfp", "k_pairing_post", "k_pairing_pre",
                                     "tail_stream_overlapped", "k_share_lagrange", "k_share_ladder", "k_share_fold", "k_share_out",
-                                    "k_secure_rank", "k_secure_gather", "k_secure_digest", "k_secure_coeff", "k_secure_out", "k_secure_fin"};
+                                    "k_secure_rank", "k_secure_gather", "k_secure_digest", "k_secure_coeff", "k_secure_out", "k_secure_fin",
+                                    "k_agg_seg_index", "k_f12_fold_seg", "k_agg_batch_fin"};
 
 struct Ctx {
   int dev = -1;
@@ -154,6 +157,7 @@ struct Knobs {
   long host_trace = 0, strict_env = 0, ab_knobs = 0;
   long shares_msm_min = 1024; // blsgpu_combine_shares: a set of at least this many shares is summed by the bucket MSM, not per-share ladders
   long secure_batch_max = 1024; // blsgpu_verify_secure_batch: a set of at least this many keys runs through blsgpu_verify_secure's machinery
+  long agg_batch_max = 32768;  // blsgpu_aggregate_verify_batch: a set of at least this many pairs runs through blsgpu_aggregate_verify's machinery
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
@@ -173,6 +177,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_STRICT_ENV", &Knobs::strict_env, 0, 1, false},             {"BLSGPU_AB_KNOBS", &Knobs::ab_knobs, 0, 1, false},
     {"BLSGPU_SHARES_MSM_MIN", &Knobs::shares_msm_min, 2, 1L << 32, false},
     {"BLSGPU_SECURE_BATCH_MAX", &Knobs::secure_batch_max, 1, 1L << 32, false},
+    {"BLSGPU_AGG_BATCH_MAX", &Knobs::agg_batch_max, 1, 1L << 32, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -3811,6 +3816,189 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
   KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, d_st);
   HIPCK(hipGetLastError());
   return status_out_and_sync(c, status, d_st, n_sets);
+}
+API_CATCH
+
+// ---- batched aggregate verify (agg_batch.cuh): n_sets independent AggregateSignature::verify checks in one call
+int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                  const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc) return rc;
+  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
+  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  // the set offsets decide every size of the call: read (and check) them on the host
+  std::vector<uint64_t> offs(n_sets + 1);
+  if (is_device_ptr(set_offsets)) HIPCK(hipMemcpy(offs.data(), set_offsets, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
+  else memcpy(offs.data(), set_offsets, 8 * (n_sets + 1));
+  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "set_offsets[0] must be 0");
+  for (size_t s = 0; s < n_sets; s++)
+    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "set_offsets must not decrease");
+  const size_t T = (size_t)offs[n_sets];
+  if (T >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more pairs in one call");
+  if (T && !pks) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  // plan: a set of at least BLSGPU_AGG_BATCH_MAX pairs runs one at a time through the kernels of blsgpu_aggregate_verify
+  // (aggregate_enqueue: its per-entry product form is what wins at tens of thousands of pairs), all others together through the
+  // segmented kernels of agg_batch.cuh.  One large set alone IS blsgpu_aggregate_verify (on one device: no sharding).
+  const uint64_t max_small = (uint64_t)knobs().agg_batch_max;
+  if (n_sets == 1 && T >= max_small) {
+    NestedScope ns;
+    return blsgpu_aggregate_verify(sig_group, scheme, pks, msgs, msg_offsets, T, sigs, fmt, status, aux);
+  }
+  CTX_ACQUIRE(c);
+  const bool basic = scheme == BLSGPU_SCHEME_BASIC;
+  uint64_t total = 0;
+  if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + T, 8, hipMemcpyDeviceToHost));
+  else total = msg_offsets[T];
+  if (total && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  // the batched sets as one flat list: boffs (their item ranges), bsrc (where a set's pairs start in the caller's arrays), bset (its index)
+  std::vector<uint64_t> boffs(1, 0), bsrc;
+  std::vector<uint32_t> bset;
+  std::vector<size_t> large;
+  uint64_t tmax_b = 0, tmax_large = 0;
+  for (size_t s = 0; s < n_sets; s++) {
+    const uint64_t t = offs[s + 1] - offs[s];
+    if (t >= max_small) {
+      large.push_back(s);
+      tmax_large = std::max(tmax_large, t);
+    } else {
+      bsrc.push_back(offs[s]);
+      bset.push_back((uint32_t)s);
+      boffs.push_back(boffs.back() + t);
+      tmax_b = std::max(tmax_b, t);
+    }
+  }
+  const size_t n_b = bset.size(), T_b = (size_t)boffs.back(), M = n_b ? T_b + n_b : 0;
+  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt);
+  size_t dup_cap = 64;
+  while (dup_cap < 2 * T_b) dup_cap <<= 1;
+  const bool dup_b = basic && T_b > 0;
+  // Miller values in rounds of at most one machine round of lane pairs (65,536 items), all of the same size; the final
+  // exponentiation in chunks of the same bound; both pass through the context's line workspace
+  const size_t round = 65536, n_rounds = (M + round - 1) / round, per_round = n_rounds ? ((M + n_rounds - 1) / n_rounds + 31) / 32 * 32 : 0;
+  const size_t fx_chunk = std::min(n_b, miller_chunk_items() ? miller_chunk_items() : round);
+  const size_t m_large = (size_t)tmax_large + 1;
+  const size_t large_bytes = large.empty() ? 0
+                                           : pad256(256 * large.size()) + pad256(4 * m_large) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * m_large) + 8192 +
+                                                 (basic ? dup_ws_bytes((size_t)tmax_large) : 0);
+  const size_t batch_bytes = n_b ? pad256(8 * (n_b + 1)) + pad256(8 * n_b) + pad256(4 * n_b) + pad256(4 * M) + 2 * pad256(4 * (T_b ? T_b : 1)) +
+                                       pad256((size_t)WS_PAIR1_WORDS * 4 * M) + pad256((size_t)WS_F_WORDS * 4 * M) + pad256((size_t)WS_F_WORDS * 4 * n_b) +
+                                       4 * pad256(4 * n_b) + (dup_b ? 2 * pad256(4 * dup_cap) + pad256(4 * T_b) : 0)
+                                 : 0;
+  rc = arena_reserve(c, pad256(psz * T) + pad256(ssz * n_sets) + pad256(total) + pad256(8 * (T + 1)) + pad256(4 * n_sets) + pad256(16 * n_sets) + batch_bytes +
+                            large_bytes + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_pks = nullptr, *d_sigs, *d_msgs, *d_moffs;
+  if (T && (rc = stage_in(c, pks, psz * T, &d_pks))) return rc;
+  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (T + 1), &d_moffs))) return rc;
+  int32_t* d_status = stage_out<int32_t>(c, status, 4 * n_sets);
+  uint64_t* d_aux = aux ? stage_out<uint64_t>(c, aux, 16 * n_sets) : nullptr;
+  if (!d_status || (aux && !d_aux)) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  const uint8_t* kp = (const uint8_t*)d_pks;
+  const uint8_t* sp = (const uint8_t*)d_sigs;
+  const uint8_t* mp = (const uint8_t*)d_msgs;
+  const uint64_t* mo = (const uint64_t*)d_moffs;
+  if (n_b) {
+    uint64_t* d_boffs = (uint64_t*)arena_take(c, 8 * (n_b + 1));
+    uint64_t* d_bsrc = (uint64_t*)arena_take(c, 8 * n_b);
+    uint32_t* d_bset = (uint32_t*)arena_take(c, 4 * n_b);
+    int32_t* d_bad = (int32_t*)arena_take(c, 4 * M);
+    uint32_t* d_sid = (uint32_t*)arena_take(c, 4 * (T_b ? T_b : 1));
+    uint32_t* d_src = (uint32_t*)arena_take(c, 4 * (T_b ? T_b : 1));
+    uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIR1_WORDS * 4 * M);
+    uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * M);
+    uint32_t* d_rec = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_b);
+    uint32_t* d_first = (uint32_t*)arena_take(c, 4 * n_b);
+    uint32_t* d_sigid = (uint32_t*)arena_take(c, 4 * n_b);
+    uint32_t* d_best = (uint32_t*)arena_take(c, 4 * n_b);
+    int32_t* d_stb = (int32_t*)arena_take(c, 4 * n_b);
+    uint32_t *d_tab = nullptr, *d_minidx = nullptr, *d_slot = nullptr;
+    if (dup_b) {
+      d_tab = (uint32_t*)arena_take(c, 4 * dup_cap);
+      d_minidx = (uint32_t*)arena_take(c, 4 * dup_cap);
+      d_slot = (uint32_t*)arena_take(c, 4 * T_b);
+    }
+    if (!d_boffs || !d_bsrc || !d_bset || !d_bad || !d_sid || !d_src || !d_pairs || !d_f || !d_rec || !d_first || !d_sigid || !d_best || !d_stb ||
+        (dup_b && (!d_tab || !d_minidx || !d_slot)))
+      return fail(BLSGPU_E_HIP, "internal: arena too small");
+    const size_t lanes_round = row_stride(lanes_for(per_round)), lanes_fx = row_stride(lanes_for(fx_chunk));
+    if (lines_reserve(c, std::max((size_t)MILLER_ENTRIES * LINE3_WORDS_H * 4 * lanes_round, (size_t)FX_STORE_WORDS * 4 * lanes_fx)))
+      return fail(BLSGPU_E_HIP, "no room for the line workspace");
+    HIPCK(hipMemcpyAsync(d_boffs, boffs.data(), 8 * (n_b + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(d_bsrc, bsrc.data(), 8 * n_b, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(d_bset, bset.data(), 4 * n_b, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemsetAsync(d_bad, 0, 4 * M, c->stream));
+    HIPCK(hipMemsetAsync(d_first, 0xff, 4 * n_b, c->stream));
+    HIPCK(hipMemsetAsync(d_best, 0xff, 4 * n_b, c->stream));
+    // 1. every item's hash, identity flag and affine pair (two lanes per item while that fits one machine round, as aggregate_enqueue)
+    const dst_arg dst = scheme_dst(sig_group, scheme);
+    const int aug = scheme == BLSGPU_SCHEME_AUG;
+    const int agg_lanes_env = (int)knobs().agg_lanes;
+    const int one_lane = agg_lanes_env == 1 || (agg_lanes_env != 2 && M > 65536 + 1024);
+    const int agg_flags = sig_group == 1 ? (one_lane ? 2 : 3) : 1;
+    const uint64_t* bo = d_boffs;
+    with_group(sig_group, [&](auto G) {
+      KL(KID_PREPARE_AGG, k_prepare_agg_seg<G()>, dim3(blocks_for((agg_flags & 1) ? 2 * M : M)), dim3(BLS_BLOCK), M, T_b, n_b, bo, (const uint64_t*)d_bsrc,
+         (const uint32_t*)d_bset, kp, sp, fmt, aug, mp, mo, dst, d_pairs, d_bad, d_sid, d_src, agg_flags);
+    });
+    // 2. one Miller value per item (a flagged item's is 1): no partial product spans two sets because none is formed.  k_miller1s
+    // multiplies items a fixed stride apart, which ragged sets cannot align with, so the remainder of a round takes the line kernels too.
+    for (size_t first = 0; first < M; first += per_round) {
+      const size_t cnt = std::min(per_round, M - first), nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
+      const dim3 grid((unsigned)(nlanes / BLS_BLOCK));
+      KL(KID_LINESP, k_linesp, grid, dim3(BLS_BLOCK), cnt, cnt, M, (const uint32_t*)(d_pairs + first), (const int32_t*)(d_bad + first), c->lines_ws, c->lines_ws,
+         lanes, (size_t)0, cnt, 1);
+      KL(KID_MILLERFP, k_millerfp3, grid, dim3(BLS_BLOCK), cnt, cnt, 1, (const int32_t*)(d_bad + first), (const uint32_t*)c->lines_ws, lanes, d_f + first, M, (size_t)0);
+    }
+    // 3. every set's product: ceil(log2(largest batched set)) halving rounds over all pair items, then times the signature's value
+    for (int r = 0, nr = agg_fold_rounds(tmax_b); r < nr; r++)
+      KL(KID_AGG_SEG_FOLD, k_f12_fold_seg, dim3(blocks_for(T_b)), dim3(BLS_BLOCK), T_b, r, (const uint32_t*)d_sid, bo, d_f, M);
+    KL(KID_AGG_SEG_FOLD, k_f12_fold_seg_out, dim3(blocks_for(n_b)), dim3(BLS_BLOCK), n_b, T_b, bo, (const uint32_t*)d_f, M, d_rec);
+    // 4., 5. the identity rules and Basic's duplicate rule, per set
+    KL(KID_AGG_SEG_INDEX, k_first_bad_seg, dim3(blocks_for(M)), dim3(BLS_BLOCK), M, T_b, (const uint32_t*)d_sid, bo, (const int32_t*)d_bad, d_first, d_sigid);
+    if (dup_b) {
+      HIPCK(hipMemsetAsync(d_tab, 0xff, 4 * dup_cap, c->stream));
+      HIPCK(hipMemsetAsync(d_minidx, 0xff, 4 * dup_cap, c->stream));
+      KL(KID_AGG_SEG_INDEX, k_dup_insert_seg, dim3(blocks_for(T_b)), dim3(BLS_BLOCK), T_b, mp, mo, (const uint32_t*)d_sid, (const uint32_t*)d_src,
+         (uint32_t)(dup_cap - 1), d_tab, d_minidx, d_slot);
+      KL(KID_AGG_SEG_INDEX, k_dup_find_seg, dim3(blocks_for(T_b)), dim3(BLS_BLOCK), T_b, (const uint32_t*)d_sid, bo, (const uint32_t*)d_slot,
+         (const uint32_t*)d_minidx, d_best);
+    }
+    const uint32_t* best = dup_b ? d_best : nullptr;
+    // 6. one final exponentiation per set the rules left open (k_finalexp2s, the batch form, whatever the number of sets)
+    KL(KID_AGG_SEG_FIN, k_agg_batch_mark, dim3(blocks_for(n_b)), dim3(BLS_BLOCK), n_b, bo, best, (const uint32_t*)d_slot, (const uint32_t*)d_minidx,
+       (const uint32_t*)d_first, (const uint32_t*)d_sigid, d_stb);
+    for (size_t first = 0; first < n_b; first += fx_chunk)
+      launch_finalexp_chunk(c, n_b, first, std::min(fx_chunk, n_b - first), d_rec, d_stb, knobs().finalexp_seg != 0);
+    // 7. the reference's precedence
+    KL(KID_AGG_SEG_FIN, k_agg_batch_fin, dim3(blocks_for(n_b)), dim3(BLS_BLOCK), n_b, bo, (const uint32_t*)d_bset, best, (const uint32_t*)d_slot,
+       (const uint32_t*)d_minidx, (const uint32_t*)d_first, (const uint32_t*)d_sigid, (const int32_t*)d_stb, d_status, d_aux);
+    HIPCK(hipGetLastError());
+  }
+  if (!large.empty()) {
+    // the large sets, one at a time as blsgpu_aggregate_verify runs them (the duplicate rule on the device: the messages are staged);
+    // the workspace is reused from set to set, the results of each stay in a record of their own
+    uint8_t* d_res = (uint8_t*)arena_take(c, 256 * large.size());
+    if (!d_res) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    const size_t mark = c->arena_off;
+    for (size_t k = 0; k < large.size(); k++) {
+      const size_t s = large[k], lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]);
+      c->arena_off = mark;
+      int64_t* d_first1 = (int64_t*)(d_res + 256 * k);
+      int32_t* d_verdict = (int32_t*)(d_res + 256 * k + 64);
+      uint64_t* d_dup = (uint64_t*)(d_res + 256 * k + 128);
+      if ((rc = aggregate_enqueue(c, sig_group, scheme, kp + psz * lo, sp + ssz * s, fmt, mp, mo + lo, t, d_first1, d_verdict, nullptr))) return rc;
+      if (basic && (rc = run_first_duplicate(c, mp, mo + lo, t, d_dup))) return rc;
+      KL(KID_AGG_SEG_FIN, k_agg_large_fin, dim3(1), dim3(BLS_BLOCK), t, (const int64_t*)d_first1, (const int32_t*)d_verdict,
+         basic ? (const uint64_t*)d_dup : nullptr, d_status + s, d_aux ? d_aux + 2 * s : nullptr);
+      HIPCK(hipGetLastError());
+    }
+  }
+  if (aux && (rc = stage_back(c, aux, d_aux, 16 * n_sets))) return rc;
+  return status_out_and_sync(c, status, d_status, n_sets);
 }
 API_CATCH
 }  // extern "C"

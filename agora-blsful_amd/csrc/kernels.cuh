@@ -578,54 +578,49 @@ template __global__ void k_prepare<2>(size_t, const uint8_t*, const uint8_t*, in
 
 
 
-#if defined(BLS_TU_AGG1) || defined(BLS_TU_AGG2)
+#if defined(BLS_TU_AGG1) || defined(BLS_TU_AGG2) || defined(BLS_TU_AGG_BATCH)
 // =====================================================================================================
 // aggregate verify / pairing product: one pair per item, then a product tree over the Fp12 values.
 // mode 0: (g1s[i], g2s[i]) given by the caller (pairing_product_is_one)
 // mode 1: aggregate verify: pk[i] + message i -> pair (H(m_i), pk_i) in the G1-first order of src/helpers.rs;
 //         item n (the extra lane) carries (sig, -g).  bad[i] = 1 when pk_i is the identity.
+// One item of such a workspace, shared by k_prepare_agg (one aggregate) and k_prepare_agg_seg (many, agg_batch.cuh): the pair goes
+// to `slot` of pairs (stride given), its identity flag to bad[slot].  is_sig: the signature's pair from point pt_i of pts; otherwise
+// key pt_i of pts with the message m.
+// two_lanes bit 0: as k_prepare (two adjacent lanes per item, the hash's two SSWU maps side by side; lane 0 stores; lane2 = which one, -1: one lane);
+// bit 1 (SG == 1): the hashes stay in E1(Fp), uncleared, and the signature's pair is (sig, -[c] g2) (verify.cuh g2_negc_gen)
 template <int SG>
-__global__ void __launch_bounds__(BLS_BLOCK, 2) k_prepare_agg(size_t n, const uint8_t* pks, const uint8_t* sig, int fmt, int aug,
-                                                         const uint8_t* msgs, const uint64_t* offs, dst_arg dst, uint32_t* pairs,
-                                                         int32_t* bad, int two_lanes, int has_sig) {
-  // two_lanes bit 0: as k_prepare (two adjacent lanes per item, the hash's two SSWU maps side by side; lane 0 stores);
-  // bit 1 (SG == 1): the hashes stay in E1(Fp), uncleared, and the signature's pair is (sig, -[c] g2) (verify.cuh g2_negc_gen)
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i = (two_lanes & 1) ? gid >> 1 : gid;
-  const int lane2 = (two_lanes & 1) ? (int)(gid & 1) : -1;
-  if (i > n || (i == n && !has_sig)) return;   // has_sig == 0: a shard without the signature pair (sig may be null)
-  const size_t stride = n + 1;
+__device__ __forceinline__ void prepare_agg_item(bool is_sig, const uint8_t* pts, size_t pt_i, int fmt, int aug, const uint8_t* m, uint32_t mlen,
+                                                 const dst_arg& dst, uint32_t* pairs, size_t stride, size_t slot, int32_t* bad, int two_lanes, int lane2) {
   g1_aff P;
   g2_aff Q;
-  if (i == n) {  // the signature pair
+  if (is_sig) {  // the signature pair
     if (SG == 1) {
       g1_jac s;
-      load_g1_pt(s, sig, 0, fmt);
+      load_g1_pt(s, pts, pt_i, fmt);
       const bool inf = jac_is_inf(s);
-      if (lane2 <= 0) bad[i] = inf ? 1 : 0;
+      if (lane2 <= 0) bad[slot] = inf ? 1 : 0;
       if (inf) return;
       jac_to_aff(P, s);
       if (two_lanes & 2) g2_negc_gen(Q);          // the pairs' message points are uncleared: (sig, -[c] g2) balances them
       else g2_neg_gen(Q);
     } else {
       g2_jac s;
-      load_g2_pt(s, sig, 0, fmt);
+      load_g2_pt(s, pts, pt_i, fmt);
       const bool inf = jac_is_inf(s);
-      if (lane2 <= 0) bad[i] = inf ? 1 : 0;
+      if (lane2 <= 0) bad[slot] = inf ? 1 : 0;
       if (inf) return;
       jac_to_aff(Q, s);
       g1_neg_gen(P);
     }
-    if (lane2 <= 0) ws_st_pair(pairs, stride, i, 0, P, Q);
+    if (lane2 <= 0) ws_st_pair(pairs, stride, slot, 0, P, Q);
     return;
   }
-  const uint8_t* m = msgs + offs[i];
-  uint32_t mlen = (uint32_t)(offs[i + 1] - offs[i]);
   if (SG == 1) {
     g2_jac pk;
-    load_g2_pt(pk, pks, i, fmt);
+    load_g2_pt(pk, pts, pt_i, fmt);
     const bool inf = jac_is_inf(pk);
-    if (lane2 <= 0) bad[i] = inf ? 1 : 0;
+    if (lane2 <= 0) bad[slot] = inf ? 1 : 0;
     if (inf) return;
     uint8_t pre[96];
     g1_jac h;
@@ -645,9 +640,9 @@ __global__ void __launch_bounds__(BLS_BLOCK, 2) k_prepare_agg(size_t n, const ui
     }
   } else {
     g1_jac pk;
-    load_g1_pt(pk, pks, i, fmt);
+    load_g1_pt(pk, pts, pt_i, fmt);
     const bool inf = jac_is_inf(pk);
-    if (lane2 <= 0) bad[i] = inf ? 1 : 0;
+    if (lane2 <= 0) bad[slot] = inf ? 1 : 0;
     if (inf) return;
     uint8_t pre[48];
     g2_jac h;
@@ -666,7 +661,22 @@ __global__ void __launch_bounds__(BLS_BLOCK, 2) k_prepare_agg(size_t n, const ui
       }
     }
   }
-  if (lane2 <= 0) ws_st_pair(pairs, stride, i, 0, P, Q);
+  if (lane2 <= 0) ws_st_pair(pairs, stride, slot, 0, P, Q);
+}
+#endif
+
+#if defined(BLS_TU_AGG1) || defined(BLS_TU_AGG2)
+template <int SG>
+__global__ void __launch_bounds__(BLS_BLOCK, 2) k_prepare_agg(size_t n, const uint8_t* pks, const uint8_t* sig, int fmt, int aug,
+                                                         const uint8_t* msgs, const uint64_t* offs, dst_arg dst, uint32_t* pairs,
+                                                         int32_t* bad, int two_lanes, int has_sig) {
+  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = (two_lanes & 1) ? gid >> 1 : gid;
+  const int lane2 = (two_lanes & 1) ? (int)(gid & 1) : -1;
+  if (i > n || (i == n && !has_sig)) return;   // has_sig == 0: a shard without the signature pair (sig may be null)
+  // the workspace stride is n + 1: item n (the extra lane) is the signature's
+  if (i == n) prepare_agg_item<SG>(true, sig, 0, fmt, aug, nullptr, 0, dst, pairs, n + 1, i, bad, two_lanes, lane2);
+  else prepare_agg_item<SG>(false, pks, i, fmt, aug, msgs + offs[i], (uint32_t)(offs[i + 1] - offs[i]), dst, pairs, n + 1, i, bad, two_lanes, lane2);
 }
 
 #if defined(BLS_TU_AGG1)

@@ -342,6 +342,26 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
                                const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt,
                                int32_t* status);
 
+/* Batched aggregate verify: AggregateSignature::verify (src/aggregate_signature.rs:230-239) for n_sets independent
+ * (keys, messages, aggregate signature) sets in one call.
+ * set_offsets: n_sets + 1 entries; set s owns pairs set_offsets[s] .. set_offsets[s + 1] of pks / msg_offsets (it starts at 0
+ *     and never decreases; anything else is BLSGPU_E_ARG).  The total pair count T = set_offsets[n_sets] must be below 2^32.
+ * msgs / msg_offsets: one message per pair (msg_offsets: T + 1 entries).  sigs: one aggregate signature per set.
+ * fmt: BLSGPU_FMT_RAW_PROJ or BLSGPU_FMT_RAW_AFFINE points.  status: n_sets entries.  aux: NULL, or 2 n_sets entries.
+ * status[s], aux[2 s], aux[2 s + 1] equal what blsgpu_aggregate_verify returns for set s alone, indices local to the set:
+ *     Basic only: the first pair i whose message equals an earlier one OF THE SAME SET is BLSGPU_DUPLICATE_MESSAGE, aux =
+ *     (earlier index, i), 0-based (src/traits/sig_basic.rs:46-58); then an identity signature is BLSGPU_SIG_IDENTITY, the
+ *     first identity key BLSGPU_PK_IDENTITY with aux[2 s] = its 1-based index (src/traits/sig_core.rs:155-167); then the
+ *     pairing product gives BLSGPU_OK or BLSGPU_INVALID_SIGNATURE.  aux is (0, 0) otherwise.  An empty set with a
+ *     non-identity signature is BLSGPU_INVALID_SIGNATURE.
+ * Sets below BLSGPU_AGG_BATCH_MAX pairs are hashed, paired, multiplied and exponentiated together on the device; larger ones
+ *     run one at a time through blsgpu_aggregate_verify's kernels.  The knob changes the plan, never a status.
+ * Every pointer may be host or device memory; a device `status` / `aux` stays on the device.  n_sets == 0 returns 0.  The
+ *     call runs on one device even when several are bound (whole sets are not sharded over devices). */
+int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                  const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status,
+                                  uint64_t* aux);
+
 #ifdef __cplusplus
 }
 #endif
