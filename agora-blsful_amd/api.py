@@ -37,7 +37,7 @@ EXPORTS = [
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
     'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
-    'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch',
+    'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
 ]
 
 
@@ -154,6 +154,7 @@ def load_library(path=None):
         lib.blsgpu_combine_shares.argtypes = [ci, u8p, vp, u8p, u64p, sz, ci, vp, i32p]
         lib.blsgpu_verify_secure_batch.argtypes = [ci, ci, vp, vp, sz, vp, vp, vp, ci, ci, vp]
         lib.blsgpu_aggregate_verify_batch.argtypes = [ci, ci, vp, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
+        lib.blsgpu_multi_verify_batch.argtypes = [ci, ci, vp, vp, sz, vp, vp, vp, ci, vp]
         _lib = lib
     return _lib
 
@@ -245,6 +246,23 @@ def multi_verify(sig_group, scheme, pks, sig, msg, fmt=FMT_RAW_PROJ):
     pkb = b''.join(pks)
     _check(lib.blsgpu_multi_verify(sig_group, scheme, _ptr(pkb), len(pks), _ptr(sig), _ptr(msg), len(msg), fmt, ctypes.byref(st)))
     return st.value
+
+
+def multi_verify_batch(sig_group, scheme, sets, fmt=FMT_RAW_PROJ):
+    """MultiSignature::verify for many independent sets in one call (blsgpu_multi_verify_batch): `sets` is a list of
+    (pks, sig, msg) with raw points in `fmt`.  Returns one status per set, each what multi_verify gives for that set alone."""
+    lib = init()
+    n_sets = len(sets)
+    koffs = (ctypes.c_uint64 * (n_sets + 1))()
+    for s, (pks, _, _) in enumerate(sets):
+        koffs[s + 1] = koffs[s] + len(pks)
+    pkb = b''.join(p for pks, _, _ in sets for p in pks)
+    moffs, mblob = _offsets([bytes(m) for _, _, m in sets])
+    sgb = b''.join(sig for _, sig, _ in sets)
+    stv = (ctypes.c_int32 * max(n_sets, 1))()
+    _check(lib.blsgpu_multi_verify_batch(sig_group, scheme, _ptr(pkb), ctypes.cast(koffs, ctypes.c_void_p), n_sets, _ptr(sgb), _ptr(mblob),
+                                         ctypes.cast(moffs, ctypes.c_void_p), fmt, ctypes.cast(stv, ctypes.c_void_p)))
+    return list(stv)[:n_sets]
 
 
 def aggregate_verify(sig_group, scheme, pks, msgs, sig, fmt=FMT_RAW_PROJ):
@@ -687,6 +705,15 @@ class TensorOps:
                                                       self._p(sigs), FMT_RAW_PROJ, self._p(st), self._p(aux)))
         return st[:n_sets], aux[:2 * n_sets].view(n_sets, 2)
 
+    def multi_verify_batch(self, sg, scheme, pks, key_offs, sigs, msgs, msg_offs, n_sets):
+        """int32 statuses (on the device) of n_sets MultiSignature::verify checks over device-resident RAW_PROJ keys, their int64
+        offsets (n_sets + 1 entries), one signature and one message per set."""
+        self._sync()
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        _check(self.lib.blsgpu_multi_verify_batch(sg, scheme, self._p(pks), self._p(key_offs), n_sets, self._p(sigs), self._p(msgs), self._p(msg_offs),
+                                                  FMT_RAW_PROJ, self._p(st)))
+        return st[:n_sets]
+
     def multi_verify(self, sg, scheme, pks, n, sig, msg):
         self._sync()
         st = ctypes.c_int32(-99)
@@ -803,6 +830,24 @@ def verify_secure_many(items, mode=MODERN):
     for scheme in sorted({sig.scheme for sig, _, _ in items}):
         idx = [i for i, (sig, _, _) in enumerate(items) if sig.scheme == scheme]
         sts = verify_secure_batch(sg, scheme, [([p.raw for p in items[i][1]], items[i][0].raw, bytes(items[i][2])) for i in idx], mode)
+        for i, st in zip(idx, sts):
+            out[i] = error_from_status(st)
+    return out
+
+
+def multi_verify_many(items):
+    """MultiSignature.verify over many items at once: `items` is a list of (MultiSignature, MultiPublicKey, msg) that share one
+    impl.  Items are grouped by scheme into at most three blsgpu_multi_verify_batch calls.  Returns one BlsError or None per
+    item, in order."""
+    if not items:
+        return []
+    sg = items[0][0].impl.sig_group
+    if any(sig.impl.sig_group != sg or mpk.impl.sig_group != sg for sig, mpk, _ in items):
+        raise ValueError('multi_verify_many: every item must use the same impl')
+    out = [None] * len(items)
+    for scheme in sorted({sig.scheme for sig, _, _ in items}):
+        idx = [i for i, (sig, _, _) in enumerate(items) if sig.scheme == scheme]
+        sts = multi_verify_batch(sg, scheme, [([k.raw for k in items[i][1].keys], items[i][0].raw, bytes(items[i][2])) for i in idx])
         for i, st in zip(idx, sts):
             out[i] = error_from_status(st)
     return out

@@ -20,6 +20,7 @@
 #include "shares.cuh"
 #include "secure.cuh"
 #include "agg_batch.cuh"
+#include "multi_batch.cuh"
 #include "host_sha256.h"
 
 namespace {
@@ -38,6 +39,7 @@ enum {
   KID_SHARE_LAGRANGE, KID_SHARE_LADDER, KID_SHARE_FOLD, KID_SHARE_OUT,     // threshold recovery (blsgpu_combine_shares)
   KID_SECURE_RANK, KID_SECURE_GATHER, KID_SECURE_DIGEST, KID_SECURE_COEFF, KID_SECURE_OUT, KID_SECURE_FIN,   // blsgpu_verify_secure_batch
   KID_AGG_SEG_INDEX, KID_AGG_SEG_FOLD, KID_AGG_SEG_FIN,   // blsgpu_aggregate_verify_batch (its prepare, Miller and final-exp kernels count under theirs)
+  KID_MULTI_SEG_ACCUM, KID_MULTI_OUT,                     // blsgpu_multi_verify_batch (its fold counts under KID_SHARE_FOLD)
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
@@ -45,7 +47,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_miller2s", "k_finalexps", "k_linesp", "k_linesp4", "k_line_quad", "k_f12_fold4", "k_f12_tree_seg", "k_f12_horner_wide", "k_millerfp", "k_pairing_post", "k_pairing_pre",
                                     "tail_stream_overlapped", "k_share_lagrange", "k_share_ladder", "k_share_fold", "k_share_out",
                                     "k_secure_rank", "k_secure_gather", "k_secure_digest", "k_secure_coeff", "k_secure_out", "k_secure_fin",
-                                    "k_agg_seg_index", "k_f12_fold_seg", "k_agg_batch_fin"};
+                                    "k_agg_seg_index", "k_f12_fold_seg", "k_agg_batch_fin",
+                                    "k_multi_accumulate_seg", "k_multi_out"};
 
 struct Ctx {
   int dev = -1;
@@ -158,6 +161,7 @@ struct Knobs {
   long shares_msm_min = 1024; // blsgpu_combine_shares: a set of at least this many shares is summed by the bucket MSM, not per-share ladders
   long secure_batch_max = 1024; // blsgpu_verify_secure_batch: a set of at least this many keys runs through blsgpu_verify_secure's machinery
   long agg_batch_max = 32768;  // blsgpu_aggregate_verify_batch: a set of at least this many pairs runs through blsgpu_aggregate_verify's machinery
+  long multi_strip = 0;        // blsgpu_multi_verify_batch: keys per strip of the segmented key sum (0: one strip per lane of a single sum, at least 4)
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
@@ -178,6 +182,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_SHARES_MSM_MIN", &Knobs::shares_msm_min, 2, 1L << 32, false},
     {"BLSGPU_SECURE_BATCH_MAX", &Knobs::secure_batch_max, 1, 1L << 32, false},
     {"BLSGPU_AGG_BATCH_MAX", &Knobs::agg_batch_max, 1, 1L << 32, false},
+    {"BLSGPU_MULTI_STRIP", &Knobs::multi_strip, 0, 1L << 32, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -3999,6 +4004,94 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
   }
   if (aux && (rc = stage_back(c, aux, d_aux, 16 * n_sets))) return rc;
   return status_out_and_sync(c, status, d_status, n_sets);
+}
+API_CATCH
+
+// ---- batched multi verify (multi_batch.cuh): n_sets independent MultiSignature::verify checks in one call
+int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
+                              const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc) return rc;
+  if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
+  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  // the offsets decide every size of the call: read (and check) them on the host
+  auto read_offsets = [&](const uint64_t* src, std::vector<uint64_t>& dst) -> int {
+    dst.resize(n_sets + 1);
+    if (is_device_ptr(src)) HIPCK(hipMemcpy(dst.data(), src, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
+    else memcpy(dst.data(), src, 8 * (n_sets + 1));
+    return 0;
+  };
+  std::vector<uint64_t> offs, moffs;
+  if ((rc = read_offsets(key_offsets, offs))) return rc;
+  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "key_offsets[0] must be 0");
+  for (size_t s = 0; s < n_sets; s++)
+    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "key_offsets must not decrease");
+  const size_t n = (size_t)offs[n_sets];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
+  if (n && !pks) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  if ((rc = read_offsets(msg_offsets, moffs))) return rc;
+  for (size_t s = 0; s < n_sets; s++)
+    if (moffs[s + 1] < moffs[s]) return fail(BLSGPU_E_ARG, "msg_offsets must not decrease");
+  if (moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  // one set alone IS blsgpu_multi_verify: its split over the bound devices and its cut tail serve one huge set
+  if (n_sets == 1) return blsgpu_multi_verify(sig_group, scheme, pks, n, sigs, msgs + moffs[0], (size_t)(moffs[1] - moffs[0]), fmt, status);
+  // plan: the strips of the segmented key sum (multi_batch.cuh)
+  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
+  std::vector<uint64_t> soffs;
+  std::vector<uint32_t> ssid;
+  const uint64_t qmax = multi_strip_plan(offs.data(), n_sets, L, soffs, ssid);
+  const size_t Q = ssid.size();
+  CTX_ACQUIRE(c);
+  const int pk_group = key_group(sig_group);
+  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
+  const size_t mtotal = (size_t)moffs[n_sets];
+  rc = arena_reserve(c, pad256(psz * n) + pad256(ssz * n_sets) + pad256(mtotal) + 3 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) +
+                            2 * pad256(288 * n_sets) + pad256(4 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) +
+                            pad256((size_t)WS_F_WORDS * 4 * n_sets) + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_pks = nullptr, *d_sigs, *d_msgs, *d_moffs;
+  if (n && (rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
+  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
+  uint64_t* d_offs = (uint64_t*)arena_take(c, 8 * (n_sets + 1));
+  uint64_t* d_soffs = (uint64_t*)arena_take(c, 8 * (n_sets + 1));
+  uint32_t* d_ssid = (uint32_t*)arena_take(c, 4 * Q);
+  uint8_t* d_part = (uint8_t*)arena_take(c, osz * Q);
+  int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
+  uint8_t* d_sigp = (uint8_t*)arena_take(c, 288 * n_sets);
+  uint8_t* d_apk = (uint8_t*)arena_take(c, 288 * n_sets);
+  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n_sets);
+  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_sets);
+  if (!d_offs || !d_soffs || !d_ssid || !d_part || !d_st || !d_sigp || !d_apk || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemcpyAsync(d_offs, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCK(hipMemcpyAsync(d_soffs, soffs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
+  if (Q) {
+    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
+    // MultiPublicKey::from_public_keys per set: the serial `g += key` of reference src/traits/pk_multi.rs:7-13 as one strip sum per
+    // lane (lane pair for G2 keys), then a segmented pairwise tree over every set's strips
+    const uint8_t* kp = (const uint8_t*)d_pks;
+    const uint64_t *o = d_offs, *so = d_soffs;
+    const uint32_t* sid = d_ssid;
+    with_group(pk_group, [&](auto G) {
+      KL(KID_MULTI_SEG_ACCUM, k_multi_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, kp, fmt, o, so, sid, d_part);
+    });
+    for (uint64_t step = 1; step < qmax; step <<= 1)
+      with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
+  }
+  // every set's signature as RAW_PROJ and its key; then ONE verification tail over all sets: core_verify with the scheme's DST,
+  // under MessageAugmentation with the summed key's bytes in front of the message (reference src/traits/sig_aug.rs:20-24)
+  with_group(sig_group, [&](auto G) {
+    KL(KID_MULTI_OUT, k_multi_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const uint64_t*)d_offs, (const uint64_t*)d_soffs,
+       (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt, d_sigp, d_apk, d_st);
+  });
+  if ((rc = run_verify_items(c, sig_group, scheme == BLSGPU_SCHEME_AUG, d_apk, d_sigp, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msgs,
+                             (const uint64_t*)d_moffs, 0, scheme_dst(sig_group, scheme), n_sets, d_pairs, d_f, d_st, 1)))
+    return rc;
+  HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, d_st, n_sets);
 }
 API_CATCH
 }  // extern "C"

@@ -113,6 +113,12 @@ BLS_FN void share_ladder(jac<F>& acc, const aff<F>& p, const uint32_t lam[8]) {
   }
 }
 
+// level `step` (1, 2, 4, ...) of the segmented pairwise tree over the records [lo, hi) of one set: does record i add in record
+// i + step?  (k_share_fold; the strips of the batched multi verify, multi_batch.cuh, fold through it too)
+BLS_FN bool share_fold_adds(uint64_t i, uint64_t step, uint64_t lo, uint64_t hi) {
+  return ((i - lo) & (2 * step - 1)) == 0 && i + step < hi;
+}
+
 #if defined(__HIPCC__)
 // ---- kernels (tu_shares1.hip: the coefficients and G1, tu_shares2.hip: G2); one lane per share unless said otherwise
 // status flags of set s: flags[s]; the share -> set map: sid[i]; the per-share products lambda_i P_i: part (RAW_PROJ records)

@@ -109,8 +109,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_share_fold(size_t n, uint64_t ste
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t s = sid[i];
-  const uint64_t k = i - offs[s];
-  if ((k & (2 * step - 1)) != 0 || i + step >= offs[s + 1]) return;
+  if (!share_fold_adds(i, step, offs[s], offs[s + 1])) return;
   typedef typename grp<G>::F F;
   jac<F> a, b;
   grp<G>::load(a, part, i, 0);

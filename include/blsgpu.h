@@ -362,6 +362,29 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
                                   const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status,
                                   uint64_t* aux);
 
+/* Batched multi verify: MultiSignature::<C>::verify(MultiPublicKey::from_public_keys(pks), msg) (src/multi_signature.rs:127-135,
+ * src/multi_public_key.rs:79-83 -> src/traits/pk_multi.rs:7-13) for n_sets independent (keys, signature, message) sets in one call.
+ * key_offsets: n_sets + 1 entries; set s owns keys key_offsets[s] .. key_offsets[s + 1] of pks (it starts at 0 and never
+ *     decreases; anything else is BLSGPU_E_ARG).  The total key count must be below 2^32.
+ * sigs: one signature per set.  msgs / msg_offsets: one message per set (msg_offsets: n_sets + 1 entries).
+ * fmt: BLSGPU_FMT_RAW_PROJ or BLSGPU_FMT_RAW_AFFINE points (anything else is BLSGPU_E_ARG); scheme and fmt apply to every set.
+ *     Under MessageAugmentation the message of set s is prefixed with the compressed bytes of the set's summed key
+ *     (src/traits/sig_aug.rs:20-24).
+ * status[s] equals what blsgpu_multi_verify returns for set s alone, the order of core_verify (src/traits/sig_core.rs:126-140):
+ *     BLSGPU_SIG_IDENTITY        the signature is the identity
+ *     BLSGPU_PK_IDENTITY         the summed key is the identity: an empty set, or keys that cancel (P, -P); an identity key
+ *                                inside a set adds nothing
+ *     BLSGPU_INVALID_SIGNATURE   the pairing check fails
+ *     BLSGPU_OK
+ * The keys are summed by one segmented point sum over all sets (strips of BLSGPU_MULTI_STRIP keys, by default as many strips as
+ *     a single sum over all keys has lanes); every set shares one verification tail.  The knob changes the plan, never a status.
+ * Every pointer may be host or device memory; a device `status` stays on the device.  key_offsets (and msg_offsets) are read
+ *     and checked on the host.  n_sets == 0 returns 0.  n_sets == 1 is blsgpu_multi_verify itself, its split over the bound
+ *     devices included; in every other case the call runs on one device even when several are bound (whole sets are not sharded
+ *     over devices). */
+int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets,
+                              const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
