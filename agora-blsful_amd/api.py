@@ -26,6 +26,7 @@ OK, INVALID_SIGNATURE, SIG_IDENTITY, PK_IDENTITY, DUPLICATE_MESSAGE, INVALID_COE
     LEGACY_FORMAT = range(9)
 COMMITMENT_IDENTITY, PROOF_IDENTITY, ZERO_CHALLENGE = 9, 10, 11    # blsgpu_sig_proof_verify_batch only
 INVALID_SCHEME, VSSS_ERROR = 12, 13                                  # blsgpu_combine_shares only
+INVALID_DECRYPTION_SHARE, BAD_FRAME = 14, 15                        # the threshold signcryption calls only
 
 EXPORTS = [
     'blsgpu_init', 'blsgpu_shutdown', 'blsgpu_last_error', 'blsgpu_verify_batch', 'blsgpu_multi_verify',
@@ -38,6 +39,7 @@ EXPORTS = [
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
     'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
+    'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
 ]
 
 
@@ -86,6 +88,8 @@ def error_from_status(st, aux=(0, 0), aggregate=False):
         return BlsError('InvalidSignatureScheme')
     if st == VSSS_ERROR:
         return BlsError('VsssError')
+    if st == INVALID_DECRYPTION_SHARE:
+        return BlsError('InvalidDecryptionShare')
     return BlsError('Unknown', str(st))
 
 
@@ -155,6 +159,8 @@ def load_library(path=None):
         lib.blsgpu_verify_secure_batch.argtypes = [ci, ci, vp, vp, sz, vp, vp, vp, ci, ci, vp]
         lib.blsgpu_aggregate_verify_batch.argtypes = [ci, ci, vp, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
         lib.blsgpu_multi_verify_batch.argtypes = [ci, ci, vp, vp, sz, vp, vp, vp, ci, vp]
+        lib.blsgpu_signcrypt_share_verify_batch.argtypes = [ci, ci, vp, vp, u8p, u64p, sz, vp, vp, u64p, ci, i32p]
+        lib.blsgpu_signcrypt_open_batch.argtypes = [ci, ci, vp, vp, u8p, u64p, sz, u8p, vp, u64p, ci, u8p, u64p, i32p]
         _lib = lib
     return _lib
 
@@ -392,6 +398,74 @@ def signcrypt_valid_batch(sig_group, scheme, us, ws, vs, fmt=FMT_RAW_PROJ):
     _check(lib.blsgpu_signcrypt_valid_batch(sig_group, scheme, _ptr(ub), _ptr(wb), _ptr(blob), ctypes.cast(offs, ctypes.c_void_p), n, fmt,
                                             ctypes.cast(st, ctypes.c_void_p)))
     return [s == OK for s in list(st)[:n]]
+
+
+def _count_offsets(groups):
+    offs = (ctypes.c_uint64 * (len(groups) + 1))()
+    for s, g in enumerate(groups):
+        offs[s + 1] = offs[s] + len(g)
+    return offs
+
+
+def signcrypt_share_verify_batch(sig_group, scheme, cts, shares, fmt=FMT_RAW_PROJ):
+    """BlsSignCrypt::verify_share for every share of many ciphertexts in one call (blsgpu_signcrypt_share_verify_batch): `cts` is a
+    list of (u, v, w), `shares` one list per ciphertext of (decryption share, public-key share) raw points.  Returns one list of
+    statuses (OK or INVALID_DECRYPTION_SHARE) per ciphertext."""
+    lib = init()
+    n_ct = len(cts)
+    if len(shares) != n_ct:
+        raise ValueError('one list of shares per ciphertext')
+    voffs, vblob = _offsets([bytes(v) for _, v, _ in cts])
+    soffs = _count_offsets(shares)
+    n = soffs[n_ct]
+    ub, wb = b''.join(u for u, _, _ in cts), b''.join(w for _, _, w in cts)
+    shb, pkb = b''.join(s for g in shares for s, _ in g), b''.join(p for g in shares for _, p in g)
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(lib.blsgpu_signcrypt_share_verify_batch(sig_group, scheme, _ptr(ub), _ptr(wb), _ptr(vblob), ctypes.cast(voffs, ctypes.c_void_p), n_ct,
+                                                   _ptr(shb), _ptr(pkb), ctypes.cast(soffs, ctypes.c_void_p), fmt, ctypes.cast(st, ctypes.c_void_p)))
+    flat = list(st)[:n]
+    return [flat[soffs[c]:soffs[c + 1]] for c in range(n_ct)]
+
+
+def _signcrypt_open(sig_group, scheme, cts, ids, pts, soffs, fmt):
+    lib = init()
+    n_ct = len(cts)
+    voffs, vblob = _offsets([bytes(v) for _, v, _ in cts])
+    ub, wb = b''.join(u for u, _, _ in cts), b''.join(w for _, _, w in cts)
+    frames = ctypes.create_string_buffer(max(len(vblob), 1))
+    rng = (ctypes.c_uint64 * (2 * max(n_ct, 1)))()
+    st = (ctypes.c_int32 * max(n_ct, 1))()
+    _check(lib.blsgpu_signcrypt_open_batch(sig_group, scheme, _ptr(ub), _ptr(wb), _ptr(vblob), ctypes.cast(voffs, ctypes.c_void_p), n_ct,
+                                           _ptr(ids) if ids is not None else None, _ptr(pts) if pts else None,
+                                           ctypes.cast(soffs, ctypes.c_void_p) if soffs is not None else None, fmt,
+                                           ctypes.cast(frames, ctypes.c_void_p), ctypes.cast(rng, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
+    raw = frames.raw
+    out = []
+    for c in range(n_ct):
+        lo = voffs[c] + rng[2 * c]
+        out.append(raw[lo:lo + rng[2 * c + 1]] if st[c] == OK else None)
+    return out, list(st)[:n_ct]
+
+
+def signcrypt_open_batch(sig_group, scheme, cts, shares, fmt=FMT_RAW_PROJ, with_status=False):
+    """SignCryptCiphertext::decrypt_with_shares for many ciphertexts in one call (blsgpu_signcrypt_open_batch): `cts` is a list of
+    (u, v, w), `shares` one list per ciphertext of (identifier: int, decryption share).  Returns [plaintext bytes or None] (None <=>
+    the reference's CtOption is none); with_status=True: (that list, the statuses)."""
+    if len(shares) != len(cts):
+        raise ValueError('one list of shares per ciphertext')
+    ids = b''.join(int(i).to_bytes(32, 'little') for g in shares for i, _ in g) or b'\0'
+    pts = b''.join(p for g in shares for _, p in g)
+    out, st = _signcrypt_open(sig_group, scheme, cts, ids, pts, _count_offsets(shares), fmt)
+    return (out, st) if with_status else out
+
+
+def signcrypt_decrypt_batch(sig_group, scheme, cts, keys, fmt=FMT_RAW_PROJ, with_status=False):
+    """SignCryptDecryptionKey::decrypt for many (ciphertext, key) pairs in one call: the same entry point with one key G per
+    ciphertext in place of shares."""
+    if len(keys) != len(cts):
+        raise ValueError('one key per ciphertext')
+    out, st = _signcrypt_open(sig_group, scheme, cts, None, b''.join(keys), None, fmt)
+    return (out, st) if with_status else out
 
 
 def proof_error_from_status(st):
@@ -663,6 +737,31 @@ class TensorOps:
         st = self.empty(max(n, 1), self.torch.int32)
         _check(self.lib.blsgpu_signcrypt_valid_batch(sg, scheme, self._p(us), self._p(ws), self._p(vs), self._p(offs), n, FMT_RAW_PROJ, self._p(st)))
         return st[:n]
+
+    def signcrypt_share_verify_batch(self, sg, scheme, us, ws, vs, v_offs, n_ct, shares, pk_shares, share_offs, n_shares):
+        """int32 statuses (on the device), one per share, over device-resident ciphertexts (us, ws, vs + int64 v_offs) and the flat
+        decryption / public-key shares with their int64 share_offs (n_ct + 1 entries)."""
+        self._sync()
+        st = self.empty(max(n_shares, 1), self.torch.int32)
+        _check(self.lib.blsgpu_signcrypt_share_verify_batch(sg, scheme, self._p(us), self._p(ws), self._p(vs), self._p(v_offs), n_ct, self._p(shares),
+                                                            self._p(pk_shares), self._p(share_offs), FMT_RAW_PROJ, self._p(st)))
+        return st[:n_shares]
+
+    def signcrypt_open_batch(self, sg, scheme, us, ws, vs, v_offs, n_ct, ids, shares, share_offs):
+        """(frames: uint8 like vs, pt_range: int64 of shape (n_ct, 2), int32 statuses), all on the device.  ids = share_offs = None:
+        `shares` holds one key per ciphertext (signcrypt_decrypt_batch)."""
+        self._sync()
+        frames = self.empty(max(vs.numel() if vs is not None else 0, 1))
+        rng = self.empty(2 * max(n_ct, 1), self.torch.int64)
+        st = self.empty(max(n_ct, 1), self.torch.int32)
+        _check(self.lib.blsgpu_signcrypt_open_batch(sg, scheme, self._p(us), self._p(ws), self._p(vs), self._p(v_offs), n_ct,
+                                                    self._p(ids) if ids is not None else None, self._p(shares),
+                                                    self._p(share_offs) if share_offs is not None else None, FMT_RAW_PROJ, self._p(frames),
+                                                    self._p(rng), self._p(st)))
+        return frames[:vs.numel() if vs is not None else 0], rng[:2 * n_ct].view(n_ct, 2), st[:n_ct]
+
+    def signcrypt_decrypt_batch(self, sg, scheme, us, ws, vs, v_offs, n_ct, keys):
+        return self.signcrypt_open_batch(sg, scheme, us, ws, vs, v_offs, n_ct, None, keys, None)
 
     def point_sum(self, group, pts, n, scalars=None):
         self._sync()
@@ -998,3 +1097,74 @@ class AggregateSignature:
         e = error_from_status(st, aux, aggregate=True)
         if e:
             raise e
+
+
+class SignCryptCiphertext:
+    """SignCryptCiphertext<C> {u, v, w, scheme}: reference src/sign_crypt_ciphertext.rs:12-27.  u: pk group, w: sig group, RAW_PROJ."""
+
+    def __init__(self, impl, scheme, u, v, w):
+        self.impl, self.scheme, self.u, self.v, self.w = impl, scheme, bytes(u), bytes(v), bytes(w)
+
+    def is_valid(self):
+        """reference src/sign_crypt_ciphertext.rs:86-101."""
+        return signcrypt_valid_batch(self.impl.sig_group, self.scheme, [self.u], [self.w], [self.v])[0]
+
+    def decrypt_with_shares(self, shares):
+        """reference src/sign_crypt_ciphertext.rs:60-72: the plaintext, or None."""
+        return signcrypt_open_batch(self.impl.sig_group, self.scheme, [(self.u, self.v, self.w)], [[(s.identifier, s.raw) for s in shares]])[0]
+
+
+class SignDecryptionShare:
+    """SignDecryptionShare<C>: reference src/sign_decryption_share.rs; `raw` is the pk-group point u * sk_i."""
+
+    def __init__(self, impl, identifier, raw):
+        self.impl, self.identifier, self.raw = impl, int(identifier), bytes(raw)
+
+    def verify(self, pks, ciphertext):
+        """reference src/sign_decryption_share.rs:45-62: always under the Basic DST, whatever the ciphertext's scheme is (:54)."""
+        ct = ciphertext
+        st = signcrypt_share_verify_batch(self.impl.sig_group, BASIC, [(ct.u, ct.v, ct.w)], [[(self.raw, pks.raw)]])[0][0]
+        e = error_from_status(st)
+        if e:
+            raise e
+
+
+class SignCryptDecryptionKey:
+    """SignCryptDecryptionKey<C>: reference src/sign_crypt_ciphertext.rs:104-163."""
+
+    def __init__(self, impl, raw):
+        self.impl, self.raw = impl, bytes(raw)
+
+    @staticmethod
+    def from_shares(shares):
+        """reference src/sign_crypt_ciphertext.rs:142-154: raises BlsError('VsssError') as the recovery does."""
+        impl = shares[0].impl if shares else Bls12381G2Impl
+        out, st = combine_shares(2 if impl.sig_group == 1 else 1, [[(s.identifier, s.raw, None) for s in shares]])
+        e = error_from_status(st[0])
+        if e:
+            raise e
+        return SignCryptDecryptionKey(impl, out[0])
+
+    def decrypt(self, ciphertext):
+        """reference src/sign_crypt_ciphertext.rs:157-163: the plaintext, or None."""
+        ct = ciphertext
+        return signcrypt_decrypt_batch(self.impl.sig_group, ct.scheme, [(ct.u, ct.v, ct.w)], [self.raw])[0]
+
+
+def open_many(items):
+    """SignCryptCiphertext.decrypt_with_shares over many items at once: `items` is a list of (SignCryptCiphertext,
+    [SignDecryptionShare]) that share one impl.  Items are grouped by scheme into at most three blsgpu_signcrypt_open_batch calls.
+    Returns one plaintext or None per item, in order."""
+    if not items:
+        return []
+    sg = items[0][0].impl.sig_group
+    if any(ct.impl.sig_group != sg for ct, _ in items):
+        raise ValueError('open_many: every item must use the same impl')
+    out = [None] * len(items)
+    for scheme in sorted({ct.scheme for ct, _ in items}):
+        idx = [i for i, (ct, _) in enumerate(items) if ct.scheme == scheme]
+        res = signcrypt_open_batch(sg, scheme, [(items[i][0].u, items[i][0].v, items[i][0].w) for i in idx],
+                                   [[(s.identifier, s.raw) for s in items[i][1]] for i in idx])
+        for i, r in zip(idx, res):
+            out[i] = r
+    return out

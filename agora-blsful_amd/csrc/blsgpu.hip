@@ -21,6 +21,7 @@
 #include "secure.cuh"
 #include "agg_batch.cuh"
 #include "multi_batch.cuh"
+#include "signcrypt.cuh"
 #include "host_sha256.h"
 
 namespace {
@@ -40,6 +41,7 @@ enum {
   KID_SECURE_RANK, KID_SECURE_GATHER, KID_SECURE_DIGEST, KID_SECURE_COEFF, KID_SECURE_OUT, KID_SECURE_FIN,   // blsgpu_verify_secure_batch
   KID_AGG_SEG_INDEX, KID_AGG_SEG_FOLD, KID_AGG_SEG_FIN,   // blsgpu_aggregate_verify_batch (its prepare, Miller and final-exp kernels count under theirs)
   KID_MULTI_SEG_ACCUM, KID_MULTI_OUT,                     // blsgpu_multi_verify_batch (its fold counts under KID_SHARE_FOLD)
+  KID_SIGNCRYPT_GATHER, KID_SIGNCRYPT_KEYSTREAM,          // blsgpu_signcrypt_share_verify_batch / blsgpu_signcrypt_open_batch
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
@@ -48,7 +50,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "tail_stream_overlapped", "k_share_lagrange", "k_share_ladder", "k_share_fold", "k_share_out",
                                     "k_secure_rank", "k_secure_gather", "k_secure_digest", "k_secure_coeff", "k_secure_out", "k_secure_fin",
                                     "k_agg_seg_index", "k_f12_fold_seg", "k_agg_batch_fin",
-                                    "k_multi_accumulate_seg", "k_multi_out"};
+                                    "k_multi_accumulate_seg", "k_multi_out",
+                                    "k_signcrypt_share_pairs", "k_signcrypt_keystream"};
 
 struct Ctx {
   int dev = -1;
@@ -2903,6 +2906,30 @@ int blsgpu_first_duplicate_message(const uint8_t* msgs, const uint64_t* msg_offs
 }
 API_CATCH
 
+// H(msg_i) into `group` for n messages on the device (RAW_PROJ out, cofactor-cleared), stream-ordered: the launch plan of
+// blsgpu_hash_to_g1 / blsgpu_hash_to_g2.  May take 768 n bytes from the arena (129 .. BLSGPU_WIDE_MAX messages into G2).
+static int run_hash_group(Ctx* c, int group, size_t n, const uint8_t* d_msgs, const uint64_t* d_offs, const dst_arg& d, uint8_t* d_out) {
+  // two lanes per message: always for G2; for G1 up to the cooperative threshold (a full hash-only batch is faster with one lane per message)
+  const int two = (group == 2 || n <= coop_max_items()) ? 1 : 0;
+  if (group == 1 && n <= wide_max_items())   // a few messages: one wave each in the row-wide field type (0.98 ms against 1.6 ms of latency)
+  {
+    prof_pre(c, KID_HASH);
+    launch_hash_g1_small(c->stream, n, d_msgs, d_offs, 0, d, d_out, (uint32_t*)nullptr);
+    prof_post(c);
+  }
+  else if (group == 1) KL(KID_HASH, k_hash_to_g1, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, two);
+  else if (n <= wide_max_items() && hash_phase_stop() == 0) {   // a few messages: row-wide maps and the engine (one workgroup per message up to 128)
+    prof_pre(c, KID_HASH);
+    launch_hash_g2_small(c->stream, n, d_msgs, d_offs, 0, d, d_out, n > 128 ? (uint32_t*)arena_take(c, 768 * n) : nullptr);
+    prof_post(c);
+  } else if (n <= wide_max_items() && hash_phase_stop() != 8) {   // measurement aids (BLSGPU_HASH_STOP=8: clearing in the lane-pair kernel; 9: none)
+    KL(KID_HASH, k_hash_to_g2, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, 3);
+    if (hash_phase_stop() != 9) KL(KID_HASH, k_g2_clear_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), n, d_out);   // 9: measurement aid, no clearing
+  } else
+    KL(KID_HASH, k_hash_to_g2, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, two);
+  HIPCK(hipGetLastError());
+  return 0;
+}
 static int hash_to_group(int group, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, const uint8_t* dst, size_t dst_len, void* out) {
   if (!initialised()) return NOT_INIT();
   if (n == 0) return 0;
@@ -2920,26 +2947,7 @@ static int hash_to_group(int group, const uint8_t* msgs, const uint64_t* msg_off
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
   uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n);
   if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  dst_arg d = make_dst(dst, dst_len);
-  // two lanes per message: always for G2; for G1 up to the cooperative threshold (a full hash-only batch is faster with one lane per message)
-  const int two = (group == 2 || n <= coop_max_items()) ? 1 : 0;
-  if (group == 1 && n <= wide_max_items())   // a few messages: one wave each in the row-wide field type (0.98 ms against 1.6 ms of latency)
-  {
-    prof_pre(c, KID_HASH);
-    launch_hash_g1_small(c->stream, n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, 0, d, d_out, (uint32_t*)nullptr);
-    prof_post(c);
-  }
-  else if (group == 1) KL(KID_HASH, k_hash_to_g1, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, d, d_out, two);
-  else if (n <= wide_max_items() && hash_phase_stop() == 0) {   // a few messages: row-wide maps and the engine (one workgroup per message up to 128)
-    prof_pre(c, KID_HASH);
-    launch_hash_g2_small(c->stream, n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, 0, d, d_out, n > 128 ? (uint32_t*)arena_take(c, 768 * n) : nullptr);
-    prof_post(c);
-  } else if (n <= wide_max_items() && hash_phase_stop() != 8) {   // measurement aids (BLSGPU_HASH_STOP=8: clearing in the lane-pair kernel; 9: none)
-    KL(KID_HASH, k_hash_to_g2, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, d, d_out, 3);
-    if (hash_phase_stop() != 9) KL(KID_HASH, k_g2_clear_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), n, d_out);   // 9: measurement aid, no clearing
-  } else
-    KL(KID_HASH, k_hash_to_g2, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, d, d_out, two);
-  HIPCK(hipGetLastError());
+  if ((rc = run_hash_group(c, group, n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, make_dst(dst, dst_len), d_out))) return rc;
   if ((rc = stage_back(c, out, d_out, osz * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
@@ -3572,78 +3580,59 @@ API_CATCH
 
 
 // ---- threshold recovery (shares.cuh): n_sets Lagrange interpolations at zero in one call
-int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const uint8_t* schemes, const uint64_t* set_offsets,
-                          size_t n_sets, int fmt, void* out, int32_t* status) try {
-  if (!initialised()) return NOT_INIT();
-  if (group != 1 && group != 2) return fail(BLSGPU_E_ARG, "group must be 1 (G1) or 2 (G2)");
-  if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE) return fail(BLSGPU_E_ARG, "fmt must be RAW_PROJ or RAW_AFFINE");
-  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
-  if (n_sets && (!out || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  CTX_ACQUIRE(c);
-  // the offsets decide every size of the call: read (and check) them on the host
-  std::vector<uint64_t> offs(n_sets + 1);
-  if (is_device_ptr(set_offsets)) HIPCK(hipMemcpy(offs.data(), set_offsets, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
-  else memcpy(offs.data(), set_offsets, 8 * (n_sets + 1));
-  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "set_offsets[0] must be 0");
-  uint64_t tmax = 0;
-  for (size_t s = 0; s < n_sets; s++) {
-    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "set_offsets must not decrease");
-    tmax = std::max(tmax, offs[s + 1] - offs[s]);
-  }
-  const size_t n = (size_t)offs[n_sets];
-  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
-  if (n && (!ids || !pts)) return fail(BLSGPU_E_ARG, "null argument");
-  if (n_sets == 0) return 0;
-  const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
-  // plan: sets of at least BLSGPU_SHARES_MSM_MIN shares run as one bucket MSM each (k_msm2_*), all others as per-share ladders and a
-  // segmented tree sum; the coefficients of a large set are split over S workgroups per tile range (k_share_lagrange)
+// The plan of one call, made on the host from the set sizes: sets of at least BLSGPU_SHARES_MSM_MIN shares run as one bucket MSM
+// each (k_msm2_*), all others as per-share ladders and a segmented tree sum; the coefficients of a large set are split over S
+// workgroups per tile range (k_share_lagrange).  ws_bytes: what run_combine_shares takes from the arena.
+struct combine_plan {
+  std::vector<uint32_t> hflags;
+  uint64_t tmax = 0, tmax_ladder = 0, tmax_msm = 0;
+  size_t S = 1, ws_bytes = 0;
+};
+static combine_plan combine_make_plan(const std::vector<uint64_t>& offs, size_t n_sets, int group) {
+  combine_plan pl;
+  const size_t n = (size_t)offs[n_sets], osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
   const uint64_t msm_min = (uint64_t)knobs().shares_msm_min;
-  std::vector<uint32_t> hflags(n_sets, 0);
-  uint64_t tmax_ladder = 0, tmax_msm = 0;
+  pl.hflags.assign(n_sets, 0);
   for (size_t s = 0; s < n_sets; s++) {
     const uint64_t t = offs[s + 1] - offs[s];
+    pl.tmax = std::max(pl.tmax, t);
     if (t >= msm_min) {
-      hflags[s] = SHARE_F_MSM;
-      tmax_msm = std::max(tmax_msm, t);
+      pl.hflags[s] = SHARE_F_MSM;
+      pl.tmax_msm = std::max(pl.tmax_msm, t);
     } else {
-      tmax_ladder = std::max(tmax_ladder, t);
+      pl.tmax_ladder = std::max(pl.tmax_ladder, t);
     }
   }
-  size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax / 256)));
-  S = std::max<size_t>(1, std::min(S, ((size_t)1 << 22) / std::max<size_t>(n, 1)));
-  const size_t msm_bytes = tmax_msm ? msm_ws_bytes(tmax_msm) + pad256(osz * accumulate_lanes(tmax_msm)) + pad256(osz * POINT_TREE_START) : 0;
-  int rc = arena_reserve(c, pad256(psz * n) + pad256(32 * n) + pad256(n) + pad256(8 * (n_sets + 1)) + pad256(32 * n) + pad256(4 * n) +
-                                pad256(64 * S * n) + pad256(osz * n) + pad256(4 * n_sets) + pad256(osz * n_sets) + pad256(4 * n_sets) + msm_bytes + 4096);
-  if (rc) return rc;
-  c->arena_off = 0;
-  const void *d_pts, *d_ids, *d_sch = nullptr, *d_offs;
-  if ((rc = stage_in(c, pts, psz * n, &d_pts))) return rc;
-  if ((rc = stage_in(c, ids, 32 * n, &d_ids))) return rc;
-  if (schemes && n && (rc = stage_in(c, schemes, n, &d_sch))) return rc;
-  {
-    void* d = arena_take(c, 8 * (n_sets + 1));
-    if (!d) return fail(BLSGPU_E_HIP, "internal: arena too small");
-    HIPCK(hipMemcpyAsync(d, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
-    d_offs = d;
-  }
+  size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(pl.tmax / 256)));
+  pl.S = std::max<size_t>(1, std::min(S, ((size_t)1 << 22) / std::max<size_t>(n, 1)));
+  const size_t msm_bytes = pl.tmax_msm ? msm_ws_bytes(pl.tmax_msm) + pad256(osz * accumulate_lanes(pl.tmax_msm)) + pad256(osz * POINT_TREE_START) : 0;
+  pl.ws_bytes = pad256(32 * n) + pad256(4 * n) + pad256(64 * pl.S * n) + pad256(osz * n) + pad256(4 * n_sets) + msm_bytes + 2048;
+  return pl;
+}
+// The device part: coefficients, ladders or MSMs, the per-set sums (Z = 1, all-zero for the identity or a failed set) into d_out and
+// the per-set statuses into d_st.  Stream-ordered on the context's stream; its workspaces come from the arena.
+static int run_combine_shares(Ctx* c, int group, const combine_plan& pl, const std::vector<uint64_t>& offs, size_t n_sets, const uint8_t* d_ids, const uint8_t* d_pts,
+                       const uint8_t* d_sch, const uint64_t* o, int fmt, uint8_t* d_out, int32_t* d_st) {
+  const size_t n = (size_t)offs[n_sets], S = pl.S;
+  const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
+  const uint64_t tmax_ladder = pl.tmax_ladder, tmax_msm = pl.tmax_msm;
+  const std::vector<uint32_t>& hflags = pl.hflags;
+  int rc = 0;
   uint8_t* d_lam = (uint8_t*)arena_take(c, 32 * n);
   uint32_t* d_sid = (uint32_t*)arena_take(c, 4 * n);
   uint32_t* d_nd = (uint32_t*)arena_take(c, 64 * S * n);
   uint8_t* d_part = (uint8_t*)arena_take(c, osz * n);
   uint32_t* d_flags = (uint32_t*)arena_take(c, 4 * n_sets);
-  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n_sets);
-  int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
-  if (!d_lam || !d_sid || !d_nd || !d_part || !d_flags || !d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (!d_lam || !d_sid || !d_nd || !d_part || !d_flags) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if (tmax_msm) HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
   else HIPCK(hipMemsetAsync(d_flags, 0, 4 * n_sets, c->stream));
-  const uint64_t* o = (const uint64_t*)d_offs;
   if (n) {
-    KL(KID_SHARE_LAGRANGE, k_share_lagrange, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_ids, d_flags, d_nd, d_sid);
-    KL(KID_SHARE_LAGRANGE, k_share_lagrange_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (int)S, o, (const uint8_t*)d_ids, (const uint8_t*)d_sch,
+    KL(KID_SHARE_LAGRANGE, k_share_lagrange, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, d_ids, d_flags, d_nd, d_sid);
+    KL(KID_SHARE_LAGRANGE, k_share_lagrange_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (int)S, o, d_ids, d_sch,
        (const uint32_t*)d_nd, (const uint32_t*)d_sid, d_flags, d_lam);
     if (tmax_ladder >= 2) {
       with_group(group, [&](auto G) {
-        KL(KID_SHARE_LADDER, k_share_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, (const uint8_t*)d_lam,
+        KL(KID_SHARE_LADDER, k_share_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_pts, fmt, (const uint8_t*)d_lam,
            (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
       });
       for (uint64_t step = 1; step < tmax_ladder; step <<= 1) {
@@ -3659,7 +3648,7 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
       c->arena_off = mark;
       uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
       if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
-      const uint8_t* sp = (const uint8_t*)d_pts + psz * lo;
+      const uint8_t* sp = d_pts + psz * lo;
       rc = with_group(group, [&](auto G) { return run_point_sum<G()>(c, sp, fmt, d_lam + 32 * lo, nullptr, t, d_msm, T); });
       if (rc) return rc;
       HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
@@ -3668,8 +3657,202 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
   with_group(group, [&](auto G) {
     KL(KID_SHARE_OUT, k_share_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out, d_st);
   });
+  HIPCK(hipGetLastError());
+  return 0;
+}
+
+int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const uint8_t* schemes, const uint64_t* set_offsets,
+                          size_t n_sets, int fmt, void* out, int32_t* status) try {
+  if (!initialised()) return NOT_INIT();
+  if (group != 1 && group != 2) return fail(BLSGPU_E_ARG, "group must be 1 (G1) or 2 (G2)");
+  if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE) return fail(BLSGPU_E_ARG, "fmt must be RAW_PROJ or RAW_AFFINE");
+  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
+  if (n_sets && (!out || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  CTX_ACQUIRE(c);
+  // the offsets decide every size of the call: read (and check) them on the host
+  std::vector<uint64_t> offs(n_sets + 1);
+  if (is_device_ptr(set_offsets)) HIPCK(hipMemcpy(offs.data(), set_offsets, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
+  else memcpy(offs.data(), set_offsets, 8 * (n_sets + 1));
+  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "set_offsets[0] must be 0");
+  for (size_t s = 0; s < n_sets; s++)
+    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "set_offsets must not decrease");
+  const size_t n = (size_t)offs[n_sets];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
+  if (n && (!ids || !pts)) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  const combine_plan pl = combine_make_plan(offs, n_sets, group);
+  const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
+  int rc = arena_reserve(c, pad256(psz * n) + pad256(32 * n) + pad256(n) + pad256(8 * (n_sets + 1)) + pad256(osz * n_sets) + pad256(4 * n_sets) + pl.ws_bytes + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_pts, *d_ids, *d_sch = nullptr, *d_offs;
+  if ((rc = stage_in(c, pts, psz * n, &d_pts))) return rc;
+  if ((rc = stage_in(c, ids, 32 * n, &d_ids))) return rc;
+  if (schemes && n && (rc = stage_in(c, schemes, n, &d_sch))) return rc;
+  {
+    void* d = arena_take(c, 8 * (n_sets + 1));
+    if (!d) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    HIPCK(hipMemcpyAsync(d, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
+    d_offs = d;
+  }
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n_sets);
+  int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
+  if (!d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if ((rc = run_combine_shares(c, group, pl, offs, n_sets, (const uint8_t*)d_ids, (const uint8_t*)d_pts, (const uint8_t*)d_sch, (const uint64_t*)d_offs, fmt, d_out, d_st)))
+    return rc;
   if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
   return status_out_and_sync(c, status, d_st, n_sets);
+}
+API_CATCH
+
+// ---- threshold signcryption (signcrypt.cuh): decryption-share checks and opening with shares, many ciphertexts per call
+// the n + 1 offsets of a ragged argument, read on the host (they decide every size of the call) and checked
+static int read_offsets(const uint64_t* p, size_t n, const char* what, std::vector<uint64_t>& offs) {
+  offs.resize(n + 1);
+  if (is_device_ptr(p)) HIPCK(hipMemcpy(offs.data(), p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  else memcpy(offs.data(), p, 8 * (n + 1));
+  if (offs[0] != 0) return fail(BLSGPU_E_ARG, std::string(what) + "[0] must be 0");
+  for (size_t s = 0; s < n; s++)
+    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, std::string(what) + " must not decrease");
+  return 0;
+}
+static int upload_offsets(Ctx* c, const std::vector<uint64_t>& offs, const uint64_t** d) {
+  void* p = arena_take(c, 8 * offs.size());
+  if (!p) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemcpyAsync(p, offs.data(), 8 * offs.size(), hipMemcpyHostToDevice, c->stream));
+  *d = (const uint64_t*)p;
+  return 0;
+}
+
+/* BlsSignCrypt::verify_share (reference src/traits/sign_crypt.rs:192-207; SignDecryptionShare::verify,
+ * src/sign_decryption_share.rs:45-62) for every share of n_ct ciphertexts: W' = H(u.to_bytes() || v) once per CIPHERTEXT, then
+ * one two-pair check (-W', share) (w, pk) per share on the stages of blsgpu_pairing2_check_batch. */
+int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs, const uint64_t* v_offsets,
+                                        size_t n_ct, const void* shares, const void* pk_shares, const uint64_t* share_offsets, int fmt,
+                                        int32_t* status) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc) return rc;
+  if (!v_offsets || !share_offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  CTX_ACQUIRE(c);
+  std::vector<uint64_t> voffs, soffs;
+  if ((rc = read_offsets(v_offsets, n_ct, "v_offsets", voffs))) return rc;
+  if ((rc = read_offsets(share_offsets, n_ct, "share_offsets", soffs))) return rc;
+  const size_t n = (size_t)soffs[n_ct], total = (size_t)voffs[n_ct];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
+  if (n == 0) return 0;
+  if (!us || !ws || !shares || !pk_shares || !status || (total && !vs)) return fail(BLSGPU_E_ARG, "null argument");
+  const int pkg = key_group(sig_group);
+  const size_t K = point_bytes(pkg, BLSGPU_FMT_COMPRESSED), ub = pk_size(sig_group, fmt) * n_ct, wb = sig_size(sig_group, fmt) * n_ct,
+               shb = pk_size(sig_group, fmt) * n, wtb = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n_ct, mtotal = total + K * n_ct;
+  std::vector<uint64_t> moffs(n_ct + 1);
+  for (size_t s = 0; s <= n_ct; s++) moffs[s] = voffs[s] + K * s;
+  if ((rc = arena_reserve(c, pad256(ub) + pad256(wb) + pad256(total) + 2 * pad256(shb) + 3 * pad256(8 * (n_ct + 1)) + pad256(mtotal) + pad256(wtb) +
+                                 pad256(768 * n_ct) + pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_us, *d_ws, *d_vs, *d_sh, *d_pk;
+  const uint64_t *d_voffs, *d_soffs, *d_moffs;
+  if ((rc = stage_in(c, us, ub, &d_us))) return rc;
+  if ((rc = stage_in(c, ws, wb, &d_ws))) return rc;
+  if ((rc = stage_in(c, vs, total, &d_vs))) return rc;
+  if ((rc = stage_in(c, shares, shb, &d_sh))) return rc;
+  if ((rc = stage_in(c, pk_shares, shb, &d_pk))) return rc;
+  if ((rc = upload_offsets(c, voffs, &d_voffs)) || (rc = upload_offsets(c, soffs, &d_soffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
+  uint8_t* d_msgs = (uint8_t*)arena_take(c, mtotal);
+  uint8_t* d_wt = (uint8_t*)arena_take(c, wtb);
+  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
+  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
+  if (!d_msgs || !d_wt || !d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  // the messages U.to_bytes() || V, one per ciphertext, and their hash: every share of a ciphertext pairs against the same W'
+  with_group(sig_group, [&](auto G) {
+    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_prefix<G()>, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_us, fmt, d_voffs, d_msgs);
+  });
+  if (total) KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_copy, dim3(blocks_for(total)), dim3(BLS_BLOCK), total, n_ct, (const uint8_t*)d_vs, d_voffs, K, d_msgs);
+  if ((rc = run_hash_group(c, sig_group, n_ct, d_msgs, d_moffs, scheme_dst(sig_group, scheme), d_wt))) return rc;
+  with_group(sig_group, [&](auto G) {
+    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_pairs<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, (const uint8_t*)d_sh, (const uint8_t*)d_pk,
+       (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_pairs, d_status);
+  });
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, 0))) return rc;
+  KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_status, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_status);
+  HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, d_status, n);
+}
+API_CATCH
+
+/* BlsSignCrypt::unseal_with_shares / SignCryptCiphertext::decrypt_with_shares (reference src/traits/sign_crypt.rs:106-136,
+ * src/sign_crypt_ciphertext.rs:60-72) for n_ct ciphertexts, or SignCryptDecryptionKey::decrypt (:157-163) when ids and
+ * share_offsets are NULL and `shares` holds one key G per ciphertext.  Launch sequence: the validity check of
+ * blsgpu_signcrypt_valid_batch (its hash of U || V runs once, inside its prepare stage), the share sum of blsgpu_combine_shares,
+ * k_compress of the sums, then k_signcrypt_keystream: SHAKE128, xor, prefix parse and the status merge. */
+int blsgpu_signcrypt_open_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs, const uint64_t* v_offsets, size_t n_ct,
+                                const uint8_t* ids, const void* shares, const uint64_t* share_offsets, int fmt, uint8_t* frames, uint64_t* pt_range,
+                                int32_t* status) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc) return rc;
+  if (!v_offsets) return fail(BLSGPU_E_ARG, "null v_offsets");
+  if ((ids == nullptr) != (share_offsets == nullptr)) return fail(BLSGPU_E_ARG, "ids and share_offsets are given together (shares) or both NULL (keys)");
+  const bool keys = share_offsets == nullptr;
+  CTX_ACQUIRE(c);
+  std::vector<uint64_t> voffs, soffs;
+  if ((rc = read_offsets(v_offsets, n_ct, "v_offsets", voffs))) return rc;
+  if (keys) {
+    soffs.resize(n_ct + 1);
+    for (size_t s = 0; s <= n_ct; s++) soffs[s] = s;
+  } else if ((rc = read_offsets(share_offsets, n_ct, "share_offsets", soffs))) {
+    return rc;
+  }
+  const size_t n = (size_t)soffs[n_ct], total = (size_t)voffs[n_ct];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
+  if (n_ct == 0) return 0;
+  if (!us || !ws || !pt_range || !status || (total && (!vs || !frames)) || (n && !shares)) return fail(BLSGPU_E_ARG, "null argument");
+  const int pkg = key_group(sig_group);
+  const size_t K = point_bytes(pkg, BLSGPU_FMT_COMPRESSED), ub = pk_size(sig_group, fmt) * n_ct, wb = sig_size(sig_group, fmt) * n_ct,
+               shb = pk_size(sig_group, fmt) * n, osz = point_bytes(pkg, BLSGPU_FMT_RAW_PROJ);
+  combine_plan pl;
+  if (!keys) pl = combine_make_plan(soffs, n_ct, pkg);
+  if ((rc = arena_reserve(c, pad256(ub) + pad256(wb) + 2 * pad256(total) + pad256(shb) + pad256(32 * n) + 2 * pad256(8 * (n_ct + 1)) + pad256(osz * n_ct) +
+                                 pad256(K * n_ct) + pad256(16 * n_ct) + 2 * pad256(4 * n_ct) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n_ct) + pl.ws_bytes + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_us, *d_ws, *d_vs, *d_sh, *d_ids = nullptr;
+  const uint64_t *d_voffs, *d_soffs = nullptr;
+  if ((rc = stage_in(c, us, ub, &d_us))) return rc;
+  if ((rc = stage_in(c, ws, wb, &d_ws))) return rc;
+  if ((rc = stage_in(c, vs, total, &d_vs))) return rc;
+  if ((rc = stage_in(c, shares, shb, &d_sh))) return rc;
+  if (!keys && (rc = stage_in(c, ids, 32 * n, &d_ids))) return rc;
+  if ((rc = upload_offsets(c, voffs, &d_voffs))) return rc;
+  if (!keys && (rc = upload_offsets(c, soffs, &d_soffs))) return rc;
+  uint8_t* d_G = keys ? nullptr : (uint8_t*)arena_take(c, osz * n_ct);
+  int32_t* d_cst = keys ? nullptr : (int32_t*)arena_take(c, 4 * n_ct);
+  uint8_t* d_gb = (uint8_t*)arena_take(c, K * n_ct);
+  uint8_t* d_frames = total ? stage_out<uint8_t>(c, frames, total) : c->arena;
+  uint64_t* d_range = stage_out<uint64_t>(c, pt_range, 16 * n_ct);
+  int32_t* d_status = (int32_t*)arena_take(c, 4 * n_ct);
+  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n_ct);
+  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_ct);
+  if ((!keys && (!d_G || !d_cst)) || !d_gb || !d_frames || !d_range || !d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  // BlsSignCrypt::valid: core_verify(pk := U, sig := W, msg := U.to_bytes() || V), the augmentation path of k_prepare
+  if ((rc = run_verify_items(c, sig_group, 1, (const uint8_t*)d_us, (const uint8_t*)d_ws, fmt, (const uint8_t*)d_vs, d_voffs, 0, scheme_dst(sig_group, scheme), n_ct,
+                             d_pairs, d_f, d_status)))
+    return rc;
+  // G = sum lambda_i share_i over all shares passed; a set the recovery rejects leaves the identity (combine().unwrap_or_default())
+  const uint8_t* d_key = (const uint8_t*)d_sh;
+  int key_fmt = fmt;
+  if (!keys) {
+    if ((rc = run_combine_shares(c, pkg, pl, soffs, n_ct, (const uint8_t*)d_ids, (const uint8_t*)d_sh, nullptr, d_soffs, fmt, d_G, d_cst))) return rc;
+    d_key = d_G;
+    key_fmt = BLSGPU_FMT_RAW_PROJ;
+  }
+  with_group(pkg, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, d_key, key_fmt, 0, d_gb); });
+  KL(KID_SIGNCRYPT_KEYSTREAM, k_signcrypt_keystream, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, d_voffs, (const uint8_t*)d_vs, (const uint8_t*)d_gb, (int)K,
+     d_soffs, d_frames, d_range, d_status);
+  HIPCK(hipGetLastError());
+  if (total && (rc = stage_back(c, frames, d_frames, total))) return rc;
+  if ((rc = stage_back(c, pt_range, d_range, 16 * n_ct))) return rc;
+  return status_out_and_sync(c, status, d_status, n_ct);
 }
 API_CATCH
 

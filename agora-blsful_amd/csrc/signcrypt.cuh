@@ -1,0 +1,101 @@
+// Threshold signcryption, the decryption-share side (reference src/traits/sign_crypt.rs:101-150,192-207) for many ciphertexts at
+// once: blsgpu_signcrypt_share_verify_batch and blsgpu_signcrypt_open_batch.  The per-item functions, shared by the kernels
+// (tu_signcrypt.inc) and the host harness (tests/hostsim_signcrypt):
+//   * signcrypt_keystream_xor: frame = SHAKE128(compressed G) xor v (compute_v, :139-150), one sponge per lane (keccak.cuh),
+//     8-byte words where the addresses allow and bytes at the edges;
+//   * signcrypt_parse_frame: the length prefix of the opened frame (decrypt, :122-136) -- the ONE place that knows the varint rule.
+#pragma once
+#include "keccak.cuh"
+
+#define BLS_ERR_INVALID_DECRYPTION_SHARE 14   // BlsError::InvalidDecryptionShare (include/blsgpu.h)
+#define BLS_ERR_BAD_FRAME 15                  // decrypt returned None: no length prefix, or a length beyond the frame
+#ifndef BLS_ERR_VSSS
+#define BLS_ERR_VSSS 13
+#endif
+
+typedef uint64_t __attribute__((may_alias, aligned(8))) signcrypt_u64;
+
+// The frame is varint(len) || message || padding.  The varint is the unsigned encoding of the uint-zigzag crate as this library
+// assumes it (include/blsgpu.h): seven value bits per byte, least significant group first, the top bit set on every byte but the
+// last; `peek` looks at up to 19 bytes (the longest encoding of a u128) and fails when none of them terminates or the frame ends
+// first; the value is taken modulo 2^64 (`as usize`).  Success iff len <= frame_len - overhead.
+#define SIGNCRYPT_VARINT_MAX 19
+KECCAK_FN bool signcrypt_parse_frame(const uint8_t* frame, uint64_t frame_len, uint64_t* pt_off, uint64_t* pt_len) {
+  uint64_t value = 0;
+  for (int i = 0; i < SIGNCRYPT_VARINT_MAX; i++) {
+    if ((uint64_t)i >= frame_len) return false;
+    const uint8_t b = frame[i];
+    if (7 * i < 64) value |= (uint64_t)(b & 0x7f) << (7 * i);
+    if (!(b & 0x80)) {
+      const uint64_t overhead = (uint64_t)i + 1;
+      if (value > frame_len - overhead) return false;
+      *pt_off = overhead;
+      *pt_len = value;
+      return true;
+    }
+  }
+  return false;
+}
+
+// frame[0, len) = SHAKE128(g[0, GLEN)) xor v[0, len).  A long frame is a sequential squeeze: one permutation per 168 bytes.
+// When frame and v are equally (mis)aligned, everything after the first 1 .. 8 bytes moves as aligned 8-byte words: memory word m
+// holds keystream bytes a + 8 m .., the top 8 - a bytes of keystream word m and the low a bytes of word m + 1 (one funnel shift).
+// Writes nothing outside frame[0, len).
+template <int GLEN>
+KECCAK_FN void signcrypt_keystream_xor(uint8_t* frame, const uint8_t* v, uint64_t len, const uint8_t* g) {
+  if (len == 0) return;
+  keccak_state st;
+  shake128_absorb_short<GLEN>(st, g);
+  const bool words = (((uintptr_t)frame ^ (uintptr_t)v) & 7) == 0;
+  const int a = 8 - (int)((uintptr_t)frame & 7);         // 1 .. 8 head bytes
+  uint64_t prev = 0;
+  for (uint64_t base = 0;; base += SHAKE128_RATE) {
+#pragma unroll
+    for (int j = 0; j < SHAKE128_RATE_WORDS; j++) {
+      const uint64_t cur = st.s[j];
+      const uint64_t k0 = base + 8 * (uint64_t)j;         // keystream index of cur's first byte
+      if (!words) {
+        if (k0 < len) {
+          for (int k = 0; k < 8; k++)
+            if (k0 + k < len) frame[k0 + k] = v[k0 + k] ^ (uint8_t)(cur >> (8 * k));
+        }
+      } else if (k0 == 0) {
+        for (int k = 0; k < 8; k++)
+          if (k < a && (uint64_t)k < len) frame[k] = v[k] ^ (uint8_t)(cur >> (8 * k));
+      } else {
+        const uint64_t p = k0 - 8 + (uint64_t)a;          // frame offset of the aligned word that ends inside cur
+        if (p < len) {
+          const uint64_t ks = ((prev >> (8 * a - 1)) >> 1) | (cur << (64 - 8 * a));
+          if (p + 8 <= len) {
+            *(signcrypt_u64*)(frame + p) = *(const signcrypt_u64*)(v + p) ^ ks;
+          } else {
+            for (int k = 0; k < 8; k++)
+              if (p + k < len) frame[p + k] = v[p + k] ^ (uint8_t)(ks >> (8 * k));
+          }
+        }
+      }
+      prev = cur;
+    }
+    if (base + SHAKE128_RATE - 8 + (uint64_t)(words ? a : 8) >= len) break;
+    keccak_f1600(st);
+  }
+}
+
+#if defined(__HIPCC__)
+// n_ct ciphertexts: msgs[v_offs[c] + c K, ..) <- compressed u_c (K = 48 / 96 bytes, the public-key group of SG), the first half of
+// the message U.to_bytes() || V of compute_w; k_signcrypt_hash_copy moves the v bytes behind it
+template <int SG>
+__global__ void k_signcrypt_hash_prefix(size_t n_ct, const uint8_t* us, int fmt, const uint64_t* v_offs, uint8_t* msgs);
+__global__ void k_signcrypt_hash_copy(size_t total, size_t n_ct, const uint8_t* vs, const uint64_t* v_offs, size_t K, uint8_t* msgs);
+// share i of ciphertext c -> the two-pair record (-W'_c, share_i) (w_c, pk_i) in the layout run_pairing2 reads (G1 member first);
+// status[i] = BLS_OK, or BLS_ERR_INVALID_DECRYPTION_SHARE when the share, its key share or w_c is the identity
+template <int SG>
+__global__ void k_signcrypt_share_pairs(size_t n, size_t n_ct, const uint64_t* share_offs, const uint8_t* shares, const uint8_t* pks,
+                                        const uint8_t* ws, int fmt, const uint8_t* wt, uint32_t* pairs, int32_t* status);
+// after the pairing stages: every verdict that is not OK becomes BLS_ERR_INVALID_DECRYPTION_SHARE (a device-side failure stays)
+__global__ void k_signcrypt_share_status(size_t n, int32_t* status);
+// one ciphertext per lane: frame = SHAKE128(gbytes[c]) xor v, the prefix parse, pt_range and the merged status (status holds the
+// validity verdicts on entry).  share_offs == nullptr: a key per ciphertext, no share-count rule.
+__global__ void k_signcrypt_keystream(size_t n_ct, const uint64_t* v_offs, const uint8_t* vs, const uint8_t* gbytes, int glen,
+                                      const uint64_t* share_offs, uint8_t* frames, uint64_t* pt_range, int32_t* status);
+#endif

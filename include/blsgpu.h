@@ -67,6 +67,9 @@ extern "C" {
 /* blsgpu_combine_shares only */
 #define BLSGPU_INVALID_SCHEME 12     /* BlsError::InvalidSignatureScheme       error.rs:19-20; signature.rs:152-154 */
 #define BLSGPU_VSSS_ERROR 13         /* BlsError::VsssError                    error.rs:25-26,60-64 */
+/* the threshold signcryption calls only */
+#define BLSGPU_INVALID_DECRYPTION_SHARE 14 /* BlsError::InvalidDecryptionShare  sign_decryption_share.rs:45-62 */
+#define BLSGPU_BAD_FRAME 15          /* no BlsError: decrypt returns None (no length prefix, or a length beyond the frame) sign_crypt.rs:122-136 */
 
 /* runtime failures (< 0): return codes.  One of them can also appear IN a status entry: BLSGPU_E_HIP when the device-side work of
  * that item failed (single-verdict checks run on workgroups that wait for each other with a bound; a wait that ran out is not a
@@ -384,6 +387,56 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
  *     over devices). */
 int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets,
                               const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status);
+
+/* ---- threshold signcryption: the decryption-share side of SignCryptCiphertext (src/sign_crypt_ciphertext.rs,
+ * src/sign_decryption_share.rs, src/traits/sign_crypt.rs:101-150,192-207).  Only public data enters: ciphertexts, public-key
+ * shares and decryption shares.  "pk group": the group of public keys (u, the decryption shares, the public-key shares);
+ * "sig group": where w lives.  The n_ct ciphertexts are given as in the validity call above: us, ws, and the v fields concatenated in
+ * vs with n_ct + 1 entries in v_offsets.  Offsets start at 0 and never decrease (anything else: BLSGPU_E_ARG); they are read and
+ * checked on the host.  fmt: BLSGPU_FMT_RAW_PROJ or BLSGPU_FMT_RAW_AFFINE for every point.  Every pointer may be host or device
+ * memory.  Both calls run on one device.
+ *
+ * Batched BlsSignCrypt::verify_share (sign_crypt.rs:192-207) for every share of every ciphertext:
+ * shares / pk_shares: one decryption share and the matching public-key share per entry (pk group), share_offsets[c] ..
+ *     share_offsets[c + 1] belong to ciphertext c (n_ct + 1 entries); the total must be below 2^32.
+ * status: one entry per share: BLSGPU_OK, or BLSGPU_INVALID_DECRYPTION_SHARE for every way the reference's Choice is 0: an identity
+ *     share, an identity public-key share, an identity w, or a pairing product e(-W', share) e(w, pk) that is not one.  As in the
+ *     reference, u is not checked for the identity here and the ciphertext's own validity plays no part.
+ * W' = H(u.to_bytes() || v) under the DST of `scheme` is computed once per ciphertext, on the device; every share of that
+ *     ciphertext pairs against it.  SignDecryptionShare::verify always passes the Basic DST, whatever the ciphertext's scheme is
+ *     (sign_decryption_share.rs:54): a caller that mirrors it passes BLSGPU_SCHEME_BASIC. */
+int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs,
+                                        const uint64_t* v_offsets, size_t n_ct, const void* shares, const void* pk_shares,
+                                        const uint64_t* share_offsets, int fmt, int32_t* status);
+
+/* Batched BlsSignCrypt::unseal_with_shares = SignCryptCiphertext::decrypt_with_shares (sign_crypt.rs:106-119,
+ * sign_crypt_ciphertext.rs:60-72):
+ * ids / shares / share_offsets: the decryption shares of all ciphertexts, flat, with their 32-byte little-endian identifiers.
+ * frames: as large as vs, same offsets: SHAKE128(G.to_bytes()) xor v per ciphertext (G.to_bytes(): 48 bytes for Bls12381G2Impl, 96
+ *     for Bls12381G1Impl; the identity is c0 00 ..).  pt_range: two uint64 per ciphertext, the offset of the plaintext inside its
+ *     frame and its length.  status: one entry per ciphertext.
+ * Per ciphertext, in the reference's order:
+ *   1. fewer than two shares (an empty set included): BLSGPU_VSSS_ERROR (CtOption::new(vec![], 0), :114-116), pt_range (0, 0);
+ *   2. G = sum lambda_i share_i over ALL shares passed (the shares are not verified here), by the machinery of the share-recovery
+ *      call above, its ladder and MSM plans included; a set that machinery rejects (a zero or duplicate identifier, an identifier
+ *      >= r) yields the identity point and goes on (combine().unwrap_or_default(), :117);
+ *   3. valid = BlsSignCrypt::valid, the verdict of the validity call above;
+ *   4. frame = SHAKE128(G.to_bytes()) xor v;
+ *   5. the frame is parsed as varint(len) || message || padding (:122-136); on success pt_range = (overhead, len).
+ * status, the first that applies: BLSGPU_VSSS_ERROR (1.); the validity check's status when it is not OK (BLSGPU_INVALID_SIGNATURE,
+ *     BLSGPU_SIG_IDENTITY for w, BLSGPU_PK_IDENTITY for u); BLSGPU_BAD_FRAME when the parse fails; BLSGPU_OK.  status == BLSGPU_OK
+ *     <=> is_some().  The frame bytes and pt_range of an item that is not OK are not part of the contract (pt_range is (0, 0)).  As
+ *     in the reference, a valid ciphertext opened with wrong or too few shares can still parse and return BLSGPU_OK with garbage.
+ * A third assumption of this library, beside the two of the share-recovery call: the varint is the unsigned encoding of the
+ *     uint-zigzag crate -- seven value bits per byte, least significant group first, the top bit set on every byte but the last;
+ *     `peek` looks at up to 19 bytes (the longest encoding of a u128) and fails if none of them terminates or the frame ends
+ *     first; the value is taken modulo 2^64 (`as usize`); the parse succeeds iff len <= frame_len - overhead.  One function holds
+ *     the rule (csrc/signcrypt.cuh signcrypt_parse_frame).
+ * Keys in place of shares (SignCryptDecryptionKey::decrypt, sign_crypt_ciphertext.rs:157-163): ids == NULL and share_offsets == NULL
+ *     means `shares` holds exactly one pk-group point per ciphertext, used as G; step 1 does not apply. */
+int blsgpu_signcrypt_open_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs,
+                                const uint64_t* v_offsets, size_t n_ct, const uint8_t* ids, const void* shares,
+                                const uint64_t* share_offsets, int fmt, uint8_t* frames, uint64_t* pt_range, int32_t* status);
 
 #ifdef __cplusplus
 }
