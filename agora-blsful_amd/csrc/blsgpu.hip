@@ -345,6 +345,38 @@ T* stage_out(Ctx* c, void* out, size_t bytes) {
   return is_device_ptr(out) ? (T*)out : (T*)arena_take(c, bytes);
 }
 int stage_back(Ctx* c, void* out, const void* d, size_t bytes) { return d == out ? 0 : copy_out(c, out, d, bytes); }
+// The buffers of a call, one per line: take (arena bytes) and stage_out (as above) clear `ok` when the arena refuses, and the call
+// tests `ok` once after the last of them, before any kernel gets a pointer.
+struct Carver {
+  Ctx* c;
+  bool ok = true;
+  template <class T>
+  T* take(size_t bytes) {
+    T* p = (T*)arena_take(c, bytes);
+    ok = ok && p;
+    return p;
+  }
+  template <class T>
+  T* stage_out(void* out, size_t bytes) { return is_device_ptr(out) ? (T*)out : take<T>(bytes); }
+};
+// the n + 1 offsets of a ragged argument, read on the host (they decide every size of the call) and checked: they never decrease,
+// and start at 0 unless the caller indexes its flat array from offs[0] (from_zero = false)
+int read_offsets(const uint64_t* p, size_t n, const char* what, std::vector<uint64_t>& offs, bool from_zero = true) {
+  offs.resize(n + 1);
+  if (is_device_ptr(p)) HIPCK(hipMemcpy(offs.data(), p, 8 * (n + 1), hipMemcpyDeviceToHost));
+  else memcpy(offs.data(), p, 8 * (n + 1));
+  if (from_zero && offs[0] != 0) return fail(BLSGPU_E_ARG, std::string(what) + "[0] must be 0");
+  for (size_t s = 0; s < n; s++)
+    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, std::string(what) + " must not decrease");
+  return 0;
+}
+int upload_offsets(Ctx* c, const std::vector<uint64_t>& offs, const uint64_t** d) {
+  void* p = arena_take(c, 8 * offs.size());
+  if (!p) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemcpyAsync(p, offs.data(), 8 * offs.size(), hipMemcpyHostToDevice, c->stream));
+  *d = (const uint64_t*)p;
+  return 0;
+}
 // a call's single verdict, decided on the host, to wherever the caller keeps it
 int put_i32(int32_t* dst, int32_t v) {
   if (is_device_ptr(dst)) HIPCK(hipMemcpy(dst, &v, 4, hipMemcpyHostToDevice));
@@ -1452,23 +1484,22 @@ int msm2_ws_take(Ctx* c, size_t n, int G, msm2_ws& w, bool tables) {
   w.p = msm2_make_plan(n, G);
   const msm2_plan& p = w.p;
   const size_t affw = (G == 1 ? 2 : 4) * FP_NL;
+  Carver mem{c};
   if (tables) {
-    w.tab = (uint32_t*)arena_take(c, 4 * affw * p.E * p.W * n);
-    w.jt = (uint32_t*)arena_take(c, 4 * (affw / 2) * 4 * (p.W > 1 ? p.W - 1 : 1) * n);
-    if (!w.tab || !w.jt) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    w.tab = mem.take<uint32_t>(4 * affw * p.E * p.W * n);
+    w.jt = mem.take<uint32_t>(4 * (affw / 2) * 4 * (p.W > 1 ? p.W - 1 : 1) * n);
   }
-  w.aff = (uint32_t*)arena_take(c, 4 * affw * p.E * n);
-  w.inf = (uint8_t*)arena_take(c, n);
-  w.subs = (uint64_t*)arena_take(c, 32 * n);
-  w.cnt = (uint32_t*)arena_take(c, 4 * p.nb);
-  w.off = (uint32_t*)arena_take(c, 4 * p.nb);
-  w.cur = (uint32_t*)arena_take(c, 4 * p.nb);
-  w.idx = (uint32_t*)arena_take(c, 4 * n * p.E * p.W);
-  w.tiles = (uint32_t*)arena_take(c, 4 * scan_tiles(p.nb));
-  w.sums = (uint8_t*)arena_take(c, 288 * p.nb * p.Q);
-  w.part = (uint8_t*)arena_take(c, 288 * p.nchunks);
-  if (!w.aff || !w.inf || !w.subs || !w.cnt || !w.off || !w.cur || !w.idx || !w.tiles || !w.sums || !w.part)
-    return fail(BLSGPU_E_HIP, "internal: arena too small");
+  w.aff = mem.take<uint32_t>(4 * affw * p.E * n);
+  w.inf = mem.take<uint8_t>(n);
+  w.subs = mem.take<uint64_t>(32 * n);
+  w.cnt = mem.take<uint32_t>(4 * p.nb);
+  w.off = mem.take<uint32_t>(4 * p.nb);
+  w.cur = mem.take<uint32_t>(4 * p.nb);
+  w.idx = mem.take<uint32_t>(4 * n * p.E * p.W);
+  w.tiles = mem.take<uint32_t>(4 * scan_tiles(p.nb));
+  w.sums = mem.take<uint8_t>(288 * p.nb * p.Q);
+  w.part = mem.take<uint8_t>(288 * p.nchunks);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   return 0;
 }
 // the scalar-independent part: every point to affine, with its endomorphism images
@@ -1515,14 +1546,15 @@ bool msm_use_pippenger(size_t n) { return !knobs().msm_naive && n >= 1024; }
 template <int G>
 int run_msm_pippenger(Ctx* c, const uint8_t* d_pts, int fmt, const uint8_t* d_scalars, const uint32_t* d_perm, size_t n, uint8_t* d_out) {
   msm_plan p = msm_make_plan(n, G);
-  uint32_t* d_cnt = (uint32_t*)arena_take(c, 4 * p.nb);
-  uint32_t* d_off = (uint32_t*)arena_take(c, 4 * p.nb);
-  uint32_t* d_cur = (uint32_t*)arena_take(c, 4 * p.nb);
-  uint32_t* d_idx = (uint32_t*)arena_take(c, 4 * n * p.W);
-  uint32_t* d_tiles = (uint32_t*)arena_take(c, 4 * scan_tiles(p.nb));
-  uint8_t* d_sums = (uint8_t*)arena_take(c, 288 * p.nb);
-  uint8_t* d_part = (uint8_t*)arena_take(c, 288 * p.nchunks);
-  if (!d_cnt || !d_off || !d_cur || !d_idx || !d_tiles || !d_sums || !d_part) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint32_t* d_cnt = mem.take<uint32_t>(4 * p.nb);
+  uint32_t* d_off = mem.take<uint32_t>(4 * p.nb);
+  uint32_t* d_cur = mem.take<uint32_t>(4 * p.nb);
+  uint32_t* d_idx = mem.take<uint32_t>(4 * n * p.W);
+  uint32_t* d_tiles = mem.take<uint32_t>(4 * scan_tiles(p.nb));
+  uint8_t* d_sums = mem.take<uint8_t>(288 * p.nb);
+  uint8_t* d_part = mem.take<uint8_t>(288 * p.nchunks);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   HIPCK(hipMemsetAsync(d_cnt, 0, 4 * p.nb, c->stream));
   HIPCK(hipMemsetAsync(d_cur, 0, 4 * p.nb, c->stream));
   KL(KID_MSM_SORT, k_msm_count, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_scalars, p.c, p.W, p.clast, d_cnt);
@@ -1542,7 +1574,6 @@ int run_msm_pippenger(Ctx* c, const uint8_t* d_pts, int fmt, const uint8_t* d_sc
   return 0;
 }
 
-
 // ---- hash_public_keys_with_sorted on the device (reference src/secure_aggregation.rs:41-103,269-335) -----------------
 // Workspace of the key sort / coefficient step, carved from the arena.
 struct keysort_ws {
@@ -1556,13 +1587,14 @@ size_t keysort_ws_bytes(size_t n, size_t width) {
 }
 int keysort_ws_take(Ctx* c, size_t n, size_t width, keysort_ws& w) {
   w.ntiles = (n + UK_SORT_TILE - 1) / UK_SORT_TILE;
-  w.perm_a = (uint32_t*)arena_take(c, 4 * n);
-  w.perm_b = (uint32_t*)arena_take(c, 4 * n);
-  w.hist = (uint32_t*)arena_take(c, 4 * 256 * w.ntiles);
-  w.tiles = (uint32_t*)arena_take(c, 4 * scan_tiles(256 * w.ntiles));
-  w.sorted = (uint8_t*)arena_take(c, width * n);
-  w.flag = (uint32_t*)arena_take(c, 64);
-  if (!w.perm_a || !w.perm_b || !w.hist || !w.tiles || !w.sorted || !w.flag) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  w.perm_a = mem.take<uint32_t>(4 * n);
+  w.perm_b = mem.take<uint32_t>(4 * n);
+  w.hist = mem.take<uint32_t>(4 * 256 * w.ntiles);
+  w.tiles = mem.take<uint32_t>(4 * scan_tiles(256 * w.ntiles));
+  w.sorted = mem.take<uint8_t>(width * n);
+  w.flag = mem.take<uint32_t>(64);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   return 0;
 }
 // stable LSD radix sort on key bytes [0, nbytes): the result lands in w.perm_a
@@ -1659,11 +1691,12 @@ int run_first_duplicate(Ctx* c, const uint8_t* d_msgs, const uint64_t* d_offs, s
   if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 messages");
   size_t cap = 64;
   while (cap < 2 * n) cap <<= 1;
-  uint32_t* tab = (uint32_t*)arena_take(c, 4 * cap);
-  uint32_t* minidx = (uint32_t*)arena_take(c, 4 * cap);
-  uint32_t* slot_of = (uint32_t*)arena_take(c, 4 * (n ? n : 1));
-  uint32_t* best = (uint32_t*)arena_take(c, 64);
-  if (!tab || !minidx || !slot_of || !best) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint32_t* tab = mem.take<uint32_t>(4 * cap);
+  uint32_t* minidx = mem.take<uint32_t>(4 * cap);
+  uint32_t* slot_of = mem.take<uint32_t>(4 * (n ? n : 1));
+  uint32_t* best = mem.take<uint32_t>(64);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   HIPCK(hipMemsetAsync(tab, 0xff, 4 * cap, c->stream));
   HIPCK(hipMemsetAsync(minidx, 0xff, 4 * cap, c->stream));
   HIPCK(hipMemsetAsync(best, 0xff, 4, c->stream));
@@ -1942,10 +1975,11 @@ int blsgpu_verify_batch(int sig_group, int scheme, const void* pks, const void* 
       if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
     }
   }
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-  if (!d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   int pre = 0, kfmt = fmt;
   if (wire) {
     // wire ingest: PublicKey / Signature from_bytes[_with_mode] -- checked decompression incl. subgroup
@@ -2003,14 +2037,15 @@ int blsgpu_verify_batch_grouped(int sig_group, int scheme, const void* pks, cons
   if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint8_t* d_scaled = (uint8_t*)arena_take(c, 144 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIR1_WORDS * 4 * m);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * m);
-  int32_t* d_skip = (int32_t*)arena_take(c, 4 * m);
-  uint32_t* d_fg = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * ng);
-  int32_t* d_gst = (int32_t*)arena_take(c, 4 * ng);
-  if (!d_status || !d_scaled || !d_pairs || !d_f || !d_skip || !d_fg || !d_gst) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint8_t* d_scaled = mem.take<uint8_t>(144 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * m);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * m);
+  int32_t* d_skip = mem.take<int32_t>(4 * m);
+  uint32_t* d_fg = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * ng);
+  int32_t* d_gst = mem.take<int32_t>(4 * ng);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   const int aug = scheme == BLSGPU_SCHEME_AUG;
   const dst_arg dst = scheme_dst(1, scheme);
   HIPCK(hipMemsetAsync(d_skip, 0xff, 4 * m, c->stream));
@@ -2036,15 +2071,15 @@ int blsgpu_verify_batch_grouped(int sig_group, int scheme, const void* pks, cons
     std::vector<uint64_t> offs2(cnt + 1);
     offs2[0] = 0;
     for (size_t j = 0; j < cnt; j++) offs2[j + 1] = offs2[j] + (offs_h[idx[j] + 1] - offs_h[idx[j]]);
-    uint32_t* d_idx = (uint32_t*)arena_take(c, 4 * cnt);
-    uint64_t* d_offs2 = (uint64_t*)arena_take(c, 8 * (cnt + 1));
-    uint8_t* d_pks2 = (uint8_t*)arena_take(c, psz * cnt);
-    uint8_t* d_sigs2 = (uint8_t*)arena_take(c, ssz * cnt);
-    uint8_t* d_msgs2 = (uint8_t*)arena_take(c, offs2[cnt] ? offs2[cnt] : 1);
-    int32_t* d_st2 = (int32_t*)arena_take(c, 4 * cnt);
-    uint32_t* d_pairs2 = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * cnt);
-    uint32_t* d_f2 = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * cnt);
-    if (!d_idx || !d_offs2 || !d_pks2 || !d_sigs2 || !d_msgs2 || !d_st2 || !d_pairs2 || !d_f2) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    uint32_t* d_idx = mem.take<uint32_t>(4 * cnt);
+    uint64_t* d_offs2 = mem.take<uint64_t>(8 * (cnt + 1));
+    uint8_t* d_pks2 = mem.take<uint8_t>(psz * cnt);
+    uint8_t* d_sigs2 = mem.take<uint8_t>(ssz * cnt);
+    uint8_t* d_msgs2 = mem.take<uint8_t>(offs2[cnt] ? offs2[cnt] : 1);
+    int32_t* d_st2 = mem.take<int32_t>(4 * cnt);
+    uint32_t* d_pairs2 = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * cnt);
+    uint32_t* d_f2 = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * cnt);
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
     HIPCK(hipMemcpyAsync(d_idx, idx.data(), 4 * cnt, hipMemcpyHostToDevice, c->stream));
     HIPCK(hipMemcpyAsync(d_offs2, offs2.data(), 8 * (cnt + 1), hipMemcpyHostToDevice, c->stream));
     KL(KID_COMPRESS, k_gather_rows, dim3(blocks_for(cnt * (psz / 4))), dim3(BLS_BLOCK), cnt, (const uint32_t*)d_idx, (const uint32_t*)d_pks, psz / 4, (uint32_t*)d_pks2);
@@ -2078,12 +2113,13 @@ static int verify_one_tail(Ctx* c, int sig_group, int scheme, int aug_prefix, co
   const void* d_msg = nullptr;
   if (!d_hash && (rc = stage_in(c, msg, msg_len, &d_msg))) return rc;
   const uint64_t offs_h[2] = {0, (uint64_t)msg_len};
-  uint64_t* d_offs = (uint64_t*)arena_take(c, 16);
-  int32_t* d_status = (int32_t*)arena_take(c, 4);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, WS_PAIRS_WORDS * 4);
-  uint32_t* d_f = (uint32_t*)arena_take(c, WS_F_WORDS * 4);
-  uint8_t* d_sig_proj = (uint8_t*)arena_take(c, 288);
-  if (!d_offs || !d_status || !d_pairs || !d_f || !d_sig_proj) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint64_t* d_offs = mem.take<uint64_t>(16);
+  int32_t* d_status = mem.take<int32_t>(4);
+  uint32_t* d_pairs = mem.take<uint32_t>(WS_PAIRS_WORDS * 4);
+  uint32_t* d_f = mem.take<uint32_t>(WS_F_WORDS * 4);
+  uint8_t* d_sig_proj = mem.take<uint8_t>(288);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if ((rc = h2d_small(c, d_offs, offs_h, 16))) return rc;
   // normalise the signature to RAW_PROJ with a 1-point "sum"
   rc = with_group(sig_group, [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_sig_in, fmt, nullptr, nullptr, 1, d_sig_proj, 1); });
@@ -2117,11 +2153,12 @@ static int cut_tail_begin(Ctx* c, int sig_group, int scheme, const void* sig, in
   t.sg = sig_group;
   if ((rc = stage_in(c, sig, sig_size(sig_group, fmt), &d_sig))) return rc;
   if ((rc = stage_in(c, msg, msg_len, &d_msg0))) return rc;
-  uint64_t* d_offs0 = (uint64_t*)arena_take(c, 16);
-  t.rec = (uint32_t*)arena_take(c, (size_t)WREC_WORDS * 4);
-  t.d_status = (int32_t*)arena_take(c, 4);
-  uint8_t* d_hash = (uint8_t*)arena_take(c, 288);
-  if (!d_offs0 || !t.rec || !t.d_status || !d_hash) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint64_t* d_offs0 = mem.take<uint64_t>(16);
+  t.rec = mem.take<uint32_t>((size_t)WREC_WORDS * 4);
+  t.d_status = mem.take<int32_t>(4);
+  uint8_t* d_hash = mem.take<uint8_t>(288);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   const uint64_t offs0[2] = {0, (uint64_t)msg_len};
   if ((rc = h2d_small(c, d_offs0, offs0, 16))) return rc;
   if ((rc = side_fork(c))) return rc;
@@ -2266,11 +2303,12 @@ static int aggregate_enqueue(Ctx* c, int sig_group, int scheme, const uint8_t* d
   int rc;
   const size_t m = n + 1, mm = d_sig ? m : n;
   const int has_sig = d_sig ? 1 : 0;
-  int32_t* d_bad = (int32_t*)arena_take(c, 4 * m);
-  unsigned long long* d_min = (unsigned long long*)arena_take(c, 64);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIR1_WORDS * 4 * m);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * m);
-  if (!d_bad || !d_min || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  int32_t* d_bad = mem.take<int32_t>(4 * m);
+  unsigned long long* d_min = mem.take<unsigned long long>(64);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * m);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * m);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   HIPCK(hipMemsetAsync(d_min, 0xff, 8, c->stream));
   HIPCK(hipMemsetAsync(d_bad, 0, 4 * m, c->stream));
   const dst_arg dst = scheme_dst(sig_group, scheme);
@@ -2484,12 +2522,13 @@ int blsgpu_aggregate_verify(int sig_group, int scheme, const void* pks, const ui
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * m, &d_offs))) return rc;
   const double t_staged = now();
-  int64_t* d_first = (int64_t*)arena_take(c, 64);
-  int32_t* d_verdict = (int32_t*)arena_take(c, 64);
-  uint64_t* d_dup = (uint64_t*)arena_take(c, 64);
+  Carver mem{c};
+  int64_t* d_first = mem.take<int64_t>(64);
+  int32_t* d_verdict = mem.take<int32_t>(64);
+  uint64_t* d_dup = mem.take<uint64_t>(64);
   struct results { int64_t first; int32_t verdict; int32_t pad; uint64_t dup[2]; };
   results* h = (results*)hsmall_take(c, sizeof(results));
-  if (!d_first || !d_verdict || !d_dup || !h) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (!mem.ok || !h) return fail(BLSGPU_E_HIP, "internal: arena too small");
   h->dup[0] = h->dup[1] = ~0ull;
   // everything is enqueued at once; the identity index, the verdict and the duplicate pair come back together and the
   // host applies the reference's precedence afterwards
@@ -2634,14 +2673,15 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
   }
   const void* d_pks;
   if ((rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
-  uint8_t* d_bytes = (uint8_t*)arena_take(c, width * n);
-  uint8_t* d_scal = (uint8_t*)arena_take(c, 32 * n);
-  uint8_t* d_part = (uint8_t*)arena_take(c, 288 * T);
-  uint8_t* d_H = (uint8_t*)arena_take(c, 64);
-  int32_t* d_zero = (int32_t*)arena_take(c, 64);
+  Carver mem{c};
+  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
+  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
+  uint8_t* d_part = mem.take<uint8_t>(288 * T);
+  uint8_t* d_H = mem.take<uint8_t>(64);
+  int32_t* d_zero = mem.take<int32_t>(64);
   int32_t* h_zero = (int32_t*)hsmall_take(c, 64);
   keysort_ws w;
-  if (!d_bytes || !d_scal || !d_part || !d_H || !d_zero || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (!mem.ok || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if ((rc = keysort_ws_take(c, n, width, w))) return rc;
   const double t0 = now();
   // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:42,47; public_key.rs:146-151)
@@ -2734,12 +2774,13 @@ int blsgpu_secure_coefficients(const uint8_t* key_bytes, size_t n, size_t width,
     c->arena_off = 0;
     const void* d_kb;
     if ((rc = stage_in(c, key_bytes, width * n, &d_kb))) return rc;
-    uint8_t* d_scal = (uint8_t*)arena_take(c, 32 * n);
-    uint8_t* d_H = (uint8_t*)arena_take(c, 64);
-    int32_t* d_zero = (int32_t*)arena_take(c, 64);
+    Carver mem{c};
+    uint8_t* d_scal = mem.take<uint8_t>(32 * n);
+    uint8_t* d_H = mem.take<uint8_t>(64);
+    int32_t* d_zero = mem.take<int32_t>(64);
     int32_t* h_zero = (int32_t*)hsmall_take(c, 64);
     keysort_ws w;
-    if (!d_scal || !d_H || !d_zero || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    if (!mem.ok || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
     if ((rc = keysort_ws_take(c, n, width, w))) return rc;
     if ((rc = run_key_sort_to_host(c, (const uint8_t*)d_kb, n, width, w, nullptr, nullptr))) return rc;
     uint8_t H[32];
@@ -2838,10 +2879,11 @@ int blsgpu_coefficients_for_range(const uint8_t* digest, const uint32_t* perm, s
     const void *d_perm, *d_H;
     if ((rc = stage_in(c, perm, 4 * n, &d_perm))) return rc;
     if ((rc = stage_in(c, digest, 32, &d_H))) return rc;
-    uint8_t* d_scal = stage_out<uint8_t>(c, out_scalars, 32 * count);
-    int32_t* d_zero = (int32_t*)arena_take(c, 64);
+    Carver mem{c};
+    uint8_t* d_scal = mem.stage_out<uint8_t>(out_scalars, 32 * count);
+    int32_t* d_zero = mem.take<int32_t>(64);
     int32_t* h_zero = (int32_t*)hsmall_take(c, 64);
-    if ((count && !d_scal) || !d_zero || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    if (!mem.ok || !h_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
     HIPCK(hipMemsetAsync(d_zero, 0, 4, c->stream));
     if ((rc = run_coefficients(c, (const uint8_t*)d_H, (const uint32_t*)d_perm, n, base, count, 0, d_scal, d_zero))) return rc;
     HIPCK(hipMemcpyAsync(h_zero, d_zero, 4, hipMemcpyDeviceToHost, c->stream));
@@ -2868,10 +2910,11 @@ int blsgpu_first_occurrence(const uint8_t* key_bytes, const uint32_t* perm, size
   const void *d_kb, *d_perm;
   if ((rc = stage_in(c, key_bytes, width * n, &d_kb))) return rc;
   if ((rc = stage_in(c, perm, 4 * n, &d_perm))) return rc;
-  uint32_t* d_start = (uint32_t*)arena_take(c, 4 * n);
-  uint32_t* d_tiles = (uint32_t*)arena_take(c, 4 * scan_tiles(n));
-  uint32_t* d_idx = stage_out<uint32_t>(c, out_idx, 4 * n);
-  if (!d_start || !d_tiles || !d_idx) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint32_t* d_start = mem.take<uint32_t>(4 * n);
+  uint32_t* d_tiles = mem.take<uint32_t>(4 * scan_tiles(n));
+  uint32_t* d_idx = mem.stage_out<uint32_t>(out_idx, 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   KL(KID_KEY_SORT, k_keys_run_start, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_kb, width, (const uint32_t*)d_perm, d_start);
   if ((rc = run_scan_max_u32(c, KID_KEY_SORT, n, d_start, d_tiles))) return rc;
   KL(KID_KEY_SORT, k_run_first_index, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_perm, (const uint32_t*)d_start, d_idx);
@@ -3007,10 +3050,11 @@ int blsgpu_pairing_product_is_one(const void* g1s, const void* g2s, size_t n, in
     const void *d1, *d2;
     if ((rc = stage_in(c, g1s, point_bytes(1, fmt) * n, &d1))) return rc;
     if ((rc = stage_in(c, g2s, point_bytes(2, fmt) * n, &d2))) return rc;
-    int32_t* d_skip = (int32_t*)arena_take(c, 4 * n + 4);
-    uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIR1_WORDS * 4 * n);
-    uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-    if (!d_skip || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    Carver mem{c};
+    int32_t* d_skip = mem.take<int32_t>(4 * n + 4);
+    uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * n);
+    uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
     KL(KID_PAIRS_AFF, k_pairs_to_affine, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d1, (const uint8_t*)d2, fmt, d_pairs, d_skip);
     size_t outputs = 0;
     if ((rc = run_miller_product(c, n, n, d_pairs, d_skip, d_f, &outputs))) return rc;
@@ -3067,11 +3111,12 @@ int blsgpu_pop_verify_batch(int sig_group, const void* pks, const void* proofs, 
   const void *d_pks, *d_sigs;
   if ((rc = stage_in(c, pks, pkb, &d_pks))) return rc;
   if ((rc = stage_in(c, proofs, sgb, &d_sigs))) return rc;
-  uint64_t* d_offs = (uint64_t*)arena_take(c, 16);
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-  if (!d_offs || !d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint64_t* d_offs = mem.take<uint64_t>(16);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   HIPCK(hipMemsetAsync(d_offs, 0, 16, c->stream));
   const char* pd = sig_group == 1 ? "BLS_POP_BLS12381G1_XMD:SHA-256_SSWU_RO_POP_" : "BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";
   // mode 2: the message is the compressed key (single_msg = 1 keeps the unused message indexing in bounds)
@@ -3114,15 +3159,16 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
     const void *d_pks, *d_sigs;
     if ((rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
     if ((rc = stage_in(c, sigs, ssz * n, &d_sigs))) return rc;
-    uint8_t* d_bytes = (uint8_t*)arena_take(c, width * n);
-    uint32_t* d_idx = (uint32_t*)arena_take(c, 4 * n);
-    uint32_t* d_start = (uint32_t*)arena_take(c, 4 * n);
-    uint32_t* d_tiles = (uint32_t*)arena_take(c, 4 * scan_tiles(n));
-    uint8_t* d_scal = (uint8_t*)arena_take(c, 32 * n);
-    uint8_t* d_H = (uint8_t*)arena_take(c, 64);
-    int32_t* d_zero = (int32_t*)arena_take(c, 64);
+    Carver mem{c};
+    uint8_t* d_bytes = mem.take<uint8_t>(width * n);
+    uint32_t* d_idx = mem.take<uint32_t>(4 * n);
+    uint32_t* d_start = mem.take<uint32_t>(4 * n);
+    uint32_t* d_tiles = mem.take<uint32_t>(4 * scan_tiles(n));
+    uint8_t* d_scal = mem.take<uint8_t>(32 * n);
+    uint8_t* d_H = mem.take<uint8_t>(64);
+    int32_t* d_zero = mem.take<int32_t>(64);
     keysort_ws w;
-    if (!d_bytes || !d_idx || !d_start || !d_tiles || !d_scal || !d_H || !d_zero) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
     if ((rc = keysort_ws_take(c, n, width, w))) return rc;
     with_group(key_group(sig_group), [&](auto G) {
       KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
@@ -3196,11 +3242,12 @@ int blsgpu_signatures_from_tagged(int sig_group, const uint8_t* bytes, size_t n,
   c->arena_off = 0;
   const void* d_in;
   if ((rc = stage_in(c, bytes, (width + 1) * n, &d_in))) return rc;
-  uint8_t* d_bytes = (uint8_t*)arena_take(c, width * n);
-  uint8_t* d_tags = stage_out<uint8_t>(c, out_schemes, n);
-  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n);
-  int32_t* d_st = stage_out<int32_t>(c, status, 4 * n);
-  if (!d_bytes || !d_tags || !d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
+  uint8_t* d_tags = mem.stage_out<uint8_t>(out_schemes, n);
+  uint8_t* d_out = mem.stage_out<uint8_t>(out, osz * n);
+  int32_t* d_st = mem.stage_out<int32_t>(status, 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   KL(KID_DECOMPRESS, k_untag, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, width, (const uint8_t*)d_in, d_bytes, d_tags, d_st);
   HIPCK(hipMemsetAsync(d_out, 0, osz * n, c->stream));      // records with a bad tag are not decoded: leave the identity encoding
   with_group(sig_group, [&](auto G) { KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_bytes, 0, d_out, d_st, 1); });
@@ -3414,10 +3461,11 @@ static int core_verify_entry(int sig_group, const dst_arg& dst, int aug, const v
   if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-  if (!d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   rc = run_verify_items(c, sig_group, aug, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, 0,
                         dst, n, d_pairs, d_f, d_status);
   if (rc) return rc;
@@ -3451,10 +3499,11 @@ int blsgpu_core_verify_hashed(int sig_group, const void* pks, const void* sigs, 
   if ((rc = stage_in(c, pks, pkb, &d_pks))) return rc;
   if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
   if ((rc = stage_in(c, hashes, sgb, &d_h))) return rc;
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-  if (!d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   with_group(sig_group, [&](auto G) {
     KL(KID_PREPARE, k_prepare_hashed<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, (const uint8_t*)d_h, d_pairs, d_status, 0);
   });
@@ -3504,10 +3553,11 @@ int blsgpu_sig_proof_verify_batch(int sig_group, int scheme, const void* commitm
   if ((rc = stage_in(c, ys, 32 * n, &d_ys))) return rc;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-  if (!d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   const dst_arg dst = scheme_dst(sig_group, scheme);
   with_group(sig_group, [&](auto G) {
     KL(KID_PREPARE, k_prepare_proof<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, (const uint8_t*)d_v, (const uint8_t*)d_pks,
@@ -3539,10 +3589,11 @@ int blsgpu_pairing2_check_batch(const void* g1a, const void* g2a, const void* g1
   if ((rc = stage_in(c, g2a, b2, &d2a))) return rc;
   if ((rc = stage_in(c, g1b, b1, &d1b))) return rc;
   if ((rc = stage_in(c, g2b, b2, &d2b))) return rc;
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-  if (!d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   KL(KID_PAIRS_AFF, k_pairs2_to_affine, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d1a, (const uint8_t*)d2a, (const uint8_t*)d1b,
      (const uint8_t*)d2b, fmt, d_pairs, d_status);
   if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, 0))) return rc;
@@ -3618,12 +3669,13 @@ static int run_combine_shares(Ctx* c, int group, const combine_plan& pl, const s
   const uint64_t tmax_ladder = pl.tmax_ladder, tmax_msm = pl.tmax_msm;
   const std::vector<uint32_t>& hflags = pl.hflags;
   int rc = 0;
-  uint8_t* d_lam = (uint8_t*)arena_take(c, 32 * n);
-  uint32_t* d_sid = (uint32_t*)arena_take(c, 4 * n);
-  uint32_t* d_nd = (uint32_t*)arena_take(c, 64 * S * n);
-  uint8_t* d_part = (uint8_t*)arena_take(c, osz * n);
-  uint32_t* d_flags = (uint32_t*)arena_take(c, 4 * n_sets);
-  if (!d_lam || !d_sid || !d_nd || !d_part || !d_flags) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint8_t* d_lam = mem.take<uint8_t>(32 * n);
+  uint32_t* d_sid = mem.take<uint32_t>(4 * n);
+  uint32_t* d_nd = mem.take<uint32_t>(64 * S * n);
+  uint8_t* d_part = mem.take<uint8_t>(osz * n);
+  uint32_t* d_flags = mem.take<uint32_t>(4 * n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if (tmax_msm) HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
   else HIPCK(hipMemsetAsync(d_flags, 0, 4 * n_sets, c->stream));
   if (n) {
@@ -3669,36 +3721,28 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
   if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
   if (n_sets && (!out || !status)) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  // the offsets decide every size of the call: read (and check) them on the host
-  std::vector<uint64_t> offs(n_sets + 1);
-  if (is_device_ptr(set_offsets)) HIPCK(hipMemcpy(offs.data(), set_offsets, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
-  else memcpy(offs.data(), set_offsets, 8 * (n_sets + 1));
-  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "set_offsets[0] must be 0");
-  for (size_t s = 0; s < n_sets; s++)
-    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "set_offsets must not decrease");
+  std::vector<uint64_t> offs;
+  int rc = read_offsets(set_offsets, n_sets, "set_offsets", offs);
+  if (rc) return rc;
   const size_t n = (size_t)offs[n_sets];
   if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
   if (n && (!ids || !pts)) return fail(BLSGPU_E_ARG, "null argument");
   if (n_sets == 0) return 0;
   const combine_plan pl = combine_make_plan(offs, n_sets, group);
   const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
-  int rc = arena_reserve(c, pad256(psz * n) + pad256(32 * n) + pad256(n) + pad256(8 * (n_sets + 1)) + pad256(osz * n_sets) + pad256(4 * n_sets) + pl.ws_bytes + 4096);
+  rc = arena_reserve(c, pad256(psz * n) + pad256(32 * n) + pad256(n) + pad256(8 * (n_sets + 1)) + pad256(osz * n_sets) + pad256(4 * n_sets) + pl.ws_bytes + 4096);
   if (rc) return rc;
   c->arena_off = 0;
-  const void *d_pts, *d_ids, *d_sch = nullptr, *d_offs;
+  const void *d_pts, *d_ids, *d_sch = nullptr;
+  const uint64_t* d_offs;
   if ((rc = stage_in(c, pts, psz * n, &d_pts))) return rc;
   if ((rc = stage_in(c, ids, 32 * n, &d_ids))) return rc;
   if (schemes && n && (rc = stage_in(c, schemes, n, &d_sch))) return rc;
-  {
-    void* d = arena_take(c, 8 * (n_sets + 1));
-    if (!d) return fail(BLSGPU_E_HIP, "internal: arena too small");
-    HIPCK(hipMemcpyAsync(d, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
-    d_offs = d;
-  }
+  if ((rc = upload_offsets(c, offs, &d_offs))) return rc;
   uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n_sets);
   int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
   if (!d_out || !d_st) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if ((rc = run_combine_shares(c, group, pl, offs, n_sets, (const uint8_t*)d_ids, (const uint8_t*)d_pts, (const uint8_t*)d_sch, (const uint64_t*)d_offs, fmt, d_out, d_st)))
+  if ((rc = run_combine_shares(c, group, pl, offs, n_sets, (const uint8_t*)d_ids, (const uint8_t*)d_pts, (const uint8_t*)d_sch, d_offs, fmt, d_out, d_st)))
     return rc;
   if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
   return status_out_and_sync(c, status, d_st, n_sets);
@@ -3706,24 +3750,6 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
 API_CATCH
 
 // ---- threshold signcryption (signcrypt.cuh): decryption-share checks and opening with shares, many ciphertexts per call
-// the n + 1 offsets of a ragged argument, read on the host (they decide every size of the call) and checked
-static int read_offsets(const uint64_t* p, size_t n, const char* what, std::vector<uint64_t>& offs) {
-  offs.resize(n + 1);
-  if (is_device_ptr(p)) HIPCK(hipMemcpy(offs.data(), p, 8 * (n + 1), hipMemcpyDeviceToHost));
-  else memcpy(offs.data(), p, 8 * (n + 1));
-  if (offs[0] != 0) return fail(BLSGPU_E_ARG, std::string(what) + "[0] must be 0");
-  for (size_t s = 0; s < n; s++)
-    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, std::string(what) + " must not decrease");
-  return 0;
-}
-static int upload_offsets(Ctx* c, const std::vector<uint64_t>& offs, const uint64_t** d) {
-  void* p = arena_take(c, 8 * offs.size());
-  if (!p) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemcpyAsync(p, offs.data(), 8 * offs.size(), hipMemcpyHostToDevice, c->stream));
-  *d = (const uint64_t*)p;
-  return 0;
-}
-
 /* BlsSignCrypt::verify_share (reference src/traits/sign_crypt.rs:192-207; SignDecryptionShare::verify,
  * src/sign_decryption_share.rs:45-62) for every share of n_ct ciphertexts: W' = H(u.to_bytes() || v) once per CIPHERTEXT, then
  * one two-pair check (-W', share) (w, pk) per share on the stages of blsgpu_pairing2_check_batch. */
@@ -3758,12 +3784,13 @@ int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* u
   if ((rc = stage_in(c, shares, shb, &d_sh))) return rc;
   if ((rc = stage_in(c, pk_shares, shb, &d_pk))) return rc;
   if ((rc = upload_offsets(c, voffs, &d_voffs)) || (rc = upload_offsets(c, soffs, &d_soffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
-  uint8_t* d_msgs = (uint8_t*)arena_take(c, mtotal);
-  uint8_t* d_wt = (uint8_t*)arena_take(c, wtb);
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
-  if (!d_msgs || !d_wt || !d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint8_t* d_msgs = mem.take<uint8_t>(mtotal);
+  uint8_t* d_wt = mem.take<uint8_t>(wtb);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   // the messages U.to_bytes() || V, one per ciphertext, and their hash: every share of a ciphertext pairs against the same W'
   with_group(sig_group, [&](auto G) {
     KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_prefix<G()>, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_us, fmt, d_voffs, d_msgs);
@@ -3825,15 +3852,20 @@ int blsgpu_signcrypt_open_batch(int sig_group, int scheme, const void* us, const
   if (!keys && (rc = stage_in(c, ids, 32 * n, &d_ids))) return rc;
   if ((rc = upload_offsets(c, voffs, &d_voffs))) return rc;
   if (!keys && (rc = upload_offsets(c, soffs, &d_soffs))) return rc;
-  uint8_t* d_G = keys ? nullptr : (uint8_t*)arena_take(c, osz * n_ct);
-  int32_t* d_cst = keys ? nullptr : (int32_t*)arena_take(c, 4 * n_ct);
-  uint8_t* d_gb = (uint8_t*)arena_take(c, K * n_ct);
-  uint8_t* d_frames = total ? stage_out<uint8_t>(c, frames, total) : c->arena;
-  uint64_t* d_range = stage_out<uint64_t>(c, pt_range, 16 * n_ct);
-  int32_t* d_status = (int32_t*)arena_take(c, 4 * n_ct);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n_ct);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_ct);
-  if ((!keys && (!d_G || !d_cst)) || !d_gb || !d_frames || !d_range || !d_status || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  Carver mem{c};
+  uint8_t* d_G = nullptr;
+  int32_t* d_cst = nullptr;
+  if (!keys) {
+    d_G = mem.take<uint8_t>(osz * n_ct);
+    d_cst = mem.take<int32_t>(4 * n_ct);
+  }
+  uint8_t* d_gb = mem.take<uint8_t>(K * n_ct);
+  uint8_t* d_frames = total ? mem.stage_out<uint8_t>(frames, total) : c->arena;
+  uint64_t* d_range = mem.stage_out<uint64_t>(pt_range, 16 * n_ct);
+  int32_t* d_status = mem.take<int32_t>(4 * n_ct);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n_ct);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n_ct);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   // BlsSignCrypt::valid: core_verify(pk := U, sig := W, msg := U.to_bytes() || V), the augmentation path of k_prepare
   if ((rc = run_verify_items(c, sig_group, 1, (const uint8_t*)d_us, (const uint8_t*)d_ws, fmt, (const uint8_t*)d_vs, d_voffs, 0, scheme_dst(sig_group, scheme), n_ct,
                              d_pairs, d_f, d_status)))
@@ -3856,6 +3888,27 @@ int blsgpu_signcrypt_open_batch(int sig_group, int scheme, const void* us, const
 }
 API_CATCH
 
+// ---- summed key -> verification tail, the last stage of the batched verify_secure and multi verify.  Its buffers are carved where the
+// entry point lists its own (before any workspace that is reused from set to set); run_set_tail writes every set's signature as RAW_PROJ,
+// its key part[part_offs[s]] and its status so far (k_set_out, under the caller's kernel id), then runs ONE core_verify tail over all sets.
+struct set_tail {
+  int32_t* st;
+  uint8_t *sigp, *apk;
+  uint32_t *pairs, *f;
+  set_tail(Carver& mem, size_t n_sets)
+      : st(mem.take<int32_t>(4 * n_sets)), sigp(mem.take<uint8_t>(288 * n_sets)), apk(mem.take<uint8_t>(288 * n_sets)),
+        pairs(mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n_sets)), f(mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n_sets)) {}
+};
+static int run_set_tail(Ctx* c, const set_tail& t, int sig_group, int scheme, int aug, int kid, size_t n_sets, const uint64_t* d_key_offs,
+                        const uint64_t* d_part_offs, uint32_t* d_flags, const uint8_t* d_part, const void* d_sigs, int fmt, const void* d_msgs, const void* d_moffs) {
+  with_group(sig_group, [&](auto G) {
+    KL(kid, k_set_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, d_key_offs, d_part_offs, d_flags, d_part, (const uint8_t*)d_sigs, fmt, t.sigp,
+       t.apk, t.st);
+  });
+  return run_verify_items(c, sig_group, aug, t.apk, t.sigp, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msgs, (const uint64_t*)d_moffs, 0,
+                          scheme_dst(sig_group, scheme), n_sets, t.pairs, t.f, t.st, 1);
+}
+
 // ---- batched verify_secure (secure.cuh): n_sets independent Signature::verify_secure checks in one call
 int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
                                const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt, int32_t* status) try {
@@ -3866,25 +3919,13 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
     return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
   if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
   if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  // the offsets decide every size of the call: read (and check) them on the host
-  auto read_offsets = [&](const uint64_t* src, std::vector<uint64_t>& dst) -> int {
-    dst.resize(n_sets + 1);
-    if (is_device_ptr(src)) HIPCK(hipMemcpy(dst.data(), src, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
-    else memcpy(dst.data(), src, 8 * (n_sets + 1));
-    return 0;
-  };
   std::vector<uint64_t> offs, moffs;
-  if ((rc = read_offsets(key_offsets, offs))) return rc;
-  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "key_offsets[0] must be 0");
-  for (size_t s = 0; s < n_sets; s++)
-    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "key_offsets must not decrease");
+  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", offs))) return rc;
   const size_t n = (size_t)offs[n_sets];
   if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
   if (n && !pks) return fail(BLSGPU_E_ARG, "null argument");
   if (n_sets == 0) return 0;
-  if ((rc = read_offsets(msg_offsets, moffs))) return rc;
-  for (size_t s = 0; s < n_sets; s++)
-    if (moffs[s + 1] < moffs[s]) return fail(BLSGPU_E_ARG, "msg_offsets must not decrease");
+  if ((rc = read_offsets(msg_offsets, n_sets, "msg_offsets", moffs, false))) return rc;      // set s's message is msgs + moffs[s]
   if (moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
   // plan: a set of at least BLSGPU_SECURE_BATCH_MAX keys runs one at a time through the machinery of blsgpu_verify_secure (device
   // sort, host SHA-256 of the stream, k_sha256_coeff, bucket MSM); all others through the segmented kernels of secure.cuh and the
@@ -3923,25 +3964,20 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
   if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
-  uint64_t* d_offs = (uint64_t*)arena_take(c, 8 * (n_sets + 1));
-  uint8_t* d_bytes = (uint8_t*)arena_take(c, width * n);
-  uint8_t* d_sorted = (uint8_t*)arena_take(c, width * n);
-  uint8_t* d_scal = (uint8_t*)arena_take(c, 32 * n);
-  uint32_t* d_rank = (uint32_t*)arena_take(c, 4 * n);
-  uint32_t* d_sid = (uint32_t*)arena_take(c, 4 * n);
-  uint8_t* d_part = (uint8_t*)arena_take(c, osz * n);
-  uint8_t* d_H = (uint8_t*)arena_take(c, 32 * n_sets);
-  uint32_t* d_flags = (uint32_t*)arena_take(c, 4 * n_sets);
-  int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
-  uint8_t* d_sigp = (uint8_t*)arena_take(c, 288 * n_sets);
-  uint8_t* d_apk = (uint8_t*)arena_take(c, 288 * n_sets);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n_sets);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_sets);
-  if (!d_offs || !d_bytes || !d_sorted || !d_scal || !d_rank || !d_sid || !d_part || !d_H || !d_flags || !d_st || !d_sigp || !d_apk || !d_pairs || !d_f)
-    return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemcpyAsync(d_offs, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
+  const uint64_t* o;
+  if ((rc = upload_offsets(c, offs, &o))) return rc;
+  Carver mem{c};
+  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
+  uint8_t* d_sorted = mem.take<uint8_t>(width * n);
+  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
+  uint32_t* d_rank = mem.take<uint32_t>(4 * n);
+  uint32_t* d_sid = mem.take<uint32_t>(4 * n);
+  uint8_t* d_part = mem.take<uint8_t>(osz * n);
+  uint8_t* d_H = mem.take<uint8_t>(32 * n_sets);
+  uint32_t* d_flags = mem.take<uint32_t>(4 * n_sets);
+  const set_tail tail(mem, n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
-  const uint64_t* o = d_offs;
   const uint8_t* kp = (const uint8_t*)d_pks;
   if (n) {
     // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:42,47,272-275)
@@ -3992,18 +4028,11 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
     }
     c->arena_off = mark;
   }
-  // every set's signature as RAW_PROJ, its key, its status so far; then ONE verification tail over all sets (core_verify with the
-  // scheme's DST and no key prefix, reference :236-246) that skips the sets already decided
-  with_group(sig_group, [&](auto G) {
-    KL(KID_SECURE_OUT, k_secure_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, d_flags, (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt,
-       d_sigp, d_apk, d_st);
-  });
-  if ((rc = run_verify_items(c, sig_group, 0, d_apk, d_sigp, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msgs, (const uint64_t*)d_moffs, 0,
-                             scheme_dst(sig_group, scheme), n_sets, d_pairs, d_f, d_st, 1)))
-    return rc;
-  KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, d_st);
+  // the tail: core_verify with the scheme's DST and no key prefix (reference :236-246); a set's key sum lies at its first key's record
+  if ((rc = run_set_tail(c, tail, sig_group, scheme, 0, KID_SECURE_OUT, n_sets, o, o, d_flags, d_part, d_sigs, fmt, d_msgs, d_moffs))) return rc;
+  KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, tail.st);
   HIPCK(hipGetLastError());
-  return status_out_and_sync(c, status, d_st, n_sets);
+  return status_out_and_sync(c, status, tail.st, n_sets);
 }
 API_CATCH
 
@@ -4014,13 +4043,8 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
   if (rc) return rc;
   if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
   if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  // the set offsets decide every size of the call: read (and check) them on the host
-  std::vector<uint64_t> offs(n_sets + 1);
-  if (is_device_ptr(set_offsets)) HIPCK(hipMemcpy(offs.data(), set_offsets, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
-  else memcpy(offs.data(), set_offsets, 8 * (n_sets + 1));
-  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "set_offsets[0] must be 0");
-  for (size_t s = 0; s < n_sets; s++)
-    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "set_offsets must not decrease");
+  std::vector<uint64_t> offs;
+  if ((rc = read_offsets(set_offsets, n_sets, "set_offsets", offs))) return rc;
   const size_t T = (size_t)offs[n_sets];
   if (T >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more pairs in one call");
   if (T && !pks) return fail(BLSGPU_E_ARG, "null argument");
@@ -4090,32 +4114,31 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
   const uint8_t* mp = (const uint8_t*)d_msgs;
   const uint64_t* mo = (const uint64_t*)d_moffs;
   if (n_b) {
-    uint64_t* d_boffs = (uint64_t*)arena_take(c, 8 * (n_b + 1));
-    uint64_t* d_bsrc = (uint64_t*)arena_take(c, 8 * n_b);
-    uint32_t* d_bset = (uint32_t*)arena_take(c, 4 * n_b);
-    int32_t* d_bad = (int32_t*)arena_take(c, 4 * M);
-    uint32_t* d_sid = (uint32_t*)arena_take(c, 4 * (T_b ? T_b : 1));
-    uint32_t* d_src = (uint32_t*)arena_take(c, 4 * (T_b ? T_b : 1));
-    uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIR1_WORDS * 4 * M);
-    uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * M);
-    uint32_t* d_rec = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_b);
-    uint32_t* d_first = (uint32_t*)arena_take(c, 4 * n_b);
-    uint32_t* d_sigid = (uint32_t*)arena_take(c, 4 * n_b);
-    uint32_t* d_best = (uint32_t*)arena_take(c, 4 * n_b);
-    int32_t* d_stb = (int32_t*)arena_take(c, 4 * n_b);
+    const uint64_t* bo;
+    if ((rc = upload_offsets(c, boffs, &bo))) return rc;
+    Carver mem{c};
+    uint64_t* d_bsrc = mem.take<uint64_t>(8 * n_b);
+    uint32_t* d_bset = mem.take<uint32_t>(4 * n_b);
+    int32_t* d_bad = mem.take<int32_t>(4 * M);
+    uint32_t* d_sid = mem.take<uint32_t>(4 * (T_b ? T_b : 1));
+    uint32_t* d_src = mem.take<uint32_t>(4 * (T_b ? T_b : 1));
+    uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * M);
+    uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * M);
+    uint32_t* d_rec = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n_b);
+    uint32_t* d_first = mem.take<uint32_t>(4 * n_b);
+    uint32_t* d_sigid = mem.take<uint32_t>(4 * n_b);
+    uint32_t* d_best = mem.take<uint32_t>(4 * n_b);
+    int32_t* d_stb = mem.take<int32_t>(4 * n_b);
     uint32_t *d_tab = nullptr, *d_minidx = nullptr, *d_slot = nullptr;
     if (dup_b) {
-      d_tab = (uint32_t*)arena_take(c, 4 * dup_cap);
-      d_minidx = (uint32_t*)arena_take(c, 4 * dup_cap);
-      d_slot = (uint32_t*)arena_take(c, 4 * T_b);
+      d_tab = mem.take<uint32_t>(4 * dup_cap);
+      d_minidx = mem.take<uint32_t>(4 * dup_cap);
+      d_slot = mem.take<uint32_t>(4 * T_b);
     }
-    if (!d_boffs || !d_bsrc || !d_bset || !d_bad || !d_sid || !d_src || !d_pairs || !d_f || !d_rec || !d_first || !d_sigid || !d_best || !d_stb ||
-        (dup_b && (!d_tab || !d_minidx || !d_slot)))
-      return fail(BLSGPU_E_HIP, "internal: arena too small");
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
     const size_t lanes_round = row_stride(lanes_for(per_round)), lanes_fx = row_stride(lanes_for(fx_chunk));
     if (lines_reserve(c, std::max((size_t)MILLER_ENTRIES * LINE3_WORDS_H * 4 * lanes_round, (size_t)FX_STORE_WORDS * 4 * lanes_fx)))
       return fail(BLSGPU_E_HIP, "no room for the line workspace");
-    HIPCK(hipMemcpyAsync(d_boffs, boffs.data(), 8 * (n_b + 1), hipMemcpyHostToDevice, c->stream));
     HIPCK(hipMemcpyAsync(d_bsrc, bsrc.data(), 8 * n_b, hipMemcpyHostToDevice, c->stream));
     HIPCK(hipMemcpyAsync(d_bset, bset.data(), 4 * n_b, hipMemcpyHostToDevice, c->stream));
     HIPCK(hipMemsetAsync(d_bad, 0, 4 * M, c->stream));
@@ -4127,7 +4150,6 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
     const int agg_lanes_env = (int)knobs().agg_lanes;
     const int one_lane = agg_lanes_env == 1 || (agg_lanes_env != 2 && M > 65536 + 1024);
     const int agg_flags = sig_group == 1 ? (one_lane ? 2 : 3) : 1;
-    const uint64_t* bo = d_boffs;
     with_group(sig_group, [&](auto G) {
       KL(KID_PREPARE_AGG, k_prepare_agg_seg<G()>, dim3(blocks_for((agg_flags & 1) ? 2 * M : M)), dim3(BLS_BLOCK), M, T_b, n_b, bo, (const uint64_t*)d_bsrc,
          (const uint32_t*)d_bset, kp, sp, fmt, aug, mp, mo, dst, d_pairs, d_bad, d_sid, d_src, agg_flags);
@@ -4197,25 +4219,13 @@ int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const 
   if (rc) return rc;
   if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
   if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  // the offsets decide every size of the call: read (and check) them on the host
-  auto read_offsets = [&](const uint64_t* src, std::vector<uint64_t>& dst) -> int {
-    dst.resize(n_sets + 1);
-    if (is_device_ptr(src)) HIPCK(hipMemcpy(dst.data(), src, 8 * (n_sets + 1), hipMemcpyDeviceToHost));
-    else memcpy(dst.data(), src, 8 * (n_sets + 1));
-    return 0;
-  };
   std::vector<uint64_t> offs, moffs;
-  if ((rc = read_offsets(key_offsets, offs))) return rc;
-  if (offs[0] != 0) return fail(BLSGPU_E_ARG, "key_offsets[0] must be 0");
-  for (size_t s = 0; s < n_sets; s++)
-    if (offs[s + 1] < offs[s]) return fail(BLSGPU_E_ARG, "key_offsets must not decrease");
+  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", offs))) return rc;
   const size_t n = (size_t)offs[n_sets];
   if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
   if (n && !pks) return fail(BLSGPU_E_ARG, "null argument");
   if (n_sets == 0) return 0;
-  if ((rc = read_offsets(msg_offsets, moffs))) return rc;
-  for (size_t s = 0; s < n_sets; s++)
-    if (moffs[s + 1] < moffs[s]) return fail(BLSGPU_E_ARG, "msg_offsets must not decrease");
+  if ((rc = read_offsets(msg_offsets, n_sets, "msg_offsets", moffs, false))) return rc;      // set s's message is msgs + moffs[s]
   if (moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
   // one set alone IS blsgpu_multi_verify: its split over the bound devices and its cut tail serve one huge set
   if (n_sets == 1) return blsgpu_multi_verify(sig_group, scheme, pks, n, sigs, msgs + moffs[0], (size_t)(moffs[1] - moffs[0]), fmt, status);
@@ -4239,24 +4249,18 @@ int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const 
   if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
-  uint64_t* d_offs = (uint64_t*)arena_take(c, 8 * (n_sets + 1));
-  uint64_t* d_soffs = (uint64_t*)arena_take(c, 8 * (n_sets + 1));
-  uint32_t* d_ssid = (uint32_t*)arena_take(c, 4 * Q);
-  uint8_t* d_part = (uint8_t*)arena_take(c, osz * Q);
-  int32_t* d_st = (int32_t*)arena_take(c, 4 * n_sets);
-  uint8_t* d_sigp = (uint8_t*)arena_take(c, 288 * n_sets);
-  uint8_t* d_apk = (uint8_t*)arena_take(c, 288 * n_sets);
-  uint32_t* d_pairs = (uint32_t*)arena_take(c, (size_t)WS_PAIRS_WORDS * 4 * n_sets);
-  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n_sets);
-  if (!d_offs || !d_soffs || !d_ssid || !d_part || !d_st || !d_sigp || !d_apk || !d_pairs || !d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemcpyAsync(d_offs, offs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCK(hipMemcpyAsync(d_soffs, soffs.data(), 8 * (n_sets + 1), hipMemcpyHostToDevice, c->stream));
+  const uint64_t *o, *so;
+  if ((rc = upload_offsets(c, offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
+  Carver mem{c};
+  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
+  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
+  const set_tail tail(mem, n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if (Q) {
     HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
     // MultiPublicKey::from_public_keys per set: the serial `g += key` of reference src/traits/pk_multi.rs:7-13 as one strip sum per
     // lane (lane pair for G2 keys), then a segmented pairwise tree over every set's strips
     const uint8_t* kp = (const uint8_t*)d_pks;
-    const uint64_t *o = d_offs, *so = d_soffs;
     const uint32_t* sid = d_ssid;
     with_group(pk_group, [&](auto G) {
       KL(KID_MULTI_SEG_ACCUM, k_multi_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, kp, fmt, o, so, sid, d_part);
@@ -4264,17 +4268,12 @@ int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const 
     for (uint64_t step = 1; step < qmax; step <<= 1)
       with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
   }
-  // every set's signature as RAW_PROJ and its key; then ONE verification tail over all sets: core_verify with the scheme's DST,
-  // under MessageAugmentation with the summed key's bytes in front of the message (reference src/traits/sig_aug.rs:20-24)
-  with_group(sig_group, [&](auto G) {
-    KL(KID_MULTI_OUT, k_multi_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const uint64_t*)d_offs, (const uint64_t*)d_soffs,
-       (const uint8_t*)d_part, (const uint8_t*)d_sigs, fmt, d_sigp, d_apk, d_st);
-  });
-  if ((rc = run_verify_items(c, sig_group, scheme == BLSGPU_SCHEME_AUG, d_apk, d_sigp, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msgs,
-                             (const uint64_t*)d_moffs, 0, scheme_dst(sig_group, scheme), n_sets, d_pairs, d_f, d_st, 1)))
-    return rc;
+  // the tail: core_verify with the scheme's DST, under MessageAugmentation with the summed key's bytes in front of the message
+  // (reference src/traits/sig_aug.rs:20-24); a set's key sum lies at its first strip's record and no set is decided before the tail
+  rc = run_set_tail(c, tail, sig_group, scheme, scheme == BLSGPU_SCHEME_AUG, KID_MULTI_OUT, n_sets, o, so, nullptr, d_part, d_sigs, fmt, d_msgs, d_moffs);
+  if (rc) return rc;
   HIPCK(hipGetLastError());
-  return status_out_and_sync(c, status, d_st, n_sets);
+  return status_out_and_sync(c, status, tail.st, n_sets);
 }
 API_CATCH
 }  // extern "C"

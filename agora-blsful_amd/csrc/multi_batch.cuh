@@ -61,9 +61,4 @@ template <>
 __global__ void k_multi_accumulate_seg<1>(size_t, const uint8_t*, int, const uint64_t*, const uint64_t*, const uint32_t*, uint8_t*);
 template <>
 __global__ void k_multi_accumulate_seg<2>(size_t, const uint8_t*, int, const uint64_t*, const uint64_t*, const uint32_t*, uint8_t*);
-// SG: the signature group.  One lane per set: the signature as RAW_PROJ, the set's summed key (the identity for an empty set),
-// status BLS_OK for the verification tail to start from
-template <int SG>
-__global__ void k_multi_out(size_t n_sets, const uint64_t* key_offs, const uint64_t* strip_offs, const uint8_t* part, const uint8_t* sigs,
-                            int fmt, uint8_t* sig_proj, uint8_t* apk, int32_t* status);
 #endif

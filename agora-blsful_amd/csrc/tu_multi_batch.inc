@@ -1,8 +1,8 @@
 // Kernels of the batched multi verify (blsgpu_multi_verify_batch, multi_batch.cuh), included by tu_multi_batch1.hip
-// (BLS_TU_MULTI_BATCH = 1: G1 keys, i.e. Bls12381G2Impl, and k_multi_out<2>) and tu_multi_batch2.hip (BLS_TU_MULTI_BATCH = 2: G2
-// keys, i.e. Bls12381G1Impl, and k_multi_out<1>).  The fold between them is k_share_fold (tu_shares.inc).
+// (BLS_TU_MULTI_BATCH = 1: G1 keys, i.e. Bls12381G2Impl) and tu_multi_batch2.hip (BLS_TU_MULTI_BATCH = 2: G2 keys, i.e.
+// Bls12381G1Impl).  The fold after it is k_share_fold (tu_shares.inc); the hand-over to the verification tail is k_set_out
+// (tu_secure.inc).
 //   k_multi_accumulate_seg : every strip's plain sum of its keys, one RAW_PROJ partial per strip
-//   k_multi_out            : per set the signature as RAW_PROJ, the summed key, status BLS_OK
 #include "kernels.cuh"
 #include "multi_batch.cuh"
 
@@ -46,26 +46,3 @@ __global__ void __launch_bounds__(BLS_BLOCK, 2) k_multi_accumulate_seg<2>(size_t
   st_g2s(part, g, acc);
 }
 #endif
-
-// the signature group is the other one: this unit's keys are in group BLS_TU_MULTI_BATCH, its signatures in 3 - BLS_TU_MULTI_BATCH
-template <int SG>
-__global__ void __launch_bounds__(BLS_BLOCK) k_multi_out(size_t n_sets, const uint64_t* key_offs, const uint64_t* strip_offs, const uint8_t* part,
-                                                       const uint8_t* sigs, int fmt, uint8_t* sig_proj, uint8_t* apk, int32_t* status) {
-  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n_sets) return;
-  typedef grp<SG> SP;
-  typedef grp<3 - SG> KP;
-  typename SP::jac_t sg;
-  SP::load(sg, sigs, s, fmt);
-  SP::store(sig_proj, s, sg);
-  uint32_t* w = (uint32_t*)(apk + s * KP::PROJ_BYTES);
-  if (key_offs[s + 1] != key_offs[s]) {
-    const uint32_t* src = (const uint32_t*)(part + strip_offs[s] * KP::PROJ_BYTES);
-    for (int k = 0; k < KP::PROJ_BYTES / 4; k++) w[k] = src[k];
-  } else {
-    for (int k = 0; k < KP::PROJ_BYTES / 4; k++) w[k] = 0u;      // no keys: the identity (Z = 0)
-  }
-  status[s] = BLS_OK;
-}
-template __global__ void k_multi_out<3 - BLS_TU_MULTI_BATCH>(size_t, const uint64_t*, const uint64_t*, const uint8_t*, const uint8_t*, int, uint8_t*,
-                                                             uint8_t*, int32_t*);

@@ -1,12 +1,13 @@
 // Kernels of the batched verify_secure (blsgpu_verify_secure_batch, secure.cuh), included by tu_secure1.hip (BLS_TU_SECURE = 1:
 // the sort and the hashes) and tu_secure2.hip (BLS_TU_SECURE = 2: the point kernels).  Only the sets below
-// BLSGPU_SECURE_BATCH_MAX keys run here (SECURE_F_LARGE clear); the key sum between k_secure_coeff and k_secure_out is
+// BLSGPU_SECURE_BATCH_MAX keys run here (SECURE_F_LARGE clear); the key sum between k_secure_coeff and k_set_out is
 // k_share_ladder / k_share_fold of the threshold recovery (tu_shares.inc).
 //   k_secure_rank   : the key's position in its set under the stable byte-lexicographic order (reference src/secure_aggregation.rs:41-42)
 //   k_secure_gather : every set's keys as one contiguous sorted stream
 //   k_secure_digest : H_s = SHA-256 of set s's stream (:45-49), one wave per set
 //   k_secure_coeff  : t = SHA-256(BE32(position) || H_s) mod r into the key's input slot (:61-100); a zero flags the set
-//   k_secure_out    : the signature as RAW_PROJ, the set's summed key, the status the verification tail starts from
+//   k_set_out       : the signature as RAW_PROJ, the set's summed key, the status the verification tail starts from; shared
+//                     with the batched multi verify (no flags there: status BLS_OK)
 //   k_secure_fin    : after the tail, the verdict of the empty sets (:189-195)
 #include "kernels.cuh"
 #include "secure.cuh"
@@ -144,12 +145,15 @@ template __global__ void k_secure_rank<24>(size_t, const uint64_t*, size_t, cons
 #endif
 
 #if BLS_TU_SECURE == 2
-// SG: the signature group (the keys live in the other one).  part[offs[s]] holds set s's key sum (k_share_fold, or the large
-// set's MSM result copied there).  Status before the tail: INVALID_SIGNATURE stands in for an empty set (non-OK, so the tail
-// skips it; k_secure_fin decides), INVALID_COEFFICIENT comes before any verification (:97-100), OK lets the tail decide.
+// SG: the signature group (the keys live in the other one).  part[part_offs[s]] holds set s's key sum: part_offs is key_offs where
+// there is one record per key (k_share_fold, or the large set's MSM result copied there), the strip offsets of the batched multi
+// verify where there is one per strip.  With flags (the batched verify_secure) the status before the tail is INVALID_SIGNATURE for
+// an empty set (non-OK, so the tail skips it; k_secure_fin decides), INVALID_COEFFICIENT before any verification (:97-100), else
+// OK; without flags it is OK and the tail decides everything.
 template <int SG>
-__global__ void __launch_bounds__(BLS_BLOCK) k_secure_out(size_t n_sets, const uint64_t* offs, uint32_t* flags, const uint8_t* part,
-                                                        const uint8_t* sigs, int fmt, uint8_t* sig_proj, uint8_t* apk, int32_t* status) {
+__global__ void __launch_bounds__(BLS_BLOCK) k_set_out(size_t n_sets, const uint64_t* key_offs, const uint64_t* part_offs, uint32_t* flags,
+                                                     const uint8_t* part, const uint8_t* sigs, int fmt, uint8_t* sig_proj, uint8_t* apk,
+                                                     int32_t* status) {
   const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_sets) return;
   typedef grp<SG> SP;
@@ -157,19 +161,23 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_out(size_t n_sets, const u
   typename SP::jac_t sg;
   SP::load(sg, sigs, s, fmt);
   SP::store(sig_proj, s, sg);
-  uint32_t f = flags[s];
-  if (jac_is_inf(sg)) f |= SECURE_F_IDSIG;
-  flags[s] = f;
-  const uint64_t lo = offs[s], cnt = offs[s + 1] - lo;
+  const bool empty = key_offs[s + 1] == key_offs[s];
   uint32_t* w = (uint32_t*)(apk + s * KP::PROJ_BYTES);
-  if (cnt) {
-    const uint32_t* src = (const uint32_t*)(part + lo * KP::PROJ_BYTES);
+  if (!empty) {
+    const uint32_t* src = (const uint32_t*)(part + part_offs[s] * KP::PROJ_BYTES);
     for (int k = 0; k < KP::PROJ_BYTES / 4; k++) w[k] = src[k];
   } else {
-    for (int k = 0; k < KP::PROJ_BYTES / 4; k++) w[k] = 0u;
+    for (int k = 0; k < KP::PROJ_BYTES / 4; k++) w[k] = 0u;      // no keys: the identity (Z = 0)
   }
-  status[s] = cnt == 0 ? BLS_ERR_INVALID_SIGNATURE : (f & SECURE_F_ZERO) ? BLS_ERR_INVALID_COEFFICIENT : BLS_OK;
+  int32_t st = BLS_OK;
+  if (flags) {
+    uint32_t f = flags[s];
+    if (jac_is_inf(sg)) f |= SECURE_F_IDSIG;
+    flags[s] = f;
+    st = empty ? BLS_ERR_INVALID_SIGNATURE : (f & SECURE_F_ZERO) ? BLS_ERR_INVALID_COEFFICIENT : BLS_OK;
+  }
+  status[s] = st;
 }
-template __global__ void k_secure_out<1>(size_t, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
-template __global__ void k_secure_out<2>(size_t, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
+template __global__ void k_set_out<1>(size_t, const uint64_t*, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
+template __global__ void k_set_out<2>(size_t, const uint64_t*, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
 #endif

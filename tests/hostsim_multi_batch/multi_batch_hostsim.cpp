@@ -13,7 +13,7 @@ static uint64_t addm(uint64_t a, uint64_t b) { return (a + b) % PRIME; }
 extern "C" {
 uint64_t hs_multi_strip_len(uint64_t N, uint64_t lanes, uint64_t forced) { return multi_strip_len(N, lanes, forced); }
 
-// plan, k_multi_accumulate_seg, the levels of k_share_fold over the strips, k_multi_out's pick.
+// plan, k_multi_accumulate_seg, the levels of k_share_fold over the strips, k_set_out's pick.
 //   in : key_offs (n_sets + 1), L, vals (one per key)
 //   out: strip_offs (n_sets + 1), strip_sid (cap entries), reads (per key: how many strips read it), sums (per set:
 //        part[strip_offs[s]], untouched for an empty set), n_strips, qmax
