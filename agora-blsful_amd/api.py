@@ -6,6 +6,8 @@ The reference is a Rust crate and no Rust toolchain exists in this image, so thi
     Signature::verify / verify_secure / verify_secure_with_mode     reference src/signature.rs:130-138,177-197,256-276
     MultiSignature::verify + MultiPublicKey::from_public_keys      src/multi_signature.rs:127-135, src/multi_public_key.rs:79-83
     AggregateSignature::verify                                     src/aggregate_signature.rs:230-239
+    MultiSignature::from_signatures                                src/multi_signature.rs:80-107,147
+    AggregateSignature::from_signatures / from_signatures_secure   src/aggregate_signature.rs:123-148,171,191-227
     BlsError                                                       src/error.rs:5-55
 
 so that the parity tests read like the reference's own tests.  Points are held as RAW_PROJ byte strings (the
@@ -40,6 +42,7 @@ EXPORTS = [
     'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
+    'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
 ]
 
 
@@ -161,6 +164,8 @@ def load_library(path=None):
         lib.blsgpu_multi_verify_batch.argtypes = [ci, ci, vp, vp, sz, vp, vp, vp, ci, vp]
         lib.blsgpu_signcrypt_share_verify_batch.argtypes = [ci, ci, vp, vp, u8p, u64p, sz, vp, vp, u64p, ci, i32p]
         lib.blsgpu_signcrypt_open_batch.argtypes = [ci, ci, vp, vp, u8p, u64p, sz, u8p, vp, u64p, ci, u8p, u64p, i32p]
+        lib.blsgpu_aggregate_secure_batch.argtypes = [ci, vp, vp, u64p, sz, ci, ci, vp, i32p]
+        lib.blsgpu_sum_batch.argtypes = [ci, vp, u64p, sz, ci, vp]
         _lib = lib
     return _lib
 
@@ -511,6 +516,41 @@ def aggregate_secure(sig_group, pks, sigs, ser_format=MODERN, fmt=FMT_RAW_PROJ):
     return st.value, out.raw
 
 
+def aggregate_secure_batch(sig_group, sets, ser_format=MODERN, fmt=FMT_RAW_PROJ):
+    """aggregate_secure[_with_mode] for many independent sets in one call (blsgpu_aggregate_secure_batch): `sets` is a list of
+    (pks, sigs) with raw points in `fmt`, one signature per key.  Returns (RAW_PROJ aggregate signatures, statuses), one per set,
+    each what aggregate_secure gives for that set alone."""
+    for s, (pks, sigs) in enumerate(sets):
+        if len(pks) != len(sigs):
+            raise ValueError('aggregate_secure_batch: set %d has %d keys and %d signatures' % (s, len(pks), len(sigs)))
+    lib = init()
+    n_sets = len(sets)
+    koffs = _count_offsets([pks for pks, _ in sets])
+    pkb = b''.join(p for pks, _ in sets for p in pks)
+    sgb = b''.join(g for _, sigs in sets for g in sigs)
+    osz = 144 if sig_group == 1 else 288
+    out = ctypes.create_string_buffer(osz * max(n_sets, 1))
+    stv = (ctypes.c_int32 * max(n_sets, 1))()
+    _check(lib.blsgpu_aggregate_secure_batch(sig_group, _ptr(pkb) if pkb else None, _ptr(sgb) if sgb else None, ctypes.cast(koffs, ctypes.c_void_p),
+                                             n_sets, ser_format, fmt, ctypes.cast(out, ctypes.c_void_p), ctypes.cast(stv, ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[osz * i:osz * (i + 1)] for i in range(n_sets)], list(stv)[:n_sets]
+
+
+def sum_batch(group, sets, fmt=FMT_RAW_PROJ):
+    """The plain point sum of many independent sets in one call (blsgpu_sum_batch): `sets` is a list of lists of raw points of
+    `group` in `fmt`.  Returns one RAW_PROJ point per set, the identity for an empty set."""
+    lib = init()
+    n_sets = len(sets)
+    offs = _count_offsets(sets)
+    blob = b''.join(p for st in sets for p in st)
+    osz = 144 if group == 1 else 288
+    out = ctypes.create_string_buffer(osz * max(n_sets, 1))
+    _check(lib.blsgpu_sum_batch(group, _ptr(blob) if blob else None, ctypes.cast(offs, ctypes.c_void_p), n_sets, fmt, ctypes.cast(out, ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[osz * i:osz * (i + 1)] for i in range(n_sets)]
+
+
 def combine_shares(group, sets, fmt=FMT_RAW_PROJ):
     """Threshold recovery of many independent sets in one call (blsgpu_combine_shares): `sets` is a list of lists of
     (identifier: int, raw point, scheme or None).  Scheme tags are checked only when every share of the call carries one
@@ -813,6 +853,27 @@ class TensorOps:
                                                   FMT_RAW_PROJ, self._p(st)))
         return st[:n_sets]
 
+    def aggregate_secure_batch(self, sg, pks, sigs, key_offs, n_sets, ser_format=MODERN):
+        """(RAW_PROJ aggregate signatures as one uint8 tensor of n_sets records, int32 statuses), both on the device, of n_sets
+        aggregate_secure sums over device-resident RAW_PROJ keys and signatures (one per key) and their int64 offsets (n_sets + 1
+        entries).  The records can go straight into verify_secure_batch as its `sigs`."""
+        self._sync()
+        osz = 144 if sg == 1 else 288
+        out = self.empty(max(n_sets, 1) * osz)
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        _check(self.lib.blsgpu_aggregate_secure_batch(sg, self._p(pks), self._p(sigs), self._p(key_offs), n_sets, ser_format, FMT_RAW_PROJ,
+                                                      self._p(out), self._p(st)))
+        return out[:n_sets * osz], st[:n_sets]
+
+    def sum_batch(self, group, pts, offs, n_sets, fmt=FMT_RAW_PROJ):
+        """RAW_PROJ sums (one uint8 tensor of n_sets records, on the device) of n_sets ragged sets of device-resident points of
+        `group` with int64 offsets (n_sets + 1 entries).  The records can go into the batched verifiers as `pks` or `sigs`."""
+        self._sync()
+        osz = 144 if group == 1 else 288
+        out = self.empty(max(n_sets, 1) * osz)
+        _check(self.lib.blsgpu_sum_batch(group, self._p(pts), self._p(offs), n_sets, fmt, self._p(out)))
+        return out[:n_sets * osz]
+
     def multi_verify(self, sg, scheme, pks, n, sig, msg):
         self._sync()
         st = ctypes.c_int32(-99)
@@ -970,6 +1031,71 @@ def aggregate_verify_many(items):
     return out
 
 
+def _plain_sum_error(sigs, refuse_aug):
+    """The BlsError of TryFrom<&[Signature]> for MultiSignature (refuse_aug) / AggregateSignature, or None: fewer than two
+    signatures; then, walking sigs[1:], a scheme other than the first one's or (MultiSignature only, reference
+    src/multi_signature.rs:92-97) a MessageAugmentation signature."""
+    if len(sigs) < 2:
+        return BlsError('InvalidSignature')
+    for s in sigs[1:]:
+        if s.scheme != sigs[0].scheme or (refuse_aug and s.scheme == AUG):
+            return BlsError('InvalidSignatureScheme')
+    return None
+
+
+def _plain_sums_many(items, cls, refuse_aug):
+    out = [_plain_sum_error(sigs, refuse_aug) for sigs in items]
+    for sg in (1, 2):
+        idx = [i for i, sigs in enumerate(items) if out[i] is None and sigs[0].impl.sig_group == sg]
+        if not idx:
+            continue
+        if any(s.impl.sig_group != sg for i in idx for s in items[i]):
+            raise ValueError('the signatures of one item must share one impl')
+        pts = sum_batch(sg, [[s.raw for s in items[i]] for i in idx])
+        for i, p in zip(idx, pts):
+            out[i] = cls(items[i][0].impl, items[i][0].scheme, p)
+    return out
+
+
+def multi_signatures_many(items):
+    """MultiSignature.from_signatures over many items at once: `items` is a list of [Signature].  The error cases are decided on
+    the host; the remaining items go into one blsgpu_sum_batch call per impl.  Returns one MultiSignature or BlsError per item."""
+    return _plain_sums_many(items, MultiSignature, True)
+
+
+def aggregate_signatures_many(items):
+    """AggregateSignature.from_signatures over many items at once: `items` is a list of [Signature].  The error cases are decided
+    on the host; the remaining items go into one blsgpu_sum_batch call per impl.  Returns one AggregateSignature or BlsError per
+    item."""
+    return _plain_sums_many(items, AggregateSignature, False)
+
+
+def aggregate_secure_many(items, mode=MODERN):
+    """AggregateSignature.from_signatures_secure over many items at once: `items` is a list of ([Signature], [PublicKey]) or
+    ([Signature], [PublicKey], mode) -- the serialisation of aggregate_secure_with_mode, `mode` where an item names none.  The
+    error cases are decided on the host in the reference's order (src/aggregate_signature.rs:197-212); the remaining items go into
+    one blsgpu_aggregate_secure_batch call per (impl, serialisation).  Returns one AggregateSignature or BlsError per item."""
+    out, groups = [None] * len(items), {}
+    for i, it in enumerate(items):
+        sigs, pks = it[0], it[1]
+        if len(sigs) != len(pks):
+            out[i] = BlsError('InvalidInputs', 'Mismatched array lengths')
+        elif not sigs:
+            out[i] = BlsError('InvalidInputs', 'Empty signatures array')
+        elif any(s.scheme != sigs[0].scheme for s in sigs[1:]):
+            out[i] = BlsError('InvalidSignatureScheme')
+        else:
+            sg = sigs[0].impl.sig_group
+            if any(x.impl.sig_group != sg for x in list(sigs) + list(pks)):
+                raise ValueError('the signatures and keys of one item must share one impl')
+            groups.setdefault((sg, it[2] if len(it) > 2 else mode), []).append(i)
+    for (sg, ser), idx in sorted(groups.items()):
+        pts, sts = aggregate_secure_batch(sg, [([p.raw for p in items[i][1]], [s.raw for s in items[i][0]]) for i in idx], ser)
+        for i, p, st in zip(idx, pts, sts):
+            out[i] = error_from_status(st) or AggregateSignature(items[i][0][0].impl, items[i][0][0].scheme, p)
+    return out
+
+
 class Impl:
     def __init__(self, sig_group):
         self.sig_group = sig_group
@@ -1077,6 +1203,14 @@ class MultiSignature:
     def __init__(self, impl, scheme, raw):
         self.impl, self.scheme, self.raw = impl, scheme, bytes(raw)
 
+    @staticmethod
+    def from_signatures(sigs):
+        """reference src/multi_signature.rs:80-107,147: the plain sum, on the GPU."""
+        r = multi_signatures_many([sigs])[0]
+        if isinstance(r, BlsError):
+            raise r
+        return r
+
     def verify(self, mpk, msg):
         """reference src/multi_signature.rs:127-135."""
         st = multi_verify(self.impl.sig_group, self.scheme, [k.raw for k in mpk.keys], self.raw, bytes(msg))
@@ -1090,6 +1224,22 @@ class AggregateSignature:
 
     def __init__(self, impl, scheme, raw):
         self.impl, self.scheme, self.raw = impl, scheme, bytes(raw)
+
+    @staticmethod
+    def from_signatures(sigs):
+        """reference src/aggregate_signature.rs:123-148,171: the plain sum, on the GPU."""
+        r = aggregate_signatures_many([sigs])[0]
+        if isinstance(r, BlsError):
+            raise r
+        return r
+
+    @staticmethod
+    def from_signatures_secure(sigs, public_keys):
+        """reference src/aggregate_signature.rs:191-227: sum t_i sig_i with the coefficients of the key set, on the GPU."""
+        r = aggregate_secure_many([(sigs, public_keys)])[0]
+        if isinstance(r, BlsError):
+            raise r
+        return r
 
     def verify(self, data):
         """data: [(PublicKey, msg)]; reference src/aggregate_signature.rs:230-239."""

@@ -42,6 +42,8 @@ enum {
   KID_AGG_SEG_INDEX, KID_AGG_SEG_FOLD, KID_AGG_SEG_FIN,   // blsgpu_aggregate_verify_batch (its prepare, Miller and final-exp kernels count under theirs)
   KID_MULTI_SEG_ACCUM, KID_MULTI_OUT,                     // blsgpu_multi_verify_batch (its fold counts under KID_SHARE_FOLD)
   KID_SIGNCRYPT_GATHER, KID_SIGNCRYPT_KEYSTREAM,          // blsgpu_signcrypt_share_verify_batch / blsgpu_signcrypt_open_batch
+  KID_SECURE_FIRST, KID_SECURE_LADDER, KID_SECURE_AGG_FOLD, KID_SECURE_AGG_OUT,   // blsgpu_aggregate_secure_batch (rank .. coeff count under theirs)
+  KID_SUM_SEG_ACCUM, KID_SUM_FOLD, KID_SUM_OUT,           // blsgpu_sum_batch
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
@@ -51,7 +53,9 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_secure_rank", "k_secure_gather", "k_secure_digest", "k_secure_coeff", "k_secure_out", "k_secure_fin",
                                     "k_agg_seg_index", "k_f12_fold_seg", "k_agg_batch_fin",
                                     "k_multi_accumulate_seg", "k_multi_out",
-                                    "k_signcrypt_share_pairs", "k_signcrypt_keystream"};
+                                    "k_signcrypt_share_pairs", "k_signcrypt_keystream",
+                                    "k_secure_first", "k_secure_ladder", "k_secure_agg_fold", "k_secure_agg_out",
+                                    "k_sum_accumulate_seg", "k_sum_fold", "k_sum_out"};
 
 struct Ctx {
   int dev = -1;
@@ -162,7 +166,7 @@ struct Knobs {
   long post_split = 3;        // the late part of a cut check runs its Miller loop on this many workgroups (k_pairing_post2: 3, 2; 0 or 1: one)
   long host_trace = 0, strict_env = 0, ab_knobs = 0;
   long shares_msm_min = 1024; // blsgpu_combine_shares: a set of at least this many shares is summed by the bucket MSM, not per-share ladders
-  long secure_batch_max = 1024; // blsgpu_verify_secure_batch: a set of at least this many keys runs through blsgpu_verify_secure's machinery
+  long secure_batch_max = 1024; // blsgpu_verify_secure_batch, blsgpu_aggregate_secure_batch: a set of at least this many keys runs through blsgpu_verify_secure's machinery
   long agg_batch_max = 32768;  // blsgpu_aggregate_verify_batch: a set of at least this many pairs runs through blsgpu_aggregate_verify's machinery
   long multi_strip = 0;        // blsgpu_multi_verify_batch: keys per strip of the segmented key sum (0: one strip per lane of a single sum, at least 4)
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
@@ -1681,6 +1685,39 @@ int run_coefficients(Ctx* c, const uint8_t* d_H, const uint32_t* d_perm, size_t 
   return 0;
 }
 
+// ---- secure aggregation of ONE key set (blsgpu_aggregate_secure, and the large sets of blsgpu_aggregate_secure_batch): from the set's
+// serialised keys d_bytes and its signatures d_sigs to sum_p t_p sig[idx_p] in d_part[0] (d_part: T records).  Device sort, host
+// SHA-256 of the sorted stream, the coefficients in sorted order, idx_p = the FIRST input position holding the key of sorted
+// position p (the reference's `position` search: the sort is stable, so that is the input index at the start of p's run of equal
+// keys), one weighted point sum.  A zero coefficient ORs 1 into *d_zero.  Synchronises the stream (the sort); its workspace comes
+// from the arena (aggregate_secure_set_bytes).
+size_t aggregate_secure_set_bytes(size_t n, size_t width) {
+  return 2 * pad256(4 * n) + pad256(4 * scan_tiles(n)) + pad256(32 * n) + 256 + msm_ws_bytes(n) + keysort_ws_bytes(n, width);
+}
+int run_aggregate_secure_set(Ctx* c, int sig_group, const uint8_t* d_bytes, const uint8_t* d_sigs, size_t n, size_t width, int fmt, int32_t* d_zero,
+                             uint8_t* d_part, size_t T) {
+  Carver mem{c};
+  uint32_t* d_idx = mem.take<uint32_t>(4 * n);
+  uint32_t* d_start = mem.take<uint32_t>(4 * n);
+  uint32_t* d_tiles = mem.take<uint32_t>(4 * scan_tiles(n));
+  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
+  uint8_t* d_H = mem.take<uint8_t>(64);
+  keysort_ws w;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  int rc = keysort_ws_take(c, n, width, w);
+  if (rc) return rc;
+  if ((rc = run_key_sort_to_host(c, d_bytes, n, width, w, nullptr, nullptr))) return rc;
+  uint8_t H[32];
+  keys_digest_host(c->hpin, width * n, H);
+  if ((rc = h2d_small(c, d_H, H, 32))) return rc;
+  if ((rc = run_coefficients(c, d_H, w.perm_a, n, 0, n, 1, d_scal, d_zero))) return rc;
+  KL(KID_KEY_SORT, k_keys_run_start, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_bytes, width, (const uint32_t*)w.perm_a, d_start);
+  if ((rc = run_scan_max_u32(c, KID_KEY_SORT, n, d_start, d_tiles))) return rc;
+  KL(KID_KEY_SORT, k_run_first_index, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)w.perm_a, (const uint32_t*)d_start, d_idx);
+  HIPCK(hipGetLastError());
+  return with_group(sig_group, [&](auto G) { return run_point_sum<G()>(c, d_sigs, fmt, d_scal, d_idx, n, d_part, T); });
+}
+
 // ---- Basic's duplicate-message rule on device-resident messages (util_kernels.cuh) -> d_out2 = (old, i) or (~0, ~0)
 size_t dup_ws_bytes(size_t n) {
   size_t cap = 64;
@@ -3143,8 +3180,7 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
   CTX_ACQUIRE(c);
   const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), T = accumulate_lanes(n);
   const size_t osz = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ);
-  size_t need = pad256(psz * n) + pad256(ssz * n) + pad256(width * n) + 2 * pad256(4 * n) + pad256(32 * n) + pad256(288 * T) + 8192 + msm_ws_bytes(n) +
-                keysort_ws_bytes(n, width) + pad256(4 * scan_tiles(n));
+  size_t need = pad256(psz * n) + pad256(ssz * n) + pad256(width * n) + pad256(288 * T) + 8192 + aggregate_secure_set_bytes(n, width);
   if ((rc = arena_reserve(c, need))) return rc;
   c->arena_off = 0;
   int32_t st = BLSGPU_OK;
@@ -3161,34 +3197,15 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
     if ((rc = stage_in(c, sigs, ssz * n, &d_sigs))) return rc;
     Carver mem{c};
     uint8_t* d_bytes = mem.take<uint8_t>(width * n);
-    uint32_t* d_idx = mem.take<uint32_t>(4 * n);
-    uint32_t* d_start = mem.take<uint32_t>(4 * n);
-    uint32_t* d_tiles = mem.take<uint32_t>(4 * scan_tiles(n));
-    uint8_t* d_scal = mem.take<uint8_t>(32 * n);
-    uint8_t* d_H = mem.take<uint8_t>(64);
     int32_t* d_zero = mem.take<int32_t>(64);
-    keysort_ws w;
     if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-    if ((rc = keysort_ws_take(c, n, width, w))) return rc;
     with_group(key_group(sig_group), [&](auto G) {
       KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, fmt, ser_format, d_bytes);
     });
     HIPCK(hipGetLastError());
-    if ((rc = run_key_sort_to_host(c, d_bytes, n, width, w, nullptr, nullptr))) return rc;
-    uint8_t H[32];
-    keys_digest_host(c->hpin, width * n, H);
-    if ((rc = h2d_small(c, d_H, H, 32))) return rc;
     HIPCK(hipMemsetAsync(d_zero, 0, 4, c->stream));
-    if ((rc = run_coefficients(c, d_H, w.perm_a, n, 0, n, 1, d_scal, d_zero))) return rc;
+    if ((rc = run_aggregate_secure_set(c, sig_group, d_bytes, (const uint8_t*)d_sigs, n, width, fmt, d_zero, d_part, T))) return rc;
     HIPCK(hipMemcpyAsync(h_zero, d_zero, 4, hipMemcpyDeviceToHost, c->stream));
-    // the signature of sorted position i is that of the FIRST input position holding an equal key (the reference's
-    // `position` search): the sort is stable, so that is the input index at the start of i's run of equal keys
-    KL(KID_KEY_SORT, k_keys_run_start, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_bytes, width, (const uint32_t*)w.perm_a, d_start);
-    if ((rc = run_scan_max_u32(c, KID_KEY_SORT, n, d_start, d_tiles))) return rc;
-    KL(KID_KEY_SORT, k_run_first_index, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)w.perm_a, (const uint32_t*)d_start, d_idx);
-    HIPCK(hipGetLastError());
-    rc = with_group(sig_group, [&](auto G) { return run_point_sum<G()>(c, (const uint8_t*)d_sigs, fmt, d_scal, d_idx, n, d_part, T); });
-    if (rc) return rc;
   }
   SYNC_FLUSH(c);
   if (*h_zero) st = BLSGPU_INVALID_COEFFICIENT;
@@ -4274,6 +4291,194 @@ int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const 
   if (rc) return rc;
   HIPCK(hipGetLastError());
   return status_out_and_sync(c, status, tail.st, n_sets);
+}
+API_CATCH
+// ---- batched secure aggregation (secure.cuh): n_sets independent aggregate_secure[_with_mode] sums in one call
+int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* sigs, const uint64_t* key_offsets, size_t n_sets, int ser_format, int fmt,
+                                  void* out_sigs, int32_t* status) try {
+  int rc = check_common(sig_group, 0, fmt);
+  if (rc) return rc;
+  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
+  if (ser_format == 1 && sig_group != 2)
+    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
+  if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
+  if (n_sets && (!out_sigs || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  std::vector<uint64_t> offs;
+  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", offs))) return rc;
+  const size_t n = (size_t)offs[n_sets];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
+  if (n && (!pks || !sigs)) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  const size_t osz = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ);
+  // plan, as blsgpu_verify_secure_batch: a set of at least BLSGPU_SECURE_BATCH_MAX keys runs one at a time through the steps of
+  // blsgpu_aggregate_secure (run_aggregate_secure_set); all others through the segmented kernels of secure.cuh, one ladder per key in
+  // the signature group and a segmented tree sum.  One large set alone IS blsgpu_aggregate_secure.
+  const uint64_t max_small = (uint64_t)knobs().secure_batch_max;
+  if (n_sets == 1 && n >= max_small) {
+    if (is_device_ptr(out_sigs)) HIPCK(hipMemset(out_sigs, 0, osz));      // the single call leaves a failed set's record alone
+    else memset(out_sigs, 0, osz);
+    return blsgpu_aggregate_secure(sig_group, pks, sigs, n, ser_format, fmt, out_sigs, status);
+  }
+  CTX_ACQUIRE(c);
+  const int pk_group = key_group(sig_group);
+  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED);
+  std::vector<uint32_t> hflags(n_sets, 0);
+  uint64_t tmax_small = 0, tmax_large = 0;
+  for (size_t s = 0; s < n_sets; s++) {
+    const uint64_t t = offs[s + 1] - offs[s];
+    if (t >= max_small) {
+      hflags[s] = SECURE_F_LARGE;
+      tmax_large = std::max(tmax_large, t);
+    } else {
+      tmax_small = std::max(tmax_small, t);
+    }
+  }
+  const size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax_small / 256)));
+  const size_t large_bytes = tmax_large ? aggregate_secure_set_bytes(tmax_large, width) + pad256(osz * accumulate_lanes(tmax_large)) +
+                                              pad256(osz * POINT_TREE_START) + 4096
+                                        : 0;
+  rc = arena_reserve(c, pad256(psz * n) + pad256(ssz * n) + pad256(8 * (n_sets + 1)) + 2 * pad256(width * n) + pad256(32 * n) + 3 * pad256(4 * n) +
+                            pad256(osz * n) + pad256(32 * n_sets) + 2 * pad256(4 * n_sets) + pad256(osz * n_sets) + large_bytes + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_pks = nullptr, *d_sigs = nullptr;
+  if (n && (rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
+  if (n && (rc = stage_in(c, sigs, ssz * n, &d_sigs))) return rc;
+  const uint64_t* o;
+  if ((rc = upload_offsets(c, offs, &o))) return rc;
+  Carver mem{c};
+  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
+  uint8_t* d_sorted = mem.take<uint8_t>(width * n);
+  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
+  uint32_t* d_rank = mem.take<uint32_t>(4 * n);
+  uint32_t* d_sid = mem.take<uint32_t>(4 * n);
+  uint32_t* d_first = mem.take<uint32_t>(4 * n);
+  uint8_t* d_part = mem.take<uint8_t>(osz * n);
+  uint8_t* d_H = mem.take<uint8_t>(32 * n_sets);
+  uint32_t* d_flags = mem.take<uint32_t>(4 * n_sets);
+  int32_t* d_st = mem.take<int32_t>(4 * n_sets);
+  uint8_t* d_out = mem.stage_out<uint8_t>(out_sigs, osz * n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
+  const uint8_t *kp = (const uint8_t*)d_pks, *sp = (const uint8_t*)d_sigs;
+  if (n) {
+    // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:141,144,166,349)
+    with_group(pk_group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes); });
+    if (tmax_small) {
+      HIPCK(hipMemsetAsync(d_rank, 0, 4 * n, c->stream));
+      HIPCK(hipMemsetAsync(d_first, 0xff, 4 * n, c->stream));
+      if (width == 96)
+        KL(KID_SECURE_RANK, k_secure_rank<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_flags, d_rank, d_sid);
+      else
+        KL(KID_SECURE_RANK, k_secure_rank<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_flags, d_rank, d_sid);
+      KL(KID_SECURE_GATHER, k_secure_gather, dim3(blocks_for(n * (width / 4))), dim3(BLS_BLOCK), n, width, o, (const uint8_t*)d_bytes,
+         (const uint32_t*)d_rank, (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_sorted);
+      KL(KID_SECURE_DIGEST, k_secure_digest, dim3((unsigned)n_sets), dim3(BLS_BLOCK), n_sets, width, o, (const uint8_t*)d_sorted,
+         (const uint32_t*)d_flags, d_H);
+      KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_rank, (const uint32_t*)d_sid,
+         (const uint8_t*)d_H, d_flags, d_scal);
+      // the signature that goes with the key of a sorted position is that of the FIRST input position holding the same bytes
+      // (reference :138-147): duplicates of a key all take the first copy's signature
+      if (width == 96)
+        KL(KID_SECURE_FIRST, k_secure_first<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_first);
+      else
+        KL(KID_SECURE_FIRST, k_secure_first<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_first);
+      // sum t_i sig[first_i] per set (reference :149-153): one joint NAF ladder per key, then a segmented tree sum
+      with_group(sig_group, [&](auto G) {
+        KL(KID_SECURE_LADDER, k_secure_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, sp, fmt, (const uint8_t*)d_scal, (const uint32_t*)d_first,
+           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+      });
+      for (uint64_t step = 1; step < tmax_small; step <<= 1) {
+        with_group(sig_group, [&](auto G) {
+          KL(KID_SECURE_AGG_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+        });
+      }
+      HIPCK(hipGetLastError());
+    }
+    // the large sets, one at a time as blsgpu_aggregate_secure runs them; the sum goes to the set's first record (where the fold left
+    // the identity), a zero coefficient into the set's flags (1 = SECURE_F_ZERO).  The workspace is reused from set to set; so is
+    // the pinned record of the digest, which the next set writes only after its sort has synchronised the stream.
+    const size_t mark = c->arena_off, hmark = c->hsmall_off;
+    for (size_t s = 0; s < n_sets; s++) {
+      if (!(hflags[s] & SECURE_F_LARGE)) continue;
+      const size_t lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]), T = accumulate_lanes(t);
+      c->arena_off = mark;
+      c->hsmall_off = hmark;
+      uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
+      if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
+      if ((rc = run_aggregate_secure_set(c, sig_group, d_bytes + width * lo, sp + ssz * lo, t, width, fmt, (int32_t*)(d_flags + s), d_msm, T))) return rc;
+      HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
+    }
+    c->arena_off = mark;
+  }
+  with_group(sig_group, [&](auto G) {
+    KL(KID_SECURE_AGG_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out,
+       d_st);
+  });
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out_sigs, d_out, osz * n_sets))) return rc;
+  return status_out_and_sync(c, status, d_st, n_sets);
+}
+API_CATCH
+
+// ---- batched plain sums (multi_batch.cuh): the sum of every one of n_sets ragged sets of points in one call
+int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t n_sets, int fmt, void* out) try {
+  if (!initialised()) return NOT_INIT();
+  if (group != 1 && group != 2) return fail(BLSGPU_E_ARG, "group must be 1 (G1) or 2 (G2)");
+  if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE) return fail(BLSGPU_E_ARG, "fmt must be RAW_PROJ or RAW_AFFINE");
+  if (!offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  if (n_sets && !out) return fail(BLSGPU_E_ARG, "null argument");
+  std::vector<uint64_t> offs;
+  int rc = read_offsets(offsets, n_sets, "offsets", offs);
+  if (rc) return rc;
+  const size_t n = (size_t)offs[n_sets];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more points in one call");
+  if (n && !pts) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  // plan: the strips of the segmented sum (multi_batch.cuh), as blsgpu_multi_verify_batch; one set is a plan with one set
+  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
+  std::vector<uint64_t> soffs;
+  std::vector<uint32_t> ssid;
+  const uint64_t qmax = multi_strip_plan(offs.data(), n_sets, L, soffs, ssid);
+  const size_t Q = ssid.size();
+  CTX_ACQUIRE(c);
+  const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
+  rc = arena_reserve(c, pad256(psz * n) + 2 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) + pad256(osz * n_sets) + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void* d_pts = nullptr;
+  if (n && (rc = stage_in(c, pts, psz * n, &d_pts))) return rc;
+  const uint64_t *o, *so;
+  if ((rc = upload_offsets(c, offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
+  Carver mem{c};
+  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
+  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
+  uint8_t* d_out = mem.stage_out<uint8_t>(out, osz * n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (Q) {
+    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
+    // the serial `g += s` of reference src/multi_signature.rs:87-100 / src/aggregate_signature.rs:130-141 as one strip sum per lane
+    // (lane pair in G2), then a segmented pairwise tree over every set's strips
+    const uint8_t* pp = (const uint8_t*)d_pts;
+    const uint32_t* sid = d_ssid;
+    with_group(group, [&](auto G) {
+      KL(KID_SUM_SEG_ACCUM, k_multi_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, pp, fmt, o, so, sid, d_part);
+    });
+    for (uint64_t step = 1; step < qmax; step <<= 1)
+      with_group(group, [&](auto G) { KL(KID_SUM_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
+  }
+  with_group(group, [&](auto G) {
+    KL(KID_SUM_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, so, (const uint32_t*)nullptr, (const uint8_t*)d_part, d_out,
+       (int32_t*)nullptr);
+  });
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
 }
 API_CATCH
 }  // extern "C"

@@ -9,8 +9,15 @@
 //   k_set_out       : the signature as RAW_PROJ, the set's summed key, the status the verification tail starts from; shared
 //                     with the batched multi verify (no flags there: status BLS_OK)
 //   k_secure_fin    : after the tail, the verdict of the empty sets (:189-195)
+// and of the batched aggregation (blsgpu_aggregate_secure_batch, blsgpu_sum_batch):
+//   k_secure_first  : the first input position of the key's set that holds the same bytes (reference :138-147)
+//   k_secure_ladder : t_i sig[first_i] in the signature group, one joint NAF ladder per key (shares.cuh share_ladder)
+//   k_set_sum_out   : the set's sum (after k_share_fold) and its status to the caller's arrays
 #include "kernels.cuh"
 #include "secure.cuh"
+#if BLS_TU_SECURE == 2
+#include "shares.cuh"
+#endif
 
 #if BLS_TU_SECURE == 1
 // key o sorts before key m: its big-endian words are smaller, or they are equal and o comes first in the input (tie)
@@ -140,6 +147,53 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_secure_fin(size_t n_sets, const u
   if (s >= n_sets || offs[s + 1] != offs[s]) return;
   status[s] = (flags[s] & SECURE_F_IDSIG) ? BLS_OK : BLS_ERR_INVALID_SIGNATURE;
 }
+// first_i = min{ j in i's set : bytes_j == bytes_i } as a flat index.  The tile walk of k_secure_rank: the lanes of a workgroup are
+// consecutive keys, the keys before them in their sets are one contiguous range [range_lo, range_hi), streamed through LDS in
+// tiles of BLS_BLOCK keys; every lane searches the tiles of its own set below its own index (secure_first_tile).  gridDim.y
+// workgroups share the tiles of a long range (tile k goes to y = k mod gridDim.y) and meet in first (preset to ~0) by atomicMin.
+template <int WPK>
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_first(size_t n, const uint64_t* offs, const uint8_t* kb, const uint32_t* sid,
+                                                          const uint32_t* flags, uint32_t* first) {
+  __shared__ uint32_t tile[BLS_BLOCK * WPK];
+  __shared__ unsigned long long range_lo, range_hi;
+  const size_t i = (size_t)blockIdx.x * BLS_BLOCK + threadIdx.x, S = gridDim.y;
+  const uint32_t* kw = (const uint32_t*)kb;
+  bool live = i < n;
+  size_t lo = 0;
+  uint32_t me[WPK];
+  if (threadIdx.x == 0) {
+    range_lo = ~0ull;
+    range_hi = 0;
+  }
+  __syncthreads();
+  if (live) {
+    const uint32_t s = sid[i];
+    live = !(flags[s] & SECURE_F_LARGE);
+    lo = offs[s];
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < WPK; k++) me[k] = kw[i * WPK + k];
+    atomicMin(&range_lo, (unsigned long long)lo);
+    atomicMax(&range_hi, (unsigned long long)i);          // a lane looks only at keys below its own
+  }
+  __syncthreads();
+  const size_t rlo = range_lo, rhi = range_hi;
+  uint32_t best = (uint32_t)i;                // no live lane: range_hi = 0 and the loop below does not run
+  for (size_t t0 = rlo + (size_t)blockIdx.y * BLS_BLOCK; t0 < rhi; t0 += S * BLS_BLOCK) {     // uniform over the workgroup
+    const size_t j = t0 + threadIdx.x;
+    if (j < rhi) {
+#pragma unroll
+      for (int k = 0; k < WPK; k++) tile[threadIdx.x * WPK + k] = kw[j * WPK + k];
+    }
+    __syncthreads();
+    if (live) best = secure_first_tile<WPK>(best, tile, t0, rhi - t0 < BLS_BLOCK ? rhi - t0 : BLS_BLOCK, lo, me);
+    __syncthreads();
+  }
+  if (live) atomicMin(&first[i], best);
+}
+template __global__ void k_secure_first<12>(size_t, const uint64_t*, const uint8_t*, const uint32_t*, const uint32_t*, uint32_t*);
+template __global__ void k_secure_first<24>(size_t, const uint64_t*, const uint8_t*, const uint32_t*, const uint32_t*, uint32_t*);
 template __global__ void k_secure_rank<12>(size_t, const uint64_t*, size_t, const uint8_t*, const uint32_t*, uint32_t*, uint32_t*);
 template __global__ void k_secure_rank<24>(size_t, const uint64_t*, size_t, const uint8_t*, const uint32_t*, uint32_t*, uint32_t*);
 #endif
@@ -178,6 +232,45 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_set_out(size_t n_sets, const uint
   }
   status[s] = st;
 }
+// k_share_ladder with a gather: the point of lane i is sigs[first[i]], its scalar the coefficient of key i.  A set that already
+// carries a flag (a zero coefficient; a large set, summed by its own MSM) leaves the identity.
+template <int G>
+__global__ void __launch_bounds__(BLS_BLOCK) k_secure_ladder(size_t n, const uint8_t* sigs, int fmt, const uint8_t* scal, const uint32_t* first,
+                                                           const uint32_t* sid, const uint32_t* flags, uint8_t* part) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  typedef typename grp<G>::F F;
+  jac<F> p, acc;
+  jac_set_inf(acc);
+  if (!flags[sid[i]]) {
+    grp<G>::load(p, sigs, first[i], fmt);
+    if (!jac_is_inf(p)) {
+      aff<F> a;
+      jac_to_aff(a, p);
+      share_ladder<G>(acc, a, (const uint32_t*)(scal + 32 * i));
+    }
+  }
+  grp<G>::store(part, i, acc);
+}
+template <int G>
+__global__ void __launch_bounds__(BLS_BLOCK) k_set_sum_out(size_t n_sets, const uint64_t* key_offs, const uint64_t* part_offs, const uint32_t* flags,
+                                                         const uint8_t* part, uint8_t* out, int32_t* status) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_sets) return;
+  const bool zero_coeff = flags && (flags[s] & SECURE_F_ZERO);
+  uint32_t* w = (uint32_t*)(out + s * grp<G>::PROJ_BYTES);
+  if (key_offs[s + 1] != key_offs[s] && !zero_coeff) {
+    const uint32_t* src = (const uint32_t*)(part + part_offs[s] * grp<G>::PROJ_BYTES);
+    for (int k = 0; k < grp<G>::PROJ_BYTES / 4; k++) w[k] = src[k];
+  } else {
+    for (int k = 0; k < grp<G>::PROJ_BYTES / 4; k++) w[k] = 0u;      // the identity (Z = 0)
+  }
+  if (status) status[s] = zero_coeff ? BLS_ERR_INVALID_COEFFICIENT : BLS_OK;
+}
+template __global__ void k_secure_ladder<1>(size_t, const uint8_t*, int, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint8_t*);
+template __global__ void k_secure_ladder<2>(size_t, const uint8_t*, int, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint8_t*);
+template __global__ void k_set_sum_out<1>(size_t, const uint64_t*, const uint64_t*, const uint32_t*, const uint8_t*, uint8_t*, int32_t*);
+template __global__ void k_set_sum_out<2>(size_t, const uint64_t*, const uint64_t*, const uint32_t*, const uint8_t*, uint8_t*, int32_t*);
 template __global__ void k_set_out<1>(size_t, const uint64_t*, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
 template __global__ void k_set_out<2>(size_t, const uint64_t*, const uint64_t*, uint32_t*, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*, int32_t*);
 #endif

@@ -438,6 +438,38 @@ int blsgpu_signcrypt_open_batch(int sig_group, int scheme, const void* us, const
                                 const uint64_t* v_offsets, size_t n_ct, const uint8_t* ids, const void* shares,
                                 const uint64_t* share_offsets, int fmt, uint8_t* frames, uint64_t* pt_range, int32_t* status);
 
+/* ---- batched aggregation: the objects the batched verifiers above consume, made for many sets in one call.
+ *
+ * Batched secure aggregation: aggregate_secure / aggregate_secure_with_mode = AggregateSignature::from_signatures_secure
+ * (src/secure_aggregation.rs:110-169,338-352, src/aggregate_signature.rs:191-227) for n_sets independent (keys, signatures) sets.
+ * key_offsets: n_sets + 1 entries; set s owns keys AND signatures key_offsets[s] .. key_offsets[s + 1] of pks / sigs, one signature
+ *     per key at the same index (it starts at 0 and never decreases; anything else is BLSGPU_E_ARG).  The total must be below 2^32.
+ * ser_format and fmt apply to every set and take the same values as in blsgpu_aggregate_secure (RAW_PROJ or RAW_AFFINE points;
+ *     Legacy only for sig_group 2).
+ * out_sigs: n_sets RAW_PROJ records of the signature group; status: n_sets entries, BLSGPU_OK or BLSGPU_INVALID_COEFFICIENT.
+ * out_sigs[s] and status[s] are what blsgpu_aggregate_secure returns for set s alone: sum_p t_p sig[idx_p] over the sorted
+ *     positions p of the set's keys, where idx_p is the FIRST input position of the set whose serialised key equals the p-th sorted
+ *     key (the reference's `position` search, :138-147), so duplicate keys all pick the first copy's signature.  An empty set gives
+ *     the identity and BLSGPU_OK.  Where status[s] is BLSGPU_INVALID_COEFFICIENT (:97-100) the record is all-zero.  The point
+ *     is the same group element as the single call's; its projective representative need not be.
+ * Sets below BLSGPU_SECURE_BATCH_MAX keys are sorted, hashed and summed together on the device; larger ones run one at a time
+ *     through blsgpu_aggregate_secure's steps, and one large set alone is that call.  The knob changes the plan, never a result.
+ * Every pointer may be host or device memory; a device out_sigs feeds blsgpu_verify_secure_batch without a host round trip.
+ *     key_offsets are read and checked on the host.  n_sets == 0 returns 0.  The call runs on one device. */
+int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* sigs, const uint64_t* key_offsets, size_t n_sets,
+                                  int ser_format, int fmt, void* out_sigs, int32_t* status);
+
+/* Batched plain sums: the point sum of MultiSignature::from_signatures and AggregateSignature::from_signatures
+ * (src/multi_signature.rs:80-107,147, src/aggregate_signature.rs:123-148,171) and of MultiPublicKey::from_public_keys
+ * (src/multi_public_key.rs:79-83) for n_sets independent sets; the scheme rules of those constructors are the caller's.
+ * group: 1 (G1) or 2 (G2).  offsets: n_sets + 1 entries; set s owns points offsets[s] .. offsets[s + 1] of pts (it starts at 0 and
+ *     never decreases; anything else is BLSGPU_E_ARG).  The total must be below 2^32.  fmt: RAW_PROJ or RAW_AFFINE.
+ * out: n_sets RAW_PROJ records; out[s] is the sum of set s, the identity (all-zero) for an empty set.
+ * One segmented point sum over all sets, the one of blsgpu_multi_verify_batch (strips of BLSGPU_MULTI_STRIP points); a single
+ *     set is a plan with one set and stays on one device.
+ * Every pointer may be host or device memory; a device `out` feeds the batched verifiers directly.  n_sets == 0 returns 0. */
+int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t n_sets, int fmt, void* out);
+
 #ifdef __cplusplus
 }
 #endif
