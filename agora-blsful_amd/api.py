@@ -251,6 +251,16 @@ def core_verify(sig_group, dst, pks, sigs, msgs, fmt=FMT_RAW_PROJ):
     return list(st)[:n]
 
 
+def core_verify_hashed(sig_group, pks, sigs, hashes):
+    """status list of core_verify for n items whose message points H(m_i) are given (all points RAW_PROJ)."""
+    lib = init()
+    n = len(hashes)
+    st = (ctypes.c_int32 * max(n, 1))()
+    pkb, sgb, hb = b''.join(pks), b''.join(sigs), b''.join(hashes)
+    _check(lib.blsgpu_core_verify_hashed(sig_group, _ptr(pkb), _ptr(sgb), _ptr(hb), n, ctypes.cast(st, ctypes.c_void_p)))
+    return list(st)[:n]
+
+
 def multi_verify(sig_group, scheme, pks, sig, msg, fmt=FMT_RAW_PROJ):
     lib = init()
     st = ctypes.c_int32(-99)

@@ -752,48 +752,21 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_prepare_hashed(size_t n, const ui
   if (i >= n) return;
   g1_aff P[2];
   g2_aff Q[2];
-  int st = BLS_OK;
+  int st;
   if (SG == 1) {
     g2_jac pk;
     g1_jac sig, h;
     load_g2_pt(pk, pks, i, fmt);
     load_g1_pt(sig, sigs, i, fmt);
     load_g1_pt(h, hashes, i, 0);
-    if (jac_is_inf(sig)) st = BLS_ERR_SIG_IDENTITY;
-    else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
-    else if (jac_is_inf(h)) {
-      g1g2_to_aff(P[1], Q[0], sig, pk);
-      jac_to_aff(P[0], h);
-    } else {
-      fp zs = sig.z, zh = h.z, nn;
-      fp2_norm_sq(nn, pk.z);
-      fp_inv3(zs, zh, nn);
-      g1_apply_zinv(P[1], sig, zs);
-      g1_apply_zinv(P[0], h, zh);
-      g2_apply_ninv(Q[0], pk, nn);
-    }
-    g2_neg_gen(Q[1]);
+    st = prepare_hashed_item(P, Q, pk, sig, h);
   } else {
     g1_jac pk;
     g2_jac sig, h;
     load_g1_pt(pk, pks, i, fmt);
     load_g2_pt(sig, sigs, i, fmt);
     load_g2_pt(h, hashes, i, 0);
-    if (jac_is_inf(sig)) st = BLS_ERR_SIG_IDENTITY;
-    else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
-    else if (jac_is_inf(h)) {
-      g1g2_to_aff(P[0], Q[1], pk, sig);
-      jac_to_aff(Q[0], h);
-    } else {
-      fp zp = pk.z, ns, nh;
-      fp2_norm_sq(ns, sig.z);
-      fp2_norm_sq(nh, h.z);
-      fp_inv3(zp, ns, nh);
-      g1_apply_zinv(P[0], pk, zp);
-      g2_apply_ninv(Q[1], sig, ns);
-      g2_apply_ninv(Q[0], h, nh);
-    }
-    g1_neg_gen(P[1]);
+    st = prepare_hashed_item(P, Q, pk, sig, h);
   }
   status[i] = st;
   if (st != BLS_OK) return;
@@ -1150,53 +1123,21 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_prepare_proof(size_t n, const uin
   uint32_t mlen = (uint32_t)(offs[i + 1] - offs[i]);
   g1_aff P[2];
   g2_aff Q[2];
-  int st = BLS_OK;
+  int st;
   if (SG == 1) {
-    g1_jac u, v, a;
+    g1_jac u, v;
     g2_jac pk;
     load_g1_pt(u, commitments, i, fmt);
     load_g1_pt(v, proofs, i, fmt);
     load_g2_pt(pk, pks, i, fmt);
-    if (jac_is_inf(u)) st = BLS_ERR_COMMITMENT_IDENTITY;
-    else if (jac_is_inf(v)) st = BLS_ERR_PROOF_IDENTITY;
-    else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
-    else if (words_all_zero(y, 8)) st = BLS_ERR_ZERO_CHALLENGE;
-    if (st == BLS_OK) {
-      hash_to_g1(a, nullptr, 0, m, mlen, dst.b, dst.len);
-      jac_mul_scalar(a, a, y);
-      jac_add(a, a, u);
-      if (jac_is_inf(a)) {          // e(T, pk) = 1: the product is e(proof, g) with proof != identity, never one
-        st = BLS_ERR_INVALID_SIGNATURE;
-      } else {
-        jac_neg(v, v);
-        g1g2_to_aff(P[1], Q[0], v, pk);
-        jac_to_aff(P[0], a);
-        g2_neg_gen(Q[1]);
-      }
-    }
+    st = prepare_proof_item(P, Q, u, v, pk, y, m, mlen, dst.b, dst.len);
   } else {
-    g2_jac u, v, a;
+    g2_jac u, v;
     g1_jac pk;
     load_g2_pt(u, commitments, i, fmt);
     load_g2_pt(v, proofs, i, fmt);
     load_g1_pt(pk, pks, i, fmt);
-    if (jac_is_inf(u)) st = BLS_ERR_COMMITMENT_IDENTITY;
-    else if (jac_is_inf(v)) st = BLS_ERR_PROOF_IDENTITY;
-    else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
-    else if (words_all_zero(y, 8)) st = BLS_ERR_ZERO_CHALLENGE;
-    if (st == BLS_OK) {
-      hash_to_g2(a, nullptr, 0, m, mlen, dst.b, dst.len);
-      jac_mul_scalar(a, a, y);
-      jac_add(a, a, u);
-      if (jac_is_inf(a)) {
-        st = BLS_ERR_INVALID_SIGNATURE;
-      } else {
-        jac_neg(v, v);
-        g1g2_to_aff(P[0], Q[1], pk, v);
-        jac_to_aff(Q[0], a);
-        g1_neg_gen(P[1]);
-      }
-    }
+    st = prepare_proof_item(P, Q, u, v, pk, y, m, mlen, dst.b, dst.len);
   }
   status[i] = st;
   if (st != BLS_OK) return;

@@ -177,3 +177,104 @@ template <class F2>
 BLS_FN int pairing_verdict(const fp12_t<F2>& f) {
   return final_exp_is_one(f) ? BLS_OK : BLS_ERR_INVALID_SIGNATURE;
 }
+
+// ---- per-item bodies of the stage-1 variants that feed the two-pair pairing stages (k_prepare_hashed, k_prepare_proof):
+// one item in, its two pairs and its status out.  A status other than BLS_OK leaves the pairs unset: the
+// kernels then write no pair slots and every later stage skips the item on its status.  tests/hostsim_pairing_doors compiles
+// the same functions for the host with the bound tracker on.
+
+// core_verify's stage 1 with H(msg) given: the identity checks (signature first, then key: reference
+// src/traits/sig_core.rs:126-135) and the shared-inversion conversion to affine pairs.  SG = 1: P[0] = H, Q[0] = pk, P[1] = sig,
+// Q[1] = -g2; SG = 2: P[0] = pk, Q[0] = H, P[1] = -g1, Q[1] = sig.
+BLS_FN int prepare_hashed_item(g1_aff* P, g2_aff* Q, const g2_jac& pk, const g1_jac& sig, const g1_jac& h) {
+  int st = BLS_OK;
+  if (jac_is_inf(sig)) st = BLS_ERR_SIG_IDENTITY;
+  else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
+  else if (jac_is_inf(h)) {
+    g1g2_to_aff(P[1], Q[0], sig, pk);
+    jac_to_aff(P[0], h);
+  } else {
+    fp zs = sig.z, zh = h.z, nn;
+    fp2_norm_sq(nn, pk.z);
+    fp_inv3(zs, zh, nn);
+    g1_apply_zinv(P[1], sig, zs);
+    g1_apply_zinv(P[0], h, zh);
+    g2_apply_ninv(Q[0], pk, nn);
+  }
+  g2_neg_gen(Q[1]);
+  return st;
+}
+BLS_FN int prepare_hashed_item(g1_aff* P, g2_aff* Q, const g1_jac& pk, const g2_jac& sig, const g2_jac& h) {
+  int st = BLS_OK;
+  if (jac_is_inf(sig)) st = BLS_ERR_SIG_IDENTITY;
+  else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
+  else if (jac_is_inf(h)) {
+    g1g2_to_aff(P[0], Q[1], pk, sig);
+    jac_to_aff(Q[0], h);
+  } else {
+    fp zp = pk.z, ns, nh;
+    fp2_norm_sq(ns, sig.z);
+    fp2_norm_sq(nh, h.z);
+    fp_inv3(zp, ns, nh);
+    g1_apply_zinv(P[0], pk, zp);
+    g2_apply_ninv(Q[1], sig, ns);
+    g2_apply_ninv(Q[0], h, nh);
+  }
+  g1_neg_gen(P[1]);
+  return st;
+}
+
+BLS_FN bool scalar_words_zero(const uint32_t* y) {
+  uint32_t o = 0;
+  for (int k = 0; k < 8; k++) o |= y[k];
+  return o == 0;
+}
+// BlsSignatureProof::verify (reference src/traits/sig_proof.rs:102-142): the checks in the reference's order (commitment, proof,
+// pk identity; y zero), T = commitment + y * H(msg), and the pairs of e(T, pk) * e(-proof, -g) == 1 in core_verify's layout with
+// H(m) := T and sig := -proof.  u: the commitment, v: the proof (negated in place), y: 8 little-endian words.
+BLS_FN int prepare_proof_item(g1_aff* P, g2_aff* Q, const g1_jac& u, g1_jac& v, const g2_jac& pk, const uint32_t* y, const uint8_t* m,
+                              uint32_t mlen, const uint8_t* dst, uint32_t dst_len) {
+  int st = BLS_OK;
+  if (jac_is_inf(u)) st = BLS_ERR_COMMITMENT_IDENTITY;
+  else if (jac_is_inf(v)) st = BLS_ERR_PROOF_IDENTITY;
+  else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
+  else if (scalar_words_zero(y)) st = BLS_ERR_ZERO_CHALLENGE;
+  if (st == BLS_OK) {
+    g1_jac a;
+    hash_to_g1(a, nullptr, 0, m, mlen, dst, dst_len);
+    jac_mul_scalar(a, a, y);
+    jac_add(a, a, u);
+    if (jac_is_inf(a)) {          // e(T, pk) = 1: the product is e(proof, g) with proof != identity, never one
+      st = BLS_ERR_INVALID_SIGNATURE;
+    } else {
+      jac_neg(v, v);
+      g1g2_to_aff(P[1], Q[0], v, pk);
+      jac_to_aff(P[0], a);
+      g2_neg_gen(Q[1]);
+    }
+  }
+  return st;
+}
+BLS_FN int prepare_proof_item(g1_aff* P, g2_aff* Q, const g2_jac& u, g2_jac& v, const g1_jac& pk, const uint32_t* y, const uint8_t* m,
+                              uint32_t mlen, const uint8_t* dst, uint32_t dst_len) {
+  int st = BLS_OK;
+  if (jac_is_inf(u)) st = BLS_ERR_COMMITMENT_IDENTITY;
+  else if (jac_is_inf(v)) st = BLS_ERR_PROOF_IDENTITY;
+  else if (jac_is_inf(pk)) st = BLS_ERR_PK_IDENTITY;
+  else if (scalar_words_zero(y)) st = BLS_ERR_ZERO_CHALLENGE;
+  if (st == BLS_OK) {
+    g2_jac a;
+    hash_to_g2(a, nullptr, 0, m, mlen, dst, dst_len);
+    jac_mul_scalar(a, a, y);
+    jac_add(a, a, u);
+    if (jac_is_inf(a)) {
+      st = BLS_ERR_INVALID_SIGNATURE;
+    } else {
+      jac_neg(v, v);
+      g1g2_to_aff(P[0], Q[1], pk, v);
+      jac_to_aff(Q[0], a);
+      g1_neg_gen(P[1]);
+    }
+  }
+  return st;
+}
