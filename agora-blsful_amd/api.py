@@ -43,6 +43,8 @@ EXPORTS = [
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
+    'blsgpu_keyset_create', 'blsgpu_keyset_destroy', 'blsgpu_keyset_info', 'blsgpu_keyset_get', 'blsgpu_keyset_mul',
+    'blsgpu_multi_verify_indexed_batch', 'blsgpu_verify_secure_indexed_batch', 'blsgpu_sum_indexed_batch', 'blsgpu_verify_indexed_batch',
 ]
 
 
@@ -166,6 +168,16 @@ def load_library(path=None):
         lib.blsgpu_signcrypt_open_batch.argtypes = [ci, ci, vp, vp, u8p, u64p, sz, u8p, vp, u64p, ci, u8p, u64p, i32p]
         lib.blsgpu_aggregate_secure_batch.argtypes = [ci, vp, vp, u64p, sz, ci, ci, vp, i32p]
         lib.blsgpu_sum_batch.argtypes = [ci, vp, u64p, sz, ci, vp]
+        h = ctypes.c_uint64
+        lib.blsgpu_keyset_create.argtypes = [ci, vp, sz, ci, ci, i32p, ctypes.POINTER(h)]
+        lib.blsgpu_keyset_destroy.argtypes = [h]
+        lib.blsgpu_keyset_info.argtypes = [h, ctypes.POINTER(ci), ctypes.POINTER(h), ctypes.POINTER(ci), ctypes.POINTER(h)]
+        lib.blsgpu_keyset_get.argtypes = [h, u32p, sz, ci, vp, i32p]
+        lib.blsgpu_keyset_mul.argtypes = [h, u32p, u8p, sz, vp]
+        lib.blsgpu_multi_verify_indexed_batch.argtypes = [ci, h, u32p, u64p, sz, vp, u8p, u64p, ci, i32p]
+        lib.blsgpu_verify_secure_indexed_batch.argtypes = [ci, h, u32p, u64p, sz, vp, u8p, u64p, ci, ci, i32p]
+        lib.blsgpu_sum_indexed_batch.argtypes = [h, u32p, u64p, sz, vp]
+        lib.blsgpu_verify_indexed_batch.argtypes = [ci, h, u32p, vp, u8p, u64p, sz, ci, i32p]
         _lib = lib
     return _lib
 
@@ -561,6 +573,157 @@ def sum_batch(group, sets, fmt=FMT_RAW_PROJ):
     return [raw[osz * i:osz * (i + 1)] for i in range(n_sets)]
 
 
+
+# ------------------------------------------------------------------ registered key sets
+KEYSET_TABLES = 1
+E_ARG = -3          # in a status slot of an indexed call: the set names an index outside the key set
+_POINT_BYTES = {FMT_RAW_PROJ: 144, FMT_RAW_AFFINE: 96, FMT_COMPRESSED: 48, FMT_LEGACY: 48}
+
+
+def indices_from_bits(bits):
+    """The positions of the set bits of a signer bitset, ascending: bit i of the set is bit (i % 8) of byte i // 8, counted from
+    the least significant bit (little-endian bit order, the order of an SSZ Bitlist / Bitvector and of a Dash quorum's signers
+    field).  `bits` is bytes-like; trailing zero bits and bytes name nobody.  A host helper: the result is what the *_indexed_batch
+    calls take as one set's `idx`."""
+    out = []
+    for i, b in enumerate(bytes(bits)):
+        while b:
+            low = b & -b
+            out.append(8 * i + low.bit_length() - 1)
+            b ^= low
+    return out
+
+
+def _u32(idx):
+    return (ctypes.c_uint32 * max(len(idx), 1))(*idx)
+
+
+class KeySet:
+    """A table of public keys that stays on the device (blsgpu_keyset_*): created once from wire bytes or raw points, then named by
+    position in the *_indexed_batch calls.  Immutable; close() (or leaving the `with` block) releases the device memory, and must
+    not run while another thread's call still uses the set."""
+
+    def __init__(self, handle, statuses):
+        self.handle, self.statuses = handle, statuses
+
+    @classmethod
+    def create(cls, sig_group, keys, fmt=FMT_COMPRESSED, tables=False):
+        """`keys`: a list of byte strings in `fmt`, the public keys of Bls12381G{sig_group}Impl.  self.statuses[i] is what
+        deserialize gives for key i; a key that fails stays in the table as an invalid entry."""
+        lib = init()
+        n = len(keys)
+        blob = b''.join(keys)
+        st = (ctypes.c_int32 * max(n, 1))()
+        h = ctypes.c_uint64(0)
+        _check(lib.blsgpu_keyset_create(sig_group, _ptr(blob) if blob else None, n, fmt, KEYSET_TABLES if tables else 0,
+                                        ctypes.cast(st, ctypes.c_void_p), ctypes.byref(h)))
+        return cls(h.value, list(st)[:n])
+
+    @classmethod
+    def create_device(cls, sig_group, keys_ptr, n, fmt=FMT_RAW_PROJ, tables=False):
+        """From n keys already on the device (an integer address, e.g. tensor.data_ptr())."""
+        lib = init()
+        h = ctypes.c_uint64(0)
+        _check(lib.blsgpu_keyset_create(sig_group, ctypes.c_void_p(keys_ptr), n, fmt, KEYSET_TABLES if tables else 0, None, ctypes.byref(h)))
+        return cls(h.value, None)
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, 0
+            _check(_lib.blsgpu_keyset_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def info(self):
+        """dict(sig_group, n, has_tables, device_bytes)"""
+        sg, ht, n, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(init().blsgpu_keyset_info(self.handle, ctypes.byref(sg), ctypes.byref(n), ctypes.byref(ht), ctypes.byref(b)))
+        return {'sig_group': sg.value, 'n': n.value, 'has_tables': bool(ht.value), 'device_bytes': b.value}
+
+    def _key_group(self):
+        return 3 - self.info()['sig_group']
+
+    def get(self, idx, fmt=FMT_RAW_PROJ):
+        """(entries, creation statuses) at the positions `idx`, the entries in `fmt`."""
+        osz = _POINT_BYTES[fmt] * self._key_group()
+        n = len(idx)
+        out = ctypes.create_string_buffer(osz * max(n, 1))
+        st = (ctypes.c_int32 * max(n, 1))()
+        _check(init().blsgpu_keyset_get(self.handle, ctypes.cast(_u32(idx), ctypes.c_void_p), n, fmt, ctypes.cast(out, ctypes.c_void_p),
+                                        ctypes.cast(st, ctypes.c_void_p)))
+        raw = out.raw
+        return [raw[osz * i:osz * (i + 1)] for i in range(n)], list(st)[:n]
+
+    def mul(self, idx, scalars):
+        """RAW_PROJ points scalars[i] * key[idx[i]] (integer scalars below 2^256, reduced modulo r)."""
+        osz = 144 * self._key_group()
+        n = len(idx)
+        sc = b''.join(int(k).to_bytes(32, 'little') for k in scalars)
+        out = ctypes.create_string_buffer(osz * max(n, 1))
+        _check(init().blsgpu_keyset_mul(self.handle, ctypes.cast(_u32(idx), ctypes.c_void_p), _ptr(sc) if sc else None, n,
+                                        ctypes.cast(out, ctypes.c_void_p)))
+        raw = out.raw
+        return [raw[osz * i:osz * (i + 1)] for i in range(n)]
+
+
+def _indexed_sets(sets):
+    n_sets = len(sets)
+    koffs = _count_offsets([s[0] for s in sets])
+    idx = _u32([i for s in sets for i in s[0]])
+    moffs, mblob = _offsets([bytes(s[2]) for s in sets])
+    sgb = b''.join(s[1] for s in sets)
+    return n_sets, koffs, idx, moffs, mblob, sgb, (ctypes.c_int32 * max(n_sets, 1))()
+
+
+def multi_verify_indexed_batch(keyset, scheme, sets, fmt=FMT_RAW_PROJ):
+    """multi_verify_batch with the keys named by position: `sets` is a list of (idx, sig, msg), idx a list of positions in
+    `keyset`.  One status per set: E_ARG for an index outside the table, the creation status of the first invalid entry named,
+    else what multi_verify_batch gives for those keys."""
+    n_sets, koffs, idx, moffs, mblob, sgb, stv = _indexed_sets(sets)
+    _check(init().blsgpu_multi_verify_indexed_batch(scheme, keyset.handle, ctypes.cast(idx, ctypes.c_void_p), ctypes.cast(koffs, ctypes.c_void_p), n_sets,
+                                                    _ptr(sgb), _ptr(mblob), ctypes.cast(moffs, ctypes.c_void_p), fmt, ctypes.cast(stv, ctypes.c_void_p)))
+    return list(stv)[:n_sets]
+
+
+def verify_secure_indexed_batch(keyset, scheme, sets, ser_format=MODERN, fmt=FMT_RAW_PROJ):
+    """verify_secure_batch with the keys named by position; `sets` and the statuses as multi_verify_indexed_batch."""
+    n_sets, koffs, idx, moffs, mblob, sgb, stv = _indexed_sets(sets)
+    _check(init().blsgpu_verify_secure_indexed_batch(scheme, keyset.handle, ctypes.cast(idx, ctypes.c_void_p), ctypes.cast(koffs, ctypes.c_void_p), n_sets,
+                                                     _ptr(sgb), _ptr(mblob), ctypes.cast(moffs, ctypes.c_void_p), ser_format, fmt,
+                                                     ctypes.cast(stv, ctypes.c_void_p)))
+    return list(stv)[:n_sets]
+
+
+def sum_indexed_batch(keyset, sets):
+    """sum_batch over positions: `sets` is a list of lists of positions; one RAW_PROJ key sum per set.  Invalid entries add nothing;
+    an index outside the table raises."""
+    n_sets = len(sets)
+    offs = _count_offsets(sets)
+    idx = _u32([i for s in sets for i in s])
+    osz = 144 * keyset._key_group()
+    out = ctypes.create_string_buffer(osz * max(n_sets, 1))
+    _check(init().blsgpu_sum_indexed_batch(keyset.handle, ctypes.cast(idx, ctypes.c_void_p), ctypes.cast(offs, ctypes.c_void_p), n_sets,
+                                           ctypes.cast(out, ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[osz * i:osz * (i + 1)] for i in range(n_sets)]
+
+
+def verify_indexed_batch(keyset, scheme, idx, sigs, msgs, fmt=FMT_RAW_PROJ):
+    """verify_batch with item i's key at position idx[i] of `keyset`."""
+    n = len(msgs)
+    offs, blob = _offsets(msgs)
+    st = (ctypes.c_int32 * max(n, 1))()
+    sgb = b''.join(sigs)
+    _check(init().blsgpu_verify_indexed_batch(scheme, keyset.handle, ctypes.cast(_u32(idx), ctypes.c_void_p), _ptr(sgb), _ptr(blob),
+                                              ctypes.cast(offs, ctypes.c_void_p), n, fmt, ctypes.cast(st, ctypes.c_void_p)))
+    return list(st)[:n]
+
+
 def combine_shares(group, sets, fmt=FMT_RAW_PROJ):
     """Threshold recovery of many independent sets in one call (blsgpu_combine_shares): `sets` is a list of lists of
     (identifier: int, raw point, scheme or None).  Scheme tags are checked only when every share of the call carries one
@@ -883,6 +1046,48 @@ class TensorOps:
         out = self.empty(max(n_sets, 1) * osz)
         _check(self.lib.blsgpu_sum_batch(group, self._p(pts), self._p(offs), n_sets, fmt, self._p(out)))
         return out[:n_sets * osz]
+
+    # registered key sets: idx is an int32 tensor whose bits are the uint32 positions, offsets are int64, everything on the device
+    def multi_verify_indexed_batch(self, keyset, scheme, idx, key_offs, sigs, msgs, msg_offs, n_sets):
+        """int32 statuses (on the device) of n_sets MultiSignature::verify checks whose keys are positions in `keyset`."""
+        self._sync()
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        _check(self.lib.blsgpu_multi_verify_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(key_offs), n_sets, self._p(sigs), self._p(msgs),
+                                                          self._p(msg_offs), FMT_RAW_PROJ, self._p(st)))
+        return st[:n_sets]
+
+    def verify_secure_indexed_batch(self, keyset, scheme, idx, key_offs, sigs, msgs, msg_offs, n_sets, ser_format=MODERN):
+        """int32 statuses (on the device) of n_sets verify_secure checks whose keys are positions in `keyset`."""
+        self._sync()
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        _check(self.lib.blsgpu_verify_secure_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(key_offs), n_sets, self._p(sigs), self._p(msgs),
+                                                           self._p(msg_offs), ser_format, FMT_RAW_PROJ, self._p(st)))
+        return st[:n_sets]
+
+    def sum_indexed_batch(self, keyset, key_group, idx, offs, n_sets):
+        """RAW_PROJ key sums (one uint8 tensor of n_sets records, on the device) over positions in `keyset` (keys of `key_group`)."""
+        self._sync()
+        osz = 144 if key_group == 1 else 288
+        out = self.empty(max(n_sets, 1) * osz)
+        _check(self.lib.blsgpu_sum_indexed_batch(keyset.handle, self._p(idx), self._p(offs), n_sets, self._p(out)))
+        return out[:n_sets * osz]
+
+    def verify_indexed_batch(self, keyset, scheme, idx, sigs, msgs, offs, n):
+        """int32 statuses (on the device) of n Signature::verify checks, item i under the key at position idx[i] of `keyset`."""
+        self._sync()
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_verify_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(sigs), self._p(msgs), self._p(offs), n, FMT_RAW_PROJ,
+                                                    self._p(st)))
+        return st[:n]
+
+    def keyset_get(self, keyset, key_group, idx, n, fmt=FMT_RAW_PROJ):
+        """(entries as one uint8 tensor, int32 creation statuses), both on the device."""
+        self._sync()
+        osz = _POINT_BYTES[fmt] * key_group
+        out = self.empty(max(n, 1) * osz)
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_keyset_get(keyset.handle, self._p(idx), n, fmt, self._p(out), self._p(st)))
+        return out[:n * osz], st[:n]
 
     def multi_verify(self, sg, scheme, pks, n, sig, msg):
         self._sync()

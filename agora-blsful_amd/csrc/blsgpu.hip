@@ -21,6 +21,7 @@
 #include "secure.cuh"
 #include "agg_batch.cuh"
 #include "multi_batch.cuh"
+#include "keyset.cuh"
 #include "signcrypt.cuh"
 #include "host_sha256.h"
 
@@ -44,6 +45,7 @@ enum {
   KID_SIGNCRYPT_GATHER, KID_SIGNCRYPT_KEYSTREAM,          // blsgpu_signcrypt_share_verify_batch / blsgpu_signcrypt_open_batch
   KID_SECURE_FIRST, KID_SECURE_LADDER, KID_SECURE_AGG_FOLD, KID_SECURE_AGG_OUT,   // blsgpu_aggregate_secure_batch (rank .. coeff count under theirs)
   KID_SUM_SEG_ACCUM, KID_SUM_FOLD, KID_SUM_OUT,           // blsgpu_sum_batch
+  KID_KEYSET_SEAL, KID_KEYSET_BUILD, KID_KEYSET_CHECK, KID_KEYSET_GATHER, KID_KEYSET_ACCUM, KID_KEYSET_MUL, KID_KEYSET_FIN,   // registered key sets (keyset.cuh)
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
@@ -55,7 +57,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_multi_accumulate_seg", "k_multi_out",
                                     "k_signcrypt_share_pairs", "k_signcrypt_keystream",
                                     "k_secure_first", "k_secure_ladder", "k_secure_agg_fold", "k_secure_agg_out",
-                                    "k_sum_accumulate_seg", "k_sum_fold", "k_sum_out"};
+                                    "k_sum_accumulate_seg", "k_sum_fold", "k_sum_out",
+                                    "k_keyset_seal", "k_keyset_build", "k_keyset_check", "k_keyset_gather", "k_keyset_accumulate_seg", "k_keyset_mul", "k_keyset_fin"};
 
 struct Ctx {
   int dev = -1;
@@ -169,6 +172,7 @@ struct Knobs {
   long secure_batch_max = 1024; // blsgpu_verify_secure_batch, blsgpu_aggregate_secure_batch: a set of at least this many keys runs through blsgpu_verify_secure's machinery
   long agg_batch_max = 32768;  // blsgpu_aggregate_verify_batch: a set of at least this many pairs runs through blsgpu_aggregate_verify's machinery
   long multi_strip = 0;        // blsgpu_multi_verify_batch: keys per strip of the segmented key sum (0: one strip per lane of a single sum, at least 4)
+  long keyset_table_mb = 4096; // blsgpu_keyset_create: fixed-base tables above this many MiB are not built (the set works without them)
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
@@ -190,6 +194,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_SECURE_BATCH_MAX", &Knobs::secure_batch_max, 1, 1L << 32, false},
     {"BLSGPU_AGG_BATCH_MAX", &Knobs::agg_batch_max, 1, 1L << 32, false},
     {"BLSGPU_MULTI_STRIP", &Knobs::multi_strip, 0, 1L << 32, false},
+    {"BLSGPU_KEYSET_TABLE_MB", &Knobs::keyset_table_mb, 0, 1L << 20, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -1746,6 +1751,42 @@ int run_first_duplicate(Ctx* c, const uint8_t* d_msgs, const uint64_t* d_offs, s
   return 0;
 }
 
+// ---- registered key sets (keyset.cuh): the registry.  A handle is an id, never a pointer: a stale one is simply not found.
+// An entry is immutable from registration to destruction, so a call works on a copy of the record taken under the lock.
+struct KeySet {
+  int sig_group = 0, group = 0;       // group: where the keys live
+  size_t n = 0, devidx = 0;
+  int dev = -1;
+  uint8_t *aff = nullptr, *comp = nullptr, *table = nullptr;     // RAW_AFFINE records, Modern bytes, fixed-base tables (or none)
+  int32_t* status = nullptr;
+  uint64_t bytes = 0;
+};
+std::mutex g_keyset_mu;
+std::unordered_map<uint64_t, KeySet> g_keysets;
+uint64_t g_keyset_next = 1;
+void keyset_free(KeySet& k) {
+  if (k.dev >= 0) (void)hipSetDevice(k.dev);
+  for (void* p : {(void*)k.aff, (void*)k.comp, (void*)k.table, (void*)k.status})
+    if (p) (void)hipFree(p);
+  k = KeySet();
+}
+void keyset_release_all() {
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  for (auto& kv : g_keysets) keyset_free(kv.second);
+  g_keysets.clear();
+}
+int keyset_find(uint64_t handle, KeySet& k) {
+  if (!initialised()) return NOT_INIT();
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  auto it = g_keysets.find(handle);
+  if (handle == 0 || it == g_keysets.end()) return fail(BLSGPU_E_ARG, "unknown key set handle (never issued, or destroyed)");
+  k = it->second;
+  return 0;
+}
+template <int G>
+size_t keyset_table_bytes_g(size_t n) { return n * (size_t)keyset_shape<G>::POINTS * 2 * G * FP_NL * 4; }
+size_t keyset_table_bytes(int group, size_t n) { return group == 1 ? keyset_table_bytes_g<1>(n) : keyset_table_bytes_g<2>(n); }
+
 }  // namespace
 
 // =========================================================================================================
@@ -1919,6 +1960,7 @@ int blsgpu_device_count(void) { return (int)g_devices.size(); }
 void blsgpu_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_init_mu);
   if (!initialised()) return;
+  keyset_release_all();
   release_devices();
 }
 
@@ -4479,6 +4521,550 @@ int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t
   if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
   SYNC_FLUSH(c);
   return 0;
+}
+API_CATCH
+// =========================================================================================================
+// Registered key sets (keyset.cuh): a table of public keys that stays on the device, sets named by positions in it
+static int keyset_fmt_check(int sig_group, int fmt) {
+  if (sig_group != 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "sig_group must be 1 (Bls12381G1Impl) or 2 (Bls12381G2Impl)");
+  if (fmt < BLSGPU_FMT_RAW_PROJ || fmt > BLSGPU_FMT_LEGACY) return fail(BLSGPU_E_ARG, "fmt must be one of BLSGPU_FMT_*");
+  if (fmt == BLSGPU_FMT_LEGACY && sig_group != 2)
+    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
+  return 0;
+}
+// scal[i] * key[cidx[i]] for every position: from the fixed-base tables when the set has them, else the joint NAF ladder
+static int keyset_launch_mul(Ctx* c, const KeySet& k, size_t n, const uint32_t* d_cidx, const uint8_t* d_scal, const uint32_t* d_sid, const uint32_t* d_flags,
+                             uint8_t* d_part) {
+  with_group(k.group, [&](auto G) {
+    if (k.table)
+      KL(KID_KEYSET_MUL, (k_keyset_mul<G(), 1>), dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)k.aff, (const uint8_t*)k.table, d_cidx, d_scal, d_sid,
+         d_flags, d_part);
+    else
+      KL(KID_KEYSET_MUL, (k_keyset_mul<G(), 0>), dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)k.aff, (const uint8_t*)nullptr, d_cidx, d_scal, d_sid,
+         d_flags, d_part);
+  });
+  return 0;
+}
+// the fixed-base tables of a new set, chunk by chunk through a workspace that lives for this call only; leaves k.table null (and
+// the set without tables) when the knob or the device's memory says no
+static int keyset_build_tables(Ctx* c, KeySet& k) {
+  const size_t tb = keyset_table_bytes(k.group, k.n);
+  if (k.n == 0 || tb > ((size_t)knobs().keyset_table_mb << 20)) return 0;
+  const size_t chunk = std::min<size_t>(k.n, 4096);
+  const size_t rec = keyset_table_bytes(k.group, 1);                   // one key's table: POINTS (x, y) records
+  uint8_t *table = nullptr, *jac_ws = nullptr, *prod_ws = nullptr;
+  if (hipMalloc((void**)&table, tb) != hipSuccess || hipMalloc((void**)&jac_ws, chunk * (rec / 2 * 3)) != hipSuccess ||
+      hipMalloc((void**)&prod_ws, chunk * (rec / 2)) != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)table, (void*)jac_ws, (void*)prod_ws})
+      if (p) (void)hipFree(p);
+    return 0;
+  }
+  for (size_t k0 = 0; k0 < k.n; k0 += chunk) {
+    const size_t cnt = std::min(chunk, k.n - k0);
+    with_group(k.group, [&](auto G) {
+      KL(KID_KEYSET_BUILD, k_keyset_build<G()>, dim3(blocks_for(cnt)), dim3(BLS_BLOCK), k0, cnt, (const uint8_t*)k.aff, jac_ws, prod_ws, table);
+    });
+  }
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(jac_ws);
+  (void)hipFree(prod_ws);
+  if (e1 != hipSuccess || e2 != hipSuccess) {
+    (void)hipFree(table);
+    return fail(BLSGPU_E_HIP, std::string("k_keyset_build: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+  }
+  k.table = table;
+  k.bytes += tb;
+  return 0;
+}
+int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int flags, int32_t* status, uint64_t* out_handle) try {
+  if (!initialised()) return NOT_INIT();
+  int rc = keyset_fmt_check(sig_group, fmt);
+  if (rc) return rc;
+  if (!out_handle || (n && !keys)) return fail(BLSGPU_E_ARG, "null argument");
+  if (flags & ~BLSGPU_KEYSET_TABLES) return fail(BLSGPU_E_ARG, "unknown flag");
+  if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 keys");
+  *out_handle = 0;
+  CTX_ACQUIRE(c);
+  KeySet k;
+  k.sig_group = sig_group;
+  k.group = key_group(sig_group);
+  k.n = n;
+  k.devidx = t_devidx;
+  k.dev = c->dev;
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  const size_t isz = point_bytes(k.group, fmt), osz = point_bytes(k.group, BLSGPU_FMT_RAW_PROJ), asz = point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE),
+               csz = point_bytes(k.group, BLSGPU_FMT_COMPRESSED), m = std::max<size_t>(n, 1);
+  struct Guard {
+    KeySet* k;
+    ~Guard() {
+      if (k) keyset_free(*k);
+    }
+  } guard{&k};
+  HIPCK(hipMalloc((void**)&k.aff, asz * m));
+  HIPCK(hipMalloc((void**)&k.comp, csz * m));
+  HIPCK(hipMalloc((void**)&k.status, 4 * m));
+  k.bytes = (asz + csz + 4) * (uint64_t)n;
+  if (n) {
+    if ((rc = arena_reserve(c, pad256(isz * n) + pad256(osz * n) + 4096))) return rc;
+    c->arena_off = 0;
+    const void* d_in;
+    if ((rc = stage_in(c, keys, isz * n, &d_in))) return rc;
+    const uint8_t* d_pts = (const uint8_t*)d_in;
+    int kfmt = fmt;
+    if (wire) {
+      // PublicKey::from_bytes[_with_mode]: the checked decompression of blsgpu_deserialize; its status is the entry's
+      uint8_t* d_raw = (uint8_t*)arena_take(c, osz * n);
+      if (!d_raw) return fail(BLSGPU_E_HIP, "internal: arena too small");
+      with_group(k.group, [&](auto G) {
+        KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_pts, (int)(fmt == BLSGPU_FMT_LEGACY), d_raw, k.status, 0);
+      });
+      d_pts = d_raw;
+      kfmt = BLSGPU_FMT_RAW_PROJ;
+    } else {
+      HIPCK(hipMemsetAsync(k.status, 0, 4 * n, c->stream));
+    }
+    with_group(k.group, [&](auto G) {
+      KL(KID_KEYSET_SEAL, k_keyset_seal<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_pts, kfmt, (const int32_t*)k.status, k.aff, k.comp);
+    });
+    HIPCK(hipGetLastError());
+    if (status && (rc = copy_out(c, status, k.status, 4 * n))) return rc;
+    if ((flags & BLSGPU_KEYSET_TABLES) && (rc = keyset_build_tables(c, k))) return rc;
+    SYNC_FLUSH(c);
+  }
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  const uint64_t id = g_keyset_next++;
+  g_keysets[id] = k;
+  guard.k = nullptr;
+  *out_handle = id;
+  return 0;
+}
+API_CATCH
+
+int blsgpu_keyset_destroy(uint64_t handle) try {
+  if (!initialised()) return NOT_INIT();
+  KeySet k;
+  {
+    std::lock_guard<std::mutex> lk(g_keyset_mu);
+    auto it = g_keysets.find(handle);
+    if (handle == 0 || it == g_keysets.end()) return fail(BLSGPU_E_ARG, "unknown key set handle (never issued, or destroyed)");
+    k = it->second;
+    g_keysets.erase(it);
+  }
+  keyset_free(k);
+  return 0;
+}
+API_CATCH
+
+int blsgpu_keyset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_tables, uint64_t* device_bytes) try {
+  KeySet k;
+  int rc = keyset_find(handle, k);
+  if (rc) return rc;
+  if (sig_group) *sig_group = k.sig_group;
+  if (n) *n = k.n;
+  if (has_tables) *has_tables = k.table ? 1 : 0;
+  if (device_bytes) *device_bytes = k.bytes;
+  return 0;
+}
+API_CATCH
+
+// the indices of a call against the table: d_cidx gets idx[i] or KEYSET_SKIP, d_pre (n_sets slots, or one when d_offs is null and
+// `whole` is set: the whole call is one set) each set's precedence
+static int keyset_check(Ctx* c, const KeySet& k, const uint32_t* d_idx, size_t n, const uint64_t* d_offs, size_t n_sets, uint32_t* d_cidx,
+                        unsigned long long* d_pre) {
+  HIPCK(hipMemsetAsync(d_pre, 0xff, 8 * n_sets, c->stream));
+  if (n)
+    KL(KID_KEYSET_CHECK, k_keyset_check, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_offs, n_sets, d_idx, (uint64_t)k.n, (const int32_t*)k.status, d_cidx,
+       d_pre);
+  return 0;
+}
+// for the calls without a status vector: one set over all positions; after the call's last synchronisation *h_pre == 0 says that
+// some index was outside the table
+static int keyset_check_whole(Ctx* c, const KeySet& k, const void* idx, size_t n, uint32_t** d_cidx, unsigned long long** h_pre) {
+  const void* d_idx;
+  int rc = stage_in(c, idx, 4 * n, &d_idx);
+  if (rc) return rc;
+  Carver mem{c};
+  uint64_t* d_one = mem.take<uint64_t>(16);
+  unsigned long long* d_pre = mem.take<unsigned long long>(8);
+  *d_cidx = mem.take<uint32_t>(4 * n);
+  *h_pre = (unsigned long long*)hsmall_take(c, 8);
+  if (!mem.ok || !*h_pre) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  const uint64_t one[2] = {0, (uint64_t)n};
+  if ((rc = h2d_small(c, d_one, one, 16))) return rc;
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, d_one, 1, *d_cidx, d_pre))) return rc;
+  HIPCK(hipMemcpyAsync(*h_pre, d_pre, 8, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+#define KEYSET_GATHER(words, src, legacy, dst) \
+  KL(KID_KEYSET_GATHER, k_keyset_gather, dim3(blocks_for((size_t)(cnt_) * (words))), dim3(BLS_BLOCK), (size_t)(cnt_), (size_t)(words), (const uint32_t*)d_cidx, \
+     (const uint32_t*)(src), legacy, (uint32_t*)(dst))
+
+int blsgpu_keyset_get(uint64_t handle, const uint32_t* idx, size_t count, int fmt_out, void* out, int32_t* status) try {
+  KeySet k;
+  int rc = keyset_find(handle, k);
+  if (rc) return rc;
+  if ((rc = keyset_fmt_check(k.sig_group, fmt_out))) return rc;
+  if (count == 0) return 0;
+  if (!idx || !out) return fail(BLSGPU_E_ARG, "null argument");
+  if (count >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more positions in one call");
+  CTX_ACQUIRE_ON(c, k.devidx);
+  const size_t asz = point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE), csz = point_bytes(k.group, BLSGPU_FMT_COMPRESSED), osz = point_bytes(k.group, fmt_out);
+  if ((rc = arena_reserve(c, 2 * pad256(4 * count) + pad256(asz * count) + pad256(osz * count) + pad256(4 * count) + 4096))) return rc;
+  c->arena_off = 0;
+  uint32_t* d_cidx;
+  unsigned long long* h_pre;
+  if ((rc = keyset_check_whole(c, k, idx, count, &d_cidx, &h_pre))) return rc;
+  Carver mem{c};
+  uint8_t* d_out = mem.stage_out<uint8_t>(out, osz * count);
+  int32_t* d_st = status ? mem.stage_out<int32_t>(status, 4 * count) : nullptr;
+  uint8_t* d_aff = fmt_out == BLSGPU_FMT_RAW_PROJ ? mem.take<uint8_t>(asz * count) : nullptr;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  const size_t cnt_ = count;
+  if (fmt_out == BLSGPU_FMT_RAW_AFFINE) {
+    KEYSET_GATHER(asz / 4, k.aff, 0, d_out);
+  } else if (fmt_out == BLSGPU_FMT_RAW_PROJ) {
+    KEYSET_GATHER(asz / 4, k.aff, 0, d_aff);
+    with_group(k.group, [&](auto G) {
+      KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_aff, d_out);
+    });
+  } else {
+    KEYSET_GATHER(csz / 4, k.comp, (int)(fmt_out == BLSGPU_FMT_LEGACY), d_out);       // the Legacy header is a transcode of byte 0
+  }
+  if (d_st) KEYSET_GATHER(1, k.status, 0, d_st);
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, osz * count))) return rc;
+  if (d_st && (rc = stage_back(c, status, d_st, 4 * count))) return rc;
+  SYNC_FLUSH(c);
+  if (*h_pre == 0) return fail(BLSGPU_E_ARG, "an index is outside the key set");
+  return 0;
+}
+API_CATCH
+
+int blsgpu_keyset_mul(uint64_t handle, const uint32_t* idx, const uint8_t* scalars, size_t count, void* out) try {
+  KeySet k;
+  int rc = keyset_find(handle, k);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  if (!idx || !scalars || !out) return fail(BLSGPU_E_ARG, "null argument");
+  if (count >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more positions in one call");
+  CTX_ACQUIRE_ON(c, k.devidx);
+  const size_t osz = point_bytes(k.group, BLSGPU_FMT_RAW_PROJ);
+  if ((rc = arena_reserve(c, 2 * pad256(4 * count) + pad256(32 * count) + pad256(osz * count) + 4096))) return rc;
+  c->arena_off = 0;
+  uint32_t* d_cidx;
+  unsigned long long* h_pre;
+  if ((rc = keyset_check_whole(c, k, idx, count, &d_cidx, &h_pre))) return rc;
+  const void* d_scal;
+  if ((rc = stage_in(c, scalars, 32 * count, &d_scal))) return rc;
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * count);
+  if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  rc = keyset_launch_mul(c, k, count, d_cidx, (const uint8_t*)d_scal, nullptr, nullptr, d_out);
+  if (rc) return rc;
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, osz * count))) return rc;
+  SYNC_FLUSH(c);
+  if (*h_pre == 0) return fail(BLSGPU_E_ARG, "an index is outside the key set");
+  return 0;
+}
+API_CATCH
+
+// ---- the batched entry points over a key set: (handle, idx) in place of the keys; fmt describes the signatures only
+// the arguments the four share, checked and read
+struct indexed_args {
+  KeySet k;
+  std::vector<uint64_t> offs, moffs;
+  size_t n = 0;
+};
+static int indexed_begin(indexed_args& a, int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
+                         const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) {
+  int rc = keyset_find(keyset, a.k);
+  if (rc) return rc;
+  if ((rc = check_common(a.k.sig_group, scheme, fmt))) return rc;
+  if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
+  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", a.offs))) return rc;
+  a.n = (size_t)a.offs[n_sets];
+  if (a.n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
+  if (a.n && !idx) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  if ((rc = read_offsets(msg_offsets, n_sets, "msg_offsets", a.moffs, false))) return rc;      // set s's message is msgs + moffs[s]
+  if (a.moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  return 0;
+}
+
+int blsgpu_multi_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
+                                      const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
+  indexed_args a;
+  int rc = indexed_begin(a, scheme, keyset, idx, key_offsets, n_sets, sigs, msgs, msg_offsets, fmt, status);
+  if (rc || n_sets == 0) return rc;
+  const KeySet& k = a.k;
+  const int sig_group = k.sig_group;
+  const size_t n = a.n;
+  // plan: the strips of the segmented key sum (multi_batch.cuh), as blsgpu_multi_verify_batch
+  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
+  std::vector<uint64_t> soffs;
+  std::vector<uint32_t> ssid;
+  const uint64_t qmax = multi_strip_plan(a.offs.data(), n_sets, L, soffs, ssid);
+  const size_t Q = ssid.size();
+  CTX_ACQUIRE_ON(c, k.devidx);
+  const size_t ssz = sig_size(sig_group, fmt), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
+  const size_t mtotal = (size_t)a.moffs[n_sets];
+  rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(ssz * n_sets) + pad256(mtotal) + 3 * pad256(8 * (n_sets + 1)) + pad256(8 * n_sets) + pad256(4 * Q) +
+                            pad256(osz * Q) + 2 * pad256(288 * n_sets) + pad256(4 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) +
+                            pad256((size_t)WS_F_WORDS * 4 * n_sets) + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_idx = nullptr, *d_sigs, *d_msgs, *d_moffs;
+  if (n && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
+  const uint64_t *o, *so;
+  if ((rc = upload_offsets(c, a.offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
+  Carver mem{c};
+  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
+  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n_sets);
+  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
+  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
+  const set_tail tail(mem, n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, o, n_sets, d_cidx, d_pre))) return rc;
+  if (Q) {
+    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
+    const uint32_t *sid = d_ssid, *ci = d_cidx;
+    with_group(k.group, [&](auto G) {
+      KL(KID_KEYSET_ACCUM, k_keyset_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, (const uint8_t*)k.aff, ci, o, so, sid, d_part);
+    });
+    for (uint64_t step = 1; step < qmax; step <<= 1)
+      with_group(k.group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
+  }
+  rc = run_set_tail(c, tail, sig_group, scheme, scheme == BLSGPU_SCHEME_AUG, KID_MULTI_OUT, n_sets, o, so, nullptr, d_part, d_sigs, fmt, d_msgs, d_moffs);
+  if (rc) return rc;
+  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const unsigned long long*)d_pre, tail.st);
+  HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, tail.st, n_sets);
+}
+API_CATCH
+
+int blsgpu_sum_indexed_batch(uint64_t keyset, const uint32_t* idx, const uint64_t* offsets, size_t n_sets, void* out) try {
+  KeySet k;
+  int rc = keyset_find(keyset, k);
+  if (rc) return rc;
+  if (!offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  if (n_sets && !out) return fail(BLSGPU_E_ARG, "null argument");
+  std::vector<uint64_t> offs;
+  if ((rc = read_offsets(offsets, n_sets, "offsets", offs))) return rc;
+  const size_t n = (size_t)offs[n_sets];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more points in one call");
+  if (n && !idx) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
+  std::vector<uint64_t> soffs;
+  std::vector<uint32_t> ssid;
+  const uint64_t qmax = multi_strip_plan(offs.data(), n_sets, L, soffs, ssid);
+  const size_t Q = ssid.size();
+  CTX_ACQUIRE_ON(c, k.devidx);
+  const int group = k.group;
+  const size_t osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
+  rc = arena_reserve(c, 2 * pad256(4 * n) + 2 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) + pad256(osz * n_sets) + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  uint32_t* d_cidx;
+  unsigned long long* h_pre;
+  if ((rc = keyset_check_whole(c, k, idx, n, &d_cidx, &h_pre))) return rc;
+  const uint64_t *o, *so;
+  if ((rc = upload_offsets(c, offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
+  Carver mem{c};
+  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
+  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
+  uint8_t* d_out = mem.stage_out<uint8_t>(out, osz * n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (Q) {
+    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
+    const uint32_t *sid = d_ssid, *ci = d_cidx;
+    with_group(group, [&](auto G) {
+      KL(KID_KEYSET_ACCUM, k_keyset_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, (const uint8_t*)k.aff, ci, o, so, sid, d_part);
+    });
+    for (uint64_t step = 1; step < qmax; step <<= 1)
+      with_group(group, [&](auto G) { KL(KID_SUM_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
+  }
+  with_group(group, [&](auto G) {
+    KL(KID_SUM_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, so, (const uint32_t*)nullptr, (const uint8_t*)d_part, d_out,
+       (int32_t*)nullptr);
+  });
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
+  SYNC_FLUSH(c);
+  if (*h_pre == 0) return fail(BLSGPU_E_ARG, "an index is outside the key set");
+  return 0;
+}
+API_CATCH
+
+int blsgpu_verify_secure_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
+                                       const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt, int32_t* status) try {
+  indexed_args a;
+  int rc = indexed_begin(a, scheme, keyset, idx, key_offsets, n_sets, sigs, msgs, msg_offsets, fmt, status);
+  if (rc) return rc;
+  const KeySet& k = a.k;
+  const int sig_group = k.sig_group, pk_group = k.group;
+  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
+  if (ser_format == 1 && sig_group != 2)
+    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
+  if (n_sets == 0) return 0;
+  const size_t n = a.n;
+  const std::vector<uint64_t>& offs = a.offs;
+  // plan, as blsgpu_verify_secure_batch: a set of at least BLSGPU_SECURE_BATCH_MAX keys runs one at a time through the machinery of
+  // blsgpu_verify_secure, on keys gathered into the arena; all others through the segmented kernels of secure.cuh and one
+  // multiplication per key, from the fixed-base tables when the set has them
+  const uint64_t max_small = (uint64_t)knobs().secure_batch_max;
+  CTX_ACQUIRE_ON(c, k.devidx);
+  const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED),
+               osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
+  std::vector<uint32_t> hflags(n_sets, 0);
+  uint64_t tmax_small = 0, tmax_large = 0;
+  for (size_t s = 0; s < n_sets; s++) {
+    const uint64_t t = offs[s + 1] - offs[s];
+    if (t >= max_small) {
+      hflags[s] = SECURE_F_LARGE;
+      tmax_large = std::max(tmax_large, t);
+    } else {
+      tmax_small = std::max(tmax_small, t);
+    }
+  }
+  const size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax_small / 256)));
+  const size_t mtotal = (size_t)a.moffs[n_sets];
+  const size_t large_bytes = tmax_large ? pad256(psz * n) + keysort_ws_bytes(tmax_large, width) + msm_ws_bytes(tmax_large) + pad256(osz * accumulate_lanes(tmax_large)) +
+                                              pad256(osz * POINT_TREE_START) + 4096
+                                        : 0;
+  rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n_sets) + 2 * pad256(width * n) + pad256(32 * n) + 2 * pad256(4 * n) + pad256(osz * n) +
+                            pad256(ssz * n_sets) + pad256(mtotal) + 2 * pad256(8 * (n_sets + 1)) + pad256(32 * n_sets) + 2 * pad256(4 * n_sets) +
+                            2 * pad256(288 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) + pad256((size_t)WS_F_WORDS * 4 * n_sets) + large_bytes + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_idx = nullptr, *d_sigs, *d_msgs, *d_moffs;
+  if (n && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
+  const uint64_t* o;
+  if ((rc = upload_offsets(c, offs, &o))) return rc;
+  Carver mem{c};
+  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
+  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n_sets);
+  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
+  uint8_t* d_sorted = mem.take<uint8_t>(width * n);
+  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
+  uint32_t* d_rank = mem.take<uint32_t>(4 * n);
+  uint32_t* d_sid = mem.take<uint32_t>(4 * n);
+  uint8_t* d_part = mem.take<uint8_t>(osz * n);
+  uint8_t* d_H = mem.take<uint8_t>(32 * n_sets);
+  uint32_t* d_flags = mem.take<uint32_t>(4 * n_sets);
+  uint8_t* d_keys = tmax_large ? mem.take<uint8_t>(psz * n) : nullptr;
+  const set_tail tail(mem, n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, o, n_sets, d_cidx, d_pre))) return rc;
+  if (n) {
+    // PublicKey::to_bytes / to_bytes_with_mode of every key: the stored bytes, no compression and no inversion
+    const size_t cnt_ = n;
+    KEYSET_GATHER(width / 4, k.comp, ser_format, d_bytes);
+    if (tmax_small) {
+      HIPCK(hipMemsetAsync(d_rank, 0, 4 * n, c->stream));
+      if (width == 96)
+        KL(KID_SECURE_RANK, k_secure_rank<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_flags, d_rank, d_sid);
+      else
+        KL(KID_SECURE_RANK, k_secure_rank<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
+           (const uint32_t*)d_flags, d_rank, d_sid);
+      KL(KID_SECURE_GATHER, k_secure_gather, dim3(blocks_for(n * (width / 4))), dim3(BLS_BLOCK), n, width, o, (const uint8_t*)d_bytes,
+         (const uint32_t*)d_rank, (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_sorted);
+      KL(KID_SECURE_DIGEST, k_secure_digest, dim3((unsigned)n_sets), dim3(BLS_BLOCK), n_sets, width, o, (const uint8_t*)d_sorted,
+         (const uint32_t*)d_flags, d_H);
+      KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_rank, (const uint32_t*)d_sid,
+         (const uint8_t*)d_H, d_flags, d_scal);
+      if ((rc = keyset_launch_mul(c, k, n, d_cidx, d_scal, d_sid, d_flags, d_part))) return rc;
+      for (uint64_t step = 1; step < tmax_small; step <<= 1) {
+        with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part); });
+      }
+    }
+    if (tmax_large) KEYSET_GATHER(psz / 4, k.aff, 0, d_keys);
+    const size_t mark = c->arena_off;
+    for (size_t s = 0; s < n_sets; s++) {
+      if (!(hflags[s] & SECURE_F_LARGE)) continue;
+      const size_t lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]), T = accumulate_lanes(t);
+      c->arena_off = mark;
+      keysort_ws w;
+      if ((rc = keysort_ws_take(c, t, width, w))) return rc;
+      uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
+      if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
+      if ((rc = run_key_sort_to_host(c, d_bytes + width * lo, t, width, w, nullptr, nullptr))) return rc;
+      uint8_t H[32];
+      keys_digest_host(c->hpin, width * t, H);
+      HIPCK(hipMemcpy(d_H + 32 * s, H, 32, hipMemcpyHostToDevice));       // the stream is idle here (the sort synchronised)
+      if ((rc = run_coefficients(c, d_H + 32 * s, w.perm_a, t, 0, t, 0, d_scal + 32 * lo, (int32_t*)(d_flags + s)))) return rc;
+      rc = with_group(pk_group, [&](auto G) {
+        return run_point_sum<G()>(c, d_keys + psz * lo, BLSGPU_FMT_RAW_AFFINE, d_scal + 32 * lo, nullptr, t, d_msm, T);
+      });
+      if (rc) return rc;
+      HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
+    }
+    c->arena_off = mark;
+  }
+  if ((rc = run_set_tail(c, tail, sig_group, scheme, 0, KID_SECURE_OUT, n_sets, o, o, d_flags, d_part, d_sigs, fmt, d_msgs, d_moffs))) return rc;
+  KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, tail.st);
+  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const unsigned long long*)d_pre, tail.st);
+  HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, tail.st, n_sets);
+}
+API_CATCH
+
+int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                size_t n, int fmt, int32_t* status) try {
+  KeySet k;
+  int rc = keyset_find(keyset, k);
+  if (rc) return rc;
+  const int sig_group = k.sig_group;
+  if ((rc = check_common(sig_group, scheme, fmt))) return rc;
+  if (n == 0) return 0;
+  if (!idx || !sigs || !msg_offsets || !status) return fail(BLSGPU_E_ARG, "null argument");
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more items in one call");
+  CTX_ACQUIRE_ON(c, k.devidx);
+  uint64_t total = 0;
+  if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + n, 8, hipMemcpyDeviceToHost));
+  else total = msg_offsets[n];
+  const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt), sgb = sig_size(sig_group, fmt) * n;
+  rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(total) + pad256(8 * (n + 1)) + pad256(4 * n) +
+                            2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_idx, *d_sigs, *d_msgs, *d_offs;
+  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
+  Carver mem{c};
+  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
+  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n);
+  uint8_t* d_aff = mem.take<uint8_t>(psz * n);
+  uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(ksz * n);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  // one key per item: the gather is a few hundred bytes against a pairing, so the keys go to the arena, in the signatures' format
+  // (run_verify_items reads both with one)
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre))) return rc;
+  const size_t cnt_ = n;
+  KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
+  if (d_keys != d_aff)
+    with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
+  rc = run_verify_items(c, sig_group, scheme == BLSGPU_SCHEME_AUG, d_keys, (const uint8_t*)d_sigs, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, 0,
+                        scheme_dst(sig_group, scheme), n, d_pairs, d_f, d_status, 0);
+  if (rc) return rc;
+  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
+  HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, d_status, n);
 }
 API_CATCH
 }  // extern "C"

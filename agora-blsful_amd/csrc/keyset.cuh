@@ -1,0 +1,91 @@
+// Registered key sets (blsgpu_keyset_*, the *_indexed_batch entry points): a long-lived table of public keys on the device, and
+// sets named as lists of positions in it.  Per entry the table keeps the affine record (RAW_AFFINE layout, all-zero for the
+// identity AND for an invalid entry), the Modern compressed bytes and the status its deserialisation gave.
+// Shared by the kernels (tu_keyset.inc), the library and the host harness (tests/hostsim_keyset):
+//   * the fixed-base table of a key P: the affine points d 2^(4 j) P for the positive digits d = 1 .. 8 of a signed 4-bit window
+//     and the windows j of ONE endomorphism sub-scalar (128 bits for G1 keys, 64 for G2 keys), plus the single point of the
+//     carry window above them.  The E images of the endomorphism split (msm2.cuh) are derived from a table point when it is
+//     used, so one table serves every sub-scalar;
+//   * keyset_digit: the signed recoding of a sub-scalar, digits in [-7, 8], the carry of the top window leaving as one more digit
+//     (0 or 1);
+//   * keyset_pre_key / keyset_pre_status: what k_keyset_check leaves per set -- an out-of-range index first, then the creation
+//     status of the first invalid entry in input order -- packed so that one atomicMin per position decides it.
+#pragma once
+#include "multi_batch.cuh"
+
+#define KEYSET_W 4
+#define KEYSET_ROW 8                      // positive digits of a window: 1 .. 2^(W - 1)
+#define KEYSET_SKIP 0xffffffffu           // an index k_keyset_check did not accept: the kernels after it read nothing for it
+#define KEYSET_PRE_NONE 0xffffffffffffffffull
+#define KEYSET_E_ARG (-3)                 // BLSGPU_E_ARG (include/blsgpu.h), in a status slot: the set names an index outside the table
+
+// G: the keys' group.  WINDOWS counts the carry window; POINTS is the table's records per key.
+template <int G>
+struct keyset_shape;
+template <>
+struct keyset_shape<1> {
+  enum { E = 2, WORDS = 2, FULL = 32, WINDOWS = 33, POINTS = 32 * KEYSET_ROW + 1, REC_BYTES = 96 };
+};
+template <>
+struct keyset_shape<2> {
+  enum { E = 4, WORDS = 1, FULL = 16, WINDOWS = 17, POINTS = 16 * KEYSET_ROW + 1, REC_BYTES = 192 };
+};
+
+// digit j of the sub-scalar a (`words` 64-bit words), recoded from the low end: the caller walks j upwards from 0 with carry = 0
+// and threads `carry` through.  Window j = 16 words (one past the value) holds the carry alone.
+BLS_FN int keyset_digit(const uint64_t* a, int words, int j, uint32_t& carry) {
+  const int wi = j >> 4, sh = (j & 15) * KEYSET_W;
+  const uint32_t v = wi < words ? (uint32_t)(a[wi] >> sh) & 15u : 0u;
+  int d = (int)v + (int)carry;
+  if (d > KEYSET_ROW) {
+    d -= 2 * KEYSET_ROW;
+    carry = 1;
+  } else {
+    carry = 0;
+  }
+  return d;
+}
+// the record of |d| 2^(4 j) P in a key's table (d != 0; in the carry window, j == full, d is 1)
+BLS_FN uint32_t keyset_record(int j, int dabs) { return (uint32_t)(j * KEYSET_ROW + dabs - 1); }
+
+BLS_FN uint64_t keyset_pre_key(bool out_of_range, uint64_t pos_in_set, int32_t entry_status) {
+  if (out_of_range) return 0;
+  if (entry_status != 0) return ((pos_in_set + 1) << 8) | (uint64_t)(entry_status & 0xff);
+  return KEYSET_PRE_NONE;
+}
+BLS_FN int32_t keyset_pre_status(uint64_t key) { return key == 0 ? KEYSET_E_ARG : (int32_t)(key & 0xff); }
+
+#if defined(__HIPCC__)
+#include "kernels.cuh"
+// ---- kernels (tu_keyset1.hip: the group-independent ones and G1 keys, tu_keyset2.hip: G2 keys)
+// create: any raw format -> the stored affine record and Modern bytes; an entry whose status is not OK becomes the zero record
+template <int G>
+__global__ void k_keyset_seal(size_t n, const uint8_t* pts, int fmt, const int32_t* status, uint8_t* recs, uint8_t* comp);
+// create, with tables: the multiples of keys [k0, k0 + cnt) as Jacobian points in jac_ws, their running Z products in prod_ws
+// (POINTS records per lane each), one inversion per lane, the affine records into table
+template <int G>
+__global__ void k_keyset_build(size_t k0, size_t cnt, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws, uint8_t* table);
+// per position: the index against the table's size and the entry's status; cidx[i] = idx[i] or KEYSET_SKIP, pre[set] by atomicMin
+// (offs == nullptr: every position is its own set)
+__global__ void k_keyset_check(size_t n, const uint64_t* offs, size_t n_sets, const uint32_t* idx, uint64_t n_keys, const int32_t* kstatus,
+                               uint32_t* cidx, unsigned long long* pre);
+__global__ void k_keyset_fin(size_t n_sets, const unsigned long long* pre, int32_t* status);
+// dst record i = src record cidx[i] (words 32-bit words each; zeros for KEYSET_SKIP); legacy: the Dash header transcode of byte 0
+__global__ void k_keyset_gather(size_t n, size_t words, const uint32_t* cidx, const uint32_t* src, int legacy, uint32_t* dst);
+// RAW_AFFINE -> RAW_PROJ (blsgpu_keyset_get)
+template <int G>
+__global__ void k_keyset_to_proj(size_t n, const uint8_t* recs, uint8_t* out);
+// the strip sum of multi_batch.cuh over table[cidx[i]]: every addition is the mixed one
+template <int G>
+__global__ void k_keyset_accumulate_seg(size_t n_strips, const uint8_t* recs, const uint32_t* cidx, const uint64_t* key_offs,
+                                        const uint64_t* strip_offs, const uint32_t* strip_sid, uint8_t* part);
+template <>
+__global__ void k_keyset_accumulate_seg<1>(size_t, const uint8_t*, const uint32_t*, const uint64_t*, const uint64_t*, const uint32_t*, uint8_t*);
+template <>
+__global__ void k_keyset_accumulate_seg<2>(size_t, const uint8_t*, const uint32_t*, const uint64_t*, const uint64_t*, const uint32_t*, uint8_t*);
+// part[i] = scal[i] * key[cidx[i]]: TAB = 1 from the fixed-base table, TAB = 0 by share_ladder.  With sid / flags (the batched
+// verify_secure) a set that carries a flag leaves the identity, as k_share_ladder.
+template <int G, int TAB>
+__global__ void k_keyset_mul(size_t n, const uint8_t* recs, const uint8_t* table, const uint32_t* cidx, const uint8_t* scal, const uint32_t* sid,
+                             const uint32_t* flags, uint8_t* part);
+#endif

@@ -470,6 +470,52 @@ int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* si
  * Every pointer may be host or device memory; a device `out` feeds the batched verifiers directly.  n_sets == 0 returns 0. */
 int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t n_sets, int fmt, void* out);
 
+/* ---- Registered key sets: a long-lived table of public keys on the device; a set of signers is a list of positions in it.
+ * The callers this serves keep a masternode list or a validator registry for hours and name signers as bitsets over it: they
+ * deserialise and upload every key ONCE (blsgpu_keyset_create) and afterwards pass 4 bytes per (set, key).
+ *
+ * A handle is an opaque non-zero id from a registry inside the library, never a pointer; every entry point given a stale or
+ * unknown id returns BLSGPU_E_ARG.  A key set is immutable; concurrent calls may read one set.  Destroying a set while a call
+ * uses it is the caller's error (the call may then read freed device memory).  blsgpu_shutdown frees every key set.  The memory
+ * is hipMalloc'd outside the context arenas on the device of the context that ran blsgpu_keyset_create (device 0 of a
+ * multi-device binding unless the call came from a sharded sub-call); the indexed entry points run on that device and do not
+ * shard.
+ *
+ * create: `keys` (host or device) holds n keys of the group the signatures of sig_group do NOT live in, in any BLSGPU_FMT_*
+ * (LEGACY for sig_group 2 only).  Wire formats go through the checked decompression of blsgpu_deserialize and status[i] (n
+ * entries, host or device, may be NULL) is what that call gives for key i; raw formats are trusted as everywhere else and give
+ * BLSGPU_OK.  A key whose status is not BLSGPU_OK is kept as an INVALID ENTRY and creation still succeeds; the identity is a valid
+ * entry.  Nothing of the caller's buffers is retained.  flags & BLSGPU_KEYSET_TABLES also builds the fixed-base tables (about
+ * 29 KB per key) that turn a scalar multiplication of an entry into about 64 mixed additions and no doubling; when they would
+ * exceed BLSGPU_KEYSET_TABLE_MB MiB (default 4096) or the device has no room, the set is created without them and `has_tables`
+ * reports 0.  Tables never change a result.
+ * get: entries idx[0 .. count) in any format, with their creation statuses (status may be NULL); an invalid entry leaves as the
+ * identity.  mul: out[i] = scalars[i] * key[idx[i]] as RAW_PROJ (scalars: 32 bytes little-endian each, any value below 2^256,
+ * reduced modulo r as blsgpu_msm_* does); the identity and invalid entries give the identity (Z = 0).  Both return BLSGPU_E_ARG when an index is not below the set's size. */
+#define BLSGPU_KEYSET_TABLES 1
+int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int flags, int32_t* status, uint64_t* out_handle);
+int blsgpu_keyset_destroy(uint64_t handle);
+int blsgpu_keyset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_tables, uint64_t* device_bytes);
+int blsgpu_keyset_get(uint64_t handle, const uint32_t* idx, size_t count, int fmt_out, void* out, int32_t* status);
+int blsgpu_keyset_mul(uint64_t handle, const uint32_t* idx, const uint8_t* scalars, size_t count, void* out);
+
+/* The batched entry points with (keyset, idx) in place of the keys: blsgpu_multi_verify_batch, blsgpu_verify_secure_batch,
+ * blsgpu_sum_batch and blsgpu_verify_batch (one key per item) over positions in a key set.  sig_group comes from the key set and
+ * fmt (RAW_PROJ / RAW_AFFINE) describes the signatures only; idx, the offsets, sigs, msgs and status may be host or device memory.
+ * status[s] is the first of: BLSGPU_E_ARG (-3, in the status slot; the call still returns 0 and the other sets are unaffected)
+ * when the set names an index that is not below the key set's size -- nothing outside the table is read; the creation status of
+ * the first invalid entry the set names, in input order (the reference fails at deserialisation, before any verify); otherwise
+ * exactly what the non-indexed entry point returns for the gathered keys (repeated indices are repeated keys, the empty-set
+ * rules are unchanged).  blsgpu_sum_indexed_batch has no status vector: an index outside the table makes the call return
+ * BLSGPU_E_ARG, invalid entries add nothing, as identities do. */
+int blsgpu_multi_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets,
+                                      const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status);
+int blsgpu_verify_secure_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets,
+                                       const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt, int32_t* status);
+int blsgpu_sum_indexed_batch(uint64_t keyset, const uint32_t* idx, const uint64_t* offsets, size_t n_sets, void* out /* RAW_PROJ */);
+int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint8_t* msgs,
+                                const uint64_t* msg_offsets, size_t n, int fmt, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

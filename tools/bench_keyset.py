@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Registered key sets against keys by value: what the index-addressed entry points and the fixed-base tables cost and save.
+
+usage: python tools/bench_keyset.py [--reps 5] [--table 16384] [--shapes 0,1,..] [--out profiles/keyset_bench.json]
+Every input lives on the device (TensorOps).  Per shape, indices are drawn at random from a table of --table keys k * g
+(blsgpu_sign_batch) and four things are timed, each the median of --reps calls:
+  (a) the non-indexed entry point on the same keys laid out contiguously (three repeats of the whole measurement: their range is the
+      run-to-run spread the other figures are read against);
+  (b) the indexed entry point on a key set without tables;
+  (c) the indexed entry point on a key set with tables (the multi shapes never multiply, so (c) only shows that tables cost nothing);
+  (d) blsgpu_keyset_create from RAW_PROJ device memory, with and without tables.
+On a build without key sets (the parent commit) only (a) runs: the tool skips what the library does not export.  The verdicts are
+mostly INVALID_SIGNATURE, which costs the same as OK.  Prints one JSON line per shape and writes them all to --out."""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+SIG_POOL = 4096
+SHAPES = [('secure', 'Bls12381G2Impl Modern', 2, 1024, 400), ('secure', 'Bls12381G2Impl Modern', 2, 4096, 50), ('secure', 'Bls12381G1Impl', 1, 256, 400),
+          ('multi', 'Bls12381G2Impl', 2, 1024, 512), ('multi', 'Bls12381G1Impl', 1, 1024, 512)]
+
+
+def median_ms(run, reps, sync):
+    run()                                                                    # warm-up (workspace growth)
+    sync()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        run()
+        ts.append(time.perf_counter() - t0)
+    return statistics.median(ts) * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--table', type=int, default=16384)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'keyset_bench.json'))
+    ap.add_argument('--shapes', default='')
+    a = ap.parse_args()
+    import torch
+    import __graft_entry__ as ge
+    api = ge.import_pkg().api
+    dev = torch.device('cuda', 0)
+    ops = api.TensorOps(dev)
+    sync = torch.cuda.synchronize
+    have = hasattr(api, 'KeySet')                                            # the parent commit has no key sets: (a) only
+    rng = random.Random(2026)
+    pools, sets, create = {}, {}, {}
+    shapes = [SHAPES[int(i)] for i in a.shapes.split(',')] if a.shapes else SHAPES
+    for sg in sorted({s[2] for s in shapes}):
+        ks = [rng.randrange(1, R) for _ in range(a.table)]
+        pks = api.sign_batch(sg, api.BASIC, ks, [b''] * a.table)[0]
+        sigs = api.sign_batch(sg, api.BASIC, ks[:SIG_POOL], [b'bench'] * SIG_POOL)[1]
+        pools[sg] = (torch.tensor(list(b''.join(pks)), dtype=torch.uint8, device=dev).view(a.table, -1),
+                     torch.tensor(list(b''.join(sigs)), dtype=torch.uint8, device=dev).view(SIG_POOL, -1))
+        if have:
+            sync()
+            made = {}
+            for tables in (False, True):
+                ts = []
+                for _ in range(3):
+                    if tables in made:
+                        made[tables].close()
+                    t0 = time.perf_counter()
+                    made[tables] = api.KeySet.create_device(sg, pools[sg][0].data_ptr(), a.table, api.FMT_RAW_PROJ, tables=tables)
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                create['sig_group %d %s tables' % (sg, 'with' if tables else 'without')] = dict(
+                    ms=round(statistics.median(ts), 3), first_ms=round(ts[0], 3), **made[tables].info())
+            sets[sg] = made
+    rows = [{'table_entries': a.table, 'create': create}]
+    print(json.dumps(rows[0]), flush=True)
+    for kind, name, sg, n_sets, t in shapes:
+        n = n_sets * t
+        gen = torch.Generator(device=dev).manual_seed(n + sg)
+        sel = torch.randint(0, a.table, (n,), device=dev, generator=gen)
+        pks_t = pools[sg][0][sel].reshape(-1).contiguous()
+        idx_t = sel.to(torch.int32).contiguous()
+        sigs_t = pools[sg][1][torch.randint(0, SIG_POOL, (n_sets,), device=dev, generator=gen)].reshape(-1).contiguous()
+        moffs, mblob = api._offsets([b'quorum commitment %06d' % s for s in range(n_sets)])
+        msgs_t = torch.tensor(list(mblob), dtype=torch.uint8, device=dev)
+        moffs_t = torch.tensor(list(moffs), dtype=torch.int64, device=dev)
+        koffs_t = torch.arange(0, n + 1, t, dtype=torch.int64, device=dev)
+        tail = (koffs_t, sigs_t, msgs_t, moffs_t, n_sets)
+        if kind == 'secure':
+            by_value = lambda: ops.verify_secure_batch(sg, api.BASIC, pks_t, *tail)
+            indexed = lambda ks: (lambda: ops.verify_secure_indexed_batch(ks, api.BASIC, idx_t, *tail))
+        else:
+            by_value = lambda: ops.multi_verify_batch(sg, api.BASIC, pks_t, *tail)
+            indexed = lambda ks: (lambda: ops.multi_verify_indexed_batch(ks, api.BASIC, idx_t, *tail))
+        a3 = [median_ms(by_value, a.reps, sync) for _ in range(3)]
+        row = {'kind': kind, 'shape': name, 'sig_group': sg, 'sets': n_sets, 'keys_per_set': t, 'reps': a.reps,
+               'a_by_value_ms': [round(x, 3) for x in a3], 'a_spread_ms': round(max(a3) - min(a3), 3)}
+        if have:
+            want = by_value().cpu().tolist()
+            for tag, tables in (('b_indexed_ms', False), ('c_indexed_tables_ms', True)):
+                run = indexed(sets[sg][tables])
+                row[tag] = round(median_ms(run, a.reps, sync), 3)
+                row[tag.replace('_ms', '_statuses_match')] = run().cpu().tolist() == want
+            api.profile_enable(True)
+            indexed(sets[sg][True])()
+            row['c_kernel_ms'] = {k: round(v[0], 3) for k, v in api.profile_read().items() if v[0] >= 0.01}
+            api.profile_enable(False)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    for made in sets.values():
+        for ks in made.values():
+            ks.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(rows, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
