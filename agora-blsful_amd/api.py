@@ -29,6 +29,7 @@ OK, INVALID_SIGNATURE, SIG_IDENTITY, PK_IDENTITY, DUPLICATE_MESSAGE, INVALID_COE
 COMMITMENT_IDENTITY, PROOF_IDENTITY, ZERO_CHALLENGE = 9, 10, 11    # blsgpu_sig_proof_verify_batch only
 INVALID_SCHEME, VSSS_ERROR = 12, 13                                  # blsgpu_combine_shares only
 INVALID_DECRYPTION_SHARE, BAD_FRAME = 14, 15                        # the threshold signcryption calls only
+ELGAMAL_IDENTITY, ELGAMAL_ZERO_PROOF, CHALLENGE_MISMATCH = 16, 17, 18   # blsgpu_elgamal_proof_verify_batch only
 
 EXPORTS = [
     'blsgpu_init', 'blsgpu_shutdown', 'blsgpu_last_error', 'blsgpu_verify_batch', 'blsgpu_multi_verify',
@@ -45,6 +46,7 @@ EXPORTS = [
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
     'blsgpu_keyset_create', 'blsgpu_keyset_destroy', 'blsgpu_keyset_info', 'blsgpu_keyset_get', 'blsgpu_keyset_mul',
     'blsgpu_multi_verify_indexed_batch', 'blsgpu_verify_secure_indexed_batch', 'blsgpu_sum_indexed_batch', 'blsgpu_verify_indexed_batch',
+    'blsgpu_elgamal_message_generator', 'blsgpu_elgamal_proof_verify_batch', 'blsgpu_elgamal_open_batch',
 ]
 
 
@@ -178,6 +180,9 @@ def load_library(path=None):
         lib.blsgpu_verify_secure_indexed_batch.argtypes = [ci, h, u32p, u64p, sz, vp, u8p, u64p, ci, ci, i32p]
         lib.blsgpu_sum_indexed_batch.argtypes = [h, u32p, u64p, sz, vp]
         lib.blsgpu_verify_indexed_batch.argtypes = [ci, h, u32p, vp, u8p, u64p, sz, ci, i32p]
+        lib.blsgpu_elgamal_message_generator.argtypes = [ci, ci, vp]
+        lib.blsgpu_elgamal_proof_verify_batch.argtypes = [ci, vp, sz, vp, vp, vp, u8p, u8p, u8p, sz, ci, i32p]
+        lib.blsgpu_elgamal_open_batch.argtypes = [ci, vp, u8p, vp, u64p, sz, ci, vp, i32p]
         _lib = lib
     return _lib
 
@@ -493,6 +498,90 @@ def signcrypt_decrypt_batch(sig_group, scheme, cts, keys, fmt=FMT_RAW_PROJ, with
         raise ValueError('one key per ciphertext')
     out, st = _signcrypt_open(sig_group, scheme, cts, None, b''.join(keys), None, fmt)
     return (out, st) if with_status else out
+
+
+def elgamal_error_from_status(st):
+    """Status of blsgpu_elgamal_proof_verify_batch -> the BlsError of BlsElGamal::verify_proof (src/traits/elgamal.rs:187-222)."""
+    if st == ELGAMAL_IDENTITY:
+        return BlsError('InvalidInputs', 'Parameters or ciphertext values are identity point')
+    if st == ELGAMAL_ZERO_PROOF:
+        return BlsError('InvalidInputs', 'Proof values are zero')
+    if st == CHALLENGE_MISMATCH:
+        return BlsError('InvalidInputs', 'Challenge values do not match')
+    return error_from_status(st)
+
+
+def _key_point_bytes(sig_group, fmt):
+    return _POINT_BYTES[fmt] * (2 if sig_group == 1 else 1)
+
+
+def elgamal_message_generator(sig_group, fmt=FMT_RAW_PROJ):
+    """BlsElGamal::message_generator() of the impl, in the key group (blsgpu_elgamal_message_generator)."""
+    lib = init()
+    out = ctypes.create_string_buffer(_key_point_bytes(sig_group, fmt))
+    _check(lib.blsgpu_elgamal_message_generator(sig_group, fmt, ctypes.cast(out, ctypes.c_void_p)))
+    return out.raw
+
+
+def _scalars(xs):
+    return b''.join(int(x).to_bytes(32, 'little') for x in xs)
+
+
+def elgamal_proof_verify_batch(sig_group, pks, generators, c1s, c2s, message_proofs, blinder_proofs, challenges, fmt=FMT_RAW_PROJ):
+    """BlsElGamal::verify_proof for n proofs in one call (blsgpu_elgamal_proof_verify_batch).  pks: n keys, or ONE key that every
+    proof is to; generators: None (the message generator) or n points; c1s, c2s: n points; the three scalar lists: n ints below
+    2^256.  Returns the list of statuses."""
+    lib = init()
+    n = len(c1s)
+    if len(c2s) != n or len(message_proofs) != n or len(blinder_proofs) != n or len(challenges) != n or (generators is not None and len(generators) != n):
+        raise ValueError('one c1, c2, generator and scalar triple per proof')
+    st = (ctypes.c_int32 * max(n, 1))()
+    pb, c1b, c2b = b''.join(pks), b''.join(c1s), b''.join(c2s)
+    gb = b''.join(generators) if generators is not None else None
+    _check(lib.blsgpu_elgamal_proof_verify_batch(sig_group, _ptr(pb), len(pks), _ptr(gb) if gb is not None else None, _ptr(c1b), _ptr(c2b),
+                                                 _ptr(_scalars(message_proofs)), _ptr(_scalars(blinder_proofs)), _ptr(_scalars(challenges)), n, fmt,
+                                                 ctypes.cast(st, ctypes.c_void_p)))
+    return list(st)[:n]
+
+
+def _elgamal_open(sig_group, c2s, ids, pts, soffs, fmt):
+    lib = init()
+    n_ct = len(c2s)
+    osz = _key_point_bytes(sig_group, FMT_RAW_PROJ)
+    out = ctypes.create_string_buffer(osz * max(n_ct, 1))
+    st = (ctypes.c_int32 * max(n_ct, 1))()
+    cb = b''.join(c2s)
+    _check(lib.blsgpu_elgamal_open_batch(sig_group, _ptr(cb) if cb else None, _ptr(ids) if ids is not None else None, _ptr(pts) if pts else None,
+                                         ctypes.cast(soffs, ctypes.c_void_p) if soffs is not None else None, n_ct, fmt,
+                                         ctypes.cast(out, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[osz * i:osz * (i + 1)] for i in range(n_ct)], list(st)[:n_ct]
+
+
+def elgamal_open_batch(sig_group, c2s, shares, fmt=FMT_RAW_PROJ):
+    """ElGamalDecryptionKey::from_shares + decrypt for many ciphertexts in one call (blsgpu_elgamal_open_batch): `c2s` the second
+    components, `shares` one list per ciphertext of (identifier: int, decryption share).  Returns (RAW_PROJ points c2 - key, the
+    statuses of the recovery); the point of a failed set is the identity."""
+    if len(shares) != len(c2s):
+        raise ValueError('one list of shares per ciphertext')
+    ids = _scalars(i for g in shares for i, _ in g) or b'\0'
+    return _elgamal_open(sig_group, c2s, ids, b''.join(p for g in shares for _, p in g), _count_offsets(shares), fmt)
+
+
+def elgamal_decrypt_batch(sig_group, c2s, keys, fmt=FMT_RAW_PROJ):
+    """ElGamalDecryptionKey::decrypt for many (ciphertext, key) pairs in one call: the same entry point with one key per ciphertext."""
+    if len(keys) != len(c2s):
+        raise ValueError('one key per ciphertext')
+    return _elgamal_open(sig_group, c2s, None, b''.join(keys), None, fmt)[0]
+
+
+def elgamal_sum_batch(sig_group, sets, fmt=FMT_RAW_PROJ):
+    """The sum of ElGamal ciphertexts (src/elgamal_ciphertext.rs:74-83) for many sets: `sets` is a list of lists of (c1, c2); two
+    blsgpu_sum_batch calls in the key group.  Returns one (c1, c2) of RAW_PROJ points per set."""
+    group = 2 if sig_group == 1 else 1
+    a = sum_batch(group, [[c1 for c1, _ in st] for st in sets], fmt)
+    b = sum_batch(group, [[c2 for _, c2 in st] for st in sets], fmt)
+    return list(zip(a, b))
 
 
 def proof_error_from_status(st):
@@ -975,6 +1064,31 @@ class TensorOps:
 
     def signcrypt_decrypt_batch(self, sg, scheme, us, ws, vs, v_offs, n_ct, keys):
         return self.signcrypt_open_batch(sg, scheme, us, ws, vs, v_offs, n_ct, None, keys, None)
+
+    def elgamal_message_generator(self, sg):
+        """The message generator of the impl as a RAW_PROJ uint8 tensor on the device."""
+        out = self.empty(288 if sg == 1 else 144)
+        _check(self.lib.blsgpu_elgamal_message_generator(sg, FMT_RAW_PROJ, self._p(out)))
+        return out
+
+    def elgamal_proof_verify_batch(self, sg, pks, n_pks, generators, c1s, c2s, mps, bps, chs, n, fmt=FMT_RAW_PROJ):
+        """int32 statuses (on the device) of n proof checks over device-resident points and 32-byte scalars; generators may be None."""
+        self._sync()
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_elgamal_proof_verify_batch(sg, self._p(pks), n_pks, self._p(generators) if generators is not None else None, self._p(c1s),
+                                                          self._p(c2s), self._p(mps), self._p(bps), self._p(chs), n, fmt, self._p(st)))
+        return st[:n]
+
+    def elgamal_open_batch(self, sg, c2s, n_ct, ids, shares, share_offs, fmt=FMT_RAW_PROJ):
+        """(RAW_PROJ points c2 - key as one uint8 tensor, int32 statuses), both on the device.  ids = share_offs = None: `shares`
+        holds one key per ciphertext."""
+        self._sync()
+        osz = 288 if sg == 1 else 144
+        out = self.empty(max(n_ct, 1) * osz)
+        st = self.empty(max(n_ct, 1), self.torch.int32)
+        _check(self.lib.blsgpu_elgamal_open_batch(sg, self._p(c2s), self._p(ids) if ids is not None else None, self._p(shares),
+                                                  self._p(share_offs) if share_offs is not None else None, n_ct, fmt, self._p(out), self._p(st)))
+        return out[:n_ct * osz], st[:n_ct]
 
     def point_sum(self, group, pts, n, scalars=None):
         self._sync()
@@ -1533,3 +1647,69 @@ def open_many(items):
         for i, r in zip(idx, res):
             out[i] = r
     return out
+
+
+class ElGamalCiphertext:
+    """ElGamalCiphertext<C> {c1, c2}: reference src/elgamal_ciphertext.rs.  Both in the pk group, RAW_PROJ."""
+
+    def __init__(self, impl, c1, c2):
+        self.impl, self.c1, self.c2 = impl, bytes(c1), bytes(c2)
+
+    def __add__(self, other):
+        """reference src/elgamal_ciphertext.rs:74-83: component-wise sums, on the GPU."""
+        c1, c2 = elgamal_sum_batch(self.impl.sig_group, [[(self.c1, self.c2), (other.c1, other.c2)]])[0]
+        return ElGamalCiphertext(self.impl, c1, c2)
+
+
+class ElGamalProof:
+    """ElGamalProof<C> {ciphertext, message_proof, blinder_proof, challenge}: reference src/elgamal_proof.rs; the scalars are ints."""
+
+    def __init__(self, ciphertext, message_proof, blinder_proof, challenge):
+        self.ciphertext, self.message_proof, self.blinder_proof, self.challenge = ciphertext, int(message_proof), int(blinder_proof), int(challenge)
+
+    def verify(self, pk):
+        """reference src/elgamal_proof.rs:74-84: verify_proof with the message generator; raises BlsError, returns None on Ok(())."""
+        e = elgamal_verify_many([(self, pk)])[0]
+        if e:
+            raise e
+
+
+class ElGamalDecryptionShare:
+    """ElGamalDecryptionShare<C>: reference src/elgamal_decryption_share.rs; `raw` is the pk-group point c1 * sk_i."""
+
+    def __init__(self, impl, identifier, raw):
+        self.impl, self.identifier, self.raw = impl, int(identifier), bytes(raw)
+
+
+class ElGamalDecryptionKey:
+    """ElGamalDecryptionKey<C>: reference src/elgamal_decryption_share.rs:76-90."""
+
+    def __init__(self, impl, raw):
+        self.impl, self.raw = impl, bytes(raw)
+
+    @staticmethod
+    def from_shares(shares):
+        """reference src/elgamal_decryption_share.rs:83-89: raises BlsError('VsssError') as the recovery does."""
+        impl = shares[0].impl if shares else Bls12381G2Impl
+        out, st = combine_shares(2 if impl.sig_group == 1 else 1, [[(s.identifier, s.raw, None) for s in shares]])
+        e = error_from_status(st[0])
+        if e:
+            raise e
+        return ElGamalDecryptionKey(impl, out[0])
+
+    def decrypt(self, ciphertext):
+        """reference src/elgamal_decryption_share.rs:78-80: c2 - key as a RAW_PROJ point."""
+        return elgamal_decrypt_batch(self.impl.sig_group, [ciphertext.c2], [self.raw])[0]
+
+
+def elgamal_verify_many(items):
+    """ElGamalProof.verify over many items at once: `items` is a list of (ElGamalProof, PublicKey) that share one impl; one
+    blsgpu_elgamal_proof_verify_batch call.  Returns None (Ok) or the BlsError per item, in order."""
+    if not items:
+        return []
+    sg = items[0][1].impl.sig_group
+    if any(pk.impl.sig_group != sg or pr.ciphertext.impl.sig_group != sg for pr, pk in items):
+        raise ValueError('elgamal_verify_many: every item must use the same impl')
+    st = elgamal_proof_verify_batch(sg, [pk.raw for _, pk in items], None, [pr.ciphertext.c1 for pr, _ in items], [pr.ciphertext.c2 for pr, _ in items],
+                                    [pr.message_proof for pr, _ in items], [pr.blinder_proof for pr, _ in items], [pr.challenge for pr, _ in items])
+    return [elgamal_error_from_status(x) for x in st]

@@ -23,6 +23,7 @@
 #include "multi_batch.cuh"
 #include "keyset.cuh"
 #include "signcrypt.cuh"
+#include "elgamal.cuh"
 #include "host_sha256.h"
 
 namespace {
@@ -46,6 +47,7 @@ enum {
   KID_SECURE_FIRST, KID_SECURE_LADDER, KID_SECURE_AGG_FOLD, KID_SECURE_AGG_OUT,   // blsgpu_aggregate_secure_batch (rank .. coeff count under theirs)
   KID_SUM_SEG_ACCUM, KID_SUM_FOLD, KID_SUM_OUT,           // blsgpu_sum_batch
   KID_KEYSET_SEAL, KID_KEYSET_BUILD, KID_KEYSET_CHECK, KID_KEYSET_GATHER, KID_KEYSET_ACCUM, KID_KEYSET_MUL, KID_KEYSET_FIN,   // registered key sets (keyset.cuh)
+  KID_ELGAMAL_PREP, KID_ELGAMAL_LADDER, KID_ELGAMAL_TRANSCRIPT, KID_ELGAMAL_SUB,   // blsgpu_elgamal_proof_verify_batch / blsgpu_elgamal_open_batch
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
@@ -58,7 +60,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_signcrypt_share_pairs", "k_signcrypt_keystream",
                                     "k_secure_first", "k_secure_ladder", "k_secure_agg_fold", "k_secure_agg_out",
                                     "k_sum_accumulate_seg", "k_sum_fold", "k_sum_out",
-                                    "k_keyset_seal", "k_keyset_build", "k_keyset_check", "k_keyset_gather", "k_keyset_accumulate_seg", "k_keyset_mul", "k_keyset_fin"};
+                                    "k_keyset_seal", "k_keyset_build", "k_keyset_check", "k_keyset_gather", "k_keyset_accumulate_seg", "k_keyset_mul", "k_keyset_fin",
+                                    "k_elgamal_prep", "k_elgamal_ladder", "k_elgamal_transcript", "k_elgamal_sub"};
 
 struct Ctx {
   int dev = -1;
@@ -3943,6 +3946,213 @@ int blsgpu_signcrypt_open_batch(int sig_group, int scheme, const void* us, const
   HIPCK(hipGetLastError());
   if (total && (rc = stage_back(c, frames, d_frames, total))) return rc;
   if ((rc = stage_back(c, pt_range, d_range, 16 * n_ct))) return rc;
+  return status_out_and_sync(c, status, d_status, n_ct);
+}
+API_CATCH
+
+// ---- ElGamal over the public-key group (elgamal.cuh): proof verification and opening with shares, many items per call
+// What every call of an impl shares, made once per process: the message generator BlsElGamal::message_generator() =
+// hash_to_curve(generator.to_bytes(), ENC_DST) in the key group (reference src/traits/elgamal.rs:20-23; ENC_DST src/impls/g1.rs:129,
+// g2.rs:127 -- the tag names the other group than the one it hashes into, kept as the reference has it) as a Z = 1 RAW_PROJ record,
+// and the transcript's state after its fixed prefix (Transcript::new, "dst", "base point").
+static const uint8_t ELGAMAL_G1_GEN[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f, 0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05,
+                                           0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58, 0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
+static const uint8_t ELGAMAL_G2_GEN[96] = {0x93, 0xe0, 0x2b, 0x60, 0x52, 0x71, 0x9f, 0x60, 0x7d, 0xac, 0xd3, 0xa0, 0x88, 0x27, 0x4f, 0x65, 0x59, 0x6b, 0xd0, 0xd0, 0x99, 0x20, 0xb6, 0x1a,
+                                           0xb5, 0xda, 0x61, 0xbb, 0xdc, 0x7f, 0x50, 0x49, 0x33, 0x4c, 0xf1, 0x12, 0x13, 0x94, 0x5d, 0x57, 0xe5, 0xac, 0x7d, 0x05, 0x5d, 0x04, 0x2b, 0x7e,
+                                           0x02, 0x4a, 0xa2, 0xb2, 0xf0, 0x8f, 0x0a, 0x91, 0x26, 0x08, 0x05, 0x27, 0x2d, 0xc5, 0x10, 0x51, 0xc6, 0xe4, 0x7a, 0xd4, 0xfa, 0x40, 0x3b, 0x02,
+                                           0xb4, 0x51, 0x0b, 0x64, 0x7a, 0xe3, 0xd1, 0x77, 0x0b, 0xac, 0x03, 0x26, 0xa8, 0x05, 0xbb, 0xef, 0xd4, 0x80, 0x56, 0xc8, 0xc1, 0x21, 0xbd, 0xb8};
+struct ElGamalConsts {
+  bool ready = false;
+  uint8_t h[288];        // the message generator, RAW_PROJ with Z = 1
+  strobe128 prefix;
+};
+static ElGamalConsts g_elgamal[2];
+static std::mutex g_elgamal_mu;
+// Takes a context of its own: call it before the entry point leases one.
+static int elgamal_consts(int sig_group, const ElGamalConsts** out) {
+  std::lock_guard<std::mutex> lk(g_elgamal_mu);
+  ElGamalConsts& e = g_elgamal[sig_group - 1];
+  if (!e.ready) {
+    const int pkg = key_group(sig_group);
+    const uint8_t* gen = pkg == 1 ? ELGAMAL_G1_GEN : ELGAMAL_G2_GEN;
+    const size_t K = point_bytes(pkg, BLSGPU_FMT_COMPRESSED), osz = point_bytes(pkg, BLSGPU_FMT_RAW_PROJ);
+    const char* dst = sig_group == 1 ? "BLS_ELGAMAL_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_" : "BLS_ELGAMAL_BLS12381G1_XMD:SHA-256_SSWU_RO_NUL_";
+    CTX_ACQUIRE(c);
+    int rc = arena_reserve(c, pad256(K) + pad256(16) + pad256(osz) + 4096);
+    if (rc) return rc;
+    c->arena_off = 0;
+    Carver mem{c};
+    uint8_t* d_msg = mem.take<uint8_t>(K);
+    uint64_t* d_offs = mem.take<uint64_t>(16);
+    uint8_t* d_h = mem.take<uint8_t>(osz);
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    const uint64_t offs[2] = {0, K};
+    if ((rc = h2d_small(c, d_msg, gen, K)) || (rc = h2d_small(c, d_offs, offs, 16))) return rc;
+    if ((rc = run_hash_group(c, pkg, 1, d_msg, d_offs, make_dst((const uint8_t*)dst, strlen(dst)), d_h))) return rc;
+    with_group(pkg, [&](auto G) { KL(KID_MSM_NORM, k_normalize<G()>, dim3(1), dim3(BLS_BLOCK), d_h); });
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(e.h, d_h, osz, hipMemcpyDeviceToHost, c->stream));
+    SYNC_FLUSH(c);
+    elgamal_transcript_prefix(e.prefix, gen, K);
+    e.ready = true;
+  }
+  *out = &e;
+  return 0;
+}
+
+int blsgpu_elgamal_message_generator(int sig_group, int fmt_out, void* out) try {
+  if (!initialised()) return NOT_INIT();
+  if (sig_group != 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "sig_group must be 1 (Bls12381G1Impl) or 2 (Bls12381G2Impl)");
+  if (fmt_out < BLSGPU_FMT_RAW_PROJ || fmt_out > BLSGPU_FMT_LEGACY) return fail(BLSGPU_E_ARG, "unknown point format");
+  if (!out) return fail(BLSGPU_E_ARG, "null argument");
+  const ElGamalConsts* e;
+  int rc = elgamal_consts(sig_group, &e);
+  if (rc) return rc;
+  const int pkg = key_group(sig_group);
+  if (fmt_out == BLSGPU_FMT_COMPRESSED || fmt_out == BLSGPU_FMT_LEGACY) return blsgpu_serialize(pkg, e->h, 1, BLSGPU_FMT_RAW_PROJ, fmt_out, out, nullptr);
+  // Z = 1: the affine record is the first two coordinates
+  HIPCK(hipMemcpy(out, e->h, point_bytes(pkg, fmt_out), is_device_ptr(out) ? hipMemcpyHostToDevice : hipMemcpyHostToHost));
+  return 0;
+}
+API_CATCH
+
+/* BlsElGamal::verify_proof (reference src/traits/elgamal.rs:177-226; ElGamalProof::verify, src/elgamal_proof.rs:74-84) for n
+ * independent proofs.  Launch sequence: k_decompress per point array (wire formats only), k_elgamal_fixed (the small multiples of
+ * G and H, once), k_elgamal_prep (checks, four points affine and compressed per proof), k_elgamal_ladder (2 n lanes: r1 and r2,
+ * one joint windowed ladder each), k_elgamal_transcript (Merlin from the shared prefix state, the 512-bit reduction, the verdict). */
+int blsgpu_elgamal_proof_verify_batch(int sig_group, const void* pks, size_t n_pks, const void* generators, const void* c1s, const void* c2s,
+                                      const uint8_t* message_proofs, const uint8_t* blinder_proofs, const uint8_t* challenges, size_t n, int fmt,
+                                      int32_t* status) try {
+  if (!initialised()) return NOT_INIT();
+  if (sig_group != 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "sig_group must be 1 (Bls12381G1Impl) or 2 (Bls12381G2Impl)");
+  if (fmt < BLSGPU_FMT_RAW_PROJ || fmt > BLSGPU_FMT_LEGACY) return fail(BLSGPU_E_ARG, "unknown point format");
+  if (n == 0) return 0;
+  if (n_pks != n && n_pks != 1) return fail(BLSGPU_E_ARG, "n_pks must be n (a key per proof) or 1 (one recipient)");
+  if (n >= ((size_t)1 << 31)) return fail(BLSGPU_E_ARG, "too many proofs in one call");
+  if (!pks || !c1s || !c2s || !message_proofs || !blinder_proofs || !challenges || !status) return fail(BLSGPU_E_ARG, "null argument");
+  const ElGamalConsts* e;
+  int rc = elgamal_consts(sig_group, &e);
+  if (rc) return rc;
+  CTX_ACQUIRE(c);
+  const int pkg = key_group(sig_group);
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  const size_t psz = point_bytes(pkg, fmt), osz = point_bytes(pkg, BLSGPU_FMT_RAW_PROJ), K = point_bytes(pkg, BLSGPU_FMT_COMPRESSED);
+  const size_t n_gens = generators ? n : 0, fixed_bytes = 2 * ELGAMAL_TAB * 2 * 48 * (size_t)pkg;
+  if ((rc = arena_reserve(c, pad256(psz * n_pks) + pad256(psz * n_gens) + 2 * pad256(psz * n) + 3 * pad256(32 * n) + pad256(osz) + pad256(fixed_bytes) +
+                                 pad256(4 * osz * n) + pad256(4 * K * n) + pad256(2 * osz * n) + 2 * pad256(4 * n) + 256 +
+                                 (wire ? pad256(osz * n_pks) + pad256(osz * n_gens) + 2 * pad256(osz * n) : 0) + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_pks, *d_gens = nullptr, *d_c1, *d_c2, *d_mp, *d_bp, *d_ch;
+  if ((rc = stage_in(c, pks, psz * n_pks, &d_pks))) return rc;
+  if (generators && (rc = stage_in(c, generators, psz * n, &d_gens))) return rc;
+  if ((rc = stage_in(c, c1s, psz * n, &d_c1))) return rc;
+  if ((rc = stage_in(c, c2s, psz * n, &d_c2))) return rc;
+  if ((rc = stage_in(c, message_proofs, 32 * n, &d_mp))) return rc;
+  if ((rc = stage_in(c, blinder_proofs, 32 * n, &d_bp))) return rc;
+  if ((rc = stage_in(c, challenges, 32 * n, &d_ch))) return rc;
+  Carver mem{c};
+  uint8_t* d_h = mem.take<uint8_t>(osz);
+  uint32_t* d_fixed = mem.take<uint32_t>(fixed_bytes);
+  uint8_t* d_aff = mem.take<uint8_t>(4 * osz * n);
+  uint8_t* d_comp = mem.take<uint8_t>(4 * K * n);
+  uint8_t* d_rj = mem.take<uint8_t>(2 * osz * n);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  int32_t *d_dec = nullptr, *d_dec_pk = nullptr;
+  int pfmt = fmt;
+  if (wire) {      // wire bytes -> RAW_PROJ with the checks of from_compressed; the first failure of a proof's points is its verdict
+    d_dec = mem.take<int32_t>(4 * n);
+    if (n_pks == 1) d_dec_pk = mem.take<int32_t>(4);
+    uint8_t* p_pk = mem.take<uint8_t>(osz * n_pks);
+    uint8_t* p_gen = generators ? mem.take<uint8_t>(osz * n) : nullptr;
+    uint8_t* p_c1 = mem.take<uint8_t>(osz * n);
+    uint8_t* p_c2 = mem.take<uint8_t>(osz * n);
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    const int legacy = fmt == BLSGPU_FMT_LEGACY;
+    HIPCK(hipMemsetAsync(d_dec, 0, 4 * n, c->stream));
+    if (d_dec_pk) HIPCK(hipMemsetAsync(d_dec_pk, 0, 4, c->stream));
+    with_group(pkg, [&](auto G) {
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n_pks)), dim3(BLS_BLOCK), n_pks, (const uint8_t*)d_pks, legacy, p_pk, d_dec_pk ? d_dec_pk : d_dec, 1);
+      if (p_gen) KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_gens, legacy, p_gen, d_dec, 1);
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_c1, legacy, p_c1, d_dec, 1);
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_c2, legacy, p_c2, d_dec, 1);
+    });
+    d_pks = p_pk;
+    d_gens = p_gen;
+    d_c1 = p_c1;
+    d_c2 = p_c2;
+    pfmt = BLSGPU_FMT_RAW_PROJ;
+  }
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if ((rc = h2d_small(c, d_h, e->h, osz))) return rc;
+  const strobe128 prefix = e->prefix;
+  with_group(pkg, [&](auto G) {
+    KL(KID_ELGAMAL_PREP, k_elgamal_fixed<G()>, dim3(1), dim3(BLS_BLOCK), (const uint8_t*)d_h, d_fixed);
+    KL(KID_ELGAMAL_PREP, k_elgamal_prep<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, n_pks, (const uint8_t*)d_gens, (const uint8_t*)d_h,
+       (const uint8_t*)d_c1, (const uint8_t*)d_c2, pfmt, (const uint8_t*)d_mp, (const uint8_t*)d_bp, (const uint8_t*)d_ch, (const int32_t*)d_dec,
+       (const int32_t*)d_dec_pk, d_aff, d_comp, d_status);
+    KL(KID_ELGAMAL_LADDER, k_elgamal_ladder<G()>, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, generators ? 1 : 0, (const uint8_t*)d_aff, (const uint32_t*)d_fixed,
+       (const uint8_t*)d_mp, (const uint8_t*)d_bp, (const uint8_t*)d_ch, (const int32_t*)d_status, d_rj);
+    KL(KID_ELGAMAL_TRANSCRIPT, k_elgamal_transcript<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, prefix, (const uint8_t*)d_comp, (const uint8_t*)d_rj,
+       (const uint8_t*)d_ch, d_status);
+  });
+  HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, d_status, n);
+}
+API_CATCH
+
+/* ElGamalDecryptionKey::from_shares + decrypt (reference src/elgamal_decryption_share.rs:76-90) for n_ct ciphertexts: the key of
+ * set s by the stages of blsgpu_combine_shares in the key group, then out[s] = c2[s] - key; or the plain decrypt when ids and
+ * share_offsets are NULL and `shares` holds one ready key per ciphertext. */
+int blsgpu_elgamal_open_batch(int sig_group, const void* c2s, const uint8_t* ids, const void* shares, const uint64_t* share_offsets, size_t n_ct, int fmt,
+                              void* out, int32_t* status) try {
+  int rc = check_common(sig_group, 0, fmt);
+  if (rc) return rc;
+  if ((ids == nullptr) != (share_offsets == nullptr)) return fail(BLSGPU_E_ARG, "ids and share_offsets are given together (shares) or both NULL (keys)");
+  const bool keys = share_offsets == nullptr;
+  CTX_ACQUIRE(c);
+  std::vector<uint64_t> soffs;
+  if (keys) {
+    soffs.resize(n_ct + 1);
+    for (size_t s = 0; s <= n_ct; s++) soffs[s] = s;
+  } else if ((rc = read_offsets(share_offsets, n_ct, "share_offsets", soffs))) {
+    return rc;
+  }
+  const size_t n = (size_t)soffs[n_ct];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
+  if (n_ct == 0) return 0;
+  if (!c2s || !out || !status || (n && !shares)) return fail(BLSGPU_E_ARG, "null argument");
+  const int pkg = key_group(sig_group);
+  const size_t psz = point_bytes(pkg, fmt), osz = point_bytes(pkg, BLSGPU_FMT_RAW_PROJ);
+  combine_plan pl;
+  if (!keys) pl = combine_make_plan(soffs, n_ct, pkg);
+  if ((rc = arena_reserve(c, pad256(psz * n_ct) + pad256(psz * n) + pad256(32 * n) + pad256(8 * (n_ct + 1)) + 2 * pad256(osz * n_ct) + 2 * pad256(4 * n_ct) +
+                                 pl.ws_bytes + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_c2, *d_sh, *d_ids = nullptr;
+  const uint64_t* d_soffs = nullptr;
+  if ((rc = stage_in(c, c2s, psz * n_ct, &d_c2))) return rc;
+  if ((rc = stage_in(c, shares, psz * n, &d_sh))) return rc;
+  if (!keys && (rc = stage_in(c, ids, 32 * n, &d_ids))) return rc;
+  if (!keys && (rc = upload_offsets(c, soffs, &d_soffs))) return rc;
+  Carver mem{c};
+  uint8_t* d_out = mem.stage_out<uint8_t>(out, osz * n_ct);
+  int32_t* d_status = mem.take<int32_t>(4 * n_ct);
+  uint8_t* d_key = nullptr;
+  int32_t* d_cst = nullptr;
+  if (!keys) {
+    d_key = mem.take<uint8_t>(osz * n_ct);
+    d_cst = mem.take<int32_t>(4 * n_ct);
+  }
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (!keys && (rc = run_combine_shares(c, pkg, pl, soffs, n_ct, (const uint8_t*)d_ids, (const uint8_t*)d_sh, nullptr, d_soffs, fmt, d_key, d_cst))) return rc;
+  with_group(pkg, [&](auto G) {
+    KL(KID_ELGAMAL_SUB, k_elgamal_sub<G()>, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_c2, fmt, keys ? (const uint8_t*)d_sh : (const uint8_t*)d_key,
+       keys ? fmt : BLSGPU_FMT_RAW_PROJ, (const int32_t*)d_cst, d_out, d_status);
+  });
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, osz * n_ct))) return rc;
   return status_out_and_sync(c, status, d_status, n_ct);
 }
 API_CATCH

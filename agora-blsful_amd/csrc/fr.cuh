@@ -14,6 +14,7 @@ struct fr {
 
 BLS_CONST uint32_t FR_MOD[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
 BLS_CONST uint32_t FR_R2[8] = {0xf3f29c6du, 0xc999e990u, 0x87925c23u, 0x2b6cedcbu, 0x7254398fu, 0x05d31496u, 0x9f59ff11u, 0x0748d9d9u};   // 2^512 mod r
+BLS_CONST uint32_t FR_R3[8] = {0x439b73afu, 0xc62c1807u, 0x8cf06990u, 0x1b3e0d18u, 0xc7b5f418u, 0x73d13c71u, 0xc8db33e9u, 0x6e2a5bb9u};   // 2^768 mod r
 BLS_CONST uint32_t FR_ONE_M[8] = {0xfffffffeu, 0x00000001u, 0x00034802u, 0x5884b7fau, 0xecbc4ff5u, 0x998c4fefu, 0xacc5056fu, 0x1824b159u}; // 2^256 mod r
 BLS_CONST uint32_t FR_RM2[8] = {0xffffffffu, 0xfffffffeu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u}; // r - 2
 #define FR_N0 0xffffffffu   // -r^-1 mod 2^32 (r = 1 mod 2^32)
@@ -93,6 +94,16 @@ BLS_FN void fr_sub(fr& o, const fr& a, const fr& b) {
   }
   for (int j = 0; j < 8; j++) o.w[j] = d[j];
 }
+BLS_FN void fr_add(fr& o, const fr& a, const fr& b) {
+  uint32_t s[8];
+  uint64_t c = 0;
+  for (int j = 0; j < 8; j++) {
+    const uint64_t t = (uint64_t)a.w[j] + b.w[j] + c;
+    s[j] = (uint32_t)t;
+    c = t >> 32;
+  }
+  fr_final_sub(o, s, (uint32_t)c);
+}
 BLS_FN void fr_one(fr& o) {
   for (int j = 0; j < 8; j++) o.w[j] = FR_ONE_M[j];
 }
@@ -104,6 +115,20 @@ BLS_FN void fr_to_mont(fr& o, const uint32_t v[8]) {
     r2.w[j] = FR_R2[j];
   }
   fr_mul(o, a, r2);
+}
+// a 512-bit little-endian value (sixteen words) -> Montgomery form of (v mod r): Scalar::from_bytes_wide.  With lo and hi the two
+// halves, v R = lo R + hi 2^256 R, and one Montgomery product each gives lo R^2 / R and hi R^3 / R.
+BLS_FN void fr_from_wide(fr& o, const uint32_t v[16]) {
+  fr lo, hi, r2, r3;
+  for (int j = 0; j < 8; j++) {
+    lo.w[j] = v[j];
+    hi.w[j] = v[8 + j];
+    r2.w[j] = FR_R2[j];
+    r3.w[j] = FR_R3[j];
+  }
+  fr_mul(lo, lo, r2);
+  fr_mul(hi, hi, r3);
+  fr_add(o, lo, hi);
 }
 // Montgomery form -> the canonical value in [0, r)
 BLS_FN void fr_from_mont(uint32_t v[8], const fr& a) {

@@ -70,6 +70,10 @@ extern "C" {
 /* the threshold signcryption calls only */
 #define BLSGPU_INVALID_DECRYPTION_SHARE 14 /* BlsError::InvalidDecryptionShare  sign_decryption_share.rs:45-62 */
 #define BLSGPU_BAD_FRAME 15          /* no BlsError: decrypt returns None (no length prefix, or a length beyond the frame) sign_crypt.rs:122-136 */
+/* blsgpu_elgamal_proof_verify_batch only: the three InvalidInputs of BlsElGamal::verify_proof, tested in this order */
+#define BLSGPU_ELGAMAL_IDENTITY 16   /* InvalidInputs("Parameters or ciphertext values are identity point")   elgamal.rs:187-192 */
+#define BLSGPU_ELGAMAL_ZERO_PROOF 17 /* InvalidInputs("Proof values are zero")                                elgamal.rs:193-195 */
+#define BLSGPU_CHALLENGE_MISMATCH 18 /* InvalidInputs("Challenge values do not match")                        elgamal.rs:219-222 */
 
 /* runtime failures (< 0): return codes.  One of them can also appear IN a status entry: BLSGPU_E_HIP when the device-side work of
  * that item failed (single-verdict checks run on workgroups that wait for each other with a bound; a wait that ran out is not a
@@ -437,6 +441,46 @@ int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* u
 int blsgpu_signcrypt_open_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs,
                                 const uint64_t* v_offsets, size_t n_ct, const uint8_t* ids, const void* shares,
                                 const uint64_t* share_offsets, int fmt, uint8_t* frames, uint64_t* pt_range, int32_t* status);
+
+/* ---- ElGamal over the public-key group (src/traits/elgamal.rs): the checks that need no secret key.  Points are in the KEY group
+ * of sig_group (G2 for Bls12381G1Impl = 1, G1 for Bls12381G2Impl = 2); scalars are 32 bytes little-endian.
+ *
+ * BlsElGamal::message_generator() (elgamal.rs:20-23): the hash-to-curve of the compressed generator of the key group under ENC_DST
+ * (src/impls/g1.rs:129, g2.rs:127; the tag names the other group than the one it hashes into, as in the reference).  Computed once
+ * per process and cached.  fmt_out: any of the four formats; out: one point, host or device memory. */
+int blsgpu_elgamal_message_generator(int sig_group, int fmt_out, void* out);
+
+/* Batched BlsElGamal::verify_proof (elgamal.rs:177-226) = ElGamalProof::verify (src/elgamal_proof.rs:74-84): n independent proofs.
+ * pks: n_pks points, n_pks == n (a key per proof) or 1 (every proof is to the same recipient); anything else is BLSGPU_E_ARG.
+ * generators: NULL (the message generator, what ElGamalProof::verify passes) or n points (the trait's Some(generator)).
+ * c1s, c2s: n points each.  message_proofs, blinder_proofs, challenges: n scalars each.  fmt: any of the four point formats, the
+ *     same for every point of the call.  Every pointer may be host or device memory.  n == 0 returns 0 and touches nothing.
+ * status[i], the first that applies:
+ *     BLSGPU_BAD_ENCODING        a point does not decode (wire formats; BLSGPU_LEGACY_FORMAT where the decoder says so), or a scalar
+ *                                is >= r: no reference value can hold it, deserialisation fails before verify_proof runs;
+ *     BLSGPU_ELGAMAL_IDENTITY    pk, generator, c1 or c2 is the identity;
+ *     BLSGPU_ELGAMAL_ZERO_PROOF  one of the three scalars is zero;
+ *     BLSGPU_CHALLENGE_MISMATCH  the challenge recomputed from r1 = (-c) c1 + bp G, r2 = (-c) c2 + mp H + bp pk differs;
+ *     BLSGPU_OK                  the proof verifies.
+ * Two assumptions of this library, neither pinned by a vector of the crates themselves: Merlin's STROBE runs
+ *     the permutation whenever an absorb or squeeze fills the 166-byte block (STROBE v1.0.2), and Scalar::from_bytes_wide reads its
+ *     64 bytes as one little-endian integer. */
+int blsgpu_elgamal_proof_verify_batch(int sig_group, const void* pks, size_t n_pks, const void* generators, const void* c1s,
+                                      const void* c2s, const uint8_t* message_proofs, const uint8_t* blinder_proofs,
+                                      const uint8_t* challenges, size_t n, int fmt, int32_t* status);
+
+/* Batched ElGamalDecryptionKey::from_shares + decrypt (src/elgamal_decryption_share.rs:76-90) for n_ct ciphertexts.
+ * c2s: the second component of every ciphertext.  ids / shares / share_offsets: the decryption shares of all ciphertexts, flat, as
+ *     in blsgpu_signcrypt_open_batch; the key of ciphertext s is what blsgpu_combine_shares gives for its set (the same stages).
+ * fmt: BLSGPU_FMT_RAW_PROJ or BLSGPU_FMT_RAW_AFFINE.  out: n_ct RAW_PROJ records, c2 - key; status: n_ct entries, the status of
+ *     blsgpu_combine_shares for the set (BLSGPU_BAD_ENCODING, BLSGPU_VSSS_ERROR or BLSGPU_OK).  out[s] is the identity (all-zero
+ *     bytes) when status[s] is not BLSGPU_OK.
+ * Keys in place of shares (ElGamalDecryptionKey::decrypt): ids == NULL and share_offsets == NULL means `shares` holds one ready key
+ *     per ciphertext; every status is BLSGPU_OK.
+ * Every pointer may be host or device memory; a device `out` stays there.  n_ct == 0 returns 0.
+ * The sum of ciphertexts (src/elgamal_ciphertext.rs:74-83) is blsgpu_sum_batch over the c1s and over the c2s. */
+int blsgpu_elgamal_open_batch(int sig_group, const void* c2s, const uint8_t* ids, const void* shares, const uint64_t* share_offsets,
+                              size_t n_ct, int fmt, void* out, int32_t* status);
 
 /* ---- batched aggregation: the objects the batched verifiers above consume, made for many sets in one call.
  *
