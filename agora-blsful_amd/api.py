@@ -47,6 +47,7 @@ EXPORTS = [
     'blsgpu_keyset_create', 'blsgpu_keyset_destroy', 'blsgpu_keyset_info', 'blsgpu_keyset_get', 'blsgpu_keyset_mul',
     'blsgpu_multi_verify_indexed_batch', 'blsgpu_verify_secure_indexed_batch', 'blsgpu_sum_indexed_batch', 'blsgpu_verify_indexed_batch',
     'blsgpu_elgamal_message_generator', 'blsgpu_elgamal_proof_verify_batch', 'blsgpu_elgamal_open_batch',
+    'blsgpu_verify_shared_batch', 'blsgpu_verify_shared_indexed_batch',
 ]
 
 
@@ -183,6 +184,8 @@ def load_library(path=None):
         lib.blsgpu_elgamal_message_generator.argtypes = [ci, ci, vp]
         lib.blsgpu_elgamal_proof_verify_batch.argtypes = [ci, vp, sz, vp, vp, vp, u8p, u8p, u8p, sz, ci, i32p]
         lib.blsgpu_elgamal_open_batch.argtypes = [ci, vp, u8p, vp, u64p, sz, ci, vp, i32p]
+        lib.blsgpu_verify_shared_batch.argtypes = [ci, ci, vp, vp, u64p, sz, u8p, u64p, ci, i32p]
+        lib.blsgpu_verify_shared_indexed_batch.argtypes = [ci, h, u32p, vp, u64p, sz, u8p, u64p, ci, i32p]
         _lib = lib
     return _lib
 
@@ -813,6 +816,43 @@ def verify_indexed_batch(keyset, scheme, idx, sigs, msgs, fmt=FMT_RAW_PROJ):
     return list(st)[:n]
 
 
+def verify_shared_batch(sig_group, scheme, groups, fmt=FMT_RAW_PROJ):
+    """Signature::verify for items that share messages (blsgpu_verify_shared_batch): `groups` is a list of (msg, pks, sigs), every
+    (pks[j], sigs[j]) verified under the group's msg, which is hashed once.  Returns one list of statuses per group -- what
+    verify_batch gives for the same items with the messages repeated."""
+    n_groups = len(groups)
+    ioffs = _count_offsets([g[1] for g in groups])
+    if any(len(g[1]) != len(g[2]) for g in groups):
+        raise ValueError('one signature per key')
+    moffs, mblob = _offsets([bytes(g[0]) for g in groups])
+    n = ioffs[n_groups]
+    pkb, sgb = b''.join(p for g in groups for p in g[1]), b''.join(s for g in groups for s in g[2])
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(init().blsgpu_verify_shared_batch(sig_group, scheme, _ptr(pkb), _ptr(sgb), ctypes.cast(ioffs, ctypes.c_void_p), n_groups, _ptr(mblob),
+                                             ctypes.cast(moffs, ctypes.c_void_p), fmt, ctypes.cast(st, ctypes.c_void_p)))
+    flat = list(st)[:n]
+    return [flat[ioffs[g]:ioffs[g + 1]] for g in range(n_groups)]
+
+
+def verify_shared_indexed_batch(keyset, scheme, groups, fmt=FMT_RAW_PROJ):
+    """verify_shared_batch with the keys named by position: `groups` is a list of (msg, idx, sigs), idx a list of positions in
+    `keyset`.  One list of statuses per group: E_ARG for a position outside the table, the creation status of an invalid entry,
+    else what verify_shared_batch gives for those keys."""
+    n_groups = len(groups)
+    ioffs = _count_offsets([g[1] for g in groups])
+    if any(len(g[1]) != len(g[2]) for g in groups):
+        raise ValueError('one signature per position')
+    moffs, mblob = _offsets([bytes(g[0]) for g in groups])
+    n = ioffs[n_groups]
+    idx = _u32([i for g in groups for i in g[1]])
+    sgb = b''.join(s for g in groups for s in g[2])
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(init().blsgpu_verify_shared_indexed_batch(scheme, keyset.handle, ctypes.cast(idx, ctypes.c_void_p), _ptr(sgb), ctypes.cast(ioffs, ctypes.c_void_p),
+                                                     n_groups, _ptr(mblob), ctypes.cast(moffs, ctypes.c_void_p), fmt, ctypes.cast(st, ctypes.c_void_p)))
+    flat = list(st)[:n]
+    return [flat[ioffs[g]:ioffs[g + 1]] for g in range(n_groups)]
+
+
 def combine_shares(group, sets, fmt=FMT_RAW_PROJ):
     """Threshold recovery of many independent sets in one call (blsgpu_combine_shares): `sets` is a list of lists of
     (identifier: int, raw point, scheme or None).  Scheme tags are checked only when every share of the call carries one
@@ -1194,6 +1234,23 @@ class TensorOps:
                                                     self._p(st)))
         return st[:n]
 
+    def verify_shared_batch(self, sg, scheme, pks, sigs, item_offs, n_groups, msgs, msg_offs, n):
+        """int32 statuses (on the device), one per item, of Signature::verify over n_groups groups that share a message each:
+        flat device-resident keys and signatures with int64 item_offs, the messages with int64 msg_offs (n_groups + 1 entries each)."""
+        self._sync()
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_verify_shared_batch(sg, scheme, self._p(pks), self._p(sigs), self._p(item_offs), n_groups, self._p(msgs), self._p(msg_offs),
+                                                   FMT_RAW_PROJ, self._p(st)))
+        return st[:n]
+
+    def verify_shared_indexed_batch(self, keyset, scheme, idx, sigs, item_offs, n_groups, msgs, msg_offs, n):
+        """the same with item i's key at position idx[i] of `keyset` (idx: an int32 tensor whose bits are the uint32 positions)."""
+        self._sync()
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_verify_shared_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(sigs), self._p(item_offs), n_groups, self._p(msgs),
+                                                           self._p(msg_offs), FMT_RAW_PROJ, self._p(st)))
+        return st[:n]
+
     def keyset_get(self, keyset, key_group, idx, n, fmt=FMT_RAW_PROJ):
         """(entries as one uint8 tensor, int32 creation statuses), both on the device."""
         self._sync()
@@ -1321,6 +1378,31 @@ def verify_secure_many(items, mode=MODERN):
         sts = verify_secure_batch(sg, scheme, [([p.raw for p in items[i][1]], items[i][0].raw, bytes(items[i][2])) for i in idx], mode)
         for i, st in zip(idx, sts):
             out[i] = error_from_status(st)
+    return out
+
+
+def verify_shared_many(groups):
+    """Signature.verify for many (PublicKey, Signature) items that share messages: `groups` is a list of
+    (message, [(PublicKey, Signature), ...]) over one impl -- the shares of a signing session against the members' key shares, say.
+    Every message is hashed once (blsgpu_verify_shared_batch, at most one call per scheme).  Returns one BlsError or None per
+    item, in input order (group after group)."""
+    flat = [(g, pk, sig) for g, (_, items) in enumerate(groups) for pk, sig in items]
+    if not flat:
+        return []
+    sg = flat[0][2].impl.sig_group
+    if any(pk.impl.sig_group != sg or sig.impl.sig_group != sg for _, pk, sig in flat):
+        raise ValueError('verify_shared_many: every item must use the same impl')
+    out = [None] * len(flat)
+    for scheme in sorted({sig.scheme for _, _, sig in flat}):
+        pos = [[] for _ in groups]
+        for i, (g, _, sig) in enumerate(flat):
+            if sig.scheme == scheme:
+                pos[g].append(i)
+        sts = verify_shared_batch(sg, scheme, [(bytes(groups[g][0]), [flat[i][1].raw for i in pos[g]], [flat[i][2].raw for i in pos[g]])
+                                               for g in range(len(groups))])
+        for g, ps in enumerate(pos):
+            for i, st in zip(ps, sts[g]):
+                out[i] = error_from_status(st)
     return out
 
 

@@ -24,6 +24,7 @@
 #include "keyset.cuh"
 #include "signcrypt.cuh"
 #include "elgamal.cuh"
+#include "verify_shared.cuh"
 #include "host_sha256.h"
 
 namespace {
@@ -48,6 +49,7 @@ enum {
   KID_SUM_SEG_ACCUM, KID_SUM_FOLD, KID_SUM_OUT,           // blsgpu_sum_batch
   KID_KEYSET_SEAL, KID_KEYSET_BUILD, KID_KEYSET_CHECK, KID_KEYSET_GATHER, KID_KEYSET_ACCUM, KID_KEYSET_MUL, KID_KEYSET_FIN,   // registered key sets (keyset.cuh)
   KID_ELGAMAL_PREP, KID_ELGAMAL_LADDER, KID_ELGAMAL_TRANSCRIPT, KID_ELGAMAL_SUB,   // blsgpu_elgamal_proof_verify_batch / blsgpu_elgamal_open_batch
+  KID_GROUP_LINES, KID_PREPARE_SHARED,   // blsgpu_verify_shared_batch (verify_shared.cuh; k_group_affine and k_shared_expand count under k_prepare_shared, k_lines2s_shared under k_lines2s)
   KID_COUNT
 };
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
@@ -61,7 +63,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_secure_first", "k_secure_ladder", "k_secure_agg_fold", "k_secure_agg_out",
                                     "k_sum_accumulate_seg", "k_sum_fold", "k_sum_out",
                                     "k_keyset_seal", "k_keyset_build", "k_keyset_check", "k_keyset_gather", "k_keyset_accumulate_seg", "k_keyset_mul", "k_keyset_fin",
-                                    "k_elgamal_prep", "k_elgamal_ladder", "k_elgamal_transcript", "k_elgamal_sub"};
+                                    "k_elgamal_prep", "k_elgamal_ladder", "k_elgamal_transcript", "k_elgamal_sub",
+                                    "k_group_lines", "k_prepare_shared"};
 
 struct Ctx {
   int dev = -1;
@@ -164,6 +167,11 @@ int fail(int code, const std::string& msg) {
 // BLSGPU_STRICT_ENV=1: blsgpu_init refuses to start when the environment holds a BLSGPU_ variable this table does not know, or an
 // A/B variable without the gate (a typo or a leftover must not go unnoticed in production).
 extern "C" char** environ;
+// blsgpu_verify_shared_batch, BLSGPU_SHARED_LINES_MIN unset: the per-group line tables are taken from this many items per group on
+// average in a batch of at least this many items ("Shared-message verify": tools/bench_verify_shared.py -- a
+// group's walk is one serial pass however few groups there are, so it pays where the pass it saves runs more than once)
+#define SHARED_LINES_AUTO_MIN 4
+#define SHARED_LINES_AUTO_ITEMS 98304
 struct Knobs {
   long coop_max = 4096, wide_max = 512, shard_min = 8192, contexts = 2, fake_devices = 0, acc_lanes = 57344;
   long msm_c = 0, msm_ch = 0, msm2_c = 0, msm2_ch = 0, msm2_q = 0;          // 0: the library's own choice
@@ -177,6 +185,7 @@ struct Knobs {
   long multi_strip = 0;        // blsgpu_multi_verify_batch: keys per strip of the segmented key sum (0: one strip per lane of a single sum, at least 4)
   long keyset_table_mb = 4096; // blsgpu_keyset_create: fixed-base tables above this many MiB are not built (the set works without them)
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
+  long shared_lines_min = -1; // blsgpu_verify_shared_batch, Bls12381G2Impl: per-group line tables from this many items per group on average (0: never; unset: SHARED_LINES_AUTO_*)
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
        tree_local = 0, lines4_max = -1, tree_engine_from = 0, agg_lanes = 0, msm_v1 = 0, msm_naive = 0, wide_test_block = 64;
@@ -198,6 +207,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_AGG_BATCH_MAX", &Knobs::agg_batch_max, 1, 1L << 32, false},
     {"BLSGPU_MULTI_STRIP", &Knobs::multi_strip, 0, 1L << 32, false},
     {"BLSGPU_KEYSET_TABLE_MB", &Knobs::keyset_table_mb, 0, 1L << 20, false},
+    {"BLSGPU_SHARED_LINES_MIN", &Knobs::shared_lines_min, 0, 1L << 32, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -734,7 +744,11 @@ void launch_finalexp_chunk(Ctx* c, size_t n, size_t first, size_t cnt, const uin
 
 // the two-pair pairing check of every item whose status is still BLS_OK: status <- OK / INVALID_SIGNATURE.
 // fixed_g2: the second pair's G2 member is a constant with precomputed lines: 1 = -g2, 2 = -[c] g2 (csrc/g2neg_lines.cuh)
-int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2) {
+// sh_table / sh_group (fixed_g2 = 0, shared-message verify): on the lane-split path pair 1's G2 member is the point of item i's group
+// sh_group[i], its normalised rows in sh_table (verify_shared.cuh; the records carry the signature's pair first) -- one line
+// launch per chunk (k_lines2s_shared) instead of two.  Every other path takes the records as two general pairs.
+int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2, const uint32_t* sh_table = nullptr,
+                 const uint32_t* sh_group = nullptr) {
   if (n <= wide_max_items() && n <= coop_max_items()) {
     // single verifications and the one-verdict tails on the row-wide engine (csrc/wide_engine.cuh): one 256-thread workgroup
     // per item runs line coefficients, Miller loop, final exponentiation and verdict as one table program.
@@ -759,7 +773,7 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
     const bool finalexp_seg = knobs().finalexp_seg != 0;
     const bool finalexp_v1 = knobs().finalexp_v1 != 0;   // A/B: the one-kernel final exponentiation of rounds 1 and 2
     const size_t chunk = n < miller_chunk_items() ? n : miller_chunk_items();
-    const size_t words_per_lane = (size_t)MILLER_ENTRIES * (LINE5_WORDS + (fixed_g2 ? 0 : LINE3_WORDS_H));   // two general pairs: pair 0's plain lines too
+    const size_t words_per_lane = (size_t)MILLER_ENTRIES * (LINE5_WORDS + (fixed_g2 || sh_table ? 0 : LINE3_WORDS_H));   // two general pairs: pair 0's plain lines too
     if (chunk && lines_reserve(c, words_per_lane * 4 * row_stride(lanes_for(chunk))) == 0) {
       for (size_t first = 0; first < n; first += chunk) {
         const size_t cnt = n - first < chunk ? n - first : chunk;
@@ -768,6 +782,8 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
         const dim3 grid((unsigned)(nlanes / BLS_BLOCK));
         if (fixed_g2) {
           KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, fixed_g2, 0);
+        } else if (sh_table) {
+          KL(KID_LINES, k_lines2s_shared, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, sh_table, sh_group);
         } else {
           KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, 0, 1);
           KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, 0, 2);
@@ -3033,7 +3049,15 @@ API_CATCH
 
 // H(msg_i) into `group` for n messages on the device (RAW_PROJ out, cofactor-cleared), stream-ordered: the launch plan of
 // blsgpu_hash_to_g1 / blsgpu_hash_to_g2.  May take 768 n bytes from the arena (129 .. BLSGPU_WIDE_MAX messages into G2).
-static int run_hash_group(Ctx* c, int group, size_t n, const uint8_t* d_msgs, const uint64_t* d_offs, const dst_arg& d, uint8_t* d_out) {
+// uncleared (group 1 only): the points stay in E1(Fp) before the cofactor clearing, what a Bls12381G1Impl verification pairs with
+// -[c] g2 -- one wave per message up to 1,024 messages, two lanes per message beyond (the measured split of run_verify_items)
+static int run_hash_group(Ctx* c, int group, size_t n, const uint8_t* d_msgs, const uint64_t* d_offs, const dst_arg& d, uint8_t* d_out, bool uncleared = false) {
+  if (uncleared && group == 1) {
+    if (n <= 1024 && wide_max_items() > 0) KL(KID_HASH, k_hash_to_g1_wide, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_msgs, d_offs, 2, d, d_out, (uint32_t*)nullptr);
+    else KL(KID_HASH, k_hash_to_g1, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, 1 | 2);
+    HIPCK(hipGetLastError());
+    return 0;
+  }
   // two lanes per message: always for G2; for G1 up to the cooperative threshold (a full hash-only batch is faster with one lane per message)
   const int two = (group == 2 || n <= coop_max_items()) ? 1 : 0;
   if (group == 1 && n <= wide_max_items())   // a few messages: one wave each in the row-wide field type (0.98 ms against 1.6 ms of latency)
@@ -5274,6 +5298,208 @@ int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx
   if (rc) return rc;
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, d_status, n);
+}
+API_CATCH
+
+// ---- shared-message verify (verify_shared.cuh): Signature::verify for items that come in groups under one message each
+// What a call needs beyond its inputs, statuses and pair / Fp12 workspaces, decided from its shape alone (never from a result).
+struct shared_plan {
+  bool aug = false;        // MessageAugmentation: nothing to share, the messages are copied out per item for run_verify_items
+  bool table = false;      // Bls12381G2Impl on the lane-split path: one line table per group (k_group_lines, k_lines2s_shared)
+  size_t table_bytes = 0, x_total = 0, ws_bytes = 0;
+  std::vector<uint64_t> x_offs;   // aug: item j's message at [x_offs[j], x_offs[j + 1]) of the per-item buffer
+};
+static void shared_make_plan(shared_plan& p, int sg, int scheme, size_t n, size_t n_groups, const std::vector<uint64_t>& ioffs,
+                             const std::vector<uint64_t>& moffs) {
+  p.aug = scheme == BLSGPU_SCHEME_AUG;
+  if (p.aug) {
+    p.x_offs.resize(n + 1);
+    uint64_t t = 0;
+    for (size_t g = 0; g < n_groups; g++)
+      for (uint64_t j = ioffs[g]; j < ioffs[g + 1]; j++) {
+        p.x_offs[j] = t;
+        t += moffs[g + 1] - moffs[g];
+      }
+    p.x_offs[n] = t;
+    p.x_total = (size_t)t;
+    p.ws_bytes = pad256(8 * (n + 1)) + pad256(p.x_total);
+    return;
+  }
+  const size_t hb = point_bytes(sg, BLSGPU_FMT_RAW_PROJ) * n_groups, ab = point_bytes(sg, BLSGPU_FMT_RAW_AFFINE) * n_groups;
+  p.ws_bytes = pad256(hb) + pad256(ab) + pad256(768 * n_groups);
+  // The table form: the lane-split path with its two-kernel Miller loop, tables that a 32-bit byte offset reaches, and groups
+  // large enough on average that a group's walk of H(m) is shared by enough items (BLSGPU_SHARED_LINES_MIN; 0: never; unset: the
+  // measured rule above the knob table).
+  p.table_bytes = n_groups * (size_t)SHARED_TABLE_WORDS * 4;
+  const long knob = knobs().shared_lines_min;
+  const bool wanted = knob < 0 ? n >= SHARED_LINES_AUTO_ITEMS && n / n_groups >= SHARED_LINES_AUTO_MIN : knob > 0 && n / n_groups >= (size_t)knob;
+  p.table = sg == 2 && wanted && n > coop_max_items() && miller_chunk_items() != 0 && p.table_bytes <= 0xffffffffull;
+  if (p.table) p.ws_bytes += 2 * pad256(p.table_bytes) + pad256(4 * (n_groups + 1)) + pad256(4 * n);
+}
+// statuses of the n items into d_status (device).  Launch sequence, Basic and ProofOfPossession: the groups' hashes
+// (run_hash_group; Bls12381G1Impl: uncleared), k_group_affine, [k_group_lines and one word back to the host], k_prepare_shared,
+// run_pairing2 (fixed_g2 = 2 for Bls12381G1Impl; two general pairs, or the groups' tables, for Bls12381G2Impl).
+static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan& p, size_t n, size_t n_groups, const uint8_t* d_pks, const uint8_t* d_sigs,
+                                   int fmt, const uint64_t* d_ioffs, const uint8_t* d_msgs, const uint64_t* d_moffs, uint32_t* d_pairs, uint32_t* d_f,
+                                   int32_t* d_status) {
+  int rc;
+  const dst_arg dst = scheme_dst(sg, scheme);
+  if (p.aug) {
+    const uint64_t* d_xoffs;
+    if ((rc = upload_offsets(c, p.x_offs, &d_xoffs))) return rc;
+    uint8_t* d_xmsgs = (uint8_t*)arena_take(c, p.x_total ? p.x_total : 1);
+    if (!d_xmsgs) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    if (p.x_total)
+      KL(KID_PREPARE_SHARED, k_shared_expand, dim3(blocks_for(p.x_total)), dim3(BLS_BLOCK), p.x_total, d_xoffs, n, d_ioffs, n_groups, d_moffs, d_msgs, d_xmsgs);
+    rc = run_verify_items(c, sg, 1, d_pks, d_sigs, fmt, d_xmsgs, d_xoffs, 0, dst, n, d_pairs, d_f, d_status);
+    if (rc) (void)hipStreamSynchronize(c->stream);      // the upload above reads p.x_offs
+    return rc;
+  }
+  Carver mem{c};
+  uint8_t* d_hash = mem.take<uint8_t>(point_bytes(sg, BLSGPU_FMT_RAW_PROJ) * n_groups);
+  uint8_t* d_aff = mem.take<uint8_t>(point_bytes(sg, BLSGPU_FMT_RAW_AFFINE) * n_groups);
+  uint32_t *d_table = nullptr, *d_scratch = nullptr, *d_group = nullptr;
+  int32_t* d_flags = nullptr;
+  if (p.table) {
+    d_table = mem.take<uint32_t>(p.table_bytes);
+    d_scratch = mem.take<uint32_t>(p.table_bytes);
+    d_flags = mem.take<int32_t>(4 * (n_groups + 1));
+    d_group = mem.take<uint32_t>(4 * n);
+  }
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if ((rc = run_hash_group(c, sg, n_groups, d_msgs, d_moffs, dst, d_hash, sg == 1))) return rc;
+  with_group(sg, [&](auto G) {
+    KL(KID_PREPARE_SHARED, k_group_affine<G()>, dim3(blocks_for(n_groups)), dim3(BLS_BLOCK), n_groups, (const uint8_t*)d_hash, d_aff);
+  });
+  bool table = p.table;
+  if (table) {
+    // a group whose point is the identity or whose walk meets h = 0 has no usable rows (never seen for a hash output): the
+    // call then takes the general form for every item -- one word read back decides it before the records are written
+    int32_t* h_any = (int32_t*)hsmall_take(c, 4);
+    if (!h_any) return fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted");
+    HIPCK(hipMemsetAsync(d_flags + n_groups, 0, 4, c->stream));
+    KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(2 * n_groups)), dim3(BLS_BLOCK), n_groups, (const uint8_t*)d_aff, d_table, d_scratch, d_flags);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(h_any, d_flags + n_groups, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    table = *h_any == 0;
+  }
+  with_group(sg, [&](auto G) {
+    KL(KID_PREPARE_SHARED, k_prepare_shared<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, d_pks, d_sigs, fmt, (const uint8_t*)d_aff, d_pairs,
+       d_status, table ? 1 : 0, table ? d_group : (uint32_t*)nullptr);
+  });
+  HIPCK(hipGetLastError());
+  return run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, table ? d_table : nullptr, table ? d_group : nullptr);
+}
+// the offsets of a shared-message call, read and checked; n = the item count
+static int shared_read_offsets(const uint64_t* item_offsets, const uint64_t* msg_offsets, size_t n_groups, std::vector<uint64_t>& ioffs,
+                               std::vector<uint64_t>& moffs, size_t* n) {
+  int rc;
+  if ((rc = read_offsets(item_offsets, n_groups, "item_offsets", ioffs))) return rc;
+  if ((rc = read_offsets(msg_offsets, n_groups, "msg_offsets", moffs))) return rc;
+  if (ioffs[n_groups] >= ((uint64_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more items in one call");
+  *n = (size_t)ioffs[n_groups];
+  return 0;
+}
+
+/* Signature::verify (reference src/signature.rs:130-138) for the items of n_groups groups, every item of a group under the
+ * group's message: status[i] is what blsgpu_verify_batch gives for item i with that message. */
+int blsgpu_verify_shared_batch(int sig_group, int scheme, const void* pks, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
+                               const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc) return rc;
+  if (n_groups == 0) return 0;
+  if (!item_offsets || !msg_offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  CTX_ACQUIRE(c);
+  std::vector<uint64_t> ioffs, moffs;
+  size_t n = 0;
+  if ((rc = shared_read_offsets(item_offsets, msg_offsets, n_groups, ioffs, moffs, &n))) return rc;
+  if (n == 0) return 0;
+  const size_t total = (size_t)moffs[n_groups];
+  if (!pks || !sigs || !status || (total && !msgs)) return fail(BLSGPU_E_ARG, "null argument");
+  shared_plan plan;
+  shared_make_plan(plan, sig_group, scheme, n, n_groups, ioffs, moffs);
+  const size_t pkb = pk_size(sig_group, fmt) * n, sgb = sig_size(sig_group, fmt) * n;
+  if ((rc = arena_reserve(c, pad256(pkb) + pad256(sgb) + pad256(total) + 2 * pad256(8 * (n_groups + 1)) + pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) +
+                                 plan.ws_bytes + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_pks, *d_sigs, *d_msgs;
+  const uint64_t *d_ioffs, *d_moffs;
+  if ((rc = stage_in(c, pks, pkb, &d_pks))) return rc;
+  if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
+  if ((rc = upload_offsets(c, ioffs, &d_ioffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  rc = run_verify_shared_items(c, sig_group, scheme, plan, n, n_groups, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, fmt, d_ioffs, (const uint8_t*)d_msgs, d_moffs,
+                               d_pairs, d_f, d_status);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);      // the uploads read ioffs / moffs
+    return rc;
+  }
+  return status_out_and_sync(c, status, d_status, n);
+}
+API_CATCH
+
+/* The same over a registered key set: item i's key is the entry at position idx[i].  k_keyset_check (every item its own set),
+ * k_keyset_gather, the shared path above, k_keyset_fin -- the sequence and the status precedence of blsgpu_verify_indexed_batch. */
+int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
+                                       const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
+  KeySet k;
+  int rc = keyset_find(keyset, k);
+  if (rc) return rc;
+  const int sig_group = k.sig_group;
+  if ((rc = check_common(sig_group, scheme, fmt))) return rc;
+  if (n_groups == 0) return 0;
+  if (!item_offsets || !msg_offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  CTX_ACQUIRE_ON(c, k.devidx);
+  std::vector<uint64_t> ioffs, moffs;
+  size_t n = 0;
+  if ((rc = shared_read_offsets(item_offsets, msg_offsets, n_groups, ioffs, moffs, &n))) return rc;
+  if (n == 0) return 0;
+  const size_t total = (size_t)moffs[n_groups];
+  if (!idx || !sigs || !status || (total && !msgs)) return fail(BLSGPU_E_ARG, "null argument");
+  shared_plan plan;
+  shared_make_plan(plan, sig_group, scheme, n, n_groups, ioffs, moffs);
+  const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt), sgb = sig_size(sig_group, fmt) * n;
+  if ((rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(total) + 2 * pad256(8 * (n_groups + 1)) +
+                                 pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + plan.ws_bytes + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_idx, *d_sigs, *d_msgs;
+  const uint64_t *d_ioffs, *d_moffs;
+  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
+  if ((rc = upload_offsets(c, ioffs, &d_ioffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
+  Carver mem{c};
+  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
+  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n);
+  uint8_t* d_aff = mem.take<uint8_t>(psz * n);
+  uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(ksz * n);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  auto drain = [&](int r) {
+    (void)hipStreamSynchronize(c->stream);      // the uploads read ioffs / moffs
+    return r;
+  };
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre))) return drain(rc);
+  const size_t cnt_ = n;
+  KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
+  if (d_keys != d_aff)
+    with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
+  rc = run_verify_shared_items(c, sig_group, scheme, plan, n, n_groups, d_keys, (const uint8_t*)d_sigs, fmt, d_ioffs, (const uint8_t*)d_msgs, d_moffs, d_pairs, d_f,
+                               d_status);
+  if (rc) return drain(rc);
+  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
   return status_out_and_sync(c, status, d_status, n);
 }
 API_CATCH

@@ -238,6 +238,10 @@ __global__ void k_prepare(size_t n, const uint8_t* pks, const uint8_t* sigs, int
                           const uint64_t* offs, int single_msg, dst_arg dst, uint32_t* pairs, int32_t* status, int pre_status, int two_lanes);
 __global__ void k_miller2s(size_t n, const uint32_t* pairs, const int32_t* status, uint32_t* fws, int fixed_g2);
 __global__ void k_lines2s(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* status, uint32_t* lines, uint32_t* lines3, size_t lanes, int fixed_g2, int pass);
+// the table form of the shared-message path (verify_shared.cuh): pair 1's G2 member is item i's GROUP's point, its normalised rows at
+// table + (group_of[i] 68 + e) 4 FP_NL
+__global__ void k_lines2s_shared(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* status, uint32_t* lines, size_t lanes,
+                                 const uint32_t* table, const uint32_t* group_of);
 __global__ void k_millerf2s(size_t n, size_t first, size_t count, const int32_t* status, const uint32_t* lines, size_t lanes, uint32_t* fws);
 __global__ void k_finalexp2s(size_t n, size_t first, size_t count, const uint32_t* fws, uint32_t* vp, size_t lanes, int32_t* status);
 __global__ void k_finalexp_seg(int seg, size_t n, size_t first, size_t count, const uint32_t* fws, uint32_t* vp, size_t lanes, int32_t* status);
@@ -909,13 +913,16 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_f12_export(const uint32_t* fws, s
 // hash_to_point batches
 // two_lanes: two adjacent lanes per message run the two SSWU maps side by side (and, for G2, the cofactor clearing on the
 // lane-split tower), as k_prepare does: the latency mode for the single message of a verify_secure tail
+// two_lanes bit 1 (value 2): the point stays in E1(Fp), NOT cofactor-cleared (the shared-message verify pairs it with -[c] g2)
 __global__ void __launch_bounds__(BLS_BLOCK) k_hash_to_g1(size_t n, const uint8_t* msgs, const uint64_t* offs, dst_arg dst, uint8_t* out, int two_lanes) {
+  const bool no_clear = (two_lanes & 2) != 0;
+  two_lanes &= 1;
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = two_lanes ? gid >> 1 : gid;
   const int lane2 = two_lanes ? (int)(gid & 1) : -1;
   if (i >= n) return;
   g1_jac h;
-  hash_to_g1(h, nullptr, 0, msgs + offs[i], (uint32_t)(offs[i + 1] - offs[i]), dst.b, dst.len, lane2);
+  hash_to_g1(h, nullptr, 0, msgs + offs[i], (uint32_t)(offs[i + 1] - offs[i]), dst.b, dst.len, lane2, no_clear);
   if (lane2 <= 0) store_g1_pt(out, i, h);
 }
 // two_lanes bit 1 (value 2): stop before the cofactor clearing (k_g2_clear_wide does it on the row-wide engine)
@@ -1465,6 +1472,72 @@ k_lines2s(size_t n, size_t first, size_t count, const uint32_t* pairs, const int
       if (miller_entry_is_add(e)) lines_step_fn<1, SRC_LINES>(sh, pw, n, i, nullptr, lines, lines3, lanes, t, e);
       else lines_step_fn<0, SRC_LINES>(sh, pw, n, i, nullptr, lines, lines3, lanes, t, e);
     }
+  }
+}
+#endif
+
+#if defined(BLS_TU_LINES)
+// The table form with the row selected PER ITEM (blsgpu_verify_shared_batch, Bls12381G2Impl: verify_shared.cuh).  The items of a
+// group share pair 1's G2 member H(m_g), whose normalised rows k_group_lines left in `table` in the *_LINES_N layout, 68 rows of
+// 4 FP_NL words per group.  As in the constant-table form the launch walks pair 0's G2 member (here the signature: the record's
+// pair order is swapped, verify_shared.cuh prepare_shared_item) and merges every step's line with the row evaluated at pair 1's G1
+// member (the key) -- ONE pass, no lines3 workspace.  The table's base stays wave-uniform and the row is a 32-bit per-lane WORD
+// offset goff + e 4 FP_NL with goff = group 68 4 FP_NL (the host keeps the table below 2^32 bytes), so that every access keeps the
+// SGPR-base + VGPR-offset form explained above line5_st.  A step function of its own: lines_step_fn and the kernels that call it
+// stay what they are.
+template <int ADD>
+static __device__ __noinline__ void lines_step_group(lds_u32* sh, const uint32_t* pairs, size_t n, size_t i, const uint32_t* table, uint32_t goff,
+                                                     uint32_t* lines, size_t lanes, uint32_t t, int e) {
+  const miller_lds st = {sh, pairs, n, i};
+  hfp2 l0, l2, l3;
+  if (ADD) miller_add_step_at(st, l0, l2, l3);
+  else miller_dbl_step_at(st, l0, l2, l3);
+  line5_t<hfp2> L;
+  fp x1, y1;
+  hfp2 n0, n2, c;
+  {
+    gc_u32* tr = uni_global(table);
+    const uint32_t o = goff + uni_u32((uint32_t)e) * (4 * FP_NL) + (lane_hi() ? FP_NL : 0);
+#pragma unroll
+    for (int k = 0; k < FP_NL; k++) {
+      n0.v.l[k] = (int32_t)g_ld(tr, o + k);
+      c.v.l[k] = (int32_t)g_ld(tr, o + 2 * FP_NL + k);
+    }
+  }
+  ls_ld_coord(x1, sh, LS_P1, false);
+  fp2_mul_fp(n2, c, x1);
+  ls_ld_coord(y1, sh, LS_P1, true);
+  lines_merge_y(L, l0, l2, l3, n0, n2, y1);
+  line5_st(lines, lanes, t, e, L);
+}
+__global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES) __attribute__((disable_tail_calls))
+k_lines2s_shared(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* status, uint32_t* lines, size_t lanes, const uint32_t* table,
+                 const uint32_t* group_of) {
+  const uint32_t t = blockIdx.x * BLS_BLOCK + threadIdx.x;
+  const size_t j = t >> 1;
+  if (j >= count) return;
+  const size_t i = first + j;                          // the item's index in the BATCH: group_of and the pairs are indexed by it
+  if (status[i] != BLS_OK) return;
+  __shared__ uint32_t lsh[LS_WORDS * BLS_BLOCK];
+  lds_u32* sh = lds_column(lsh);
+  {
+    hfp2 q;
+    fp p;
+    ws_ld_hfp2(q, pairs, n, i, W2);
+    ls_st(sh, LS_TX, q.v);
+    ws_ld_hfp2(q, pairs, n, i, 2 * W2);
+    ls_st(sh, LS_TY, q.v);
+    fp2_one(q);
+    ls_st(sh, LS_TZ, q.v);
+    ws_ld_fp(p, pairs, n, i, lane_hi() ? W1 : 0);                   // pair 0's G1 point: x on the even lane, y on the odd lane
+    ls_st(sh, LS_P0, p);
+    ws_ld_fp(p, pairs, n, i, 3 * W2 + (lane_hi() ? W1 : 0));        // pair 1's G1 point, where the group's rows are evaluated
+    ls_st(sh, LS_P1, p);
+  }
+  const uint32_t goff = group_of[i] * (uint32_t)(MILLER_ENTRIES * 4 * FP_NL);
+  for (int e = 0; e < MILLER_ENTRIES; e++) {
+    if (miller_entry_is_add(e)) lines_step_group<1>(sh, pairs, n, i, table, goff, lines, lanes, t, e);
+    else lines_step_group<0>(sh, pairs, n, i, table, goff, lines, lanes, t, e);
   }
 }
 #endif

@@ -560,6 +560,32 @@ int blsgpu_sum_indexed_batch(uint64_t keyset, const uint32_t* idx, const uint64_
 int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint8_t* msgs,
                                 const uint64_t* msg_offsets, size_t n, int fmt, int32_t* status);
 
+/* ---- Shared-message verify: Signature::verify (src/signature.rs:130-138) for items that come in GROUPS under one message each --
+ * the signature shares of a signing session checked one by one against the members' key shares (PublicKeyShare::verify,
+ * src/public_key_share.rs:55-72), or unaggregated attestations: a handful of messages, many (key, signature) items, one verdict
+ * per item.
+ * Group g owns items item_offsets[g] .. item_offsets[g + 1] of pks / sigs, and message g = msgs[msg_offsets[g] .. msg_offsets[g + 1]).
+ *     Both offset arrays have n_groups + 1 entries, start at 0 and never decrease (anything else is BLSGPU_E_ARG, and no status
+ *     is written); they are read and checked on the host.  A group may be empty.  The item count must be below 2^32.
+ * fmt: RAW_PROJ or RAW_AFFINE.  status: one entry per ITEM, exactly what blsgpu_verify_batch returns for the item with its
+ *     group's message (signature identity, then key identity, then the pairing: src/traits/sig_core.rs:126-145).
+ * Basic and ProofOfPossession hash every message ONCE and make the point affine once per group; an item costs its identity checks,
+ *     one inversion and the two-pair pairing.  For Bls12381G2Impl on the lane-split path (more than BLSGPU_COOP_MAX items) with
+ *     at least BLSGPU_SHARED_LINES_MIN items per group on average (0: never; unset: 4, and only in batches of at least 98,304
+ *     items, where the form was measured to pay) and line tables (15,232 bytes per group) below 4 GiB, H(m)'s 68 Miller-loop
+ *     lines are derived once per group as well and an item walks one G2 point instead of two.  The knob changes the plan, never
+ *     a status.  Under MessageAugmentation every item hashes pk_i || m: nothing is
+ *     shared, the messages are copied out per item on the device and the items run as blsgpu_verify_batch runs them.
+ * Every pointer may be host or device memory; a device status stays on the device.  n_groups == 0 or no items returns 0.  The
+ *     call runs on one device. */
+int blsgpu_verify_shared_batch(int sig_group, int scheme, const void* pks, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
+                               const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status);
+/* The same with item i's key at position idx[i] of a registered key set; sig_group comes from the key set, fmt describes the
+ * signatures, and status[i] follows the precedence of the other indexed calls with every item its own set: BLSGPU_E_ARG for a
+ * position outside the table, then the entry's creation status, then what blsgpu_verify_shared_batch gives. */
+int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint64_t* item_offsets,
+                                       size_t n_groups, const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
