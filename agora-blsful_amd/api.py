@@ -40,7 +40,7 @@ EXPORTS = [
     'blsgpu_aggregate_partial', 'blsgpu_fp12_product_is_one', 'blsgpu_core_verify', 'blsgpu_deserialize', 'blsgpu_pop_verify_batch', 'blsgpu_aggregate_secure',
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
-    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
@@ -160,6 +160,9 @@ def load_library(path=None):
         lib.blsgpu_debug_wide_mul.argtypes = [u8p, u8p, sz, ci, u8p]
         lib.blsgpu_debug_wide_program.argtypes = [vp, sz, ci, u8p, u8p]
         lib.blsgpu_debug_finalexp_batch.argtypes = [vp, sz, ci, sz, i32p]
+        lib.blsgpu_debug_field_op_shape.argtypes = [ci] + [ctypes.POINTER(ctypes.c_int)] * 5
+        lib.blsgpu_debug_field_op.argtypes = [ci, i32p, sz, ci, i32p]
+        lib.blsgpu_debug_millerf.argtypes = [i32p, sz, i32p, i32p]
         lib.blsgpu_verify_batch_grouped.argtypes = [ci, ci, vp, vp, u8p, vp, sz, ci, ctypes.c_uint64, i32p]
         lib.blsgpu_signatures_from_tagged.argtypes = [ci, u8p, sz, u8p, vp, i32p]
         lib.blsgpu_signatures_to_tagged.argtypes = [ci, u8p, vp, sz, ci, u8p]
@@ -991,6 +994,75 @@ def debug_finalexp_batch(records, form, chunk=0, status=None):
     st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
     _check(lib.blsgpu_debug_finalexp_batch(_ptr(b''.join(records)), n, form, chunk, ctypes.cast(st, ctypes.c_void_p)))
     return list(st[:n])
+
+
+_field_op_table = None
+
+
+def field_op_table():
+    """{name: (id, lanes, n_in, n_out, n_par, chain)} of the operations of debug_field_op: the one table of csrc/debug_ops.h (read from
+    the source file; needs neither the library nor a device)"""
+    global _field_op_table
+    if _field_op_table is None:
+        import re
+        text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'debug_ops.h')).read()
+        _field_op_table = {m.group(1): tuple(int(x) for x in m.group(2).split(', '))
+                           for m in re.finditer(r'^\s*X\((\w+), (\d+, \d+, \d+, \d+, \d+, \d+)\)', text, re.M)}
+    return _field_op_table
+
+
+def field_ops():
+    """{name: id} of the operations of debug_field_op"""
+    return {name: row[0] for name, row in field_op_table().items()}
+
+
+def field_op_shape(op):
+    """(lanes, n_in, n_out, n_par, chain) of operation `op` (name or id), as the library's own table states it"""
+    lib = load_library()
+    vals = [ctypes.c_int() for _ in range(5)]
+    _check(lib.blsgpu_debug_field_op_shape(field_ops()[op] if isinstance(op, str) else op, *[ctypes.byref(v) for v in vals]))
+    return tuple(v.value for v in vals)
+
+
+def debug_field_op(op, records, reps=1):
+    """One field / tower operation of csrc/debug_ops.h on the device.  records: per item (limb vectors, parameters) -- n_in vectors of
+    fourteen signed limbs and n_par integers.  Returns per item the n_out output vectors (lists of fourteen signed integers)."""
+    lib = init()
+    _, n_in, n_out, n_par, _ = field_op_shape(op)
+    n = len(records)
+    flat = []
+    for vecs, pars in records:
+        assert len(vecs) == n_in and len(pars) == n_par and all(len(v) == 14 for v in vecs)
+        for v in vecs:
+            flat += v
+        flat += pars
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    out = (ctypes.c_int32 * max(14 * n_out * n, 1))()
+    _check(lib.blsgpu_debug_field_op(field_ops()[op] if isinstance(op, str) else op, ctypes.cast(arr, ctypes.c_void_p), n, reps, ctypes.cast(out, ctypes.c_void_p)))
+    o = list(out)
+    return [[o[14 * (n_out * i + k):14 * (n_out * i + k + 1)] for k in range(n_out)] for i in range(n)]
+
+
+def debug_millerf(tables, status=None):
+    """k_millerf2s on caller-supplied line tables.  tables: per item 68 entries of five Fp2 coefficients (c0, c2, c4, c3, c5), each a pair
+    of limb vectors.  Returns per item the twelve limb vectors of the result in tower order (zeros for an item whose status is not OK)."""
+    lib = init()
+    n = len(tables)
+    flat = []
+    for t in tables:
+        assert len(t) == 68
+        for entry in t:
+            assert len(entry) == 5
+            for c0, c1 in entry:
+                flat += c0
+                flat += c1
+    assert len(flat) == n * 68 * 5 * 2 * 14
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
+    out = (ctypes.c_int32 * max(168 * n, 1))()
+    _check(lib.blsgpu_debug_millerf(ctypes.cast(arr, ctypes.c_void_p), n, ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+    o = list(out)
+    return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n)]
 
 
 _wide_defs = None

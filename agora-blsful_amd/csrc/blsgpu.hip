@@ -25,6 +25,7 @@
 #include "signcrypt.cuh"
 #include "elgamal.cuh"
 #include "verify_shared.cuh"
+#include "debug_ops.h"
 #include "host_sha256.h"
 
 namespace {
@@ -52,6 +53,7 @@ enum {
   KID_GROUP_LINES, KID_PREPARE_SHARED,   // blsgpu_verify_shared_batch (verify_shared.cuh; k_group_affine and k_shared_expand count under k_prepare_shared, k_lines2s_shared under k_lines2s)
   KID_COUNT
 };
+#define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
 const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", "k_prepare_agg", "k_pairs_to_affine", "k_miller1s", "k_f12_fold",
                                     "k_finalexp_one", "k_hash_to_point", "k_accumulate", "k_point_fold", "k_compress", "k_sign", "k_f12_io", "k_msm_sort", "k_msm_bucket", "k_msm_chunk", "k_decompress", "k_pairing_coop", "k_key_sort", "k_sha256_coeff", "k_duplicate_rule", "k_first_identity", "k_msm_prep", "k_normalize", "k_msm_merge", "k_wide", "k_lines2s", "k_cyc_run4",
                                     "k_miller2s", "k_finalexps", "k_linesp", "k_linesp4", "k_line_quad", "k_f12_fold4", "k_f12_tree_seg", "k_f12_horner_wide", "k_millerfp", "k_pairing_post", "k_pairing_pre",
@@ -3450,6 +3452,106 @@ int blsgpu_debug_finalexp_batch(const void* f12s, size_t n, int form, size_t chu
   }
   HIPCK(hipGetLastError());
   if (d_status != status) return copy_out_and_sync(c, status, d_status, 4 * n);
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* Self-test hook of the field leaves and the lane-split tower, one operation at a time on caller-supplied limb vectors (fourteen
+ * signed 32-bit limbs per Fp, the internal form of fp.cuh): the operation table is csrc/debug_ops.h.  Host pointers only. */
+namespace {
+struct dbg_shape {
+  int op, lanes, n_in, n_out, n_par, chain;
+};
+const dbg_shape DBG_SHAPES[] = {
+#define X(name, id, lanes, nin, nout, npar, chain) {id, lanes, nin, nout, npar, chain},
+    BLS_DEBUG_OPS(X)
+#undef X
+};
+const dbg_shape* dbg_find(int op) {
+  for (const dbg_shape& s : DBG_SHAPES)
+    if (s.op == op) return &s;
+  return nullptr;
+}
+}  // namespace
+int blsgpu_debug_field_op_shape(int op, int* lanes, int* n_in, int* n_out, int* n_par, int* chain) {
+  const dbg_shape* s = dbg_find(op);
+  if (!s || !lanes || !n_in || !n_out || !n_par || !chain) return fail(BLSGPU_E_ARG, "unknown operation");
+  *lanes = s->lanes;
+  *n_in = s->n_in;
+  *n_out = s->n_out;
+  *n_par = s->n_par;
+  *chain = s->chain;
+  return 0;
+}
+int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t* out) try {
+  if (!initialised()) return NOT_INIT();
+  const dbg_shape* s = dbg_find(op);
+  if (!s) return fail(BLSGPU_E_ARG, "unknown operation");
+  if (n == 0) return 0;
+  if (!in || !out || reps < 1 || (reps > 1 && !s->chain) || n > ((size_t)1 << 20) || is_device_ptr(in) || is_device_ptr(out)) return fail(BLSGPU_E_ARG, "bad argument");
+  CTX_ACQUIRE(c);
+  const int rec_in = s->n_in * DBG_NL + s->n_par, rec_out = s->n_out * DBG_NL;
+  int rc = arena_reserve(c, pad256((size_t)4 * rec_in * n) + pad256((size_t)4 * rec_out * n) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void* d_in;
+  if ((rc = stage_in(c, in, (size_t)4 * rec_in * n, &d_in))) return rc;
+  int32_t* d_out = stage_out<int32_t>(c, out, (size_t)4 * rec_out * n);
+  if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  const dim3 grid(blocks_for((size_t)s->lanes * n)), block(BLS_BLOCK);
+#define DBG_LAUNCH(kern) KL(KID_DEBUG_OPS, kern, grid, block, op, n, reps, (const int32_t*)d_in, rec_in, d_out, rec_out)
+  if (s->lanes == 1) DBG_LAUNCH(k_dbg_fp1);
+  else if (op < DBG_F12_SH_SQR) DBG_LAUNCH(k_dbg_fp2s);
+  else if (op < DBG_CYC_C_SQR) DBG_LAUNCH(k_dbg_f12acc);
+  else if (op < DBG_F12_POW_X) DBG_LAUNCH(k_dbg_cyc);
+  else DBG_LAUNCH(k_dbg_f12misc);
+#undef DBG_LAUNCH
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, (size_t)4 * rec_out * n))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* Self-test hook of the accumulator's kernel: k_millerf2s, launched as run_pairing2 launches it, on a caller-supplied line table.
+ * lines: n x 68 entries x five Fp2 coefficients (c0, c2, c4, c3, c5 of tower.cuh line5_t; c0 and c1 of each, fourteen limbs
+ * each), written into the context's line workspace in the library's word-major layout.  status: n entries; an item that is not
+ * BLSGPU_OK is skipped, as the verify path skips it, and its output is left zero.  out_f12: n x twelve limb vectors, tower order. */
+int blsgpu_debug_millerf(const int32_t* lines, size_t n, const int32_t* status, int32_t* out_f12) try {
+  if (!initialised()) return NOT_INIT();
+  if (n == 0) return 0;
+  if (!lines || !status || !out_f12 || n > 4096 || is_device_ptr(lines) || is_device_ptr(status) || is_device_ptr(out_f12)) return fail(BLSGPU_E_ARG, "bad argument");
+  CTX_ACQUIRE(c);
+  const size_t nlanes = lanes_for(n), lanes = row_stride(nlanes);
+  const size_t line_words = (size_t)MILLER_ENTRIES * LINE5_WORDS * lanes;
+  int rc = arena_reserve(c, pad256(4 * n) + 2 * pad256((size_t)WS_F_WORDS * 4 * n) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  if (lines_reserve(c, line_words * 4)) return fail(BLSGPU_E_HIP, "no room for the line workspace");
+  // lines[(e * LINE5_WORDS + w) * lanes + t]: word w = 14 * (coefficient number) + limb, lane t = 2 * item + component
+  std::vector<uint32_t> h(line_words, 0u);
+  for (size_t i = 0; i < n; i++)
+    for (size_t e = 0; e < MILLER_ENTRIES; e++)
+      for (size_t k = 0; k < 5; k++)
+        for (size_t comp = 0; comp < 2; comp++)
+          for (size_t l = 0; l < FP_NL; l++)
+            h[(e * LINE5_WORDS + k * FP_NL + l) * lanes + 2 * i + comp] = (uint32_t)lines[(((i * MILLER_ENTRIES + e) * 5 + k) * 2 + comp) * FP_NL + l];
+  HIPCK(hipMemcpyAsync(c->lines_ws, h.data(), line_words * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));           // h leaves scope after the call; pageable memory
+  const void* d_st;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
+  if (!d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemsetAsync(d_f, 0, (size_t)WS_F_WORDS * 4 * n, c->stream));
+  KL(KID_MILLER2, k_millerf2s, dim3((unsigned)(nlanes / BLS_BLOCK)), dim3(BLS_BLOCK), n, (size_t)0, n, (const int32_t*)d_st, (const uint32_t*)c->lines_ws, lanes, d_f);
+  HIPCK(hipGetLastError());
+  std::vector<uint32_t> f((size_t)WS_F_WORDS * n);
+  HIPCK(hipMemcpyAsync(f.data(), d_f, f.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));
+  // Fp12 workspace: word w of item i at fws[w * n + i], w = 28 * (Fp2 in tower order) + 14 * component + limb
+  for (size_t i = 0; i < n; i++)
+    for (size_t w = 0; w < WS_F_WORDS; w++) out_f12[i * WS_F_WORDS + w] = (int32_t)f[w * n + i];
   SYNC_FLUSH(c);
   return 0;
 }

@@ -1,0 +1,74 @@
+// Operation table of the field / tower self-test door (blsgpu_debug_field_op, include/blsgpu.h): ONE list that the device
+// kernels (tu_debug_ops*.hip), the host entry (blsgpu.hip) and, through blsgpu_debug_field_op_shape, the Python binding read.
+// Elements cross the door in the internal form: fourteen signed 32-bit limbs of 28 bits (fp.cuh), R = 2^392.
+//     X(name, id, lanes, n_in, n_out, n_par, chain)
+// lanes: 1 = one item per lane (the code of k_prepare, the MSM and the point kernels), 2 = one item per lane pair (hfp2: item j
+// on lanes 2j and 2j + 1, 32 items per workgroup).  n_in / n_out: Fp limb vectors per record; an Fp2 is two of them (c0, c1), an
+// Fp12 twelve, in tower order (c0.a0, c0.a1, c0.a2, c1.a0, c1.a1, c1.a2).  n_par: small integers after the input vectors.
+// chain: reps > 1 is allowed and feeds the output back as the first operand.
+#pragma once
+
+#define BLS_DEBUG_OPS(X)                                                                                            \
+  /* ---- one lane per item */                                                                                      \
+  X(FP_NORM, 0, 1, 1, 1, 0, 0)         /* fp_norm */                                                                 \
+  X(FP_REDUCE, 1, 1, 1, 1, 0, 0)       /* fp_reduce */                                                               \
+  X(FP_CANON, 2, 1, 1, 2, 0, 0)        /* out0 = fp_canon; out1 = [fp_is_zero, fp_to_raw words 0..11, 0] */          \
+  X(FP_REDUCE_LIN2, 3, 1, 2, 1, 2, 0)  /* fp_reduce_lin2(a, ka, b, kb) */                                            \
+  X(FP_MUL, 4, 1, 2, 1, 0, 1)          /* fp_mul */                                                                  \
+  X(FP_SQR, 5, 1, 1, 1, 0, 1)          /* fp_sqr */                                                                  \
+  X(FP_INV, 6, 1, 1, 1, 0, 0)          /* fp_inv (constant-time safegcd) */                                          \
+  X(FP_INV_VAR, 7, 1, 1, 1, 0, 0)      /* fp_inv_var */                                                              \
+  X(FP_SQRT, 8, 1, 1, 2, 0, 0)         /* out0 = fp_sqrt root; out1 = [fp_sqrt flag, fp_is_square, 0..] */           \
+  X(FP_FROM_RAW, 9, 1, 1, 1, 0, 0)     /* in0 = [raw words 0..11, 0, 0]; out = fp_from_raw */                        \
+  X(FP2_KARA_PRODUCTS, 10, 1, 4, 2, 0, 0) /* fp2_kara_products(a0, a1, b0, b1) -> c0, c0 + c1 */                     \
+  X(FP2_KARA_DIFFS, 11, 1, 4, 2, 0, 0)    /* fp2_kara_diffs */                                                       \
+  X(FP2L_MUL, 12, 1, 4, 2, 0, 0)       /* one-lane fp2_mul (tower.cuh fp2) */                                        \
+  X(FP2L_SQR, 13, 1, 2, 2, 0, 0)       /* one-lane fp2_sqr */                                                        \
+  X(FP2L_INV, 14, 1, 2, 2, 0, 0)       /* one-lane fp2_inv */                                                        \
+  /* ---- two lanes per item: lane-split Fp2 */                                                                     \
+  X(FP2_MUL, 20, 2, 4, 2, 0, 1)        /* fp2_mul (fp2_mul_split_leaf) */                                            \
+  X(FP2_SQR, 21, 2, 2, 2, 0, 1)        /* fp2_sqr */                                                                 \
+  X(FP2_MUL_XI, 22, 2, 2, 2, 0, 0)     /* fp2_mul_xi */                                                              \
+  X(FP2_MUL_FP, 23, 2, 3, 2, 0, 0)     /* fp2_mul_fp(a, k): in = a.c0, a.c1, k */                                    \
+  X(FP2_CONJ, 24, 2, 2, 2, 0, 0)       /* fp2_conj */                                                                \
+  X(FP2_INV, 25, 2, 2, 2, 0, 0)        /* fp2_inv (fp_inv_pair) */                                                   \
+  X(F12_PACK, 26, 2, 12, 12, 0, 0)     /* sh_st_f12 then sh_ld_f12 */                                                \
+  /* ---- two lanes per item: the accumulator in LDS */                                                             \
+  X(F12_SH_SQR, 30, 2, 12, 12, 0, 1)        /* f12_sh_sqr */                                                         \
+  X(F12_SH_MUL, 31, 2, 24, 12, 0, 1)        /* f12_sh_mul(acc, b) */                                                 \
+  X(F12_SH_MUL_LINE, 32, 2, 18, 12, 0, 1)   /* f12_sh_mul_line(acc, l0, l2, l3) */                                   \
+  X(F12_SH_MUL_2LINES, 33, 2, 24, 12, 0, 1) /* f12_sh_mul_2lines(acc, a0, a2, a3, b0, b2, b3) */                     \
+  X(F12_SH_MUL_LINE5, 34, 2, 22, 12, 0, 1)  /* f12_sh_mul_line5(acc, c0, c2, c4, c3, c5) */                          \
+  X(F12_SH_CYC_SQR, 35, 2, 12, 12, 0, 1)    /* f12_sh_cyclotomic_sqr */                                              \
+  /* ---- two lanes per item: compressed squarings on (z2, z3, z4, z5) */                                           \
+  X(CYC_C_SQR, 40, 2, 8, 8, 0, 1)           /* f12_sh_cyc_c_sqr_body (packed slots) */                               \
+  X(CYC_C_SQR_UNPACKED, 41, 2, 8, 8, 0, 1)  /* f12_sh_cyc_c_sqr_unpacked_body */                                     \
+  X(CYC_C_SQR_KARA, 42, 2, 8, 8, 0, 1)      /* cyck_from_split, f12_sh_cyc_c_sqr_kara_body, cyck_to_split */         \
+  /* ---- two lanes per item: other Fp12 operations on fp12_t<hfp2> */                                              \
+  X(F12_POW_X, 50, 2, 12, 12, 0, 0)    /* fp12_pow_x */                                                              \
+  X(F12_INV, 51, 2, 12, 12, 0, 0)      /* fp12_inv */                                                                \
+  X(F12_FROB1, 52, 2, 12, 12, 0, 0)    /* fp12_frob<1> */                                                            \
+  X(F12_FROB2, 53, 2, 12, 12, 0, 0)    /* fp12_frob<2> */
+
+enum {
+#define X(name, id, lanes, nin, nout, npar, chain) DBG_##name = id,
+  BLS_DEBUG_OPS(X)
+#undef X
+};
+
+#define DBG_NL 14   // limbs per Fp (FP_NL)
+
+#if defined(__HIPCC__)
+#ifndef BLS_BLOCK
+#define BLS_BLOCK 64
+#endif
+#ifndef BLS_SPLIT_WAVES
+#define BLS_SPLIT_WAVES 2
+#endif
+// in: n records of rec_in 32-bit words (the input vectors, then the parameters), out: n records of rec_out words
+__global__ void k_dbg_fp1(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_fp2s(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_f12acc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_cyc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_f12misc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+#endif

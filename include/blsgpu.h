@@ -298,6 +298,20 @@ int blsgpu_debug_wide_program(const uint32_t* prog, size_t len, int reps, const 
  * is, as the verify path skips identity items; the others become BLSGPU_OK (fin^(3 (p^12 - 1) / r) == 1) or
  * BLSGPU_ERR_INVALID_SIGNATURE. */
 int blsgpu_debug_finalexp_batch(const void* f12s, size_t n, int form, size_t chunk, int32_t* status);
+/* Self-test hook of the field leaves and the lane-split tower (not part of the reference interface): ONE operation of
+ * csrc/debug_ops.h on n caller-supplied records.  Elements cross in the internal form -- fourteen signed 32-bit limbs of 28 bits
+ * per Fp, R = 2^392 -- so that lazy, redundant and negative operands can be injected.  A record of `in` is n_in limb vectors
+ * followed by n_par 32-bit parameters, a record of `out` n_out limb vectors (blsgpu_debug_field_op_shape; an Fp2 is two vectors,
+ * an Fp12 twelve in tower order).  lanes = 1: one item per lane; 2: item j on lanes 2j and 2j + 1.  reps > 1 (operations with
+ * chain = 1 only) feeds the output back as the first operand.  Host pointers.  The caller keeps the operands inside the input
+ * contract of the function under test (fp.cuh); nothing is checked here. */
+int blsgpu_debug_field_op_shape(int op, int* lanes, int* n_in, int* n_out, int* n_par, int* chain);
+int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t* out);
+/* Self-test hook of the Miller accumulator's kernel (not part of the reference interface): k_millerf2s itself, launched as the
+ * verify path launches it, on a caller-supplied line table.  lines: n x 68 entries x five Fp2 coefficients in the order c0, c2,
+ * c4, c3, c5 (c0 then c1 of each, fourteen limbs each, reduced form).  status: an item that is not BLSGPU_OK is skipped and its
+ * output left zero.  out_f12: n x twelve limb vectors in tower order.  Host pointers, n <= 4096. */
+int blsgpu_debug_millerf(const int32_t* lines, size_t n, const int32_t* status, int32_t* out_f12);
 
 /* Sign side, provided so that benchmarks and tests can build inputs on the device:
  * pk[i] = sk[i] * g (SecretKey::public_key, src/secret_key.rs:342-344) and

@@ -6,6 +6,7 @@
 #include "../../agora-blsful_amd/csrc/verify.cuh"
 #include "../../agora-blsful_amd/csrc/tower_split.cuh"
 #include "../../agora-blsful_amd/csrc/msm2.cuh"
+#include "../../agora-blsful_amd/csrc/debug_ops.h"
 
 // callers pass blst-style Montgomery words (R = 2^384, 12 words per Fp) exactly like the RAW formats of the C ABI
 static void raw_fp2(fp2& r, const uint32_t* w) { fp_from_raw(r.c0, w); fp_from_raw(r.c1, w + 12); }
@@ -587,5 +588,143 @@ void hs_msm2_small(int group, int n, const uint32_t* pts, const uint32_t* scalar
     delete[] qx; delete[] qy; delete[] subs;
   }
   delete[] inf;
+}
+
+// ---- one operation of csrc/debug_ops.h on one record, the host twin of the device door blsgpu_debug_field_op: tests/field_cases.py runs
+// every case through it with the bound tracker on (lb / vb: the case's declared limb and value bounds per input vector; nn: limbs
+// 0..12 in [0, 2^28), a reduced or multiplied value), which proves the case legal for the function under test.  The lane-split
+// operations run on the host emulation of tower_split.cuh; what exists on the device only (the LDS packing, the accumulator functions)
+// is represented by the template body it wraps.  Returns 0, or -1 for an operation it does not know.
+static void fo_ld(fp& r, const int32_t* in, const double* lb, const double* vb, const int32_t* nn, int k) {
+  for (int i = 0; i < FP_NL; i++) r.l[i] = in[k * FP_NL + i];
+  FP_TRK(r.lb = lb[k]; r.vb = vb[k]; r.nn = nn[k] != 0;)
+  (void)lb; (void)vb; (void)nn;
+}
+static void fo_st(int32_t* out, int k, const fp& a) {
+  for (int i = 0; i < FP_NL; i++) out[k * FP_NL + i] = a.l[i];
+}
+#define FO_LD(r, k) fo_ld(r, in, lb, vb, nn, k)
+#define FO_LD2(h, k) { FO_LD(h.c[0], 2 * (k)); FO_LD(h.c[1], 2 * (k) + 1); }
+#define FO_ST2(k, h) { fo_st(out, 2 * (k), h.c[0]); fo_st(out, 2 * (k) + 1, h.c[1]); }
+static void fo_ld12(fp12_t<hfp2>& f, const int32_t* in, const double* lb, const double* vb, const int32_t* nn, int k0) {
+  hfp2* c[6] = {&f.c0.a0, &f.c0.a1, &f.c0.a2, &f.c1.a0, &f.c1.a1, &f.c1.a2};
+  for (int k = 0; k < 6; k++) FO_LD2((*c[k]), k0 + k);
+}
+static void fo_st12(int32_t* out, const fp12_t<hfp2>& f) {
+  const hfp2* c[6] = {&f.c0.a0, &f.c0.a1, &f.c0.a2, &f.c1.a0, &f.c1.a1, &f.c1.a2};
+  for (int k = 0; k < 6; k++) FO_ST2(k, (*c[k]));
+}
+int hs_field_op(int op, const int32_t* in, const double* lb, const double* vb, const int32_t* nn, const int32_t* par, int reps, int32_t* out) {
+  fp a, b, c, d, r, s;
+  hfp2 x, y, z;
+  switch (op) {
+    case DBG_FP_NORM: FO_LD(a, 0); fp_norm(r, a); fo_st(out, 0, r); return 0;
+    case DBG_FP_REDUCE: FO_LD(a, 0); fp_reduce(r, a); fo_st(out, 0, r); return 0;
+    case DBG_FP_CANON: {
+      FO_LD(a, 0);
+      fp_canon(r, a);
+      fo_st(out, 0, r);
+      uint32_t w[12];
+      fp_to_raw(w, a);
+      out[FP_NL] = fp_is_zero(a) ? 1 : 0;
+      for (int k = 0; k < 12; k++) out[FP_NL + 1 + k] = (int32_t)w[k];
+      out[2 * FP_NL - 1] = 0;
+      return 0;
+    }
+    case DBG_FP_REDUCE_LIN2: FO_LD(a, 0); FO_LD(b, 1); fp_reduce_lin2(r, a, par[0], b, par[1]); fo_st(out, 0, r); return 0;
+    case DBG_FP_MUL: FO_LD(a, 0); FO_LD(b, 1); for (int k = 0; k < reps; k++) fp_mul(a, a, b); fo_st(out, 0, a); return 0;
+    case DBG_FP_SQR: FO_LD(a, 0); for (int k = 0; k < reps; k++) fp_sqr(a, a); fo_st(out, 0, a); return 0;
+    case DBG_FP_INV: FO_LD(a, 0); fp_inv(r, a); fo_st(out, 0, r); return 0;
+    case DBG_FP_INV_VAR: FO_LD(a, 0); fp_inv_var(r, a); fo_st(out, 0, r); return 0;
+    case DBG_FP_SQRT: {
+      FO_LD(a, 0);
+      const bool ok = fp_sqrt(r, a);
+      const bool sq = fp_is_square(a);
+      fo_st(out, 0, r);
+      for (int k = 0; k < FP_NL; k++) out[FP_NL + k] = 0;
+      out[FP_NL] = ok ? 1 : 0;
+      out[FP_NL + 1] = sq ? 1 : 0;
+      return 0;
+    }
+    case DBG_FP_FROM_RAW: {
+      uint32_t w[12];
+      for (int k = 0; k < 12; k++) w[k] = (uint32_t)in[k];
+      fp_from_raw(r, w);
+      fo_st(out, 0, r);
+      return 0;
+    }
+    case DBG_FP2_KARA_PRODUCTS:
+    case DBG_FP2_KARA_DIFFS:
+      FO_LD(a, 0); FO_LD(b, 1); FO_LD(c, 2); FO_LD(d, 3);
+      if (op == DBG_FP2_KARA_PRODUCTS) fp2_kara_products(r, s, a, b, c, d);
+      else fp2_kara_diffs(r, s, a, b, c, d);
+      fo_st(out, 0, r);
+      fo_st(out, 1, s);
+      return 0;
+    case DBG_FP2L_MUL:
+    case DBG_FP2L_SQR:
+    case DBG_FP2L_INV: {
+      fp2 u, v, w;
+      FO_LD(u.c0, 0); FO_LD(u.c1, 1);
+      if (op == DBG_FP2L_MUL) { FO_LD(v.c0, 2); FO_LD(v.c1, 3); fp2_mul(w, u, v); }
+      else if (op == DBG_FP2L_SQR) fp2_sqr(w, u);
+      else fp2_inv(w, u);
+      fo_st(out, 0, w.c0);
+      fo_st(out, 1, w.c1);
+      return 0;
+    }
+    case DBG_FP2_MUL: FO_LD2(x, 0); FO_LD2(y, 1); for (int k = 0; k < reps; k++) fp2_mul(x, x, y); FO_ST2(0, x); return 0;
+    case DBG_FP2_SQR: FO_LD2(x, 0); for (int k = 0; k < reps; k++) fp2_sqr(x, x); FO_ST2(0, x); return 0;
+    case DBG_FP2_MUL_XI: FO_LD2(x, 0); fp2_mul_xi(z, x); FO_ST2(0, z); return 0;
+    case DBG_FP2_MUL_FP: FO_LD2(x, 0); FO_LD(a, 2); fp2_mul_fp(z, x, a); FO_ST2(0, z); return 0;
+    case DBG_FP2_CONJ: FO_LD2(x, 0); fp2_conj(z, x); FO_ST2(0, z); return 0;
+    case DBG_FP2_INV: FO_LD2(x, 0); fp2_inv(z, x); FO_ST2(0, z); return 0;
+    default: break;
+  }
+  if (op == DBG_CYC_C_SQR || op == DBG_CYC_C_SQR_UNPACKED || op == DBG_CYC_C_SQR_KARA) {
+    const int keep = g_cyc_kara;
+    g_cyc_kara = op == DBG_CYC_C_SQR_KARA;
+    cyc_c<hfp2> cc;
+    FO_LD2(cc.z2, 0); FO_LD2(cc.z3, 1); FO_LD2(cc.z4, 2); FO_LD2(cc.z5, 3);
+    for (int k = 0; k < reps; k++) cyc_c_sqr(cc, cc);
+    FO_ST2(0, cc.z2); FO_ST2(1, cc.z3); FO_ST2(2, cc.z4); FO_ST2(3, cc.z5);
+    g_cyc_kara = keep;
+    return 0;
+  }
+  fp12_t<hfp2> f, g;
+  fo_ld12(f, in, lb, vb, nn, 0);
+  switch (op) {
+    case DBG_F12_PACK: break;     // the packing itself is device code: the case list states its operand contract (tests/field_cases.py)
+    case DBG_F12_SH_SQR: for (int k = 0; k < reps; k++) { fp12_sqr_body(g, f); f = g; } break;
+    case DBG_F12_SH_MUL: fo_ld12(g, in, lb, vb, nn, 6); for (int k = 0; k < reps; k++) { fp12_t<hfp2> t; fp12_mul_body(t, f, g); f = t; } break;
+    case DBG_F12_SH_MUL_LINE: FO_LD2(x, 6); FO_LD2(y, 7); FO_LD2(z, 8); for (int k = 0; k < reps; k++) fp12_mul_by_line_body(f, x, y, z); break;
+    case DBG_F12_SH_MUL_2LINES: {
+      hfp2 b0, b2, b3;
+      FO_LD2(x, 6); FO_LD2(y, 7); FO_LD2(z, 8); FO_LD2(b0, 9); FO_LD2(b2, 10); FO_LD2(b3, 11);
+      for (int k = 0; k < reps; k++) fp12_mul_by_2lines_body(f, x, y, z, b0, b2, b3);
+      break;
+    }
+    case DBG_F12_SH_MUL_LINE5: {
+      line5_t<hfp2> L;
+      FO_LD2(L.c0, 6); FO_LD2(L.c2, 7); FO_LD2(L.c4, 8); FO_LD2(L.c3, 9); FO_LD2(L.c5, 10);
+      for (int k = 0; k < reps; k++) fp12_mul_by_line5_body(f, L);
+      break;
+    }
+    case DBG_F12_SH_CYC_SQR: for (int k = 0; k < reps; k++) { fp12_cyclotomic_sqr_body(g, f); f = g; } break;
+    case DBG_F12_POW_X: {
+      const int keep = g_cyc_kara;
+      g_cyc_kara = 0;             // the device's fp12_pow_x: six powers, lane-split squarings
+      fp12_pow_x(g, f);
+      g_cyc_kara = keep;
+      f = g;
+      break;
+    }
+    case DBG_F12_INV: fp12_inv(g, f); f = g; break;
+    case DBG_F12_FROB1: fp12_frob<1>(g, f); f = g; break;
+    case DBG_F12_FROB2: fp12_frob<2>(g, f); f = g; break;
+    default: return -1;
+  }
+  fo_st12(out, f);
+  return 0;
 }
 }

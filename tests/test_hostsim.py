@@ -7,13 +7,14 @@ import random
 
 import pytest
 
+import field_cases as fc
 import util
 from util import c, ref, P
 
 
 def test_fp_ops(hs):
     rng = random.Random(1)
-    edge = [0, 1, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, 2**380, 2**381 % P]
+    edge = fc.CANON_EDGES             # 0, 1, 2, p-1, p-2, (p+-1)/2, 2^380, 2^381 mod p, 2^28-1, 2^28, 2^364, R mod p
     vals = edge + [rng.randrange(P) for _ in range(300)]
     out = ctypes.create_string_buffer(48)
     for i in range(len(vals) - 1):
@@ -89,44 +90,23 @@ def test_fp_lazy_limbs(hs):
     """fp_norm / fp_reduce / fp_canon / fp_is_zero on redundant signed-limb vectors: exact multiples of p in lazy form,
     values at the rounding boundary of the quotient estimate, negative values, maximal limb magnitudes."""
     rng = random.Random(5)
-    M = (1 << 28) - 1
+    M = fc.M
+    val, limbs_of = util.val, util.limbs_of          # the limb-form helpers and generators are shared with tests/field_cases.py
 
-    def val(l):
-        return sum(int(x) << (28 * i) for i, x in enumerate(l))
-
-    def limbs_of(v):          # canonical limbs of a non-negative integer < 2^392
-        return [(v >> (28 * i)) & M for i in range(14)]
-
-    def scramble(l, spread):  # same integer, redundant limbs: move multiples of 2^28 between neighbours
-        l = list(l)
-        for i in range(13):
-            d = rng.randint(-spread, spread)
-            l[i] += d << 28
-            l[i + 1] -= d
-        return l
+    def scramble(l, spread):
+        return fc.scramble(l, spread, rng)
 
     cases = []
     for k in (-100, -7, -3, -1, 0, 1, 2, 5, 64, 100):                       # exact multiples of p
-        v = k * P
-        base = limbs_of(v % (1 << 392))
-        if v < 0:
-            base[13] -= 1 << 28                                              # two's-complement top limb -> signed value
-        assert val(base) == v
+        base = limbs_of(k * P)
         cases.append(base)
         cases.append(scramble(base, 3))
     for k in (-9, -1, 0, 1, 8):                                              # around the rounding boundary k p +- p/2
         for d in (-2, -1, 0, 1, 2):
-            v = k * P + P // 2 + d
-            base = limbs_of(v % (1 << 392))
-            if v < 0:
-                base[13] -= 1 << 28
-            cases.append(scramble(base, 2))
+            cases.append(scramble(limbs_of(k * P + P // 2 + d), 2))
     for _ in range(300):                                                     # random values within +-110 p, lazy limbs
-        v = rng.randrange(-110 * P, 110 * P)
-        base = limbs_of(v % (1 << 392))
-        if v < 0:
-            base[13] -= 1 << 28
-        cases.append(scramble(base, rng.choice((0, 1, 3, 7))))
+        cases.append(scramble(limbs_of(rng.randrange(-110 * P, 110 * P)), rng.choice((0, 1, 3, 7))))
+    cases += [cs['vecs'][0] for cs in fc.build()['FP_REDUCE']]               # and the shared list: edges, extreme limbs, extreme reduced top limbs
     out = (ctypes.c_int32 * 55)()
     for l in cases:
         v = val(l)
@@ -149,21 +129,11 @@ def test_fp_reduce_lin2(hs):
     squarings): against integers on redundant signed-limb operands -- limb magnitudes up to what three products' sums and a xi-twist
     leave (6 x 2^28), coefficient pairs the kernels use and larger ones, values at the rounding boundary of the quotient estimate."""
     rng = random.Random(15)
-    M = (1 << 28) - 1
+    M = fc.M
+    val = util.val
 
-    def val(l):
-        return sum(int(x) << (28 * i) for i, x in enumerate(l))
-
-    def lazy(v, spread):      # redundant limbs of v: multiples of 2^28 moved between neighbours
-        base = [(v % (1 << 392) >> (28 * i)) & M for i in range(14)]
-        if v < 0:
-            base[13] -= 1 << 28
-        for i in range(13):
-            d = rng.randint(-spread, spread)
-            base[i] += d << 28
-            base[i + 1] -= d
-        assert val(base) == v
-        return base
+    def lazy(v, spread):      # redundant limbs of v (tests/field_cases.py)
+        return fc.lazy(v, spread, rng)
 
     out = (ctypes.c_int32 * 14)()
     cases = []
@@ -177,6 +147,7 @@ def test_fp_reduce_lin2(hs):
                 v = k * P + P // 2 + d
                 if v % ka == 0:
                     cases.append((ka, kb, lazy(v // ka, 2), lazy(0, 2)))
+    cases += [(cs['par'][0], cs['par'][1], cs['vecs'][0], cs['vecs'][1]) for cs in fc.build()['FP_REDUCE_LIN2']]     # and the shared list
     for ka, kb, la, lb in cases:
         va, vb = val(la), val(lb)
         lba = float(max(abs(x) for x in la) + 1)

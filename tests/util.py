@@ -76,7 +76,7 @@ def build_hostsim():
     so = os.path.join(ROOT, 'tests', 'hostsim', 'libhostsim.so')
     if os.environ.get('BLS_HOSTSIM_SO'):          # a debug build (-O0 -g) for locating a tracked-bound violation
         return ctypes.CDLL(os.environ['BLS_HOSTSIM_SO'])
-    deps = [src] + [os.path.join(ROOT, 'agora-blsful_amd', 'csrc', f) for f in os.listdir(os.path.join(ROOT, 'agora-blsful_amd', 'csrc')) if f.endswith('.cuh')]
+    deps = [src] + [os.path.join(ROOT, 'agora-blsful_amd', 'csrc', f) for f in os.listdir(os.path.join(ROOT, 'agora-blsful_amd', 'csrc')) if f.endswith(('.cuh', '.h'))]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         import subprocess
         # BLS_TRACK_BOUNDS: every Fp value carries worst-case limb/value bounds that are checked on every operation
@@ -122,3 +122,33 @@ def f12_from_record(b):
     for k in range(6):
         out[_TOWER_TO_W[k]] = (fp_from_raw(b[96 * k:96 * k + 48]), fp_from_raw(b[96 * k + 48:96 * k + 96]))
     return tuple(out)
+
+
+# ---- the internal form of csrc/fp.cuh: fourteen signed limbs of 28 bits, Montgomery factor R = 2^392
+NL = 14
+LIMB_MASK = (1 << 28) - 1
+R392 = 1 << 392
+R392_INV = pow(R392, -1, P)
+
+
+def val(l):
+    """the integer a limb vector stands for"""
+    return sum(int(x) << (28 * i) for i, x in enumerate(l))
+
+
+def limbs_of(v):
+    """limbs 0..12 in [0, 2^28) and a signed top limb: the exact-limb form of any integer of magnitude below 2^394"""
+    l = [(v >> (28 * i)) & LIMB_MASK for i in range(NL - 1)] + [v >> (28 * (NL - 1))]
+    assert val(l) == v and -2**31 <= l[-1] < 2**31
+    return l
+
+
+def limbs_of_elem(x):
+    """the reduced internal form of the field element x: its Montgomery residue in (-p/2, p/2], exact limbs"""
+    v = x % P * R392 % P
+    return limbs_of(v - P if 2 * v > P else v)
+
+
+def elem_of(l):
+    """limb vector -> the field element it stands for"""
+    return val(l) * R392_INV % P
