@@ -671,6 +671,7 @@ def sum_batch(group, sets, fmt=FMT_RAW_PROJ):
 
 # ------------------------------------------------------------------ registered key sets
 KEYSET_TABLES = 1
+KEYSET_LINES = 2    # Bls12381G1Impl: every key's Miller-loop rows, read by the one-key-per-item indexed calls on the lane-split path
 E_ARG = -3          # in a status slot of an indexed call: the set names an index outside the key set
 _POINT_BYTES = {FMT_RAW_PROJ: 144, FMT_RAW_AFFINE: 96, FMT_COMPRESSED: 48, FMT_LEGACY: 48}
 
@@ -702,25 +703,30 @@ class KeySet:
         self.handle, self.statuses = handle, statuses
 
     @classmethod
-    def create(cls, sig_group, keys, fmt=FMT_COMPRESSED, tables=False):
+    def create(cls, sig_group, keys, fmt=FMT_COMPRESSED, tables=False, lines=False):
         """`keys`: a list of byte strings in `fmt`, the public keys of Bls12381G{sig_group}Impl.  self.statuses[i] is what
-        deserialize gives for key i; a key that fails stays in the table as an invalid entry."""
+        deserialize gives for key i; a key that fails stays in the table as an invalid entry.  tables: the fixed-base tables
+        (KEYSET_TABLES); lines: the per-key line tables (KEYSET_LINES; built for sig_group 1 only).  info() says what was built."""
         lib = init()
         n = len(keys)
         blob = b''.join(keys)
         st = (ctypes.c_int32 * max(n, 1))()
         h = ctypes.c_uint64(0)
-        _check(lib.blsgpu_keyset_create(sig_group, _ptr(blob) if blob else None, n, fmt, KEYSET_TABLES if tables else 0,
+        _check(lib.blsgpu_keyset_create(sig_group, _ptr(blob) if blob else None, n, fmt, cls._flags(tables, lines),
                                         ctypes.cast(st, ctypes.c_void_p), ctypes.byref(h)))
         return cls(h.value, list(st)[:n])
 
     @classmethod
-    def create_device(cls, sig_group, keys_ptr, n, fmt=FMT_RAW_PROJ, tables=False):
+    def create_device(cls, sig_group, keys_ptr, n, fmt=FMT_RAW_PROJ, tables=False, lines=False):
         """From n keys already on the device (an integer address, e.g. tensor.data_ptr())."""
         lib = init()
         h = ctypes.c_uint64(0)
-        _check(lib.blsgpu_keyset_create(sig_group, ctypes.c_void_p(keys_ptr), n, fmt, KEYSET_TABLES if tables else 0, None, ctypes.byref(h)))
+        _check(lib.blsgpu_keyset_create(sig_group, ctypes.c_void_p(keys_ptr), n, fmt, cls._flags(tables, lines), None, ctypes.byref(h)))
         return cls(h.value, None)
+
+    @staticmethod
+    def _flags(tables, lines):
+        return (KEYSET_TABLES if tables else 0) | (KEYSET_LINES if lines else 0)
 
     def close(self):
         if self.handle:
@@ -735,10 +741,11 @@ class KeySet:
         return False
 
     def info(self):
-        """dict(sig_group, n, has_tables, device_bytes)"""
+        """dict(sig_group, n, has_tables, has_lines, device_bytes): what creation built (bit 0 / bit 1 of the C call's mask)"""
         sg, ht, n, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
         _check(init().blsgpu_keyset_info(self.handle, ctypes.byref(sg), ctypes.byref(n), ctypes.byref(ht), ctypes.byref(b)))
-        return {'sig_group': sg.value, 'n': n.value, 'has_tables': bool(ht.value), 'device_bytes': b.value}
+        return {'sig_group': sg.value, 'n': n.value, 'has_tables': bool(ht.value & KEYSET_TABLES), 'has_lines': bool(ht.value & KEYSET_LINES),
+                'device_bytes': b.value}
 
     def _key_group(self):
         return 3 - self.info()['sig_group']

@@ -51,6 +51,7 @@ enum {
   KID_KEYSET_SEAL, KID_KEYSET_BUILD, KID_KEYSET_CHECK, KID_KEYSET_GATHER, KID_KEYSET_ACCUM, KID_KEYSET_MUL, KID_KEYSET_FIN,   // registered key sets (keyset.cuh)
   KID_ELGAMAL_PREP, KID_ELGAMAL_LADDER, KID_ELGAMAL_TRANSCRIPT, KID_ELGAMAL_SUB,   // blsgpu_elgamal_proof_verify_batch / blsgpu_elgamal_open_batch
   KID_GROUP_LINES, KID_PREPARE_SHARED,   // blsgpu_verify_shared_batch (verify_shared.cuh; k_group_affine and k_shared_expand count under k_prepare_shared, k_lines2s_shared under k_lines2s)
+  KID_KEYSET_LINES, KID_LINES_KEYED,     // key sets with line tables (keyset.cuh): the build at creation, and the line kernel that reads both rows
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -66,7 +67,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_sum_accumulate_seg", "k_sum_fold", "k_sum_out",
                                     "k_keyset_seal", "k_keyset_build", "k_keyset_check", "k_keyset_gather", "k_keyset_accumulate_seg", "k_keyset_mul", "k_keyset_fin",
                                     "k_elgamal_prep", "k_elgamal_ladder", "k_elgamal_transcript", "k_elgamal_sub",
-                                    "k_group_lines", "k_prepare_shared"};
+                                    "k_group_lines", "k_prepare_shared",
+                                    "k_keyset_lines", "k_lines2s_keyed"};
 
 struct Ctx {
   int dev = -1;
@@ -185,7 +187,7 @@ struct Knobs {
   long secure_batch_max = 1024; // blsgpu_verify_secure_batch, blsgpu_aggregate_secure_batch: a set of at least this many keys runs through blsgpu_verify_secure's machinery
   long agg_batch_max = 32768;  // blsgpu_aggregate_verify_batch: a set of at least this many pairs runs through blsgpu_aggregate_verify's machinery
   long multi_strip = 0;        // blsgpu_multi_verify_batch: keys per strip of the segmented key sum (0: one strip per lane of a single sum, at least 4)
-  long keyset_table_mb = 4096; // blsgpu_keyset_create: fixed-base tables above this many MiB are not built (the set works without them)
+  long keyset_table_mb = 4096; // blsgpu_keyset_create: fixed-base and line tables above this many MiB together are not built (the set works without them)
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
   long shared_lines_min = -1; // blsgpu_verify_shared_batch, Bls12381G2Impl: per-group line tables from this many items per group on average (0: never; unset: SHARED_LINES_AUTO_*)
   // A/B
@@ -749,8 +751,11 @@ void launch_finalexp_chunk(Ctx* c, size_t n, size_t first, size_t cnt, const uin
 // sh_table / sh_group (fixed_g2 = 0, shared-message verify): on the lane-split path pair 1's G2 member is the point of item i's group
 // sh_group[i], its normalised rows in sh_table (verify_shared.cuh; the records carry the signature's pair first) -- one line
 // launch per chunk (k_lines2s_shared) instead of two.  Every other path takes the records as two general pairs.
+// key_table / key_of (fixed_g2 = 2, registered key sets with line tables): on the lane-split path pair 0's G2 member is the entry
+// key_of[i] of a set whose rows are in key_table (keyset.cuh) -- the chunk's line launch reads both rows and walks nothing
+// (k_lines2s_keyed).  Every other path ignores them.
 int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2, const uint32_t* sh_table = nullptr,
-                 const uint32_t* sh_group = nullptr) {
+                 const uint32_t* sh_group = nullptr, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
   if (n <= wide_max_items() && n <= coop_max_items()) {
     // single verifications and the one-verdict tails on the row-wide engine (csrc/wide_engine.cuh): one 256-thread workgroup
     // per item runs line coefficients, Miller loop, final exponentiation and verdict as one table program.
@@ -782,7 +787,9 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
         const size_t nlanes = lanes_for(cnt), lanes = row_stride(nlanes);       // `lanes` below: the row stride the kernels index with
         uint32_t* lines3 = c->lines_ws + (size_t)MILLER_ENTRIES * LINE5_WORDS * lanes;
         const dim3 grid((unsigned)(nlanes / BLS_BLOCK));
-        if (fixed_g2) {
+        if (fixed_g2 == 2 && key_table) {
+          KL(KID_LINES_KEYED, k_lines2s_keyed, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, key_table, key_of);
+        } else if (fixed_g2) {
           KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, fixed_g2, 0);
         } else if (sh_table) {
           KL(KID_LINES, k_lines2s_shared, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, sh_table, sh_group);
@@ -900,7 +907,8 @@ int launch_lines_and_post(Ctx* c, size_t n, uint32_t* d_rec, int32_t* d_status) 
 // one core_verify per item: statuses end up in d_status (device)
 int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_t* d_sigs, int fmt, const uint8_t* d_msgs,
                      const uint64_t* d_offs, int single_msg, const dst_arg& dst, size_t n, uint32_t* d_pairs, uint32_t* d_f,
-                     int32_t* d_status, int pre_status = 0) {
+                     int32_t* d_status, int pre_status = 0, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
+  // key_table / key_of: the keys are entries of a registered set with line tables (run_pairing2); only the last plan passes them on
   if (n == 0) return 0;
   if (sg == 1 && aug == 0 && !pre_status && n <= wide_max_items() && n <= coop_max_items()) {
     // Single verifications of Bls12381G1Impl without a key prefix, cut where the inputs allow (csrc/kernels.cuh k_pairing_pre /
@@ -1002,7 +1010,7 @@ int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_
     KL(KID_PREPARE, k_prepare<1>, dim3(nb), dim3(BLS_BLOCK), n, d_pks, d_sigs, fmt, aug, d_msgs, d_offs, single_msg, dst, d_pairs, d_status, pre_status, two_lanes | 2);
   else
     KL(KID_PREPARE, k_prepare<2>, dim3(nb), dim3(BLS_BLOCK), n, d_pks, d_sigs, fmt, aug, d_msgs, d_offs, single_msg, dst, d_pairs, d_status, pre_status, two_lanes);
-  return run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0);
+  return run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, nullptr, nullptr, sg == 1 ? key_table : nullptr, key_of);
 }
 
 // Pairing products, second form (round 3): the product over the items entry by entry, then one Horner chain (kernels.cuh
@@ -1779,6 +1787,8 @@ struct KeySet {
   size_t n = 0, devidx = 0;
   int dev = -1;
   uint8_t *aff = nullptr, *comp = nullptr, *table = nullptr;     // RAW_AFFINE records, Modern bytes, fixed-base tables (or none)
+  uint32_t* lines = nullptr;          // line tables (G2 keys, BLSGPU_KEYSET_LINES; or none) ...
+  int32_t* nolines = nullptr;         // ... and per entry 0 or KEYSET_NOLINES_*
   int32_t* status = nullptr;
   uint64_t bytes = 0;
 };
@@ -1787,7 +1797,7 @@ std::unordered_map<uint64_t, KeySet> g_keysets;
 uint64_t g_keyset_next = 1;
 void keyset_free(KeySet& k) {
   if (k.dev >= 0) (void)hipSetDevice(k.dev);
-  for (void* p : {(void*)k.aff, (void*)k.comp, (void*)k.table, (void*)k.status})
+  for (void* p : {(void*)k.aff, (void*)k.comp, (void*)k.table, (void*)k.lines, (void*)k.nolines, (void*)k.status})
     if (p) (void)hipFree(p);
   k = KeySet();
 }
@@ -4913,12 +4923,43 @@ static int keyset_build_tables(Ctx* c, KeySet& k) {
   k.bytes += tb;
   return 0;
 }
+// the line tables of a new set of G2 keys, in chunks of 4,096 keys so that the scratch rows k_keyset_lines needs (as much again as
+// the rows it writes) stay at 62 MB; leaves k.lines null (and the set without them) when the size rule (keyset_lines_fit: the
+// 32-bit offset of k_lines2s_keyed, and the knob's cap together with the fixed-base tables) or the device's memory says no
+static int keyset_build_lines(Ctx* c, KeySet& k) {
+  if (k.group != 2 || !keyset_lines_fit(k.n, k.table ? keyset_table_bytes(k.group, k.n) : 0, (uint64_t)knobs().keyset_table_mb)) return 0;
+  const size_t lb = k.n * (size_t)KEYSET_LINES_KEY_BYTES, chunk = std::min<size_t>(k.n, 4096);
+  uint32_t *lines = nullptr, *scratch = nullptr;
+  int32_t* nolines = nullptr;
+  if (hipMalloc((void**)&lines, lb) != hipSuccess || hipMalloc((void**)&scratch, chunk * (size_t)KEYSET_LINES_KEY_BYTES) != hipSuccess ||
+      hipMalloc((void**)&nolines, 4 * k.n) != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)lines, (void*)scratch, (void*)nolines})
+      if (p) (void)hipFree(p);
+    return 0;
+  }
+  for (size_t k0 = 0; k0 < k.n; k0 += chunk) {
+    const size_t cnt = std::min(chunk, k.n - k0);
+    KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), k0, cnt, (const uint8_t*)k.aff, lines, scratch, nolines);
+  }
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(scratch);
+  if (e1 != hipSuccess || e2 != hipSuccess) {
+    (void)hipFree(lines);
+    (void)hipFree(nolines);
+    return fail(BLSGPU_E_HIP, std::string("k_keyset_lines: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+  }
+  k.lines = lines;
+  k.nolines = nolines;
+  k.bytes += lb + 4 * (uint64_t)k.n;
+  return 0;
+}
 int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int flags, int32_t* status, uint64_t* out_handle) try {
   if (!initialised()) return NOT_INIT();
   int rc = keyset_fmt_check(sig_group, fmt);
   if (rc) return rc;
   if (!out_handle || (n && !keys)) return fail(BLSGPU_E_ARG, "null argument");
-  if (flags & ~BLSGPU_KEYSET_TABLES) return fail(BLSGPU_E_ARG, "unknown flag");
+  if (flags & ~(BLSGPU_KEYSET_TABLES | BLSGPU_KEYSET_LINES)) return fail(BLSGPU_E_ARG, "unknown flag");
   if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 keys");
   *out_handle = 0;
   CTX_ACQUIRE(c);
@@ -4966,6 +5007,7 @@ int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int
     HIPCK(hipGetLastError());
     if (status && (rc = copy_out(c, status, k.status, 4 * n))) return rc;
     if ((flags & BLSGPU_KEYSET_TABLES) && (rc = keyset_build_tables(c, k))) return rc;
+    if ((flags & BLSGPU_KEYSET_LINES) && (rc = keyset_build_lines(c, k))) return rc;
     SYNC_FLUSH(c);
   }
   std::lock_guard<std::mutex> lk(g_keyset_mu);
@@ -4998,7 +5040,7 @@ int blsgpu_keyset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_ta
   if (rc) return rc;
   if (sig_group) *sig_group = k.sig_group;
   if (n) *n = k.n;
-  if (has_tables) *has_tables = k.table ? 1 : 0;
+  if (has_tables) *has_tables = (k.table ? BLSGPU_KEYSET_TABLES : 0) | (k.lines ? BLSGPU_KEYSET_LINES : 0);
   if (device_bytes) *device_bytes = k.bytes;
   return 0;
 }
@@ -5006,12 +5048,29 @@ API_CATCH
 
 // the indices of a call against the table: d_cidx gets idx[i] or KEYSET_SKIP, d_pre (n_sets slots, or one when d_offs is null and
 // `whole` is set: the whole call is one set) each set's precedence
+// d_walk (a set with line tables, a call that may take the keyed line kernel): one word, raised when a position names a finite
+// entry without usable rows
 static int keyset_check(Ctx* c, const KeySet& k, const uint32_t* d_idx, size_t n, const uint64_t* d_offs, size_t n_sets, uint32_t* d_cidx,
-                        unsigned long long* d_pre) {
+                        unsigned long long* d_pre, uint32_t* d_walk = nullptr) {
   HIPCK(hipMemsetAsync(d_pre, 0xff, 8 * n_sets, c->stream));
+  if (d_walk) HIPCK(hipMemsetAsync(d_walk, 0, 4, c->stream));
   if (n)
     KL(KID_KEYSET_CHECK, k_keyset_check, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_offs, n_sets, d_idx, (uint64_t)k.n, (const int32_t*)k.status, d_cidx,
-       d_pre);
+       d_pre, d_walk ? (const int32_t*)k.nolines : (const int32_t*)nullptr, d_walk);
+  return 0;
+}
+// May a one-key-per-item call of n items over set k take the keyed line kernel?  Decided from the call's shape: a set with line
+// tables (so: signatures in G1) on the lane-split path with its two-kernel Miller loop.
+static bool keyset_lines_wanted(const KeySet& k, size_t n) { return k.lines && k.sig_group == 1 && n > coop_max_items() && miller_chunk_items() != 0; }
+// ... and, after k_keyset_check with d_walk: the one word read back (as run_verify_shared_items reads k_group_lines' word) says
+// whether every named entry has rows; *table = the set's rows, or null: the call walks the keys
+static int keyset_lines_decide(Ctx* c, const KeySet& k, const uint32_t* d_walk, const uint32_t** table) {
+  uint32_t* h_walk = (uint32_t*)hsmall_take(c, 4);
+  if (!h_walk) return fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted");
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(h_walk, d_walk, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));
+  *table = *h_walk == 0 ? k.lines : nullptr;
   return 0;
 }
 // for the calls without a status vector: one set over all positions; after the call's last synchronisation *h_pre == 0 says that
@@ -5371,7 +5430,7 @@ int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx
   else total = msg_offsets[n];
   const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt), sgb = sig_size(sig_group, fmt) * n;
   rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(total) + pad256(8 * (n + 1)) + pad256(4 * n) +
-                            2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 4096);
+                            2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 256 + 4096);
   if (rc) return rc;
   c->arena_off = 0;
   const void *d_idx, *d_sigs, *d_msgs, *d_offs;
@@ -5387,16 +5446,19 @@ int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx
   int32_t* d_status = mem.take<int32_t>(4 * n);
   uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
   uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  uint32_t* d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   // one key per item: the gather is a few hundred bytes against a pairing, so the keys go to the arena, in the signatures' format
   // (run_verify_items reads both with one)
-  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre))) return rc;
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return rc;
+  const uint32_t* key_table = nullptr;
+  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_table))) return rc;
   const size_t cnt_ = n;
   KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
   if (d_keys != d_aff)
     with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
   rc = run_verify_items(c, sig_group, scheme == BLSGPU_SCHEME_AUG, d_keys, (const uint8_t*)d_sigs, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, 0,
-                        scheme_dst(sig_group, scheme), n, d_pairs, d_f, d_status, 0);
+                        scheme_dst(sig_group, scheme), n, d_pairs, d_f, d_status, 0, key_table, d_cidx);
   if (rc) return rc;
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   HIPCK(hipGetLastError());
@@ -5444,7 +5506,8 @@ static void shared_make_plan(shared_plan& p, int sg, int scheme, size_t n, size_
 // run_pairing2 (fixed_g2 = 2 for Bls12381G1Impl; two general pairs, or the groups' tables, for Bls12381G2Impl).
 static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan& p, size_t n, size_t n_groups, const uint8_t* d_pks, const uint8_t* d_sigs,
                                    int fmt, const uint64_t* d_ioffs, const uint8_t* d_msgs, const uint64_t* d_moffs, uint32_t* d_pairs, uint32_t* d_f,
-                                   int32_t* d_status) {
+                                   int32_t* d_status, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
+  // key_table / key_of (Bls12381G1Impl over a registered set with line tables): passed on to run_pairing2, all three schemes
   int rc;
   const dst_arg dst = scheme_dst(sg, scheme);
   if (p.aug) {
@@ -5454,7 +5517,7 @@ static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan
     if (!d_xmsgs) return fail(BLSGPU_E_HIP, "internal: arena too small");
     if (p.x_total)
       KL(KID_PREPARE_SHARED, k_shared_expand, dim3(blocks_for(p.x_total)), dim3(BLS_BLOCK), p.x_total, d_xoffs, n, d_ioffs, n_groups, d_moffs, d_msgs, d_xmsgs);
-    rc = run_verify_items(c, sg, 1, d_pks, d_sigs, fmt, d_xmsgs, d_xoffs, 0, dst, n, d_pairs, d_f, d_status);
+    rc = run_verify_items(c, sg, 1, d_pks, d_sigs, fmt, d_xmsgs, d_xoffs, 0, dst, n, d_pairs, d_f, d_status, 0, key_table, key_of);
     if (rc) (void)hipStreamSynchronize(c->stream);      // the upload above reads p.x_offs
     return rc;
   }
@@ -5492,7 +5555,7 @@ static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan
        d_status, table ? 1 : 0, table ? d_group : (uint32_t*)nullptr);
   });
   HIPCK(hipGetLastError());
-  return run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, table ? d_table : nullptr, table ? d_group : nullptr);
+  return run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, table ? d_table : nullptr, table ? d_group : nullptr, sg == 1 ? key_table : nullptr, key_of);
 }
 // the offsets of a shared-message call, read and checked; n = the item count
 static int shared_read_offsets(const uint64_t* item_offsets, const uint64_t* msg_offsets, size_t n_groups, std::vector<uint64_t>& ioffs,
@@ -5570,7 +5633,7 @@ int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32
   shared_make_plan(plan, sig_group, scheme, n, n_groups, ioffs, moffs);
   const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt), sgb = sig_size(sig_group, fmt) * n;
   if ((rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(total) + 2 * pad256(8 * (n_groups + 1)) +
-                                 pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + plan.ws_bytes + 8192)))
+                                 pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + plan.ws_bytes + 256 + 8192)))
     return rc;
   c->arena_off = 0;
   const void *d_idx, *d_sigs, *d_msgs;
@@ -5587,18 +5650,21 @@ int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32
   int32_t* d_status = mem.take<int32_t>(4 * n);
   uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
   uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  uint32_t* d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   auto drain = [&](int r) {
     (void)hipStreamSynchronize(c->stream);      // the uploads read ioffs / moffs
     return r;
   };
-  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre))) return drain(rc);
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
+  const uint32_t* key_table = nullptr;
+  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_table))) return drain(rc);
   const size_t cnt_ = n;
   KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
   if (d_keys != d_aff)
     with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
   rc = run_verify_shared_items(c, sig_group, scheme, plan, n, n_groups, d_keys, (const uint8_t*)d_sigs, fmt, d_ioffs, (const uint8_t*)d_msgs, d_moffs, d_pairs, d_f,
-                               d_status);
+                               d_status, key_table, d_cidx);
   if (rc) return drain(rc);
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));

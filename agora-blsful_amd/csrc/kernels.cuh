@@ -242,6 +242,10 @@ __global__ void k_lines2s(size_t n, size_t first, size_t count, const uint32_t* 
 // table + (group_of[i] 68 + e) 4 FP_NL
 __global__ void k_lines2s_shared(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* status, uint32_t* lines, size_t lanes,
                                  const uint32_t* table, const uint32_t* group_of);
+// the keyed form of the registered key sets (keyset.cuh, Bls12381G1Impl): pair 0's G2 member is the key at position key_of[i] of a set
+// with line tables, its normalised rows at key_table + (key_of[i] 68 + e) 4 FP_NL; pair 1's is -[c] g2: no G2 point is walked
+__global__ void k_lines2s_keyed(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* status, uint32_t* lines, size_t lanes,
+                                const uint32_t* key_table, const uint32_t* key_of);
 __global__ void k_millerf2s(size_t n, size_t first, size_t count, const int32_t* status, const uint32_t* lines, size_t lanes, uint32_t* fws);
 __global__ void k_finalexp2s(size_t n, size_t first, size_t count, const uint32_t* fws, uint32_t* vp, size_t lanes, int32_t* status);
 __global__ void k_finalexp_seg(int seg, size_t n, size_t first, size_t count, const uint32_t* fws, uint32_t* vp, size_t lanes, int32_t* status);
@@ -1539,6 +1543,72 @@ k_lines2s_shared(size_t n, size_t first, size_t count, const uint32_t* pairs, co
     if (miller_entry_is_add(e)) lines_step_group<1>(sh, pairs, n, i, table, goff, lines, lanes, t, e);
     else lines_step_group<0>(sh, pairs, n, i, table, goff, lines, lanes, t, e);
   }
+}
+#endif
+
+#if defined(BLS_TU_LINES)
+// The form with BOTH lines read from tables (registered key sets with BLSGPU_KEYSET_LINES, Bls12381G1Impl: keyset.cuh).  Pair 0 is
+// (H'(m), pk) with pk the set's entry key_of[i], whose normalised rows k_keyset_lines left in key_table when the set was created;
+// pair 1 is (sig, -[c] g2) with the constant rows G2NEGC_LINES_N.  Nothing is doubled or added on the curve: an entry costs two
+// row loads, the two c x products and the sparse merge with both w^3 coefficients in Fp (tower.cuh lines_merge_yy).  The only
+// state is the two G1 points, in LDS as k_lines2s keeps them (x on the even lane, y on the odd one): 28 dwords per lane.  The key
+// table's base stays wave-uniform and the row is a 32-bit per-lane WORD offset koff + e 4 FP_NL with koff = key 68 4 FP_NL (the
+// host keeps the table below 2^32 bytes), as in k_lines2s_shared; the constant row is a wave-uniform pointer.  A step function
+// of its own, arguments scalars only: lines_step_fn, lines_step_group and the kernels that call them stay what they are.
+#define LK_P0 0
+#define LK_P1 FP_NL
+#define LK_WORDS (2 * FP_NL)
+static __device__ __noinline__ void lines_step_keyed(lds_u32* sh, const uint32_t* key_table, uint32_t koff, const uint32_t* crow, uint32_t* lines,
+                                                     size_t lanes, uint32_t t, int e) {
+  hfp2 a0, a2, b0, b2, c;
+  fp x, ya, yb;
+  const uint32_t lo = lane_hi() ? FP_NL : 0;
+  {
+    gc_u32* tr = uni_global(key_table);
+    const uint32_t o = koff + uni_u32((uint32_t)e) * (4 * FP_NL) + lo;
+#pragma unroll
+    for (int k = 0; k < FP_NL; k++) {
+      a0.v.l[k] = (int32_t)g_ld(tr, o + k);
+      c.v.l[k] = (int32_t)g_ld(tr, o + 2 * FP_NL + k);
+    }
+  }
+  ls_ld_coord(x, sh, LK_P0, false);
+  fp2_mul_fp(a2, c, x);
+  {
+    gc_u32* tr = uni_global(crow);
+#pragma unroll
+    for (int k = 0; k < FP_NL; k++) {
+      b0.v.l[k] = (int32_t)g_ld(tr, lo + k);
+      c.v.l[k] = (int32_t)g_ld(tr, lo + 2 * FP_NL + k);
+    }
+  }
+  ls_ld_coord(x, sh, LK_P1, false);
+  fp2_mul_fp(b2, c, x);
+  ls_ld_coord(ya, sh, LK_P0, true);
+  ls_ld_coord(yb, sh, LK_P1, true);
+  line5_t<hfp2> L;
+  lines_merge_yy(L, a0, a2, ya, b0, b2, yb);
+  line5_st(lines, lanes, t, e, L);
+}
+__global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES) __attribute__((disable_tail_calls))
+k_lines2s_keyed(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* status, uint32_t* lines, size_t lanes, const uint32_t* key_table,
+                const uint32_t* key_of) {
+  const uint32_t t = blockIdx.x * BLS_BLOCK + threadIdx.x;
+  const size_t j = t >> 1;
+  if (j >= count) return;
+  const size_t i = first + j;                          // the item's index in the BATCH: key_of and the pairs are indexed by it
+  if (status[i] != BLS_OK) return;                     // before any table read: a position without a usable entry never has status OK
+  __shared__ uint32_t lsh[LK_WORDS * BLS_BLOCK];
+  lds_u32* sh = lds_column(lsh);
+  {
+    fp p;
+    ws_ld_fp(p, pairs, n, i, lane_hi() ? W1 : 0);                   // pair 0's G1 point, the uncleared hash: x on the even lane, y on the odd lane
+    ls_st(sh, LK_P0, p);
+    ws_ld_fp(p, pairs, n, i, 3 * W2 + (lane_hi() ? W1 : 0));        // pair 1's G1 point, the signature
+    ls_st(sh, LK_P1, p);
+  }
+  const uint32_t koff = key_of[i] * (uint32_t)(MILLER_ENTRIES * 4 * FP_NL);
+  for (int e = 0; e < MILLER_ENTRIES; e++) lines_step_keyed(sh, key_table, koff, G2NEGC_LINES_N[e], lines, lanes, t, e);
 }
 #endif
 

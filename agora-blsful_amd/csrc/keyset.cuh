@@ -9,9 +9,12 @@
 //   * keyset_digit: the signed recoding of a sub-scalar, digits in [-7, 8], the carry of the top window leaving as one more digit
 //     (0 or 1);
 //   * keyset_pre_key / keyset_pre_status: what k_keyset_check leaves per set -- an out-of-range index first, then the creation
-//     status of the first invalid entry in input order -- packed so that one atomicMin per position decides it.
+//     status of the first invalid entry in input order -- packed so that one atomicMin per position decides it;
+//   * the line table of a G2 key (BLSGPU_KEYSET_LINES): the 68 normalised Miller rows of verify_shared.cuh, derived once at
+//     creation, and the rule that says whether a set may have them.
 #pragma once
 #include "multi_batch.cuh"
+#include "verify_shared.cuh"
 
 #define KEYSET_W 4
 #define KEYSET_ROW 8                      // positive digits of a window: 1 .. 2^(W - 1)
@@ -55,6 +58,40 @@ BLS_FN uint64_t keyset_pre_key(bool out_of_range, uint64_t pos_in_set, int32_t e
 }
 BLS_FN int32_t keyset_pre_status(uint64_t key) { return key == 0 ? KEYSET_E_ARG : (int32_t)(key & 0xff); }
 
+// ---- line tables per key (Bls12381G1Impl: keys in G2).  One verification is e(H'(m), pk) e(sig, -[c] g2) = 1, and a registered
+// key is known long before any signature: its rows (n0, c)_e = (l0 / h, g / h)_e are group_lines_build's, SHARED_TABLE_WORDS words
+// per entry in the *_LINES_N layout, entry k's row e at word (k 68 + e) 4 FP_NL.  The line kernel (kernels.cuh k_lines2s_keyed)
+// reaches a row by a 32-bit BYTE offset from a wave-uniform base, so the whole table stays below 2^32 bytes: 281,970 keys.
+#define KEYSET_LINES_KEY_BYTES ((uint64_t)SHARED_TABLE_WORDS * 4)
+#define KEYSET_NOLINES_EMPTY 1            // the identity or an invalid entry: no verification under it reaches the line kernel
+#define KEYSET_NOLINES_FINITE 2           // a finite point whose walk met h = 0 (no key of order r; trusted raw input only)
+// may a set of n_keys keys have line tables?  other_bytes: its fixed-base tables, which share the cap of cap_mib MiB (a host rule:
+// the library and the host harness call it)
+static inline bool keyset_lines_fit(uint64_t n_keys, uint64_t other_bytes, uint64_t cap_mib) {
+  if (n_keys == 0 || n_keys > 0xffffffffull / KEYSET_LINES_KEY_BYTES) return false;
+  return n_keys * KEYSET_LINES_KEY_BYTES + other_bytes <= cap_mib << 20;
+}
+BLS_FN void keyset_raw_hfp2(hfp2& r, const uint32_t* w) {
+#if defined(__HIPCC__)
+  fp_from_raw(r.v, w + (lane_hi() ? 12 : 0));
+#else
+  fp_from_raw(r.c[0], w);
+  fp_from_raw(r.c[1], w + 12);
+#endif
+}
+// the rows of the entry whose stored record (RAW_AFFINE G2, 48 words, all-zero for the identity and for an invalid entry) is rec,
+// through io (group_lines_build's); 0 when they are usable, else KEYSET_NOLINES_*
+template <class IO>
+BLS_FN int keyset_lines_entry(const uint32_t* rec, const IO& io) {
+  bool inf = true;
+  for (int k = 0; k < 48; k++) inf = inf && rec[k] == 0;
+  hfp2 qx, qy;
+  keyset_raw_hfp2(qx, rec);
+  keyset_raw_hfp2(qy, rec + 24);
+  const bool ok = group_lines_build(qx, qy, inf, io);
+  return ok ? 0 : inf ? KEYSET_NOLINES_EMPTY : KEYSET_NOLINES_FINITE;
+}
+
 #if defined(__HIPCC__)
 #include "kernels.cuh"
 // ---- kernels (tu_keyset1.hip: the group-independent ones and G1 keys, tu_keyset2.hip: G2 keys)
@@ -65,10 +102,14 @@ __global__ void k_keyset_seal(size_t n, const uint8_t* pts, int fmt, const int32
 // (POINTS records per lane each), one inversion per lane, the affine records into table
 template <int G>
 __global__ void k_keyset_build(size_t k0, size_t cnt, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws, uint8_t* table);
+// create, with line tables (G2 keys): one lane pair per key of [k0, k0 + cnt) runs keyset_lines_entry into the key's rows of
+// `table`; scratch: SHARED_TABLE_WORDS words per key of the CHUNK; nolines[k] = 0 or KEYSET_NOLINES_*
+__global__ void k_keyset_lines(size_t k0, size_t cnt, const uint8_t* recs, uint32_t* table, uint32_t* scratch, int32_t* nolines);
 // per position: the index against the table's size and the entry's status; cidx[i] = idx[i] or KEYSET_SKIP, pre[set] by atomicMin
-// (offs == nullptr: every position is its own set)
+// (offs == nullptr: every position is its own set).  nolines != nullptr (a set with line tables): *walk |= 1 when a position names
+// a finite entry without usable rows (the caller clears the word before the launch)
 __global__ void k_keyset_check(size_t n, const uint64_t* offs, size_t n_sets, const uint32_t* idx, uint64_t n_keys, const int32_t* kstatus,
-                               uint32_t* cidx, unsigned long long* pre);
+                               uint32_t* cidx, unsigned long long* pre, const int32_t* nolines, uint32_t* walk);
 __global__ void k_keyset_fin(size_t n_sets, const unsigned long long* pre, int32_t* status);
 // dst record i = src record cidx[i] (words 32-bit words each; zeros for KEYSET_SKIP); legacy: the Dash header transcode of byte 0
 __global__ void k_keyset_gather(size_t n, size_t words, const uint32_t* cidx, const uint32_t* src, int legacy, uint32_t* dst);

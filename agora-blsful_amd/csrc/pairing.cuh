@@ -343,6 +343,30 @@ BLS_FN void miller_loop_fixed_g2_merged(ACC& f, const g1_aff& P0, const aff<F2>&
   }
   acc_finish(f);
 }
+// ... and with BOTH G2 arguments given as normalised tables (a registered key's rows and a constant's; what kernels.cuh
+// k_lines2s_keyed + k_millerf2s compute): nothing is walked, every step is two row evaluations and lines_merge_yy
+template <class F2, class ACC>
+BLS_FN void miller_loop_tables_merged(ACC& f, const g1_aff& P0, const uint32_t* rows0, const g1_aff& P1, const uint32_t (*rows1)[4 * FP_NL]) {
+  line5_t<F2> L;
+  F2 a0, a2, b0, b2, t;
+  for (int e = 0; e < MILLER_ENTRIES; e++) {
+    const uint32_t* r0 = rows0 + (size_t)e * (4 * FP_NL);
+    fp2_load(a0, r0);
+    fp2_load(t, r0 + 2 * FP_NL);
+    fp2_mul_fp(a2, t, P0.x);
+    fp2_load(b0, rows1[e]);
+    fp2_load(t, rows1[e] + 2 * FP_NL);
+    fp2_mul_fp(b2, t, P1.x);
+    lines_merge_yy(L, a0, a2, P0.y, b0, b2, P1.y);
+    if (e == 0) {
+      acc_set_line5(f, L);
+    } else {
+      if (!miller_entry_is_add(e)) acc_sqr(f);
+      acc_mul_line5(f, L);
+    }
+  }
+  acc_finish(f);
+}
 template <class ACC, class F2>
 BLS_FN void miller_loop2_merged(ACC& f, const g1_aff* P, const aff<F2>* Q) {
   g2_hom_t<F2> T0, T1;

@@ -677,6 +677,36 @@ BLS_FN void lines_merge_y(line5_t<F2>& L, const F2& a0, const F2& a2, const F2& 
   fp2_sub(m, m, p33);
   fp2_reduce(L.c5, m);
 }
+// ... and with BOTH w^3 coefficients in Fp (two normalised lines: the rows of a registered key and of the constant pair,
+// kernels.cuh k_lines2s_keyed): a3 b3 = ya yb is ONE Fp product, and c3 = a0 yb + b0 ya, c5 = a2 yb + b2 ya are Fp2-by-Fp products
+// with nothing to subtract.  c0, c2, c4 as above; every coefficient leaves as lines_merge_y leaves it.
+template <class F2>
+BLS_FN void lines_merge_yy(line5_t<F2>& L, const F2& a0, const F2& a2, const fp& ya, const F2& b0, const F2& b2, const fp& yb) {
+  F2 p00, p22, p33, s, t, m;
+  fp yy;
+  fp2_mul(p00, a0, b0);
+  fp2_mul(p22, a2, b2);
+  fp_mul(yy, ya, yb);
+  fp2_from_fp(p33, yy);
+  fp2_mul_xi(m, p33);
+  fp2_add(m, m, p00);
+  fp2_reduce(L.c0, m);       // c0 = a0 b0 + xi ya yb
+  fp2_add(s, a0, a2);
+  fp2_add(t, b0, b2);
+  fp2_mul(m, s, t);
+  fp2_sub(m, m, p00);
+  fp2_sub(m, m, p22);
+  fp2_reduce(L.c2, m);       // c2 = a0 b2 + a2 b0
+  L.c4 = p22;
+  fp2_mul_fp(s, a0, yb);
+  fp2_mul_fp(t, b0, ya);
+  fp2_add(m, s, t);
+  fp2_reduce(L.c3, m);       // c3 = a0 yb + b0 ya
+  fp2_mul_fp(s, a2, yb);
+  fp2_mul_fp(t, b2, ya);
+  fp2_add(m, s, t);
+  fp2_reduce(L.c5, m);       // c5 = a2 yb + b2 ya
+}
 // f * (c0 + c2 w^2 + c3 w^3 + c4 w^4 + c5 w^5): L0 = (c0, c2, c4), L1 = (0, c3, c5) in Fp6; 6 + 5 + 6 Fp2 multiplications
 template <class F2>
 BLS_FN void fp12_mul_by_line5_body(fp12_t<F2>& f, const line5_t<F2>& L) {

@@ -3,6 +3,7 @@
 // keys, i.e. Bls12381G1Impl).
 //   k_keyset_seal           : create: the stored affine record and Modern bytes of every entry
 //   k_keyset_build          : create: the fixed-base table, one lane per key, ONE inversion per lane
+//   k_keyset_lines          : create: the line table of G2 keys, one lane pair per key, ONE inversion per key
 //   k_keyset_check          : every position's index and entry status, once; the sanitised indices and each set's precedence
 //   k_keyset_fin            : the precedence over the statuses of the verification tail
 //   k_keyset_gather         : records by index (affine records, compressed bytes with the Legacy header transcode, statuses)
@@ -37,7 +38,8 @@ __device__ __forceinline__ void ks_raw(uint32_t* w, const fp2& a) { fp2_to_raw(w
 
 #if BLS_TU_KEYSET == 1
 __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_check(size_t n, const uint64_t* offs, size_t n_sets, const uint32_t* idx, uint64_t n_keys,
-                                                          const int32_t* kstatus, uint32_t* cidx, unsigned long long* pre) {
+                                                          const int32_t* kstatus, uint32_t* cidx, unsigned long long* pre, const int32_t* nolines,
+                                                          uint32_t* walk) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const size_t s = offs ? ragged_set_of(offs, n_sets, i) : i;
@@ -47,6 +49,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_check(size_t n, const uint
   cidx[i] = oob ? KEYSET_SKIP : ix;
   const uint64_t key = keyset_pre_key(oob, offs ? i - offs[s] : 0, st);
   if (key != KEYSET_PRE_NONE) atomicMin(&pre[s], (unsigned long long)key);
+  if (nolines && !oob && nolines[ix] == KEYSET_NOLINES_FINITE) atomicOr(walk, 1u);
 }
 __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_fin(size_t n_sets, const unsigned long long* pre, int32_t* status) {
   const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -174,6 +177,18 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_build(size_t k0, size_t cn
     ks_st(t + C, m.y);
   }
 }
+
+#if BLS_TU_KEYSET == 2
+__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_lines(size_t k0, size_t cnt, const uint8_t* recs, uint32_t* table, uint32_t* scratch, int32_t* nolines) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t l = t >> 1;                                  // both lanes of a pair are inside or outside: BLS_BLOCK is even
+  if (l >= cnt) return;
+  const size_t k = k0 + l, lane = lane_hi() ? FP_NL : 0;
+  const group_lines_io io = {table + k * (size_t)SHARED_TABLE_WORDS + lane, scratch + l * (size_t)SHARED_TABLE_WORDS + lane};
+  const int no = keyset_lines_entry((const uint32_t*)(recs + k * 192), io);
+  if (!lane_hi()) nolines[k] = no;
+}
+#endif
 
 #if BLS_TU_KEYSET == 1
 // one lane per strip

@@ -75,22 +75,7 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_shared_expand(size_t total, const
 #endif
 
 #if BLS_TU_VERIFY_SHARED == 2
-// where k_group_lines keeps a group's values: this lane's component (real on the even lane, imaginary on the odd one) of the two
-// Fp2 of entry e's table row (slots 0, 1) and scratch row (slots 2, 3)
-struct group_lines_io {
-  uint32_t* row;
-  uint32_t* scr;
-  __device__ __forceinline__ uint32_t* at(int e, int slot) const {
-    return (slot < 2 ? row : scr) + (size_t)e * SHARED_ROW_WORDS + (slot & 1) * (2 * FP_NL);
-  }
-  __device__ __forceinline__ void st(int e, int slot, const hfp2& v) const { fp_store(at(e, slot), v.v); }
-  __device__ __forceinline__ void ld(hfp2& v, int e, int slot) const { fp_load(v.v, at(e, slot)); }
-  __device__ __forceinline__ void st_canon(int e, int slot, const hfp2& v) const {
-    fp t;
-    fp_canon(t, v.v);
-    fp_store(at(e, slot), t);
-  }
-};
+// (group_lines_io, where the lane pair keeps a group's values: verify_shared.cuh)
 __global__ void __launch_bounds__(BLS_BLOCK) k_group_lines(size_t n_groups, const uint8_t* group_aff, uint32_t* table, uint32_t* scratch, int32_t* flags) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t g = t >> 1;                                  // both lanes of a pair are inside or outside: BLS_BLOCK is even

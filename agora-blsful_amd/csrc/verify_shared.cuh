@@ -120,6 +120,23 @@ BLS_FN uint64_t shared_expand_src(const uint64_t* x_offs, size_t n_items, const 
 
 #if defined(__HIPCC__)
 #include "kernels.cuh"
+// where a lane pair that runs group_lines_build (k_group_lines; tu_keyset.inc k_keyset_lines) keeps a point's values: this lane's
+// component (real on the even lane, imaginary on the odd one) of the two Fp2 of entry e's table row (slots 0, 1) and scratch row
+// (slots 2, 3)
+struct group_lines_io {
+  uint32_t* row;
+  uint32_t* scr;
+  __device__ __forceinline__ uint32_t* at(int e, int slot) const {
+    return (slot < 2 ? row : scr) + (size_t)e * SHARED_ROW_WORDS + (slot & 1) * (2 * FP_NL);
+  }
+  __device__ __forceinline__ void st(int e, int slot, const hfp2& v) const { fp_store(at(e, slot), v.v); }
+  __device__ __forceinline__ void ld(hfp2& v, int e, int slot) const { fp_load(v.v, at(e, slot)); }
+  __device__ __forceinline__ void st_canon(int e, int slot, const hfp2& v) const {
+    fp t;
+    fp_canon(t, v.v);
+    fp_store(at(e, slot), t);
+  }
+};
 // ---- kernels (tu_verify_shared1.hip: Bls12381G1Impl and the group-independent one, tu_verify_shared2.hip: Bls12381G2Impl)
 // the n_groups hash outputs (RAW_PROJ, group SG) -> RAW_AFFINE records, all-zero for the identity: one inversion per GROUP
 template <int SG>

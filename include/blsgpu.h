@@ -547,10 +547,20 @@ int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t
  * 29 KB per key) that turn a scalar multiplication of an entry into about 64 mixed additions and no doubling; when they would
  * exceed BLSGPU_KEYSET_TABLE_MB MiB (default 4096) or the device has no room, the set is created without them and `has_tables`
  * reports 0.  Tables never change a result.
+ * flags & BLSGPU_KEYSET_LINES (Bls12381G1Impl, keys in G2; accepted and without effect for sig_group 2, whose keys have no lines)
+ * also derives every key's 68 normalised Miller-loop rows (15,232 bytes per key; the reference's G2Prepared::from(pk), kept instead
+ * of recomputed per call): blsgpu_verify_indexed_batch and blsgpu_verify_shared_indexed_batch on the lane-split path (more than
+ * BLSGPU_COOP_MAX items) then read rows where they walked the key, under every scheme.  The lines are not built, and the set works
+ * without them, when they would not stay below 2^32 bytes (more than 281,970 keys), when together with the fixed-base tables they
+ * would exceed BLSGPU_KEYSET_TABLE_MB MiB, or when the device has no room.  A call that names a finite entry whose rows are
+ * unusable (no key of order r; raw input only) walks the keys of all its items.  Line tables never change a status.
+ * info: *has_tables is the mask of what was built -- bit 0 (BLSGPU_KEYSET_TABLES) the fixed-base tables, bit 1 (BLSGPU_KEYSET_LINES)
+ * the line tables -- so a caller that created the set with flags 0 or 1 reads the 0 or 1 it read before; device_bytes counts both.
  * get: entries idx[0 .. count) in any format, with their creation statuses (status may be NULL); an invalid entry leaves as the
  * identity.  mul: out[i] = scalars[i] * key[idx[i]] as RAW_PROJ (scalars: 32 bytes little-endian each, any value below 2^256,
  * reduced modulo r as blsgpu_msm_* does); the identity and invalid entries give the identity (Z = 0).  Both return BLSGPU_E_ARG when an index is not below the set's size. */
 #define BLSGPU_KEYSET_TABLES 1
+#define BLSGPU_KEYSET_LINES 2
 int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int flags, int32_t* status, uint64_t* out_handle);
 int blsgpu_keyset_destroy(uint64_t handle);
 int blsgpu_keyset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_tables, uint64_t* device_bytes);

@@ -10,7 +10,14 @@ Every input lives on the device (TensorOps).  Per shape, indices are drawn at ra
   (c) the indexed entry point on a key set with tables (the multi shapes never multiply, so (c) only shows that tables cost nothing);
   (d) blsgpu_keyset_create from RAW_PROJ device memory, with and without tables.
 On a build without key sets (the parent commit) only (a) runs: the tool skips what the library does not export.  The verdicts are
-mostly INVALID_SIGNATURE, which costs the same as OK.  Prints one JSON line per shape and writes them all to --out."""
+mostly INVALID_SIGNATURE, which costs the same as OK.  Prints one JSON line per shape and writes them all to --out.
+
+--lines [--out profiles/keyset_lines_bench.json]: the per-key line tables (BLSGPU_KEYSET_LINES) instead -- one key per item,
+Bls12381G1Impl, Basic: blsgpu_verify_batch / blsgpu_verify_indexed_batch at 8,192, 65,536 and 262,144 items and
+blsgpu_verify_shared_batch / blsgpu_verify_shared_indexed_batch at 64 x 1,024 and 400 x 400, with (a) keys by value, (b) indexed over a
+set without lines, (c) indexed over a set with lines; EVERY cell three medians of --reps calls (their range is the cell's spread),
+the line kernel's time per call from the profile, and blsgpu_keyset_create with and without the flag.  A library that refuses the
+flag (the parent commit) runs (a) and (b) only."""
 import argparse
 import json
 import os
@@ -39,8 +46,75 @@ def median_ms(run, reps, sync):
     return statistics.median(ts) * 1e3
 
 
+LINES_SHAPES = [('verify', 8192, 1), ('verify', 65536, 1), ('verify', 262144, 1), ('shared', 64, 1024), ('shared', 400, 400)]
+
+
+def lines_bench(a, api, ops, torch, dev, sync):
+    rng = random.Random(2027)
+    ks = [rng.randrange(1, R) for _ in range(a.table)]
+    pks = api.sign_batch(1, api.BASIC, ks, [b''] * a.table)[0]
+    sigs = api.sign_batch(1, api.BASIC, ks[:SIG_POOL], [b'bench'] * SIG_POOL)[1]
+    pk_pool = torch.tensor(list(b''.join(pks)), dtype=torch.uint8, device=dev).view(a.table, -1)
+    sig_pool = torch.tensor(list(b''.join(sigs)), dtype=torch.uint8, device=dev).view(SIG_POOL, -1)
+    sync()
+    made, create = {}, {}
+    for lines in (False, True):
+        ts = []
+        try:
+            for _ in range(3):
+                if lines in made:
+                    made.pop(lines).close()
+                t0 = time.perf_counter()
+                made[lines] = api.KeySet.create_device(1, pk_pool.data_ptr(), a.table, api.FMT_RAW_PROJ, lines=lines)
+                ts.append((time.perf_counter() - t0) * 1e3)
+        except api.BlsGpuRuntimeError as e:                                  # a library without the flag
+            create['with lines'] = 'refused: %s' % e
+            continue
+        create['with lines' if lines else 'without lines'] = dict(ms=round(statistics.median(ts), 3), first_ms=round(ts[0], 3), **made[lines].info())
+    rows = [{'table_entries': a.table, 'create': create}]
+    print(json.dumps(rows[0]), flush=True)
+    shapes = [LINES_SHAPES[int(i)] for i in a.shapes.split(',')] if a.shapes else LINES_SHAPES
+    for kind, n_groups, per in shapes:
+        n = n_groups * per
+        gen = torch.Generator(device=dev).manual_seed(n + n_groups)
+        sel = torch.randint(0, a.table, (n,), device=dev, generator=gen)
+        pks_t = pk_pool[sel].reshape(-1).contiguous()
+        idx_t = sel.to(torch.int32).contiguous()
+        sigs_t = sig_pool[torch.randint(0, SIG_POOL, (n,), device=dev, generator=gen)].reshape(-1).contiguous()
+        moffs, mblob = api._offsets([b'attestation %06d' % s for s in range(n_groups)])
+        msgs_t = torch.tensor(list(mblob), dtype=torch.uint8, device=dev)
+        moffs_t = torch.tensor(list(moffs), dtype=torch.int64, device=dev)
+        if kind == 'verify':
+            by_value = lambda: ops.verify_batch(1, api.BASIC, pks_t, sigs_t, msgs_t, moffs_t, n)
+            indexed = lambda kset: (lambda: ops.verify_indexed_batch(kset, api.BASIC, idx_t, sigs_t, msgs_t, moffs_t, n))
+        else:
+            ioffs_t = torch.arange(0, n + 1, per, dtype=torch.int64, device=dev)
+            by_value = lambda: ops.verify_shared_batch(1, api.BASIC, pks_t, sigs_t, ioffs_t, n_groups, msgs_t, moffs_t, n)
+            indexed = lambda kset: (lambda: ops.verify_shared_indexed_batch(kset, api.BASIC, idx_t, sigs_t, ioffs_t, n_groups, msgs_t, moffs_t, n))
+        row = {'kind': kind, 'shape': 'Bls12381G1Impl Basic', 'groups': n_groups, 'items_per_group': per, 'items': n, 'reps': a.reps}
+        want = by_value().cpu().tolist()
+        cells = [('a_by_value', by_value)] + [(tag, indexed(made[lines])) for tag, lines in (('b_indexed', False), ('c_indexed_lines', True)) if lines in made]
+        for tag, run in cells:
+            m3 = [median_ms(run, a.reps, sync) for _ in range(3)]
+            row[tag + '_ms'] = [round(x, 3) for x in m3]
+            row[tag + '_spread_ms'] = round(max(m3) - min(m3), 3)
+            row[tag + '_statuses_match'] = run().cpu().tolist() == want
+            api.profile_enable(True)
+            run()
+            row[tag + '_kernel_ms'] = {k: round(v[0], 3) for k, v in api.profile_read().items() if v[0] >= 0.01}
+            api.profile_enable(False)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    for kset in made.values():
+        kset.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--lines', action='store_true')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--table', type=int, default=16384)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'keyset_bench.json'))
@@ -52,6 +126,10 @@ def main():
     dev = torch.device('cuda', 0)
     ops = api.TensorOps(dev)
     sync = torch.cuda.synchronize
+    if a.lines:
+        if a.out.endswith('keyset_bench.json'):
+            a.out = os.path.join(ROOT, 'profiles', 'keyset_lines_bench.json')
+        return lines_bench(a, api, ops, torch, dev, sync)
     have = hasattr(api, 'KeySet')                                            # the parent commit has no key sets: (a) only
     rng = random.Random(2026)
     pools, sets, create = {}, {}, {}
