@@ -40,7 +40,7 @@ EXPORTS = [
     'blsgpu_aggregate_partial', 'blsgpu_fp12_product_is_one', 'blsgpu_core_verify', 'blsgpu_deserialize', 'blsgpu_pop_verify_batch', 'blsgpu_aggregate_secure',
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
-    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_coop_pairing', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
@@ -163,6 +163,7 @@ def load_library(path=None):
         lib.blsgpu_debug_field_op_shape.argtypes = [ci] + [ctypes.POINTER(ctypes.c_int)] * 5
         lib.blsgpu_debug_field_op.argtypes = [ci, i32p, sz, ci, i32p]
         lib.blsgpu_debug_millerf.argtypes = [i32p, sz, i32p, i32p]
+        lib.blsgpu_debug_coop_pairing.argtypes = [ci, ci, i32p, sz, i32p, i32p]
         lib.blsgpu_verify_batch_grouped.argtypes = [ci, ci, vp, vp, u8p, vp, sz, ci, ctypes.c_uint64, i32p]
         lib.blsgpu_signatures_from_tagged.argtypes = [ci, u8p, sz, u8p, vp, i32p]
         lib.blsgpu_signatures_to_tagged.argtypes = [ci, u8p, vp, sz, ci, u8p]
@@ -1068,6 +1069,31 @@ def debug_millerf(tables, status=None):
     st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
     out = (ctypes.c_int32 * max(168 * n, 1))()
     _check(lib.blsgpu_debug_millerf(ctypes.cast(arr, ctypes.c_void_p), n, ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+    o = list(out)
+    return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n)]
+
+
+COOP_SENTINEL = 0xa5a5a5a5 - (1 << 32)       # BLSGPU_DEBUG_COOP_SENTINEL as a signed limb
+
+
+def debug_coop_pairing(mode, fixed_g2, items, status=None):
+    """The wave-cooperative pairing kernels on caller-supplied operands.  items: per item twelve limb vectors -- modes 0 and 1: P.x, P.y,
+    Q.x.c0, Q.x.c1, Q.y.c0, Q.y.c1 of pair 0, then of pair 1; mode 2: an Fp12 in tower order.  mode 0 (k_pairing_coop_easy) returns per
+    item the twelve limb vectors of the easy-part value in tower order (every limb COOP_SENTINEL for an item whose status is not OK);
+    modes 1 (k_pairing_coop) and 2 (k_finalexp_coop) return the statuses."""
+    lib = init()
+    n = len(items)
+    flat = []
+    for vecs in items:
+        assert len(vecs) == 12 and all(len(v) == 14 for v in vecs)
+        for v in vecs:
+            flat += v
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
+    out = (ctypes.c_int32 * max(168 * n, 1))()
+    _check(lib.blsgpu_debug_coop_pairing(mode, fixed_g2, ctypes.cast(arr, ctypes.c_void_p), n, ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+    if mode != 0:
+        return list(st[:n])
     o = list(out)
     return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n)]
 

@@ -3511,7 +3511,8 @@ int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t
   if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
   const dim3 grid(blocks_for((size_t)s->lanes * n)), block(BLS_BLOCK);
 #define DBG_LAUNCH(kern) KL(KID_DEBUG_OPS, kern, grid, block, op, n, reps, (const int32_t*)d_in, rec_in, d_out, rec_out)
-  if (s->lanes == 1) DBG_LAUNCH(k_dbg_fp1);
+  if (s->lanes == 64) DBG_LAUNCH(k_dbg_coop);      // one workgroup per item: blocks_for(64 n) = n
+  else if (s->lanes == 1) DBG_LAUNCH(k_dbg_fp1);
   else if (op < DBG_F12_SH_SQR) DBG_LAUNCH(k_dbg_fp2s);
   else if (op < DBG_CYC_C_SQR) DBG_LAUNCH(k_dbg_f12acc);
   else if (op < DBG_F12_POW_X) DBG_LAUNCH(k_dbg_cyc);
@@ -3564,6 +3565,60 @@ int blsgpu_debug_millerf(const int32_t* lines, size_t n, const int32_t* status, 
     for (size_t w = 0; w < WS_F_WORDS; w++) out_f12[i * WS_F_WORDS + w] = (int32_t)f[w * n + i];
   SYNC_FLUSH(c);
   return 0;
+}
+API_CATCH
+
+/* Self-test hook of the wave-cooperative pairing kernels on caller-supplied pairs (include/blsgpu.h).  pairs: n x twelve limb vectors
+ * (P.x, P.y, Q.x.c0, Q.x.c1, Q.y.c0, Q.y.c1 of pair 0, then of pair 1; reduced form), written into a pair workspace in the layout
+ * run_pairing2 reads: word w = 14 * vector + limb of item i at pairs_ws[w * n + i].  The kernels are launched exactly as
+ * run_pairing2 / run_f12_product_verdict launch them. */
+int blsgpu_debug_coop_pairing(int mode, int fixed_g2, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
+  if (!initialised()) return NOT_INIT();
+  if (n == 0) return 0;
+  if (!in || !status || mode < 0 || mode > 2 || fixed_g2 < 0 || fixed_g2 > 2 || n > 4096 || (mode == 0 && !out_f12) || is_device_ptr(in) || is_device_ptr(status) ||
+      is_device_ptr(out_f12))
+    return fail(BLSGPU_E_ARG, "bad argument");
+  CTX_ACQUIRE(c);
+  const size_t rec = mode == 2 ? WS_F_WORDS : WS_PAIRS_WORDS;       // words per item of the input workspace
+  int rc = arena_reserve(c, pad256(rec * 4 * n) + pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  std::vector<uint32_t> h(rec * n);
+  for (size_t i = 0; i < n; i++)
+    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
+  const void *d_in, *d_st;
+  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
+  uint32_t* d_ws = (uint32_t*)d_in;
+  int32_t* d_status = (int32_t*)d_st;
+  if (mode == 0) {
+    uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
+    if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
+    KL(KID_PAIRING_COOP, k_pairing_coop_easy, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_ws, (const int32_t*)d_status, fixed_g2, d_easy);
+    HIPCK(hipGetLastError());
+    std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
+    HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    // the engine's value layout: value v = 2 * (power of w) + component, sixteen words each -> tower order, fourteen limbs each
+    for (size_t i = 0; i < n; i++)
+      for (size_t k = 0; k < 6; k++) {
+        const size_t pw = k < 3 ? 2 * k : 2 * (k - 3) + 1;
+        for (size_t comp = 0; comp < 2; comp++)
+          for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * k + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
+      }
+    SYNC_FLUSH(c);
+    return 0;
+  }
+  if (mode == 1) {
+    KL(KID_PAIRING_COOP, k_pairing_coop, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_ws, d_status, fixed_g2);
+  } else {                    // one launch per live item: the item's column is slot 0 of a workspace of stride n
+    for (size_t i = 0; i < n; i++)
+      if (status[i] == BLS_OK) KL(KID_FINALEXP_ONE, k_finalexp_coop, dim3(1), dim3(BLS_BLOCK), (const uint32_t*)(d_ws + i), n, d_status + i);
+  }
+  HIPCK(hipGetLastError());
+  return copy_out_and_sync(c, status, d_status, 4 * n);
 }
 API_CATCH
 

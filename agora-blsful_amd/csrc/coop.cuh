@@ -9,7 +9,7 @@
 // anti-diagonals i + j = k (mod 6), multiplying the wrapped half by xi.  Squaring uses the 21 products i <= j, the
 // sparse line multiplication 18.  Point arithmetic of the Miller loop (9 dependent Fp2 products per doubling) stays on
 // lane pair 0, which runs the ordinary lane-split template code.
-// Device only.
+// Device code; tests/hostsim_coop compiles the same round functions on the host (one thread per lane pair) under the bound tracker.
 #pragma once
 #include "tower_split.cuh"
 #include "verify.cuh"
@@ -28,6 +28,7 @@ struct coop_shared {
 };
 
 __device__ __forceinline__ int coop_pair() { return (int)(threadIdx.x >> 1); }
+#if defined(__HIPCC__)
 __device__ __forceinline__ void coop_ld(hfp2& r, const uint32_t* slot) {
   const uint32_t* p = slot + (lane_hi() ? FP_NL : 0);
 #pragma unroll
@@ -38,6 +39,23 @@ __device__ __forceinline__ void coop_st(uint32_t* slot, const hfp2& a) {
 #pragma unroll
   for (int i = 0; i < FP_NL; i++) p[i] = (uint32_t)a.v.l[i];
 }
+#else
+// Host build (tests/hostsim_coop, test only): a wave is 32 threads, one per lane pair, with threadIdx.x = 2 * (lane pair), and the
+// host hfp2 holds both halves.  The harness supplies threadIdx, __syncthreads and coop_trk_ld / coop_trk_st, which carry an
+// element's tracked bounds through its LDS slot.
+static inline void coop_ld(hfp2& r, const uint32_t* slot) {
+  for (int h = 0; h < 2; h++) {
+    for (int i = 0; i < FP_NL; i++) r.c[h].l[i] = (int32_t)slot[h * FP_NL + i];
+    FP_TRK(coop_trk_ld(r.c[h], slot + h * FP_NL);)
+  }
+}
+static inline void coop_st(uint32_t* slot, const hfp2& a) {
+  for (int h = 0; h < 2; h++) {
+    for (int i = 0; i < FP_NL; i++) slot[h * FP_NL + i] = (uint32_t)a.c[h].l[i];
+    FP_TRK(coop_trk_st(slot + h * FP_NL, a.c[h]);)
+  }
+}
+#endif
 // Anti-diagonal reduction: lane pair k < 6 builds  sum_{i+j = k} w P_ij  +  xi * sum_{i+j = k+6} w P_ij  from the staged
 // products.  MODE 0: full product (P_ij at prod[6 i + j]);  1: squaring (prod index of i <= j, off-diagonal weight 2);
 // 2: sparse line (prod[3 i + c], c = 0, 1, 2 for the line coefficients at w^0, w^2, w^3).
@@ -138,10 +156,22 @@ __device__ __noinline__ void coop_mul_line(coop_shared& S, coop_f12& f, int set)
   __syncthreads();
   coop_reduce<2>(S, f);
 }
+#if defined(__HIPCC__)
 __device__ __forceinline__ void coop_copy(coop_f12& dst, const coop_f12& a) {
   for (int w = threadIdx.x; w < 6 * COOP_FP2_WORDS; w += BLS_BLOCK) (&dst.c[0][0])[w] = (&a.c[0][0])[w];
   __syncthreads();
 }
+#else
+static inline void coop_copy(coop_f12& dst, const coop_f12& a) {   // host: coefficient by coefficient, with the tracked bounds
+  const int k = coop_pair();
+  if (k < 6) {
+    hfp2 x;
+    coop_ld(x, a.c[k]);
+    coop_st(dst.c[k], x);
+  }
+  __syncthreads();
+}
+#endif
 // a^(p^6): negate the odd coefficients
 __device__ __forceinline__ void coop_conj(coop_f12& dst, const coop_f12& a) {
   const int k = coop_pair();
@@ -345,17 +375,24 @@ __device__ __noinline__ void coop_miller2(coop_shared& S, const g1_aff* P, const
   const uint32_t (*LINES)[6 * FP_NL] = fixed_g2 == 2 ? G2NEGC_LINES : G2NEG_LINES;   // 2: the table of -[c] g2 (uncleared message points)
   g1_aff Pm;
   aff<hfp2> Qm;
+  hfp2 xp2, yp2;                                 // (xP, 0), (yP, 0): Fp scalings as Fp2 products, so that all jobs are alike
+#if defined(__HIPCC__)
   fp_sel(Pm.x, second, P[1].x, P[0].x);
   fp_sel(Pm.y, second, P[1].y, P[0].y);
   fp_sel(Qm.x.v, second, Q[1].x.v, Q[0].x.v);
   fp_sel(Qm.y.v, second, Q[1].y.v, Q[0].y.v);
-  hfp2 xp2, yp2;                                 // (xP, 0), (yP, 0): Fp scalings as Fp2 products, so that all jobs are alike
   {
     fp z;
     fp_zero(z);
     fp_sel(xp2.v, lane_hi(), z, Pm.x);
     fp_sel(yp2.v, lane_hi(), z, Pm.y);
   }
+#else
+  Pm = P[second ? 1 : 0];
+  Qm = Q[second ? 1 : 0];
+  fp2_from_fp(xp2, Pm.x);
+  fp2_from_fp(yp2, Pm.y);
+#endif
   g2_hom_t<hfp2> T;
   T.x = Qm.x;
   T.y = Qm.y;

@@ -3,9 +3,12 @@
 // Elements cross the door in the internal form: fourteen signed 32-bit limbs of 28 bits (fp.cuh), R = 2^392.
 //     X(name, id, lanes, n_in, n_out, n_par, chain)
 // lanes: 1 = one item per lane (the code of k_prepare, the MSM and the point kernels), 2 = one item per lane pair (hfp2: item j
-// on lanes 2j and 2j + 1, 32 items per workgroup).  n_in / n_out: Fp limb vectors per record; an Fp2 is two of them (c0, c1), an
+// on lanes 2j and 2j + 1, 32 items per workgroup), 64 = one item per 64-lane workgroup (the wave-cooperative engine of coop.cuh on a
+// __shared__ coop_shared, launched with BLS_BLOCK threads as k_pairing_coop is).  n_in / n_out: Fp limb vectors per record; an Fp2 is two of them (c0, c1), an
 // Fp12 twelve, in tower order (c0.a0, c0.a1, c0.a2, c1.a0, c1.a1, c1.a2).  n_par: small integers after the input vectors.
 // chain: reps > 1 is allowed and feeds the output back as the first operand.
+// The last parameter of every lanes = 64 row is `fill`: the word the kernel writes over the whole coop_shared before it stages the
+// operands.  An Fp12 crosses the door in tower order there too; the kernel maps it to the w-power slots of coop_f12 as k_finalexp_coop does.
 #pragma once
 
 #define BLS_DEBUG_OPS(X)                                                                                            \
@@ -48,7 +51,21 @@
   X(F12_POW_X, 50, 2, 12, 12, 0, 0)    /* fp12_pow_x */                                                              \
   X(F12_INV, 51, 2, 12, 12, 0, 0)      /* fp12_inv */                                                                \
   X(F12_FROB1, 52, 2, 12, 12, 0, 0)    /* fp12_frob<1> */                                                            \
-  X(F12_FROB2, 53, 2, 12, 12, 0, 0)    /* fp12_frob<2> */
+  X(F12_FROB2, 53, 2, 12, 12, 0, 0)    /* fp12_frob<2> */                                                            \
+  /* ---- one 64-lane workgroup per item: coop.cuh */                                                               \
+  X(COOP_MUL, 60, 64, 24, 12, 2, 1)    /* coop_mul(S, dst, a, b); par = alias (0: own dst, 1: dst = a, 2: dst = b), fill */ \
+  X(COOP_SQR, 61, 64, 12, 12, 1, 1)    /* coop_sqr; par = fill */                                                    \
+  X(COOP_MUL_LINE, 62, 64, 18, 12, 2, 1) /* coop_mul_line(S, f, set): in = f, l0, l2, l3; par = set, fill (the other set: the line rotated) */ \
+  X(COOP_CYC_SQR, 63, 64, 12, 12, 2, 1)  /* coop_cyc_sqr; par = alias (0: own dst, 1: dst = a), fill */              \
+  X(COOP_POW_X, 64, 64, 12, 12, 1, 0)    /* coop_pow_x */                                                            \
+  X(COOP_CONJ, 65, 64, 12, 12, 1, 0)     /* coop_conj */                                                             \
+  X(COOP_FROB1, 66, 64, 12, 12, 1, 0)    /* coop_frob<1> */                                                          \
+  X(COOP_FROB2, 67, 64, 12, 12, 1, 0)    /* coop_frob<2> */                                                          \
+  X(COOP_JOBS, 68, 64, 48, 24, 2, 0)     /* coop_jobs(S, njobs): in = job[k][j][0], job[k][j][1] for k < 2, j < 6; out = res[k][j] (fill where not computed); par = njobs, fill */ \
+  X(COOP_SQR_MUL_JOBS, 69, 64, 52, 32, 1, 0)  /* coop_sqr_with_jobs: in = f, job[k][j][0..1] for j < 5; out = f^2, res[k][j] */ \
+  X(COOP_LINE_MUL_JOBS, 70, 64, 66, 36, 2, 0) /* coop_mul_line_with_jobs: in = f, l0, l2, l3, job[k][j][0..1] for j < 6; out = f * line, res[k][j]; par = set, fill */ \
+  X(COOP_FINAL_EASY, 71, 64, 12, 12, 1, 0)    /* coop_final_easy on S.f */                                           \
+  X(COOP_FINAL_VERDICT, 72, 64, 12, 1, 1, 0)  /* coop_final_verdict on S.f: out limb 0 = the status */
 
 enum {
 #define X(name, id, lanes, nin, nout, npar, chain) DBG_##name = id,
@@ -71,4 +88,5 @@ __global__ void k_dbg_fp2s(int op, size_t n, int reps, const int32_t* in, int re
 __global__ void k_dbg_f12acc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_cyc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_f12misc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_coop(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 #endif

@@ -312,6 +312,19 @@ int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t
  * c4, c3, c5 (c0 then c1 of each, fourteen limbs each, reduced form).  status: an item that is not BLSGPU_OK is skipped and its
  * output left zero.  out_f12: n x twelve limb vectors in tower order.  Host pointers, n <= 4096. */
 int blsgpu_debug_millerf(const int32_t* lines, size_t n, const int32_t* status, int32_t* out_f12);
+/* Self-test hook of the wave-cooperative pairing kernels (not part of the reference interface): the shipped kernels, launched as
+ * the verify path launches them, on caller-supplied pairs.  pairs: n x twelve limb vectors in reduced form -- P.x, P.y, Q.x.c0,
+ * Q.x.c1, Q.y.c0, Q.y.c1 of pair 0, then of pair 1 (affine; nothing is checked, the points need not lie in the subgroups).
+ * fixed_g2 as the verify path passes it: 0 = two general pairs, 1 = pair 1's G2 member is -g2, 2 = it is the constant of
+ * G2NEGC_LINES (pair 1's Q is then not read).  status is in/out: an item that is not BLSGPU_OK on entry is skipped.
+ * mode 0: k_pairing_coop_easy; out_f12 gets the exported easy-part value miller(pairs)^((p^6 - 1)(p^2 + 1)) per item as twelve limb
+ *         vectors in tower order, and every limb of a skipped item is BLSGPU_DEBUG_COOP_SENTINEL; status is left as it is.
+ * mode 1: k_pairing_coop; status becomes BLSGPU_OK or BLSGPU_ERR_INVALID_SIGNATURE; out_f12 is not used.
+ * mode 2: k_finalexp_coop; `pairs` is n x twelve limb vectors of an Fp12 in tower order instead, each run as slot 0 of a workspace of
+ *         stride n; status becomes the verdict; out_f12 is not used.
+ * Host pointers, n <= 4096. */
+#define BLSGPU_DEBUG_COOP_SENTINEL ((int32_t)0xa5a5a5a5)
+int blsgpu_debug_coop_pairing(int mode, int fixed_g2, const int32_t* pairs, size_t n, int32_t* status, int32_t* out_f12);
 
 /* Sign side, provided so that benchmarks and tests can build inputs on the device:
  * pk[i] = sk[i] * g (SecretKey::public_key, src/secret_key.rs:342-344) and

@@ -347,14 +347,177 @@ def build():
     L['F12_INV'] = [case(nm, vs) for nm, vs in ops12 + cyc]
     L['F12_FROB1'] = L['F12_INV']
     L['F12_FROB2'] = L['F12_INV']
+    coop_lists(L, ops12, cyc, accs, mv, ext2)
     _cache.update(L)
     return _cache
+
+
+# ---- the wave-cooperative engine (csrc/coop.cuh, lanes = 64).  The last parameter of every row is the fill word of coop_shared.
+FILLS = (0, -1, 0x7fffffff)           # 0, 0xffffffff and 0x7fffffff as the signed words of a record
+COOP_ALIASES = {'COOP_MUL': (0, 1, 2), 'COOP_CYC_SQR': (0, 1)}
+ZERO_VEC = [0] * NL
+# the two ends of the reduced range, as (name, the positive vector, the negative vector)
+COOP_MAGS = (('0.52 p', limbs_of(RED_MAX), limbs_of(-RED_MAX)),
+             ('extreme limbs', [M] * (NL - 1) + [TOP_MAX - 1], [0] * (NL - 1) + [TOP_MIN + 1]))
+
+
+def neg_vec(v):
+    return [-x for x in v]
+
+
+def conj_vecs(vs):
+    """what coop_conj makes of a reduced element: the odd powers of w (tower vectors 6..11) negated limb by limb"""
+    return [list(v) for v in vs[:6]] + [neg_vec(v) for v in vs[6:]]
+
+
+def mult_form(x):
+    """a multiplier output for the field element x: its Montgomery residue in [0, p), exact limbs"""
+    return limbs_of(x % P * R392 % P)
+
+
+def frob_vecs(f, j):
+    """what coop_frob<j> makes of the reduced element f: the w^0 coefficient copied (j = 2) or conjugated limb-wise (j = 1), every
+    other coefficient a product by a constant"""
+    g = c.f12_frob(f, j)
+    out = []
+    for k in range(6):
+        pw = TOWER_TO_W[k]
+        if pw == 0:
+            a = f2_vecs(f[0])
+            out += [a[0], neg_vec(a[1]) if j == 1 else a[1]]
+        else:
+            out += [mult_form(g[pw][0]), mult_form(g[pw][1])]
+    return out
+
+
+def signed_f12(pos, neg, re, im, flip0=False):
+    """twelve vectors: every coefficient (re, im) times the magnitude (+1: pos, -1: neg, 0: zero); flip0 negates the w^0 coefficient"""
+    pick = lambda s: pos if s > 0 else neg if s < 0 else ZERO_VEC
+    out = []
+    for k in range(6):
+        s = -1 if flip0 and TOWER_TO_W[k] == 0 else 1
+        out += [pick(s * re), pick(s * im)]
+    return out
+
+
+# (a.re, a.im, b.re, b.im): the signs that give every product a_i b_j the same sign in the named part (and zero in the other one):
+# re = a.re b.re - a.im b.im, im = a.re b.im + a.im b.re.  All 36 products alike means six like terms in the half i + j = 5 of
+# coefficient 5 and five in the wrapped half i + j = 6 of coefficient 0; flip0 (a_0 negated) sets coefficient 0's own half i + j = 0
+# against its wrapped half and one term of every other sum against the rest.
+SAME_SIGN = (('real parts all positive', (1, 1, 1, -1)), ('real parts all negative', (1, 1, -1, 1)),
+             ('imaginary parts all positive', (1, 1, 1, 1)), ('imaginary parts all negative', (1, 1, -1, -1)))
+# squaring: a_i a_j of one operand (re = re^2 - im^2, im = 2 re im); the off-diagonal products are doubled
+SAME_SIGN_SQR = (('real parts all positive', (1, 0)), ('real parts all negative', (0, 1)), ('imaginary parts all positive', (1, 1)),
+                 ('imaginary parts all negative', (1, -1)), ('imaginary parts all positive, operand negative', (-1, -1)))
+
+
+def _cycle_pars(cases_, pars):
+    """give case i the parameters pars(i) + fill i: alias / set / njobs and the three fills all occur, and neighbours differ"""
+    out = []
+    for i, (nm, vs) in enumerate(cases_):
+        out.append(case(nm, vs, tuple(pars(i)) + (FILLS[(i + i // 3) % 3],)))
+    for a, b in zip(out, out[1:] + out[:1]):
+        assert a['vecs'] != b['vecs'], (a['name'], b['name'])       # neighbours differ in their operands, whatever the parameters
+    return out
+
+
+def coop_lists(L, ops12, cyc, accs, mv, ext2):
+    rng = random.Random(20250923)          # a generator of its own: the lists above stay as they were
+    n12 = len(ops12)
+    rand12 = [vs for nm, vs in ops12 if nm.startswith('random')]
+    # -- coop_mul
+    mul = [('%s * %s' % (ops12[i][0], ops12[(5 * i + 2) % n12][0]), ops12[i][1] + ops12[(5 * i + 2) % n12][1]) for i in range(n12)]
+    for mn, pos, neg in COOP_MAGS:
+        for sn, (ar, ai, br, bi) in SAME_SIGN:
+            for flip0 in (False, True):
+                mul.append(('same-sign products, %s, at %s%s' % (sn, mn, ', a_0 negated' if flip0 else ''),
+                            signed_f12(pos, neg, ar, ai, flip0) + signed_f12(pos, neg, br, bi)))
+    ext12 = f12_extreme_vecs()
+    chain_ops = [(nm, vs) for nm, vs in ext12] + [('random %d' % i, vs) for i, vs in enumerate(rand12[:3])] + cyc[1:]
+    for i, (nm, vs) in enumerate(chain_ops):
+        onm, ovs = chain_ops[(i + 3) % len(chain_ops)]
+        mul.append(('conj(%s) * %s' % (nm, onm), conj_vecs(vs) + ovs))
+        mul.append(('%s * conj(%s)' % (onm, nm), ovs + conj_vecs(vs)))
+        mul.append(('conj(%s) * conj(%s)' % (nm, onm), conj_vecs(vs) + conj_vecs(ovs)))
+    for i, (nm, vs) in enumerate(chain_ops):
+        f, (onm, ovs) = f12_of_vecs(vs), chain_ops[(i + 2) % len(chain_ops)]
+        mul.append(('frob1(%s) * %s' % (nm, onm), frob_vecs(f, 1) + ovs))
+        mul.append(('%s * frob2(%s)' % (onm, nm), ovs + frob_vecs(f, 2)))
+        mul.append(('frob1(%s) * frob2(%s)' % (nm, onm), frob_vecs(f, 1) + frob_vecs(f12_of_vecs(ovs), 2)))
+    L['COOP_MUL'] = _cycle_pars(mul, lambda i: (i % 3,))
+    # -- coop_sqr
+    sqr = list(ops12) + list(cyc)
+    for mn, pos, neg in COOP_MAGS:
+        for sn, (re, im) in SAME_SIGN_SQR:
+            for flip0 in (False, True):
+                sqr.append(('same-sign products, %s, at %s%s' % (sn, mn, ', a_0 negated' if flip0 else ''), signed_f12(pos, neg, re, im, flip0)))
+    L['COOP_SQR'] = _cycle_pars(sqr, lambda i: ())
+    # -- coop_mul_line: f, l0, l2, l3
+    lines = line_coeff_sets(rng, 3, 8)
+    for z in range(3):
+        cs = [(rng.randrange(1, P), rng.randrange(1, P)) for _ in range(3)]
+        cs[z] = (0, 0)
+        lines.append(('sparse line, coefficient %d zero' % z, cs))
+    ml = [('%s * %s' % (accs[(3 * i + 1) % len(accs)][0], nm), accs[(3 * i + 1) % len(accs)][1] + sum((f2_vecs(x) for x in cs), []))
+          for i, (nm, cs) in enumerate(lines * 2)]
+    for i, (mn, pos, neg) in enumerate(COOP_MAGS):
+        ml.append(('%s * coefficients at %s' % (accs[-(i + 1)][0], mn), accs[-(i + 1)][1] + [pos] * 6))
+        ml.append(('%s * coefficients at -%s' % (accs[-(i + 3)][0], mn), accs[-(i + 3)][1] + [neg] * 6))
+        for sn, (ar, ai, br, bi) in SAME_SIGN:
+            for flip0 in (False, True):
+                ml.append(('same-sign products, %s, at %s%s' % (sn, mn, ', f_0 negated' if flip0 else ''),
+                           signed_f12(pos, neg, ar, ai, flip0) + signed_f12(pos, neg, br, bi)[:6]))
+    for i, (nm, vs) in enumerate(cyc[1:]):
+        ml.append(('conj(%s) * %s' % (nm, lines[-(i + 1)][0]), conj_vecs(vs) + sum((f2_vecs(x) for x in lines[-(i + 1)][1]), [])))
+    L['COOP_MUL_LINE'] = _cycle_pars(ml, lambda i: (i % 2,))
+    # -- the cyclotomic squaring (judged by gs_sqr, defined everywhere), a^x, conjugation and the Frobenius maps
+    L['COOP_CYC_SQR'] = _cycle_pars(list(cyc) + list(ops12) + [('conj(%s)' % nm, conj_vecs(vs)) for nm, vs in cyc[1:]], lambda i: (i % 2,))
+    more = [('cyclotomic %d' % i, vecs_of_f12(cyclotomic(rand_f12(rng)))) for i in range(3, 7)]
+    L['COOP_POW_X'] = _cycle_pars(list(cyc) + more + [('conj(%s)' % nm, conj_vecs(vs)) for nm, vs in cyc[1:3]], lambda i: ())
+    for op in ('COOP_CONJ', 'COOP_FROB1', 'COOP_FROB2'):
+        L[op] = _cycle_pars(list(ops12) + list(cyc), lambda i: ())
+    # -- the product rounds of the point steps: operands as fp2_mul takes them (the multiplier's operand families)
+    def jobs(i, count, step):
+        return [mv[(step * i + 7 * t + 1) % len(mv)] for t in range(count)]
+    jl = []
+    for i in range(36):
+        js = jobs(i, 48, 11)
+        jl.append((' | '.join(nm for nm, _ in js[:4]) + ' ...', [l for _, l in js]))
+    for i in range(4):
+        jl.append(('extreme limbs: %s ...' % ext2[i][0], [ext2[(i + t) % len(ext2)][1] for t in range(48)]))
+    L['COOP_JOBS'] = _cycle_pars(jl, lambda i: (5 + i % 2,))
+    fs = list(ops12) + list(cyc)
+    L['COOP_SQR_MUL_JOBS'] = _cycle_pars([('%s, jobs from %d' % (nm, i), vs + [l for _, l in jobs(i, 40, 13)]) for i, (nm, vs) in enumerate(fs)], lambda i: ())
+    L['COOP_LINE_MUL_JOBS'] = _cycle_pars([(nm + ', jobs from %d' % i, vs + [l for _, l in jobs(i, 48, 17)]) for i, (nm, vs) in enumerate(ml[::2])], lambda i: (i % 2,))
+    # -- the final exponentiation: random elements (not one), r-th powers, elements of Fp6 and Fp2, +-1 (one), zero (fp12_inv(0) = 0
+    # must give INVALID); Fp12 is a field, so there is no non-invertible element but zero
+    fe = [(nm, vs) for nm, vs in ops12 if nm.startswith(('random', 'element of', 'one', 'minus one', 'zero', 'every component'))]
+    rth = [('r-th power %d' % i, vecs_of_f12(c.f12_pow(rand_f12(rng), c.R))) for i in range(3)]
+    fe += rth
+    fe += [('single component %d' % pos, ops12[6 + pos][1]) for pos in (0, 1, 5, 6, 11)]
+    fe += ext12[:3] + cyc[1:2]
+    fe.append(('r-th power times an element of Fp6', vecs_of_f12(c.f12_mul(f12_of_vecs(rth[0][1]), f12_of_vecs(ops12[18][1])))))
+    assert ops12[18][0] == 'element of Fp6'
+    L['COOP_FINAL_EASY'] = _cycle_pars(fe, lambda i: ())
+    L['COOP_FINAL_VERDICT'] = _cycle_pars(fe, lambda i: ())
+
+
+def with_pars(cs, fill=None, first=None):
+    """the same case (the same operand vectors, so the same expected value) with another fill word or another first parameter"""
+    par = list(cs['par'])
+    if fill is not None:
+        par[-1] = fill
+    if first is not None:
+        par[0] = first
+    return dict(cs, par=par)
 
 
 # ---- judging the outputs
 MULT_OUT = {'FP_MUL', 'FP_SQR', 'FP_INV', 'FP_INV_VAR', 'FP2_KARA_PRODUCTS', 'FP2_KARA_DIFFS', 'FP2_MUL', 'FP2_SQR', 'FP2_MUL_FP'}
 REDUCED_OUT = {'FP_REDUCE', 'FP_REDUCE_LIN2', 'FP_FROM_RAW', 'F12_SH_SQR', 'F12_SH_MUL', 'F12_SH_MUL_LINE', 'F12_SH_MUL_2LINES', 'F12_SH_MUL_LINE5', 'F12_SH_CYC_SQR',
-               'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'F12_INV'}
+               'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'F12_INV',
+               'COOP_MUL', 'COOP_SQR', 'COOP_MUL_LINE', 'COOP_CYC_SQR', 'COOP_FINAL_EASY'}     # (the rounds of coop.cuh end in fp2_reduce)
+COOP_REDUCED_F = {'COOP_SQR_MUL_JOBS', 'COOP_LINE_MUL_JOBS'}      # outputs 0..11: f, reduced; the rest: products
 
 
 def _f2mul_raw(a, b):
@@ -415,6 +578,8 @@ def expected(op, cs, reps=1):
             return [0, 0]
         ni = pow(n, -1, P) * R392 * R392 % P
         return [v[0] * ni % P, -v[1] * ni % P]
+    if op.startswith('COOP_'):
+        return _coop_expected(op, cs, v, reps)
     if op in ('CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA'):
         z = tuple(f2_of_vecs(cs['vecs'][2 * k:2 * k + 2]) for k in range(4))
         for _ in range(reps):
@@ -453,6 +618,68 @@ def expected(op, cs, reps=1):
             f = c.f12_mul(f, b)
     return [x * R392 % P for k in range(6) for x in f[TOWER_TO_W[k]]]
 
+BLS_OK, BLS_INVALID = 0, 1             # status codes of coop_final_verdict (BLS_OK, BLS_ERR_INVALID_SIGNATURE)
+
+
+def coop_pow_x(f):
+    """coop_pow_x restated on the oracle's tower with the Granger-Scott formulas, so that it is defined for any input; on the
+    cyclotomic subgroup it is conj(f^|x|) (tests/test_hostsim_coop.py checks that)"""
+    acc = f
+    for i in range(62, -1, -1):
+        acc = gs_sqr(acc)
+        if (c.X_ABS >> i) & 1:
+            acc = c.f12_mul(acc, f)
+    return c.f12_conj(acc)
+
+
+def final_verdict(f):
+    """the status coop_final_verdict must return for S.f = f, from the oracle's final exponentiation; zero has no inverse: INVALID"""
+    return BLS_OK if f != F12_ZERO and c.final_exponentiation(f) == F12_ONE else BLS_INVALID
+
+
+def _coop_expected(op, cs, v, reps):
+    tower = lambda f: [x * R392 % P for k in range(6) for x in f[TOWER_TO_W[k]]]
+    prods = lambda k0, cnt: [x for t in range(cnt) for x in _f2mul_raw(v[k0 + 4 * t:k0 + 4 * t + 2], v[k0 + 4 * t + 2:k0 + 4 * t + 4])]
+    if op == 'COOP_JOBS':            # res[k][j] for j < njobs; the other slots keep the fill (None: judged in check)
+        out = prods(0, 12)
+        for t in range(12):
+            if t % 6 >= cs['par'][0]:
+                out[2 * t] = out[2 * t + 1] = None
+        return out
+    f = f12_of_vecs(cs['vecs'][:12])
+    if op == 'COOP_CONJ':
+        return [v[k] if k < 6 else -v[k] for k in range(12)]
+    if op == 'COOP_FINAL_VERDICT':
+        return [None]
+    if op == 'COOP_SQR_MUL_JOBS':
+        return tower(c.f12_sqr(f)) + prods(12, 10)
+    if op in ('COOP_MUL_LINE', 'COOP_LINE_MUL_JOBS'):
+        b = line3_f12(*[f2_of_vecs(cs['vecs'][12 + 2 * k:14 + 2 * k]) for k in range(3)])
+        for _ in range(reps):
+            f = c.f12_mul(f, b)
+        return tower(f) + (prods(18, 12) if op == 'COOP_LINE_MUL_JOBS' else [])
+    if op == 'COOP_MUL':
+        b = f12_of_vecs(cs['vecs'][12:24])
+        for _ in range(reps):
+            f = c.f12_mul(f, b)
+    elif op == 'COOP_SQR':
+        for _ in range(reps):
+            f = c.f12_sqr(f)
+    elif op == 'COOP_CYC_SQR':
+        for _ in range(reps):
+            f = gs_sqr(f)
+    elif op == 'COOP_POW_X':
+        f = coop_pow_x(f)
+    elif op == 'COOP_FROB1':
+        f = c.f12_frob(f, 1)
+    elif op == 'COOP_FROB2':
+        f = c.f12_frob(f, 2)
+    elif op == 'COOP_FINAL_EASY':
+        f = cyclotomic(f) if f != F12_ZERO else F12_ZERO       # fp12_inv(0) = 0
+    else:
+        raise KeyError(op)
+    return tower(f)
+
 
 _expected = {}
 
@@ -460,7 +687,8 @@ _expected = {}
 def check(op, cs, outs, reps=1):
     """assert that the output vectors of one case are right; the message names the operation and the case"""
     tag = '%s%s, case "%s": ' % (op, ' x%d' % reps if reps > 1 else '', cs['name'])
-    key = (op, id(cs), reps)
+    # (a lanes = 64 case run with another fill shares its operand vectors, and so its expected value, with the case of the list)
+    key = (op, id(cs['vecs']), tuple(cs['par'][:-1]), reps) if op.startswith('COOP_') else (op, id(cs), reps)
     if key not in _expected:
         _expected[key] = expected(op, cs, reps)        # computed once, shared by every test that runs the case
     want = _expected[key]
@@ -470,14 +698,14 @@ def check(op, cs, outs, reps=1):
         if w is None:
             continue
         got = val(o)
-        if op in ('FP_NORM', 'FP2_MUL_XI', 'FP2_CONJ', 'F12_PACK'):
+        if op in ('FP_NORM', 'FP2_MUL_XI', 'FP2_CONJ', 'F12_PACK', 'COOP_CONJ'):
             assert got == w, tag + 'output %d is not the same integer: %d instead of %d' % (k, got, w)
         else:
             assert (got - w) % P == 0, tag + 'output %d is not congruent to the exact result (off by %d mod p)' % (k, (got - w) % P)
-        if op in REDUCED_OUT:
+        if op in REDUCED_OUT or (op in COOP_REDUCED_F and k < 12):
             assert all(0 <= x <= M for x in o[:NL - 1]), tag + 'output %d: a limb outside [0, 2^28): %s' % (k, o)
             assert abs(got) * 100 <= 52 * P, tag + 'output %d: reduced value outside +-0.52 p: %.6f p' % (k, got / P)
-        if op in MULT_OUT:
+        if op in MULT_OUT or (op in COOP_REDUCED_F and k >= 12) or op == 'COOP_JOBS':
             assert all(0 <= x <= M for x in o[:NL - 1]), tag + 'output %d: a limb outside [0, 2^28): %s' % (k, o)
             assert -P < 8 * got < 9 * P, tag + 'output %d: multiplier output outside (-p/8, p + p/8): %.6f p' % (k, got / P)
     def mult_out(o, what):
@@ -498,12 +726,23 @@ def check(op, cs, outs, reps=1):
     if op == 'FP2L_SQR':                     # c0 a product, c1 twice a product after a carry pass
         mult_out(outs[0], 'c0')
         normalised_out(outs[1], 'c1', 2.25)
-    if op == 'F12_POW_X':                    # conj(accumulator): a reduced c0 and a limb-wise negated reduced c1 (tower order: vectors 6..11)
+    if op == 'COOP_JOBS':                    # a slot the call does not compute still holds the fill word
+        for k, (o, w) in enumerate(zip(outs, want)):
+            assert w is not None or all(x == cs['par'][-1] for x in o), tag + 'result slot %d (job %d >= njobs) does not hold the fill word: %s' % (k, k // 2 % 6, o)
+    if op == 'COOP_FINAL_VERDICT':
+        f = f12_of_vecs(cs['vecs'][:12])
+        st = _expected.setdefault(key + ('status',), None)
+        if st is None:
+            st = _expected[key + ('status',)] = final_verdict(f)
+        assert list(outs[0]) == [st] + [0] * (NL - 1), tag + 'status %s, the oracle says %d' % (outs[0], st)
+    if op == 'COOP_CONJ':                    # the same integers, the odd powers of w negated limb by limb
+        assert [list(o) for o in outs] == conj_vecs(cs['vecs']), tag + 'limbs'
+    if op in ('F12_POW_X', 'COOP_POW_X'):    # conj(accumulator): a reduced c0 and a limb-wise negated reduced c1 (tower order: vectors 6..11)
         for k, o in enumerate(outs):
             reduced_out(o if k < 6 else neg(o), 'vector %d%s' % (k, '' if k < 6 else ' negated'))
-    if op in ('F12_FROB1', 'F12_FROB2'):     # the w^0 coefficient is copied (J = 2) or conjugated limb-wise (J = 1); the others are products by constants
+    if op in ('F12_FROB1', 'F12_FROB2', 'COOP_FROB1', 'COOP_FROB2'):     # the w^0 coefficient is copied (J = 2) or conjugated limb-wise (J = 1); the others are products by constants
         a0, a1 = cs['vecs'][0], cs['vecs'][1]
-        assert list(outs[0]) == a0 and list(outs[1]) == (neg(a1) if op == 'F12_FROB1' else a1), tag + 'limbs of the w^0 coefficient'
+        assert list(outs[0]) == a0 and list(outs[1]) == (neg(a1) if op.endswith('FROB1') else a1), tag + 'limbs of the w^0 coefficient'
         for k in range(2, 12):
             mult_out(outs[k], 'vector %d' % k)
     if op == 'FP_NORM':
@@ -602,8 +841,148 @@ def check_miller(name, table, out):
         assert all(0 <= x <= M for x in l[:NL - 1]) and abs(val(l)) * 100 <= 52 * P, tag + 'vector %d is not a (negated) reduced value: %s' % (k, o)
 
 
+# ---- pairs for the shipped wave-cooperative kernels (blsgpu_debug_coop_pairing): chosen and judged with the oracle alone
+def g2_negc():
+    """-[c] g2, c = (1 - x)^-1 mod r: the constant of G2NEGC_LINES (tools/gen_g2_lines.py)"""
+    return c.E2.neg(c.E2.mul(c.G2_GEN, pow(c.H_EFF_G1, -1, c.R)))
+
+
+def largest_g1():
+    """the point of E1(Fp) with the largest canonical x, and of its two y the larger one"""
+    x = P - 1
+    while not c.fp_is_square((x * x * x + 4) % P):
+        x -= 1
+    y = c.fp_sqrt((x * x * x + 4) % P)
+    return (x, max(y, P - y))
+
+
+def largest_g2():
+    """the point of E2(Fp2) with x = (p - 1) + (p - 1 - t) u for the smallest t that gives one, and the y with the larger c1"""
+    x = (P - 1, P - 1)
+    while not c.f2_is_square(c.E2.rhs(x)):
+        x = (x[0], x[1] - 1)
+    y = c.f2_sqrt(c.E2.rhs(x))
+    ny = c.f2_neg(y)
+    return (x, y if (y[1], y[0]) > (ny[1], ny[0]) else ny)
+
+
+def two_representatives(x):
+    """the Montgomery residue of x lies in [0.48 p, 0.52 p]: both v and v - p are reduced forms of it"""
+    v = x % P * R392 % P
+    return 48 * P <= 100 * v <= 52 * P
+
+
+def miller_walk_is_regular(q):
+    """no step of the 63-iteration loop on Q is exceptional: T is never infinity, no doubling meets y = 0, and no addition meets
+    T = +-Q"""
+    t = q
+    for bit in bin(c.X_ABS)[3:]:
+        if t is None or t[1] == (0, 0):
+            return False
+        t = c.E2.dbl(t)
+        if bit == '1':
+            if t is None or t[0] == q[0]:
+                return False
+            t = c.E2.add(t, q)
+    return t is not None
+
+
+def pair_vecs(pairs, negative=()):
+    """twelve limb vectors (P.x, P.y, Q.x.c0, Q.x.c1, Q.y.c0, Q.y.c1 per pair) in reduced form, each the representative limbs_of_elem
+    picks -- except the vectors named in `negative`: index i >= 0 takes the representative v - p, index -(i + 1) the one in [0, p)"""
+    out = []
+    for (px, py), ((qx0, qx1), (qy0, qy1)) in pairs:
+        out += [limbs_of_elem(z) for z in (px, py, qx0, qx1, qy0, qy1)]
+    for i in negative:
+        k = i if i >= 0 else -(i + 1)
+        v = val(out[k]) % P
+        out[k] = limbs_of(v - P if i >= 0 else v)
+        assert abs(val(out[k])) * 100 <= 52 * P
+    return out
+
+
+def pairing_cases():
+    """[{'name', 'fixed_g2', 'pairs': two (P, Q) of oracle points, 'vecs': the twelve limb vectors}], deterministic.  For fixed_g2 = 1
+    pair 1's Q is -g2, for 2 the constant of G2NEGC_LINES (the kernels take it from their line table)."""
+    if 'pairs' in _cache_b:
+        return _cache_b['pairs']
+    rng = random.Random(4096)
+    E1, E2, g1, g2, R = c.E1, c.E2, c.G1_GEN, c.G2_GEN, c.R
+    a, b, sk, h = (rng.randrange(1, R) for _ in range(4))
+    ag1, bg2, H, pk = E1.mul(g1, a), E2.mul(g2, b), E1.mul(g1, h), E2.mul(g2, sk)
+    sig = E1.mul(H, sk)
+    PL, QL = largest_g1(), largest_g2()
+    PU, QU = c.map_to_curve_g1(rng.randrange(P)), c.map_to_curve_g2((rng.randrange(P), rng.randrange(P)))     # not cofactor-cleared
+    fixed_q = {1: E2.neg(g2), 2: g2_negc()}
+    sig2 = E1.mul(E1.mul(PU, c.H_EFF_G1), sk)
+    out = []
+
+    def add(name, fixed, pairs, negative=()):
+        out.append({'name': 'fixed_g2 = %d: %s' % (fixed, name), 'fixed_g2': fixed, 'pairs': pairs, 'vecs': pair_vecs(pairs, negative)})
+    add('subgroup points, product one', 0, [(ag1, bg2), (E1.neg(g1), E2.mul(g2, a * b % R))])
+    add('subgroup points, product not one', 0, [(ag1, bg2), (H, pk)])
+    add('P with the largest canonical coordinates', 0, [(PL, bg2), (ag1, pk)])
+    add('Q with the largest canonical coordinates', 0, [(ag1, QL), (H, bg2)])
+    add('the largest P and Q as pair 1', 0, [(H, bg2), (PL, QL)])
+    add('points outside the subgroups', 0, [(PU, QU), (ag1, bg2)])
+    add('the same P and Q in both pairs', 0, [(ag1, bg2), (ag1, bg2)])
+    add('P and -P against the same Q, product one', 0, [(ag1, bg2), (E1.neg(ag1), bg2)])
+    for fx in (1, 2):
+        fq = fixed_q[fx]
+        add('signature, product one', fx, [(H, pk), (sig, fq)] if fx == 1 else [(PU, pk), (sig2, fq)])
+        add('another message, product not one', fx, [(ag1, pk), (sig, fq)])
+        add('P with the largest canonical coordinates in both pairs', fx, [(PL, pk), (PL, fq)])
+        add('Q with the largest canonical coordinates', fx, [(H, QL), (sig, fq)])
+        add('points outside the subgroups', fx, [(PU, QU), (PL, fq)])
+        add('the same P and Q in both pairs', fx, [(H, fq), (H, fq)])
+    # a coordinate with two reduced representatives: the positive one beside the negative one (congruent results)
+    t, found = g1, {}
+    while len(found) < 2:
+        t = E1.add(t, g1)
+        for k in (0, 1):
+            if k not in found and two_representatives(t[k]):
+                found[k] = t
+    u, qx = g2, None
+    while qx is None:
+        u = E2.add(u, g2)
+        if two_representatives(u[0][0]):
+            qx = u
+    for fx in (0, 1, 2):
+        second = (H, bg2 if fx == 0 else fixed_q[fx])
+        for k, nm in ((0, 'P.x'), (1, 'P.y')):
+            add('%s as its positive representative' % nm, fx, [(found[k], pk), second], (-(k + 1),))
+            add('%s as its negative representative' % nm, fx, [(found[k], pk), second], (k,))
+            if fx:       # ... and in pair 1, whose P scales the rows of the line table
+                add('%s of pair 1 as its positive representative' % nm, fx, [(H, pk), (found[k], second[1])], (-(6 + k + 1),))
+                add('%s of pair 1 as its negative representative' % nm, fx, [(H, pk), (found[k], second[1])], (6 + k,))
+        add('Q.x.c0 as its positive representative', fx, [(ag1, qx), second], (-3,))
+        add('Q.x.c0 as its negative representative', fx, [(ag1, qx), second], (2,))
+    _cache_b['pairs'] = out
+    return out
+
+
+def pairing_expected(cs):
+    """(the oracle's Miller value, its easy part, the status of the pairing check)"""
+    key = ('pairing', id(cs))
+    if key not in _cache_b:
+        m = c.miller_loop(cs['pairs'])
+        _cache_b[key] = (m, cyclotomic(m), BLS_OK if c.final_exponentiation(m) == F12_ONE else BLS_INVALID)
+    return _cache_b[key]
+
+
+def check_easy(cs, out):
+    """one item's exported easy-part value (twelve limb vectors, tower order): miller_loop(pairs)^((p^6 - 1)(p^2 + 1)) exactly -- the
+    Fp2 factors by which the kernel's projective lines differ from the oracle's affine ones vanish under p^6 - 1 -- and reduced"""
+    tag = 'k_pairing_coop_easy, case "%s": ' % cs['name']
+    want, got = pairing_expected(cs)[1], f12_of_vecs(out)
+    for k in range(6):
+        assert got[k] == want[k], tag + 'coefficient of w^%d differs' % k
+    for k, o in enumerate(out):
+        assert all(0 <= x <= M for x in o[:NL - 1]) and abs(val(o)) * 100 <= 52 * P, tag + 'vector %d is not a reduced value: %s' % (k, o)
+
+
 CHAINS = ('FP_MUL', 'FP_SQR', 'FP2_MUL', 'FP2_SQR', 'F12_SH_SQR', 'F12_SH_MUL', 'F12_SH_MUL_LINE', 'F12_SH_MUL_2LINES', 'F12_SH_MUL_LINE5', 'F12_SH_CYC_SQR',
-          'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA')
+          'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'COOP_MUL', 'COOP_SQR', 'COOP_MUL_LINE', 'COOP_CYC_SQR')
 CHAIN_REPS = ((2, 1), (17, 5), (63, 11))       # (reps, stride through the list)
 
 
@@ -612,7 +991,7 @@ def chain_cases(op, stride):
     every element of that subgroup -- so that at each length, 63 included, non-trivial cyclotomic elements are squared"""
     lst = build()[op]
     cases = lst[::stride][:24]
-    if op in ('F12_SH_CYC_SQR', 'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA'):
+    if op in ('F12_SH_CYC_SQR', 'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'COOP_CYC_SQR'):
         cases = [cs for cs in lst if cs['name'].startswith('cyclotomic')] + [cs for cs in cases if not cs['name'].startswith('cyclotomic')]
         assert sum(cs['name'].startswith('cyclotomic ') and cs['name'] != 'cyclotomic one' for cs in cases) >= 3
     return cases

@@ -1,5 +1,6 @@
 """The shared case list of tests/field_cases.py on the CPU: every case of every operation runs through the host-compiled headers
-(tests/hostsim hs_field_op) with the bound tracker on and the case's declared limb and value bounds, so a case that passes lies
+(tests/hostsim hs_field_op; the lanes = 64 rows of the wave-cooperative engine through tests/hostsim_coop hs_coop_op, a wave as 32
+threads) with the bound tracker on and the case's declared limb and value bounds, so a case that passes lies
 inside the documented input contract of the function under test; the results are judged by field_cases.check (exact integers).
 tests/test_gpu_field_ops.py then runs the same cases on the device.  No case is skipped: a case the tracker rejects aborts the run
 and is removed from the list in the source."""
@@ -8,6 +9,7 @@ import ctypes
 import pytest
 
 import field_cases as fc
+import util
 from util import c, P
 
 
@@ -16,12 +18,19 @@ def ops(pkg):
     return pkg.api.field_ops()
 
 
+@pytest.fixture(scope='module')
+def hs(hs):
+    """hs_field_op of tests/hostsim and hs_coop_op of tests/hostsim_coop behind one name: run_host picks by the row's lanes"""
+    hs.hs_coop_op = util.build_hostsim_coop().hs_coop_op
+    return hs
+
+
 def run_host(hs, ops, shapes, op, cs, reps=1):
-    _, n_in, n_out, n_par, _ = shapes[op]
+    lanes, n_in, n_out, n_par, _ = shapes[op]
     assert len(cs['vecs']) == n_in and len(cs['par']) == n_par, (op, cs['name'])
     flat = [x for v in cs['vecs'] for x in v]
     out = (ctypes.c_int32 * (14 * n_out))()
-    rc = hs.hs_field_op(ops[op], (ctypes.c_int32 * len(flat))(*flat), (ctypes.c_double * n_in)(*cs['lb']), (ctypes.c_double * n_in)(*cs['vb']),
+    rc = (hs.hs_coop_op if lanes == 64 else hs.hs_field_op)(ops[op], (ctypes.c_int32 * len(flat))(*flat), (ctypes.c_double * n_in)(*cs['lb']), (ctypes.c_double * n_in)(*cs['vb']),
                         (ctypes.c_int32 * n_in)(*cs['nn']), (ctypes.c_int32 * max(n_par, 1))(*cs['par']), reps, out)
     assert rc == 0, op
     o = list(out)

@@ -85,6 +85,20 @@ def build_hostsim():
     return ctypes.CDLL(so)
 
 
+def build_hostsim_coop():
+    """tests/hostsim_coop: csrc/coop.cuh as host C++ with the bound tracker on, one thread per lane pair (hs_coop_op, hs_coop_pairing)"""
+    import subprocess
+    src = os.path.join(ROOT, 'tests', 'hostsim_coop', 'coop_hostsim.cpp')
+    so = os.path.join(ROOT, 'tests', 'hostsim_coop', 'libcoop_hostsim.so')
+    if os.environ.get('BLS_HOSTSIM_COOP_SO'):     # a debug build (-O0 -g), as BLS_HOSTSIM_SO above
+        return ctypes.CDLL(os.environ['BLS_HOSTSIM_COOP_SO'])
+    deps = [src] + [os.path.join(ROOT, 'agora-blsful_amd', 'csrc', f) for f in os.listdir(os.path.join(ROOT, 'agora-blsful_amd', 'csrc')) if f.endswith(('.cuh', '.h'))]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        # -fwrapv: the engine multiplies job slots whose values nobody uses; their arithmetic may wrap on the device and must here too
+        subprocess.check_call(['g++', '-O2', '-fwrapv', '-pthread', '-DBLS_TRACK_BOUNDS', '-shared', '-fPIC', '-o', so, src])
+    return ctypes.CDLL(so)
+
+
 def load_c_oracle():
     """Build (if needed) and load oracle/c/liboracle.so with argument types declared."""
     import subprocess
