@@ -48,6 +48,7 @@ EXPORTS = [
     'blsgpu_multi_verify_indexed_batch', 'blsgpu_verify_secure_indexed_batch', 'blsgpu_sum_indexed_batch', 'blsgpu_verify_indexed_batch',
     'blsgpu_elgamal_message_generator', 'blsgpu_elgamal_proof_verify_batch', 'blsgpu_elgamal_open_batch',
     'blsgpu_verify_shared_batch', 'blsgpu_verify_shared_indexed_batch',
+    'blsgpu_aggregate_verify_indexed_batch',
 ]
 
 
@@ -190,6 +191,7 @@ def load_library(path=None):
         lib.blsgpu_elgamal_open_batch.argtypes = [ci, vp, u8p, vp, u64p, sz, ci, vp, i32p]
         lib.blsgpu_verify_shared_batch.argtypes = [ci, ci, vp, vp, u64p, sz, u8p, u64p, ci, i32p]
         lib.blsgpu_verify_shared_indexed_batch.argtypes = [ci, h, u32p, vp, u64p, sz, u8p, u64p, ci, i32p]
+        lib.blsgpu_aggregate_verify_indexed_batch.argtypes = [ci, h, u32p, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
         _lib = lib
     return _lib
 
@@ -827,6 +829,26 @@ def verify_indexed_batch(keyset, scheme, idx, sigs, msgs, fmt=FMT_RAW_PROJ):
     return list(st)[:n]
 
 
+def aggregate_verify_indexed_batch(keyset, scheme, sets, fmt=FMT_RAW_PROJ):
+    """aggregate_verify_batch with pair i's key named by position: `sets` is a list of (idx, msgs, sig), idx a list of positions in
+    `keyset`, one message each.  Returns one (status, (aux0, aux1)) per set: E_ARG for an index outside the table, the creation
+    status of the first invalid entry named (both with aux (0, 0)), else what aggregate_verify_batch gives for those keys."""
+    n_sets = len(sets)
+    for s, (ix, msgs, _) in enumerate(sets):
+        if len(ix) != len(msgs):
+            raise ValueError('aggregate_verify_indexed_batch: set %d has %d indices and %d messages' % (s, len(ix), len(msgs)))
+    soffs = _count_offsets([ix for ix, _, _ in sets])
+    idx = _u32([i for ix, _, _ in sets for i in ix])
+    moffs, mblob = _offsets([bytes(m) for _, msgs, _ in sets for m in msgs])
+    sgb = b''.join(sig for _, _, sig in sets)
+    stv = (ctypes.c_int32 * max(n_sets, 1))()
+    aux = (ctypes.c_uint64 * (2 * max(n_sets, 1)))()
+    _check(init().blsgpu_aggregate_verify_indexed_batch(scheme, keyset.handle, ctypes.cast(idx, ctypes.c_void_p), _ptr(mblob),
+                                                        ctypes.cast(moffs, ctypes.c_void_p), ctypes.cast(soffs, ctypes.c_void_p), n_sets, _ptr(sgb), fmt,
+                                                        ctypes.cast(stv, ctypes.c_void_p), ctypes.cast(aux, ctypes.c_void_p)))
+    return [(stv[s], (aux[2 * s], aux[2 * s + 1])) for s in range(n_sets)]
+
+
 def verify_shared_batch(sig_group, scheme, groups, fmt=FMT_RAW_PROJ):
     """Signature::verify for items that share messages (blsgpu_verify_shared_batch): `groups` is a list of (msg, pks, sigs), every
     (pks[j], sigs[j]) verified under the group's msg, which is hashed once.  Returns one list of statuses per group -- what
@@ -1338,6 +1360,17 @@ class TensorOps:
         _check(self.lib.blsgpu_verify_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(sigs), self._p(msgs), self._p(offs), n, FMT_RAW_PROJ,
                                                     self._p(st)))
         return st[:n]
+
+    def aggregate_verify_indexed_batch(self, keyset, scheme, idx, msgs, msg_offs, set_offs, n_sets, sigs):
+        """(int32 statuses, int64 aux of shape (n_sets, 2)), both on the device, of n_sets aggregate_verify checks whose pair i has
+        its key at position idx[i] of `keyset`: one message per pair (int64 offsets, one more entry than pairs), the sets' int64
+        offsets into the pairs (n_sets + 1 entries) and one RAW_PROJ aggregate signature per set."""
+        self._sync()
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        aux = self.empty(2 * max(n_sets, 1), self.torch.int64)
+        _check(self.lib.blsgpu_aggregate_verify_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(msgs), self._p(msg_offs), self._p(set_offs),
+                                                              n_sets, self._p(sigs), FMT_RAW_PROJ, self._p(st), self._p(aux)))
+        return st[:n_sets], aux[:2 * n_sets].view(n_sets, 2)
 
     def verify_shared_batch(self, sg, scheme, pks, sigs, item_offs, n_groups, msgs, msg_offs, n):
         """int32 statuses (on the device), one per item, of Signature::verify over n_groups groups that share a message each:

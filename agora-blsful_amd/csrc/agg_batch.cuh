@@ -9,7 +9,9 @@
 //     (util_kernels.cuh) keyed by (set, message bytes);
 //   * agg_first_bad_item: per set, the first identity key and whether the signature is the identity;
 //   * agg_fold_partner: which item multiplies into which in round r of the segmented product;
-//   * agg_decide: the reference's precedence.
+//   * agg_decide: the reference's precedence;
+//   * agg_batch_plan / agg_flat_pair / agg_flat_key: which sets are batched, where flat item i lies in the caller's arrays, and --
+//     for a call over a registered key set (blsgpu_aggregate_verify_indexed_batch) -- which entry of the set is its key.
 #pragma once
 #include <stddef.h>
 #include "verify.cuh"
@@ -109,6 +111,43 @@ BLS_FN int32_t agg_decide(uint32_t dup_old, uint32_t dup_i, bool sig_is_id, uint
   return BLS_OK;
 }
 
+// The plan of a call (host): set s of offs[s] .. offs[s + 1] is batched when it has fewer than max_small pairs, else large.  The
+// batched sets form the flat list in the caller's order: boffs (their item ranges in it, n_b + 1 entries), bsrc (where a set's pairs
+// start in the caller's arrays), bset (its index in the caller's sigs / status / aux).  Returns the largest batched set's size.
+template <class V64, class V32, class VSZ>
+static inline uint64_t agg_batch_plan(const uint64_t* offs, size_t n_sets, uint64_t max_small, V64& boffs, V64& bsrc, V32& bset, VSZ& large,
+                                      uint64_t* tmax_large) {
+  uint64_t tmax_b = 0;
+  *tmax_large = 0;
+  boffs.assign(1, 0);
+  for (size_t s = 0; s < n_sets; s++) {
+    const uint64_t t = offs[s + 1] - offs[s];
+    if (t >= max_small) {
+      large.push_back(s);
+      if (t > *tmax_large) *tmax_large = t;
+    } else {
+      bsrc.push_back(offs[s]);
+      bset.push_back((uint32_t)s);
+      boffs.push_back(boffs.back() + t);
+      if (t > tmax_b) tmax_b = t;
+    }
+  }
+  return tmax_b;
+}
+// pair item i of the flat list (i < T_b = boffs[n_b]), a member of batched set b: its index in the caller's pks / idx / msg_offsets
+BLS_FN uint64_t agg_flat_pair(const uint64_t* boffs, const uint64_t* bsrc, uint32_t b, size_t i) { return bsrc[b] + (i - boffs[b]); }
+// ... and, over a registered key set, the entry that is its key: the flat list REORDERS the caller's pairs (batched sets only, then
+// the signature items), so the sanitised index cidx (one per caller position, k_keyset_check) is reached through src
+// (k_prepare_agg_seg's map), never by the flat index itself
+BLS_FN uint32_t agg_flat_key(const uint32_t* src, const uint32_t* cidx, size_t i) { return cidx[src[i]]; }
+// The Miller values of the M flat items are formed in rounds of at most `round` items (one machine round of lane pairs), all of
+// the same size, a multiple of 32: the round that starts at `first` takes the items first .. first + size, lane pair j the flat item
+// first + j -- key_of, like the pairs and the flags, is indexed by that, not by j
+static inline size_t agg_round_size(size_t M, size_t round) {
+  const size_t n_rounds = (M + round - 1) / round;
+  return n_rounds ? ((M + n_rounds - 1) / n_rounds + 31) / 32 * 32 : 0;
+}
+
 #if defined(__HIPCC__)
 #include "kernels.cuh"
 // two (or one) lanes per item: k_prepare_agg's item (kernels.cuh prepare_agg_item) for every item of the flat list; also writes sid / src
@@ -121,6 +160,8 @@ __global__ void k_first_bad_seg(size_t M, size_t T_b, const uint32_t* sid, const
 __global__ void k_dup_insert_seg(size_t T_b, const uint8_t* msgs, const uint64_t* moffs, const uint32_t* sid, const uint32_t* src, uint32_t mask,
                                  uint32_t* tab, uint32_t* minidx, uint32_t* slot_of);
 __global__ void k_dup_find_seg(size_t T_b, const uint32_t* sid, const uint64_t* boffs, const uint32_t* slot_of, const uint32_t* minidx, uint32_t* best);
+// key_of[i] = agg_flat_key(src, cidx, i) for every pair item: what k_linesp_keyed (kernels.cuh) indexes by the flat index
+__global__ void k_agg_flat_keys(size_t T_b, const uint32_t* src, const uint32_t* cidx, uint32_t* key_of);
 // round r of the segmented product over the pair items of the Fp12 workspace; then, one lane per set, the set's product times its
 // signature item as record b of a workspace of stride n_b
 __global__ void k_f12_fold_seg(size_t T_b, int r, const uint32_t* sid, const uint64_t* boffs, uint32_t* fws, size_t stride);

@@ -52,6 +52,7 @@ enum {
   KID_ELGAMAL_PREP, KID_ELGAMAL_LADDER, KID_ELGAMAL_TRANSCRIPT, KID_ELGAMAL_SUB,   // blsgpu_elgamal_proof_verify_batch / blsgpu_elgamal_open_batch
   KID_GROUP_LINES, KID_PREPARE_SHARED,   // blsgpu_verify_shared_batch (verify_shared.cuh; k_group_affine and k_shared_expand count under k_prepare_shared, k_lines2s_shared under k_lines2s)
   KID_KEYSET_LINES, KID_LINES_KEYED,     // key sets with line tables (keyset.cuh): the build at creation, and the line kernel that reads both rows
+  KID_LINESP_KEYED,                      // ... and the one of the batched aggregate verify over such a set (in the place of k_linesp)
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -68,7 +69,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_keyset_seal", "k_keyset_build", "k_keyset_check", "k_keyset_gather", "k_keyset_accumulate_seg", "k_keyset_mul", "k_keyset_fin",
                                     "k_elgamal_prep", "k_elgamal_ladder", "k_elgamal_transcript", "k_elgamal_sub",
                                     "k_group_lines", "k_prepare_shared",
-                                    "k_keyset_lines", "k_lines2s_keyed"};
+                                    "k_keyset_lines", "k_lines2s_keyed",
+                                    "k_linesp_keyed"};
 
 struct Ctx {
   int dev = -1;
@@ -4497,49 +4499,32 @@ int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const
 API_CATCH
 
 // ---- batched aggregate verify (agg_batch.cuh): n_sets independent AggregateSignature::verify checks in one call
-int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, const uint8_t* msgs, const uint64_t* msg_offsets,
-                                  const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) try {
-  int rc = check_common(sig_group, scheme, fmt);
-  if (rc) return rc;
-  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
-  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  std::vector<uint64_t> offs;
-  if ((rc = read_offsets(set_offsets, n_sets, "set_offsets", offs))) return rc;
+// The call after its argument checks, shared by blsgpu_aggregate_verify_batch (keys by value) and
+// blsgpu_aggregate_verify_indexed_batch (keys named in a registered key set).  offs: the checked set_offsets, T pairs, `total`
+// message bytes; every other pointer as the caller gave it (host or device).  The keys come from `keys`:
+//   keys.arena_bytes                          what stage() takes from the arena
+//   keys.stage(c, &kp, &key_table, &cidx)     after the arena is reserved: the T keys as a DEVICE buffer in the signatures' format
+//                                             (kp), and optionally the rows of a key set with line tables plus the sanitised index
+//                                             of every caller position -- then the batched sets' pair items take their line values
+//                                             from the rows (k_linesp_keyed) and no item walks a point
+//   keys.fin(c, d_status, d_aux)              after the last kernel, before the results leave the device
+extern "C++" {
+template <class Keys>
+static int aggregate_batch_run(Ctx* c, int sig_group, int scheme, const Keys& keys, const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t total,
+                               const std::vector<uint64_t>& offs, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) {
+  int rc;
   const size_t T = (size_t)offs[n_sets];
-  if (T >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more pairs in one call");
-  if (T && !pks) return fail(BLSGPU_E_ARG, "null argument");
-  if (n_sets == 0) return 0;
   // plan: a set of at least BLSGPU_AGG_BATCH_MAX pairs runs one at a time through the kernels of blsgpu_aggregate_verify
   // (aggregate_enqueue: its per-entry product form is what wins at tens of thousands of pairs), all others together through the
-  // segmented kernels of agg_batch.cuh.  One large set alone IS blsgpu_aggregate_verify (on one device: no sharding).
+  // segmented kernels of agg_batch.cuh.
   const uint64_t max_small = (uint64_t)knobs().agg_batch_max;
-  if (n_sets == 1 && T >= max_small) {
-    NestedScope ns;
-    return blsgpu_aggregate_verify(sig_group, scheme, pks, msgs, msg_offsets, T, sigs, fmt, status, aux);
-  }
-  CTX_ACQUIRE(c);
   const bool basic = scheme == BLSGPU_SCHEME_BASIC;
-  uint64_t total = 0;
-  if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + T, 8, hipMemcpyDeviceToHost));
-  else total = msg_offsets[T];
-  if (total && !msgs) return fail(BLSGPU_E_ARG, "null argument");
   // the batched sets as one flat list: boffs (their item ranges), bsrc (where a set's pairs start in the caller's arrays), bset (its index)
-  std::vector<uint64_t> boffs(1, 0), bsrc;
+  std::vector<uint64_t> boffs, bsrc;
   std::vector<uint32_t> bset;
   std::vector<size_t> large;
-  uint64_t tmax_b = 0, tmax_large = 0;
-  for (size_t s = 0; s < n_sets; s++) {
-    const uint64_t t = offs[s + 1] - offs[s];
-    if (t >= max_small) {
-      large.push_back(s);
-      tmax_large = std::max(tmax_large, t);
-    } else {
-      bsrc.push_back(offs[s]);
-      bset.push_back((uint32_t)s);
-      boffs.push_back(boffs.back() + t);
-      tmax_b = std::max(tmax_b, t);
-    }
-  }
+  uint64_t tmax_large = 0;
+  const uint64_t tmax_b = agg_batch_plan(offs.data(), n_sets, max_small, boffs, bsrc, bset, large, &tmax_large);
   const size_t n_b = bset.size(), T_b = (size_t)boffs.back(), M = n_b ? T_b + n_b : 0;
   const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt);
   size_t dup_cap = 64;
@@ -4547,7 +4532,7 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
   const bool dup_b = basic && T_b > 0;
   // Miller values in rounds of at most one machine round of lane pairs (65,536 items), all of the same size; the final
   // exponentiation in chunks of the same bound; both pass through the context's line workspace
-  const size_t round = 65536, n_rounds = (M + round - 1) / round, per_round = n_rounds ? ((M + n_rounds - 1) / n_rounds + 31) / 32 * 32 : 0;
+  const size_t round = 65536, per_round = agg_round_size(M, round);
   const size_t fx_chunk = std::min(n_b, miller_chunk_items() ? miller_chunk_items() : round);
   const size_t m_large = (size_t)tmax_large + 1;
   const size_t large_bytes = large.empty() ? 0
@@ -4555,21 +4540,22 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
                                                  (basic ? dup_ws_bytes((size_t)tmax_large) : 0);
   const size_t batch_bytes = n_b ? pad256(8 * (n_b + 1)) + pad256(8 * n_b) + pad256(4 * n_b) + pad256(4 * M) + 2 * pad256(4 * (T_b ? T_b : 1)) +
                                        pad256((size_t)WS_PAIR1_WORDS * 4 * M) + pad256((size_t)WS_F_WORDS * 4 * M) + pad256((size_t)WS_F_WORDS * 4 * n_b) +
-                                       4 * pad256(4 * n_b) + (dup_b ? 2 * pad256(4 * dup_cap) + pad256(4 * T_b) : 0)
+                                       4 * pad256(4 * n_b) + (dup_b ? 2 * pad256(4 * dup_cap) + pad256(4 * T_b) : 0) + keys.flat_bytes(T_b)
                                  : 0;
-  rc = arena_reserve(c, pad256(psz * T) + pad256(ssz * n_sets) + pad256(total) + pad256(8 * (T + 1)) + pad256(4 * n_sets) + pad256(16 * n_sets) + batch_bytes +
+  rc = arena_reserve(c, keys.arena_bytes + pad256(ssz * n_sets) + pad256(total) + pad256(8 * (T + 1)) + pad256(4 * n_sets) + pad256(16 * n_sets) + batch_bytes +
                             large_bytes + 16384);
   if (rc) return rc;
   c->arena_off = 0;
-  const void *d_pks = nullptr, *d_sigs, *d_msgs, *d_moffs;
-  if (T && (rc = stage_in(c, pks, psz * T, &d_pks))) return rc;
+  const void *d_sigs, *d_msgs, *d_moffs;
+  const uint8_t* kp = nullptr;
+  const uint32_t *key_table = nullptr, *d_cidx = nullptr;
+  if ((rc = keys.stage(c, &kp, &key_table, &d_cidx))) return rc;
   if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (T + 1), &d_moffs))) return rc;
   int32_t* d_status = stage_out<int32_t>(c, status, 4 * n_sets);
   uint64_t* d_aux = aux ? stage_out<uint64_t>(c, aux, 16 * n_sets) : nullptr;
   if (!d_status || (aux && !d_aux)) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  const uint8_t* kp = (const uint8_t*)d_pks;
   const uint8_t* sp = (const uint8_t*)d_sigs;
   const uint8_t* mp = (const uint8_t*)d_msgs;
   const uint64_t* mo = (const uint64_t*)d_moffs;
@@ -4595,6 +4581,7 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
       d_minidx = mem.take<uint32_t>(4 * dup_cap);
       d_slot = mem.take<uint32_t>(4 * T_b);
     }
+    uint32_t* d_key_of = key_table && T_b ? mem.take<uint32_t>(4 * T_b) : nullptr;
     if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
     const size_t lanes_round = row_stride(lanes_for(per_round)), lanes_fx = row_stride(lanes_for(fx_chunk));
     if (lines_reserve(c, std::max((size_t)MILLER_ENTRIES * LINE3_WORDS_H * 4 * lanes_round, (size_t)FX_STORE_WORDS * 4 * lanes_fx)))
@@ -4616,11 +4603,17 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
     });
     // 2. one Miller value per item (a flagged item's is 1): no partial product spans two sets because none is formed.  k_miller1s
     // multiplies items a fixed stride apart, which ragged sets cannot align with, so the remainder of a round takes the line kernels too.
+    // (over a key set with line tables: every item's rows come from a table -- a pair item's from its key's, found through src)
+    if (d_key_of) KL(KID_AGG_SEG_INDEX, k_agg_flat_keys, dim3(blocks_for(T_b)), dim3(BLS_BLOCK), T_b, (const uint32_t*)d_src, d_cidx, d_key_of);
     for (size_t first = 0; first < M; first += per_round) {
       const size_t cnt = std::min(per_round, M - first), nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
       const dim3 grid((unsigned)(nlanes / BLS_BLOCK));
-      KL(KID_LINESP, k_linesp, grid, dim3(BLS_BLOCK), cnt, cnt, M, (const uint32_t*)(d_pairs + first), (const int32_t*)(d_bad + first), c->lines_ws, c->lines_ws,
-         lanes, (size_t)0, cnt, 1);
+      if (key_table)
+        KL(KID_LINESP_KEYED, k_linesp_keyed, grid, dim3(BLS_BLOCK), T_b, first, cnt, M, (const uint32_t*)d_pairs, (const int32_t*)d_bad, c->lines_ws, lanes, key_table,
+           (const uint32_t*)d_key_of);
+      else
+        KL(KID_LINESP, k_linesp, grid, dim3(BLS_BLOCK), cnt, cnt, M, (const uint32_t*)(d_pairs + first), (const int32_t*)(d_bad + first), c->lines_ws, c->lines_ws,
+           lanes, (size_t)0, cnt, 1);
       KL(KID_MILLERFP, k_millerfp3, grid, dim3(BLS_BLOCK), cnt, cnt, 1, (const int32_t*)(d_bad + first), (const uint32_t*)c->lines_ws, lanes, d_f + first, M, (size_t)0);
     }
     // 3. every set's product: ceil(log2(largest batched set)) halving rounds over all pair items, then times the signature's value
@@ -4667,8 +4660,51 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
       HIPCK(hipGetLastError());
     }
   }
+  if ((rc = keys.fin(c, d_status, d_aux))) return rc;
   if (aux && (rc = stage_back(c, aux, d_aux, 16 * n_sets))) return rc;
   return status_out_and_sync(c, status, d_status, n_sets);
+}
+}  // extern "C++"
+
+// the keys of the by-value call: the caller's array, staged
+struct agg_keys_by_value {
+  const void* pks;
+  size_t bytes, arena_bytes;
+  size_t flat_bytes(size_t) const { return 0; }
+  int stage(Ctx* c, const uint8_t** kp, const uint32_t**, const uint32_t**) const {
+    const void* d_pks = nullptr;
+    int rc;
+    if (bytes && (rc = stage_in(c, pks, bytes, &d_pks))) return rc;
+    *kp = (const uint8_t*)d_pks;
+    return 0;
+  }
+  int fin(Ctx*, int32_t*, uint64_t*) const { return 0; }
+};
+int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                  const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc) return rc;
+  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
+  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  std::vector<uint64_t> offs;
+  if ((rc = read_offsets(set_offsets, n_sets, "set_offsets", offs))) return rc;
+  const size_t T = (size_t)offs[n_sets];
+  if (T >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more pairs in one call");
+  if (T && !pks) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  // One large set alone IS blsgpu_aggregate_verify (on one device: no sharding).
+  if (n_sets == 1 && T >= (uint64_t)knobs().agg_batch_max) {
+    NestedScope ns;
+    return blsgpu_aggregate_verify(sig_group, scheme, pks, msgs, msg_offsets, T, sigs, fmt, status, aux);
+  }
+  CTX_ACQUIRE(c);
+  uint64_t total = 0;
+  if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + T, 8, hipMemcpyDeviceToHost));
+  else total = msg_offsets[T];
+  if (total && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  const size_t psz = pk_size(sig_group, fmt);
+  const agg_keys_by_value keys = {pks, psz * T, pad256(psz * T)};
+  return aggregate_batch_run(c, sig_group, scheme, keys, msgs, msg_offsets, total, offs, n_sets, sigs, fmt, status, aux);
 }
 API_CATCH
 
@@ -5518,6 +5554,83 @@ int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   HIPCK(hipGetLastError());
   return status_out_and_sync(c, status, d_status, n);
+}
+API_CATCH
+
+// The batched aggregate verify over a key set: pair i's key is the entry at position idx[i].  k_keyset_check with the call's
+// set_offsets (per-set precedence, and with line tables the one word that says whether every named entry has rows),
+// k_keyset_gather of the affine records in the caller's pair order (k_keyset_to_proj for RAW_PROJ signatures), then the body of
+// blsgpu_aggregate_verify_batch on the gathered keys -- with line tables and signatures in G1 its line kernel is k_linesp_keyed,
+// which reads a pair item's rows at cidx[src[i]] -- and k_keyset_fin_aux: the precedence over status AND aux.
+struct agg_keys_indexed {
+  const KeySet& k;
+  const void* idx;
+  const std::vector<uint64_t>& offs;
+  size_t n_sets;
+  int fmt;
+  bool want_lines;           // a set with line tables, signatures in G1: the call may take the keyed line kernel
+  size_t arena_bytes;
+  mutable unsigned long long* d_pre = nullptr;
+  static size_t bytes_for(const KeySet& k, size_t T, size_t n_sets, int fmt) {
+    return 2 * pad256(4 * (T ? T : 1)) + pad256(8 * (n_sets + 1)) + pad256(8 * n_sets) + pad256(pk_size(k.sig_group, BLSGPU_FMT_RAW_AFFINE) * (T ? T : 1)) +
+           pad256(pk_size(k.sig_group, fmt) * (T ? T : 1)) + 256;
+  }
+  size_t flat_bytes(size_t T_b) const { return want_lines ? pad256(4 * (T_b ? T_b : 1)) : 0; }
+  int stage(Ctx* c, const uint8_t** kp, const uint32_t** key_table, const uint32_t** cidx) const {
+    const size_t T = (size_t)offs[n_sets], asz = pk_size(k.sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(k.sig_group, fmt);
+    int rc;
+    const void* d_idx = nullptr;
+    if (T && (rc = stage_in(c, idx, 4 * T, &d_idx))) return rc;
+    const uint64_t* o;
+    if ((rc = upload_offsets(c, offs, &o))) return rc;
+    Carver mem{c};
+    uint32_t* d_cidx = mem.take<uint32_t>(4 * (T ? T : 1));
+    d_pre = mem.take<unsigned long long>(8 * n_sets);
+    uint8_t* d_aff = mem.take<uint8_t>(asz * (T ? T : 1));
+    uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(ksz * (T ? T : 1));
+    uint32_t* d_walk = want_lines && T ? mem.take<uint32_t>(4) : nullptr;
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, T, o, n_sets, d_cidx, d_pre, d_walk))) return rc;
+    if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, key_table))) return rc;      // a named finite entry without rows: every item walks
+    if (T) {
+      const size_t cnt_ = T;
+      KEYSET_GATHER(asz / 4, k.aff, 0, d_aff);
+      if (d_keys != d_aff)
+        with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, (const uint8_t*)d_aff, d_keys); });
+      HIPCK(hipGetLastError());
+    }
+    *kp = d_keys;
+    *cidx = d_cidx;
+    return 0;
+  }
+  int fin(Ctx* c, int32_t* d_status, uint64_t* d_aux) const {
+    KL(KID_KEYSET_FIN, k_keyset_fin_aux, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const unsigned long long*)d_pre, d_status, d_aux);
+    HIPCK(hipGetLastError());
+    return 0;
+  }
+};
+int blsgpu_aggregate_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                          const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) try {
+  KeySet k;
+  int rc = keyset_find(keyset, k);
+  if (rc) return rc;
+  const int sig_group = k.sig_group;
+  if ((rc = check_common(sig_group, scheme, fmt))) return rc;
+  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
+  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  std::vector<uint64_t> offs;
+  if ((rc = read_offsets(set_offsets, n_sets, "set_offsets", offs))) return rc;
+  const size_t T = (size_t)offs[n_sets];
+  if (T >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more pairs in one call");
+  if (T && !idx) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  CTX_ACQUIRE_ON(c, k.devidx);                 // on the key set's device, without sharding (one large set alone too: its keys are gathered here)
+  uint64_t total = 0;
+  if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + T, 8, hipMemcpyDeviceToHost));
+  else total = msg_offsets[T];
+  if (total && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  const agg_keys_indexed keys = {k, idx, offs, n_sets, fmt, k.lines != nullptr && sig_group == 1, agg_keys_indexed::bytes_for(k, T, n_sets, fmt)};
+  return aggregate_batch_run(c, sig_group, scheme, keys, msgs, msg_offsets, total, offs, n_sets, sigs, fmt, status, aux);
 }
 API_CATCH
 

@@ -253,6 +253,11 @@ __global__ void k_cyc_run4(size_t count, uint32_t* vp, size_t lanes, const int32
 __global__ void k_linesp(size_t mm, size_t half, size_t stride, const uint32_t* pairs, const int32_t* bad, uint32_t* lines, uint32_t* lines3, size_t lanes, size_t first_v, size_t count_v, int pass);
 __global__ void k_linesp4(size_t cnt, size_t stride, const uint32_t* pairs, const int32_t* bad, uint32_t* lines3, size_t lanes);
 __global__ void k_lines_fixed(size_t stride, const uint32_t* pairs, const int32_t* bad, uint32_t* lines3, size_t lanes, int fixed_g2);
+// the keyed form of k_linesp pass 1 (blsgpu_aggregate_verify_indexed_batch, Bls12381G1Impl over a key set with line tables): flat item
+// first + j of the batched list takes its rows from key_table + (key_of[first + j] 68 + e) 4 FP_NL (a pair item, index below T_b) or
+// from G2NEGC_LINES_N (a signature item): no G2 point is walked
+__global__ void k_linesp_keyed(size_t T_b, size_t first, size_t cnt, size_t stride, const uint32_t* pairs, const int32_t* bad, uint32_t* lines3, size_t lanes,
+                               const uint32_t* key_table, const uint32_t* key_of);
 __global__ void k_millerfp(size_t count_v, size_t q, int group, const uint32_t* lines, size_t lanes, uint32_t* fws, size_t stride, size_t out0);
 __global__ void k_millerfp3(size_t count, size_t q, int group, const int32_t* bad, const uint32_t* lines3, size_t lanes, uint32_t* fws, size_t stride, size_t out0);
 __global__ void k_line_quad(size_t count, size_t q, const int32_t* bad, const uint32_t* lines3, size_t lanes, uint32_t* fout, size_t sout, size_t rout, size_t oout);
@@ -1811,6 +1816,54 @@ __global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES) k_lines_fixed(size
     fp2_load(c, rows[e] + 2 * FP_NL);
     fp2_mul_fp(l2, c, x1);
     line3_st(lines3, lanes, hi, e, n0, l2, l3);
+  }
+}
+// The plain line values of the flat list of a batched aggregate verify with EVERY row read from a table (registered key sets with
+// BLSGPU_KEYSET_LINES, Bls12381G1Impl: keyset.cuh, agg_batch.cuh) -- k_lines_fixed's entry for many items, in the place of k_linesp
+// pass 1: same grid, same lines3 workspace, item j of the round at lanes 2 j, 2 j + 1.  The round covers the flat items
+// [first, first + cnt); `pairs`, `bad` and key_of are indexed by the FLAT index i = first + j, not by j.  A pair item (i < T_b) is
+// (H'(m), pk) with pk the set's entry key_of[i], whose normalised rows k_keyset_lines left in key_table; a signature item
+// (i >= T_b) is (sig, -[c] g2) with the constant rows G2NEGC_LINES_N.  An entry is one row load (n0 and c, this lane's
+// components), one Fp2-by-Fp product and the store (pairing.cuh miller_line3_row): no curve arithmetic, no LDS, and the G2 member
+// of `pairs` is never read.  A flagged item returns before any table read: a position that is out of range, invalid or the
+// identity gathered the zero record and was flagged by the prepare kernel.  Addressing as lines_step_keyed: the table's base stays
+// wave-uniform and the row is a 32-bit per-lane WORD offset koff + e 4 FP_NL with koff = key 68 4 FP_NL (the host keeps the
+// table below 2^32 bytes).
+__global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES)
+k_linesp_keyed(size_t T_b, size_t first, size_t cnt, size_t stride, const uint32_t* pairs, const int32_t* bad, uint32_t* lines3, size_t lanes,
+               const uint32_t* key_table, const uint32_t* key_of) {
+  const uint32_t t = blockIdx.x * BLS_BLOCK + threadIdx.x;
+  const size_t j = t >> 1;
+  if (j >= cnt) return;
+  const size_t i = first + j;                          // the item's index in the FLAT LIST: pairs, bad and key_of are indexed by it
+  if (bad[i] != 0) return;                             // before any table read
+  fp x, y;
+  ws_ld_fp(x, pairs, stride, i, 0);
+  ws_ld_fp(y, pairs, stride, i, W1);
+  const bool is_sig = i >= T_b;
+  const uint32_t lo = lane_hi() ? FP_NL : 0;
+  const uint32_t koff = (is_sig ? 0u : key_of[i] * (uint32_t)(MILLER_ENTRIES * 4 * FP_NL)) + lo;
+#pragma unroll 1
+  for (int e = 0; e < MILLER_ENTRIES; e++) {
+    hfp2 n0, c, l0, l2, l3;
+    if (is_sig) {
+      gc_u32* tr = uni_global(G2NEGC_LINES_N[e]);
+#pragma unroll
+      for (int k = 0; k < FP_NL; k++) {
+        n0.v.l[k] = (int32_t)g_ld(tr, lo + k);
+        c.v.l[k] = (int32_t)g_ld(tr, lo + 2 * FP_NL + k);
+      }
+    } else {
+      gc_u32* tr = uni_global(key_table);
+      const uint32_t o = koff + uni_u32((uint32_t)e) * (4 * FP_NL);
+#pragma unroll
+      for (int k = 0; k < FP_NL; k++) {
+        n0.v.l[k] = (int32_t)g_ld(tr, o + k);
+        c.v.l[k] = (int32_t)g_ld(tr, o + 2 * FP_NL + k);
+      }
+    }
+    miller_line3_row(l0, l2, l3, n0, c, x, y);
+    line3_st(lines3, lanes, t, e, l0, l2, l3);
   }
 }
 __global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES) __attribute__((disable_tail_calls))

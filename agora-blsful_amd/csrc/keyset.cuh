@@ -111,6 +111,9 @@ __global__ void k_keyset_lines(size_t k0, size_t cnt, const uint8_t* recs, uint3
 __global__ void k_keyset_check(size_t n, const uint64_t* offs, size_t n_sets, const uint32_t* idx, uint64_t n_keys, const int32_t* kstatus,
                                uint32_t* cidx, unsigned long long* pre, const int32_t* nolines, uint32_t* walk);
 __global__ void k_keyset_fin(size_t n_sets, const unsigned long long* pre, int32_t* status);
+// ... and over a call that also reports two aux words per set (blsgpu_aggregate_verify_indexed_batch): a set the precedence decides
+// gets aux (0, 0); aux may be null
+__global__ void k_keyset_fin_aux(size_t n_sets, const unsigned long long* pre, int32_t* status, uint64_t* aux);
 // dst record i = src record cidx[i] (words 32-bit words each; zeros for KEYSET_SKIP); legacy: the Dash header transcode of byte 0
 __global__ void k_keyset_gather(size_t n, size_t words, const uint32_t* cidx, const uint32_t* src, int legacy, uint32_t* dst);
 // RAW_AFFINE -> RAW_PROJ (blsgpu_keyset_get)

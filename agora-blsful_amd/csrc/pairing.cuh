@@ -299,6 +299,16 @@ BLS_FN void miller_line5_fixed(line5_t<F2>& L, g2_hom_t<F2>& T, bool add, const 
   const miller_regs<F2> st = {T, xp, yp, &xq, &yq};
   miller_line5_fixed_at(L, st, add, x1, y1, row);
 }
+// The PLAIN (one-pair) line value of an entry whose G2 argument is given as such a row, (n0, c) = (l0 / h, g / h), at P = (x, y):
+// n0 + (c x) w^2 + y w^3, the three coefficients k_linesp pass 1 stores for a walked point (up to the factor in Fp2 that the
+// normalisation divided out).  Shared by the line kernel that reads every row from a table (kernels.cuh k_linesp_keyed) and the
+// host harness (tests/hostsim_agg_keyed).
+template <class F2>
+BLS_FN void miller_line3_row(F2& l0, F2& l2, F2& l3, const F2& n0, const F2& c, const fp& x, const fp& y) {
+  l0 = n0;
+  fp2_mul_fp(l2, c, x);
+  fp2_from_fp(l3, y);
+}
 // ... and for two general pairs
 template <class F2>
 BLS_FN void miller_line5_pair(line5_t<F2>& L, g2_hom_t<F2>& T0, g2_hom_t<F2>& T1, bool add, const aff<F2>* Q, const g1_aff* P) {

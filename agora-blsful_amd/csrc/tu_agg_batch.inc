@@ -4,6 +4,7 @@
 // of M = T_b + n_b items (pairs, then one signature item per set); the Miller values between k_prepare_agg_seg and k_f12_fold_seg
 // are k_linesp pass 1 + k_millerfp3, the verdicts between k_agg_batch_mark and k_agg_batch_fin k_finalexp2s (kernels.cuh).
 //   k_prepare_agg_seg : hash-to-curve, identity flag and affine pair of every item (k_prepare_agg's item), and the maps sid / src
+//   k_agg_flat_keys   : over a registered key set, the entry that is each pair item's key (k_linesp_keyed reads its rows)
 //   k_first_bad_seg   : per set the first identity key and whether the signature is the identity (sig_core.rs:155-167)
 //   k_dup_insert_seg / k_dup_find_seg : Basic's duplicate rule per set (sig_basic.rs:46-58)
 //   k_f12_fold_seg    : one halving round of every set's product; k_f12_fold_seg_out: times the signature's value, one record per set
@@ -29,7 +30,7 @@ __global__ void __launch_bounds__(BLS_BLOCK, 2) k_prepare_agg_seg(size_t M, size
     return;
   }
   const uint32_t b = ragged_set_of(boffs, n_b, i);
-  const size_t p = (size_t)(bsrc[b] + (i - boffs[b]));
+  const size_t p = (size_t)agg_flat_pair(boffs, bsrc, b, i);
   if (lane2 <= 0) {
     sid[i] = b;
     src[i] = (uint32_t)p;
@@ -55,6 +56,10 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_dup_find_seg(size_t T_b, const ui
                                                          const uint32_t* minidx, uint32_t* best) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < T_b) agg_dup_find((uint32_t)i, sid, boffs, slot_of, minidx, best);
+}
+__global__ void __launch_bounds__(BLS_BLOCK) k_agg_flat_keys(size_t T_b, const uint32_t* src, const uint32_t* cidx, uint32_t* key_of) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < T_b) key_of[i] = agg_flat_key(src, cidx, i);
 }
 // what the rules decide for set b, and its aux
 __device__ __forceinline__ int32_t agg_batch_decide(size_t b, const uint64_t* boffs, const uint32_t* best, const uint32_t* slot_of, const uint32_t* minidx,

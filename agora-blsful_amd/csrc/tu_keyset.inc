@@ -6,6 +6,7 @@
 //   k_keyset_lines          : create: the line table of G2 keys, one lane pair per key, ONE inversion per key
 //   k_keyset_check          : every position's index and entry status, once; the sanitised indices and each set's precedence
 //   k_keyset_fin            : the precedence over the statuses of the verification tail
+//   k_keyset_fin_aux        : the same over statuses and aux words (the batched aggregate verify)
 //   k_keyset_gather         : records by index (affine records, compressed bytes with the Legacy header transcode, statuses)
 //   k_keyset_accumulate_seg : the strip sum of the batched multi verify over table[idx[i]], mixed additions only
 //   k_keyset_mul            : scalar times entry, from the fixed-base table or by the joint NAF ladder of the threshold recovery
@@ -56,6 +57,14 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_fin(size_t n_sets, const u
   if (s >= n_sets) return;
   const uint64_t key = pre[s];
   if (key != KEYSET_PRE_NONE) status[s] = keyset_pre_status(key);
+}
+__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_fin_aux(size_t n_sets, const unsigned long long* pre, int32_t* status, uint64_t* aux) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_sets) return;
+  const uint64_t key = pre[s];
+  if (key == KEYSET_PRE_NONE) return;
+  status[s] = keyset_pre_status(key);
+  if (aux) aux[2 * s] = aux[2 * s + 1] = 0;
 }
 // one lane per 32-bit word of the output
 __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_gather(size_t n, size_t words, const uint32_t* cidx, const uint32_t* src, int legacy,

@@ -563,7 +563,9 @@ int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t
  * flags & BLSGPU_KEYSET_LINES (Bls12381G1Impl, keys in G2; accepted and without effect for sig_group 2, whose keys have no lines)
  * also derives every key's 68 normalised Miller-loop rows (15,232 bytes per key; the reference's G2Prepared::from(pk), kept instead
  * of recomputed per call): blsgpu_verify_indexed_batch and blsgpu_verify_shared_indexed_batch on the lane-split path (more than
- * BLSGPU_COOP_MAX items) then read rows where they walked the key, under every scheme.  The lines are not built, and the set works
+ * BLSGPU_COOP_MAX items) then read rows where they walked the key, under every scheme, and so do the batched sets of
+ * blsgpu_aggregate_verify_indexed_batch (whatever their number), whose signature items read the constant rows of -[c] g2 as
+ * well.  The lines are not built, and the set works
  * without them, when they would not stay below 2^32 bytes (more than 281,970 keys), when together with the fixed-base tables they
  * would exceed BLSGPU_KEYSET_TABLE_MB MiB, or when the device has no room.  A call that names a finite entry whose rows are
  * unusable (no key of order r; raw input only) walks the keys of all its items.  Line tables never change a status.
@@ -581,7 +583,7 @@ int blsgpu_keyset_get(uint64_t handle, const uint32_t* idx, size_t count, int fm
 int blsgpu_keyset_mul(uint64_t handle, const uint32_t* idx, const uint8_t* scalars, size_t count, void* out);
 
 /* The batched entry points with (keyset, idx) in place of the keys: blsgpu_multi_verify_batch, blsgpu_verify_secure_batch,
- * blsgpu_sum_batch and blsgpu_verify_batch (one key per item) over positions in a key set.  sig_group comes from the key set and
+ * blsgpu_sum_batch, blsgpu_verify_batch (one key per item) and blsgpu_aggregate_verify_batch over positions in a key set.  sig_group comes from the key set and
  * fmt (RAW_PROJ / RAW_AFFINE) describes the signatures only; idx, the offsets, sigs, msgs and status may be host or device memory.
  * status[s] is the first of: BLSGPU_E_ARG (-3, in the status slot; the call still returns 0 and the other sets are unaffected)
  * when the set names an index that is not below the key set's size -- nothing outside the table is read; the creation status of
@@ -596,6 +598,24 @@ int blsgpu_verify_secure_indexed_batch(int scheme, uint64_t keyset, const uint32
 int blsgpu_sum_indexed_batch(uint64_t keyset, const uint32_t* idx, const uint64_t* offsets, size_t n_sets, void* out /* RAW_PROJ */);
 int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint8_t* msgs,
                                 const uint64_t* msg_offsets, size_t n, int fmt, int32_t* status);
+/* blsgpu_aggregate_verify_batch with pair i's key at position idx[i] of the key set (idx has set_offsets[n_sets] = T entries):
+ * AggregateSignature::verify, many keys with one message each, over a registered key set.  sig_group comes from the key set and
+ * fmt (RAW_PROJ / RAW_AFFINE) describes the signatures only; set_offsets, msg_offsets (T + 1 entries), msgs, aux (NULL or
+ * 2 n_sets entries) and the T < 2^32 rule are the by-value entry point's.  Every pointer may be host or device memory; a device
+ * status / aux stays on the device.  n_sets == 0 returns 0.  An unknown or destroyed handle, offsets that decrease or do not
+ * start at 0, and a null required argument are BLSGPU_E_ARG, and no status is written.  The call runs on the key set's device,
+ * without sharding.
+ * status[s] is the first of: BLSGPU_E_ARG in the slot when the set names an index that is not below the key set's size (nothing
+ * outside the table is read); the creation status of the first invalid entry the set names, in input order; otherwise exactly
+ * what blsgpu_aggregate_verify_batch returns for the gathered keys -- Basic's duplicate-message rule per set, the identity
+ * signature, the first identity key with its 1-based index in aux, the pairing product, the empty-set rules.  The identity is a
+ * valid entry (BLSGPU_PK_IDENTITY as by value), repeated indices are repeated keys, and a set decided by one of the first two rules
+ * gets aux (0, 0); its neighbours never see it.  Sets below BLSGPU_AGG_BATCH_MAX pairs are batched, larger ones run one at a time
+ * on the gathered keys, as by value.  Over a set with line tables (BLSGPU_KEYSET_LINES, Bls12381G1Impl) no item of the batched
+ * sets walks a G2 point; a call that names a finite entry without usable rows walks all its items.  Line tables never change
+ * a status or an aux value. */
+int blsgpu_aggregate_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                          const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux);
 
 /* ---- Shared-message verify: Signature::verify (src/signature.rs:130-138) for items that come in GROUPS under one message each --
  * the signature shares of a signing session checked one by one against the members' key shares (PublicKeyShare::verify,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Registered key sets against keys by value: what the index-addressed entry points and the fixed-base tables cost and save.
 
-usage: python tools/bench_keyset.py [--reps 5] [--table 16384] [--shapes 0,1,..] [--out profiles/keyset_bench.json]
+usage: python tools/bench_keyset.py [--lines | --agg] [--reps 5] [--table 16384] [--shapes 0,1,..] [--out profiles/keyset_bench.json]
 Every input lives on the device (TensorOps).  Per shape, indices are drawn at random from a table of --table keys k * g
 (blsgpu_sign_batch) and four things are timed, each the median of --reps calls:
   (a) the non-indexed entry point on the same keys laid out contiguously (three repeats of the whole measurement: their range is the
@@ -17,7 +17,15 @@ Bls12381G1Impl, Basic: blsgpu_verify_batch / blsgpu_verify_indexed_batch at 8,19
 blsgpu_verify_shared_batch / blsgpu_verify_shared_indexed_batch at 64 x 1,024 and 400 x 400, with (a) keys by value, (b) indexed over a
 set without lines, (c) indexed over a set with lines; EVERY cell three medians of --reps calls (their range is the cell's spread),
 the line kernel's time per call from the profile, and blsgpu_keyset_create with and without the flag.  A library that refuses the
-flag (the parent commit) runs (a) and (b) only."""
+flag (the parent commit) runs (a) and (b) only.
+
+--agg [--out profiles/keyset_agg_bench.json]: the batched aggregate verify (many keys with one message each per set), Basic with
+distinct messages: (a) blsgpu_aggregate_verify_batch by value, (b) blsgpu_aggregate_verify_indexed_batch over a set without lines,
+(c) the same over a set with lines, at 4,096 x 16, 1,024 x 64 and 256 x 600 for Bls12381G1Impl and 1,024 x 64 for Bls12381G2Impl
+((a) and (b): its keys have no lines); every cell three medians of --reps calls, the kernel times of one call from the profile,
+and for (c) the bytes per second k_linesp_keyed reached against its own traffic (per item and entry one 224-byte row read and
+336 bytes of line value written, 68 entries, plus the item's G1 point).  A library without the indexed entry point (the parent
+commit) runs (a) only."""
 import argparse
 import json
 import os
@@ -112,9 +120,74 @@ def lines_bench(a, api, ops, torch, dev, sync):
         json.dump(rows, f, indent=1)
 
 
+AGG_SHAPES = [(1, 4096, 16), (1, 1024, 64), (1, 256, 600), (2, 1024, 64)]
+LINESP_KEYED_ITEM_BYTES = 68 * (4 + 6) * 14 * 4 + 2 * 14 * 4      # rows read + line values written + the G1 point
+
+
+def agg_bench(a, api, ops, torch, dev, sync):
+    have = hasattr(ops, 'aggregate_verify_indexed_batch')
+    rng = random.Random(2028)
+    shapes = [AGG_SHAPES[int(i)] for i in a.shapes.split(',')] if a.shapes else AGG_SHAPES
+    pools, made = {}, {}
+    for sg in sorted({s[0] for s in shapes}):
+        ks = [rng.randrange(1, R) for _ in range(a.table)]
+        pks = api.sign_batch(sg, api.BASIC, ks, [b''] * a.table)[0]
+        sigs = api.sign_batch(sg, api.BASIC, ks[:SIG_POOL], [b'bench'] * SIG_POOL)[1]
+        pools[sg] = (torch.tensor(list(b''.join(pks)), dtype=torch.uint8, device=dev).view(a.table, -1),
+                     torch.tensor(list(b''.join(sigs)), dtype=torch.uint8, device=dev).view(SIG_POOL, -1))
+        sync()
+        if have:
+            made[sg] = {lines: api.KeySet.create_device(sg, pools[sg][0].data_ptr(), a.table, api.FMT_RAW_PROJ, lines=lines)
+                        for lines in ((False, True) if sg == 1 else (False,))}
+    rows = [{'table_entries': a.table, 'sets': {'sig_group %d %s lines' % (sg, 'with' if lines else 'without'): k.info()
+                                                for sg, m in made.items() for lines, k in m.items()}}]
+    print(json.dumps(rows[0]), flush=True)
+    for sg, n_sets, t in shapes:
+        n = n_sets * t
+        gen = torch.Generator(device=dev).manual_seed(n + sg)
+        sel = torch.randint(0, a.table, (n,), device=dev, generator=gen)
+        pks_t = pools[sg][0][sel].reshape(-1).contiguous()
+        idx_t = sel.to(torch.int32).contiguous()
+        sigs_t = pools[sg][1][torch.randint(0, SIG_POOL, (n_sets,), device=dev, generator=gen)].reshape(-1).contiguous()
+        moffs, mblob = api._offsets([b'block %05d vote %05d' % (i // t, i % t) for i in range(n)])
+        msgs_t = torch.tensor(list(mblob), dtype=torch.uint8, device=dev)
+        moffs_t = torch.tensor(list(moffs), dtype=torch.int64, device=dev)
+        soffs_t = torch.arange(0, n + 1, t, dtype=torch.int64, device=dev)
+        tail = (msgs_t, moffs_t, soffs_t, n_sets, sigs_t)
+        by_value = lambda: ops.aggregate_verify_batch(sg, api.BASIC, pks_t, *tail)[0]
+        indexed = lambda kset: (lambda: ops.aggregate_verify_indexed_batch(kset, api.BASIC, idx_t, *tail)[0])
+        row = {'kind': 'aggregate', 'shape': 'Bls12381G%dImpl Basic' % sg, 'sig_group': sg, 'sets': n_sets, 'pairs_per_set': t, 'pairs': n, 'reps': a.reps}
+        want = by_value().cpu().tolist()
+        cells = [('a_by_value', by_value)]
+        if have:
+            cells += [(tag, indexed(made[sg][lines])) for tag, lines in (('b_indexed', False), ('c_indexed_lines', True)) if lines in made[sg]]
+        for tag, run in cells:
+            m3 = [median_ms(run, a.reps, sync) for _ in range(3)]
+            row[tag + '_ms'] = [round(x, 3) for x in m3]
+            row[tag + '_spread_ms'] = round(max(m3) - min(m3), 3)
+            row[tag + '_statuses_match'] = run().cpu().tolist() == want
+            api.profile_enable(True)
+            before = {k: v[0] for k, v in api.profile_read().items()}
+            run()
+            km = {k: v[0] - before.get(k, 0.0) for k, v in api.profile_read().items()}
+            api.profile_enable(False)
+            row[tag + '_kernel_ms'] = {k: round(v, 3) for k, v in km.items() if v >= 0.01}
+            if km.get('k_linesp_keyed', 0) > 0:
+                row[tag + '_linesp_keyed_GBps'] = round((n + n_sets) * LINESP_KEYED_ITEM_BYTES / (km['k_linesp_keyed'] * 1e-3) / 1e9, 1)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    for m in made.values():
+        for kset in m.values():
+            kset.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--lines', action='store_true')
+    ap.add_argument('--agg', action='store_true')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--table', type=int, default=16384)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'keyset_bench.json'))
@@ -126,6 +199,10 @@ def main():
     dev = torch.device('cuda', 0)
     ops = api.TensorOps(dev)
     sync = torch.cuda.synchronize
+    if a.agg:
+        if a.out.endswith('keyset_bench.json'):
+            a.out = os.path.join(ROOT, 'profiles', 'keyset_agg_bench.json')
+        return agg_bench(a, api, ops, torch, dev, sync)
     if a.lines:
         if a.out.endswith('keyset_bench.json'):
             a.out = os.path.join(ROOT, 'profiles', 'keyset_lines_bench.json')
