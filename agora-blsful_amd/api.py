@@ -45,6 +45,7 @@ EXPORTS = [
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
     'blsgpu_keyset_create', 'blsgpu_keyset_destroy', 'blsgpu_keyset_info', 'blsgpu_keyset_get', 'blsgpu_keyset_mul',
+    'blsgpu_keyset_update', 'blsgpu_keyset_append',
     'blsgpu_multi_verify_indexed_batch', 'blsgpu_verify_secure_indexed_batch', 'blsgpu_sum_indexed_batch', 'blsgpu_verify_indexed_batch',
     'blsgpu_elgamal_message_generator', 'blsgpu_elgamal_proof_verify_batch', 'blsgpu_elgamal_open_batch',
     'blsgpu_verify_shared_batch', 'blsgpu_verify_shared_indexed_batch',
@@ -182,6 +183,8 @@ def load_library(path=None):
         lib.blsgpu_keyset_info.argtypes = [h, ctypes.POINTER(ci), ctypes.POINTER(h), ctypes.POINTER(ci), ctypes.POINTER(h)]
         lib.blsgpu_keyset_get.argtypes = [h, u32p, sz, ci, vp, i32p]
         lib.blsgpu_keyset_mul.argtypes = [h, u32p, u8p, sz, vp]
+        lib.blsgpu_keyset_update.argtypes = [h, u32p, vp, sz, ci, i32p]
+        lib.blsgpu_keyset_append.argtypes = [h, vp, sz, ci, i32p, ctypes.POINTER(h)]
         lib.blsgpu_multi_verify_indexed_batch.argtypes = [ci, h, u32p, u64p, sz, vp, u8p, u64p, ci, i32p]
         lib.blsgpu_verify_secure_indexed_batch.argtypes = [ci, h, u32p, u64p, sz, vp, u8p, u64p, ci, ci, i32p]
         lib.blsgpu_sum_indexed_batch.argtypes = [h, u32p, u64p, sz, vp]
@@ -699,8 +702,9 @@ def _u32(idx):
 
 class KeySet:
     """A table of public keys that stays on the device (blsgpu_keyset_*): created once from wire bytes or raw points, then named by
-    position in the *_indexed_batch calls.  Immutable; close() (or leaving the `with` block) releases the device memory, and must
-    not run while another thread's call still uses the set."""
+    position in the *_indexed_batch calls.  update() replaces entries and append() adds entries in place; afterwards the set is
+    what create() gives for the final key list.  Neither they nor close() (or leaving the `with` block, which releases the device
+    memory) take a lock against readers: none of the three may run while another thread's call still uses the set."""
 
     def __init__(self, handle, statuses):
         self.handle, self.statuses = handle, statuses
@@ -763,6 +767,49 @@ class KeySet:
                                         ctypes.cast(st, ctypes.c_void_p)))
         raw = out.raw
         return [raw[osz * i:osz * (i + 1)] for i in range(n)], list(st)[:n]
+
+    def update(self, pos, keys, fmt=FMT_COMPRESSED):
+        """Entry pos[i] becomes keys[i] (byte strings in `fmt`, as for create): records, statuses, tables and line rows of the named
+        entries are rewritten, nothing else.  Returns what deserialize gives for each key.  A position outside the set or named
+        twice raises, and nothing is written."""
+        n = len(pos)
+        if len(keys) != n:
+            raise ValueError('one key per position')
+        blob = b''.join(keys)
+        st = (ctypes.c_int32 * max(n, 1))()
+        _check(init().blsgpu_keyset_update(self.handle, ctypes.cast(_u32(pos), ctypes.c_void_p), _ptr(blob) if blob else None, n, fmt,
+                                           ctypes.cast(st, ctypes.c_void_p)))
+        out = list(st)[:n]
+        if isinstance(self.statuses, list):
+            for p, s in zip(pos, out):
+                self.statuses[p] = s
+        return out
+
+    def append(self, keys, fmt=FMT_COMPRESSED):
+        """The set grows by `keys` (byte strings in `fmt`, as for create).  Returns (the first new position, what deserialize gives
+        for each key).  Tables and lines the grown set has no room for are dropped, as create would not build them: see info()."""
+        n = len(keys)
+        blob = b''.join(keys)
+        st = (ctypes.c_int32 * max(n, 1))()
+        first = ctypes.c_uint64(0)
+        _check(init().blsgpu_keyset_append(self.handle, _ptr(blob) if blob else None, n, fmt, ctypes.cast(st, ctypes.c_void_p), ctypes.byref(first)))
+        out = list(st)[:n]
+        if isinstance(self.statuses, list):
+            self.statuses.extend(out)
+        return first.value, out
+
+    def update_device(self, pos_ptr, keys_ptr, count, fmt=FMT_RAW_PROJ):
+        """update() from `count` uint32 positions and keys already on the device (integer addresses); no statuses come back."""
+        _check(init().blsgpu_keyset_update(self.handle, ctypes.c_void_p(pos_ptr), ctypes.c_void_p(keys_ptr),
+                                           count, fmt, None))
+        self.statuses = None
+
+    def append_device(self, keys_ptr, count, fmt=FMT_RAW_PROJ):
+        """append() from `count` keys already on the device (an integer address); returns the first new position."""
+        first = ctypes.c_uint64(0)
+        _check(init().blsgpu_keyset_append(self.handle, ctypes.c_void_p(keys_ptr), count, fmt, None, ctypes.byref(first)))
+        self.statuses = None
+        return first.value
 
     def mul(self, idx, scalars):
         """RAW_PROJ points scalars[i] * key[idx[i]] (integer scalars below 2^256, reduced modulo r)."""
@@ -1397,6 +1444,26 @@ class TensorOps:
         st = self.empty(max(n, 1), self.torch.int32)
         _check(self.lib.blsgpu_keyset_get(keyset.handle, self._p(idx), n, fmt, self._p(out), self._p(st)))
         return out[:n * osz], st[:n]
+
+    def keyset_update(self, keyset, pos, keys, count, fmt=FMT_RAW_PROJ):
+        """KeySet.update from the device: `pos` an int32 tensor whose bits are the uint32 positions, `keys` a uint8 tensor of `count`
+        keys in `fmt`.  Returns the int32 statuses (on the device).  The host's copy of the statuses (keyset.statuses) is dropped."""
+        self._sync()
+        st = self.empty(max(count, 1), self.torch.int32)
+        _check(self.lib.blsgpu_keyset_update(keyset.handle, self._p(pos), self._p(keys), count, fmt,
+                                             self._p(st)))
+        keyset.statuses = None
+        return st[:count]
+
+    def keyset_append(self, keyset, keys, count, fmt=FMT_RAW_PROJ):
+        """KeySet.append from the device.  Returns (the first new position, int32 statuses on the device)."""
+        self._sync()
+        st = self.empty(max(count, 1), self.torch.int32)
+        first = ctypes.c_uint64(0)
+        _check(self.lib.blsgpu_keyset_append(keyset.handle, self._p(keys), count, fmt, self._p(st),
+                                             ctypes.byref(first)))
+        keyset.statuses = None
+        return first.value, st[:count]
 
     def multi_verify(self, sg, scheme, pks, n, sig, msg):
         self._sync()

@@ -53,6 +53,7 @@ enum {
   KID_GROUP_LINES, KID_PREPARE_SHARED,   // blsgpu_verify_shared_batch (verify_shared.cuh; k_group_affine and k_shared_expand count under k_prepare_shared, k_lines2s_shared under k_lines2s)
   KID_KEYSET_LINES, KID_LINES_KEYED,     // key sets with line tables (keyset.cuh): the build at creation, and the line kernel that reads both rows
   KID_LINESP_KEYED,                      // ... and the one of the batched aggregate verify over such a set (in the place of k_linesp)
+  KID_KEYSET_SEAL_AT, KID_KEYSET_BUILD_AT, KID_KEYSET_LINES_AT,   // blsgpu_keyset_update / blsgpu_keyset_append: the positional forms of seal, build, lines
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -70,7 +71,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_elgamal_prep", "k_elgamal_ladder", "k_elgamal_transcript", "k_elgamal_sub",
                                     "k_group_lines", "k_prepare_shared",
                                     "k_keyset_lines", "k_lines2s_keyed",
-                                    "k_linesp_keyed"};
+                                    "k_linesp_keyed",
+                                    "k_keyset_seal_at", "k_keyset_build_at", "k_keyset_lines_at"};
 
 struct Ctx {
   int dev = -1;
@@ -1783,9 +1785,13 @@ int run_first_duplicate(Ctx* c, const uint8_t* d_msgs, const uint64_t* d_offs, s
 }
 
 // ---- registered key sets (keyset.cuh): the registry.  A handle is an id, never a pointer: a stale one is simply not found.
-// An entry is immutable from registration to destruction, so a call works on a copy of the record taken under the lock.
+// A call works on a copy of the record taken under the lock.  blsgpu_keyset_update rewrites entries behind unchanged pointers;
+// blsgpu_keyset_append moves the arrays and replaces the record under the lock (keyset_publish), freeing an old array only after
+// the record has stopped naming it.  Neither waits for calls that hold a copy: running one while another thread updates, appends
+// to or destroys the same set is the caller's error.
 struct KeySet {
   int sig_group = 0, group = 0;       // group: where the keys live
+  int flags = 0;                      // BLSGPU_KEYSET_* the creator asked for (what is built: table, lines)
   size_t n = 0, devidx = 0;
   int dev = -1;
   uint8_t *aff = nullptr, *comp = nullptr, *table = nullptr;     // RAW_AFFINE records, Modern bytes, fixed-base tables (or none)
@@ -1815,6 +1821,12 @@ int keyset_find(uint64_t handle, KeySet& k) {
   if (handle == 0 || it == g_keysets.end()) return fail(BLSGPU_E_ARG, "unknown key set handle (never issued, or destroyed)");
   k = it->second;
   return 0;
+}
+// the record of a live set after an append moved its arrays; a handle destroyed meanwhile (the caller's error) stays gone
+void keyset_publish(uint64_t handle, const KeySet& k) {
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  auto it = g_keysets.find(handle);
+  if (it != g_keysets.end()) it->second = k;
 }
 template <int G>
 size_t keyset_table_bytes_g(size_t n) { return n * (size_t)keyset_shape<G>::POINTS * 2 * G * FP_NL * 4; }
@@ -5057,6 +5069,7 @@ int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int
   KeySet k;
   k.sig_group = sig_group;
   k.group = key_group(sig_group);
+  k.flags = flags;
   k.n = n;
   k.devidx = t_devidx;
   k.dev = c->dev;
@@ -5121,6 +5134,208 @@ int blsgpu_keyset_destroy(uint64_t handle) try {
     g_keysets.erase(it);
   }
   keyset_free(k);
+  return 0;
+}
+API_CATCH
+
+// ---- blsgpu_keyset_update / blsgpu_keyset_append: `count` keys in `fmt` become the entries h_pos[0 .. count) of k (positions the
+// caller has checked with keyset_positions_check: in range, no two equal).  The steps of creation on those entries alone:
+// the checked decompression of a wire format, k_keyset_seal_at (record, Modern bytes, status), and -- for a set that has them --
+// k_keyset_build_at and k_keyset_lines_at in chunks of 4,096 keys through workspaces that live for this call only.  The
+// workspaces are allocated before anything is written, so a device without room for them leaves the set as it was.
+static int keyset_apply(Ctx* c, const KeySet& k, const uint32_t* h_pos, const void* keys, size_t count, int fmt, int32_t* status) {
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  const size_t isz = point_bytes(k.group, fmt), osz = point_bytes(k.group, BLSGPU_FMT_RAW_PROJ), chunk = std::min<size_t>(count, 4096);
+  const size_t rec = keyset_table_bytes(k.group, 1);
+  int rc = arena_reserve(c, pad256(isz * count) + pad256(osz * count) + 2 * pad256(4 * count) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  struct Work {
+    void *jac = nullptr, *prod = nullptr, *scratch = nullptr;
+    ~Work() {
+      for (void* p : {jac, prod, scratch})
+        if (p) (void)hipFree(p);
+    }
+  } ws;
+  if (k.table) {
+    HIPCK(hipMalloc(&ws.jac, chunk * (rec / 2 * 3)));
+    HIPCK(hipMalloc(&ws.prod, chunk * (rec / 2)));
+  }
+  if (k.lines) HIPCK(hipMalloc(&ws.scratch, chunk * (size_t)KEYSET_LINES_KEY_BYTES));
+  Carver mem{c};
+  uint32_t* d_pos = mem.take<uint32_t>(4 * count);
+  int32_t* d_st = mem.take<int32_t>(4 * count);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemcpyAsync(d_pos, h_pos, 4 * count, hipMemcpyHostToDevice, c->stream));
+  const void* d_in;
+  if ((rc = stage_in(c, keys, isz * count, &d_in))) return rc;
+  const uint8_t* d_pts = (const uint8_t*)d_in;
+  int kfmt = fmt;
+  if (wire) {
+    uint8_t* d_raw = (uint8_t*)arena_take(c, osz * count);
+    if (!d_raw) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    with_group(k.group, [&](auto G) {
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, d_pts, (int)(fmt == BLSGPU_FMT_LEGACY), d_raw, d_st, 0);
+    });
+    d_pts = d_raw;
+    kfmt = BLSGPU_FMT_RAW_PROJ;
+  } else {
+    HIPCK(hipMemsetAsync(d_st, 0, 4 * count, c->stream));
+  }
+  with_group(k.group, [&](auto G) {
+    KL(KID_KEYSET_SEAL_AT, k_keyset_seal_at<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, d_pts, kfmt, (const int32_t*)d_st, (const uint32_t*)d_pos,
+       k.aff, k.comp, k.status);
+  });
+  for (size_t l0 = 0; l0 < count; l0 += chunk) {
+    const size_t cnt = std::min(chunk, count - l0);
+    if (k.table)
+      with_group(k.group, [&](auto G) {
+        KL(KID_KEYSET_BUILD_AT, k_keyset_build_at<G()>, dim3(blocks_for(cnt)), dim3(BLS_BLOCK), cnt, (const uint32_t*)d_pos + l0, (const uint8_t*)k.aff,
+           (uint8_t*)ws.jac, (uint8_t*)ws.prod, k.table);
+      });
+    if (k.lines)
+      KL(KID_KEYSET_LINES_AT, k_keyset_lines_at, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), cnt, (const uint32_t*)d_pos + l0, (const uint8_t*)k.aff, k.lines,
+         (uint32_t*)ws.scratch, k.nolines);
+  }
+  HIPCK(hipGetLastError());
+  if (status && (rc = copy_out(c, status, d_st, 4 * count))) return rc;
+  SYNC_FLUSH(c);                      // before the workspaces go
+  return 0;
+}
+// the position list of an update, on the host (copied down first when it lives on the device)
+static int keyset_read_positions(const uint32_t* pos, size_t count, std::vector<uint32_t>& h) {
+  h.resize(count);
+  if (is_device_ptr(pos)) HIPCK(hipMemcpy(h.data(), pos, 4 * count, hipMemcpyDeviceToHost));
+  else memcpy(h.data(), pos, 4 * count);
+  return 0;
+}
+
+int blsgpu_keyset_update(uint64_t handle, const uint32_t* pos, const void* keys, size_t count, int fmt, int32_t* status) try {
+  KeySet k;
+  int rc = keyset_find(handle, k);
+  if (rc) return rc;
+  if ((rc = keyset_fmt_check(k.sig_group, fmt))) return rc;
+  if (count == 0) return 0;
+  if (!pos || !keys) return fail(BLSGPU_E_ARG, "null argument");
+  if (count > k.n) return fail(BLSGPU_E_ARG, "more positions than the key set has entries");
+  CTX_ACQUIRE_ON(c, k.devidx);
+  std::vector<uint32_t> h_pos;
+  if ((rc = keyset_read_positions(pos, count, h_pos))) return rc;
+  switch (keyset_positions_check(h_pos.data(), count, k.n)) {
+    case KEYSET_POS_RANGE: return fail(BLSGPU_E_ARG, "a position is outside the key set");
+    case KEYSET_POS_DUP: return fail(BLSGPU_E_ARG, "the same position twice in one update");
+  }
+  return keyset_apply(c, k, h_pos.data(), keys, count, fmt, status);
+}
+API_CATCH
+
+// One array of a growing set: `bytes_new` bytes with the first `bytes_old` copied from *p; *p is replaced and the old array left in
+// *old for the caller to free once no record names it.  false: the device has no room (or the copy failed) and *p is untouched.
+static bool keyset_grow(Ctx* c, void** p, size_t bytes_old, size_t bytes_new, void** old) {
+  void* q = nullptr;
+  if (hipMalloc(&q, std::max<size_t>(bytes_new, 1)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (bytes_old && (hipMemcpyAsync(q, *p, bytes_old, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) {
+    (void)hipGetLastError();
+    (void)hipFree(q);
+    return false;
+  }
+  *old = *p;
+  *p = q;
+  return true;
+}
+static uint64_t keyset_bytes(const KeySet& k) {
+  const uint64_t base = point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE) + point_bytes(k.group, BLSGPU_FMT_COMPRESSED) + 4;
+  return base * k.n + (k.table ? keyset_table_bytes(k.group, k.n) : 0) + (k.lines ? k.n * (KEYSET_LINES_KEY_BYTES + 4) : 0);
+}
+
+int blsgpu_keyset_append(uint64_t handle, const void* keys, size_t count, int fmt, int32_t* status, uint64_t* out_first) try {
+  KeySet k;
+  int rc = keyset_find(handle, k);
+  if (rc) return rc;
+  if ((rc = keyset_fmt_check(k.sig_group, fmt))) return rc;
+  if (count && !keys) return fail(BLSGPU_E_ARG, "null argument");
+  if (keyset_positions_check(nullptr, count, k.n) != KEYSET_POS_OK) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 keys");
+  if (out_first) *out_first = k.n;
+  if (count == 0) return 0;
+  CTX_ACQUIRE_ON(c, k.devidx);
+  const size_t n0 = k.n, n1 = k.n + count, asz = point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE), csz = point_bytes(k.group, BLSGPU_FMT_COMPRESSED);
+  const uint64_t cap_mib = (uint64_t)knobs().keyset_table_mb;
+  // the three base arrays: all of the new ones before any of the old ones goes; the record keeps n0 until the tail is written
+  {
+    KeySet g = k;
+    void* old[3] = {nullptr, nullptr, nullptr};
+    if (!keyset_grow(c, (void**)&g.aff, asz * n0, asz * n1, &old[0]) || !keyset_grow(c, (void**)&g.comp, csz * n0, csz * n1, &old[1]) ||
+        !keyset_grow(c, (void**)&g.status, 4 * n0, 4 * n1, &old[2])) {
+      if (old[0]) (void)hipFree(g.aff);
+      if (old[1]) (void)hipFree(g.comp);
+      return fail(BLSGPU_E_HIP, "no device memory for the grown key set");
+    }
+    k = g;
+    keyset_publish(handle, k);
+    for (void* p : old) (void)hipFree(p);
+  }
+  // tables and lines by the creation rule on the final size: grown, or dropped (the set works without them)
+  if (k.table) {
+    void* old = nullptr;
+    const size_t tb = keyset_table_bytes(k.group, n1);
+    if (tb > (size_t)cap_mib << 20 || !keyset_grow(c, (void**)&k.table, keyset_table_bytes(k.group, n0), tb, &old)) {
+      old = k.table;
+      k.table = nullptr;
+    }
+    k.bytes = keyset_bytes(k);
+    keyset_publish(handle, k);
+    (void)hipFree(old);
+  }
+  if (k.lines) {
+    void *old = nullptr, *old_no = nullptr, *unused = nullptr;
+    bool keep = keyset_lines_fit(n1, k.table ? keyset_table_bytes(k.group, n1) : 0, cap_mib) &&
+                keyset_grow(c, (void**)&k.lines, n0 * (size_t)KEYSET_LINES_KEY_BYTES, n1 * (size_t)KEYSET_LINES_KEY_BYTES, &old);
+    if (keep && !keyset_grow(c, (void**)&k.nolines, 4 * n0, 4 * n1, &old_no)) {
+      unused = k.lines;                         // the grown rows go with the old ones
+      k.lines = (uint32_t*)old;
+      keep = false;
+    }
+    if (!keep) {
+      old = k.lines;
+      old_no = k.nolines;
+      k.lines = nullptr;
+      k.nolines = nullptr;
+    }
+    k.bytes = keyset_bytes(k);
+    keyset_publish(handle, k);
+    for (void* p : {old, old_no, unused}) (void)hipFree(p);
+  }
+  // the tail through the update path; the published record still says n0, so nothing names the new entries before they are whole
+  std::vector<uint32_t> h_pos(count);
+  for (size_t i = 0; i < count; i++) h_pos[i] = (uint32_t)(n0 + i);
+  if ((rc = keyset_apply(c, k, h_pos.data(), keys, count, fmt, status))) return rc;
+  k.n = n1;
+  k.bytes = keyset_bytes(k);
+  keyset_publish(handle, k);
+  // what the creator asked for and the set does not have (an empty set has neither) is built whole where creation would build it:
+  // tables first, then the lines in what the cap leaves.  Every record published on the way is a whole set.
+  if ((k.flags & BLSGPU_KEYSET_TABLES) && !k.table) {
+    if ((rc = keyset_build_tables(c, k))) return rc;
+    if (k.table && k.lines && !keyset_lines_fit(n1, keyset_table_bytes(k.group, n1), cap_mib)) {
+      void *old = k.lines, *old_no = k.nolines;
+      k.lines = nullptr;
+      k.nolines = nullptr;
+      k.bytes = keyset_bytes(k);
+      keyset_publish(handle, k);
+      (void)hipFree(old);
+      (void)hipFree(old_no);
+    } else if (k.table) {
+      keyset_publish(handle, k);
+    }
+  }
+  if ((k.flags & BLSGPU_KEYSET_LINES) && !k.lines) {
+    if ((rc = keyset_build_lines(c, k))) return rc;
+    if (k.lines) keyset_publish(handle, k);
+  }
+  SYNC_FLUSH(c);
   return 0;
 }
 API_CATCH

@@ -11,8 +11,11 @@
 //   * keyset_pre_key / keyset_pre_status: what k_keyset_check leaves per set -- an out-of-range index first, then the creation
 //     status of the first invalid entry in input order -- packed so that one atomicMin per position decides it;
 //   * the line table of a G2 key (BLSGPU_KEYSET_LINES): the 68 normalised Miller rows of verify_shared.cuh, derived once at
-//     creation, and the rule that says whether a set may have them.
+//     creation, and the rule that says whether a set may have them;
+//   * keyset_positions_check: which position lists blsgpu_keyset_update and blsgpu_keyset_append accept.
 #pragma once
+#include <algorithm>
+#include <vector>
 #include "multi_batch.cuh"
 #include "verify_shared.cuh"
 
@@ -71,6 +74,22 @@ static inline bool keyset_lines_fit(uint64_t n_keys, uint64_t other_bytes, uint6
   if (n_keys == 0 || n_keys > 0xffffffffull / KEYSET_LINES_KEY_BYTES) return false;
   return n_keys * KEYSET_LINES_KEY_BYTES + other_bytes <= cap_mib << 20;
 }
+// The positions of one blsgpu_keyset_update over a set of n_keys entries, or (pos == nullptr) the tail [n_keys, n_keys + count) that
+// blsgpu_keyset_append adds: every lane of the positional kernels writes the rows of its own entry, so a list is accepted only when
+// all positions are below n_keys and no two are equal; an append only while the grown set keeps fewer than 2^32 - 1 entries (as at
+// creation: KEYSET_SKIP stays free).  Range is decided before duplicates.  (A host rule: the library and the host harness call it.)
+#define KEYSET_POS_OK 0
+#define KEYSET_POS_RANGE 1                // a position not below the set's size
+#define KEYSET_POS_DUP 2                  // the same position twice
+#define KEYSET_POS_FULL 3                 // an append past 2^32 - 2 entries
+static inline int keyset_positions_check(const uint32_t* pos, uint64_t count, uint64_t n_keys) {
+  if (!pos) return n_keys >= 0xffffffffull || count >= 0xffffffffull - n_keys ? KEYSET_POS_FULL : KEYSET_POS_OK;
+  for (uint64_t i = 0; i < count; i++)
+    if ((uint64_t)pos[i] >= n_keys) return KEYSET_POS_RANGE;
+  std::vector<uint32_t> sorted(pos, pos + count);
+  std::sort(sorted.begin(), sorted.end());
+  return std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end() ? KEYSET_POS_DUP : KEYSET_POS_OK;
+}
 BLS_FN void keyset_raw_hfp2(hfp2& r, const uint32_t* w) {
 #if defined(__HIPCC__)
   fp_from_raw(r.v, w + (lane_hi() ? 12 : 0));
@@ -98,13 +117,22 @@ BLS_FN int keyset_lines_entry(const uint32_t* rec, const IO& io) {
 // create: any raw format -> the stored affine record and Modern bytes; an entry whose status is not OK becomes the zero record
 template <int G>
 __global__ void k_keyset_seal(size_t n, const uint8_t* pts, int fmt, const int32_t* status, uint8_t* recs, uint8_t* comp);
+// update / append: the same per key, input key l (and status[l]) into entry pos[l]; the entry's creation status becomes status[l]
+template <int G>
+__global__ void k_keyset_seal_at(size_t n, const uint8_t* pts, int fmt, const int32_t* status, const uint32_t* pos, uint8_t* recs, uint8_t* comp,
+                                 int32_t* kstatus);
 // create, with tables: the multiples of keys [k0, k0 + cnt) as Jacobian points in jac_ws, their running Z products in prod_ws
 // (POINTS records per lane each), one inversion per lane, the affine records into table
 template <int G>
 __global__ void k_keyset_build(size_t k0, size_t cnt, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws, uint8_t* table);
+// update / append: lane l builds the table of entry pos[l]; workspace rows by l, table rows by pos[l]
+template <int G>
+__global__ void k_keyset_build_at(size_t cnt, const uint32_t* pos, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws, uint8_t* table);
 // create, with line tables (G2 keys): one lane pair per key of [k0, k0 + cnt) runs keyset_lines_entry into the key's rows of
 // `table`; scratch: SHARED_TABLE_WORDS words per key of the CHUNK; nolines[k] = 0 or KEYSET_NOLINES_*
 __global__ void k_keyset_lines(size_t k0, size_t cnt, const uint8_t* recs, uint32_t* table, uint32_t* scratch, int32_t* nolines);
+// update / append: lane pair l builds the rows of entry pos[l]; scratch rows by l, table rows and nolines by pos[l]
+__global__ void k_keyset_lines_at(size_t cnt, const uint32_t* pos, const uint8_t* recs, uint32_t* table, uint32_t* scratch, int32_t* nolines);
 // per position: the index against the table's size and the entry's status; cidx[i] = idx[i] or KEYSET_SKIP, pre[set] by atomicMin
 // (offs == nullptr: every position is its own set).  nolines != nullptr (a set with line tables): *walk |= 1 when a position names
 // a finite entry without usable rows (the caller clears the word before the launch)

@@ -4,6 +4,8 @@
 //   k_keyset_seal           : create: the stored affine record and Modern bytes of every entry
 //   k_keyset_build          : create: the fixed-base table, one lane per key, ONE inversion per lane
 //   k_keyset_lines          : create: the line table of G2 keys, one lane pair per key, ONE inversion per key
+//   k_keyset_seal_at, k_keyset_build_at, k_keyset_lines_at : update / append: the same three per-key bodies on the entries a
+//                             position list names (lane l: input and workspace row l, entry pos[l])
 //   k_keyset_check          : every position's index and entry status, once; the sanitised indices and each set's precedence
 //   k_keyset_fin            : the precedence over the statuses of the verification tail
 //   k_keyset_fin_aux        : the same over statuses and aux words (the batched aggregate verify)
@@ -83,25 +85,39 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_gather(size_t n, size_t wo
 }
 #endif
 
+// input key i (any raw format; the identity when status[i] is not OK) -> the stored record and Modern bytes of entry k
 template <int G>
-__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_seal(size_t n, const uint8_t* pts, int fmt, const int32_t* status, uint8_t* recs, uint8_t* comp) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void keyset_seal_entry(size_t i, size_t k, const uint8_t* pts, int fmt, const int32_t* status, uint8_t* recs, uint8_t* comp) {
   typename grp<G>::jac_t p;
   typename grp<G>::aff_t a;
   if (status[i] != BLS_OK) jac_set_inf(p);
   else grp<G>::load(p, pts, i, fmt);
   jac_to_aff(a, p);
-  uint32_t* w = (uint32_t*)(recs + i * (grp<G>::PROJ_BYTES / 3 * 2));
+  uint32_t* w = (uint32_t*)(recs + k * (grp<G>::PROJ_BYTES / 3 * 2));
   if (a.inf) {
-    for (int k = 0; k < grp<G>::PROJ_BYTES / 6; k++) w[k] = 0u;
+    for (int j = 0; j < grp<G>::PROJ_BYTES / 6; j++) w[j] = 0u;
   } else {
     ks_raw(w, a.x);
     ks_raw(w + grp<G>::PROJ_BYTES / 12, a.y);
   }
   uint8_t b[grp<G>::COMP_BYTES];
   grp<G>::compress(b, a, false);
-  for (int k = 0; k < grp<G>::COMP_BYTES; k++) comp[i * grp<G>::COMP_BYTES + k] = b[k];
+  for (int j = 0; j < grp<G>::COMP_BYTES; j++) comp[k * grp<G>::COMP_BYTES + j] = b[j];
+}
+template <int G>
+__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_seal(size_t n, const uint8_t* pts, int fmt, const int32_t* status, uint8_t* recs, uint8_t* comp) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  keyset_seal_entry<G>(i, i, pts, fmt, status, recs, comp);
+}
+template <int G>
+__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_seal_at(size_t n, const uint8_t* pts, int fmt, const int32_t* status, const uint32_t* pos, uint8_t* recs,
+                                                            uint8_t* comp, int32_t* kstatus) {
+  const size_t l = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= n) return;
+  const size_t k = pos[l];
+  keyset_seal_entry<G>(l, k, pts, fmt, status, recs, comp);
+  kstatus[k] = status[l];
 }
 
 template <int G>
@@ -118,24 +134,22 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_to_proj(size_t n, const ui
   grp<G>::store(out, i, p);
 }
 
-// Lane `l` works on key k0 + l.  Its POINTS multiples are computed as Jacobian points (per window: B, 2B = dbl, 3B .. 8B by
-// additions of B, then the next window's B = dbl(8B) -- a doubling and seven additions per window), each kept in jac_ws with the
+// Workspace row `l` serves key `key` (k_keyset_build: k0 + l; k_keyset_build_at: pos[l]).  Its POINTS multiples are computed as
+// Jacobian points (per window: B, 2B = dbl, 3B .. 8B by additions of B, then the next window's B = dbl(8B) -- a doubling and seven additions per window), each kept in jac_ws with the
 // running product of the Z coordinates in prod_ws; ONE inversion of the last product and a walk back give every 1 / Z.  A key of
 // order r has no multiple d 2^(4j) P = identity (d 2^(4j) has the prime factors 2, 3, 5, 7 only); a raw point that is no such key
 // may, and then leaves a zero record, which k_keyset_mul skips.
 template <int G>
-__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_build(size_t k0, size_t cnt, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws, uint8_t* table) {
-  const size_t l = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= cnt) return;
+__device__ __forceinline__ void keyset_build_entry(size_t key, size_t l, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws, uint8_t* table) {
   typedef keyset_shape<G> S;
   typedef typename grp<G>::F F;
   constexpr int C = KS_CO_WORDS(G);
   jac<F> base, m;
-  grp<G>::load(base, recs, k0 + l, 1);
-  if (jac_is_inf(base)) return;               // the identity or an invalid entry: k_keyset_mul never reads its table
+  grp<G>::load(base, recs, key, 1);
+  if (jac_is_inf(base)) return;               // the identity or an invalid entry: k_keyset_mul never reads its table (stale rows included)
   uint32_t* jw = (uint32_t*)jac_ws + l * (size_t)S::POINTS * 3 * C;
   uint32_t* pw = (uint32_t*)prod_ws + l * (size_t)S::POINTS * C;
-  uint32_t* tw = (uint32_t*)table + (k0 + l) * (size_t)S::POINTS * KS_TAB_WORDS(G);
+  uint32_t* tw = (uint32_t*)table + key * (size_t)S::POINTS * KS_TAB_WORDS(G);
   F run, one;
   fe_one(run);
   fe_one(one);
@@ -186,16 +200,41 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_build(size_t k0, size_t cn
     ks_st(t + C, m.y);
   }
 }
+template <int G>
+__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_build(size_t k0, size_t cnt, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws, uint8_t* table) {
+  const size_t l = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= cnt) return;
+  keyset_build_entry<G>(k0 + l, l, recs, jac_ws, prod_ws, table);
+}
+template <int G>
+__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_build_at(size_t cnt, const uint32_t* pos, const uint8_t* recs, uint8_t* jac_ws, uint8_t* prod_ws,
+                                                             uint8_t* table) {
+  const size_t l = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= cnt) return;
+  keyset_build_entry<G>(pos[l], l, recs, jac_ws, prod_ws, table);
+}
 
 #if BLS_TU_KEYSET == 2
+// this lane's half of the rows of entry k, through scratch row l; nolines[k] = 0 or KEYSET_NOLINES_* (an entry that is, or has
+// become, the identity or invalid keeps whatever rows it had: nothing reads them)
+__device__ __forceinline__ void keyset_lines_pair(size_t k, size_t l, const uint8_t* recs, uint32_t* table, uint32_t* scratch, int32_t* nolines) {
+  const size_t lane = lane_hi() ? FP_NL : 0;
+  const group_lines_io io = {table + k * (size_t)SHARED_TABLE_WORDS + lane, scratch + l * (size_t)SHARED_TABLE_WORDS + lane};
+  const int no = keyset_lines_entry((const uint32_t*)(recs + k * 192), io);
+  if (!lane_hi()) nolines[k] = no;
+}
 __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_lines(size_t k0, size_t cnt, const uint8_t* recs, uint32_t* table, uint32_t* scratch, int32_t* nolines) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t l = t >> 1;                                  // both lanes of a pair are inside or outside: BLS_BLOCK is even
   if (l >= cnt) return;
-  const size_t k = k0 + l, lane = lane_hi() ? FP_NL : 0;
-  const group_lines_io io = {table + k * (size_t)SHARED_TABLE_WORDS + lane, scratch + l * (size_t)SHARED_TABLE_WORDS + lane};
-  const int no = keyset_lines_entry((const uint32_t*)(recs + k * 192), io);
-  if (!lane_hi()) nolines[k] = no;
+  keyset_lines_pair(k0 + l, l, recs, table, scratch, nolines);
+}
+__global__ void __launch_bounds__(BLS_BLOCK) k_keyset_lines_at(size_t cnt, const uint32_t* pos, const uint8_t* recs, uint32_t* table, uint32_t* scratch,
+                                                             int32_t* nolines) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t l = t >> 1;
+  if (l >= cnt) return;
+  keyset_lines_pair(pos[l], l, recs, table, scratch, nolines);
 }
 #endif
 
@@ -329,8 +368,10 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_keyset_mul(size_t n, const uint8_
 }
 
 template __global__ void k_keyset_seal<BLS_TU_KEYSET>(size_t, const uint8_t*, int, const int32_t*, uint8_t*, uint8_t*);
+template __global__ void k_keyset_seal_at<BLS_TU_KEYSET>(size_t, const uint8_t*, int, const int32_t*, const uint32_t*, uint8_t*, uint8_t*, int32_t*);
 template __global__ void k_keyset_to_proj<BLS_TU_KEYSET>(size_t, const uint8_t*, uint8_t*);
 template __global__ void k_keyset_build<BLS_TU_KEYSET>(size_t, size_t, const uint8_t*, uint8_t*, uint8_t*, uint8_t*);
+template __global__ void k_keyset_build_at<BLS_TU_KEYSET>(size_t, const uint32_t*, const uint8_t*, uint8_t*, uint8_t*, uint8_t*);
 template __global__ void k_keyset_mul<BLS_TU_KEYSET, 0>(size_t, const uint8_t*, const uint8_t*, const uint32_t*, const uint8_t*, const uint32_t*, const uint32_t*,
                                                         uint8_t*);
 template __global__ void k_keyset_mul<BLS_TU_KEYSET, 1>(size_t, const uint8_t*, const uint8_t*, const uint32_t*, const uint8_t*, const uint32_t*, const uint32_t*,

@@ -546,8 +546,10 @@ int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t
  * deserialise and upload every key ONCE (blsgpu_keyset_create) and afterwards pass 4 bytes per (set, key).
  *
  * A handle is an opaque non-zero id from a registry inside the library, never a pointer; every entry point given a stale or
- * unknown id returns BLSGPU_E_ARG.  A key set is immutable; concurrent calls may read one set.  Destroying a set while a call
- * uses it is the caller's error (the call may then read freed device memory).  blsgpu_shutdown frees every key set.  The memory
+ * unknown id returns BLSGPU_E_ARG.  Concurrent calls may read one set.  A set changes only through blsgpu_keyset_update and
+ * blsgpu_keyset_append, and those take no lock against its readers: running any call on a set while another thread updates,
+ * appends to or destroys the same set is the caller's error (the call may then read half-written entries or freed device memory).
+ * blsgpu_shutdown frees every key set.  The memory
  * is hipMalloc'd outside the context arenas on the device of the context that ran blsgpu_keyset_create (device 0 of a
  * multi-device binding unless the call came from a sharded sub-call); the indexed entry points run on that device and do not
  * shard.
@@ -581,6 +583,31 @@ int blsgpu_keyset_destroy(uint64_t handle);
 int blsgpu_keyset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_tables, uint64_t* device_bytes);
 int blsgpu_keyset_get(uint64_t handle, const uint32_t* idx, size_t count, int fmt_out, void* out, int32_t* status);
 int blsgpu_keyset_mul(uint64_t handle, const uint32_t* idx, const uint8_t* scalars, size_t count, void* out);
+
+/* A registered list changes -- a masternode list by a handful of entries every block, a validator registry by growth every epoch
+ * -- and the set follows in place.  After either call the set is what blsgpu_keyset_create with the same flags gives for the
+ * final key list, through every call above and below: records, Modern bytes, creation statuses, fixed-base tables, line rows.
+ *
+ * update: entry pos[i] becomes keys[i] (count keys; `keys`, `fmt` and `status` exactly as at creation: any BLSGPU_FMT_*, LEGACY for
+ * sig_group 2 only, wire formats through the checked decompression, status[i] -- may be NULL -- what deserialisation gives for
+ * key i, a key that fails kept as an invalid entry, raw formats trusted).  pos, keys and status may be host or device memory; pos
+ * is read and checked on the host (copied down first when it lives on the device).  A position not below the set's size, the same
+ * position twice in one call, an unknown handle, a null pos or keys with count > 0 and a bad format return BLSGPU_E_ARG with
+ * nothing written to the set and no status written.  count == 0 returns 0.  For every named entry the call rewrites all the set
+ * has of it, so an entry may gain or lose its table and its line rows (a real key in the place of the identity, and the reverse);
+ * no other entry changes.  The work is that of creation on the named entries alone, in chunks of 4,096 keys.
+ *
+ * append: the set grows from n to n + count entries (fewer than 2^32 - 1, as at creation; more is BLSGPU_E_ARG), *out_first
+ * (may be NULL) receives n, and the new entries are keys[0 .. count) as for update.  The arrays are reallocated and copied on
+ * the device, each new array allocated before the old one is freed; when the device has no room for the grown records the call
+ * returns BLSGPU_E_HIP and the set is unchanged.  Tables and lines follow the creation rule on the final size: where the grown
+ * tables or lines would exceed BLSGPU_KEYSET_TABLE_MB MiB, break the 2^32-byte bound of the lines or find no room on the device,
+ * they are dropped, the set works without them, blsgpu_keyset_info reports the new mask, and no status of any later call changes.
+ * A set created empty gets the tables and lines it was created for with its first keys.  device_bytes afterwards is what
+ * creation of the final list reports.
+ * Both run on the key set's device. */
+int blsgpu_keyset_update(uint64_t handle, const uint32_t* pos, const void* keys, size_t count, int fmt, int32_t* status);
+int blsgpu_keyset_append(uint64_t handle, const void* keys, size_t count, int fmt, int32_t* status, uint64_t* out_first);
 
 /* The batched entry points with (keyset, idx) in place of the keys: blsgpu_multi_verify_batch, blsgpu_verify_secure_batch,
  * blsgpu_sum_batch, blsgpu_verify_batch (one key per item) and blsgpu_aggregate_verify_batch over positions in a key set.  sig_group comes from the key set and

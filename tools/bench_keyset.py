@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Registered key sets against keys by value: what the index-addressed entry points and the fixed-base tables cost and save.
 
-usage: python tools/bench_keyset.py [--lines | --agg] [--reps 5] [--table 16384] [--shapes 0,1,..] [--out profiles/keyset_bench.json]
+usage: python tools/bench_keyset.py [--lines | --agg | --update] [--reps 5] [--table 16384] [--shapes 0,1,..] [--out profiles/keyset_bench.json]
 Every input lives on the device (TensorOps).  Per shape, indices are drawn at random from a table of --table keys k * g
 (blsgpu_sign_batch) and four things are timed, each the median of --reps calls:
   (a) the non-indexed entry point on the same keys laid out contiguously (three repeats of the whole measurement: their range is the
@@ -25,7 +25,13 @@ distinct messages: (a) blsgpu_aggregate_verify_batch by value, (b) blsgpu_aggreg
 ((a) and (b): its keys have no lines); every cell three medians of --reps calls, the kernel times of one call from the profile,
 and for (c) the bytes per second k_linesp_keyed reached against its own traffic (per item and entry one 224-byte row read and
 336 bytes of line value written, 68 entries, plus the item's G1 point).  A library without the indexed entry point (the parent
-commit) runs (a) only."""
+commit) runs (a) only.
+
+--update [--out profiles/keyset_update_bench.json]: following a list that changes.  Per impl a set of --table keys with BOTH flags
+(fixed-base tables, and line tables where the keys have them), keys as RAW_PROJ in device memory: blsgpu_keyset_update of 1, 16, 256
+and 4,096 random distinct positions and blsgpu_keyset_append of 256 keys (onto a fresh set of --table keys each time, made outside
+the timed region), each against blsgpu_keyset_create of the final list on the same build -- the only way to the same set without
+these calls.  EVERY cell three medians of --reps calls, and the kernel times of one call from the profile."""
 import argparse
 import json
 import os
@@ -184,9 +190,80 @@ def agg_bench(a, api, ops, torch, dev, sync):
         json.dump(rows, f, indent=1)
 
 
+UPDATE_COUNTS = [1, 16, 256, 4096]
+APPEND_COUNT = 256
+
+
+def update_bench(a, api, ops, torch, dev, sync):
+    rng = random.Random(2029)
+    rows = [{'table_entries': a.table, 'flags': 'tables + lines', 'reps': a.reps}]
+
+    def kernel_ms(run):
+        api.profile_enable(True)
+        before = {k: v[0] for k, v in api.profile_read().items()}
+        run()
+        km = {k: v[0] - before.get(k, 0.0) for k, v in api.profile_read().items()}
+        api.profile_enable(False)
+        return {k: round(v, 3) for k, v in km.items() if v >= 0.001}
+
+    def three(run):
+        m3 = [median_ms(run, a.reps, sync) for _ in range(3)]
+        return {'ms': [round(x, 3) for x in m3], 'spread_ms': round(max(m3) - min(m3), 3)}
+
+    for sg in (1, 2):
+        total = a.table + APPEND_COUNT
+        ks = [rng.randrange(1, R) for _ in range(total + max(UPDATE_COUNTS))]
+        pks = api.sign_batch(sg, api.BASIC, ks, [b''] * len(ks))[0]
+        pool = torch.tensor(list(b''.join(pks)), dtype=torch.uint8, device=dev).view(len(ks), -1)
+        fresh = pool[total:].contiguous()                                    # the keys an update writes
+        grown = pool[:total].contiguous()
+        sync()
+        make = lambda n: api.KeySet.create_device(sg, grown.data_ptr(), n, api.FMT_RAW_PROJ, tables=True, lines=True)
+        kset = make(a.table)
+        row = {'impl': 'Bls12381G%dImpl' % sg, 'sig_group': sg, 'set': kset.info()}
+
+        def recreate(n):
+            make(n).close()
+        row['create_%d' % a.table] = dict(three(lambda: recreate(a.table)), kernel_ms=kernel_ms(lambda: recreate(a.table)))
+        row['create_%d' % total] = dict(three(lambda: recreate(total)), kernel_ms=kernel_ms(lambda: recreate(total)))
+        for count in UPDATE_COUNTS:
+            pos = torch.tensor(rng.sample(range(a.table), count), dtype=torch.int32, device=dev)
+            keys = fresh[:count].reshape(-1).contiguous()
+            sync()
+            run = lambda: ops.keyset_update(kset, pos, keys, count, api.FMT_RAW_PROJ)
+            cell = dict(three(run), kernel_ms=kernel_ms(run))
+            cell['against_create'] = round(statistics.median(cell['ms']) / statistics.median(row['create_%d' % a.table]['ms']), 3)
+            row['update_%d' % count] = cell
+        kset.close()
+        # append: every timed call grows a set of --table keys, made (and closed) outside the timed region
+        tail = grown[a.table:].reshape(-1).contiguous()
+        ts, km = [], None
+        for r in range(3 * a.reps + 2):
+            kset = make(a.table)
+            sync()
+            if r == 1:
+                km = kernel_ms(lambda: ops.keyset_append(kset, tail, APPEND_COUNT, api.FMT_RAW_PROJ))
+            else:
+                t0 = time.perf_counter()
+                ops.keyset_append(kset, tail, APPEND_COUNT, api.FMT_RAW_PROJ)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            after = kset.info()
+            kset.close()
+        ts = ts[1:]                                                          # the first call is the warm-up
+        m3 = [statistics.median(ts[i * a.reps:(i + 1) * a.reps]) for i in range(3)]
+        row['append_%d' % APPEND_COUNT] = {'ms': [round(x, 3) for x in m3], 'spread_ms': round(max(m3) - min(m3), 3), 'kernel_ms': km, 'set_after': after,
+                                           'against_create': round(statistics.median(m3) / statistics.median(row['create_%d' % total]['ms']), 3)}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--lines', action='store_true')
+    ap.add_argument('--update', action='store_true')
     ap.add_argument('--agg', action='store_true')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--table', type=int, default=16384)
@@ -199,6 +276,10 @@ def main():
     dev = torch.device('cuda', 0)
     ops = api.TensorOps(dev)
     sync = torch.cuda.synchronize
+    if a.update:
+        if a.out.endswith('keyset_bench.json'):
+            a.out = os.path.join(ROOT, 'profiles', 'keyset_update_bench.json')
+        return update_bench(a, api, ops, torch, dev, sync)
     if a.agg:
         if a.out.endswith('keyset_bench.json'):
             a.out = os.path.join(ROOT, 'profiles', 'keyset_agg_bench.json')
