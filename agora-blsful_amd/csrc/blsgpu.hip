@@ -490,6 +490,14 @@ int check_common(int sg, int scheme, int fmt) {
     return fail(BLSGPU_E_ARG, "this entry point takes BLSGPU_FMT_RAW_PROJ or BLSGPU_FMT_RAW_AFFINE points");
   return 0;
 }
+// the key serialisation of the secure calls; blsgpu_aggregate_secure has always given the Legacy refusal without its citation
+int check_ser_format(int sig_group, int ser_format, bool cite = true) {
+  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
+  if (ser_format == 1 && sig_group != 2)
+    return fail(BLSGPU_E_ARG, std::string("Legacy serialization exists only for Bls12381G2Impl") +
+                                  (cite ? " (48-byte keys), reference src/signature.rs:201-204" : ""));
+  return 0;
+}
 
 hipEvent_t prof_event(Ctx* c) {
   if (!c->prof_pool.empty()) {
@@ -2721,9 +2729,7 @@ int blsgpu_verify_secure(int sig_group, int scheme, const void* pks, size_t n, c
   int rc = check_common(sig_group, scheme, fmt);
   if (rc) return rc;
   if (!sig || !status || (n && !pks)) return fail(BLSGPU_E_ARG, "null argument");
-  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
-  if (ser_format == 1 && sig_group != 2)
-    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
+  if ((rc = check_ser_format(sig_group, ser_format))) return rc;
   if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 keys");
   if (const size_t D = shard_devices(n, {pks, sig}); D > 1) {
     // every device serialises its range of the keys; device 0 sorts all of them and a host core hashes the sorted stream
@@ -3269,8 +3275,7 @@ int blsgpu_aggregate_secure(int sig_group, const void* pks, const void* sigs, si
   int rc = check_common(sig_group, 0, fmt);
   if (rc) return rc;
   if (!out_sig || !status || (n && (!pks || !sigs))) return fail(BLSGPU_E_ARG, "null argument");
-  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
-  if (ser_format == 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl");
+  if ((rc = check_ser_format(sig_group, ser_format, false))) return rc;
   if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 keys");
   CTX_ACQUIRE(c);
   const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), T = accumulate_lanes(n);
@@ -4383,130 +4388,302 @@ static int run_set_tail(Ctx* c, const set_tail& t, int sig_group, int scheme, in
                           scheme_dst(sig_group, scheme), n_sets, t.pairs, t.f, t.st, 1);
 }
 
-// ---- batched verify_secure (secure.cuh): n_sets independent Signature::verify_secure checks in one call
-int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
-                               const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt, int32_t* status) try {
-  int rc = check_common(sig_group, scheme, fmt);
-  if (rc) return rc;
-  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
-  if (ser_format == 1 && sig_group != 2)
-    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
+// ---- the ragged arguments of the batched secure / multi verify and of the batched sums, checked and read.  `keys` stands for the
+// keys in the null check: the caller's array, or its positions in a key set (indexed_begin)
+struct set_args {
+  std::vector<uint64_t> offs, moffs;
+  size_t n = 0;
+};
+static int set_args_read(set_args& a, const void* keys, const uint64_t* key_offsets, size_t n_sets, const void* sigs, const uint8_t* msgs,
+                         const uint64_t* msg_offsets, const int32_t* status) {
+  int rc;
   if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
   if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  std::vector<uint64_t> offs, moffs;
-  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", offs))) return rc;
-  const size_t n = (size_t)offs[n_sets];
-  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
-  if (n && !pks) return fail(BLSGPU_E_ARG, "null argument");
+  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", a.offs))) return rc;
+  a.n = (size_t)a.offs[n_sets];
+  if (a.n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
+  if (a.n && !keys) return fail(BLSGPU_E_ARG, "null argument");
   if (n_sets == 0) return 0;
-  if ((rc = read_offsets(msg_offsets, n_sets, "msg_offsets", moffs, false))) return rc;      // set s's message is msgs + moffs[s]
-  if (moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
-  // plan: a set of at least BLSGPU_SECURE_BATCH_MAX keys runs one at a time through the machinery of blsgpu_verify_secure (device
-  // sort, host SHA-256 of the stream, k_sha256_coeff, bucket MSM); all others through the segmented kernels of secure.cuh and the
-  // per-key ladders of the threshold recovery.  One large set alone IS blsgpu_verify_secure (on one device: no sharding).
-  const uint64_t max_small = (uint64_t)knobs().secure_batch_max;
-  if (n_sets == 1 && n >= max_small) {
-    NestedScope ns;
-    return blsgpu_verify_secure(sig_group, scheme, pks, n, sigs, msgs + moffs[0], (size_t)(moffs[1] - moffs[0]), ser_format, fmt, status);
-  }
-  CTX_ACQUIRE(c);
-  const int pk_group = key_group(sig_group);
-  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
-  std::vector<uint32_t> hflags(n_sets, 0);
+  if ((rc = read_offsets(msg_offsets, n_sets, "msg_offsets", a.moffs, false))) return rc;      // set s's message is msgs + moffs[s]
+  if (a.moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  return 0;
+}
+static int sum_args_read(std::vector<uint64_t>& offs, const void* pts, const uint64_t* offsets, size_t n_sets, const void* out) {
+  if (!offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  if (n_sets && !out) return fail(BLSGPU_E_ARG, "null argument");
+  int rc = read_offsets(offsets, n_sets, "offsets", offs);
+  if (rc) return rc;
+  if (offs[n_sets] >= ((uint64_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more points in one call");
+  return offs[n_sets] && !pts ? fail(BLSGPU_E_ARG, "null argument") : 0;
+}
+
+// ---- the secure batch calls (secure.cuh).  Their plan: a set of at least BLSGPU_SECURE_BATCH_MAX keys (SECURE_F_LARGE in its flags)
+// runs one at a time through the machinery of the single call, all others together through the segmented kernels; S is the second
+// grid dimension of the rank kernels.
+struct secure_plan {
+  std::vector<uint32_t> hflags;
   uint64_t tmax_small = 0, tmax_large = 0;
-  for (size_t s = 0; s < n_sets; s++) {
-    const uint64_t t = offs[s + 1] - offs[s];
-    if (t >= max_small) {
-      hflags[s] = SECURE_F_LARGE;
-      tmax_large = std::max(tmax_large, t);
-    } else {
-      tmax_small = std::max(tmax_small, t);
+  size_t S;
+  secure_plan(const std::vector<uint64_t>& offs, size_t n_sets, uint64_t max_small) : hflags(n_sets, 0) {
+    for (size_t s = 0; s < n_sets; s++) {
+      const uint64_t t = offs[s + 1] - offs[s];
+      if (t >= max_small) {
+        hflags[s] = SECURE_F_LARGE;
+        tmax_large = std::max(tmax_large, t);
+      } else {
+        tmax_small = std::max(tmax_small, t);
+      }
     }
+    S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax_small / 256)));
   }
-  size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax_small / 256)));
-  const size_t mtotal = (size_t)moffs[n_sets];
+};
+// The buffers of the coefficient pipeline, carved as set_tail is: per key its serialised bytes, their sorted copy, coefficient, rank,
+// set id and product (osz bytes: a key or a signature as RAW_PROJ); per set its digest and flags.
+struct secure_bufs {
+  uint8_t *bytes, *sorted, *scal;
+  uint32_t *rank, *sid;
+  uint8_t *part, *H;
+  uint32_t* flags;
+  secure_bufs(Carver& mem, size_t n, size_t n_sets, size_t width, size_t osz)
+      : bytes(mem.take<uint8_t>(width * n)), sorted(mem.take<uint8_t>(width * n)), scal(mem.take<uint8_t>(32 * n)), rank(mem.take<uint32_t>(4 * n)),
+        sid(mem.take<uint32_t>(4 * n)), part(mem.take<uint8_t>(osz * n)), H(mem.take<uint8_t>(32 * n_sets)), flags(mem.take<uint32_t>(4 * n_sets)) {}
+};
+// the small sets' coefficients from b.bytes: every key's rank within its set, the sorted stream, its digest per set, the scalars
+static int run_secure_coefficients(Ctx* c, const secure_plan& p, const secure_bufs& b, size_t n, const uint64_t* o, size_t n_sets, size_t width) {
+  HIPCK(hipMemsetAsync(b.rank, 0, 4 * n, c->stream));
+  const dim3 grid(blocks_for(n), (unsigned)p.S);
+  const uint32_t *flags = b.flags, *rank = b.rank, *sid = b.sid;
+  if (width == 96) KL(KID_SECURE_RANK, k_secure_rank<24>, grid, dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)b.bytes, flags, b.rank, b.sid);
+  else KL(KID_SECURE_RANK, k_secure_rank<12>, grid, dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)b.bytes, flags, b.rank, b.sid);
+  KL(KID_SECURE_GATHER, k_secure_gather, dim3(blocks_for(n * (width / 4))), dim3(BLS_BLOCK), n, width, o, (const uint8_t*)b.bytes, rank, sid, flags, b.sorted);
+  KL(KID_SECURE_DIGEST, k_secure_digest, dim3((unsigned)n_sets), dim3(BLS_BLOCK), n_sets, width, o, (const uint8_t*)b.sorted, flags, b.H);
+  KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, rank, sid, (const uint8_t*)b.H, b.flags, b.scal);
+  return 0;
+}
+
+// ---- The batched secure verify, multi verify and plain sums after their argument checks: each body serves the entry point with keys
+// by value and its twin with keys named in a registered key set.  The keys (for the sums: points) come from `keys`, which is
+// keys_by_value or keys_indexed:
+//   keys.arena_bytes(n_sets, large)      what stage() takes from the arena; large: some secure set runs one at a time
+//   keys.stage(c, o, n_sets, large)      after the arena is reserved and the key offsets are uploaded (o): the caller's keys on the
+//                                        device, or its positions and k_keyset_check of them into d_cidx and d_pre
+//   keys.key_bytes(c, n, d_bytes)        secure: PublicKey::to_bytes / to_bytes_with_mode of every key (reference
+//                                        src/secure_aggregation.rs:42,47,272-275)
+//   keys.mul_small(c, n, scal, sid, flags, part)    secure: part[i] = scal[i] * key i for the keys of the small sets
+//   keys.large_keys(c, n, &kfmt)         secure: the n keys as a DEVICE buffer in kfmt, for run_point_sum over a large set
+//   keys.accumulate(c, Q, o, so, sid, part)         multi, sums: the strip sums
+//   keys.fin(c, n_sets, d_status)        after the last kernel, before the statuses leave the device
+//   keys.done()                          sums (no status vector): after the call's synchronisation, its return code
+extern "C++" {
+// batched verify_secure: n_sets independent Signature::verify_secure checks in one call.  a: the checked key and message offsets;
+// every other pointer as the caller gave it (host or device).
+template <class Keys>
+static int verify_secure_batch_run(Ctx* c, int sig_group, int scheme, const Keys& keys, const set_args& a, size_t n_sets, const void* sigs, const uint8_t* msgs,
+                                   const uint64_t* msg_offsets, int fmt, int32_t* status) {
+  int rc;
+  const int pk_group = key_group(sig_group);
+  const size_t n = a.n, ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
+  const secure_plan plan(a.offs, n_sets, (uint64_t)knobs().secure_batch_max);
+  const uint64_t tmax_large = plan.tmax_large;
+  const size_t mtotal = (size_t)a.moffs[n_sets];
   const size_t large_bytes = tmax_large ? keysort_ws_bytes(tmax_large, width) + msm_ws_bytes(tmax_large) + pad256(osz * accumulate_lanes(tmax_large)) +
                                               pad256(osz * POINT_TREE_START) + 4096
                                         : 0;
-  rc = arena_reserve(c, pad256(psz * n) + 2 * pad256(width * n) + pad256(32 * n) + 2 * pad256(4 * n) + pad256(osz * n) + pad256(ssz * n_sets) +
-                            pad256(mtotal) + 2 * pad256(8 * (n_sets + 1)) + pad256(32 * n_sets) + 2 * pad256(4 * n_sets) + 2 * pad256(288 * n_sets) +
-                            pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) + pad256((size_t)WS_F_WORDS * 4 * n_sets) + large_bytes + 16384);
+  rc = arena_reserve(c, keys.arena_bytes(n_sets, tmax_large != 0) + 2 * pad256(width * n) + pad256(32 * n) + 2 * pad256(4 * n) + pad256(osz * n) +
+                            pad256(ssz * n_sets) + pad256(mtotal) + 2 * pad256(8 * (n_sets + 1)) + pad256(32 * n_sets) + 2 * pad256(4 * n_sets) +
+                            2 * pad256(288 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) + pad256((size_t)WS_F_WORDS * 4 * n_sets) + large_bytes + 16384);
   if (rc) return rc;
   c->arena_off = 0;
-  const void *d_pks = nullptr, *d_sigs, *d_msgs, *d_moffs;
-  if (n && (rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
+  const uint64_t* o;
+  if ((rc = upload_offsets(c, a.offs, &o)) || (rc = keys.stage(c, o, n_sets, tmax_large != 0))) return rc;
+  const void *d_sigs, *d_msgs, *d_moffs;
   if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
-  const uint64_t* o;
-  if ((rc = upload_offsets(c, offs, &o))) return rc;
   Carver mem{c};
-  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
-  uint8_t* d_sorted = mem.take<uint8_t>(width * n);
-  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
-  uint32_t* d_rank = mem.take<uint32_t>(4 * n);
-  uint32_t* d_sid = mem.take<uint32_t>(4 * n);
-  uint8_t* d_part = mem.take<uint8_t>(osz * n);
-  uint8_t* d_H = mem.take<uint8_t>(32 * n_sets);
-  uint32_t* d_flags = mem.take<uint32_t>(4 * n_sets);
+  const secure_bufs b(mem, n, n_sets, width, osz);
   const set_tail tail(mem, n_sets);
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
-  const uint8_t* kp = (const uint8_t*)d_pks;
+  HIPCK(hipMemcpyAsync(b.flags, plan.hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
   if (n) {
-    // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:42,47,272-275)
-    with_group(pk_group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes); });
-    if (tmax_small) {
-      HIPCK(hipMemsetAsync(d_rank, 0, 4 * n, c->stream));
-      if (width == 96)
-        KL(KID_SECURE_RANK, k_secure_rank<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_flags, d_rank, d_sid);
-      else
-        KL(KID_SECURE_RANK, k_secure_rank<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_flags, d_rank, d_sid);
-      KL(KID_SECURE_GATHER, k_secure_gather, dim3(blocks_for(n * (width / 4))), dim3(BLS_BLOCK), n, width, o, (const uint8_t*)d_bytes,
-         (const uint32_t*)d_rank, (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_sorted);
-      KL(KID_SECURE_DIGEST, k_secure_digest, dim3((unsigned)n_sets), dim3(BLS_BLOCK), n_sets, width, o, (const uint8_t*)d_sorted,
-         (const uint32_t*)d_flags, d_H);
-      KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_rank, (const uint32_t*)d_sid,
-         (const uint8_t*)d_H, d_flags, d_scal);
-      // aggregated_pk = sum t_i pk_i per set (reference :201-204): one joint NAF ladder per key, then a segmented tree sum
-      with_group(pk_group, [&](auto G) {
-        KL(KID_SHARE_LADDER, k_share_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, (const uint8_t*)d_scal,
-           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
-      });
-      for (uint64_t step = 1; step < tmax_small; step <<= 1) {
-        with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part); });
+    keys.key_bytes(c, n, b.bytes);
+    if (plan.tmax_small) {
+      if ((rc = run_secure_coefficients(c, plan, b, n, o, n_sets, width))) return rc;
+      // aggregated_pk = sum t_i pk_i per set (reference :201-204): one multiplication per key, then a segmented tree sum
+      keys.mul_small(c, n, b.scal, b.sid, b.flags, b.part);
+      for (uint64_t step = 1; step < plan.tmax_small; step <<= 1) {
+        with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)b.sid, b.part); });
       }
     }
     // the large sets, one at a time as blsgpu_verify_secure runs them: device sort, host SHA-256 of the sorted stream, the
     // coefficients, one MSM; its result goes to the set's first record (after the fold, which left the identity there).  The
     // workspace is reused from set to set.
-    const size_t mark = c->arena_off;
+    int kfmt = fmt;
+    const uint8_t* kp = tmax_large ? keys.large_keys(c, n, &kfmt) : nullptr;
+    const size_t ksz = pk_size(sig_group, kfmt), mark = c->arena_off;
     for (size_t s = 0; s < n_sets; s++) {
-      if (!(hflags[s] & SECURE_F_LARGE)) continue;
-      const size_t lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]), T = accumulate_lanes(t);
+      if (!(plan.hflags[s] & SECURE_F_LARGE)) continue;
+      const size_t lo = (size_t)a.offs[s], t = (size_t)(a.offs[s + 1] - a.offs[s]), T = accumulate_lanes(t);
       c->arena_off = mark;
       keysort_ws w;
       if ((rc = keysort_ws_take(c, t, width, w))) return rc;
       uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
       if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
-      if ((rc = run_key_sort_to_host(c, d_bytes + width * lo, t, width, w, nullptr, nullptr))) return rc;
+      if ((rc = run_key_sort_to_host(c, b.bytes + width * lo, t, width, w, nullptr, nullptr))) return rc;
       uint8_t H[32];
       keys_digest_host(c->hpin, width * t, H);
-      HIPCK(hipMemcpy(d_H + 32 * s, H, 32, hipMemcpyHostToDevice));       // the stream is idle here (the sort synchronised)
-      if ((rc = run_coefficients(c, d_H + 32 * s, w.perm_a, t, 0, t, 0, d_scal + 32 * lo, (int32_t*)(d_flags + s)))) return rc;
-      rc = with_group(pk_group, [&](auto G) { return run_point_sum<G()>(c, kp + psz * lo, fmt, d_scal + 32 * lo, nullptr, t, d_msm, T); });
+      HIPCK(hipMemcpy(b.H + 32 * s, H, 32, hipMemcpyHostToDevice));       // the stream is idle here (the sort synchronised)
+      if ((rc = run_coefficients(c, b.H + 32 * s, w.perm_a, t, 0, t, 0, b.scal + 32 * lo, (int32_t*)(b.flags + s)))) return rc;
+      rc = with_group(pk_group, [&](auto G) { return run_point_sum<G()>(c, kp + ksz * lo, kfmt, b.scal + 32 * lo, nullptr, t, d_msm, T); });
       if (rc) return rc;
-      HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
+      HIPCK(hipMemcpyAsync(b.part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
     }
     c->arena_off = mark;
   }
   // the tail: core_verify with the scheme's DST and no key prefix (reference :236-246); a set's key sum lies at its first key's record
-  if ((rc = run_set_tail(c, tail, sig_group, scheme, 0, KID_SECURE_OUT, n_sets, o, o, d_flags, d_part, d_sigs, fmt, d_msgs, d_moffs))) return rc;
-  KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, tail.st);
+  if ((rc = run_set_tail(c, tail, sig_group, scheme, 0, KID_SECURE_OUT, n_sets, o, o, b.flags, b.part, d_sigs, fmt, d_msgs, d_moffs))) return rc;
+  KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)b.flags, tail.st);
+  keys.fin(c, n_sets, tail.st);
   HIPCK(hipGetLastError());
   return status_out_and_sync(c, status, tail.st, n_sets);
+}
+
+// The segmented strip sum (multi_batch.cuh) of the batched multi verify and plain sums: every set's points in strips, one strip sum
+// per lane (lane pair in G2) -- the serial `g += key` of reference src/traits/pk_multi.rs:7-13, src/multi_signature.rs:87-100 and
+// src/aggregate_signature.rs:130-141 -- then a segmented pairwise tree over every set's strips under the caller's fold id.  Set s's
+// sum lies at its first strip's record, d_part[so[s]].  The constructor plans; begin() uploads both offset arrays and carves.
+struct strip_sum {
+  std::vector<uint64_t> soffs;
+  std::vector<uint32_t> ssid;
+  uint64_t qmax;
+  size_t Q;
+  const uint64_t *o = nullptr, *so = nullptr;
+  uint32_t* d_ssid = nullptr;
+  uint8_t* d_part = nullptr;
+  strip_sum(const std::vector<uint64_t>& offs, size_t n_sets) {
+    const uint64_t n = offs[n_sets];
+    qmax = multi_strip_plan(offs.data(), n_sets, multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip), soffs, ssid);
+    Q = ssid.size();
+  }
+  int begin(Ctx* c, const std::vector<uint64_t>& offs, size_t osz) {
+    int rc;
+    if ((rc = upload_offsets(c, offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
+    Carver mem{c};
+    d_ssid = mem.take<uint32_t>(4 * Q);
+    d_part = mem.take<uint8_t>(osz * Q);
+    return mem.ok ? 0 : fail(BLSGPU_E_HIP, "internal: arena too small");
+  }
+  template <class Keys>
+  int run(Ctx* c, int group, const Keys& keys, int fold_kid) const {
+    if (!Q) return 0;
+    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
+    const uint32_t* sid = d_ssid;
+    keys.accumulate(c, Q, o, so, sid, d_part);
+    for (uint64_t step = 1; step < qmax; step <<= 1)
+      with_group(group, [&](auto G) { KL(fold_kid, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
+    return 0;
+  }
+};
+
+// batched multi verify (multi_batch.cuh): n_sets independent MultiSignature::verify checks in one call
+template <class Keys>
+static int multi_verify_batch_run(Ctx* c, int sig_group, int scheme, const Keys& keys, const set_args& a, size_t n_sets, const void* sigs, const uint8_t* msgs,
+                                  const uint64_t* msg_offsets, int fmt, int32_t* status) {
+  int rc;
+  strip_sum strips(a.offs, n_sets);
+  const size_t ssz = sig_size(sig_group, fmt), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ), mtotal = (size_t)a.moffs[n_sets], Q = strips.Q;
+  rc = arena_reserve(c, keys.arena_bytes(n_sets, false) + pad256(ssz * n_sets) + pad256(mtotal) + 3 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) +
+                            2 * pad256(288 * n_sets) + pad256(4 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) +
+                            pad256((size_t)WS_F_WORDS * 4 * n_sets) + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  if ((rc = strips.begin(c, a.offs, osz)) || (rc = keys.stage(c, strips.o, n_sets, false))) return rc;
+  const void *d_sigs, *d_msgs, *d_moffs;
+  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
+  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
+  Carver mem{c};
+  const set_tail tail(mem, n_sets);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if ((rc = strips.run(c, key_group(sig_group), keys, KID_SHARE_FOLD))) return rc;
+  // the tail: core_verify with the scheme's DST, under MessageAugmentation with the summed key's bytes in front of the message
+  // (reference src/traits/sig_aug.rs:20-24); no set is decided before the tail
+  rc = run_set_tail(c, tail, sig_group, scheme, scheme == BLSGPU_SCHEME_AUG, KID_MULTI_OUT, n_sets, strips.o, strips.so, nullptr, strips.d_part, d_sigs, fmt,
+                    d_msgs, d_moffs);
+  if (rc) return rc;
+  keys.fin(c, n_sets, tail.st);
+  HIPCK(hipGetLastError());
+  return status_out_and_sync(c, status, tail.st, n_sets);
+}
+
+// batched plain sums (multi_batch.cuh): the sum of every one of n_sets ragged sets of points in one call; one set is a plan with one set
+template <class Keys>
+static int sum_batch_run(Ctx* c, int group, const Keys& keys, const std::vector<uint64_t>& offs, size_t n_sets, void* out) {
+  int rc;
+  strip_sum strips(offs, n_sets);
+  const size_t osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ), Q = strips.Q;
+  rc = arena_reserve(c, keys.arena_bytes(n_sets, false) + 2 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) + pad256(osz * n_sets) + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  if ((rc = strips.begin(c, offs, osz)) || (rc = keys.stage(c, strips.o, n_sets, false))) return rc;
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n_sets);
+  if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if ((rc = strips.run(c, group, keys, KID_SUM_FOLD))) return rc;
+  with_group(group, [&](auto G) {
+    KL(KID_SUM_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, strips.o, strips.so, (const uint32_t*)nullptr,
+       (const uint8_t*)strips.d_part, d_out, (int32_t*)nullptr);
+  });
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
+  SYNC_FLUSH(c);
+  return keys.done();
+}
+}  // extern "C++"
+
+// The keys of a by-value call: the caller's array of points of `group` in `fmt`, staged.  For the secure verify one joint NAF ladder
+// per key of a small set; kid: the caller's profile id of the strip sums.
+struct keys_by_value {
+  const void* pts;
+  int group, fmt, ser_format, kid;
+  size_t bytes;
+  mutable const void* d_pts = nullptr;
+  size_t arena_bytes(size_t, bool) const { return pad256(bytes); }
+  int stage(Ctx* c, const uint64_t*, size_t, bool) const { return stage_in(c, pts, bytes, &d_pts); }
+  void key_bytes(Ctx* c, size_t n, uint8_t* d_bytes) const {
+    with_group(group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, ser_format, d_bytes); });
+  }
+  void mul_small(Ctx* c, size_t n, const uint8_t* d_scal, const uint32_t* d_sid, const uint32_t* d_flags, uint8_t* d_part) const {
+    with_group(group, [&](auto G) {
+      KL(KID_SHARE_LADDER, k_share_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pts, fmt, d_scal, d_sid, d_flags, d_part);
+    });
+  }
+  const uint8_t* large_keys(Ctx*, size_t, int* kfmt) const {
+    *kfmt = fmt;
+    return (const uint8_t*)d_pts;
+  }
+  void accumulate(Ctx* c, size_t Q, const uint64_t* o, const uint64_t* so, const uint32_t* sid, uint8_t* d_part) const {
+    with_group(group, [&](auto G) {
+      KL(kid, k_multi_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, (const uint8_t*)d_pts, fmt, o, so, sid, d_part);
+    });
+  }
+  void fin(Ctx*, size_t, int32_t*) const {}
+  int done() const { return 0; }
+};
+int blsgpu_verify_secure_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
+                               const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt, int32_t* status) try {
+  int rc = check_common(sig_group, scheme, fmt);
+  if (rc || (rc = check_ser_format(sig_group, ser_format))) return rc;
+  set_args a;
+  rc = set_args_read(a, pks, key_offsets, n_sets, sigs, msgs, msg_offsets, status);
+  if (rc || n_sets == 0) return rc;
+  // One large set alone IS blsgpu_verify_secure (on one device: no sharding).
+  if (n_sets == 1 && a.n >= (uint64_t)knobs().secure_batch_max) {
+    NestedScope ns;
+    return blsgpu_verify_secure(sig_group, scheme, pks, a.n, sigs, msgs + a.moffs[0], (size_t)(a.moffs[1] - a.moffs[0]), ser_format, fmt, status);
+  }
+  CTX_ACQUIRE(c);
+  const keys_by_value keys = {pks, key_group(sig_group), fmt, ser_format, 0, pk_size(sig_group, fmt) * a.n};
+  return verify_secure_batch_run(c, sig_group, scheme, keys, a, n_sets, sigs, msgs, msg_offsets, fmt, status);
 }
 API_CATCH
 
@@ -4720,68 +4897,18 @@ int blsgpu_aggregate_verify_batch(int sig_group, int scheme, const void* pks, co
 }
 API_CATCH
 
-// ---- batched multi verify (multi_batch.cuh): n_sets independent MultiSignature::verify checks in one call
 int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
                               const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
   int rc = check_common(sig_group, scheme, fmt);
   if (rc) return rc;
-  if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
-  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  std::vector<uint64_t> offs, moffs;
-  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", offs))) return rc;
-  const size_t n = (size_t)offs[n_sets];
-  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
-  if (n && !pks) return fail(BLSGPU_E_ARG, "null argument");
-  if (n_sets == 0) return 0;
-  if ((rc = read_offsets(msg_offsets, n_sets, "msg_offsets", moffs, false))) return rc;      // set s's message is msgs + moffs[s]
-  if (moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  set_args a;
+  rc = set_args_read(a, pks, key_offsets, n_sets, sigs, msgs, msg_offsets, status);
+  if (rc || n_sets == 0) return rc;
   // one set alone IS blsgpu_multi_verify: its split over the bound devices and its cut tail serve one huge set
-  if (n_sets == 1) return blsgpu_multi_verify(sig_group, scheme, pks, n, sigs, msgs + moffs[0], (size_t)(moffs[1] - moffs[0]), fmt, status);
-  // plan: the strips of the segmented key sum (multi_batch.cuh)
-  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
-  std::vector<uint64_t> soffs;
-  std::vector<uint32_t> ssid;
-  const uint64_t qmax = multi_strip_plan(offs.data(), n_sets, L, soffs, ssid);
-  const size_t Q = ssid.size();
+  if (n_sets == 1) return blsgpu_multi_verify(sig_group, scheme, pks, a.n, sigs, msgs + a.moffs[0], (size_t)(a.moffs[1] - a.moffs[0]), fmt, status);
   CTX_ACQUIRE(c);
-  const int pk_group = key_group(sig_group);
-  const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
-  const size_t mtotal = (size_t)moffs[n_sets];
-  rc = arena_reserve(c, pad256(psz * n) + pad256(ssz * n_sets) + pad256(mtotal) + 3 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) +
-                            2 * pad256(288 * n_sets) + pad256(4 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) +
-                            pad256((size_t)WS_F_WORDS * 4 * n_sets) + 16384);
-  if (rc) return rc;
-  c->arena_off = 0;
-  const void *d_pks = nullptr, *d_sigs, *d_msgs, *d_moffs;
-  if (n && (rc = stage_in(c, pks, psz * n, &d_pks))) return rc;
-  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
-  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
-  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
-  const uint64_t *o, *so;
-  if ((rc = upload_offsets(c, offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
-  Carver mem{c};
-  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
-  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
-  const set_tail tail(mem, n_sets);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if (Q) {
-    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
-    // MultiPublicKey::from_public_keys per set: the serial `g += key` of reference src/traits/pk_multi.rs:7-13 as one strip sum per
-    // lane (lane pair for G2 keys), then a segmented pairwise tree over every set's strips
-    const uint8_t* kp = (const uint8_t*)d_pks;
-    const uint32_t* sid = d_ssid;
-    with_group(pk_group, [&](auto G) {
-      KL(KID_MULTI_SEG_ACCUM, k_multi_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, kp, fmt, o, so, sid, d_part);
-    });
-    for (uint64_t step = 1; step < qmax; step <<= 1)
-      with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
-  }
-  // the tail: core_verify with the scheme's DST, under MessageAugmentation with the summed key's bytes in front of the message
-  // (reference src/traits/sig_aug.rs:20-24); a set's key sum lies at its first strip's record and no set is decided before the tail
-  rc = run_set_tail(c, tail, sig_group, scheme, scheme == BLSGPU_SCHEME_AUG, KID_MULTI_OUT, n_sets, o, so, nullptr, d_part, d_sigs, fmt, d_msgs, d_moffs);
-  if (rc) return rc;
-  HIPCK(hipGetLastError());
-  return status_out_and_sync(c, status, tail.st, n_sets);
+  const keys_by_value keys = {pks, key_group(sig_group), fmt, 0, KID_MULTI_SEG_ACCUM, pk_size(sig_group, fmt) * a.n};
+  return multi_verify_batch_run(c, sig_group, scheme, keys, a, n_sets, sigs, msgs, msg_offsets, fmt, status);
 }
 API_CATCH
 // ---- batched secure aggregation (secure.cuh): n_sets independent aggregate_secure[_with_mode] sums in one call
@@ -4789,9 +4916,7 @@ int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* si
                                   void* out_sigs, int32_t* status) try {
   int rc = check_common(sig_group, 0, fmt);
   if (rc) return rc;
-  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
-  if (ser_format == 1 && sig_group != 2)
-    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
+  if ((rc = check_ser_format(sig_group, ser_format))) return rc;
   if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
   if (n_sets && (!out_sigs || !status)) return fail(BLSGPU_E_ARG, "null argument");
   std::vector<uint64_t> offs;
@@ -4801,9 +4926,9 @@ int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* si
   if (n && (!pks || !sigs)) return fail(BLSGPU_E_ARG, "null argument");
   if (n_sets == 0) return 0;
   const size_t osz = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ);
-  // plan, as blsgpu_verify_secure_batch: a set of at least BLSGPU_SECURE_BATCH_MAX keys runs one at a time through the steps of
-  // blsgpu_aggregate_secure (run_aggregate_secure_set); all others through the segmented kernels of secure.cuh, one ladder per key in
-  // the signature group and a segmented tree sum.  One large set alone IS blsgpu_aggregate_secure.
+  // plan (secure_plan): a large set runs through the steps of blsgpu_aggregate_secure (run_aggregate_secure_set); all others through
+  // the segmented kernels of secure.cuh, one ladder per key in the signature group and a segmented tree sum.  One large set alone IS
+  // blsgpu_aggregate_secure.
   const uint64_t max_small = (uint64_t)knobs().secure_batch_max;
   if (n_sets == 1 && n >= max_small) {
     if (is_device_ptr(out_sigs)) HIPCK(hipMemset(out_sigs, 0, osz));      // the single call leaves a failed set's record alone
@@ -4813,18 +4938,8 @@ int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* si
   CTX_ACQUIRE(c);
   const int pk_group = key_group(sig_group);
   const size_t psz = pk_size(sig_group, fmt), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED);
-  std::vector<uint32_t> hflags(n_sets, 0);
-  uint64_t tmax_small = 0, tmax_large = 0;
-  for (size_t s = 0; s < n_sets; s++) {
-    const uint64_t t = offs[s + 1] - offs[s];
-    if (t >= max_small) {
-      hflags[s] = SECURE_F_LARGE;
-      tmax_large = std::max(tmax_large, t);
-    } else {
-      tmax_small = std::max(tmax_small, t);
-    }
-  }
-  const size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax_small / 256)));
+  const secure_plan plan(offs, n_sets, max_small);
+  const uint64_t tmax_large = plan.tmax_large;
   const size_t large_bytes = tmax_large ? aggregate_secure_set_bytes(tmax_large, width) + pad256(osz * accumulate_lanes(tmax_large)) +
                                               pad256(osz * POINT_TREE_START) + 4096
                                         : 0;
@@ -4838,54 +4953,34 @@ int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* si
   const uint64_t* o;
   if ((rc = upload_offsets(c, offs, &o))) return rc;
   Carver mem{c};
-  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
-  uint8_t* d_sorted = mem.take<uint8_t>(width * n);
-  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
-  uint32_t* d_rank = mem.take<uint32_t>(4 * n);
-  uint32_t* d_sid = mem.take<uint32_t>(4 * n);
+  const secure_bufs b(mem, n, n_sets, width, osz);
   uint32_t* d_first = mem.take<uint32_t>(4 * n);
-  uint8_t* d_part = mem.take<uint8_t>(osz * n);
-  uint8_t* d_H = mem.take<uint8_t>(32 * n_sets);
-  uint32_t* d_flags = mem.take<uint32_t>(4 * n_sets);
   int32_t* d_st = mem.take<int32_t>(4 * n_sets);
   uint8_t* d_out = mem.stage_out<uint8_t>(out_sigs, osz * n_sets);
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
+  HIPCK(hipMemcpyAsync(b.flags, plan.hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
   const uint8_t *kp = (const uint8_t*)d_pks, *sp = (const uint8_t*)d_sigs;
   if (n) {
     // PublicKey::to_bytes / to_bytes_with_mode of every key (reference src/secure_aggregation.rs:141,144,166,349)
-    with_group(pk_group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, d_bytes); });
-    if (tmax_small) {
-      HIPCK(hipMemsetAsync(d_rank, 0, 4 * n, c->stream));
-      HIPCK(hipMemsetAsync(d_first, 0xff, 4 * n, c->stream));
-      if (width == 96)
-        KL(KID_SECURE_RANK, k_secure_rank<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_flags, d_rank, d_sid);
-      else
-        KL(KID_SECURE_RANK, k_secure_rank<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_flags, d_rank, d_sid);
-      KL(KID_SECURE_GATHER, k_secure_gather, dim3(blocks_for(n * (width / 4))), dim3(BLS_BLOCK), n, width, o, (const uint8_t*)d_bytes,
-         (const uint32_t*)d_rank, (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_sorted);
-      KL(KID_SECURE_DIGEST, k_secure_digest, dim3((unsigned)n_sets), dim3(BLS_BLOCK), n_sets, width, o, (const uint8_t*)d_sorted,
-         (const uint32_t*)d_flags, d_H);
-      KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_rank, (const uint32_t*)d_sid,
-         (const uint8_t*)d_H, d_flags, d_scal);
+    with_group(pk_group, [&](auto G) { KL(KID_COMPRESS, k_compress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, kp, fmt, ser_format, b.bytes); });
+    if (plan.tmax_small) {
+      if ((rc = run_secure_coefficients(c, plan, b, n, o, n_sets, width))) return rc;
       // the signature that goes with the key of a sorted position is that of the FIRST input position holding the same bytes
       // (reference :138-147): duplicates of a key all take the first copy's signature
+      HIPCK(hipMemsetAsync(d_first, 0xff, 4 * n, c->stream));
+      const dim3 grid(blocks_for(n), (unsigned)plan.S);
       if (width == 96)
-        KL(KID_SECURE_FIRST, k_secure_first<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_first);
+        KL(KID_SECURE_FIRST, k_secure_first<24>, grid, dim3(BLS_BLOCK), n, o, (const uint8_t*)b.bytes, (const uint32_t*)b.sid, (const uint32_t*)b.flags, d_first);
       else
-        KL(KID_SECURE_FIRST, k_secure_first<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_first);
+        KL(KID_SECURE_FIRST, k_secure_first<12>, grid, dim3(BLS_BLOCK), n, o, (const uint8_t*)b.bytes, (const uint32_t*)b.sid, (const uint32_t*)b.flags, d_first);
       // sum t_i sig[first_i] per set (reference :149-153): one joint NAF ladder per key, then a segmented tree sum
       with_group(sig_group, [&](auto G) {
-        KL(KID_SECURE_LADDER, k_secure_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, sp, fmt, (const uint8_t*)d_scal, (const uint32_t*)d_first,
-           (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_part);
+        KL(KID_SECURE_LADDER, k_secure_ladder<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, sp, fmt, (const uint8_t*)b.scal, (const uint32_t*)d_first,
+           (const uint32_t*)b.sid, (const uint32_t*)b.flags, b.part);
       });
-      for (uint64_t step = 1; step < tmax_small; step <<= 1) {
+      for (uint64_t step = 1; step < plan.tmax_small; step <<= 1) {
         with_group(sig_group, [&](auto G) {
-          KL(KID_SECURE_AGG_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part);
+          KL(KID_SECURE_AGG_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)b.sid, b.part);
         });
       }
       HIPCK(hipGetLastError());
@@ -4895,19 +4990,19 @@ int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* si
     // the pinned record of the digest, which the next set writes only after its sort has synchronised the stream.
     const size_t mark = c->arena_off, hmark = c->hsmall_off;
     for (size_t s = 0; s < n_sets; s++) {
-      if (!(hflags[s] & SECURE_F_LARGE)) continue;
+      if (!(plan.hflags[s] & SECURE_F_LARGE)) continue;
       const size_t lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]), T = accumulate_lanes(t);
       c->arena_off = mark;
       c->hsmall_off = hmark;
       uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
       if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
-      if ((rc = run_aggregate_secure_set(c, sig_group, d_bytes + width * lo, sp + ssz * lo, t, width, fmt, (int32_t*)(d_flags + s), d_msm, T))) return rc;
-      HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
+      if ((rc = run_aggregate_secure_set(c, sig_group, b.bytes + width * lo, sp + ssz * lo, t, width, fmt, (int32_t*)(b.flags + s), d_msm, T))) return rc;
+      HIPCK(hipMemcpyAsync(b.part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
     }
     c->arena_off = mark;
   }
   with_group(sig_group, [&](auto G) {
-    KL(KID_SECURE_AGG_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, o, (const uint32_t*)d_flags, (const uint8_t*)d_part, d_out,
+    KL(KID_SECURE_AGG_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, o, (const uint32_t*)b.flags, (const uint8_t*)b.part, d_out,
        d_st);
   });
   HIPCK(hipGetLastError());
@@ -4916,60 +5011,16 @@ int blsgpu_aggregate_secure_batch(int sig_group, const void* pks, const void* si
 }
 API_CATCH
 
-// ---- batched plain sums (multi_batch.cuh): the sum of every one of n_sets ragged sets of points in one call
 int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t n_sets, int fmt, void* out) try {
   if (!initialised()) return NOT_INIT();
   if (group != 1 && group != 2) return fail(BLSGPU_E_ARG, "group must be 1 (G1) or 2 (G2)");
   if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE) return fail(BLSGPU_E_ARG, "fmt must be RAW_PROJ or RAW_AFFINE");
-  if (!offsets) return fail(BLSGPU_E_ARG, "null offsets");
-  if (n_sets && !out) return fail(BLSGPU_E_ARG, "null argument");
   std::vector<uint64_t> offs;
-  int rc = read_offsets(offsets, n_sets, "offsets", offs);
-  if (rc) return rc;
-  const size_t n = (size_t)offs[n_sets];
-  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more points in one call");
-  if (n && !pts) return fail(BLSGPU_E_ARG, "null argument");
-  if (n_sets == 0) return 0;
-  // plan: the strips of the segmented sum (multi_batch.cuh), as blsgpu_multi_verify_batch; one set is a plan with one set
-  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
-  std::vector<uint64_t> soffs;
-  std::vector<uint32_t> ssid;
-  const uint64_t qmax = multi_strip_plan(offs.data(), n_sets, L, soffs, ssid);
-  const size_t Q = ssid.size();
+  int rc = sum_args_read(offs, pts, offsets, n_sets, out);
+  if (rc || n_sets == 0) return rc;
   CTX_ACQUIRE(c);
-  const size_t psz = point_bytes(group, fmt), osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
-  rc = arena_reserve(c, pad256(psz * n) + 2 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) + pad256(osz * n_sets) + 16384);
-  if (rc) return rc;
-  c->arena_off = 0;
-  const void* d_pts = nullptr;
-  if (n && (rc = stage_in(c, pts, psz * n, &d_pts))) return rc;
-  const uint64_t *o, *so;
-  if ((rc = upload_offsets(c, offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
-  Carver mem{c};
-  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
-  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
-  uint8_t* d_out = mem.stage_out<uint8_t>(out, osz * n_sets);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if (Q) {
-    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
-    // the serial `g += s` of reference src/multi_signature.rs:87-100 / src/aggregate_signature.rs:130-141 as one strip sum per lane
-    // (lane pair in G2), then a segmented pairwise tree over every set's strips
-    const uint8_t* pp = (const uint8_t*)d_pts;
-    const uint32_t* sid = d_ssid;
-    with_group(group, [&](auto G) {
-      KL(KID_SUM_SEG_ACCUM, k_multi_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, pp, fmt, o, so, sid, d_part);
-    });
-    for (uint64_t step = 1; step < qmax; step <<= 1)
-      with_group(group, [&](auto G) { KL(KID_SUM_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
-  }
-  with_group(group, [&](auto G) {
-    KL(KID_SUM_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, so, (const uint32_t*)nullptr, (const uint8_t*)d_part, d_out,
-       (int32_t*)nullptr);
-  });
-  HIPCK(hipGetLastError());
-  if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
-  SYNC_FLUSH(c);
-  return 0;
+  const keys_by_value keys = {pts, group, fmt, 0, KID_SUM_SEG_ACCUM, point_bytes(group, fmt) * (size_t)offs[n_sets]};
+  return sum_batch_run(c, group, keys, offs, n_sets, out);
 }
 API_CATCH
 // =========================================================================================================
@@ -5471,80 +5522,81 @@ int blsgpu_keyset_mul(uint64_t handle, const uint32_t* idx, const uint8_t* scala
 API_CATCH
 
 // ---- the batched entry points over a key set: (handle, idx) in place of the keys; fmt describes the signatures only
-// the arguments the four share, checked and read
-struct indexed_args {
+// the arguments of the secure and multi verify, checked and read as their by-value twins': the key set gives the signature group,
+// idx stands for the keys
+struct indexed_args : set_args {
   KeySet k;
-  std::vector<uint64_t> offs, moffs;
-  size_t n = 0;
 };
 static int indexed_begin(indexed_args& a, int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
                          const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) {
   int rc = keyset_find(keyset, a.k);
   if (rc) return rc;
   if ((rc = check_common(a.k.sig_group, scheme, fmt))) return rc;
-  if (!key_offsets) return fail(BLSGPU_E_ARG, "null key_offsets");
-  if (n_sets && (!sigs || !msg_offsets || !status)) return fail(BLSGPU_E_ARG, "null argument");
-  if ((rc = read_offsets(key_offsets, n_sets, "key_offsets", a.offs))) return rc;
-  a.n = (size_t)a.offs[n_sets];
-  if (a.n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more keys in one call");
-  if (a.n && !idx) return fail(BLSGPU_E_ARG, "null argument");
-  if (n_sets == 0) return 0;
-  if ((rc = read_offsets(msg_offsets, n_sets, "msg_offsets", a.moffs, false))) return rc;      // set s's message is msgs + moffs[s]
-  if (a.moffs[n_sets] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
-  return 0;
+  return set_args_read(a, idx, key_offsets, n_sets, sigs, msgs, msg_offsets, status);
 }
+
+// The keys of an indexed call: n positions in key set k (the hooks: above verify_secure_batch_run).  stage: the indices, and
+// k_keyset_check of them into d_cidx (idx[i] or KEYSET_SKIP) and d_pre (each set's precedence); fin: k_keyset_fin, the precedence
+// over the statuses.  The strip sums read the set's affine records through d_cidx.  For the secure verify: the stored compressed
+// bytes (no compression and no inversion), one multiplication per key of a small set -- from the fixed-base tables when the set
+// has them -- and for the large sets one gather of the affine records into the arena.
+struct keys_indexed {
+  const KeySet& k;
+  const void* idx;
+  size_t n;
+  int ser_format;
+  mutable uint32_t* d_cidx = nullptr;
+  mutable unsigned long long* d_pre = nullptr;
+  mutable uint8_t* d_keys = nullptr;
+  size_t asz() const { return point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE); }
+  size_t arena_bytes(size_t n_sets, bool large) const { return 2 * pad256(4 * n) + pad256(8 * n_sets) + (large ? pad256(asz() * n) : 0); }
+  int stage(Ctx* c, const uint64_t* o, size_t n_sets, bool large) const {
+    const void* d_idx = nullptr;
+    int rc;
+    if (n && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+    Carver mem{c};
+    d_cidx = mem.take<uint32_t>(4 * n);
+    d_pre = mem.take<unsigned long long>(8 * n_sets);
+    if (large) d_keys = mem.take<uint8_t>(asz() * n);
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    return keyset_check(c, k, (const uint32_t*)d_idx, n, o, n_sets, d_cidx, d_pre);
+  }
+  void key_bytes(Ctx* c, size_t cnt_, uint8_t* d_bytes) const { KEYSET_GATHER(point_bytes(k.group, BLSGPU_FMT_COMPRESSED) / 4, k.comp, ser_format, d_bytes); }
+  void mul_small(Ctx* c, size_t cnt, const uint8_t* d_scal, const uint32_t* d_sid, const uint32_t* d_flags, uint8_t* d_part) const {
+    (void)keyset_launch_mul(c, k, cnt, d_cidx, d_scal, d_sid, d_flags, d_part);
+  }
+  const uint8_t* large_keys(Ctx* c, size_t cnt_, int* kfmt) const {
+    KEYSET_GATHER(asz() / 4, k.aff, 0, d_keys);
+    *kfmt = BLSGPU_FMT_RAW_AFFINE;
+    return d_keys;
+  }
+  void accumulate(Ctx* c, size_t Q, const uint64_t* o, const uint64_t* so, const uint32_t* sid, uint8_t* d_part) const {
+    const uint32_t* ci = d_cidx;
+    with_group(k.group, [&](auto G) {
+      KL(KID_KEYSET_ACCUM, k_keyset_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, (const uint8_t*)k.aff, ci, o, so, sid, d_part);
+    });
+  }
+  void fin(Ctx* c, size_t n_sets, int32_t* d_status) const {
+    KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const unsigned long long*)d_pre, d_status);
+  }
+};
+// ... of the indexed sum, a call without a status vector: keyset_check_whole in place of the per-set check, and after the call's
+// synchronisation the one word that says whether some index was outside the table
+struct keys_indexed_whole : keys_indexed {
+  mutable unsigned long long* h_pre = nullptr;
+  size_t arena_bytes(size_t, bool) const { return 2 * pad256(4 * n); }
+  int stage(Ctx* c, const uint64_t*, size_t, bool) const { return keyset_check_whole(c, k, idx, n, &d_cidx, &h_pre); }
+  int done() const { return *h_pre == 0 ? fail(BLSGPU_E_ARG, "an index is outside the key set") : 0; }
+};
 
 int blsgpu_multi_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
                                       const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
   indexed_args a;
   int rc = indexed_begin(a, scheme, keyset, idx, key_offsets, n_sets, sigs, msgs, msg_offsets, fmt, status);
   if (rc || n_sets == 0) return rc;
-  const KeySet& k = a.k;
-  const int sig_group = k.sig_group;
-  const size_t n = a.n;
-  // plan: the strips of the segmented key sum (multi_batch.cuh), as blsgpu_multi_verify_batch
-  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
-  std::vector<uint64_t> soffs;
-  std::vector<uint32_t> ssid;
-  const uint64_t qmax = multi_strip_plan(a.offs.data(), n_sets, L, soffs, ssid);
-  const size_t Q = ssid.size();
-  CTX_ACQUIRE_ON(c, k.devidx);
-  const size_t ssz = sig_size(sig_group, fmt), osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
-  const size_t mtotal = (size_t)a.moffs[n_sets];
-  rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(ssz * n_sets) + pad256(mtotal) + 3 * pad256(8 * (n_sets + 1)) + pad256(8 * n_sets) + pad256(4 * Q) +
-                            pad256(osz * Q) + 2 * pad256(288 * n_sets) + pad256(4 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) +
-                            pad256((size_t)WS_F_WORDS * 4 * n_sets) + 16384);
-  if (rc) return rc;
-  c->arena_off = 0;
-  const void *d_idx = nullptr, *d_sigs, *d_msgs, *d_moffs;
-  if (n && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
-  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
-  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
-  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
-  const uint64_t *o, *so;
-  if ((rc = upload_offsets(c, a.offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
-  Carver mem{c};
-  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
-  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n_sets);
-  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
-  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
-  const set_tail tail(mem, n_sets);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, o, n_sets, d_cidx, d_pre))) return rc;
-  if (Q) {
-    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
-    const uint32_t *sid = d_ssid, *ci = d_cidx;
-    with_group(k.group, [&](auto G) {
-      KL(KID_KEYSET_ACCUM, k_keyset_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, (const uint8_t*)k.aff, ci, o, so, sid, d_part);
-    });
-    for (uint64_t step = 1; step < qmax; step <<= 1)
-      with_group(k.group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
-  }
-  rc = run_set_tail(c, tail, sig_group, scheme, scheme == BLSGPU_SCHEME_AUG, KID_MULTI_OUT, n_sets, o, so, nullptr, d_part, d_sigs, fmt, d_msgs, d_moffs);
-  if (rc) return rc;
-  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const unsigned long long*)d_pre, tail.st);
-  HIPCK(hipGetLastError());
-  return status_out_and_sync(c, status, tail.st, n_sets);
+  CTX_ACQUIRE_ON(c, a.k.devidx);
+  const keys_indexed keys = {a.k, idx, a.n, 0};
+  return multi_verify_batch_run(c, a.k.sig_group, scheme, keys, a, n_sets, sigs, msgs, msg_offsets, fmt, status);
 }
 API_CATCH
 
@@ -5552,53 +5604,12 @@ int blsgpu_sum_indexed_batch(uint64_t keyset, const uint32_t* idx, const uint64_
   KeySet k;
   int rc = keyset_find(keyset, k);
   if (rc) return rc;
-  if (!offsets) return fail(BLSGPU_E_ARG, "null offsets");
-  if (n_sets && !out) return fail(BLSGPU_E_ARG, "null argument");
   std::vector<uint64_t> offs;
-  if ((rc = read_offsets(offsets, n_sets, "offsets", offs))) return rc;
-  const size_t n = (size_t)offs[n_sets];
-  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more points in one call");
-  if (n && !idx) return fail(BLSGPU_E_ARG, "null argument");
-  if (n_sets == 0) return 0;
-  const uint64_t L = multi_strip_len(n, accumulate_lanes(n), (uint64_t)knobs().multi_strip);
-  std::vector<uint64_t> soffs;
-  std::vector<uint32_t> ssid;
-  const uint64_t qmax = multi_strip_plan(offs.data(), n_sets, L, soffs, ssid);
-  const size_t Q = ssid.size();
+  rc = sum_args_read(offs, idx, offsets, n_sets, out);
+  if (rc || n_sets == 0) return rc;
   CTX_ACQUIRE_ON(c, k.devidx);
-  const int group = k.group;
-  const size_t osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
-  rc = arena_reserve(c, 2 * pad256(4 * n) + 2 * pad256(8 * (n_sets + 1)) + pad256(4 * Q) + pad256(osz * Q) + pad256(osz * n_sets) + 16384);
-  if (rc) return rc;
-  c->arena_off = 0;
-  uint32_t* d_cidx;
-  unsigned long long* h_pre;
-  if ((rc = keyset_check_whole(c, k, idx, n, &d_cidx, &h_pre))) return rc;
-  const uint64_t *o, *so;
-  if ((rc = upload_offsets(c, offs, &o)) || (rc = upload_offsets(c, soffs, &so))) return rc;
-  Carver mem{c};
-  uint32_t* d_ssid = mem.take<uint32_t>(4 * Q);
-  uint8_t* d_part = mem.take<uint8_t>(osz * Q);
-  uint8_t* d_out = mem.stage_out<uint8_t>(out, osz * n_sets);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  if (Q) {
-    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
-    const uint32_t *sid = d_ssid, *ci = d_cidx;
-    with_group(group, [&](auto G) {
-      KL(KID_KEYSET_ACCUM, k_keyset_accumulate_seg<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, (const uint8_t*)k.aff, ci, o, so, sid, d_part);
-    });
-    for (uint64_t step = 1; step < qmax; step <<= 1)
-      with_group(group, [&](auto G) { KL(KID_SUM_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, so, sid, d_part); });
-  }
-  with_group(group, [&](auto G) {
-    KL(KID_SUM_OUT, k_set_sum_out<G()>, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, so, (const uint32_t*)nullptr, (const uint8_t*)d_part, d_out,
-       (int32_t*)nullptr);
-  });
-  HIPCK(hipGetLastError());
-  if ((rc = stage_back(c, out, d_out, osz * n_sets))) return rc;
-  SYNC_FLUSH(c);
-  if (*h_pre == 0) return fail(BLSGPU_E_ARG, "an index is outside the key set");
-  return 0;
+  const keys_indexed_whole keys = {{k, idx, (size_t)offs[n_sets], 0}};
+  return sum_batch_run(c, k.group, keys, offs, n_sets, out);
 }
 API_CATCH
 
@@ -5606,117 +5617,10 @@ int blsgpu_verify_secure_indexed_batch(int scheme, uint64_t keyset, const uint32
                                        const uint8_t* msgs, const uint64_t* msg_offsets, int ser_format, int fmt, int32_t* status) try {
   indexed_args a;
   int rc = indexed_begin(a, scheme, keyset, idx, key_offsets, n_sets, sigs, msgs, msg_offsets, fmt, status);
-  if (rc) return rc;
-  const KeySet& k = a.k;
-  const int sig_group = k.sig_group, pk_group = k.group;
-  if (ser_format != 0 && ser_format != 1) return fail(BLSGPU_E_ARG, "ser_format must be 0 (Modern) or 1 (Legacy)");
-  if (ser_format == 1 && sig_group != 2)
-    return fail(BLSGPU_E_ARG, "Legacy serialization exists only for Bls12381G2Impl (48-byte keys), reference src/signature.rs:201-204");
-  if (n_sets == 0) return 0;
-  const size_t n = a.n;
-  const std::vector<uint64_t>& offs = a.offs;
-  // plan, as blsgpu_verify_secure_batch: a set of at least BLSGPU_SECURE_BATCH_MAX keys runs one at a time through the machinery of
-  // blsgpu_verify_secure, on keys gathered into the arena; all others through the segmented kernels of secure.cuh and one
-  // multiplication per key, from the fixed-base tables when the set has them
-  const uint64_t max_small = (uint64_t)knobs().secure_batch_max;
-  CTX_ACQUIRE_ON(c, k.devidx);
-  const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ssz = sig_size(sig_group, fmt), width = pk_size(sig_group, BLSGPU_FMT_COMPRESSED),
-               osz = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ);
-  std::vector<uint32_t> hflags(n_sets, 0);
-  uint64_t tmax_small = 0, tmax_large = 0;
-  for (size_t s = 0; s < n_sets; s++) {
-    const uint64_t t = offs[s + 1] - offs[s];
-    if (t >= max_small) {
-      hflags[s] = SECURE_F_LARGE;
-      tmax_large = std::max(tmax_large, t);
-    } else {
-      tmax_small = std::max(tmax_small, t);
-    }
-  }
-  const size_t S = std::max<size_t>(1, std::min<size_t>(64, (size_t)(tmax_small / 256)));
-  const size_t mtotal = (size_t)a.moffs[n_sets];
-  const size_t large_bytes = tmax_large ? pad256(psz * n) + keysort_ws_bytes(tmax_large, width) + msm_ws_bytes(tmax_large) + pad256(osz * accumulate_lanes(tmax_large)) +
-                                              pad256(osz * POINT_TREE_START) + 4096
-                                        : 0;
-  rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n_sets) + 2 * pad256(width * n) + pad256(32 * n) + 2 * pad256(4 * n) + pad256(osz * n) +
-                            pad256(ssz * n_sets) + pad256(mtotal) + 2 * pad256(8 * (n_sets + 1)) + pad256(32 * n_sets) + 2 * pad256(4 * n_sets) +
-                            2 * pad256(288 * n_sets) + pad256((size_t)WS_PAIRS_WORDS * 4 * n_sets) + pad256((size_t)WS_F_WORDS * 4 * n_sets) + large_bytes + 16384);
-  if (rc) return rc;
-  c->arena_off = 0;
-  const void *d_idx = nullptr, *d_sigs, *d_msgs, *d_moffs;
-  if (n && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
-  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
-  if ((rc = stage_in(c, msgs, mtotal, &d_msgs))) return rc;
-  if ((rc = stage_in(c, msg_offsets, 8 * (n_sets + 1), &d_moffs))) return rc;
-  const uint64_t* o;
-  if ((rc = upload_offsets(c, offs, &o))) return rc;
-  Carver mem{c};
-  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
-  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n_sets);
-  uint8_t* d_bytes = mem.take<uint8_t>(width * n);
-  uint8_t* d_sorted = mem.take<uint8_t>(width * n);
-  uint8_t* d_scal = mem.take<uint8_t>(32 * n);
-  uint32_t* d_rank = mem.take<uint32_t>(4 * n);
-  uint32_t* d_sid = mem.take<uint32_t>(4 * n);
-  uint8_t* d_part = mem.take<uint8_t>(osz * n);
-  uint8_t* d_H = mem.take<uint8_t>(32 * n_sets);
-  uint32_t* d_flags = mem.take<uint32_t>(4 * n_sets);
-  uint8_t* d_keys = tmax_large ? mem.take<uint8_t>(psz * n) : nullptr;
-  const set_tail tail(mem, n_sets);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemcpyAsync(d_flags, hflags.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
-  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, o, n_sets, d_cidx, d_pre))) return rc;
-  if (n) {
-    // PublicKey::to_bytes / to_bytes_with_mode of every key: the stored bytes, no compression and no inversion
-    const size_t cnt_ = n;
-    KEYSET_GATHER(width / 4, k.comp, ser_format, d_bytes);
-    if (tmax_small) {
-      HIPCK(hipMemsetAsync(d_rank, 0, 4 * n, c->stream));
-      if (width == 96)
-        KL(KID_SECURE_RANK, k_secure_rank<24>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_flags, d_rank, d_sid);
-      else
-        KL(KID_SECURE_RANK, k_secure_rank<12>, dim3(blocks_for(n), (unsigned)S), dim3(BLS_BLOCK), n, o, n_sets, (const uint8_t*)d_bytes,
-           (const uint32_t*)d_flags, d_rank, d_sid);
-      KL(KID_SECURE_GATHER, k_secure_gather, dim3(blocks_for(n * (width / 4))), dim3(BLS_BLOCK), n, width, o, (const uint8_t*)d_bytes,
-         (const uint32_t*)d_rank, (const uint32_t*)d_sid, (const uint32_t*)d_flags, d_sorted);
-      KL(KID_SECURE_DIGEST, k_secure_digest, dim3((unsigned)n_sets), dim3(BLS_BLOCK), n_sets, width, o, (const uint8_t*)d_sorted,
-         (const uint32_t*)d_flags, d_H);
-      KL(KID_SECURE_COEFF, k_secure_coeff, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_rank, (const uint32_t*)d_sid,
-         (const uint8_t*)d_H, d_flags, d_scal);
-      if ((rc = keyset_launch_mul(c, k, n, d_cidx, d_scal, d_sid, d_flags, d_part))) return rc;
-      for (uint64_t step = 1; step < tmax_small; step <<= 1) {
-        with_group(pk_group, [&](auto G) { KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, step, o, (const uint32_t*)d_sid, d_part); });
-      }
-    }
-    if (tmax_large) KEYSET_GATHER(psz / 4, k.aff, 0, d_keys);
-    const size_t mark = c->arena_off;
-    for (size_t s = 0; s < n_sets; s++) {
-      if (!(hflags[s] & SECURE_F_LARGE)) continue;
-      const size_t lo = (size_t)offs[s], t = (size_t)(offs[s + 1] - offs[s]), T = accumulate_lanes(t);
-      c->arena_off = mark;
-      keysort_ws w;
-      if ((rc = keysort_ws_take(c, t, width, w))) return rc;
-      uint8_t* d_msm = (uint8_t*)arena_take(c, osz * T);
-      if (!d_msm) return fail(BLSGPU_E_HIP, "internal: arena too small");
-      if ((rc = run_key_sort_to_host(c, d_bytes + width * lo, t, width, w, nullptr, nullptr))) return rc;
-      uint8_t H[32];
-      keys_digest_host(c->hpin, width * t, H);
-      HIPCK(hipMemcpy(d_H + 32 * s, H, 32, hipMemcpyHostToDevice));       // the stream is idle here (the sort synchronised)
-      if ((rc = run_coefficients(c, d_H + 32 * s, w.perm_a, t, 0, t, 0, d_scal + 32 * lo, (int32_t*)(d_flags + s)))) return rc;
-      rc = with_group(pk_group, [&](auto G) {
-        return run_point_sum<G()>(c, d_keys + psz * lo, BLSGPU_FMT_RAW_AFFINE, d_scal + 32 * lo, nullptr, t, d_msm, T);
-      });
-      if (rc) return rc;
-      HIPCK(hipMemcpyAsync(d_part + osz * lo, d_msm, osz, hipMemcpyDeviceToDevice, c->stream));
-    }
-    c->arena_off = mark;
-  }
-  if ((rc = run_set_tail(c, tail, sig_group, scheme, 0, KID_SECURE_OUT, n_sets, o, o, d_flags, d_part, d_sigs, fmt, d_msgs, d_moffs))) return rc;
-  KL(KID_SECURE_FIN, k_secure_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_flags, tail.st);
-  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const unsigned long long*)d_pre, tail.st);
-  HIPCK(hipGetLastError());
-  return status_out_and_sync(c, status, tail.st, n_sets);
+  if (rc || (rc = check_ser_format(a.k.sig_group, ser_format)) || n_sets == 0) return rc;
+  CTX_ACQUIRE_ON(c, a.k.devidx);
+  const keys_indexed keys = {a.k, idx, a.n, ser_format};
+  return verify_secure_batch_run(c, a.k.sig_group, scheme, keys, a, n_sets, sigs, msgs, msg_offsets, fmt, status);
 }
 API_CATCH
 

@@ -58,19 +58,20 @@ def draw(t, sizes, rng):
     return out
 
 
-def multi_sets(api, sg, scheme, t, rng, sizes=SIZES):
-    """[(idx, sig, msg)], every non-empty set valid for MultiSignature::verify: the signature is (sum of the secrets) H(msg)"""
-    idxs = draw(t, sizes, rng)
+def multi_sets(api, sg, scheme, t, rng, sizes=SIZES, idxs=None):
+    """[(idx, sig, msg)], every non-empty set valid for MultiSignature::verify: the signature is (sum of the secrets) H(msg).
+    idxs: the index lists themselves, in place of a draw."""
+    idxs = idxs or draw(t, sizes, rng)
     msgs = [b'keyset multi %d' % s for s in range(len(idxs))]
     sigs = mb.signatures(api, sg, scheme, [sum(t['ks'][i] for i in idx) for idx in idxs], msgs)
     return list(zip(idxs, sigs, msgs))
 
 
-def secure_sets(api, sg, scheme, t, rng, legacy=False, sizes=SIZES):
-    """[(idx, sig, msg)], every non-empty set valid for verify_secure over the keys' Modern or Legacy bytes"""
+def secure_sets(api, sg, scheme, t, rng, legacy=False, sizes=SIZES, idxs=None):
+    """[(idx, sig, msg)], every non-empty set valid for verify_secure over the keys' Modern or Legacy bytes (idxs: as multi_sets)"""
     g = 3 - sg
     out = []
-    for s, idx in enumerate(draw(t, sizes, rng)):
+    for s, idx in enumerate(idxs or draw(t, sizes, rng)):
         msg = b'keyset secure %d' % s
         kb = api.serialize(g, [t['points'][i] for i in idx], legacy=legacy) if idx else []
         out.append((idx, sb.sign(api, sg, scheme, aggregate_secret(kb, [t['ks'][i] for i in idx]) if idx else 0, msg), msg))

@@ -11,6 +11,7 @@ import sys
 import pytest
 
 import keyset_cases as kc
+import keyset_single_worker as single
 import util
 from util import c
 
@@ -182,6 +183,37 @@ def test_indexed_secure(api, sets_of, sg, scheme):
         print('indexed', got, 'by value', want)
         assert got == want and len(set(want)) >= 4
         assert api.verify_secure_indexed_batch(sets_of(sg, True), scheme, sets + bad, ser_format=int(legacy)) == st + want
+
+
+@pytest.mark.parametrize('sg', [1, 2])
+def test_single_set_indexed(api, sets_of, sg):
+    """One set alone: the by-value calls forward it to the single-set entry points, the indexed calls run it through the bodies they
+    share with the by-value calls of many sets.  Five positions, one of them twice; a good signature and one over another message."""
+    g = 3 - sg
+    ks = sets_of(sg, False)
+    want = {'good': [[api.OK]] * 2, 'tampered': [[api.INVALID_SIGNATURE]] * 2}
+    got = {}
+    for name, sets in single.cases(api, kc, sg, kc.multi_sets).items():
+        got[name] = [api.multi_verify_indexed_batch(ks, api.BASIC, sets), api.multi_verify_batch(sg, api.BASIC, kc.gathered(api, ks, sets))]
+    print('multi [indexed, by value]', got)
+    assert got == want
+    got = single.secure_statuses(api, kc, sg, ks)
+    print('secure [indexed, by value]', got)
+    assert got == want
+    sums = [api.sum_indexed_batch(ks, [single.IDX]), api.sum_batch(g, [ks.get(single.IDX)[0]])]       # no signature in this one
+    assert api.serialize(g, sums[0]) == api.serialize(g, sums[1]) and sums[0][0] != bytes(144 * g)
+
+
+def test_single_set_indexed_large_path(api):
+    """... and with BLSGPU_SECURE_BATCH_MAX=2 the lone secure set takes the one-at-a-time loop of large sets through the indexed key
+    source (its by-value twin is the single call): tests/keyset_single_worker.py in a child process, as test_every_plan_same_statuses."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, BLSGPU_SECURE_BATCH_MAX='2')
+    p = subprocess.run([sys.executable, os.path.join(here, 'keyset_single_worker.py')], env=env, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    got = json.loads(p.stdout.strip().splitlines()[-1])
+    print('secure [indexed, by value]', got)
+    assert got == {str(sg): {'good': [[api.OK]] * 2, 'tampered': [[api.INVALID_SIGNATURE]] * 2} for sg in (1, 2)}
 
 
 @pytest.mark.parametrize('tables', [False, True], ids=['ladder', 'tables'])
