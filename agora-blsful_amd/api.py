@@ -40,7 +40,7 @@ EXPORTS = [
     'blsgpu_aggregate_partial', 'blsgpu_fp12_product_is_one', 'blsgpu_core_verify', 'blsgpu_deserialize', 'blsgpu_pop_verify_batch', 'blsgpu_aggregate_secure',
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
-    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_coop_pairing', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
@@ -195,6 +195,7 @@ def load_library(path=None):
         lib.blsgpu_verify_shared_batch.argtypes = [ci, ci, vp, vp, u64p, sz, u8p, u64p, ci, i32p]
         lib.blsgpu_verify_shared_indexed_batch.argtypes = [ci, h, u32p, vp, u64p, sz, u8p, u64p, ci, i32p]
         lib.blsgpu_aggregate_verify_indexed_batch.argtypes = [ci, h, u32p, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
+        lib.blsgpu_debug_coop_pairing_keyed.argtypes = [ci, h, u32p, i32p, sz, i32p, i32p]
         _lib = lib
     return _lib
 
@@ -1161,6 +1162,30 @@ def debug_coop_pairing(mode, fixed_g2, items, status=None):
     st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
     out = (ctypes.c_int32 * max(168 * n, 1))()
     _check(lib.blsgpu_debug_coop_pairing(mode, fixed_g2, ctypes.cast(arr, ctypes.c_void_p), n, ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+    if mode != 0:
+        return list(st[:n])
+    o = list(out)
+    return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n)]
+
+
+def debug_coop_pairing_keyed(mode, keyset, idx, items, status=None):
+    """k_pairing_coop_keyed on caller-supplied operands: the records of debug_coop_pairing with fixed_g2 = 2, pair 0's G2 member being
+    entry idx[i] of `keyset` (a KeySet created with lines; the record's own Q members are not read).  mode 0 returns per item the twelve
+    limb vectors of the easy-part value in tower order (every limb COOP_SENTINEL for an item whose status is not OK), mode 1 the
+    statuses.  A set without line tables, an index outside the set and more than 4,096 items raise (BLSGPU_E_ARG)."""
+    lib = init()
+    n = len(items)
+    assert len(idx) == n
+    flat = []
+    for vecs in items:
+        assert len(vecs) == 12 and all(len(v) == 14 for v in vecs)
+        for v in vecs:
+            flat += v
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
+    out = (ctypes.c_int32 * max(168 * n, 1))()
+    _check(lib.blsgpu_debug_coop_pairing_keyed(mode, keyset.handle, ctypes.cast(_u32(idx), ctypes.c_void_p), ctypes.cast(arr, ctypes.c_void_p), n,
+                                               ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
     if mode != 0:
         return list(st[:n])
     o = list(out)

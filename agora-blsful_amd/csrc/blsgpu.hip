@@ -54,6 +54,7 @@ enum {
   KID_KEYSET_LINES, KID_LINES_KEYED,     // key sets with line tables (keyset.cuh): the build at creation, and the line kernel that reads both rows
   KID_LINESP_KEYED,                      // ... and the one of the batched aggregate verify over such a set (in the place of k_linesp)
   KID_KEYSET_SEAL_AT, KID_KEYSET_BUILD_AT, KID_KEYSET_LINES_AT,   // blsgpu_keyset_update / blsgpu_keyset_append: the positional forms of seal, build, lines
+  KID_PAIRING_COOP_KEYED,                // the one-wave pairing that reads a registered key's rows (in the place of k_pairing_coop)
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -72,7 +73,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_group_lines", "k_prepare_shared",
                                     "k_keyset_lines", "k_lines2s_keyed",
                                     "k_linesp_keyed",
-                                    "k_keyset_seal_at", "k_keyset_build_at", "k_keyset_lines_at"};
+                                    "k_keyset_seal_at", "k_keyset_build_at", "k_keyset_lines_at",
+                                    "k_pairing_coop_keyed"};
 
 struct Ctx {
   int dev = -1;
@@ -763,9 +765,10 @@ void launch_finalexp_chunk(Ctx* c, size_t n, size_t first, size_t cnt, const uin
 // sh_table / sh_group (fixed_g2 = 0, shared-message verify): on the lane-split path pair 1's G2 member is the point of item i's group
 // sh_group[i], its normalised rows in sh_table (verify_shared.cuh; the records carry the signature's pair first) -- one line
 // launch per chunk (k_lines2s_shared) instead of two.  Every other path takes the records as two general pairs.
-// key_table / key_of (fixed_g2 = 2, registered key sets with line tables): on the lane-split path pair 0's G2 member is the entry
-// key_of[i] of a set whose rows are in key_table (keyset.cuh) -- the chunk's line launch reads both rows and walks nothing
-// (k_lines2s_keyed).  Every other path ignores them.
+// key_table / key_of (fixed_g2 = 2, registered key sets with line tables): pair 0's G2 member is the entry key_of[i] of a set whose
+// rows are in key_table (keyset.cuh).  On the lane-split path the chunk's line launch reads both rows and walks nothing
+// (k_lines2s_keyed); on the one-wave path k_pairing_coop_keyed runs the Miller loop of two tabled pairs (coop.cuh
+// coop_miller2_tables).  The row-wide engine and the BLSGPU_WIDE_MODE=1 branch ignore them.
 int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2, const uint32_t* sh_table = nullptr,
                  const uint32_t* sh_group = nullptr, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
   if (n <= wide_max_items() && n <= coop_max_items()) {
@@ -781,7 +784,10 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
       KL(KID_WIDE, k_pairing_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), n, (const uint32_t*)d_pairs, d_status, fixed_g2);
     }
   } else if (n <= coop_max_items()) {  // small batches: one wave per item
-    KL(KID_PAIRING_COOP, k_pairing_coop, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, fixed_g2);
+    if (fixed_g2 == 2 && key_table)
+      KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, key_table, key_of, (uint32_t*)nullptr);
+    else
+      KL(KID_PAIRING_COOP, k_pairing_coop, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, fixed_g2);
   } else {                      // two lanes per item (tower_split.cuh)
     // The Miller loop in two kernels (kernels.cuh k_lines2s / k_millerf2s), a chunk of at most miller_chunk_items() items at a
     // time: the chunk's merged line values pass through the context's line workspace.  BLSGPU_MILLER_V1=1, or no memory for
@@ -920,7 +926,8 @@ int launch_lines_and_post(Ctx* c, size_t n, uint32_t* d_rec, int32_t* d_status) 
 int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_t* d_sigs, int fmt, const uint8_t* d_msgs,
                      const uint64_t* d_offs, int single_msg, const dst_arg& dst, size_t n, uint32_t* d_pairs, uint32_t* d_f,
                      int32_t* d_status, int pre_status = 0, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
-  // key_table / key_of: the keys are entries of a registered set with line tables (run_pairing2); only the last plan passes them on
+  // key_table / key_of: the keys are entries of a registered set with line tables (run_pairing2); the two plans above
+  // BLSGPU_WIDE_MAX items pass them on
   if (n == 0) return 0;
   if (sg == 1 && aug == 0 && !pre_status && n <= wide_max_items() && n <= coop_max_items()) {
     // Single verifications of Bls12381G1Impl without a key prefix, cut where the inputs allow (csrc/kernels.cuh k_pairing_pre /
@@ -1006,7 +1013,7 @@ int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_
     // the hashes stay uncleared (bit 1) and the fixed pair is (sig, -[c] g2) (table 2), as everywhere for this implementation
     KL(KID_HASH, k_hash_to_g1_wide, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_msgs, d_offs, (single_msg & 1) | 2, dst, d_hashes, (uint32_t*)nullptr);
     KL(KID_PREPARE, k_prepare_hashed<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_pks, d_sigs, (const uint8_t*)d_hashes, d_pairs, d_status, fmt);
-    return run_pairing2(c, n, d_pairs, d_f, d_status, 2);
+    return run_pairing2(c, n, d_pairs, d_f, d_status, 2, nullptr, nullptr, key_table, key_of);
   }
   // two lanes per item (the two SSWU maps side by side, G2 point arithmetic on the lane-split tower) for both implementations
   // and every batch size (rounds 1-2 used one lane per item for full Bls12381G1Impl batches; see below)
@@ -5405,7 +5412,7 @@ API_CATCH
 
 // the indices of a call against the table: d_cidx gets idx[i] or KEYSET_SKIP, d_pre (n_sets slots, or one when d_offs is null and
 // `whole` is set: the whole call is one set) each set's precedence
-// d_walk (a set with line tables, a call that may take the keyed line kernel): one word, raised when a position names a finite
+// d_walk (a set with line tables, a call that may take a kernel that reads the rows): one word, raised when a position names a finite
 // entry without usable rows
 static int keyset_check(Ctx* c, const KeySet& k, const uint32_t* d_idx, size_t n, const uint64_t* d_offs, size_t n_sets, uint32_t* d_cidx,
                         unsigned long long* d_pre, uint32_t* d_walk = nullptr) {
@@ -5416,9 +5423,14 @@ static int keyset_check(Ctx* c, const KeySet& k, const uint32_t* d_idx, size_t n
        d_pre, d_walk ? (const int32_t*)k.nolines : (const int32_t*)nullptr, d_walk);
   return 0;
 }
-// May a one-key-per-item call of n items over set k take the keyed line kernel?  Decided from the call's shape: a set with line
-// tables (so: signatures in G1) on the lane-split path with its two-kernel Miller loop.
-static bool keyset_lines_wanted(const KeySet& k, size_t n) { return k.lines && k.sig_group == 1 && n > coop_max_items() && miller_chunk_items() != 0; }
+// May a one-key-per-item call of n items over set k read the keys' rows?  Decided from the call's shape: a set with line tables
+// (so: signatures in G1) above the row-wide engine's range -- on the one-wave path (k_pairing_coop_keyed), or on the lane-split
+// path with its two-kernel Miller loop (k_lines2s_keyed).  At and below BLSGPU_WIDE_MAX items a call gains no read-back.
+static bool keyset_lines_wanted(const KeySet& k, size_t n) {
+  if (!k.lines || k.sig_group != 1) return false;
+  if (n > coop_max_items()) return miller_chunk_items() != 0;     // the lane-split path
+  return n > wide_max_items();                                     // one wave per item; the engine below that
+}
 // ... and, after k_keyset_check with d_walk: the one word read back (as run_verify_shared_items reads k_group_lines' word) says
 // whether every named entry has rows; *table = the set's rows, or null: the call walks the keys
 static int keyset_lines_decide(Ctx* c, const KeySet& k, const uint32_t* d_walk, const uint32_t** table) {
@@ -5956,6 +5968,60 @@ int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
   return status_out_and_sync(c, status, d_status, n);
+}
+API_CATCH
+
+/* Self-test hook of k_pairing_coop_keyed (include/blsgpu.h): the records of blsgpu_debug_coop_pairing with fixed_g2 = 2, pair 0's G2
+ * member being entry idx[i] of a set with line tables.  The kernel is launched exactly as run_pairing2 launches it (mode 1), or with
+ * the export of the easy-part value (mode 0). */
+int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* idx, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
+  KeySet k;
+  int rc = keyset_find(keyset, k);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!in || !idx || !status || mode < 0 || mode > 1 || n > 4096 || (mode == 0 && !out_f12) || is_device_ptr(in) || is_device_ptr(idx) || is_device_ptr(status) ||
+      is_device_ptr(out_f12))
+    return fail(BLSGPU_E_ARG, "bad argument");
+  if (!k.lines || k.sig_group != 1) return fail(BLSGPU_E_ARG, "the key set has no line tables");
+  for (size_t i = 0; i < n; i++)
+    if ((uint64_t)idx[i] >= (uint64_t)k.n) return fail(BLSGPU_E_ARG, "index outside the key set");
+  CTX_ACQUIRE_ON(c, k.devidx);
+  const size_t rec = WS_PAIRS_WORDS;
+  if ((rc = arena_reserve(c, pad256(rec * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096))) return rc;
+  c->arena_off = 0;
+  std::vector<uint32_t> h(rec * n);
+  for (size_t i = 0; i < n; i++)
+    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
+  const void *d_in, *d_st, *d_idx;
+  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
+  int32_t* d_status = (int32_t*)d_st;
+  if (mode == 1) {
+    KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)k.lines,
+       (const uint32_t*)d_idx, (uint32_t*)nullptr);
+    HIPCK(hipGetLastError());
+    return copy_out_and_sync(c, status, d_status, 4 * n);
+  }
+  uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
+  if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
+  KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)k.lines,
+     (const uint32_t*)d_idx, d_easy);
+  HIPCK(hipGetLastError());
+  std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
+  HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));
+  // the engine's value layout -> tower order, fourteen limbs each, as blsgpu_debug_coop_pairing
+  for (size_t i = 0; i < n; i++)
+    for (size_t kk = 0; kk < 6; kk++) {
+      const size_t pw = kk < 3 ? 2 * kk : 2 * (kk - 3) + 1;
+      for (size_t comp = 0; comp < 2; comp++)
+        for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * kk + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
+    }
+  SYNC_FLUSH(c);
+  return 0;
 }
 API_CATCH
 }  // extern "C"

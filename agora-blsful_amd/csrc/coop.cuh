@@ -533,6 +533,194 @@ __device__ __noinline__ void coop_miller2(coop_shared& S, const g1_aff* P, const
   coop_conj(S.f, S.f);
 }
 
+// ---- Miller loop of two pairs whose G2 members are BOTH given as normalised line tables (a registered key's rows, keyset.cuh, and
+// the constant's: the *_LINES_N layout, (n0.c0, n0.c1, c.c0, c.c1) per entry).  Nothing is walked and no lane pair owns a point:
+// entry e has the lines a = a0 + (c_a xP0) w^2 + yP0 w^3 and b = b0 + (c_b xP1) w^2 + yP1 w^3, whose product
+//     L = c0 + c2 w^2 + c3 w^3 + c4 w^4 + c5 w^5      c0 = a0 b0 + xi ya yb    c2 = (a0 + a2)(b0 + b2) - a0 b0 - a2 b2
+//                                                     c3 = a0 yb + b0 ya       c4 = a2 b2       c5 = a2 yb + b2 ya
+// (tower.cuh lines_merge_yy) multiplies f once.  The lines do not depend on f, so their work rides in rounds f pays for anyway:
+//   merge round    lane pairs 0..20 the squaring of f, 21..27 the seven merge products of THIS entry (ya, yb as Fp2 values with
+//                  a zero imaginary part: one product code for every lane pair); then lane pairs 0..5 reduce the square while
+//                  6..10 combine the five coefficients.  Lane pairs 30, 31 load the rows of the NEXT entry before that
+//                  reduction and stage them after it: the only memory reads of the loop, off the product rounds.
+//   multiply round lane pairs 0..29 the 6 x 5 products f_i L_j, 30 and 31 the scalings c_a xP0, c_b xP1 of the NEXT entry, which
+//                  they leave in the line slots together with a0 + a2, b0 + b2 (nobody reads those slots in this round).
+// Two product rounds per entry, doubling or addition (an addition entry's merge round carries no squaring); entry 0 sets f = L.
+// Slots, all inside the blocks coop_miller2 keeps for its point steps (coop_shared is unchanged):
+//   S.line[s][0..2]  a0, a2, a0 + a2 (s = 0) / b0, b2, b0 + b2 (s = 1) of the current entry     S.job[s][0][0..1]  n0, c of the next
+//   S.v.c[0..4]      ya, yb, xP0, xP1 (Fp2, imaginary part zero), xi ya yb                       S.res[m / 6][m % 6]  merge product m
+//   S.u.c[0..4]      c0, c2, c3, c4, c5
+// MODE 3 of the anti-diagonal reduction: the 30 products f_i L_j at prod[5 i + j], at most five like terms per diagonal.
+__device__ __forceinline__ void coop_reduce_line5(coop_shared& S, coop_f12& dst) {
+  const int k = coop_pair();
+  if (k < 6) {
+    const int jw[5] = {0, 2, 3, 4, 5};
+    hfp2 lo, hiacc, p;
+    fp2_zero(lo);
+    fp2_zero(hiacc);
+#pragma unroll
+    for (int c = 0; c < 5; c++) {
+      const int i = (k - jw[c] + 6) % 6;               // i + jw[c] = k or k + 6
+      coop_ld(p, S.prod[5 * i + c]);
+      if (i + jw[c] == k) fp2_add(lo, lo, p);
+      else fp2_add(hiacc, hiacc, p);
+    }
+    fp2_norm(hiacc, hiacc);                            // as coop_reduce: five staged products per half at the most
+    fp2_mul_xi(hiacc, hiacc);
+    fp2_norm(lo, lo);
+    fp2_add(lo, lo, hiacc);
+    fp2_reduce(lo, lo);
+    coop_st(dst.c[k], lo);
+  }
+  __syncthreads();
+}
+// the five coefficients of the merged line from the seven staged products (lane pairs 6..10; no barrier of its own)
+__device__ __forceinline__ void coop_tl_combine(coop_shared& S) {
+  const int j = coop_pair() - 6;
+  if (j >= 0 && j < 5) {
+    hfp2 x, y, r;
+    if (j == 0) {                                      // c0 = a0 b0 + xi ya yb
+      coop_ld(x, S.res[0][0]);
+      coop_ld(y, S.v.c[4]);
+      fp2_add(r, x, y);
+      fp2_reduce(r, r);
+    } else if (j == 1) {                               // c2 = (a0 + a2)(b0 + b2) - a0 b0 - a2 b2
+      coop_ld(r, S.res[0][2]);
+      coop_ld(x, S.res[0][0]);
+      coop_ld(y, S.res[0][1]);
+      fp2_sub(r, r, x);
+      fp2_sub(r, r, y);
+      fp2_reduce(r, r);
+    } else if (j == 3) {                               // c4 = a2 b2, a plain product
+      coop_ld(r, S.res[0][1]);
+    } else {                                           // c3 = a0 yb + b0 ya, c5 = a2 yb + b2 ya
+      coop_ld(x, j == 2 ? S.res[0][3] : S.res[0][5]);
+      coop_ld(y, j == 2 ? S.res[0][4] : S.res[1][0]);
+      fp2_add(r, x, y);
+      fp2_reduce(r, r);
+    }
+    coop_st(S.u.c[j], r);
+  }
+}
+// Merge round of one entry.  sqr: f <- f^2 rides along (doubling entries after the first).  next: this lane pair's row of the next
+// entry (lane pair 30: the key's, 31: the constant's), or null at the last entry.
+__device__ __forceinline__ void coop_tl_merge_round(coop_shared& S, bool sqr, const uint32_t* next) {
+  const int q = coop_pair();
+  const uint32_t *pa = nullptr, *pb = nullptr;
+  uint32_t* pd = nullptr;
+  if (q < 21) {
+    if (sqr) {
+      int i, j, w;
+      coop_sqr_idx(q, i, j, w);
+      pa = S.f.c[i];
+      pb = S.f.c[j];
+      pd = S.prod[q];
+    }
+  } else if (q < 28) {
+    const int m = q - 21;                              // a0 b0, a2 b2, (a0 + a2)(b0 + b2), a0 yb, b0 ya, a2 yb, b2 ya
+    pa = m == 0 || m == 3 ? S.line[0][0] : m == 1 || m == 5 ? S.line[0][1] : m == 2 ? S.line[0][2] : m == 4 ? S.line[1][0] : S.line[1][1];
+    pb = m == 0 ? S.line[1][0] : m == 1 ? S.line[1][1] : m == 2 ? S.line[1][2] : m == 3 || m == 5 ? S.v.c[1] : S.v.c[0];
+    pd = S.res[m / 6][m % 6];
+  }
+  if (pd) {
+    hfp2 x, y, p;
+    coop_ld(x, pa);
+    coop_ld(y, pb);
+    fp2_mul(p, x, y);
+    coop_st(pd, p);
+  }
+  __syncthreads();
+  hfp2 n0, c;
+  const bool stage = q >= 30 && next;
+  if (stage) {                                         // issued here, consumed after the reduction
+    fp2_load(n0, next);
+    fp2_load(c, next + 2 * FP_NL);
+  }
+  coop_tl_combine(S);
+  if (stage) {
+    coop_st(S.job[q - 30][0][0], n0);
+    coop_st(S.job[q - 30][0][1], c);
+  }
+  if (sqr) coop_reduce<1>(S, S.f);
+  else __syncthreads();
+}
+// Multiply round.  what 2: f *= L;  1: f = L (entry 0);  0: the round before the loop, which forms xi ya yb.  scale: lane pairs 30, 31
+// turn the staged rows of the next entry into its line slots.
+__device__ __forceinline__ void coop_tl_mul_round(coop_shared& S, int what, bool scale) {
+  const int q = coop_pair();
+  const uint32_t *pa = nullptr, *pb = nullptr;
+  uint32_t* pd = nullptr;
+  if (q < 30) {
+    if (what == 2) {
+      pa = S.f.c[q / 5];
+      pb = S.u.c[q % 5];
+      pd = S.prod[q];
+    } else if (what == 0 && q == 0) {
+      pa = S.v.c[0];
+      pb = S.v.c[1];
+      pd = S.v.c[4];
+    }
+  } else if (scale) {
+    pa = S.job[q - 30][0][1];
+    pb = S.v.c[2 + (q - 30)];
+    pd = S.line[q - 30][1];
+  }
+  if (pd) {
+    hfp2 x, y, p;
+    coop_ld(x, pa);
+    coop_ld(y, pb);
+    fp2_mul(p, x, y);
+    if (q >= 30) {                                     // a2 (b2), and beside it n0 and n0 + a2: the operands of the next merge round
+      coop_ld(x, S.job[q - 30][0][0]);
+      coop_st(S.line[q - 30][0], x);
+      fp2_add(y, x, p);
+      coop_st(S.line[q - 30][2], y);
+    } else if (what == 0) {                            // (ya yb, 0) -> xi ya yb
+      fp2_mul_xi(p, p);
+      fp2_reduce(p, p);
+    }
+    coop_st(pd, p);
+  }
+  __syncthreads();
+  if (what == 2) {
+    coop_reduce_line5(S, S.f);
+  } else if (what == 1) {
+    if (q < 6) {
+      const int j = q == 0 ? 0 : q - 1;                // w^k <- coefficient k of L; there is no w^1 term
+      hfp2 x;
+      if (q == 1) fp2_zero(x);
+      else coop_ld(x, S.u.c[j]);
+      coop_st(S.f.c[q], x);
+    }
+    __syncthreads();
+  }
+}
+// f ends as conj(f_{|x|,Q0}(P0) f_{|x|,Q1}(P1)) up to a factor in Fp2, as miller_loop_tables_merged (pairing.cuh) leaves it.
+// rows0: the 68 rows of pair 0's G2 member, 4 FP_NL words each; rows1: a constant's table (G2NEGC_LINES_N).
+__device__ __noinline__ void coop_miller2_tables(coop_shared& S, const g1_aff* P, const uint32_t* rows0, const uint32_t (*rows1)[4 * FP_NL]) {
+  const int me = coop_pair();
+  const uint32_t* rows = me == 31 ? &rows1[0][0] : rows0;       // read by lane pairs 30 and 31 only
+  if (me < 4) {
+    hfp2 k;
+    fp2_from_fp(k, me == 0 ? P[0].y : me == 1 ? P[1].y : me == 2 ? P[0].x : P[1].x);
+    coop_st(S.v.c[me], k);
+  } else if (me >= 30) {
+    hfp2 n0, c;
+    fp2_load(n0, rows);
+    fp2_load(c, rows + 2 * FP_NL);
+    coop_st(S.job[me - 30][0][0], n0);
+    coop_st(S.job[me - 30][0][1], c);
+  }
+  __syncthreads();
+  coop_tl_mul_round(S, 0, true);
+  for (int e = 0; e < MILLER_ENTRIES; e++) {
+    const bool last = e == MILLER_ENTRIES - 1;
+    coop_tl_merge_round(S, e != 0 && !miller_entry_is_add(e), last ? nullptr : rows + (e + 1) * (4 * FP_NL));
+    coop_tl_mul_round(S, e == 0 ? 1 : 2, !last);
+  }
+  coop_conj(S.f, S.f);
+}
+
 // easy part of the final exponentiation: S.f <- S.f^((p^6 - 1)(p^2 + 1))
 __device__ __noinline__ void coop_final_easy(coop_shared& S) {
   if (coop_pair() == 0) {

@@ -349,6 +349,10 @@ __global__ void k_wide_mul_test(size_t n, const uint8_t* a, const uint8_t* b, ui
 #define WIDE_ENGINE_BLOCK (16 * WIDE_TABLE_ROWS)   // threads of the engine kernels: one DPP row per product of a sub-round
 #define WIDE_EASY_WORDS (12 * 16)     // f^((p^6-1)(p^2+1)) of one item in the engine's value layout
 __global__ void k_pairing_coop_easy(size_t n, const uint32_t* pairs, const int32_t* status, int fixed_g2, uint32_t* easy);
+// ... and with pair 0's G2 member given as entry key_of[i] of a key set's line tables (keyset.cuh; Bls12381G1Impl, fixed_g2 = 2):
+// coop_miller2_tables, nothing is walked.  easy == nullptr: final exponentiation and verdict into status[i]; else the easy-part
+// value in k_pairing_coop_easy's layout and status stays as it is
+__global__ void k_pairing_coop_keyed(size_t n, const uint32_t* pairs, int32_t* status, const uint32_t* key_table, const uint32_t* key_of, uint32_t* easy);
 __global__ void k_finalexp_wide(size_t n, const uint32_t* easy, int32_t* status);
 __global__ void k_finalexp_wide_ws(const uint32_t* fws, size_t stride, int32_t* verdict);
 __global__ void k_f12_tree_wide(size_t m, const uint32_t* fin, size_t sin, uint32_t* fout, size_t sout);
@@ -3393,6 +3397,45 @@ __global__ void __launch_bounds__(BLS_BLOCK, 2) k_pairing_coop_easy(size_t n, co
     Q[k].inf = false;
   }
   coop_miller2(S, P, Q, fixed_g2);
+  coop_final_easy(S);
+  uint32_t* e = easy + i * WIDE_EASY_WORDS;
+  for (int t = threadIdx.x; t < WIDE_EASY_WORDS; t += BLS_BLOCK) {
+    const int v = t >> 4, l = t & 15;                  // value v = 2 k + component
+    e[t] = l < FP_NL ? S.f.c[v >> 1][(v & 1) * FP_NL + l] : 0u;
+  }
+}
+#endif
+
+#if defined(BLS_TU_COOP_KEYED)
+// =====================================================================================================
+#include "coop.cuh"
+// The one-wave pairing of an item whose key is a registered one with line tables (blsgpu_verify_indexed_batch and
+// blsgpu_verify_shared_indexed_batch between BLSGPU_WIDE_MAX and BLSGPU_COOP_MAX items): pair 0 is (H'(m), pk) with pk the set's
+// entry key_of[i], pair 1 (sig, -[c] g2) with the constant rows G2NEGC_LINES_N.  The record's Q members are not read.  The key
+// table's base is wave-uniform and the key's rows start at the 32-bit WORD offset key_of[i] 68 4 FP_NL, as in k_lines2s_keyed (the
+// host keeps the table below 2^32 bytes).  An item whose position names no usable entry never has status OK here, so its rows are
+// never read.  A translation unit of its own: the kernels of BLS_TU_COOP stay what they are.
+__global__ void __launch_bounds__(BLS_BLOCK, 2) k_pairing_coop_keyed(size_t n, const uint32_t* pairs, int32_t* status, const uint32_t* key_table,
+                                                                     const uint32_t* key_of, uint32_t* easy) {
+  __shared__ coop_shared S;
+  const size_t i = blockIdx.x;
+  if (i >= n) return;
+  if (status[i] != BLS_OK) return;                     // before any table read
+  g1_aff P[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const int w0 = k * 3 * W2;
+    ws_ld_fp(P[k].x, pairs, n, i, w0);
+    ws_ld_fp(P[k].y, pairs, n, i, w0 + W1);
+    P[k].inf = false;
+  }
+  const uint32_t koff = key_of[i] * (uint32_t)(MILLER_ENTRIES * 4 * FP_NL);
+  coop_miller2_tables(S, P, key_table + koff, G2NEGC_LINES_N);
+  if (!easy) {
+    int st = coop_final_verdict(S);
+    if (threadIdx.x == 0) status[i] = st;
+    return;
+  }
   coop_final_easy(S);
   uint32_t* e = easy + i * WIDE_EASY_WORDS;
   for (int t = threadIdx.x; t < WIDE_EASY_WORDS; t += BLS_BLOCK) {

@@ -325,6 +325,15 @@ int blsgpu_debug_millerf(const int32_t* lines, size_t n, const int32_t* status, 
  * Host pointers, n <= 4096. */
 #define BLSGPU_DEBUG_COOP_SENTINEL ((int32_t)0xa5a5a5a5)
 int blsgpu_debug_coop_pairing(int mode, int fixed_g2, const int32_t* pairs, size_t n, int32_t* status, int32_t* out_f12);
+/* Self-test hook of the one-wave pairing kernel that reads a registered key's line rows (not part of the reference interface):
+ * k_pairing_coop_keyed, launched as the verify path launches it.  pairs, status, out_f12 and the sentinel are those of
+ * blsgpu_debug_coop_pairing with fixed_g2 = 2, except that pair 0's G2 member is entry idx[i] of `keyset`, a set created with
+ * BLSGPU_KEYSET_LINES (Bls12381G1Impl): the record's own Q members are not read.  Every named entry must be a finite key with usable
+ * rows; the rows of other entries are not defined.
+ * mode 0: out_f12 gets the exported easy-part value per item, every limb of a skipped item is BLSGPU_DEBUG_COOP_SENTINEL, status is
+ *         left as it is.   mode 1: status becomes BLSGPU_OK or BLSGPU_ERR_INVALID_SIGNATURE; out_f12 is not used.
+ * BLSGPU_E_ARG: a set without line tables, an index that is not below the set's size, n > 4096, any other mode.  Host pointers. */
+int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* idx, const int32_t* pairs, size_t n, int32_t* status, int32_t* out_f12);
 
 /* Sign side, provided so that benchmarks and tests can build inputs on the device:
  * pk[i] = sk[i] * g (SecretKey::public_key, src/secret_key.rs:342-344) and
@@ -564,8 +573,10 @@ int blsgpu_sum_batch(int group, const void* pts, const uint64_t* offsets, size_t
  * reports 0.  Tables never change a result.
  * flags & BLSGPU_KEYSET_LINES (Bls12381G1Impl, keys in G2; accepted and without effect for sig_group 2, whose keys have no lines)
  * also derives every key's 68 normalised Miller-loop rows (15,232 bytes per key; the reference's G2Prepared::from(pk), kept instead
- * of recomputed per call): blsgpu_verify_indexed_batch and blsgpu_verify_shared_indexed_batch on the lane-split path (more than
- * BLSGPU_COOP_MAX items) then read rows where they walked the key, under every scheme, and so do the batched sets of
+ * of recomputed per call): blsgpu_verify_indexed_batch and blsgpu_verify_shared_indexed_batch above BLSGPU_WIDE_MAX items -- the
+ * one-wave path up to BLSGPU_COOP_MAX items (k_pairing_coop_keyed) and the lane-split path beyond (k_lines2s_keyed) -- then read
+ * rows where they walked the key, under every scheme; calls of at most BLSGPU_WIDE_MAX items run on the row-wide engine, which
+ * derives the key's lines beside the hash and does not read the rows.  So do the batched sets of
  * blsgpu_aggregate_verify_indexed_batch (whatever their number), whose signature items read the constant rows of -[c] g2 as
  * well.  The lines are not built, and the set works
  * without them, when they would not stay below 2^32 bytes (more than 281,970 keys), when together with the fixed-base tables they

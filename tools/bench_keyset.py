@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Registered key sets against keys by value: what the index-addressed entry points and the fixed-base tables cost and save.
 
-usage: python tools/bench_keyset.py [--lines | --agg | --update] [--reps 5] [--table 16384] [--shapes 0,1,..] [--out profiles/keyset_bench.json]
+usage: python tools/bench_keyset.py [--lines | --coop | --agg | --update] [--reps 5] [--table 16384] [--shapes 0,1,..] [--out profiles/keyset_bench.json]
 Every input lives on the device (TensorOps).  Per shape, indices are drawn at random from a table of --table keys k * g
 (blsgpu_sign_batch) and four things are timed, each the median of --reps calls:
   (a) the non-indexed entry point on the same keys laid out contiguously (three repeats of the whole measurement: their range is the
@@ -18,6 +18,11 @@ blsgpu_verify_shared_batch / blsgpu_verify_shared_indexed_batch at 64 x 1,024 an
 set without lines, (c) indexed over a set with lines; EVERY cell three medians of --reps calls (their range is the cell's spread),
 the line kernel's time per call from the profile, and blsgpu_keyset_create with and without the flag.  A library that refuses the
 flag (the parent commit) runs (a) and (b) only.
+
+--coop [--out profiles/keyset_lines_coop_bench.json]: the same cells on the one-wave-per-item pairing path (BLSGPU_WIDE_MAX < items <=
+BLSGPU_COOP_MAX), where a set with lines runs k_pairing_coop_keyed in the place of k_pairing_coop: blsgpu_verify_indexed_batch at 513,
+1,024, 2,048 and 4,096 items, 4,097 (the first lane-split size) beside them, and blsgpu_verify_shared_indexed_batch at 8 x 256.  On
+the parent commit (c) walks the keys as (b) does: its (a) and (b) are the yardstick.
 
 --agg [--out profiles/keyset_agg_bench.json]: the batched aggregate verify (many keys with one message each per set), Basic with
 distinct messages: (a) blsgpu_aggregate_verify_batch by value, (b) blsgpu_aggregate_verify_indexed_batch over a set without lines,
@@ -61,9 +66,10 @@ def median_ms(run, reps, sync):
 
 
 LINES_SHAPES = [('verify', 8192, 1), ('verify', 65536, 1), ('verify', 262144, 1), ('shared', 64, 1024), ('shared', 400, 400)]
+COOP_SHAPES = [('verify', 513, 1), ('verify', 1024, 1), ('verify', 2048, 1), ('verify', 4096, 1), ('verify', 4097, 1), ('shared', 8, 256)]
 
 
-def lines_bench(a, api, ops, torch, dev, sync):
+def lines_bench(a, api, ops, torch, dev, sync, all_shapes=LINES_SHAPES):
     rng = random.Random(2027)
     ks = [rng.randrange(1, R) for _ in range(a.table)]
     pks = api.sign_batch(1, api.BASIC, ks, [b''] * a.table)[0]
@@ -87,7 +93,7 @@ def lines_bench(a, api, ops, torch, dev, sync):
         create['with lines' if lines else 'without lines'] = dict(ms=round(statistics.median(ts), 3), first_ms=round(ts[0], 3), **made[lines].info())
     rows = [{'table_entries': a.table, 'create': create}]
     print(json.dumps(rows[0]), flush=True)
-    shapes = [LINES_SHAPES[int(i)] for i in a.shapes.split(',')] if a.shapes else LINES_SHAPES
+    shapes = [all_shapes[int(i)] for i in a.shapes.split(',')] if a.shapes else all_shapes
     for kind, n_groups, per in shapes:
         n = n_groups * per
         gen = torch.Generator(device=dev).manual_seed(n + n_groups)
@@ -263,6 +269,7 @@ def update_bench(a, api, ops, torch, dev, sync):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--lines', action='store_true')
+    ap.add_argument('--coop', action='store_true')
     ap.add_argument('--update', action='store_true')
     ap.add_argument('--agg', action='store_true')
     ap.add_argument('--reps', type=int, default=5)
@@ -284,6 +291,10 @@ def main():
         if a.out.endswith('keyset_bench.json'):
             a.out = os.path.join(ROOT, 'profiles', 'keyset_agg_bench.json')
         return agg_bench(a, api, ops, torch, dev, sync)
+    if a.coop:
+        if a.out.endswith('keyset_bench.json'):
+            a.out = os.path.join(ROOT, 'profiles', 'keyset_lines_coop_bench.json')
+        return lines_bench(a, api, ops, torch, dev, sync, COOP_SHAPES)
     if a.lines:
         if a.out.endswith('keyset_bench.json'):
             a.out = os.path.join(ROOT, 'profiles', 'keyset_lines_bench.json')
