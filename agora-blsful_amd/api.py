@@ -26,6 +26,8 @@ MODERN, LEGACY = 0, 1
 
 OK, INVALID_SIGNATURE, SIG_IDENTITY, PK_IDENTITY, DUPLICATE_MESSAGE, INVALID_COEFFICIENT, BAD_LENGTH, BAD_ENCODING, \
     LEGACY_FORMAT = range(9)
+E_ARG = -3                                                          # in a status slot: blsgpu_sig_proof_timestamp_verify_batch only
+KEYGEN_SALT = b'BLS-SIG-KEYGEN-SALT-'                               # reference src/helpers.rs:7
 COMMITMENT_IDENTITY, PROOF_IDENTITY, ZERO_CHALLENGE = 9, 10, 11    # blsgpu_sig_proof_verify_batch only
 INVALID_SCHEME, VSSS_ERROR = 12, 13                                  # blsgpu_combine_shares only
 INVALID_DECRYPTION_SHARE, BAD_FRAME = 14, 15                        # the threshold signcryption calls only
@@ -50,6 +52,7 @@ EXPORTS = [
     'blsgpu_elgamal_message_generator', 'blsgpu_elgamal_proof_verify_batch', 'blsgpu_elgamal_open_batch',
     'blsgpu_verify_shared_batch', 'blsgpu_verify_shared_indexed_batch',
     'blsgpu_aggregate_verify_indexed_batch',
+    'blsgpu_hash_to_scalar', 'blsgpu_sig_proof_challenge_batch', 'blsgpu_sig_proof_timestamp_verify_batch',
 ]
 
 
@@ -196,6 +199,9 @@ def load_library(path=None):
         lib.blsgpu_verify_shared_indexed_batch.argtypes = [ci, h, u32p, vp, u64p, sz, u8p, u64p, ci, i32p]
         lib.blsgpu_aggregate_verify_indexed_batch.argtypes = [ci, h, u32p, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
         lib.blsgpu_debug_coop_pairing_keyed.argtypes = [ci, h, u32p, i32p, sz, i32p, i32p]
+        lib.blsgpu_hash_to_scalar.argtypes = [u8p, u64p, sz, u8p, sz, u8p]
+        lib.blsgpu_sig_proof_challenge_batch.argtypes = [ci, vp, u64p, sz, ci, u8p]
+        lib.blsgpu_sig_proof_timestamp_verify_batch.argtypes = [ci, ci, vp, vp, vp, u64p, u8p, u64p, sz, ci, ctypes.c_uint64, ctypes.c_int64, i32p]
         _lib = lib
     return _lib
 
@@ -598,12 +604,56 @@ def elgamal_sum_batch(sig_group, sets, fmt=FMT_RAW_PROJ):
 
 
 def proof_error_from_status(st):
-    """Status of blsgpu_sig_proof_verify_batch -> the BlsError of BlsSignatureProof::verify (src/traits/sig_proof.rs:110-140)."""
+    """Status of blsgpu_sig_proof_verify_batch / blsgpu_sig_proof_timestamp_verify_batch -> the BlsError of BlsSignatureProof::verify
+    (src/traits/sig_proof.rs:110-140).  The E_ARG slot value of the timestamp call (a timestamp in the future beside a timeout: the
+    reference panics there) is a BlsGpuRuntimeError, not a BlsError; a wire point that did not decode maps as error_from_status does."""
+    if st == E_ARG:
+        return BlsGpuRuntimeError('proof timestamp lies after now_ms (the reference panics: duration_since(..).unwrap(), sig_proof.rs:157)')
+    if st in (BAD_LENGTH, BAD_ENCODING, LEGACY_FORMAT):
+        return error_from_status(st)
     return {OK: None, INVALID_SIGNATURE: BlsError('InvalidProof'),
             COMMITMENT_IDENTITY: BlsError('InvalidInputs', 'commitment is the identity point'),
             PROOF_IDENTITY: BlsError('InvalidInputs', 'proof is the identity point'),
             PK_IDENTITY: BlsError('InvalidInputs', 'pk is the identity point'),
             ZERO_CHALLENGE: BlsError('InvalidInputs', 'y is the zero')}.get(st, BlsError('Unknown', str(st)))
+
+
+def hash_to_scalar(msgs, salt):
+    """[HashToScalar::hash_to_scalar(m, salt)] as ints (reference src/helpers.rs:9-26), one blsgpu_hash_to_scalar call."""
+    lib = init()
+    n = len(msgs)
+    offs, blob = _offsets(msgs)
+    out = ctypes.create_string_buffer(32 * max(n, 1))
+    _check(lib.blsgpu_hash_to_scalar(_ptr(blob), ctypes.cast(offs, ctypes.c_void_p), n, _ptr(bytes(salt)), len(salt), ctypes.cast(out, ctypes.c_void_p)))
+    return [int.from_bytes(out.raw[32 * i:32 * i + 32], 'little') for i in range(n)]
+
+
+def _u64s(xs):
+    return (ctypes.c_uint64 * max(len(xs), 1))(*xs)
+
+
+def sig_proof_challenge_batch(sig_group, commitments, timestamps, fmt=FMT_RAW_PROJ):
+    """[BlsSignatureProof::compute_y(u, t)] as ints (reference src/traits/sig_proof.rs:38-46)."""
+    lib = init()
+    n = len(commitments)
+    out = ctypes.create_string_buffer(32 * max(n, 1))
+    _check(lib.blsgpu_sig_proof_challenge_batch(sig_group, _ptr(b''.join(commitments)), ctypes.cast(_u64s(timestamps), ctypes.c_void_p), n, fmt,
+                                                ctypes.cast(out, ctypes.c_void_p)))
+    return [int.from_bytes(out.raw[32 * i:32 * i + 32], 'little') for i in range(n)]
+
+
+def sig_proof_timestamp_verify_batch(sig_group, scheme, commitments, proofs, pks, timestamps, msgs, now_ms, timeout_ms=None, fmt=FMT_RAW_PROJ):
+    """status list of ProofOfKnowledgeTimestamp::verify(pk, msg, timeout_ms) for n proofs (u, v, t), the challenges derived on the
+    device; timeout_ms None: no timeout.  now_ms is the caller's clock in milliseconds."""
+    lib = init()
+    n = len(msgs)
+    offs, blob = _offsets(msgs)
+    st = (ctypes.c_int32 * max(n, 1))()
+    ub, vb, pkb = b''.join(commitments), b''.join(proofs), b''.join(pks)
+    _check(lib.blsgpu_sig_proof_timestamp_verify_batch(sig_group, scheme, _ptr(ub), _ptr(vb), _ptr(pkb), ctypes.cast(_u64s(timestamps), ctypes.c_void_p),
+                                                       _ptr(blob), ctypes.cast(offs, ctypes.c_void_p), n, fmt, now_ms,
+                                                       -1 if timeout_ms is None else timeout_ms, ctypes.cast(st, ctypes.c_void_p)))
+    return list(st)[:n]
 
 
 def sig_proof_verify_batch(sig_group, scheme, commitments, proofs, pks, ys, msgs, fmt=FMT_RAW_PROJ):
@@ -1271,6 +1321,27 @@ class TensorOps:
         st = self.empty(max(n, 1), self.torch.int32)
         _check(self.lib.blsgpu_sig_proof_verify_batch(sg, scheme, self._p(us), self._p(vs), self._p(pks), self._p(ys), self._p(msgs), self._p(offs), n,
                                                       FMT_RAW_PROJ, self._p(st)))
+        return st[:n]
+
+    def hash_to_scalar(self, msgs, offs, n, salt, salt_len):
+        """n x 32 bytes, little-endian canonical; salt: a uint8 tensor (or None with salt_len 0)"""
+        self._sync()
+        out = self.empty(32 * max(n, 1))
+        _check(self.lib.blsgpu_hash_to_scalar(self._p(msgs), self._p(offs), n, self._p(salt), salt_len, self._p(out)))
+        return out[:32 * n]
+
+    def sig_proof_challenge_batch(self, sg, us, ts, n, fmt=FMT_RAW_PROJ):
+        """ts: int64 tensor holding the u64 timestamps' bits"""
+        self._sync()
+        out = self.empty(32 * max(n, 1))
+        _check(self.lib.blsgpu_sig_proof_challenge_batch(sg, self._p(us), self._p(ts), n, fmt, self._p(out)))
+        return out[:32 * n]
+
+    def sig_proof_timestamp_verify_batch(self, sg, scheme, us, vs, pks, ts, msgs, offs, n, now_ms, timeout_ms=None, fmt=FMT_RAW_PROJ):
+        self._sync()
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_sig_proof_timestamp_verify_batch(sg, scheme, self._p(us), self._p(vs), self._p(pks), self._p(ts), self._p(msgs), self._p(offs), n,
+                                                                fmt, now_ms, -1 if timeout_ms is None else timeout_ms, self._p(st)))
         return st[:n]
 
     def signcrypt_valid_batch(self, sg, scheme, us, ws, vs, offs, n):
@@ -2025,3 +2096,65 @@ def elgamal_verify_many(items):
     st = elgamal_proof_verify_batch(sg, [pk.raw for _, pk in items], None, [pr.ciphertext.c1 for pr, _ in items], [pr.ciphertext.c2 for pr, _ in items],
                                     [pr.message_proof for pr, _ in items], [pr.blinder_proof for pr, _ in items], [pr.challenge for pr, _ in items])
     return [elgamal_error_from_status(x) for x in st]
+
+
+class ProofCommitmentChallenge:
+    """ProofCommitmentChallenge<C>: reference src/proof_commitment.rs; the scalar is an int."""
+
+    def __init__(self, impl, value):
+        self.impl, self.value = impl, int(value)
+
+    @staticmethod
+    def from_hash(impl, data):
+        """reference src/proof_commitment.rs:256-261: hash_to_scalar(data, KEYGEN_SALT), on the GPU."""
+        return ProofCommitmentChallenge(impl, hash_to_scalar([bytes(data)], KEYGEN_SALT)[0])
+
+    def to_le_bytes(self):
+        return self.value.to_bytes(32, 'little')
+
+    def to_be_bytes(self):
+        return self.value.to_bytes(32, 'big')
+
+
+class ProofOfKnowledge:
+    """ProofOfKnowledge<C> {u, v}: reference src/proof_of_knowledge.rs:9-20; both in the signature group, RAW_PROJ."""
+
+    def __init__(self, impl, scheme, u, v):
+        self.impl, self.scheme, self.u, self.v = impl, scheme, bytes(u), bytes(v)
+
+    def verify(self, pk, msg, y):
+        """reference src/proof_of_knowledge.rs:132-164; y: a ProofCommitmentChallenge or an int.  Raises BlsError, returns None on Ok(())."""
+        y = y.value if isinstance(y, ProofCommitmentChallenge) else int(y)
+        e = proof_error_from_status(sig_proof_verify_batch(self.impl.sig_group, self.scheme, [self.u], [self.v], [pk.raw], [y], [bytes(msg)])[0])
+        if e:
+            raise e
+
+
+class ProofOfKnowledgeTimestamp:
+    """ProofOfKnowledgeTimestamp<C> {u, v, t}: reference src/proof_of_knowledge.rs:166-180; t in milliseconds."""
+
+    def __init__(self, impl, scheme, u, v, t):
+        self.impl, self.scheme, self.u, self.v, self.t = impl, scheme, bytes(u), bytes(v), int(t)
+
+    def verify(self, pk, msg, timeout_ms=None, now_ms=None):
+        """reference src/proof_of_knowledge.rs:287-326.  now_ms None: this host's clock (the library itself reads none)."""
+        e = proof_timestamp_verify_many([(self, pk, msg)], now_ms, timeout_ms)[0]
+        if e:
+            raise e
+
+
+def proof_timestamp_verify_many(items, now_ms=None, timeout_ms=None):
+    """ProofOfKnowledgeTimestamp.verify over many items at once: `items` is a list of (proof, PublicKey, msg) that share one impl
+    and scheme; one blsgpu_sig_proof_timestamp_verify_batch call.  Returns None (Ok), the BlsError, or the BlsGpuRuntimeError of a
+    timestamp in the future, per item, in order."""
+    if not items:
+        return []
+    if now_ms is None:
+        import time
+        now_ms = int(time.time() * 1000)
+    sg, scheme = items[0][0].impl.sig_group, items[0][0].scheme
+    if any(pr.impl.sig_group != sg or pk.impl.sig_group != sg or pr.scheme != scheme for pr, pk, _ in items):
+        raise ValueError('proof_timestamp_verify_many: every item must use the same impl and scheme')
+    st = sig_proof_timestamp_verify_batch(sg, scheme, [pr.u for pr, _, _ in items], [pr.v for pr, _, _ in items], [pk.raw for _, pk, _ in items],
+                                          [pr.t for pr, _, _ in items], [bytes(m) for _, _, m in items], now_ms, timeout_ms)
+    return [proof_error_from_status(x) for x in st]

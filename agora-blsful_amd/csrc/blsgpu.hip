@@ -25,6 +25,7 @@
 #include "signcrypt.cuh"
 #include "elgamal.cuh"
 #include "verify_shared.cuh"
+#include "hkdf.cuh"
 #include "debug_ops.h"
 #include "host_sha256.h"
 
@@ -55,6 +56,7 @@ enum {
   KID_LINESP_KEYED,                      // ... and the one of the batched aggregate verify over such a set (in the place of k_linesp)
   KID_KEYSET_SEAL_AT, KID_KEYSET_BUILD_AT, KID_KEYSET_LINES_AT,   // blsgpu_keyset_update / blsgpu_keyset_append: the positional forms of seal, build, lines
   KID_PAIRING_COOP_KEYED,                // the one-wave pairing that reads a registered key's rows (in the place of k_pairing_coop)
+  KID_HASH_TO_SCALAR, KID_PROOF_CHALLENGE, KID_PROOF_TIMEOUT,   // blsgpu_hash_to_scalar, blsgpu_sig_proof_challenge_batch / _timestamp_verify_batch (hkdf.cuh)
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -74,7 +76,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_keyset_lines", "k_lines2s_keyed",
                                     "k_linesp_keyed",
                                     "k_keyset_seal_at", "k_keyset_build_at", "k_keyset_lines_at",
-                                    "k_pairing_coop_keyed"};
+                                    "k_pairing_coop_keyed",
+                                    "k_hash_to_scalar", "k_proof_challenge", "k_proof_timeout"};
 
 struct Ctx {
   int dev = -1;
@@ -434,7 +437,8 @@ int copy_out_and_sync(Ctx* c, void* dst, const void* dsrc, size_t bytes) {
 }
 
 // the statuses of a call on their way to the caller.  A device-side hand-over that ran out of its bounded wait (kernels.cuh
-// BLS_ERR_STREAM_TIMEOUT, the one negative value a kernel ever writes into a status) is a failure of the CALL, not a verdict:
+// BLS_ERR_STREAM_TIMEOUT; the only other negative value a kernel writes into a status is k_proof_timeout's BLSGPU_E_ARG, which IS
+// the item's verdict) is a failure of the CALL, not a verdict:
 // wherever the host gets to see the statuses it says so with the return code; a caller that keeps them on the device finds the
 // -2 in the item's entry (include/blsgpu.h).
 int status_out_and_sync(Ctx* c, int32_t* status, const int32_t* d_status, size_t n) {
@@ -3804,6 +3808,97 @@ int blsgpu_signcrypt_valid_batch(int sig_group, int scheme, const void* us, cons
 }
 API_CATCH
 
+// The proof-of-knowledge check of n items, shared by blsgpu_sig_proof_verify_batch (ys given, raw formats) and
+// blsgpu_sig_proof_timestamp_verify_batch (stamped: the challenges are carved from the arena and derived on the device from
+// (commitment, timestamp); all four point formats; the timeout rule on top).  Launch sequence of the timestamp form:
+// k_decompress x 3 (wire formats only), k_proof_challenge, k_prepare_proof, k_proof_timeout, run_pairing2.
+int sig_proof_entry(bool stamped, int sig_group, int scheme, const void* commitments, const void* proofs, const void* pks, const uint8_t* ys,
+                    const uint64_t* timestamps, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, int fmt, uint64_t now_ms,
+                    int64_t timeout_ms, int32_t* status) {
+  const bool wire = stamped && (fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY);
+  int rc = check_common(sig_group, scheme, wire ? BLSGPU_FMT_RAW_PROJ : fmt);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!commitments || !proofs || !pks || (stamped ? !timestamps : !ys) || !msg_offsets || !status) return fail(BLSGPU_E_ARG, "null argument");
+  CTX_ACQUIRE(c);
+  uint64_t total = 0;
+  if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + n, 8, hipMemcpyDeviceToHost));
+  else total = msg_offsets[n];
+  // a batch whose every item trips the timeout rule needs no hash and no pairing: the host reads the timestamps to know
+  bool all_late = false;
+  if (stamped && timeout_ms >= 0) {
+    std::vector<uint64_t> ts(n);
+    if (is_device_ptr(timestamps)) HIPCK(hipMemcpy(ts.data(), timestamps, 8 * n, hipMemcpyDeviceToHost));
+    else memcpy(ts.data(), timestamps, 8 * n);
+    all_late = true;
+    for (size_t i = 0; i < n && all_late; i++) all_late = pok_timeout_status(ts[i], now_ms, timeout_ms) != 0;
+  }
+  const size_t pkb = pk_size(sig_group, fmt) * n, sgb = sig_size(sig_group, fmt) * n;
+  const size_t pk_raw = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n, sig_raw = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n;
+  size_t need = pad256(pkb) + 2 * pad256(sgb) + pad256(32 * n) + pad256(total) + pad256(8 * (n + 1)) + pad256(4 * n) +
+                2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 4096;
+  if (stamped) need += pad256(8 * n) + (wire ? pad256(pk_raw) + 2 * pad256(sig_raw) + pad256(4 * n) : 0);
+  if ((rc = arena_reserve(c, need))) return rc;
+  c->arena_off = 0;
+  const void *d_u, *d_v, *d_pks, *d_ys = nullptr, *d_ts = nullptr, *d_msgs, *d_offs;
+  if (stamped && (rc = stage_in(c, timestamps, 8 * n, &d_ts))) return rc;
+  if (all_late) {
+    int32_t* d_status = (int32_t*)arena_take(c, 4 * n);
+    if (!d_status) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    KL(KID_PROOF_TIMEOUT, k_proof_timeout, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint64_t*)d_ts, now_ms, timeout_ms, (const int32_t*)nullptr, d_status);
+    HIPCK(hipGetLastError());
+    return status_out_and_sync(c, status, d_status, n);
+  }
+  if ((rc = stage_in(c, commitments, sgb, &d_u))) return rc;
+  if ((rc = stage_in(c, proofs, sgb, &d_v))) return rc;
+  if ((rc = stage_in(c, pks, pkb, &d_pks))) return rc;
+  if (!stamped && (rc = stage_in(c, ys, 32 * n, &d_ys))) return rc;
+  if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
+  if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
+  Carver mem{c};
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  uint8_t* d_y = stamped ? mem.take<uint8_t>(32 * n) : nullptr;
+  int32_t* d_dec = wire ? mem.take<int32_t>(4 * n) : nullptr;
+  uint8_t* d_u_raw = wire ? mem.take<uint8_t>(sig_raw) : nullptr;
+  uint8_t* d_v_raw = wire ? mem.take<uint8_t>(sig_raw) : nullptr;
+  uint8_t* d_pk_raw = wire ? mem.take<uint8_t>(pk_raw) : nullptr;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  int kfmt = fmt;
+  if (wire) {
+    // ProofOfKnowledgeTimestamp's points from their wire bytes, checked (subgroup test included): the first failure of
+    // commitment, proof, key is the item's decode status; a point that was not decoded stays the identity
+    const int legacy = fmt == BLSGPU_FMT_LEGACY;
+    HIPCK(hipMemsetAsync(d_v_raw, 0, sig_raw, c->stream));
+    HIPCK(hipMemsetAsync(d_pk_raw, 0, pk_raw, c->stream));
+    with_group(sig_group, [&](auto G) {
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, legacy, d_u_raw, d_dec, 0);
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_v, legacy, d_v_raw, d_dec, 1);
+      KL(KID_DECOMPRESS, k_decompress<3 - G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, legacy, d_pk_raw, d_dec, 1);
+    });
+    d_u = d_u_raw;
+    d_v = d_v_raw;
+    d_pks = d_pk_raw;
+    kfmt = BLSGPU_FMT_RAW_PROJ;
+  }
+  if (stamped) {
+    with_group(sig_group, [&](auto G) {
+      KL(KID_PROOF_CHALLENGE, k_proof_challenge<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, kfmt, (const uint64_t*)d_ts, (const int32_t*)d_dec, d_y);
+    });
+    d_ys = d_y;
+  }
+  const dst_arg dst = scheme_dst(sig_group, scheme);
+  with_group(sig_group, [&](auto G) {
+    KL(KID_PREPARE, k_prepare_proof<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, (const uint8_t*)d_v, (const uint8_t*)d_pks,
+       (const uint8_t*)d_ys, kfmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, dst, d_pairs, d_status);
+  });
+  if (stamped && (timeout_ms >= 0 || d_dec))
+    KL(KID_PROOF_TIMEOUT, k_proof_timeout, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint64_t*)d_ts, now_ms, timeout_ms, (const int32_t*)d_dec, d_status);
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0))) return rc;
+  if ((rc = status_out_and_sync(c, status, d_status, n))) return rc;
+  return 0;
+}
 /* ProofOfKnowledge::verify for n proofs (reference src/proof_of_knowledge.rs:132-164 -> BlsSignatureProof::verify,
  * src/traits/sig_proof.rs:102-142; verify_timestamp_proof :145-175 derives y and calls the same check): status[i] in
  * {OK, COMMITMENT_IDENTITY, PROOF_IDENTITY, PK_IDENTITY, ZERO_CHALLENGE, INVALID_SIGNATURE (= BlsError::InvalidProof)}.
@@ -3812,38 +3907,90 @@ API_CATCH
 int blsgpu_sig_proof_verify_batch(int sig_group, int scheme, const void* commitments, const void* proofs, const void* pks,
                                   const uint8_t* ys, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, int fmt,
                                   int32_t* status) try {
-  int rc = check_common(sig_group, scheme, fmt);
+  return sig_proof_entry(false, sig_group, scheme, commitments, proofs, pks, ys, nullptr, msgs, msg_offsets, n, fmt, 0, -1, status);
+}
+API_CATCH
+
+/* ProofOfKnowledgeTimestamp::verify(pk, msg, timeout_ms) for n proofs (reference src/proof_of_knowledge.rs:287-326 ->
+ * verify_timestamp_proof, src/traits/sig_proof.rs:145-166): the timeout rule first (:154-161; the library reads no clock, now_ms
+ * is the caller's; timeout_ms < 0 is None), then y = compute_y(u, t) on the device (:163, k_proof_challenge) and the check of
+ * blsgpu_sig_proof_verify_batch (:165).  With a timeout, t > now_ms puts BLSGPU_E_ARG into the item's slot (the reference panics). */
+int blsgpu_sig_proof_timestamp_verify_batch(int sig_group, int scheme, const void* commitments, const void* proofs, const void* pks,
+                                            const uint64_t* timestamps, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n,
+                                            int fmt, uint64_t now_ms, int64_t timeout_ms, int32_t* status) try {
+  return sig_proof_entry(true, sig_group, scheme, commitments, proofs, pks, nullptr, timestamps, msgs, msg_offsets, n, fmt, now_ms, timeout_ms, status);
+}
+API_CATCH
+
+/* BlsSignatureProof::compute_y(u, t) for n commitments (reference src/traits/sig_proof.rs:38-46): HashToScalar over the modern
+ * compressed commitment and LE64(t) under the proof salt, whatever format the point came in.  out_ys: n x 32 B little-endian
+ * canonical.  A wire-format commitment that does not decode gets y = 0. */
+int blsgpu_sig_proof_challenge_batch(int sig_group, const void* commitments, const uint64_t* timestamps, size_t n, int fmt, uint8_t* out_ys) try {
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  int rc = check_common(sig_group, 0, wire ? BLSGPU_FMT_RAW_PROJ : fmt);
   if (rc) return rc;
   if (n == 0) return 0;
-  if (!commitments || !proofs || !pks || !ys || !msg_offsets || !status) return fail(BLSGPU_E_ARG, "null argument");
+  if (!commitments || !timestamps || !out_ys) return fail(BLSGPU_E_ARG, "null argument");
   CTX_ACQUIRE(c);
-  uint64_t total = 0;
-  if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + n, 8, hipMemcpyDeviceToHost));
-  else total = msg_offsets[n];
-  const size_t pkb = pk_size(sig_group, fmt) * n, sgb = sig_size(sig_group, fmt) * n;
-  size_t need = pad256(pkb) + 2 * pad256(sgb) + pad256(32 * n) + pad256(total) + pad256(8 * (n + 1)) + pad256(4 * n) +
-                2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 4096;
-  if ((rc = arena_reserve(c, need))) return rc;
+  const size_t sgb = sig_size(sig_group, fmt) * n, sig_raw = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n;
+  if ((rc = arena_reserve(c, pad256(sgb) + pad256(8 * n) + pad256(32 * n) + (wire ? pad256(sig_raw) + pad256(4 * n) : 0) + 4096))) return rc;
   c->arena_off = 0;
-  const void *d_u, *d_v, *d_pks, *d_ys, *d_msgs, *d_offs;
+  const void *d_u, *d_ts;
   if ((rc = stage_in(c, commitments, sgb, &d_u))) return rc;
-  if ((rc = stage_in(c, proofs, sgb, &d_v))) return rc;
-  if ((rc = stage_in(c, pks, pkb, &d_pks))) return rc;
-  if ((rc = stage_in(c, ys, 32 * n, &d_ys))) return rc;
+  if ((rc = stage_in(c, timestamps, 8 * n, &d_ts))) return rc;
+  Carver mem{c};
+  uint8_t* d_y = mem.stage_out<uint8_t>(out_ys, 32 * n);
+  int32_t* d_dec = wire ? mem.take<int32_t>(4 * n) : nullptr;
+  uint8_t* d_u_raw = wire ? mem.take<uint8_t>(sig_raw) : nullptr;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  int kfmt = fmt;
+  if (wire) {
+    with_group(sig_group, [&](auto G) {
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, (int)(fmt == BLSGPU_FMT_LEGACY), d_u_raw, d_dec, 0);
+    });
+    d_u = d_u_raw;
+    kfmt = BLSGPU_FMT_RAW_PROJ;
+  }
+  with_group(sig_group, [&](auto G) {
+    KL(KID_PROOF_CHALLENGE, k_proof_challenge<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, kfmt, (const uint64_t*)d_ts, (const int32_t*)d_dec, d_y);
+  });
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out_ys, d_y, 32 * n))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* HashToScalar::hash_to_scalar(m, salt) for n inputs (reference src/impls/g1.rs:25-27, g2.rs:23-25 -> scalar_from_hkdf_bytes,
+ * src/helpers.rs:9-26; ProofCommitmentChallenge::from_hash and SecretKey::from_hash with KEYGEN_SALT, proof_commitment.rs:256-261,
+ * secret_key.rs:276-281).  out: n x 32 B little-endian canonical; a zero result is written as zero (hkdf.cuh).  Not constant
+ * time: public inputs only. */
+int blsgpu_hash_to_scalar(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, const uint8_t* salt, size_t salt_len, uint8_t* out) try {
+  if (!initialised()) return NOT_INIT();
+  if (n == 0) return 0;
+  if (!msg_offsets || !out || (!salt && salt_len)) return fail(BLSGPU_E_ARG, "null argument");
+  if (salt_len >> 32) return fail(BLSGPU_E_ARG, "salt longer than 2^32 - 1 bytes");
+  CTX_ACQUIRE(c);
+  std::vector<uint64_t> offs;
+  int rc = read_offsets(msg_offsets, n, "msg_offsets", offs);
+  if (rc) return rc;
+  const uint64_t total = offs[n];
+  if (!msgs && total) return fail(BLSGPU_E_ARG, "null argument");
+  for (size_t i = 0; i < n; i++)
+    if ((offs[i + 1] - offs[i]) >> 29) return fail(BLSGPU_E_ARG, "message of 512 MiB or more");
+  if ((rc = arena_reserve(c, pad256(total) + pad256(8 * (n + 1)) + pad256(salt_len) + pad256(32 * n) + 4096))) return rc;
+  c->arena_off = 0;
+  const void *d_msgs, *d_offs, *d_salt;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
-  Carver mem{c};
-  int32_t* d_status = mem.take<int32_t>(4 * n);
-  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  const dst_arg dst = scheme_dst(sig_group, scheme);
-  with_group(sig_group, [&](auto G) {
-    KL(KID_PREPARE, k_prepare_proof<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_u, (const uint8_t*)d_v, (const uint8_t*)d_pks,
-       (const uint8_t*)d_ys, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, dst, d_pairs, d_status);
-  });
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0))) return rc;
-  if ((rc = status_out_and_sync(c, status, d_status, n))) return rc;
+  if ((rc = stage_in(c, salt, salt_len, &d_salt))) return rc;
+  uint8_t* d_out = stage_out<uint8_t>(c, out, 32 * n);
+  if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  KL(KID_HASH_TO_SCALAR, k_hash_to_scalar, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, (const uint8_t*)d_salt,
+     (uint32_t)salt_len, d_out);
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, 32 * n))) return rc;
+  SYNC_FLUSH(c);
   return 0;
 }
 API_CATCH

@@ -14,13 +14,17 @@
 //   ProofOfPossession<C>                           src/proof_of_possession.rs:79-81
 //   PublicKeyShare<C>, SignatureShare<C>           src/public_key_share.rs:53-72 (verify = the scheme's verify on the share values)
 //   verify_batch (additive; no reference entry)    n independent Signature::verify calls in one launch
+//   ProofCommitmentChallenge<C>                    src/proof_commitment.rs:256-261 (from_hash)
+//   ProofOfKnowledge<C>, ProofOfKnowledgeTimestamp<C>   src/proof_of_knowledge.rs:132-164, 287-326
 //
 // Header-only; link with -lblsgpu.  Every call goes to the GPU: there is no CPU path behind these types, and a missing
 // device surfaces as BlsError{Kind::Runtime} from the first call.
 #pragma once
 #include <array>
+#include <chrono>
 #include <cstdint>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <utility>
 #include <variant>
@@ -373,6 +377,85 @@ struct PublicKeyShare {
   uint8_t identifier;
   PublicKey<C> value;
   BlsResult<Unit> verify(const SignatureShare<C>& sig, const Bytes& msg) const { return sig.value.verify(value, msg); }
+};
+
+namespace detail {
+// status of the proof-of-knowledge calls -> the BlsError of BlsSignatureProof::verify (strings: src/traits/sig_proof.rs:110-140).
+// BLSGPU_E_ARG in the slot (a timestamp after now_ms beside a timeout: the reference panics there) is a Runtime error.
+inline BlsResult<Unit> proof_from_status(int32_t st) {
+  using K = BlsError::Kind;
+  switch (st) {
+    case BLSGPU_OK: return Unit{};
+    case BLSGPU_INVALID_SIGNATURE: return BlsError{K::InvalidProof, ""};
+    case BLSGPU_COMMITMENT_IDENTITY: return BlsError{K::InvalidInputs, "commitment is the identity point"};
+    case BLSGPU_PROOF_IDENTITY: return BlsError{K::InvalidInputs, "proof is the identity point"};
+    case BLSGPU_PK_IDENTITY: return BlsError{K::InvalidInputs, "pk is the identity point"};
+    case BLSGPU_ZERO_CHALLENGE: return BlsError{K::InvalidInputs, "y is the zero"};
+    case BLSGPU_E_ARG: return BlsError{K::Runtime, "proof timestamp lies after now_ms"};
+    default: return BlsError{K::Runtime, "unexpected status " + std::to_string(st)};
+  }
+}
+}  // namespace detail
+
+// the server's move of the three-move protocol: a scalar, 32 bytes little-endian as the C ABI takes it
+template <class C>
+struct ProofCommitmentChallenge {
+  std::array<uint8_t, 32> le;
+  // ProofCommitmentChallenge::from_hash, src/proof_commitment.rs:256-261: hash_to_scalar(data, KEYGEN_SALT), on the GPU
+  static BlsResult<ProofCommitmentChallenge> from_hash(const Bytes& data) {
+    if (int rc = detail::ensure_init()) return detail::runtime_error(rc);
+    static const char salt[] = "BLS-SIG-KEYGEN-SALT-";                      // src/helpers.rs:7
+    const uint64_t offs[2] = {0, data.size()};
+    ProofCommitmentChallenge y;
+    if (int rc = blsgpu_hash_to_scalar(data.data(), offs, 1, (const uint8_t*)salt, sizeof salt - 1, y.le.data())) return detail::runtime_error(rc);
+    return y;
+  }
+  Bytes to_le_bytes() const { return Bytes(le.begin(), le.end()); }
+  Bytes to_be_bytes() const { return Bytes(le.rbegin(), le.rend()); }
+};
+
+template <class C>
+struct ProofOfKnowledge {
+  SignatureSchemes scheme;                 // the enum tag of src/proof_of_knowledge.rs:9-20
+  std::array<uint8_t, C::SIG_RAW> u, v;
+  // ProofOfKnowledge::verify(pk, msg, y), src/proof_of_knowledge.rs:132-164
+  BlsResult<Unit> verify(const PublicKey<C>& pk, const Bytes& msg, const ProofCommitmentChallenge<C>& y) const {
+    if (int rc = detail::ensure_init()) return detail::runtime_error(rc);
+    const uint64_t offs[2] = {0, msg.size()};
+    int32_t st = 0;
+    int rc = blsgpu_sig_proof_verify_batch(C::SIG_GROUP, (int)scheme, u.data(), v.data(), pk.raw.data(), y.le.data(), msg.data(), offs, 1,
+                                           BLSGPU_FMT_RAW_PROJ, &st);
+    if (rc) return detail::runtime_error(rc);
+    return detail::proof_from_status(st);
+  }
+};
+
+template <class C>
+struct ProofOfKnowledgeTimestamp {
+  SignatureSchemes scheme;                 // src/proof_of_knowledge.rs:166-180
+  std::array<uint8_t, C::SIG_RAW> u, v;
+  uint64_t t;                              // milliseconds since the epoch
+  // ProofOfKnowledgeTimestamp::verify(pk, msg, timeout_ms), src/proof_of_knowledge.rs:287-326: one call, the challenge derived on
+  // the device.  The library reads no clock: now_ms defaults to this host's.
+  BlsResult<Unit> verify(const PublicKey<C>& pk, const Bytes& msg, std::optional<uint64_t> timeout_ms = std::nullopt,
+                         std::optional<uint64_t> now_ms = std::nullopt) const {
+    if (int rc = detail::ensure_init()) return detail::runtime_error(rc);
+    const uint64_t now = now_ms ? *now_ms
+                                : (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
+    const uint64_t offs[2] = {0, msg.size()};
+    int32_t st = 0;
+    int rc = blsgpu_sig_proof_timestamp_verify_batch(C::SIG_GROUP, (int)scheme, u.data(), v.data(), pk.raw.data(), &t, msg.data(), offs, 1,
+                                                     BLSGPU_FMT_RAW_PROJ, now, timeout_ms ? (int64_t)*timeout_ms : -1, &st);
+    if (rc) return detail::runtime_error(rc);
+    return detail::proof_from_status(st);
+  }
+  // the challenge the verification derives: BlsSignatureProof::compute_y(u, t), src/traits/sig_proof.rs:38-46
+  BlsResult<ProofCommitmentChallenge<C>> challenge() const {
+    if (int rc = detail::ensure_init()) return detail::runtime_error(rc);
+    ProofCommitmentChallenge<C> y;
+    if (int rc = blsgpu_sig_proof_challenge_batch(C::SIG_GROUP, u.data(), &t, 1, BLSGPU_FMT_RAW_PROJ, y.le.data())) return detail::runtime_error(rc);
+    return y;
+  }
 };
 
 }  // namespace blsful

@@ -264,12 +264,38 @@ int blsgpu_signcrypt_valid_batch(int sig_group, int scheme, const void* us, cons
 
 /* ProofOfKnowledge::<C>::verify(pk, msg, y) for n proofs (u = commitment, v = proof)   src/proof_of_knowledge.rs:132-164
  *   -> BlsSignatureProof::verify                                              src/traits/sig_proof.rs:102-142
- * (ProofOfKnowledgeTimestamp::verify derives y from (u, t) and runs the same check, :145-175 / proof_of_knowledge.rs:287-326).
+ * (ProofOfKnowledgeTimestamp::verify derives y from (u, t) and runs the same check: blsgpu_sig_proof_timestamp_verify_batch).
  * ys: the challenges, 32 B little-endian canonical scalars.  status[i]: OK, COMMITMENT_IDENTITY, PROOF_IDENTITY,
  * PK_IDENTITY, ZERO_CHALLENGE (checked in that order) or INVALID_SIGNATURE (= BlsError::InvalidProof). */
 int blsgpu_sig_proof_verify_batch(int sig_group, int scheme, const void* commitments, const void* proofs, const void* pks,
                                   const uint8_t* ys, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, int fmt,
                                   int32_t* status);
+
+/* HashToScalar::hash_to_scalar(m, salt) for n inputs                           src/impls/g1.rs:25-27 -> src/helpers.rs:9-26
+ * (ProofCommitmentChallenge::from_hash with KEYGEN_SALT, src/proof_commitment.rs:256-261; SecretKey::from_hash,
+ * src/secret_key.rs:276-281): HKDF-SHA-256 extract with the salt over m || 0x00, expand to 48 bytes with info = 00 30, reduce
+ * modulo r.  msgs is the concatenation of the inputs, msg_offsets has n + 1 entries.  out: n x 32 B little-endian canonical.
+ * The reference repeats the expand while the result is zero, which cannot end; here a zero result is written as zero.
+ * Not constant time: public inputs only. */
+int blsgpu_hash_to_scalar(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, const uint8_t* salt, size_t salt_len, uint8_t* out);
+
+/* BlsSignatureProof::compute_y(u, t) for n commitments                         src/traits/sig_proof.rs:38-46
+ * y = hash_to_scalar(u.to_bytes() || LE64(t), "BLS_POK__BLS12381_XOF:HKDF-SHA2-256_"): the modern compressed encoding of u whatever
+ * fmt it came in (all four formats).  out_ys: n x 32 B, the form blsgpu_sig_proof_verify_batch reads.  A COMPRESSED / LEGACY
+ * commitment that does not decode gets y = 0. */
+int blsgpu_sig_proof_challenge_batch(int sig_group, const void* commitments, const uint64_t* timestamps, size_t n, int fmt, uint8_t* out_ys);
+
+/* ProofOfKnowledgeTimestamp::<C>::verify(pk, msg, timeout_ms) for n proofs     src/proof_of_knowledge.rs:287-326
+ *   -> BlsSignatureProof::verify_timestamp_proof                              src/traits/sig_proof.rs:145-166
+ * timestamps: n x u64 milliseconds (the proof's t).  timeout_ms < 0: None.  The library reads no clock: now_ms is the caller's.
+ * status[i] is what blsgpu_sig_proof_verify_batch gives the item with y = compute_y(u, t), except that, with a timeout and tested
+ * before anything else (:154-161): t > now_ms puts BLSGPU_E_ARG into the slot (the reference panics there), and
+ * now_ms - t > timeout_ms gives BLSGPU_INVALID_SIGNATURE (= InvalidProof) whatever the points are; elapsed == timeout_ms passes.
+ * All four point formats; a COMPRESSED / LEGACY point that does not decode gives the item its decode status (BAD_ENCODING, ...:
+ * commitment, proof, key in that order) unless the timeout rule applies. */
+int blsgpu_sig_proof_timestamp_verify_batch(int sig_group, int scheme, const void* commitments, const void* proofs, const void* pks,
+                                            const uint64_t* timestamps, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n,
+                                            int fmt, uint64_t now_ms, int64_t timeout_ms, int32_t* status);
 
 /* n independent products of two pairings: is_one[i] = Pairing::pairing(&[(g1a_i, g2a_i), (g1b_i, g2b_i)]).is_identity()
  * (src/traits/pairings.rs:50, src/helpers.rs:41-63) -- the shape of BlsSignCrypt::verify_share
