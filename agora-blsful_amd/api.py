@@ -42,7 +42,7 @@ EXPORTS = [
     'blsgpu_aggregate_partial', 'blsgpu_fp12_product_is_one', 'blsgpu_core_verify', 'blsgpu_deserialize', 'blsgpu_pop_verify_batch', 'blsgpu_aggregate_secure',
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
-    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_map_to_curve', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
@@ -168,6 +168,7 @@ def load_library(path=None):
         lib.blsgpu_debug_field_op_shape.argtypes = [ci] + [ctypes.POINTER(ctypes.c_int)] * 5
         lib.blsgpu_debug_field_op.argtypes = [ci, i32p, sz, ci, i32p]
         lib.blsgpu_debug_millerf.argtypes = [i32p, sz, i32p, i32p]
+        lib.blsgpu_debug_map_to_curve.argtypes = [ci, ci, ci, u8p, sz, vp]
         lib.blsgpu_debug_coop_pairing.argtypes = [ci, ci, i32p, sz, i32p, i32p]
         lib.blsgpu_verify_batch_grouped.argtypes = [ci, ci, vp, vp, u8p, vp, sz, ci, ctypes.c_uint64, i32p]
         lib.blsgpu_signatures_from_tagged.argtypes = [ci, u8p, sz, u8p, vp, i32p]
@@ -1191,6 +1192,23 @@ def debug_millerf(tables, status=None):
     _check(lib.blsgpu_debug_millerf(ctypes.cast(arr, ctypes.c_void_p), n, ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
     o = list(out)
     return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n)]
+
+
+# the kernel paths of blsgpu_debug_map_to_curve (include/blsgpu.h BLSGPU_H2C_*)
+H2C_LANE, H2C_PAIR, H2C_WIDE, H2C_ENGINE, H2C_MAPS_TAIL, H2C_WIDE_REC, H2C_PAIR_CLEAR_WIDE = range(7)
+
+
+def debug_map_to_curve(group, path, uncleared, uniform):
+    """Hash-to-curve behind expand_message_xmd on one kernel path, on caller-supplied uniform bytes.  uniform: per item 128 (group 1)
+    or 256 (group 2) bytes.  Returns per item the RAW_PROJ point (144 / 288 bytes, Jacobian; Z = 0: the identity); uncleared = 1: the
+    point before the cofactor clearing.  A (group, path, uncleared) that no launch of the library uses raises."""
+    lib = init()
+    ub, osz = (128, 144) if group == 1 else (256, 288)
+    n = len(uniform)
+    assert all(len(u) == ub for u in uniform)
+    out = ctypes.create_string_buffer(max(osz * n, 1))
+    _check(lib.blsgpu_debug_map_to_curve(group, path, uncleared, b''.join(uniform), n, ctypes.cast(out, ctypes.c_void_p)))
+    return [out.raw[osz * i:osz * (i + 1)] for i in range(n)]
 
 
 COOP_SENTINEL = 0xa5a5a5a5 - (1 << 32)       # BLSGPU_DEBUG_COOP_SENTINEL as a signed limb

@@ -857,9 +857,9 @@ int side_fork(Ctx* c, int which = 3) {
 void launch_hash_g1_small(hipStream_t stream, size_t n, const uint8_t* d_msgs, const uint64_t* d_offs, int flags, const dst_arg& dst, uint8_t* d_out,
                           uint32_t* d_rec) {
   if (n <= 128 && hash_phase_stop() == 0)     // measured (tools/dbg/small.py): at 256 items the pre-workgroups compete for the CUs and the one-wave hash wins
-    hipLaunchKernelGGL(k_hash_to_g1_engine, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), 0, stream, n, d_msgs, d_offs, flags, dst, d_out, d_rec);
+    hipLaunchKernelGGL(k_hash_to_g1_engine<false>, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), 0, stream, n, d_msgs, d_offs, flags, dst, d_out, d_rec);
   else
-    hipLaunchKernelGGL(k_hash_to_g1_wide, dim3((unsigned)n), dim3(BLS_BLOCK), 0, stream, n, d_msgs, d_offs, flags | hash_phase_stop() << 8, dst, d_out, d_rec);
+    hipLaunchKernelGGL(k_hash_to_g1_wide<false>, dim3((unsigned)n), dim3(BLS_BLOCK), 0, stream, n, d_msgs, d_offs, flags | hash_phase_stop() << 8, dst, d_out, d_rec);
 }
 
 // hash-to-G2 of a few messages on `stream` (RAW_PROJ out): one workgroup per message on the engine up to 128 messages; beyond
@@ -870,15 +870,15 @@ bool launch_hash_g2_small(hipStream_t stream, size_t n, const uint8_t* d_msgs, c
   // d_rec: the records of a cut check (WREC_Q0 of item i <- H(m_i)); true when they were written -- the lane-pair form only
   // fills d_out and the caller converts (k_prepare_keys part 4)
   if (n <= 128 && hash_phase_stop() == 0) {
-    hipLaunchKernelGGL(k_hash_to_g2_engine, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), 0, stream, n, d_msgs, d_offs, flags, dst, d_out, d_rec);
+    hipLaunchKernelGGL(k_hash_to_g2_engine<false>, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), 0, stream, n, d_msgs, d_offs, flags, dst, d_out, d_rec);
     return d_rec != nullptr;
   }
   if (d_pts && hash_phase_stop() == 0) {
-    hipLaunchKernelGGL(k_hash_to_g2_maps, dim3((unsigned)n), dim3(BLS_BLOCK), 0, stream, n, d_msgs, d_offs, flags, dst, d_pts);
+    hipLaunchKernelGGL(k_hash_to_g2_maps<false>, dim3((unsigned)n), dim3(BLS_BLOCK), 0, stream, n, d_msgs, d_offs, flags, dst, d_pts);
     hipLaunchKernelGGL(k_g2_hash_tail_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), 0, stream, n, (const uint32_t*)d_pts, d_out, d_rec);
     return d_rec != nullptr;
   }
-  hipLaunchKernelGGL(k_hash_to_g2, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), 0, stream, n, d_msgs, d_offs, dst, d_out, 3);
+  hipLaunchKernelGGL(k_hash_to_g2<false>, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), 0, stream, n, d_msgs, d_offs, dst, d_out, 3);
   hipLaunchKernelGGL(k_g2_clear_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), 0, stream, n, d_out);
   return false;
 }
@@ -1015,7 +1015,7 @@ int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_
     uint8_t* d_hashes = (uint8_t*)arena_take(c, 144 * n);
     if (!d_hashes) return fail(BLSGPU_E_HIP, "internal: arena too small");
     // the hashes stay uncleared (bit 1) and the fixed pair is (sig, -[c] g2) (table 2), as everywhere for this implementation
-    KL(KID_HASH, k_hash_to_g1_wide, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_msgs, d_offs, (single_msg & 1) | 2, dst, d_hashes, (uint32_t*)nullptr);
+    KL(KID_HASH, k_hash_to_g1_wide<false>, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_msgs, d_offs, (single_msg & 1) | 2, dst, d_hashes, (uint32_t*)nullptr);
     KL(KID_PREPARE, k_prepare_hashed<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_pks, d_sigs, (const uint8_t*)d_hashes, d_pairs, d_status, fmt);
     return run_pairing2(c, n, d_pairs, d_f, d_status, 2, nullptr, nullptr, key_table, key_of);
   }
@@ -3096,8 +3096,8 @@ API_CATCH
 // -[c] g2 -- one wave per message up to 1,024 messages, two lanes per message beyond (the measured split of run_verify_items)
 static int run_hash_group(Ctx* c, int group, size_t n, const uint8_t* d_msgs, const uint64_t* d_offs, const dst_arg& d, uint8_t* d_out, bool uncleared = false) {
   if (uncleared && group == 1) {
-    if (n <= 1024 && wide_max_items() > 0) KL(KID_HASH, k_hash_to_g1_wide, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_msgs, d_offs, 2, d, d_out, (uint32_t*)nullptr);
-    else KL(KID_HASH, k_hash_to_g1, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, 1 | 2);
+    if (n <= 1024 && wide_max_items() > 0) KL(KID_HASH, k_hash_to_g1_wide<false>, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_msgs, d_offs, 2, d, d_out, (uint32_t*)nullptr);
+    else KL(KID_HASH, k_hash_to_g1<false>, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, 1 | 2);
     HIPCK(hipGetLastError());
     return 0;
   }
@@ -3109,16 +3109,16 @@ static int run_hash_group(Ctx* c, int group, size_t n, const uint8_t* d_msgs, co
     launch_hash_g1_small(c->stream, n, d_msgs, d_offs, 0, d, d_out, (uint32_t*)nullptr);
     prof_post(c);
   }
-  else if (group == 1) KL(KID_HASH, k_hash_to_g1, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, two);
+  else if (group == 1) KL(KID_HASH, k_hash_to_g1<false>, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, two);
   else if (n <= wide_max_items() && hash_phase_stop() == 0) {   // a few messages: row-wide maps and the engine (one workgroup per message up to 128)
     prof_pre(c, KID_HASH);
     launch_hash_g2_small(c->stream, n, d_msgs, d_offs, 0, d, d_out, n > 128 ? (uint32_t*)arena_take(c, 768 * n) : nullptr);
     prof_post(c);
   } else if (n <= wide_max_items() && hash_phase_stop() != 8) {   // measurement aids (BLSGPU_HASH_STOP=8: clearing in the lane-pair kernel; 9: none)
-    KL(KID_HASH, k_hash_to_g2, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, 3);
+    KL(KID_HASH, k_hash_to_g2<false>, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, 3);
     if (hash_phase_stop() != 9) KL(KID_HASH, k_g2_clear_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), n, d_out);   // 9: measurement aid, no clearing
   } else
-    KL(KID_HASH, k_hash_to_g2, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, two);
+    KL(KID_HASH, k_hash_to_g2<false>, dim3(blocks_for(two ? 2 * n : n)), dim3(BLS_BLOCK), n, d_msgs, d_offs, d, d_out, two);
   HIPCK(hipGetLastError());
   return 0;
 }
@@ -3550,6 +3550,73 @@ int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t
 #undef DBG_LAUNCH
   HIPCK(hipGetLastError());
   if ((rc = stage_back(c, out, d_out, (size_t)4 * rec_out * n))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* Self-test hook of hash-to-curve behind expand_message_xmd (include/blsgpu.h): the kernels of run_hash_group, launch_hash_g1_small and
+ * launch_hash_g2_small in their UB = true form (tu_debug_h2c.hip, tu_debug_h2c_wide.hip), launched with the grids and flags those
+ * functions use, on caller-supplied uniform bytes. */
+int blsgpu_debug_map_to_curve(int group, int path, int uncleared, const uint8_t* uniform, size_t n, void* out) try {
+  if (!initialised()) return NOT_INIT();
+  bool known = false;
+  if (group == 1) {
+    known = ((path == BLSGPU_H2C_LANE || path == BLSGPU_H2C_PAIR || path == BLSGPU_H2C_WIDE || path == BLSGPU_H2C_ENGINE) && (uncleared == 0 || uncleared == 1)) ||
+            (path == BLSGPU_H2C_WIDE_REC && uncleared == 1);
+  } else if (group == 2) {
+    known = ((path == BLSGPU_H2C_LANE || path == BLSGPU_H2C_ENGINE || path == BLSGPU_H2C_MAPS_TAIL || path == BLSGPU_H2C_PAIR_CLEAR_WIDE) && uncleared == 0) ||
+            (path == BLSGPU_H2C_PAIR && (uncleared == 0 || uncleared == 1));
+  }
+  if (!known) return fail(BLSGPU_E_ARG, "no launch of the library uses this (group, path, uncleared)");
+  if (n == 0) return 0;
+  if (!uniform || !out || n > 4096 || is_device_ptr(uniform) || is_device_ptr(out)) return fail(BLSGPU_E_ARG, "bad argument");
+  CTX_ACQUIRE(c);
+  const size_t ubytes = group == 1 ? 128 : 256, osz = point_bytes(group, BLSGPU_FMT_RAW_PROJ);
+  const bool record = group == 1 && (path == BLSGPU_H2C_WIDE_REC || (path == BLSGPU_H2C_ENGINE && uncleared));
+  const size_t rec_bytes = record ? (size_t)WREC_WORDS * 4 * n : 0, maps_bytes = path == BLSGPU_H2C_MAPS_TAIL ? 768 * n : 0;
+  int rc = arena_reserve(c, pad256(ubytes * n) + pad256(osz * n) + pad256(rec_bytes) + pad256(maps_bytes) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void* d_in;
+  if ((rc = stage_in(c, uniform, ubytes * n, &d_in))) return rc;
+  uint8_t* d_out = stage_out<uint8_t>(c, out, osz * n);
+  uint32_t* d_rec = record ? (uint32_t*)arena_take(c, rec_bytes) : nullptr;
+  uint32_t* d_maps = maps_bytes ? (uint32_t*)arena_take(c, maps_bytes) : nullptr;
+  if (!d_out || (record && !d_rec) || (maps_bytes && !d_maps)) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  const uint8_t* d_ub = (const uint8_t*)d_in;
+  const uint64_t* no_offs = nullptr;
+  dst_arg d;
+  memset(&d, 0, sizeof d);
+  const dim3 one(BLS_BLOCK), wg(WIDE_ENGINE_BLOCK), per_item((unsigned)n);
+  const int two = path == BLSGPU_H2C_LANE ? 0 : 1;
+  if (group == 1) {
+    if (path == BLSGPU_H2C_LANE || path == BLSGPU_H2C_PAIR)
+      KL(KID_DEBUG_OPS, k_hash_to_g1<true>, dim3(blocks_for(two ? 2 * n : n)), one, n, d_ub, no_offs, d, d_out, two | (uncleared ? 2 : 0));
+    else if (path == BLSGPU_H2C_WIDE)
+      KL(KID_DEBUG_OPS, k_hash_to_g1_wide<true>, per_item, one, n, d_ub, no_offs, uncleared ? 2 : 0, d, d_out, (uint32_t*)nullptr);
+    else if (path == BLSGPU_H2C_WIDE_REC)
+      KL(KID_DEBUG_OPS, k_hash_to_g1_wide<true>, per_item, one, n, d_ub, no_offs, 0, d, (uint8_t*)nullptr, d_rec);
+    else if (uncleared)
+      KL(KID_DEBUG_OPS, k_hash_to_g1_engine<true>, per_item, wg, n, d_ub, no_offs, 0, d, (uint8_t*)nullptr, d_rec);
+    else
+      KL(KID_DEBUG_OPS, k_hash_to_g1_engine<true>, per_item, wg, n, d_ub, no_offs, 0, d, d_out, (uint32_t*)nullptr);
+    if (record) KL(KID_DEBUG_OPS, k_dbg_rec_g1_to_raw, dim3(blocks_for(n)), one, n, (const uint32_t*)d_rec, d_out);
+  } else {
+    if (path == BLSGPU_H2C_LANE || path == BLSGPU_H2C_PAIR)
+      KL(KID_DEBUG_OPS, k_hash_to_g2<true>, dim3(blocks_for(two ? 2 * n : n)), one, n, d_ub, no_offs, d, d_out, two | (uncleared ? 2 : 0));
+    else if (path == BLSGPU_H2C_PAIR_CLEAR_WIDE) {
+      KL(KID_DEBUG_OPS, k_hash_to_g2<true>, dim3(blocks_for(2 * n)), one, n, d_ub, no_offs, d, d_out, 3);
+      KL(KID_DEBUG_OPS, k_g2_clear_wide, per_item, wg, n, d_out);
+    } else if (path == BLSGPU_H2C_ENGINE)
+      KL(KID_DEBUG_OPS, k_hash_to_g2_engine<true>, per_item, wg, n, d_ub, no_offs, 0, d, d_out, (uint32_t*)nullptr);
+    else {
+      KL(KID_DEBUG_OPS, k_hash_to_g2_maps<true>, per_item, one, n, d_ub, no_offs, 0, d, d_maps);
+      KL(KID_DEBUG_OPS, k_g2_hash_tail_wide, per_item, wg, n, (const uint32_t*)d_maps, d_out, (uint32_t*)nullptr);
+    }
+  }
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, osz * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
 }

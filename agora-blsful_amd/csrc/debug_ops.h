@@ -89,4 +89,6 @@ __global__ void k_dbg_f12acc(int op, size_t n, int reps, const int32_t* in, int 
 __global__ void k_dbg_cyc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_f12misc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_coop(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+// blsgpu_debug_map_to_curve: the G1 point at WREC_P0 of n cut-check records (engine values, Jacobian) -> RAW_PROJ
+__global__ void k_dbg_rec_g1_to_raw(size_t n, const uint32_t* rec, uint8_t* out);
 #endif

@@ -490,12 +490,11 @@ __device__ __noinline__ void jac_mul_u64_pair(g1_jac& r, const g1_jac& p, uint64
   r = acc;
 }
 #endif
-// no_clear: stop before the cofactor clearing -- the point of E1(Fp) whose multiple by h_eff is the hash (verification pairs it
-// with -[c] g2 instead of -g2 and needs no clearing: csrc/g2neg_lines.cuh)
-BLS_NOINLINE void hash_to_g1(g1_jac& r, const uint8_t* pre, uint32_t pre_len, const uint8_t* m, uint32_t m_len,
-                       const uint8_t* dst, uint32_t dst_len, int lane2 = -1, bool no_clear = false) {
-  uint32_t ub[32];                 // 128 uniform bytes as big-endian words
-  expand_message_xmd_words<128>(ub, pre, pre_len, m, m_len, dst, dst_len);
+// Everything of hash_to_g1 behind expand_message_xmd: ub = the 128 uniform bytes as 32 big-endian words.  Inlined into hash_to_g1;
+// on its own it is what the self-test door blsgpu_debug_map_to_curve and tests/hostsim run on caller-chosen uniform bytes.
+// (G1 and G2 are split in different ways -- a function behind the expansion here, one templated body for hash_to_g2 -- because
+// these are the forms that leave the stack frames of the product's kernels exactly as they were.)
+BLS_FN void hash_to_g1_map(g1_jac& r, const uint32_t* ub, int lane2, bool no_clear) {
   fp u0, u1, xn, xd, y;
   g1_jac q0, q1;
 #if defined(__HIPCC__)
@@ -532,6 +531,14 @@ BLS_NOINLINE void hash_to_g1(g1_jac& r, const uint8_t* pre, uint32_t pre_len, co
 #endif
     jac_mul_u64(q1, q0, BLS_X_ABS);
   jac_add(r, q1, q0);
+}
+// no_clear: stop before the cofactor clearing -- the point of E1(Fp) whose multiple by h_eff is the hash (verification pairs it
+// with -[c] g2 instead of -g2 and needs no clearing: csrc/g2neg_lines.cuh)
+BLS_NOINLINE void hash_to_g1(g1_jac& r, const uint8_t* pre, uint32_t pre_len, const uint8_t* m, uint32_t m_len,
+                       const uint8_t* dst, uint32_t dst_len, int lane2 = -1, bool no_clear = false) {
+  uint32_t ub[32];                 // 128 uniform bytes as big-endian words
+  expand_message_xmd_words<128>(ub, pre, pre_len, m, m_len, dst, dst_len);
+  hash_to_g1_map(r, ub, lane2, no_clear);
 }
 
 // ------------------------------------------------------------------ G2: simplified SWU (RFC 9380 6.6.2, generic form)
@@ -678,11 +685,17 @@ BLS_FN void iso_map_g2_hom(F2& X, F2& Y, F2& Z, const F2& x, const F2& y) {
   fp2_mul(Y, t, y);
   fp2_mul(Z, XD, YD);
 }
-// no_clear: stop before the cofactor clearing (the caller clears it elsewhere: k_g2_clear_wide)
-BLS_NOINLINE void hash_to_g2(g2_jac& r, const uint8_t* pre, uint32_t pre_len, const uint8_t* m, uint32_t m_len,
-                       const uint8_t* dst, uint32_t dst_len, int lane2 = -1, bool no_clear = false) {
+// The body of hash_to_g2.  UB = false: the product, expand_message_xmd first.  UB = true (hash_to_g2_map): everything behind the
+// expansion on the caller's 256 uniform bytes, given as 64 big-endian words.
+template <bool UB>
+BLS_FN void hash_to_g2_body(g2_jac& r, const uint8_t* pre, uint32_t pre_len, const uint8_t* m, uint32_t m_len,
+                            const uint8_t* dst, uint32_t dst_len, const uint32_t* words, int lane2, bool no_clear) {
   uint32_t ub[64];                 // 256 uniform bytes as big-endian words
-  expand_message_xmd_words<256>(ub, pre, pre_len, m, m_len, dst, dst_len);
+  if constexpr (UB) {
+    for (int i = 0; i < 64; i++) ub[i] = words[i];
+  } else {
+    expand_message_xmd_words<256>(ub, pre, pre_len, m, m_len, dst, dst_len);
+  }
   fp2 u0, u1, x, y;
   g2_jac q0, q1;
 #if defined(__HIPCC__)
@@ -735,4 +748,13 @@ BLS_NOINLINE void hash_to_g2(g2_jac& r, const uint8_t* pre, uint32_t pre_len, co
   jac_add(q0, q0, q1);
   if (no_clear) r = q0;
   else g2_clear_cofactor(r, q0);
+}
+// no_clear: stop before the cofactor clearing (the caller clears it elsewhere: k_g2_clear_wide)
+BLS_NOINLINE void hash_to_g2(g2_jac& r, const uint8_t* pre, uint32_t pre_len, const uint8_t* m, uint32_t m_len,
+                       const uint8_t* dst, uint32_t dst_len, int lane2 = -1, bool no_clear = false) {
+  hash_to_g2_body<false>(r, pre, pre_len, m, m_len, dst, dst_len, nullptr, lane2, no_clear);
+}
+// everything behind expand_message_xmd on caller-chosen uniform bytes: as hash_to_g1_map
+BLS_FN void hash_to_g2_map(g2_jac& r, const uint32_t* words, int lane2, bool no_clear) {
+  hash_to_g2_body<true>(r, nullptr, 0, nullptr, 0, nullptr, 0, words, lane2, no_clear);
 }

@@ -290,7 +290,12 @@ __global__ void k_group_sigsum(size_t ng, size_t n, const uint8_t* scaled_sigs, 
 __global__ void k_f12_mul3(size_t ng, const uint32_t* fin, size_t stride_in, uint32_t* fout);
 __global__ void k_f12_import(size_t n, const uint8_t* src, uint32_t* fws, size_t stride);
 __global__ void k_f12_export(const uint32_t* fws, size_t stride, uint8_t* dst);
+// The hash kernels take a compile-time switch UB.  false: the product.  true: the self-test door blsgpu_debug_map_to_curve
+// (tu_debug_h2c*.hip): `msgs` holds the items' uniform bytes -- what expand_message_xmd would have produced, 128 per item for G1, 256
+// for G2 -- and the expansion is not run (offs and dst are not read); everything behind it is the same code.
+template <bool UB>
 __global__ void k_hash_to_g1(size_t n, const uint8_t* msgs, const uint64_t* offs, dst_arg dst, uint8_t* out, int two_lanes);
+template <bool UB>
 __global__ void k_hash_to_g2(size_t n, const uint8_t* msgs, const uint64_t* offs, dst_arg dst, uint8_t* out, int two_lanes);
 template <int G, int WITH_SCALARS>
 __global__ void k_accumulate(size_t n, const uint8_t* pts, int fmt, const uint8_t* scalars, const uint32_t* perm,
@@ -361,9 +366,11 @@ __global__ void k_f12_horner_wide(const uint32_t* fin, size_t sin, uint32_t* fou
 __global__ void k_wide_prog_test(const uint32_t* prog, int len, int reps, const uint8_t* fin, uint8_t* tout);
 bool wide_prog_is_fp12(const uint32_t* prog, size_t len);   // host: what k_wide_prog_test may be given
 __global__ void k_pairing_wide(size_t n, const uint32_t* pairs, int32_t* status, int fixed_g2);
+template <bool UB>
 __global__ void k_hash_to_g1_wide(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst, uint8_t* out, uint32_t* rec);
 // the same with one WORKGROUP per message: wave 0 hashes up to the sum of the two mapped points, then all four waves clear the
 // cofactor on the engine (program G1_HASH_TAIL); for up to 128 messages
+template <bool UB>
 __global__ void k_hash_to_g1_engine(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst, uint8_t* out, uint32_t* rec);
 // The same check cut where its inputs become known (csrc/wide_tables.cuh programs PRE_LINES, PRE_F1 / PRE_F1G, POST).  The pairs
 // are (P0, Q0) (P1, Q1) = (H(m), key) (signature, -g2) for Bls12381G1Impl and (key, H(m)) (-g1, signature) for Bls12381G2Impl.
@@ -407,9 +414,11 @@ __global__ void k_g2_clear_wide(size_t n, uint8_t* pts);
 // hash-to-G2 with one WORKGROUP per message: wave 0 expands the message and runs the two SSWU maps and isogenies on two DPP rows
 // (row-wide Fp2, csrc/wide_fp2.cuh), then all four waves add the two points and clear the cofactor on the engine (program
 // G2_HASH_TAIL).  out: RAW_PROJ (Jacobian).  single_msg bit 0: every item hashes message 0.  For up to 128 messages.
+template <bool UB>
 __global__ void k_hash_to_g2_engine(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst, uint8_t* out, uint32_t* rec);   // out / rec: either may be null; rec: the cut check's record (WREC_Q0)
 // the same for more messages as two launches: the maps with one WAVE per message (pts: 12 engine values = 768 bytes per message),
 // then the engine program with one workgroup per message
+template <bool UB>
 __global__ void k_hash_to_g2_maps(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst, uint32_t* pts);
 __global__ void k_g2_hash_tail_wide(size_t n, const uint32_t* pts, uint8_t* out, uint32_t* rec);
 
@@ -920,13 +929,19 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_f12_export(const uint32_t* fws, s
 }
 #endif  // BLS_TU_FINALEXP
 
-#if defined(BLS_TU_POINTS)
-#include "msm2.cuh"     // jac_madd
+#if defined(BLS_TU_POINTS) || defined(BLS_TU_DEBUG_H2C)
 // =====================================================================================================
 // hash_to_point batches
+// item i's uniform bytes (NW / 4 x 16 of them at ub + 4 NW i) as NW big-endian words: what the UB = true forms read where the
+// product runs expand_message_xmd
+template <int NW>
+__device__ __forceinline__ void load_uniform_words(uint32_t* w, const uint8_t* ub, size_t i) {
+  for (int j = 0; j < NW; j++) w[j] = be32_at(ub + (i * NW + j) * 4);
+}
 // two_lanes: two adjacent lanes per message run the two SSWU maps side by side (and, for G2, the cofactor clearing on the
 // lane-split tower), as k_prepare does: the latency mode for the single message of a verify_secure tail
 // two_lanes bit 1 (value 2): the point stays in E1(Fp), NOT cofactor-cleared (the shared-message verify pairs it with -[c] g2)
+template <bool UB>
 __global__ void __launch_bounds__(BLS_BLOCK) k_hash_to_g1(size_t n, const uint8_t* msgs, const uint64_t* offs, dst_arg dst, uint8_t* out, int two_lanes) {
   const bool no_clear = (two_lanes & 2) != 0;
   two_lanes &= 1;
@@ -935,10 +950,17 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_hash_to_g1(size_t n, const uint8_
   const int lane2 = two_lanes ? (int)(gid & 1) : -1;
   if (i >= n) return;
   g1_jac h;
-  hash_to_g1(h, nullptr, 0, msgs + offs[i], (uint32_t)(offs[i + 1] - offs[i]), dst.b, dst.len, lane2, no_clear);
+  if constexpr (UB) {
+    uint32_t ub[32];
+    load_uniform_words<32>(ub, msgs, i);
+    hash_to_g1_map(h, ub, lane2, no_clear);
+  } else {
+    hash_to_g1(h, nullptr, 0, msgs + offs[i], (uint32_t)(offs[i + 1] - offs[i]), dst.b, dst.len, lane2, no_clear);
+  }
   if (lane2 <= 0) store_g1_pt(out, i, h);
 }
 // two_lanes bit 1 (value 2): stop before the cofactor clearing (k_g2_clear_wide does it on the row-wide engine)
+template <bool UB>
 __global__ void __launch_bounds__(BLS_BLOCK) k_hash_to_g2(size_t n, const uint8_t* msgs, const uint64_t* offs, dst_arg dst, uint8_t* out, int two_lanes) {
   const bool no_clear = (two_lanes & 2) != 0;
   two_lanes &= 1;
@@ -947,9 +969,20 @@ __global__ void __launch_bounds__(BLS_BLOCK) k_hash_to_g2(size_t n, const uint8_
   const int lane2 = two_lanes ? (int)(gid & 1) : -1;
   if (i >= n) return;
   g2_jac h;
-  hash_to_g2(h, nullptr, 0, msgs + offs[i], (uint32_t)(offs[i + 1] - offs[i]), dst.b, dst.len, lane2, no_clear);
+  if constexpr (UB) {
+    uint32_t ub[64];
+    load_uniform_words<64>(ub, msgs, i);
+    hash_to_g2_map(h, ub, lane2, no_clear);
+  } else {
+    hash_to_g2(h, nullptr, 0, msgs + offs[i], (uint32_t)(offs[i + 1] - offs[i]), dst.b, dst.len, lane2, no_clear);
+  }
   if (lane2 <= 0) store_g2_pt(out, i, h);
 }
+#endif  // BLS_TU_POINTS || BLS_TU_DEBUG_H2C
+#if defined(BLS_TU_POINTS)
+template __global__ void k_hash_to_g1<false>(size_t, const uint8_t*, const uint64_t*, dst_arg, uint8_t*, int);
+template __global__ void k_hash_to_g2<false>(size_t, const uint8_t*, const uint64_t*, dst_arg, uint8_t*, int);
+#include "msm2.cuh"     // jac_madd
 
 // =====================================================================================================
 // point sums and multi-scalar multiplication.  Partials are RAW_PROJ structs in a workspace array.
@@ -3445,10 +3478,13 @@ __global__ void __launch_bounds__(BLS_BLOCK, 2) k_pairing_coop_keyed(size_t n, c
 }
 #endif
 
-#if defined(BLS_TU_WIDE)
+// BLS_TU_DEBUG_H2C_WIDE (tu_debug_h2c_wide.hip): the hash kernels of this section alone, in their UB = true form
+#if defined(BLS_TU_WIDE) || defined(BLS_TU_DEBUG_H2C_WIDE)
 // =====================================================================================================
 #include "wide.cuh"
 #include "wide_fp2.cuh"
+#endif
+#if defined(BLS_TU_WIDE)
 // self-test of the row-wide multiplier: item i = a_i * b_i (caller format: 48-byte Montgomery words), `reps` chained
 // multiplications by b (reps = 1: the plain product), four items per wave
 __global__ void __launch_bounds__(WIDE_BLOCK) k_wide_mul_test(size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, int reps) {
@@ -3475,7 +3511,11 @@ __global__ void __launch_bounds__(WIDE_BLOCK) k_wide_mul_test(size_t n, const ui
     fp_to_raw((uint32_t*)(out + 48 * i), z);
   }
 }
+#endif
+#if defined(BLS_TU_WIDE) || defined(BLS_TU_DEBUG_H2C_WIDE)
 #include "wide_engine.cuh"
+#endif
+#if defined(BLS_TU_WIDE)
 bool wide_prog_is_fp12(const uint32_t* prog, size_t len) {
   if (len > WIDE_PROG_MAX) return false;
   for (size_t k = 0; k < len; k++) {
@@ -4048,6 +4088,8 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_g2_clear_wide(size_t n, u
     fp_to_raw(w + 12 * threadIdx.x, x);
   }
 }
+#endif
+#if defined(BLS_TU_WIDE) || defined(BLS_TU_DEBUG_H2C_WIDE)
 
 // ---- hash_to_curve to G1 for single items: ONE wave per message, the two SSWU maps on rows 0 and 1 of the wave in the
 // row-wide field type `wf` (csrc/wide.cuh), then both rows add the two points and clear the cofactor redundantly.
@@ -4241,7 +4283,15 @@ __device__ __forceinline__ void fp_from_be_words(fp& r, const uint32_t* bw) {
   fp_add(t, t, hi);
   fp_reduce(r, t);
 }
+// item i's uniform bytes as NW big-endian words: what the UB = true forms of the kernels below read where the product runs
+// expand_message_xmd_wave (every lane of the wave loads all of them, as every lane holds the expansion's words)
+template <int NW>
+__device__ __forceinline__ void load_uniform_words_wave(uint32_t* w, const uint8_t* ub, size_t i) {
+#pragma unroll
+  for (int j = 0; j < NW; j++) w[j] = be32_at(ub + (i * NW + j) * 4);
+}
 
+template <bool UB>
 __global__ void __launch_bounds__(WIDE_BLOCK) k_hash_to_g1_wide(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst, uint8_t* out,
                                                              uint32_t* rec) {
   __shared__ uint32_t pts[4][2][3][16];     // per wave: the Jacobian points of the two maps
@@ -4254,7 +4304,8 @@ __global__ void __launch_bounds__(WIDE_BLOCK) k_hash_to_g1_wide(size_t n, const 
   const int stop = single_msg >> 8;            // measurement aid (blsgpu.hip hash_phase_stop): leave after phase `stop`
   const size_t mi = (single_msg & 1) ? 0 : i;
   uint32_t ubw[32];
-  expand_message_xmd_wave<128>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk[wave]);   // the whole wave
+  if constexpr (UB) load_uniform_words_wave<32>(ubw, msgs, mi);
+  else expand_message_xmd_wave<128>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk[wave]);   // the whole wave
   if (row >= 2) return;                       // rows 2 and 3 of the wave stay idle from here: the hash has two independent maps
   uint32_t uw[16];
 #pragma unroll
@@ -4318,7 +4369,12 @@ __global__ void __launch_bounds__(WIDE_BLOCK) k_hash_to_g1_wide(size_t n, const 
 // multiplications, the row-wide field type's business); everything behind them is program G1_HASH_TAIL of table set PT on all
 // four waves -- the 11-isogeny of both points as eight table steps (every polynomial ONE linear row over monomial x constant
 // products: 15 us where the Horner chains took 87), their sum, and the cofactor clearing (1 + |x|) q as 70 complete additions
-// (0.17 ms where the two rows took 0.29).  (A point on a pole of the isogeny would need the identity here; no message hashes there.)
+// (0.17 ms where the two rows took 0.29).
+// A mapped point on a pole of the isogeny (sixteen values of u; no message is known to hash there) is the identity (RFC 9380 6.6.3).
+// The program's homogeneous image (XN YD : y YN zx : zx YD), zx = XD xd, is (0 : 0 : 0) there, which the complete additions would carry
+// through to the end.  So zx of both maps is looked at AFTER the program: when one is zero the sum is the other map's point, taken
+// from where the program left it and cleared by program G1_CLEAR; when both are, the result is the identity.
+template <bool UB>
 __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g1_engine(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst,
                                                                        uint8_t* out, uint32_t* rec) {
   __shared__ wide_lds_t<wide_tb_pt> S;
@@ -4337,7 +4393,8 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g1_engine(size_t 
   if (wave == 0) {
     const size_t mi = (single_msg & 1) ? 0 : i;
     uint32_t ubw[32];
-    expand_message_xmd_wave<128>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk);   // the whole wave
+    if constexpr (UB) load_uniform_words_wave<32>(ubw, msgs, mi);
+    else expand_message_xmd_wave<128>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk);   // the whole wave
     if (row < 2) {
       uint32_t uw[16];
 #pragma unroll
@@ -4363,7 +4420,47 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g1_engine(size_t 
     }
   }
   __syncthreads();
-  wide_exec(S, prog_len, K);
+  for (int pass = 0;; pass++) {
+    wide_exec(S, pass ? WIDE_PROG_G1_CLEAR_LEN : prog_len, K);
+    if (pass) break;
+    if (threadIdx.x == 0) {
+      fp z0, z1;
+      w_load_local(z0, S.V[WPV_ISO + WIDE_PT_ISO_ZX]);
+      w_load_local(z1, S.V[WPV_ISO + WIDE_PT_ISO_STRIDE + WIDE_PT_ISO_ZX]);
+      S.flag = (fp_is_zero(z0) ? 1 : 0) | (fp_is_zero(z1) ? 2 : 0);
+    }
+    __syncthreads();
+    const int pole = S.flag;                 // uniform over the workgroup
+    if (!pole) break;
+    if (threadIdx.x == 0) {                  // R0 <- the other map's point, Jacobian (X Z : Y Z^2 : Z), or the identity (0, 1, 0)
+      fp X, Y, Z, t;
+      if (pole == 3) {
+        fp_zero(X);
+        fp_one(Y);
+        fp_zero(Z);
+      } else {
+        uint32_t (*pt)[16] = &S.V[WPV_ISO + (pole == 1 ? WIDE_PT_ISO_STRIDE : 0) + WIDE_PT_ISO_PT];
+        w_load_local(X, pt[0]);
+        w_load_local(Y, pt[1]);
+        w_load_local(Z, pt[2]);
+        fp_mul(X, X, Z);
+        fp_sqr(t, Z);
+        fp_mul(Y, Y, t);
+      }
+      fp_reduce(X, X);
+      fp_reduce(Y, Y);
+      fp_reduce(Z, Z);
+      w_store_local(S.V[WPV_R0], X);
+      w_store_local(S.V[WPV_R0 + 1], Y);
+      w_store_local(S.V[WPV_R0 + 2], Z);
+    }
+    if (no_clear) {                          // the record takes R0 as it is
+      __syncthreads();
+      break;
+    }
+    wide_stage(S, WIDE_PROG_G1_CLEAR, WIDE_PROG_G1_CLEAR_LEN);     // R1 <- h_eff R0
+    __syncthreads();
+  }
   const int v = (int)(threadIdx.x >> 4);
   if (rec && v < 3) rec[i * WREC_WORDS + 16 * (WREC_P0 + v) + l] = S.V[res + v][l];
   if (out && threadIdx.x < 3) {
@@ -4403,6 +4500,7 @@ __device__ __forceinline__ void hash_g2_map_row(const uint32_t* ubw, int row, in
   pt[4][l] = (uint32_t)Z.c0.v;
   pt[5][l] = (uint32_t)Z.c1.v;
 }
+template <bool UB>
 __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g2_engine(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst,
                                                                        uint8_t* out, uint32_t* rec) {
   __shared__ wide_lds_t<wide_tb_pt> S;
@@ -4418,7 +4516,8 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g2_engine(size_t 
   if (wave == 0) {
     const size_t mi = (single_msg & 1) ? 0 : i;
     uint32_t ubw[64];
-    expand_message_xmd_wave<256>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk);   // the whole wave
+    if constexpr (UB) load_uniform_words_wave<64>(ubw, msgs, mi);
+    else expand_message_xmd_wave<256>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk);   // the whole wave
     if (row < 2) hash_g2_map_row(ubw, row, l, &S.V[row == 1 ? WPV_R1 : WPV_R0]);
   } else if (threadIdx.x < 64 + 4 * 16) {                   // meanwhile: psi's constants cx, cy (real, imaginary limbs)
     const int t = (int)threadIdx.x - 64, v = t >> 4;
@@ -4437,6 +4536,7 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g2_engine(size_t 
 }
 // The same in two launches for more messages than there are CUs: one WAVE per message for the maps (pts: twelve engine values
 // per message, the two points), then one workgroup per message for the engine program.
+template <bool UB>
 __global__ void __launch_bounds__(WIDE_BLOCK) k_hash_to_g2_maps(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst, uint32_t* pts) {
   __shared__ __attribute__((aligned(16))) uint8_t shablk[4][64];
   const int wave = threadIdx.x >> 6, row = (threadIdx.x >> 4) & 3, l = threadIdx.x & 15;
@@ -4446,9 +4546,16 @@ __global__ void __launch_bounds__(WIDE_BLOCK) k_hash_to_g2_maps(size_t n, const 
   if (i >= n) return;
   const size_t mi = (single_msg & 1) ? 0 : i;
   uint32_t ubw[64];
-  expand_message_xmd_wave<256>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk[wave]);
+  if constexpr (UB) load_uniform_words_wave<64>(ubw, msgs, mi);
+  else expand_message_xmd_wave<256>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk[wave]);
   if (row < 2) hash_g2_map_row(ubw, row, l, (uint32_t (*)[16])(pts + (i * 12 + 6 * row) * 16));
 }
+#endif  // BLS_TU_WIDE || BLS_TU_DEBUG_H2C_WIDE
+#if defined(BLS_TU_WIDE)
+template __global__ void k_hash_to_g1_wide<false>(size_t, const uint8_t*, const uint64_t*, int, dst_arg, uint8_t*, uint32_t*);
+template __global__ void k_hash_to_g1_engine<false>(size_t, const uint8_t*, const uint64_t*, int, dst_arg, uint8_t*, uint32_t*);
+template __global__ void k_hash_to_g2_engine<false>(size_t, const uint8_t*, const uint64_t*, int, dst_arg, uint8_t*, uint32_t*);
+template __global__ void k_hash_to_g2_maps<false>(size_t, const uint8_t*, const uint64_t*, int, dst_arg, uint32_t*);
 __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_g2_hash_tail_wide(size_t n, const uint32_t* pts, uint8_t* out, uint32_t* rec) {
   __shared__ wide_lds_t<wide_tb_pt> S;
   const size_t i = blockIdx.x;

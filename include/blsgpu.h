@@ -338,6 +338,23 @@ int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t
  * c4, c3, c5 (c0 then c1 of each, fourteen limbs each, reduced form).  status: an item that is not BLSGPU_OK is skipped and its
  * output left zero.  out_f12: n x twelve limb vectors in tower order.  Host pointers, n <= 4096. */
 int blsgpu_debug_millerf(const int32_t* lines, size_t n, const int32_t* status, int32_t* out_f12);
+/* Self-test hook of hash-to-curve behind expand_message_xmd (not part of the reference interface): the shipped kernels in their
+ * compile-time form that reads the uniform bytes from memory where the product expands a message, so that the field elements
+ * u0, u1 are the caller's choice (zero, equal, opposite, on a pole of the isogeny, at the edges of the 512-bit reduction).
+ * uniform: n x 128 bytes (group 1) or n x 256 bytes (group 2), what expand_message_xmd would have produced.  out: n RAW_PROJ
+ * points (Jacobian, Z = 0 for the identity).  uncleared = 1: the point before the cofactor clearing.  path: one kernel path;
+ * a (group, path, uncleared) triple that no launch of the library uses is BLSGPU_E_ARG:
+ *   group 1: LANE 0 / 1, PAIR 0 / 1, WIDE 0 / 1, WIDE_REC 1, ENGINE 0 / 1 (1: the cut check's record, program G1_HASH_MAP)
+ *   group 2: LANE 0, PAIR 0 / 1, PAIR_CLEAR_WIDE 0, ENGINE 0, MAPS_TAIL 0
+ * Host pointers, n <= 4096. */
+#define BLSGPU_H2C_LANE 0             /* k_hash_to_g1 / k_hash_to_g2, one lane per item (the form the prepare kernels call) */
+#define BLSGPU_H2C_PAIR 1             /* the same kernels, two lanes per item */
+#define BLSGPU_H2C_WIDE 2             /* k_hash_to_g1_wide: one wave per item, point through `out` */
+#define BLSGPU_H2C_ENGINE 3           /* k_hash_to_g1_engine / k_hash_to_g2_engine: one workgroup per item */
+#define BLSGPU_H2C_MAPS_TAIL 4        /* k_hash_to_g2_maps, then k_g2_hash_tail_wide */
+#define BLSGPU_H2C_WIDE_REC 5         /* k_hash_to_g1_wide writing the cut check's record (uncleared), converted to RAW_PROJ */
+#define BLSGPU_H2C_PAIR_CLEAR_WIDE 6  /* k_hash_to_g2 on lane pairs without the clearing, then k_g2_clear_wide */
+int blsgpu_debug_map_to_curve(int group, int path, int uncleared, const uint8_t* uniform, size_t n, void* out);
 /* Self-test hook of the wave-cooperative pairing kernels (not part of the reference interface): the shipped kernels, launched as
  * the verify path launches them, on caller-supplied pairs.  pairs: n x twelve limb vectors in reduced form -- P.x, P.y, Q.x.c0,
  * Q.x.c1, Q.y.c0, Q.y.c1 of pair 0, then of pair 1 (affine; nothing is checked, the points need not lie in the subgroups).

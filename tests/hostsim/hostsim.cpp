@@ -158,6 +158,23 @@ void hs_hash_to_g2(const uint8_t* msg, uint32_t len, const uint8_t* dst, uint32_
   jac_to_aff(a, h);
   g2_compress(out96, a, false);
 }
+// hash-to-curve behind expand_message_xmd, the one-lane forms (h2c.cuh hash_to_g1_map / hash_to_g2_map), on caller-chosen uniform bytes
+// (128 for group 1, 256 for group 2): the host twin of blsgpu_debug_map_to_curve.  out: the point as RAW_PROJ words (36 / 72; Jacobian,
+// Z = 0 for the identity).  The bound tracker proves every case inside the contracts of fp_set_words / fp_mul on the way.
+void hs_map_to_curve(int group, const uint8_t* uniform, int no_clear, uint32_t* out) {
+  uint32_t w[64];
+  for (int i = 0; i < (group == 1 ? 32 : 64); i++) w[i] = be32_at(uniform + 4 * i);
+  if (group == 1) {
+    g1_jac h;
+    hash_to_g1_map(h, w, -1, no_clear != 0);
+    fp_to_raw(out, h.x); fp_to_raw(out + 12, h.y); fp_to_raw(out + 24, h.z);
+  } else {
+    g2_jac h;
+    hash_to_g2_map(h, w, -1, no_clear != 0);
+    fp_to_raw(out, h.x.c0); fp_to_raw(out + 12, h.x.c1); fp_to_raw(out + 24, h.y.c0); fp_to_raw(out + 36, h.y.c1);
+    fp_to_raw(out + 48, h.z.c0); fp_to_raw(out + 60, h.z.c1);
+  }
+}
 // k * P for raw Jacobian inputs; compressed outputs.  also P + Q
 void hs_g1_mul_add(const uint32_t* p, const uint32_t* q, const uint32_t* k, uint8_t* out_mul, uint8_t* out_add, int legacy) {
   g1_jac a, b, r; g1_aff f;

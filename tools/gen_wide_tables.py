@@ -1253,6 +1253,8 @@ def emit(path):
     emit_set(out, OPS_PT, lay_pt, PROGRAMS_PT, 'WIDE_PT', 'WPV', 'wide_tb_pt', False)
     out.append('#define WIDE_PT_ISO_STRIDE %d   // values per mapped point in array ISO (x\' = xn / xd at 0, 1; y at 2)' % ISO_STRIDE)
     out.append('#define WIDE_PT_ISO_K %d        // first isogeny coefficient in array CONST' % ISO_K)
+    out.append('#define WIDE_PT_ISO_ZX %d      // zx = XD xd of a mapped point: zero exactly on a pole of the isogeny' % ISO_ZX)
+    out.append('#define WIDE_PT_ISO_PT %d      // the mapped point on E1, homogeneous (X : Y : Z), three values' % ISO_PT)
     out.append('#define WIDE_PT_SLOT_G1 %d' % G1S)
     out.append('#define WIDE_PT_SLOT_G2 %d' % G2S)
     open(path, 'w').write('\n'.join(out) + '\n')
