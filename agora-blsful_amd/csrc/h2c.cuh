@@ -329,8 +329,15 @@ BLS_FN void fp_from_be64(fp& r, const uint8_t* b) {
 
 // ------------------------------------------------------------------ G1: simplified SWU (RFC 9380 F.2, straight line)
 // returns x = xn/xd and y on E'1.  F = fp (one lane) or wf (one DPP row, csrc/wide.cuh: the single-item latency path)
-template <class F>
-BLS_NOINLINE void sswu_g1(F& xn, F& xd, F& y, const F& u) {
+// INV: also xinv = 1 / xd, out of the square-root chain.  The chain raises w = gx1 gxd^3 (gx1 the numerator of g(x1), gxd = xd^3) to
+// (p - 3) / 4, and c = w^((p-3)/4) has c^2 = w^((p-3)/2) = chi(w) / w with chi the quadratic character -- the is_qr of the map, as
+// gx1 gxd^3 and gx1 / gxd differ by the square gxd^4.  So 1 / xd = chi c^2 gx1 xd^8: one squaring and three multiplications, chi
+// applied as a conditional negation.  w is never zero: xd is not by construction, and gx1 = 0 would put a point of order 2 on E'1,
+// which is isogenous to E1 of odd order h r.  gx1 xd^8 is formed BEFORE the chain, where xd^2 and xd^6 exist anyway, and waits for
+// it in the caller's second output, which takes 1 / xd INSTEAD of xd (sswu_g1_inv): neither this function's frame nor the caller's
+// keeps one value more than before.
+template <class F, bool INV>
+BLS_FN void sswu_g1_body(F& xn, F& xd, F& y, const F& u) {
   F A, B, Z, tv1, tv2, tv3, tv4, tv5, tv6, x, y1, t;
   fp_load(A, SSWU1_A);
   fp_load(B, SSWU1_B);
@@ -350,6 +357,8 @@ BLS_NOINLINE void sswu_g1(F& xn, F& xd, F& y, const F& u) {
   fp_mul(tv5, A, tv6);
   fp_add(tv2, tv2, tv5);
   fp_mul(tv2, tv2, tv3);
+  F xd2;
+  if constexpr (INV) xd2 = tv6;
   fp_mul(tv6, tv6, tv4);
   fp_mul(tv5, B, tv6);
   fp_add(tv2, tv2, tv5);
@@ -358,8 +367,16 @@ BLS_NOINLINE void sswu_g1(F& xn, F& xd, F& y, const F& u) {
   F s1, s2, s3, y2, c2;
   fp_sqr(s1, tv6);
   fp_mul(s2, tv2, tv6);
+  if constexpr (INV) {
+    fp_mul(t, s1, xd2);             // xd^8
+    fp_mul(xd, t, tv2);             // gx1 xd^8
+  }
   fp_mul(s1, s1, s2);
   fp_pow(y1, s1, EXP_PM3D4, EXP_PM3D4_BITS);
+  if constexpr (INV) {
+    fp_sqr(t, y1);                  // chi(w) / w
+    fp_mul(xd, xd, t);
+  }
   fp_mul(y1, y1, s2);
   fp_load(c2, SSWU1_C2);
   fp_mul(y2, y1, c2);
@@ -374,58 +391,85 @@ BLS_NOINLINE void sswu_g1(F& xn, F& xd, F& y, const F& u) {
   F ny;
   fp_neg(ny, y);
   fp_cmov(y, ny, fp_parity(u) != fp_parity(y));
+  if constexpr (INV) {
+    fp_neg(ny, xd);
+    fp_cmov(xd, ny, !is_qr);
+  } else {
+    xd = tv4;
+  }
   xn = x;
-  xd = tv4;
 }
+template <class F>
+BLS_NOINLINE void sswu_g1(F& xn, F& xd, F& y, const F& u) { sswu_g1_body<F, false>(xn, xd, y, u); }
+BLS_NOINLINE void sswu_g1_inv(fp& xn, fp& xinv, fp& y, const fp& u) { sswu_g1_body<fp, true>(xn, xinv, y, u); }
 
-// The four polynomials of the 11-isogeny E'1 -> E1 in homogenised Horner form, sum_i k_i xn^i xd^(D-i), evaluated IN LOCKSTEP over one
-// running power xd^j (round 4): acc_q <- acc_q xn + k_q[D_q - j] xd^j for every polynomial of degree D_q >= j.  The same 15 + 2 x 51
-// multiplications as with a table of the sixteen powers, but the table was 896 bytes of scratch per lane read through a run-time index (14 loads in
-// front of every second multiplication) -- the largest frame of the k_prepare<1> / k_prepare_agg<1> / k_hash_to_g1 family, whose waves wait
-// twice as long as the other kernels' (profiles/r04_pmc_default.json).
-BLS_NOINLINE void iso_map_g1(g1_jac& r, const fp& xn, const fp& xd, const fp& y) {
-  fp XN, XD, YN, YD, pw, c, t;
+// The four polynomials of the 11-isogeny E'1 -> E1 at an AFFINE x (sswu_g1 hands out 1 / xd from its square-root chain, so x = xn / xd
+// costs five multiplications): plain Horner, acc_q <- acc_q x + k_q[i], 11 + 9 + 15 + 14 = 49 multiplications where the homogenised
+// form sum_i k_i xn^i xd^(D-i) took 15 for the running power of xd and 2 x 51.  The two denominators are monic (asserted where the
+// constants are generated, tools/gen_consts.py, and by iso1_monic_check below in every host build), so their first step is the
+// addition x + k[D-1].  The four chains are independent and advance in lockstep, one step of each per round: the multiplier always
+// has independent work, and with static coefficient addresses (the loop is unrolled) the constants' loads are issued ahead of the
+// products instead of one exposed latency per term.  An accumulator is a product plus one constant when it enters the next product:
+// limbs below 2^29, no carry pass.
+// Output: Jacobian, (X, Y, Z) = (XN XD YD^2, y YN XD^3 YD^2, XD YD).  At a pole -- x a root of the x-denominator, sixteen values of u --
+// XD = 0 and the point is Z = 0, the identity (RFC 9380 6.6.3).
+BLS_NOINLINE void iso_map_g1(g1_jac& r, const fp& x, const fp& y) {
+  fp XN, XD, YN, YD, c;
   fp_load(XN, ISO1_XNUM[11]);
-  fp_load(XD, ISO1_XDEN[10]);
   fp_load(YN, ISO1_YNUM[15]);
-  fp_load(YD, ISO1_YDEN[15]);
-  pw = xd;
-#pragma unroll          // static coefficient addresses: their loads are issued ahead of the multiplications instead of one exposed latency per term
+#pragma unroll
   for (int j = 1; j <= 15; j++) {
-    if (j > 1) fp_mul(pw, pw, xd);
     if (j <= 11) {
-      fp_mul(XN, XN, xn);
+      fp_mul(XN, XN, x);
       fp_load(c, ISO1_XNUM[11 - j]);
-      fp_mul(t, c, pw);
-      fp_add(XN, XN, t);
+      fp_add(XN, XN, c);
     }
     if (j <= 10) {
-      fp_mul(XD, XD, xn);
       fp_load(c, ISO1_XDEN[10 - j]);
-      fp_mul(t, c, pw);
-      fp_add(XD, XD, t);
+      if (j == 1) {
+        fp_add(XD, x, c);
+      } else {
+        fp_mul(XD, XD, x);
+        fp_add(XD, XD, c);
+      }
     }
-    fp_mul(YN, YN, xn);
+    fp_mul(YN, YN, x);
     fp_load(c, ISO1_YNUM[15 - j]);
-    fp_mul(t, c, pw);
-    fp_add(YN, YN, t);
-    fp_mul(YD, YD, xn);
+    fp_add(YN, YN, c);
     fp_load(c, ISO1_YDEN[15 - j]);
-    fp_mul(t, c, pw);
-    fp_add(YD, YD, t);
+    if (j == 1) {
+      fp_add(YD, x, c);
+    } else {
+      fp_mul(YD, YD, x);
+      fp_add(YD, YD, c);
+    }
   }
-  fp zx, yd2;
-  fp_mul(zx, XD, xd);     // x_out = XN / zx,  y_out = y YN / YD
-  fp_mul(r.z, zx, YD);    // Z = zx YD
+  fp t, yd2;
+  fp_mul(r.z, XD, YD);    // x_out = XN / XD,  y_out = y YN / YD,  Z = XD YD
   fp_sqr(yd2, YD);
-  fp_mul(t, XN, zx);
-  fp_mul(r.x, t, yd2);    // X = XN zx YD^2
-  fp_sqr(t, zx);
-  fp_mul(t, t, zx);
+  fp_mul(t, XN, XD);
+  fp_mul(r.x, t, yd2);    // X = XN XD YD^2
+  fp_sqr(t, XD);
+  fp_mul(t, t, XD);
   fp_mul(t, t, yd2);
   fp_mul(t, t, YN);
-  fp_mul(r.y, t, y);      // Y = y YN zx^3 YD^2
+  fp_mul(r.y, t, y);      // Y = y YN XD^3 YD^2
 }
+#if !defined(__HIPCC__)
+#include <stdio.h>
+#include <stdlib.h>
+// host builds (tests/hostsim and its siblings), once at load time: the leading coefficients that iso_map_g1 takes as additions are
+// the Montgomery one
+static bool iso1_monic_check() {
+  for (int i = 0; i < FP_NL; i++)
+    if (ISO1_XDEN[10][i] != FP_ONE[i] || ISO1_YDEN[15][i] != FP_ONE[i]) {
+      fprintf(stderr, "h2c.cuh: the x- and y-denominators of the 11-isogeny must be monic\n");
+      abort();
+    }
+  return true;
+}
+static const bool ISO1_MONIC_CHECKED = iso1_monic_check();
+#endif
 
 // lane2 >= 0 (device only, latency mode for single verifications): the item occupies two adjacent lanes, lane2 = 0 / 1 maps
 // u0 / u1 and the two points are exchanged by DPP, so the two SSWU maps -- half of the hash -- run side by side; both lanes
@@ -501,8 +545,9 @@ BLS_FN void hash_to_g1_map(g1_jac& r, const uint32_t* ub, int lane2, bool no_cle
   if (lane2 >= 0) {
     g1_jac mine, other;
     fp_from_be64_words(u0, ub + 16 * lane2);
-    sswu_g1(xn, xd, y, u0);
-    iso_map_g1(mine, xn, xd, y);
+    sswu_g1_inv(xn, xd, y, u0);
+    fp_mul(xn, xn, xd);             // x = xn / xd
+    iso_map_g1(mine, xn, y);
     fp_lane_swap(other.x, mine.x);
     fp_lane_swap(other.y, mine.y);
     fp_lane_swap(other.z, mine.z);
@@ -514,10 +559,12 @@ BLS_FN void hash_to_g1_map(g1_jac& r, const uint32_t* ub, int lane2, bool no_cle
     (void)lane2;
     fp_from_be64_words(u0, ub);
     fp_from_be64_words(u1, ub + 16);
-    sswu_g1(xn, xd, y, u0);
-    iso_map_g1(q0, xn, xd, y);
-    sswu_g1(xn, xd, y, u1);
-    iso_map_g1(q1, xn, xd, y);
+    sswu_g1_inv(xn, xd, y, u0);
+    fp_mul(xn, xn, xd);             // x = xn / xd
+    iso_map_g1(q0, xn, y);
+    sswu_g1_inv(xn, xd, y, u1);
+    fp_mul(xn, xn, xd);
+    iso_map_g1(q1, xn, y);
   }
   jac_add(q0, q0, q1);
   if (no_clear) {
