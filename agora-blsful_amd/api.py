@@ -53,6 +53,8 @@ EXPORTS = [
     'blsgpu_verify_shared_batch', 'blsgpu_verify_shared_indexed_batch',
     'blsgpu_aggregate_verify_indexed_batch',
     'blsgpu_hash_to_scalar', 'blsgpu_sig_proof_challenge_batch', 'blsgpu_sig_proof_timestamp_verify_batch',
+    'blsgpu_msgset_create', 'blsgpu_msgset_destroy', 'blsgpu_msgset_info', 'blsgpu_msgset_update', 'blsgpu_msgset_append',
+    'blsgpu_verify_msgset_batch', 'blsgpu_verify_msgset_indexed_batch', 'blsgpu_debug_msgset_from_points', 'blsgpu_debug_coop_pairing_rows',
 ]
 
 
@@ -203,6 +205,15 @@ def load_library(path=None):
         lib.blsgpu_hash_to_scalar.argtypes = [u8p, u64p, sz, u8p, sz, u8p]
         lib.blsgpu_sig_proof_challenge_batch.argtypes = [ci, vp, u64p, sz, ci, u8p]
         lib.blsgpu_sig_proof_timestamp_verify_batch.argtypes = [ci, ci, vp, vp, vp, u64p, u8p, u64p, sz, ci, ctypes.c_uint64, ctypes.c_int64, i32p]
+        lib.blsgpu_msgset_create.argtypes = [ci, ci, u8p, u64p, sz, ci, ctypes.POINTER(h)]
+        lib.blsgpu_msgset_destroy.argtypes = [h]
+        lib.blsgpu_msgset_info.argtypes = [h, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(h), ctypes.POINTER(ci), ctypes.POINTER(h)]
+        lib.blsgpu_msgset_update.argtypes = [h, u32p, u8p, u64p, sz]
+        lib.blsgpu_msgset_append.argtypes = [h, u8p, u64p, sz, ctypes.POINTER(h)]
+        lib.blsgpu_verify_msgset_batch.argtypes = [h, u32p, vp, vp, u64p, sz, ci, i32p]
+        lib.blsgpu_verify_msgset_indexed_batch.argtypes = [h, u32p, h, u32p, vp, u64p, sz, ci, i32p]
+        lib.blsgpu_debug_msgset_from_points.argtypes = [ci, vp, sz, ci, ctypes.POINTER(h)]
+        lib.blsgpu_debug_coop_pairing_rows.argtypes = [ci, h, u32p, i32p, sz, i32p, i32p]
         _lib = lib
     return _lib
 
@@ -985,6 +996,109 @@ def verify_shared_indexed_batch(keyset, scheme, groups, fmt=FMT_RAW_PROJ):
     return [flat[ioffs[g]:ioffs[g + 1]] for g in range(n_groups)]
 
 
+MSGSET_LINES = 1    # Bls12381G2Impl: every message point's Miller-loop rows, read above BLSGPU_WIDE_MAX items
+
+
+class MessageSet:
+    """A table of hashed messages that stays on the device (blsgpu_msgset_*): every message is hashed once, under the scheme's DST, and
+    later named by position in verify_msgset_batch / verify_msgset_indexed_batch.  update() replaces entries and append() adds
+    entries in place; afterwards the set is what create() gives for the final message list.  Neither they nor close() (or leaving
+    the `with` block, which releases the device memory) take a lock against readers: none of the three may run while another
+    thread's call still uses the set."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    @classmethod
+    def create(cls, sig_group, scheme, msgs, lines=False):
+        """`msgs`: a list of byte strings (empty ones and an empty list are fine); scheme BASIC or POP (AUG raises: it hashes
+        pk || m, so there is nothing to register).  lines: the per-entry line rows (MSGSET_LINES; built for sig_group 2 only).
+        info() says what was built."""
+        offs, blob = _offsets([bytes(m) for m in msgs])
+        h = ctypes.c_uint64(0)
+        _check(init().blsgpu_msgset_create(sig_group, scheme, _ptr(blob) if blob else None, ctypes.cast(offs, ctypes.c_void_p), len(msgs),
+                                           MSGSET_LINES if lines else 0, ctypes.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def create_device(cls, sig_group, scheme, msgs_ptr, offs_ptr, n, lines=False):
+        """From n messages already on the device (integer addresses of the bytes and of the n + 1 uint64 offsets)."""
+        h = ctypes.c_uint64(0)
+        _check(init().blsgpu_msgset_create(sig_group, scheme, ctypes.c_void_p(msgs_ptr), ctypes.c_void_p(offs_ptr), n, MSGSET_LINES if lines else 0,
+                                           ctypes.byref(h)))
+        return cls(h.value)
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, 0
+            _check(_lib.blsgpu_msgset_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def info(self):
+        """dict(sig_group, scheme, n, has_lines, device_bytes)"""
+        sg, sc, hl, n, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(init().blsgpu_msgset_info(self.handle, ctypes.byref(sg), ctypes.byref(sc), ctypes.byref(n), ctypes.byref(hl), ctypes.byref(b)))
+        return {'sig_group': sg.value, 'scheme': sc.value, 'n': n.value, 'has_lines': bool(hl.value), 'device_bytes': b.value}
+
+    def update(self, pos, msgs):
+        """Entry pos[i] becomes the hash of msgs[i]: the named entries' points and rows are rewritten, nothing else.  A position
+        outside the set or named twice raises, and nothing is written."""
+        if len(msgs) != len(pos):
+            raise ValueError('one message per position')
+        offs, blob = _offsets([bytes(m) for m in msgs])
+        _check(init().blsgpu_msgset_update(self.handle, ctypes.cast(_u32(pos), ctypes.c_void_p), _ptr(blob) if blob else None,
+                                           ctypes.cast(offs, ctypes.c_void_p), len(pos)))
+
+    def append(self, msgs):
+        """The set grows by `msgs`; returns the first new position.  Rows the grown set has no room for are dropped: see info()."""
+        offs, blob = _offsets([bytes(m) for m in msgs])
+        first = ctypes.c_uint64(0)
+        _check(init().blsgpu_msgset_append(self.handle, _ptr(blob) if blob else None, ctypes.cast(offs, ctypes.c_void_p), len(msgs), ctypes.byref(first)))
+        return first.value
+
+
+def verify_msgset_batch(msgset, groups, fmt=FMT_RAW_PROJ):
+    """verify_shared_batch with the messages named by position: `groups` is a list of (msg_idx, pks, sigs), msg_idx a position in
+    `msgset`.  One list of statuses per group: E_ARG in every slot of a group whose index lies outside the set, else what
+    verify_shared_batch gives under the entry's message.  Nothing is hashed."""
+    n_groups = len(groups)
+    ioffs = _count_offsets([g[1] for g in groups])
+    if any(len(g[1]) != len(g[2]) for g in groups):
+        raise ValueError('one signature per key')
+    n = ioffs[n_groups]
+    pkb, sgb = b''.join(p for g in groups for p in g[1]), b''.join(s for g in groups for s in g[2])
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(init().blsgpu_verify_msgset_batch(msgset.handle, ctypes.cast(_u32([g[0] for g in groups]), ctypes.c_void_p), _ptr(pkb), _ptr(sgb),
+                                             ctypes.cast(ioffs, ctypes.c_void_p), n_groups, fmt, ctypes.cast(st, ctypes.c_void_p)))
+    flat = list(st)[:n]
+    return [flat[ioffs[g]:ioffs[g + 1]] for g in range(n_groups)]
+
+
+def verify_msgset_indexed_batch(msgset, keyset, groups, fmt=FMT_RAW_PROJ):
+    """verify_msgset_batch with the keys named by position too: `groups` is a list of (msg_idx, idx, sigs), idx a list of positions
+    in `keyset`.  Per item: E_ARG for a message index outside the message set, then E_ARG for a position outside the key set, then
+    the creation status of an invalid entry, else what verify_shared_batch gives."""
+    n_groups = len(groups)
+    ioffs = _count_offsets([g[1] for g in groups])
+    if any(len(g[1]) != len(g[2]) for g in groups):
+        raise ValueError('one signature per position')
+    n = ioffs[n_groups]
+    idx = _u32([i for g in groups for i in g[1]])
+    sgb = b''.join(s for g in groups for s in g[2])
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(init().blsgpu_verify_msgset_indexed_batch(msgset.handle, ctypes.cast(_u32([g[0] for g in groups]), ctypes.c_void_p), keyset.handle,
+                                                     ctypes.cast(idx, ctypes.c_void_p), _ptr(sgb), ctypes.cast(ioffs, ctypes.c_void_p), n_groups, fmt,
+                                                     ctypes.cast(st, ctypes.c_void_p)))
+    flat = list(st)[:n]
+    return [flat[ioffs[g]:ioffs[g + 1]] for g in range(n_groups)]
+
+
 def combine_shares(group, sets, fmt=FMT_RAW_PROJ):
     """Threshold recovery of many independent sets in one call (blsgpu_combine_shares): `sets` is a list of lists of
     (identifier: int, raw point, scheme or None).  Scheme tags are checked only when every share of the call carries one
@@ -1254,6 +1368,39 @@ def debug_coop_pairing_keyed(mode, keyset, idx, items, status=None):
     out = (ctypes.c_int32 * max(168 * n, 1))()
     _check(lib.blsgpu_debug_coop_pairing_keyed(mode, keyset.handle, ctypes.cast(_u32(idx), ctypes.c_void_p), ctypes.cast(arr, ctypes.c_void_p), n,
                                                ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+    if mode != 0:
+        return list(st[:n])
+    o = list(out)
+    return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n)]
+
+
+def debug_msgset_from_points(sig_group, points, lines=False):
+    """A MessageSet (scheme BASIC) whose entries are the given RAW_AFFINE points (byte strings of 96 * sig_group bytes) instead of hash
+    outputs: crafted G2 points for the rows of debug_coop_pairing_rows.  Nothing is checked."""
+    blob = b''.join(points)
+    h = ctypes.c_uint64(0)
+    _check(init().blsgpu_debug_msgset_from_points(sig_group, _ptr(blob) if blob else None, len(points), MSGSET_LINES if lines else 0, ctypes.byref(h)))
+    return MessageSet(h.value)
+
+
+def debug_coop_pairing_rows(mode, msgset, msg_of, items, status=None):
+    """k_pairing_coop_rows on caller-supplied operands: the records of debug_coop_pairing with fixed_g2 = 0, pair 0's G2 member being
+    entry msg_of[i] of `msgset` (a Bls12381G2Impl MessageSet with rows; the record's own pair-0 Q is not read).  mode 0 returns per item
+    the twelve limb vectors of the easy-part value in tower order (every limb COOP_SENTINEL for an item whose status is not OK), mode 1
+    the statuses.  A set without rows, an index outside the set and more than 4,096 items raise (BLSGPU_E_ARG)."""
+    lib = init()
+    n = len(items)
+    assert len(msg_of) == n
+    flat = []
+    for vecs in items:
+        assert len(vecs) == 12 and all(len(v) == 14 for v in vecs)
+        for v in vecs:
+            flat += v
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
+    out = (ctypes.c_int32 * max(168 * n, 1))()
+    _check(lib.blsgpu_debug_coop_pairing_rows(mode, msgset.handle, ctypes.cast(_u32(msg_of), ctypes.c_void_p), ctypes.cast(arr, ctypes.c_void_p), n,
+                                              ctypes.cast(st, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
     if mode != 0:
         return list(st[:n])
     o = list(out)
@@ -1548,6 +1695,24 @@ class TensorOps:
         st = self.empty(max(n, 1), self.torch.int32)
         _check(self.lib.blsgpu_verify_shared_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(sigs), self._p(item_offs), n_groups, self._p(msgs),
                                                            self._p(msg_offs), FMT_RAW_PROJ, self._p(st)))
+        return st[:n]
+
+    def verify_msgset_batch(self, msgset, msg_idx, pks, sigs, item_offs, n_groups, n):
+        """int32 statuses (on the device), one per item, of Signature::verify over n_groups groups whose messages are entries of
+        `msgset`: msg_idx an int32 tensor whose bits are the uint32 positions (one per group), flat device-resident keys and
+        signatures with int64 item_offs (n_groups + 1 entries)."""
+        self._sync()
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_verify_msgset_batch(msgset.handle, self._p(msg_idx), self._p(pks), self._p(sigs), self._p(item_offs), n_groups, FMT_RAW_PROJ,
+                                                   self._p(st)))
+        return st[:n]
+
+    def verify_msgset_indexed_batch(self, msgset, msg_idx, keyset, idx, sigs, item_offs, n_groups, n):
+        """the same with item i's key at position idx[i] of `keyset` (idx: an int32 tensor whose bits are the uint32 positions)."""
+        self._sync()
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_verify_msgset_indexed_batch(msgset.handle, self._p(msg_idx), keyset.handle, self._p(idx), self._p(sigs), self._p(item_offs),
+                                                           n_groups, FMT_RAW_PROJ, self._p(st)))
         return st[:n]
 
     def keyset_get(self, keyset, key_group, idx, n, fmt=FMT_RAW_PROJ):

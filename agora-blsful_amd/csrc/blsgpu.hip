@@ -25,6 +25,7 @@
 #include "signcrypt.cuh"
 #include "elgamal.cuh"
 #include "verify_shared.cuh"
+#include "msgset.cuh"
 #include "hkdf.cuh"
 #include "debug_ops.h"
 #include "host_sha256.h"
@@ -57,6 +58,8 @@ enum {
   KID_KEYSET_SEAL_AT, KID_KEYSET_BUILD_AT, KID_KEYSET_LINES_AT,   // blsgpu_keyset_update / blsgpu_keyset_append: the positional forms of seal, build, lines
   KID_PAIRING_COOP_KEYED,                // the one-wave pairing that reads a registered key's rows (in the place of k_pairing_coop)
   KID_HASH_TO_SCALAR, KID_PROOF_CHALLENGE, KID_PROOF_TIMEOUT,   // blsgpu_hash_to_scalar, blsgpu_sig_proof_challenge_batch / _timestamp_verify_batch (hkdf.cuh)
+  KID_MSGSET_SEAL, KID_MSGSET_CHECK,     // registered message sets (msgset.cuh; k_msgset_mark counts under k_msgset_check, the rows' build under k_keyset_lines[_at])
+  KID_PAIRING_COOP_ROWS,                 // the one-wave pairing that reads a registered message's rows (in the place of k_pairing_coop)
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -77,7 +80,9 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_linesp_keyed",
                                     "k_keyset_seal_at", "k_keyset_build_at", "k_keyset_lines_at",
                                     "k_pairing_coop_keyed",
-                                    "k_hash_to_scalar", "k_proof_challenge", "k_proof_timeout"};
+                                    "k_hash_to_scalar", "k_proof_challenge", "k_proof_timeout",
+                                    "k_msgset_seal", "k_msgset_check",
+                                    "k_pairing_coop_rows"};
 
 struct Ctx {
   int dev = -1;
@@ -773,8 +778,12 @@ void launch_finalexp_chunk(Ctx* c, size_t n, size_t first, size_t cnt, const uin
 // rows are in key_table (keyset.cuh).  On the lane-split path the chunk's line launch reads both rows and walks nothing
 // (k_lines2s_keyed); on the one-wave path k_pairing_coop_keyed runs the Miller loop of two tabled pairs (coop.cuh
 // coop_miller2_tables).  The row-wide engine and the BLSGPU_WIDE_MODE=1 branch ignore them.
+// ms_rows / ms_of (fixed_g2 = 0, registered message sets with rows, Bls12381G2Impl; records in their usual pair order): on the one-wave
+// path pair 0's G2 member is entry ms_of[i] of a set whose rows are in ms_rows, and k_pairing_coop_rows reads them while it walks the
+// signature (coop_rows.cuh).  Every other path ignores them (the lane-split path takes such a set as sh_table / sh_group).
 int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2, const uint32_t* sh_table = nullptr,
-                 const uint32_t* sh_group = nullptr, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
+                 const uint32_t* sh_group = nullptr, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr,
+                 const uint32_t* ms_rows = nullptr, const uint32_t* ms_of = nullptr) {
   if (n <= wide_max_items() && n <= coop_max_items()) {
     // single verifications and the one-verdict tails on the row-wide engine (csrc/wide_engine.cuh): one 256-thread workgroup
     // per item runs line coefficients, Miller loop, final exponentiation and verdict as one table program.
@@ -790,6 +799,8 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
   } else if (n <= coop_max_items()) {  // small batches: one wave per item
     if (fixed_g2 == 2 && key_table)
       KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, key_table, key_of, (uint32_t*)nullptr);
+    else if (fixed_g2 == 0 && ms_rows)
+      KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, ms_rows, ms_of, (uint32_t*)nullptr);
     else
       KL(KID_PAIRING_COOP, k_pairing_coop, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, fixed_g2);
   } else {                      // two lanes per item (tower_split.cuh)
@@ -1847,6 +1858,43 @@ void keyset_publish(uint64_t handle, const KeySet& k) {
   auto it = g_keysets.find(handle);
   if (it != g_keysets.end()) it->second = k;
 }
+// ---- registered message sets (msgset.cuh): the same registry rules.  Ids come from the key sets' counter, so a handle of one kind
+// is never found as the other.
+struct MsgSet {
+  int sig_group = 0, scheme = 0;
+  int flags = 0;                      // BLSGPU_MSGSET_* the creator asked for
+  size_t n = 0, devidx = 0;
+  int dev = -1;
+  uint8_t* aff = nullptr;             // RAW_AFFINE records of the hashed messages (group sig_group)
+  uint32_t* lines = nullptr;          // their rows (Bls12381G2Impl, BLSGPU_MSGSET_LINES; or none) ...
+  int32_t* nolines = nullptr;         // ... and per entry 0 or KEYSET_NOLINES_*
+  uint64_t bytes = 0;
+};
+std::unordered_map<uint64_t, MsgSet> g_msgsets;       // under g_keyset_mu
+void msgset_free(MsgSet& m) {
+  if (m.dev >= 0) (void)hipSetDevice(m.dev);
+  for (void* p : {(void*)m.aff, (void*)m.lines, (void*)m.nolines})
+    if (p) (void)hipFree(p);
+  m = MsgSet();
+}
+void msgset_release_all() {
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  for (auto& kv : g_msgsets) msgset_free(kv.second);
+  g_msgsets.clear();
+}
+int msgset_find(uint64_t handle, MsgSet& m) {
+  if (!initialised()) return NOT_INIT();
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  auto it = g_msgsets.find(handle);
+  if (handle == 0 || it == g_msgsets.end()) return fail(BLSGPU_E_ARG, "unknown message set handle (never issued, or destroyed)");
+  m = it->second;
+  return 0;
+}
+void msgset_publish(uint64_t handle, const MsgSet& m) {
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  auto it = g_msgsets.find(handle);
+  if (it != g_msgsets.end()) it->second = m;
+}
 template <int G>
 size_t keyset_table_bytes_g(size_t n) { return n * (size_t)keyset_shape<G>::POINTS * 2 * G * FP_NL * 4; }
 size_t keyset_table_bytes(int group, size_t n) { return group == 1 ? keyset_table_bytes_g<1>(n) : keyset_table_bytes_g<2>(n); }
@@ -2025,6 +2073,7 @@ void blsgpu_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_init_mu);
   if (!initialised()) return;
   keyset_release_all();
+  msgset_release_all();
   release_devices();
 }
 
@@ -6223,6 +6272,434 @@ int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* i
   HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
   KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)k.lines,
      (const uint32_t*)d_idx, d_easy);
+  HIPCK(hipGetLastError());
+  std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
+  HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));
+  // the engine's value layout -> tower order, fourteen limbs each, as blsgpu_debug_coop_pairing
+  for (size_t i = 0; i < n; i++)
+    for (size_t kk = 0; kk < 6; kk++) {
+      const size_t pw = kk < 3 ? 2 * kk : 2 * (kk - 3) + 1;
+      for (size_t comp = 0; comp < 2; comp++)
+        for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * kk + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
+    }
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+// =========================================================================================================
+// Registered message sets (msgset.cuh): a table of HASHED messages that stays on the device, groups named by positions in it
+static int msgset_kind_check(int sig_group, int scheme) {
+  if (sig_group != 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "sig_group must be 1 (Bls12381G1Impl) or 2 (Bls12381G2Impl)");
+  if (scheme != BLSGPU_SCHEME_BASIC && scheme != BLSGPU_SCHEME_POP)
+    return fail(BLSGPU_E_ARG, "a message set is Basic or ProofOfPossession: MessageAugmentation hashes pk || m, so there is nothing to register");
+  return 0;
+}
+static size_t msgset_rec_bytes(const MsgSet& m) { return point_bytes(m.sig_group, BLSGPU_FMT_RAW_AFFINE); }
+static uint64_t msgset_bytes(const MsgSet& m) { return (uint64_t)msgset_rec_bytes(m) * m.n + (m.lines ? m.n * (uint64_t)(MSGSET_ENTRY_LINE_BYTES + 4) : 0); }
+// the rows of a whole set (Bls12381G2Impl), as keyset_build_lines builds a key set's: chunks of 4,096 entries; leaves m.lines null (and
+// the set without rows) when the size rule (keyset_lines_fit: the 32-bit offset of the kernels that read them, and the cap of
+// BLSGPU_KEYSET_TABLE_MB) or the device's memory says no
+static int msgset_build_lines(Ctx* c, MsgSet& m) {
+  if (m.sig_group != 2 || !keyset_lines_fit(m.n, 0, (uint64_t)knobs().keyset_table_mb)) return 0;
+  const size_t lb = m.n * (size_t)MSGSET_ENTRY_LINE_BYTES, chunk = std::min<size_t>(m.n, 4096);
+  uint32_t *lines = nullptr, *scratch = nullptr;
+  int32_t* nolines = nullptr;
+  if (hipMalloc((void**)&lines, lb) != hipSuccess || hipMalloc((void**)&scratch, chunk * (size_t)MSGSET_ENTRY_LINE_BYTES) != hipSuccess ||
+      hipMalloc((void**)&nolines, 4 * m.n) != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)lines, (void*)scratch, (void*)nolines})
+      if (p) (void)hipFree(p);
+    return 0;
+  }
+  for (size_t k0 = 0; k0 < m.n; k0 += chunk) {
+    const size_t cnt = std::min(chunk, m.n - k0);
+    KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), k0, cnt, (const uint8_t*)m.aff, lines, scratch, nolines);
+  }
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(scratch);
+  if (e1 != hipSuccess || e2 != hipSuccess) {
+    (void)hipFree(lines);
+    (void)hipFree(nolines);
+    return fail(BLSGPU_E_HIP, std::string("k_keyset_lines: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+  }
+  m.lines = lines;
+  m.nolines = nolines;
+  m.bytes = msgset_bytes(m);
+  return 0;
+}
+// `count` messages become the entries h_pos[0 .. count) of m (positions the caller has checked), or -- h_pos == nullptr -- the entries
+// [first, first + count): the hash under the set's DST (run_hash_group; Bls12381G1Impl: uncleared), k_msgset_seal, and for a set that
+// has rows k_keyset_lines[_at] on those entries alone, through a scratch that lives for this call only and is allocated before
+// anything is written.
+static int msgset_apply(Ctx* c, const MsgSet& m, const uint32_t* h_pos, size_t first, const uint8_t* msgs, const uint64_t* msg_offsets, size_t count) {
+  std::vector<uint64_t> moffs;
+  int rc = read_offsets(msg_offsets, count, "msg_offsets", moffs);
+  if (rc) return rc;
+  const size_t total = (size_t)moffs[count], hsz = point_bytes(m.sig_group, BLSGPU_FMT_RAW_PROJ), chunk = std::min<size_t>(count, 4096);
+  if (total && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  if ((rc = arena_reserve(c, pad256(total) + pad256(8 * (count + 1)) + pad256(hsz * count) + pad256(768 * count) + pad256(4 * count) + 4096))) return rc;
+  c->arena_off = 0;
+  struct Work {
+    void* scratch = nullptr;
+    ~Work() {
+      if (scratch) (void)hipFree(scratch);
+    }
+  } ws;
+  if (m.lines) HIPCK(hipMalloc(&ws.scratch, chunk * (size_t)MSGSET_ENTRY_LINE_BYTES));
+  const void* d_msgs;
+  const uint64_t* d_moffs;
+  if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
+  if ((rc = upload_offsets(c, moffs, &d_moffs))) return rc;
+  Carver mem{c};
+  uint8_t* d_hash = mem.take<uint8_t>(hsz * count);
+  uint32_t* d_pos = h_pos ? mem.take<uint32_t>(4 * count) : nullptr;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  auto drain = [&](int r) {
+    (void)hipStreamSynchronize(c->stream);      // the uploads read moffs / h_pos
+    return r;
+  };
+  if (h_pos && hipMemcpyAsync(d_pos, h_pos, 4 * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) return drain(fail(BLSGPU_E_HIP, "position upload failed"));
+  if ((rc = run_hash_group(c, m.sig_group, count, (const uint8_t*)d_msgs, d_moffs, scheme_dst(m.sig_group, m.scheme), d_hash, m.sig_group == 1))) return drain(rc);
+  with_group(m.sig_group, [&](auto G) {
+    KL(KID_MSGSET_SEAL, k_msgset_seal<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_hash, (const uint32_t*)d_pos, first, m.aff);
+  });
+  if (m.lines)
+    for (size_t l0 = 0; l0 < count; l0 += chunk) {
+      const size_t cnt = std::min(chunk, count - l0);
+      if (h_pos)
+        KL(KID_KEYSET_LINES_AT, k_keyset_lines_at, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), cnt, (const uint32_t*)d_pos + l0, (const uint8_t*)m.aff, m.lines,
+           (uint32_t*)ws.scratch, m.nolines);
+      else
+        KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), first + l0, cnt, (const uint8_t*)m.aff, m.lines, (uint32_t*)ws.scratch,
+           m.nolines);
+    }
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
+  SYNC_FLUSH(c);                      // before the scratch goes
+  return 0;
+}
+// a new set around `m` (kind, flags, n set by the caller) in two steps: the records allocated; then, once the caller has filled them,
+// the rows built and the handle issued.  A failure in between frees what the set holds (msgset_free).
+static int msgset_create_begin(Ctx* c, MsgSet& m) {
+  m.devidx = t_devidx;
+  m.dev = c->dev;
+  HIPCK(hipMalloc((void**)&m.aff, msgset_rec_bytes(m) * std::max<size_t>(m.n, 1)));
+  m.bytes = msgset_bytes(m);
+  return 0;
+}
+static int msgset_create_finish(Ctx* c, MsgSet& m, uint64_t* out_handle) {
+  int rc;
+  if (m.n && (m.flags & BLSGPU_MSGSET_LINES) && (rc = msgset_build_lines(c, m))) return rc;
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  const uint64_t id = g_keyset_next++;
+  g_msgsets[id] = m;
+  *out_handle = id;
+  return 0;
+}
+int blsgpu_msgset_create(int sig_group, int scheme, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, int flags, uint64_t* out_handle) try {
+  if (!initialised()) return NOT_INIT();
+  int rc = msgset_kind_check(sig_group, scheme);
+  if (rc) return rc;
+  if (!out_handle || (n && !msg_offsets)) return fail(BLSGPU_E_ARG, "null argument");
+  if (flags & ~BLSGPU_MSGSET_LINES) return fail(BLSGPU_E_ARG, "unknown flag");
+  if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 messages");
+  *out_handle = 0;
+  CTX_ACQUIRE(c);
+  MsgSet m;
+  m.sig_group = sig_group;
+  m.scheme = scheme;
+  m.flags = flags;
+  m.n = n;
+  if ((rc = msgset_create_begin(c, m)) || (n && (rc = msgset_apply(c, m, nullptr, 0, msgs, msg_offsets, n))) || (rc = msgset_create_finish(c, m, out_handle)))
+    msgset_free(m);
+  return rc;
+}
+API_CATCH
+
+int blsgpu_msgset_destroy(uint64_t handle) try {
+  if (!initialised()) return NOT_INIT();
+  MsgSet m;
+  {
+    std::lock_guard<std::mutex> lk(g_keyset_mu);
+    auto it = g_msgsets.find(handle);
+    if (handle == 0 || it == g_msgsets.end()) return fail(BLSGPU_E_ARG, "unknown message set handle (never issued, or destroyed)");
+    m = it->second;
+    g_msgsets.erase(it);
+  }
+  msgset_free(m);
+  return 0;
+}
+API_CATCH
+
+int blsgpu_msgset_info(uint64_t handle, int* sig_group, int* scheme, uint64_t* n, int* has_lines, uint64_t* device_bytes) try {
+  MsgSet m;
+  int rc = msgset_find(handle, m);
+  if (rc) return rc;
+  if (sig_group) *sig_group = m.sig_group;
+  if (scheme) *scheme = m.scheme;
+  if (n) *n = m.n;
+  if (has_lines) *has_lines = m.lines ? 1 : 0;
+  if (device_bytes) *device_bytes = m.bytes;
+  return 0;
+}
+API_CATCH
+
+int blsgpu_msgset_update(uint64_t handle, const uint32_t* pos, const uint8_t* msgs, const uint64_t* msg_offsets, size_t count) try {
+  MsgSet m;
+  int rc = msgset_find(handle, m);
+  if (rc) return rc;
+  if (count == 0) return 0;
+  if (!pos || !msg_offsets) return fail(BLSGPU_E_ARG, "null argument");
+  if (count > m.n) return fail(BLSGPU_E_ARG, "more positions than the message set has entries");
+  CTX_ACQUIRE_ON(c, m.devidx);
+  std::vector<uint32_t> h_pos;
+  if ((rc = keyset_read_positions(pos, count, h_pos))) return rc;
+  switch (keyset_positions_check(h_pos.data(), count, m.n)) {
+    case KEYSET_POS_RANGE: return fail(BLSGPU_E_ARG, "a position is outside the message set");
+    case KEYSET_POS_DUP: return fail(BLSGPU_E_ARG, "the same position twice in one update");
+  }
+  return msgset_apply(c, m, h_pos.data(), 0, msgs, msg_offsets, count);
+}
+API_CATCH
+
+int blsgpu_msgset_append(uint64_t handle, const uint8_t* msgs, const uint64_t* msg_offsets, size_t count, uint64_t* out_first) try {
+  MsgSet m;
+  int rc = msgset_find(handle, m);
+  if (rc) return rc;
+  if (count && !msg_offsets) return fail(BLSGPU_E_ARG, "null argument");
+  if (keyset_positions_check(nullptr, count, m.n) != KEYSET_POS_OK) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 messages");
+  if (out_first) *out_first = m.n;
+  if (count == 0) return 0;
+  CTX_ACQUIRE_ON(c, m.devidx);
+  {  // the offsets are checked before anything moves
+    std::vector<uint64_t> moffs;
+    if ((rc = read_offsets(msg_offsets, count, "msg_offsets", moffs))) return rc;
+    if (moffs[count] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
+  }
+  const size_t n0 = m.n, n1 = m.n + count, asz = msgset_rec_bytes(m);
+  {  // the records: the new array before the old one goes; the record keeps n0 until the tail is written
+    void* old = nullptr;
+    if (!keyset_grow(c, (void**)&m.aff, asz * n0, asz * n1, &old)) return fail(BLSGPU_E_HIP, "no device memory for the grown message set");
+    msgset_publish(handle, m);
+    (void)hipFree(old);
+  }
+  if (m.lines) {  // rows by the creation rule on the final size: grown, or dropped (the set works without them)
+    void *old = nullptr, *old_no = nullptr, *unused = nullptr;
+    bool keep = keyset_lines_fit(n1, 0, (uint64_t)knobs().keyset_table_mb) &&
+                keyset_grow(c, (void**)&m.lines, n0 * (size_t)MSGSET_ENTRY_LINE_BYTES, n1 * (size_t)MSGSET_ENTRY_LINE_BYTES, &old);
+    if (keep && !keyset_grow(c, (void**)&m.nolines, 4 * n0, 4 * n1, &old_no)) {
+      unused = m.lines;                         // the grown rows go with the old ones
+      m.lines = (uint32_t*)old;
+      keep = false;
+    }
+    if (!keep) {
+      old = m.lines;
+      old_no = m.nolines;
+      m.lines = nullptr;
+      m.nolines = nullptr;
+    }
+    m.bytes = msgset_bytes(m);
+    msgset_publish(handle, m);
+    for (void* p : {old, old_no, unused}) (void)hipFree(p);
+  }
+  if ((rc = msgset_apply(c, m, nullptr, n0, msgs, msg_offsets, count))) return rc;
+  m.n = n1;
+  m.bytes = msgset_bytes(m);
+  msgset_publish(handle, m);
+  // rows the creator asked for and the set does not have (an empty set has none) are built whole where creation would build them
+  if ((m.flags & BLSGPU_MSGSET_LINES) && !m.lines) {
+    if ((rc = msgset_build_lines(c, m))) return rc;
+    if (m.lines) msgset_publish(handle, m);
+  }
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* Self-test hook (include/blsgpu.h): a set whose entries are the given RAW_AFFINE points instead of hash outputs. */
+int blsgpu_debug_msgset_from_points(int sig_group, const void* points, size_t n, int flags, uint64_t* out_handle) try {
+  if (!initialised()) return NOT_INIT();
+  int rc = msgset_kind_check(sig_group, BLSGPU_SCHEME_BASIC);
+  if (rc) return rc;
+  if (!out_handle || (n && !points)) return fail(BLSGPU_E_ARG, "null argument");
+  if (flags & ~BLSGPU_MSGSET_LINES) return fail(BLSGPU_E_ARG, "unknown flag");
+  if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 points");
+  *out_handle = 0;
+  CTX_ACQUIRE(c);
+  MsgSet m;
+  m.sig_group = sig_group;
+  m.scheme = BLSGPU_SCHEME_BASIC;
+  m.flags = flags;
+  m.n = n;
+  if ((rc = msgset_create_begin(c, m))) return rc;
+  if (n && hipMemcpy(m.aff, points, msgset_rec_bytes(m) * n, hipMemcpyDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    msgset_free(m);
+    return fail(BLSGPU_E_HIP, "the copy of the points failed");
+  }
+  if ((rc = msgset_create_finish(c, m, out_handle))) msgset_free(m);
+  return rc;
+}
+API_CATCH
+
+// ---- the verify calls over a message set.  Launch sequence: k_msgset_check (every group's index; whether every named entry has
+// rows, one word back to the host where the plan may read rows), k_keyset_gather (the groups' stored points), [indexed:
+// k_keyset_check, k_keyset_gather of the keys], k_prepare_shared, k_msgset_mark, run_pairing2, [indexed: k_keyset_fin, k_msgset_mark].
+// No hash kernel, no k_group_affine, no k_group_lines.  keyset == 0: keys by value.
+static int msgset_verify(uint64_t msgset, const uint32_t* msg_idx, bool indexed, uint64_t keyset, const uint32_t* idx, const void* pks, const void* sigs,
+                         const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status) {
+  MsgSet m;
+  int rc = msgset_find(msgset, m);
+  if (rc) return rc;
+  KeySet k;
+  if (indexed) {
+    if ((rc = keyset_find(keyset, k))) return rc;
+    if (k.sig_group != m.sig_group) return fail(BLSGPU_E_ARG, "the key set belongs to the other orientation");
+    if (k.dev != m.dev || k.devidx != m.devidx) return fail(BLSGPU_E_ARG, "the key set and the message set live on different devices");
+  }
+  const int sg = m.sig_group;
+  if ((rc = check_common(sg, m.scheme, fmt))) return rc;
+  if (n_groups == 0) return 0;
+  if (!item_offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  CTX_ACQUIRE_ON(c, m.devidx);
+  std::vector<uint64_t> ioffs;
+  if ((rc = read_offsets(item_offsets, n_groups, "item_offsets", ioffs))) return rc;
+  if (ioffs[n_groups] >= ((uint64_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more items in one call");
+  if (n_groups >= ((uint64_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more groups in one call");
+  const size_t n = (size_t)ioffs[n_groups];
+  if (n == 0) return 0;
+  if (!msg_idx || !sigs || !status || (indexed ? !idx : !pks)) return fail(BLSGPU_E_ARG, "null argument");
+  // the plan, from the call's shape alone: the row-wide engine reads no rows; the one-wave path reads them in k_pairing_coop_rows, the
+  // lane-split path in k_lines2s_shared (BLSGPU_SHARED_LINES_MIN prices a build that has already happened: it does not apply)
+  const bool engine = n <= wide_max_items() && n <= coop_max_items(), coop = !engine && n <= coop_max_items();
+  const bool rows_wanted = m.lines && sg == 2 && !engine && (coop || miller_chunk_items() != 0);
+  const size_t asz = point_bytes(sg, BLSGPU_FMT_RAW_AFFINE), psz = pk_size(sg, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sg, fmt), sgb = sig_size(sg, fmt) * n;
+  if ((rc = arena_reserve(c, 4 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(8 * (n_groups + 1)) +
+                                 2 * pad256(4 * n_groups) + pad256(asz * n_groups) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 512 + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_midx, *d_idx = nullptr, *d_sigs, *d_pks = nullptr;
+  const uint64_t* d_ioffs;
+  if ((rc = stage_in(c, msg_idx, 4 * n_groups, &d_midx))) return rc;
+  if (indexed && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  if (!indexed && (rc = stage_in(c, pks, ksz * n, &d_pks))) return rc;
+  if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
+  if ((rc = upload_offsets(c, ioffs, &d_ioffs))) return rc;
+  Carver mem{c};
+  uint32_t* d_cmsg = mem.take<uint32_t>(4 * n_groups);
+  uint8_t* d_haff = mem.take<uint8_t>(asz * n_groups);
+  uint32_t* d_group = mem.take<uint32_t>(4 * n);
+  uint32_t* d_msg_of = mem.take<uint32_t>(4 * n);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  uint32_t* d_mwalk = mem.take<uint32_t>(4);
+  uint32_t* d_cidx = nullptr;
+  unsigned long long* d_pre = nullptr;
+  uint8_t *d_kaff = nullptr, *d_keys = nullptr;
+  uint32_t* d_walk = nullptr;
+  if (indexed) {
+    d_cidx = mem.take<uint32_t>(4 * n);
+    d_pre = mem.take<unsigned long long>(8 * n);
+    d_kaff = mem.take<uint8_t>(psz * n);
+    d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_kaff : mem.take<uint8_t>(ksz * n);
+    d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
+  }
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  auto drain = [&](int r) {
+    (void)hipStreamSynchronize(c->stream);      // the upload reads ioffs
+    return r;
+  };
+  if (hipMemsetAsync(d_mwalk, 0, 4, c->stream) != hipSuccess) return drain(fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
+  KL(KID_MSGSET_CHECK, k_msgset_check, dim3(blocks_for(n_groups)), dim3(BLS_BLOCK), n_groups, (const uint32_t*)d_midx, (uint64_t)m.n,
+     rows_wanted ? (const int32_t*)m.nolines : (const int32_t*)nullptr, d_cmsg, d_mwalk);
+  const uint32_t* rows = nullptr;
+  if (rows_wanted) {  // one plan per call: a named entry without usable rows makes every item walk
+    uint32_t* h_walk = (uint32_t*)hsmall_take(c, 4);
+    if (!h_walk) return drain(fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted"));
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_walk, d_mwalk, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+      return drain(fail(BLSGPU_E_HIP, "k_msgset_check failed"));
+    rows = *h_walk == 0 ? m.lines : nullptr;
+  }
+  KL(KID_KEYSET_GATHER, k_keyset_gather, dim3(blocks_for(n_groups * (asz / 4))), dim3(BLS_BLOCK), n_groups, asz / 4, (const uint32_t*)d_cmsg, (const uint32_t*)m.aff,
+     0, (uint32_t*)d_haff);
+  const uint32_t* key_table = nullptr;
+  if (indexed) {
+    if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
+    if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_table))) return drain(rc);
+    const size_t cnt_ = n;
+    KEYSET_GATHER(psz / 4, k.aff, 0, d_kaff);
+    if (d_keys != d_kaff)
+      with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_kaff, d_keys); });
+    d_pks = d_keys;
+  }
+  const bool split_rows = rows && !coop;        // the table form of the line kernel: the signature's pair first
+  with_group(sg, [&](auto G) {
+    KL(KID_PREPARE_SHARED, k_prepare_shared<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, fmt,
+       (const uint8_t*)d_haff, d_pairs, d_status, split_rows ? 1 : 0, d_group);
+  });
+  KL(KID_MSGSET_CHECK, k_msgset_mark, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_group, (const uint32_t*)d_cmsg, d_status, d_msg_of);
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, split_rows ? rows : nullptr, split_rows ? d_msg_of : nullptr,
+                         sg == 1 ? key_table : nullptr, d_cidx, rows && coop ? rows : nullptr, d_msg_of)))
+    return drain(rc);
+  if (indexed) {
+    KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
+    KL(KID_MSGSET_CHECK, k_msgset_mark, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_group, (const uint32_t*)d_cmsg, d_status, (uint32_t*)nullptr);
+    if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
+  }
+  return status_out_and_sync(c, status, d_status, n);
+}
+int blsgpu_verify_msgset_batch(uint64_t msgset, const uint32_t* msg_idx, const void* pks, const void* sigs, const uint64_t* item_offsets, size_t n_groups, int fmt,
+                               int32_t* status) try {
+  return msgset_verify(msgset, msg_idx, false, 0, nullptr, pks, sigs, item_offsets, n_groups, fmt, status);
+}
+API_CATCH
+int blsgpu_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx, const void* sigs,
+                                       const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status) try {
+  return msgset_verify(msgset, msg_idx, true, keyset, idx, nullptr, sigs, item_offsets, n_groups, fmt, status);
+}
+API_CATCH
+
+/* Self-test hook of k_pairing_coop_rows (include/blsgpu.h): the records of blsgpu_debug_coop_pairing with fixed_g2 = 0, pair 0's G2
+ * member being entry msg_of[i] of a set with rows.  The kernel is launched exactly as run_pairing2 launches it (mode 1), or with the
+ * export of the easy-part value (mode 0). */
+int blsgpu_debug_coop_pairing_rows(int mode, uint64_t msgset, const uint32_t* msg_of, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
+  MsgSet m;
+  int rc = msgset_find(msgset, m);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!in || !msg_of || !status || mode < 0 || mode > 1 || n > 4096 || (mode == 0 && !out_f12) || is_device_ptr(in) || is_device_ptr(msg_of) ||
+      is_device_ptr(status) || is_device_ptr(out_f12))
+    return fail(BLSGPU_E_ARG, "bad argument");
+  if (!m.lines || m.sig_group != 2) return fail(BLSGPU_E_ARG, "the message set has no rows");
+  for (size_t i = 0; i < n; i++)
+    if ((uint64_t)msg_of[i] >= (uint64_t)m.n) return fail(BLSGPU_E_ARG, "index outside the message set");
+  CTX_ACQUIRE_ON(c, m.devidx);
+  const size_t rec = WS_PAIRS_WORDS;
+  if ((rc = arena_reserve(c, pad256(rec * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096))) return rc;
+  c->arena_off = 0;
+  std::vector<uint32_t> h(rec * n);
+  for (size_t i = 0; i < n; i++)
+    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
+  const void *d_in, *d_st, *d_of;
+  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  if ((rc = stage_in(c, msg_of, 4 * n, &d_of))) return rc;
+  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
+  int32_t* d_status = (int32_t*)d_st;
+  if (mode == 1) {
+    KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)m.lines,
+       (const uint32_t*)d_of, (uint32_t*)nullptr);
+    HIPCK(hipGetLastError());
+    return copy_out_and_sync(c, status, d_status, 4 * n);
+  }
+  uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
+  if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
+  KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)m.lines,
+     (const uint32_t*)d_of, d_easy);
   HIPCK(hipGetLastError());
   std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
   HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));

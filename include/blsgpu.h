@@ -377,6 +377,19 @@ int blsgpu_debug_coop_pairing(int mode, int fixed_g2, const int32_t* pairs, size
  *         left as it is.   mode 1: status becomes BLSGPU_OK or BLSGPU_ERR_INVALID_SIGNATURE; out_f12 is not used.
  * BLSGPU_E_ARG: a set without line tables, an index that is not below the set's size, n > 4096, any other mode.  Host pointers. */
 int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* idx, const int32_t* pairs, size_t n, int32_t* status, int32_t* out_f12);
+/* Self-test hooks of the one-wave pairing kernel that reads a registered message's line rows (not part of the reference interface).
+ * blsgpu_debug_msgset_from_points: a message set (below: blsgpu_msgset_*) of scheme Basic whose n entries are the given RAW_AFFINE
+ *   points of group sig_group (host or device memory) instead of hash outputs, so that crafted G2 points can reach the rows; flags as
+ *   blsgpu_msgset_create.  Nothing is checked: an all-zero record is the identity.
+ * blsgpu_debug_coop_pairing_rows: k_pairing_coop_rows, launched as the verify path launches it.  pairs, status, out_f12 and the
+ *   sentinel are those of blsgpu_debug_coop_pairing with fixed_g2 = 0, except that pair 0's G2 member is entry msg_of[i] of `msgset`, a
+ *   Bls12381G2Impl set with rows: the record's own pair-0 Q is not read.  Every named entry must be a finite point with usable rows;
+ *   the rows of other entries are not defined.
+ *   mode 0: out_f12 gets the exported easy-part value per item, every limb of a skipped item is BLSGPU_DEBUG_COOP_SENTINEL, status is
+ *           left as it is.   mode 1: status becomes BLSGPU_OK or BLSGPU_ERR_INVALID_SIGNATURE; out_f12 is not used.
+ *   BLSGPU_E_ARG: a set without rows, an index that is not below the set's size, n > 4096, any other mode.  Host pointers. */
+int blsgpu_debug_msgset_from_points(int sig_group, const void* points, size_t n, int flags, uint64_t* out_handle);
+int blsgpu_debug_coop_pairing_rows(int mode, uint64_t msgset, const uint32_t* msg_of, const int32_t* pairs, size_t n, int32_t* status, int32_t* out_f12);
 
 /* Sign side, provided so that benchmarks and tests can build inputs on the device:
  * pk[i] = sk[i] * g (SecretKey::public_key, src/secret_key.rs:342-344) and
@@ -723,6 +736,52 @@ int blsgpu_verify_shared_batch(int sig_group, int scheme, const void* pks, const
  * position outside the table, then the entry's creation status, then what blsgpu_verify_shared_batch gives. */
 int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint64_t* item_offsets,
                                        size_t n_groups, const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status);
+
+/* ---- Registered message sets: the messages of blsgpu_verify_shared_batch hashed ONCE and kept on the device.  The shares of a
+ * signing session or the attestations of a slot arrive over many calls; each of them would hash the same message again
+ * (hash-to-G2 is more than half of one Bls12381G2Impl verification).  A set keeps per message what a shared-message call computes
+ * per group before its items start -- the hash-to-curve point under the scheme's DST as an affine record (Bls12381G1Impl: before
+ * the cofactor clearing; Bls12381G2Impl: cleared), 96 or 192 bytes -- and later calls name a group's message by its position.
+ *
+ * Handles follow the key sets' rules: an opaque non-zero id, never a pointer; a stale or unknown id (a key set's included) returns
+ * BLSGPU_E_ARG; hipMalloc'd outside the context arenas on the device of the context that ran the creation, freed by
+ * blsgpu_msgset_destroy or blsgpu_shutdown; update and append take no lock against readers (running any call on a set while another
+ * thread updates, appends to or destroys it is the caller's error).
+ *
+ * create: msgs / msg_offsets (n + 1 entries from 0, never decreasing) as everywhere; empty messages and n == 0 are valid; scheme is
+ *   Basic or ProofOfPossession -- MessageAugmentation hashes pk || m, so there is nothing to register: BLSGPU_E_ARG.  Nothing of the
+ *   caller's buffers is retained.  flags & BLSGPU_MSGSET_LINES (Bls12381G2Impl; accepted and without effect for sig_group 1, whose
+ *   messages are G1 points and have no lines): every entry also gets the 68 normalised Miller rows of its point, 15,232 bytes, so
+ *   that a verification above BLSGPU_WIDE_MAX items walks the signature alone (k_pairing_coop_rows up to BLSGPU_COOP_MAX items, the
+ *   table form of the line kernel beyond).  The rows are not built, and the set works without them, when they would reach 2^32 bytes
+ *   (281,970 entries), exceed BLSGPU_KEYSET_TABLE_MB MiB, or find no room on the device.  An entry whose point is the identity or
+ *   whose walk meets a vanishing denominator (neither happens for a hash output) keeps its point and has no usable rows: a call that
+ *   names it walks all its items.  Rows change the plan, never a status.
+ * info: *has_lines is 1 when the set has rows.
+ * update: entry pos[i] becomes the hash of message i; a position outside the set or named twice is BLSGPU_E_ARG and nothing is
+ *   written.  append: the set grows by `count` messages, *out_first (may be null) gets the first new position; when the device has
+ *   no room for the grown records the set is unchanged.  Both hash and build the touched entries only; afterwards the set is what
+ *   creation of the final message list gives (rows the grown set has no room for are dropped, rows the creator asked for and an
+ *   empty set could not have are built).  pos, msgs and msg_offsets may be host or device memory. */
+#define BLSGPU_MSGSET_LINES 1
+int blsgpu_msgset_create(int sig_group, int scheme, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, int flags, uint64_t* out_handle);
+int blsgpu_msgset_destroy(uint64_t handle);
+int blsgpu_msgset_info(uint64_t handle, int* sig_group, int* scheme, uint64_t* n, int* has_lines, uint64_t* device_bytes);
+int blsgpu_msgset_update(uint64_t handle, const uint32_t* pos, const uint8_t* msgs, const uint64_t* msg_offsets, size_t count);
+int blsgpu_msgset_append(uint64_t handle, const uint8_t* msgs, const uint64_t* msg_offsets, size_t count, uint64_t* out_first);
+/* blsgpu_verify_shared_batch with group g's message named as entry msg_idx[g] of a message set: the group structure, item_offsets,
+ * pks, sigs, fmt and status are that call's (empty groups allowed; two groups may name one entry); sig_group and scheme come from the
+ * set.  status[i] is, first, BLSGPU_E_ARG in the slot when the item's group names an index outside the set (other groups are
+ * unaffected and the call returns 0); else exactly what blsgpu_verify_shared_batch returns for the item under the entry's message
+ * bytes.  No call hashes anything.  Every pointer may be host or device memory; the call runs on the set's device. */
+int blsgpu_verify_msgset_batch(uint64_t msgset, const uint32_t* msg_idx, const void* pks, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
+                               int fmt, int32_t* status);
+/* The same with item i's key at position idx[i] of a registered key set of the same orientation on the same device (anything else:
+ * BLSGPU_E_ARG).  status[i]: the message index rule above first, then the key set's two rules in their order (a position outside the
+ * table, the entry's creation status), then the verification.  Over a Bls12381G1Impl key set with line tables an item above
+ * BLSGPU_WIDE_MAX items needs nothing but its signature. */
+int blsgpu_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx, const void* sigs,
+                                       const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status);
 
 #ifdef __cplusplus
 }
