@@ -3591,7 +3591,11 @@ int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t
   const dim3 grid(blocks_for((size_t)s->lanes * n)), block(BLS_BLOCK);
 #define DBG_LAUNCH(kern) KL(KID_DEBUG_OPS, kern, grid, block, op, n, reps, (const int32_t*)d_in, rec_in, d_out, rec_out)
   if (s->lanes == 64) DBG_LAUNCH(k_dbg_coop);      // one workgroup per item: blocks_for(64 n) = n
-  else if (s->lanes == 1) DBG_LAUNCH(k_dbg_fp1);
+  else if (op >= DBG_G1_DBL) {                     // the curve layer
+    if (s->lanes == 1) DBG_LAUNCH(k_dbg_pt1);
+    else if (s->lanes == 2) DBG_LAUNCH(k_dbg_pt2s);
+    else DBG_LAUNCH(k_dbg_g2q);
+  } else if (s->lanes == 1) DBG_LAUNCH(k_dbg_fp1);
   else if (op < DBG_F12_SH_SQR) DBG_LAUNCH(k_dbg_fp2s);
   else if (op < DBG_CYC_C_SQR) DBG_LAUNCH(k_dbg_f12acc);
   else if (op < DBG_F12_POW_X) DBG_LAUNCH(k_dbg_cyc);

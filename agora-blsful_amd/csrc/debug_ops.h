@@ -7,6 +7,11 @@
 // __shared__ coop_shared, launched with BLS_BLOCK threads as k_pairing_coop is).  n_in / n_out: Fp limb vectors per record; an Fp2 is two of them (c0, c1), an
 // Fp12 twelve, in tower order (c0.a0, c0.a1, c0.a2, c1.a0, c1.a1, c1.a2).  n_par: small integers after the input vectors.
 // chain: reps > 1 is allowed and feeds the output back as the first operand.
+// lanes = 4: one item per four adjacent lanes (item j on lanes 4j .. 4j + 3, 16 items per workgroup): both lane pairs are loaded with
+// the same lane-split point, as k_msm_chunk_g2q holds it, and each pair writes the point it ends with.
+// Point records: a Jacobian point is its coordinates X, Y, Z in that order -- three limb vectors over Fp, six over Fp2 (c0 then c1 of
+// each); an affine operand is (x, y); outputs likewise.  A scalar crosses in the parameter slots as little-endian 32-bit words (a word
+// of 2^31 or more as the negative int32 with the same bits).  The identity is any point with Z = 0 mod p.
 // The last parameter of every lanes = 64 row is `fill`: the word the kernel writes over the whole coop_shared before it stages the
 // operands.  An Fp12 crosses the door in tower order there too; the kernel maps it to the w-power slots of coop_f12 as k_finalexp_coop does.
 #pragma once
@@ -65,7 +70,35 @@
   X(COOP_SQR_MUL_JOBS, 69, 64, 52, 32, 1, 0)  /* coop_sqr_with_jobs: in = f, job[k][j][0..1] for j < 5; out = f^2, res[k][j] */ \
   X(COOP_LINE_MUL_JOBS, 70, 64, 66, 36, 2, 0) /* coop_mul_line_with_jobs: in = f, l0, l2, l3, job[k][j][0..1] for j < 6; out = f * line, res[k][j]; par = set, fill */ \
   X(COOP_FINAL_EASY, 71, 64, 12, 12, 1, 0)    /* coop_final_easy on S.f */                                           \
-  X(COOP_FINAL_VERDICT, 72, 64, 12, 1, 1, 0)  /* coop_final_verdict on S.f: out limb 0 = the status */
+  X(COOP_FINAL_VERDICT, 72, 64, 12, 1, 1, 0)  /* coop_final_verdict on S.f: out limb 0 = the status */                \
+  /* ---- one lane per item: the curve layer on jac<fp> (curve.cuh, msm2.cuh) */                                    \
+  X(G1_DBL, 80, 1, 3, 3, 1, 1)         /* jac_dbl (par = form: 0 the non-inlined function, 1 jac_dbl_body) */        \
+  X(G1_ADD, 81, 1, 6, 3, 1, 1)         /* jac_add / jac_add_body(p, q); chain: p <- p + q */                         \
+  X(G1_MADD, 82, 1, 5, 3, 1, 1)        /* jac_madd / jac_madd_body(p, x2, y2); chain: p <- p + (x2, y2) */           \
+  X(G1_TO_AFF, 83, 1, 3, 3, 0, 0)      /* jac_to_aff: out = x, y, [inf, 0..] */                                      \
+  X(G1_MUL_U64, 84, 1, 3, 3, 2, 0)     /* jac_mul_u64; par = k as two 32-bit words */                                \
+  X(G1_MUL_SCALAR, 85, 1, 3, 3, 8, 0)  /* jac_mul_scalar; par = k as eight 32-bit words */                           \
+  X(G1_IN_SUBGROUP, 86, 1, 2, 1, 1, 0) /* g1_in_subgroup(x, y; par = inf): out limb 0 = the verdict */               \
+  /* ---- one lane per item: the curve layer on jac<fp2> */                                                         \
+  X(G2L_DBL, 90, 1, 6, 6, 1, 1)        /* jac_dbl / jac_dbl_body */                                                  \
+  X(G2L_ADD, 91, 1, 12, 6, 1, 1)       /* jac_add / jac_add_body */                                                  \
+  X(G2L_MADD, 92, 1, 10, 6, 1, 1)      /* jac_madd / jac_madd_body */                                                \
+  X(G2L_TO_AFF, 93, 1, 6, 5, 0, 0)     /* jac_to_aff: out = x, y, [inf, 0..] */                                      \
+  X(G2L_MUL_U64, 94, 1, 6, 6, 2, 0)    /* jac_mul_u64 */                                                             \
+  X(G2L_MUL_SCALAR, 95, 1, 6, 6, 8, 0) /* jac_mul_scalar */                                                          \
+  X(G2L_IN_SUBGROUP, 96, 1, 4, 1, 1, 0) /* g2_in_subgroup */                                                         \
+  X(G2L_PSI, 97, 1, 6, 6, 0, 0)        /* g2_psi */                                                                  \
+  X(G2L_PSI2, 98, 1, 6, 6, 0, 0)       /* g2_psi2 */                                                                 \
+  X(G2L_CLEAR, 99, 1, 6, 6, 0, 0)      /* g2_clear_cofactor<fp2> */                                                  \
+  /* ---- two lanes per item: the curve layer on jac<hfp2> */                                                       \
+  X(G2S_DBL, 100, 2, 6, 6, 1, 1)       /* jac_dbl / jac_dbl_body */                                                  \
+  X(G2S_ADD, 101, 2, 12, 6, 1, 1)      /* jac_add / jac_add_body */                                                  \
+  X(G2S_MADD, 102, 2, 10, 6, 1, 1)     /* jac_madd / jac_madd_body */                                                \
+  X(G2S_PSI, 103, 2, 6, 6, 0, 0)       /* g2_psi */                                                                  \
+  X(G2S_PSI2, 104, 2, 6, 6, 0, 0)      /* g2_psi2 */                                                                 \
+  X(G2S_CLEAR, 105, 2, 6, 6, 0, 0)     /* g2_clear_cofactor<hfp2> */                                                 \
+  /* ---- four lanes per item: jac_dbl_quad (curve_quad.cuh) */                                                     \
+  X(G2Q_DBL, 110, 4, 6, 12, 0, 1)      /* out = the point as lane pair 0 holds it, then as lane pair 1 holds it */
 
 enum {
 #define X(name, id, lanes, nin, nout, npar, chain) DBG_##name = id,
@@ -89,6 +122,9 @@ __global__ void k_dbg_f12acc(int op, size_t n, int reps, const int32_t* in, int 
 __global__ void k_dbg_cyc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_f12misc(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_coop(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_pt1(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_pt2s(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_g2q(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 // blsgpu_debug_map_to_curve: the G1 point at WREC_P0 of n cut-check records (engine values, Jacobian) -> RAW_PROJ
 __global__ void k_dbg_rec_g1_to_raw(size_t n, const uint32_t* rec, uint8_t* out);
 #endif

@@ -348,6 +348,8 @@ def build():
     L['F12_FROB1'] = L['F12_INV']
     L['F12_FROB2'] = L['F12_INV']
     coop_lists(L, ops12, cyc, accs, mv, ext2)
+    import point_cases                       # the curve-layer rows (G1_*, G2L_*, G2S_*, G2Q_DBL): tests/point_cases.py
+    L.update(point_cases.build())
     _cache.update(L)
     return _cache
 
@@ -686,6 +688,9 @@ _expected = {}
 
 def check(op, cs, outs, reps=1):
     """assert that the output vectors of one case are right; the message names the operation and the case"""
+    import point_cases
+    if op in point_cases.ROWS:               # a point row: judged by the chord-and-tangent rule and the oracle's curve (tests/point_cases.py)
+        return point_cases.check(op, cs, outs, reps)
     tag = '%s%s, case "%s": ' % (op, ' x%d' % reps if reps > 1 else '', cs['name'])
     # (a lanes = 64 case run with another fill shares its operand vectors, and so its expected value, with the case of the list)
     key = (op, id(cs['vecs']), tuple(cs['par'][:-1]), reps) if op.startswith('COOP_') else (op, id(cs), reps)
@@ -982,13 +987,17 @@ def check_easy(cs, out):
 
 
 CHAINS = ('FP_MUL', 'FP_SQR', 'FP2_MUL', 'FP2_SQR', 'F12_SH_SQR', 'F12_SH_MUL', 'F12_SH_MUL_LINE', 'F12_SH_MUL_2LINES', 'F12_SH_MUL_LINE5', 'F12_SH_CYC_SQR',
-          'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'COOP_MUL', 'COOP_SQR', 'COOP_MUL_LINE', 'COOP_CYC_SQR')
+          'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'COOP_MUL', 'COOP_SQR', 'COOP_MUL_LINE', 'COOP_CYC_SQR',
+          'G1_ADD', 'G1_DBL', 'G1_MADD', 'G2L_ADD', 'G2L_DBL', 'G2L_MADD', 'G2Q_DBL', 'G2S_ADD', 'G2S_DBL', 'G2S_MADD')      # (point_cases.CHAINS)
 CHAIN_REPS = ((2, 1), (17, 5), (63, 11))       # (reps, stride through the list)
 
 
 def chain_cases(op, stride):
     """the cases a chain runs on: every stride-th of the list (24 at the most), and for the squarings in the cyclotomic subgroup
     every element of that subgroup -- so that at each length, 63 included, non-trivial cyclotomic elements are squared"""
+    import point_cases
+    if op in point_cases.ROWS:               # P + Q, P + 2Q, ...: the marked cases (through the identity, from a doubling) and every stride-th
+        return point_cases.chain_cases(op, stride)
     lst = build()[op]
     cases = lst[::stride][:24]
     if op in ('F12_SH_CYC_SQR', 'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'COOP_CYC_SQR'):

@@ -631,7 +631,102 @@ static void fo_st12(int32_t* out, const fp12_t<hfp2>& f) {
   const hfp2* c[6] = {&f.c0.a0, &f.c0.a1, &f.c0.a2, &f.c1.a0, &f.c1.a1, &f.c1.a2};
   for (int k = 0; k < 6; k++) FO_ST2(k, (*c[k]));
 }
+}  // extern "C"
+// ---- the curve layer (G1_* on jac<fp>, G2L_* on jac<fp2>, G2S_* on the host emulation of jac<hfp2>): the rows as the kernels of
+// csrc/tu_debug_ops5.hip / tu_debug_ops6.hip run them.  G2Q_DBL (jac_dbl_quad, DPP code) has no host form: it follows jac_dbl_body's
+// operation order and reductions, and its cases are those of G2S_DBL, which run here.
+struct fo_rec {
+  const int32_t* in; const double* lb; const double* vb; const int32_t* nn;
+};
+static void fo_ldf(fp& r, const fo_rec& R, int k) { fo_ld(r, R.in, R.lb, R.vb, R.nn, k); }
+static void fo_ldf(fp2& r, const fo_rec& R, int k) { fo_ld(r.c0, R.in, R.lb, R.vb, R.nn, 2 * k); fo_ld(r.c1, R.in, R.lb, R.vb, R.nn, 2 * k + 1); }
+static void fo_ldf(hfp2& r, const fo_rec& R, int k) { fo_ld(r.c[0], R.in, R.lb, R.vb, R.nn, 2 * k); fo_ld(r.c[1], R.in, R.lb, R.vb, R.nn, 2 * k + 1); }
+static void fo_stf(int32_t* out, int k, const fp& a) { fo_st(out, k, a); }
+static void fo_stf(int32_t* out, int k, const fp2& a) { fo_st(out, 2 * k, a.c0); fo_st(out, 2 * k + 1, a.c1); }
+static void fo_stf(int32_t* out, int k, const hfp2& a) { fo_st(out, 2 * k, a.c[0]); fo_st(out, 2 * k + 1, a.c[1]); }
+template <class F> static void fo_ldj(jac<F>& p, const fo_rec& R, int k0) { fo_ldf(p.x, R, k0); fo_ldf(p.y, R, k0 + 1); fo_ldf(p.z, R, k0 + 2); }
+template <class F> static void fo_stj(int32_t* out, const jac<F>& p) { fo_stf(out, 0, p.x); fo_stf(out, 1, p.y); fo_stf(out, 2, p.z); }
+static bool fo_in_subgroup(const g1_aff& a) { return g1_in_subgroup(a); }
+static bool fo_in_subgroup(const g2_aff& a) { return g2_in_subgroup(a); }
+enum { FO_DBL, FO_ADD, FO_MADD, FO_TO_AFF, FO_MUL_U64, FO_MUL_SCALAR, FO_IN_SUBGROUP, FO_PSI, FO_PSI2, FO_CLEAR };
+template <class F, int W, bool G2>
+static int fo_point_row(int row, const fo_rec& R, const int32_t* par, int reps, int32_t* out) {
+  jac<F> p, q;
+  switch (row) {
+    case FO_DBL:
+      fo_ldj(p, R, 0);
+      for (int k = 0; k < reps; k++) { if (par[0]) jac_dbl_body(p, p); else jac_dbl(p, p); }
+      fo_stj(out, p);
+      return 0;
+    case FO_ADD:
+      fo_ldj(p, R, 0); fo_ldj(q, R, 3);
+      for (int k = 0; k < reps; k++) { if (par[0]) jac_add_body(p, p, q); else jac_add(p, p, q); }
+      fo_stj(out, p);
+      return 0;
+    case FO_MADD: {
+      F x2, y2;
+      fo_ldj(p, R, 0); fo_ldf(x2, R, 3); fo_ldf(y2, R, 4);
+      for (int k = 0; k < reps; k++) { if (par[0]) jac_madd_body(p, p, x2, y2); else jac_madd(p, p, x2, y2); }
+      fo_stj(out, p);
+      return 0;
+    }
+    default: break;
+  }
+  if constexpr (G2) {
+    if (row == FO_PSI || row == FO_PSI2 || row == FO_CLEAR) {
+      fo_ldj(p, R, 0);
+      if (row == FO_PSI) g2_psi(q, p); else if (row == FO_PSI2) g2_psi2(q, p); else g2_clear_cofactor(q, p);
+      fo_stj(out, q);
+      return 0;
+    }
+  }
+  if constexpr (W != 0) {              // the one-lane rows only
+    switch (row) {
+      case FO_TO_AFF: {
+        aff<F> a;
+        fo_ldj(p, R, 0);
+        jac_to_aff(a, p);
+        fo_stf(out, 0, a.x); fo_stf(out, 1, a.y);
+        for (int k = 0; k < FP_NL; k++) out[2 * W * FP_NL + k] = 0;
+        out[2 * W * FP_NL] = a.inf ? 1 : 0;
+        return 0;
+      }
+      case FO_MUL_U64:
+        fo_ldj(p, R, 0);
+        jac_mul_u64(q, p, ((uint64_t)(uint32_t)par[1] << 32) | (uint32_t)par[0]);
+        fo_stj(out, q);
+        return 0;
+      case FO_MUL_SCALAR: {
+        uint32_t k[8];
+        for (int i = 0; i < 8; i++) k[i] = (uint32_t)par[i];
+        fo_ldj(p, R, 0);
+        jac_mul_scalar(q, p, k);
+        fo_stj(out, q);
+        return 0;
+      }
+      case FO_IN_SUBGROUP: {
+        aff<F> a;
+        fo_ldf(a.x, R, 0); fo_ldf(a.y, R, 1);
+        a.inf = par[0] != 0;
+        for (int k = 0; k < FP_NL; k++) out[k] = 0;
+        out[0] = fo_in_subgroup(a) ? 1 : 0;
+        return 0;
+      }
+      default: break;
+    }
+  }
+  return -1;
+}
+extern "C" {
 int hs_field_op(int op, const int32_t* in, const double* lb, const double* vb, const int32_t* nn, const int32_t* par, int reps, int32_t* out) {
+  if (op >= DBG_G1_DBL) {
+    const fo_rec R = {in, lb, vb, nn};
+    if (op >= DBG_G2S_DBL && op <= DBG_G2S_MADD) return fo_point_row<hfp2, 0, true>(op - DBG_G2S_DBL, R, par, reps, out);
+    if (op >= DBG_G2S_PSI && op <= DBG_G2S_CLEAR) return fo_point_row<hfp2, 0, true>(FO_PSI + op - DBG_G2S_PSI, R, par, reps, out);
+    if (op >= DBG_G2L_DBL && op <= DBG_G2L_CLEAR) return fo_point_row<fp2, 2, true>(op - DBG_G2L_DBL, R, par, reps, out);
+    if (op <= DBG_G1_IN_SUBGROUP) return fo_point_row<fp, 1, false>(op - DBG_G1_DBL, R, par, reps, out);
+    return -1;
+  }
   fp a, b, c, d, r, s;
   hfp2 x, y, z;
   switch (op) {

@@ -43,7 +43,7 @@ def test_item_counts(api, op):
     """1, 2, 31, 32, 33, 65 items (lane pairs; the one-lane operations also at twice that: 62 .. 130 lanes of 64-lane workgroups)"""
     lst = fc.build()[op]
     lanes = api.field_op_shape(op)[0]
-    counts = COUNTS if lanes == 2 else COUNTS + (62, 64, 66, 130)
+    counts = COUNTS if lanes != 1 else COUNTS + (62, 64, 66, 130)        # (lane pairs and, for G2Q_DBL, quads)
     for k, n in enumerate(counts):
         cases = take(lst, n, 7 * k)
         outs = run(api, op, cases)
@@ -52,10 +52,11 @@ def test_item_counts(api, op):
             fc.check(op, cs, o)
 
 
-@pytest.mark.parametrize('op', [op for op in OPS if op.startswith(('FP2_', 'F12_', 'CYC_')) and not op.startswith('FP2_KARA')])
+@pytest.mark.parametrize('op', [op for op in OPS if op.startswith(('FP2_', 'F12_', 'CYC_', 'G2S_', 'G2Q_')) and not op.startswith('FP2_KARA')])
 def test_both_quad_positions(api, op):
     """the same cases at an even and at an odd pair index -- both positions of a DPP quad -- give identical limbs: a quad_perm that
-    reaches the wrong partner, or anything leaking between neighbours, shows here (and in check() at either position)"""
+    reaches the wrong partner, or anything leaking between neighbours, shows here (and in check() at either position); for G2Q_DBL the
+    two runs put a case at an even and at an odd quad index"""
     lst = fc.build()[op]
     sub = take(lst, min(len(lst), 21), 3)
     even = run(api, op, sub)
