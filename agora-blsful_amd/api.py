@@ -55,6 +55,7 @@ EXPORTS = [
     'blsgpu_hash_to_scalar', 'blsgpu_sig_proof_challenge_batch', 'blsgpu_sig_proof_timestamp_verify_batch',
     'blsgpu_msgset_create', 'blsgpu_msgset_destroy', 'blsgpu_msgset_info', 'blsgpu_msgset_update', 'blsgpu_msgset_append',
     'blsgpu_verify_msgset_batch', 'blsgpu_verify_msgset_indexed_batch', 'blsgpu_debug_msgset_from_points', 'blsgpu_debug_coop_pairing_rows',
+    'blsgpu_aggregate_verify_msgset_batch', 'blsgpu_aggregate_verify_msgset_indexed_batch',
 ]
 
 
@@ -214,6 +215,8 @@ def load_library(path=None):
         lib.blsgpu_verify_msgset_indexed_batch.argtypes = [h, u32p, h, u32p, vp, u64p, sz, ci, i32p]
         lib.blsgpu_debug_msgset_from_points.argtypes = [ci, vp, sz, ci, ctypes.POINTER(h)]
         lib.blsgpu_debug_coop_pairing_rows.argtypes = [ci, h, u32p, i32p, sz, i32p, i32p]
+        lib.blsgpu_aggregate_verify_msgset_batch.argtypes = [h, u32p, vp, u64p, sz, vp, ci, i32p, u64p]
+        lib.blsgpu_aggregate_verify_msgset_indexed_batch.argtypes = [h, u32p, h, u32p, u64p, sz, vp, ci, i32p, u64p]
         _lib = lib
     return _lib
 
@@ -1099,6 +1102,43 @@ def verify_msgset_indexed_batch(msgset, keyset, groups, fmt=FMT_RAW_PROJ):
     return [flat[ioffs[g]:ioffs[g + 1]] for g in range(n_groups)]
 
 
+def _aggregate_msgset_sets(name, sets):
+    n_sets = len(sets)
+    for s, (ks, mi, _) in enumerate(sets):
+        if len(ks) != len(mi):
+            raise ValueError('%s: set %d has %d keys and %d message indices' % (name, s, len(ks), len(mi)))
+    soffs = _count_offsets([ks for ks, _, _ in sets])
+    midx = _u32([i for _, mi, _ in sets for i in mi])
+    sgb = b''.join(sig for _, _, sig in sets)
+    stv = (ctypes.c_int32 * max(n_sets, 1))()
+    aux = (ctypes.c_uint64 * (2 * max(n_sets, 1)))()
+    return n_sets, soffs, midx, sgb, stv, aux
+
+
+def aggregate_verify_msgset_batch(msgset, sets, fmt=FMT_RAW_PROJ):
+    """aggregate_verify_batch with pair i's message named by position: `sets` is a list of (pks, msg_idx, sig), msg_idx a list of
+    positions in `msgset`, one per key.  The keys of a set that name one message are summed and paired once; nothing is hashed.
+    Returns one (status, (aux0, aux1)) per set: E_ARG with aux (0, 0) for a set that names an index outside the message set, else
+    what aggregate_verify_batch gives for those keys under the entries' messages."""
+    n_sets, soffs, midx, sgb, stv, aux = _aggregate_msgset_sets('aggregate_verify_msgset_batch', sets)
+    pkb = b''.join(p for ks, _, _ in sets for p in ks)
+    _check(init().blsgpu_aggregate_verify_msgset_batch(msgset.handle, ctypes.cast(midx, ctypes.c_void_p), _ptr(pkb), ctypes.cast(soffs, ctypes.c_void_p), n_sets,
+                                                       _ptr(sgb), fmt, ctypes.cast(stv, ctypes.c_void_p), ctypes.cast(aux, ctypes.c_void_p)))
+    return [(stv[s], (aux[2 * s], aux[2 * s + 1])) for s in range(n_sets)]
+
+
+def aggregate_verify_msgset_indexed_batch(msgset, keyset, sets, fmt=FMT_RAW_PROJ):
+    """The same with the keys named by position too: `sets` is a list of (idx, msg_idx, sig), idx a list of positions in `keyset`.
+    Per set: E_ARG for a message index outside the message set, then E_ARG for a position outside the key set, then the creation
+    status of the first invalid entry named (all with aux (0, 0)), else what aggregate_verify_batch gives."""
+    n_sets, soffs, midx, sgb, stv, aux = _aggregate_msgset_sets('aggregate_verify_msgset_indexed_batch', sets)
+    idx = _u32([i for ix, _, _ in sets for i in ix])
+    _check(init().blsgpu_aggregate_verify_msgset_indexed_batch(msgset.handle, ctypes.cast(midx, ctypes.c_void_p), keyset.handle,
+                                                               ctypes.cast(idx, ctypes.c_void_p), ctypes.cast(soffs, ctypes.c_void_p), n_sets, _ptr(sgb), fmt,
+                                                               ctypes.cast(stv, ctypes.c_void_p), ctypes.cast(aux, ctypes.c_void_p)))
+    return [(stv[s], (aux[2 * s], aux[2 * s + 1])) for s in range(n_sets)]
+
+
 def combine_shares(group, sets, fmt=FMT_RAW_PROJ):
     """Threshold recovery of many independent sets in one call (blsgpu_combine_shares): `sets` is a list of lists of
     (identifier: int, raw point, scheme or None).  Scheme tags are checked only when every share of the call carries one
@@ -1714,6 +1754,26 @@ class TensorOps:
         _check(self.lib.blsgpu_verify_msgset_indexed_batch(msgset.handle, self._p(msg_idx), keyset.handle, self._p(idx), self._p(sigs), self._p(item_offs),
                                                            n_groups, FMT_RAW_PROJ, self._p(st)))
         return st[:n]
+
+    def aggregate_verify_msgset_batch(self, msgset, msg_idx, pks, set_offs, n_sets, sigs):
+        """(int32 statuses, int64 aux of shape (n_sets, 2)), both on the device, of n_sets aggregate_verify checks whose pair i has
+        its message at position msg_idx[i] of `msgset` (an int32 tensor whose bits are the uint32 positions, one per pair): flat
+        device-resident RAW_PROJ keys, the sets' int64 offsets into the pairs (n_sets + 1 entries), one RAW_PROJ signature per set."""
+        self._sync()
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        aux = self.empty(2 * max(n_sets, 1), self.torch.int64)
+        _check(self.lib.blsgpu_aggregate_verify_msgset_batch(msgset.handle, self._p(msg_idx), self._p(pks), self._p(set_offs), n_sets, self._p(sigs),
+                                                             FMT_RAW_PROJ, self._p(st), self._p(aux)))
+        return st[:n_sets], aux[:2 * n_sets].view(n_sets, 2)
+
+    def aggregate_verify_msgset_indexed_batch(self, msgset, msg_idx, keyset, idx, set_offs, n_sets, sigs):
+        """the same with pair i's key at position idx[i] of `keyset` (idx: an int32 tensor whose bits are the uint32 positions)."""
+        self._sync()
+        st = self.empty(max(n_sets, 1), self.torch.int32)
+        aux = self.empty(2 * max(n_sets, 1), self.torch.int64)
+        _check(self.lib.blsgpu_aggregate_verify_msgset_indexed_batch(msgset.handle, self._p(msg_idx), keyset.handle, self._p(idx), self._p(set_offs), n_sets,
+                                                                     self._p(sigs), FMT_RAW_PROJ, self._p(st), self._p(aux)))
+        return st[:n_sets], aux[:2 * n_sets].view(n_sets, 2)
 
     def keyset_get(self, keyset, key_group, idx, n, fmt=FMT_RAW_PROJ):
         """(entries as one uint8 tensor, int32 creation statuses), both on the device."""

@@ -26,6 +26,7 @@
 #include "elgamal.cuh"
 #include "verify_shared.cuh"
 #include "msgset.cuh"
+#include "agg_msgset.cuh"
 #include "hkdf.cuh"
 #include "debug_ops.h"
 #include "host_sha256.h"
@@ -60,6 +61,7 @@ enum {
   KID_HASH_TO_SCALAR, KID_PROOF_CHALLENGE, KID_PROOF_TIMEOUT,   // blsgpu_hash_to_scalar, blsgpu_sig_proof_challenge_batch / _timestamp_verify_batch (hkdf.cuh)
   KID_MSGSET_SEAL, KID_MSGSET_CHECK,     // registered message sets (msgset.cuh; k_msgset_mark counts under k_msgset_check, the rows' build under k_keyset_lines[_at])
   KID_PAIRING_COOP_ROWS,                 // the one-wave pairing that reads a registered message's rows (in the place of k_pairing_coop)
+  KID_AGGM_CLASS, KID_AGGM_SUM, KID_AGGM_ITEMS,   // aggregate verify by message index (agg_msgset.cuh): check / class table / numbering, the class key sum, the flat items
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -82,7 +84,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_pairing_coop_keyed",
                                     "k_hash_to_scalar", "k_proof_challenge", "k_proof_timeout",
                                     "k_msgset_seal", "k_msgset_check",
-                                    "k_pairing_coop_rows"};
+                                    "k_pairing_coop_rows",
+                                    "k_agg_msgset_class", "k_agg_msgset_sum", "k_agg_msgset_items"};
 
 struct Ctx {
   int dev = -1;
@@ -6663,6 +6666,233 @@ API_CATCH
 int blsgpu_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx, const void* sigs,
                                        const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status) try {
   return msgset_verify(msgset, msg_idx, true, keyset, idx, nullptr, sigs, item_offsets, n_groups, fmt, status);
+}
+API_CATCH
+
+// ---- aggregate verify by message index (agg_msgset.cuh): the batched aggregate verify with pair i's message named as entry
+// msg_idx[i] of a message set.  Every set runs through the segmented kernels (no message bytes exist for the single call's path).
+// Launch sequence: [indexed: k_keyset_check, k_keyset_gather], k_aggm_check, k_aggm_insert, [Basic: k_dup_find_seg], k_aggm_reps,
+// k_scan_*, k_aggm_number, k_aggm_offsets -- the class count C and the rows word come back to the host -- then, unless every class is
+// a singleton (C == T): k_scan_* over the member counts, k_aggm_widen, k_aggm_scatter -- the member offsets come back for the strip
+// plan -- k_aggm_sum, k_share_fold; then k_aggm_items and the stages of aggregate_batch_run over M = C + n_sets items: per round
+// k_linesp_keyed for the class items when the message set's rows are usable (Bls12381G2Impl; the signature items, contiguous at the
+// end of the list, always walk with k_linesp) or k_linesp for all, k_millerfp3; k_f12_fold_seg[_out], k_agg_batch_mark, k_aggm_mark,
+// the final exponentiation, k_agg_batch_fin, [indexed: k_keyset_fin_aux], k_aggm_fin.  The rules take their inputs from the pairs
+// (k_aggm_insert, k_dup_find_seg), never from the class items: k_first_bad_seg does not run here.
+extern "C++" {
+template <class Keys>
+static int aggregate_msgset_run(Ctx* c, const MsgSet& m, const Keys& keys, const uint32_t* msg_idx, const std::vector<uint64_t>& offs, size_t n_sets,
+                                const void* sigs, int fmt, int32_t* status, uint64_t* aux) {
+  int rc;
+  const int sg = m.sig_group;
+  const size_t T = (size_t)offs[n_sets], Tz = T + 1, Mmax = T + n_sets;
+  const bool basic = m.scheme == BLSGPU_SCHEME_BASIC, rows_wanted = m.lines != nullptr && sg == 2;
+  const size_t ssz = sig_size(sg, fmt), osz = pk_size(sg, BLSGPU_FMT_RAW_PROJ);
+  size_t cap = 64;
+  while (cap < 2 * T) cap <<= 1;
+  uint64_t tmax = 0;
+  for (size_t s = 0; s < n_sets; s++) tmax = std::max(tmax, offs[s + 1] - offs[s]);
+  const size_t round = 65536, fx_chunk = std::min(n_sets, miller_chunk_items() ? miller_chunk_items() : round);
+  rc = arena_reserve(c, keys.arena_bytes + pad256(ssz * n_sets) + 2 * pad256(8 * (n_sets + 1)) + pad256(16 * n_sets) + 8 * pad256(4 * n_sets) +
+                            14 * pad256(4 * Tz) + pad256(4 * scan_tiles(Tz)) + 2 * pad256(4 * cap) + 2 * pad256(8 * Tz) + pad256(osz * Tz) + pad256(4 * Mmax) +
+                            pad256((size_t)WS_PAIR1_WORDS * 4 * Mmax) + pad256((size_t)WS_F_WORDS * 4 * Mmax) + pad256((size_t)WS_F_WORDS * 4 * n_sets) + 16384);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_sigs, *d_midx;
+  const uint8_t* kp = nullptr;
+  const uint32_t *key_table = nullptr, *d_cidx = nullptr;     // (a summed key has no line table: key sets' tables are not used here)
+  const uint64_t* o;
+  if ((rc = keys.stage(c, &kp, &key_table, &d_cidx))) return rc;
+  if ((rc = stage_in(c, msg_idx, 4 * T, &d_midx))) return rc;
+  if ((rc = stage_in(c, sigs, ssz * n_sets, &d_sigs))) return rc;
+  if ((rc = upload_offsets(c, offs, &o))) return rc;
+  Carver mem{c};
+  int32_t* d_status = mem.stage_out<int32_t>(status, 4 * n_sets);
+  uint64_t* d_aux = aux ? mem.stage_out<uint64_t>(aux, 16 * n_sets) : nullptr;
+  uint32_t* d_cmsg = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_sid = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_slot = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_isrep = mem.take<uint32_t>(4 * Tz);        // after the numbering: the member offsets as 32-bit words
+  uint32_t* d_rank = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_cid = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_csid = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_cent = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_crep = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_count = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_cursor = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_perm = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_ssid = mem.take<uint32_t>(4 * Tz);
+  uint32_t* d_tiles = mem.take<uint32_t>(4 * scan_tiles(Tz));
+  uint32_t* d_tab = mem.take<uint32_t>(4 * cap);
+  uint32_t* d_minidx = mem.take<uint32_t>(4 * cap);
+  uint64_t* d_moffs = mem.take<uint64_t>(8 * Tz);
+  uint64_t* d_so = mem.take<uint64_t>(8 * Tz);
+  uint64_t* d_coffs = mem.take<uint64_t>(8 * (n_sets + 1));
+  uint8_t* d_part = mem.take<uint8_t>(osz * Tz);
+  uint32_t* d_skipped = mem.take<uint32_t>(4 * n_sets);
+  uint32_t* d_first = mem.take<uint32_t>(4 * n_sets);
+  uint32_t* d_best = mem.take<uint32_t>(4 * n_sets);
+  uint32_t* d_sigid = mem.take<uint32_t>(4 * n_sets);
+  int32_t* d_stb = mem.take<int32_t>(4 * n_sets);
+  uint32_t* d_bset = mem.take<uint32_t>(4 * n_sets);
+  uint32_t* d_walk = mem.take<uint32_t>(4);
+  int32_t* d_bad = mem.take<int32_t>(4 * Mmax);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * Mmax);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * Mmax);
+  uint32_t* d_rec = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n_sets);
+  uint32_t* h_back = (uint32_t*)hsmall_take(c, 8);
+  if (!mem.ok || !h_back) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  std::vector<uint32_t> bset(n_sets);
+  std::iota(bset.begin(), bset.end(), 0u);
+  std::vector<uint64_t> hm, soffs;
+  std::vector<uint32_t> ssid;
+  auto drain = [&](int r) {
+    (void)hipStreamSynchronize(c->stream);      // the uploads read this frame's vectors
+    return r;
+  };
+  HIPCK(hipMemcpyAsync(d_bset, bset.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
+  HIPCK(hipMemsetAsync(d_skipped, 0, 4 * n_sets, c->stream));
+  HIPCK(hipMemsetAsync(d_first, 0xff, 4 * n_sets, c->stream));
+  HIPCK(hipMemsetAsync(d_best, 0xff, 4 * n_sets, c->stream));
+  HIPCK(hipMemsetAsync(d_tab, 0xff, 4 * cap, c->stream));
+  HIPCK(hipMemsetAsync(d_minidx, 0xff, 4 * cap, c->stream));
+  HIPCK(hipMemsetAsync(d_isrep, 0, 4 * Tz, c->stream));
+  HIPCK(hipMemsetAsync(d_count, 0, 4 * Tz, c->stream));
+  HIPCK(hipMemsetAsync(d_cursor, 0, 4 * Tz, c->stream));
+  HIPCK(hipMemsetAsync(d_walk, 0, 4, c->stream));
+  const uint32_t* best = basic ? d_best : nullptr;
+  // a., b. the pairs: entries, the class table, the rules
+  if (T) {
+    KL(KID_AGGM_CLASS, k_aggm_check, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, n_sets, o, (const uint32_t*)d_midx, (uint64_t)m.n,
+       rows_wanted ? (const int32_t*)m.nolines : (const int32_t*)nullptr, d_cmsg, d_sid, d_skipped, d_walk);
+    with_group(sg, [&](auto G) {
+      KL(KID_AGGM_CLASS, k_aggm_insert<G()>, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, basic ? 1 : 0, (const uint32_t*)d_cmsg, (const uint32_t*)d_sid,
+         (const uint32_t*)m.aff, (uint32_t)(cap - 1), d_tab, d_minidx, d_slot, kp, fmt, o, d_first);
+    });
+    if (basic)
+      KL(KID_AGGM_CLASS, k_dup_find_seg, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, (const uint32_t*)d_sid, o, (const uint32_t*)d_slot, (const uint32_t*)d_minidx, d_best);
+    KL(KID_AGGM_CLASS, k_aggm_reps, dim3(blocks_for(Tz)), dim3(BLS_BLOCK), T, (const uint32_t*)d_slot, (const uint32_t*)d_tab, d_isrep);
+  }
+  // c. the classes numbered set after set
+  if ((rc = run_scan_u32(c, KID_AGGM_CLASS, Tz, d_isrep, d_rank, d_tiles))) return drain(rc);
+  if (T)
+    KL(KID_AGGM_CLASS, k_aggm_number, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, (const uint32_t*)d_slot, (const uint32_t*)d_tab, (const uint32_t*)d_rank,
+       (const uint32_t*)d_sid, (const uint32_t*)d_cmsg, d_cid, d_csid, d_cent, d_crep, d_count);
+  KL(KID_AGGM_CLASS, k_aggm_offsets, dim3(blocks_for(n_sets + 1)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_rank, d_coffs);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_back, d_rank + T, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipMemcpyAsync(h_back + 1, d_walk, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+    return drain(fail(BLSGPU_E_HIP, "the class kernels failed"));
+  const size_t C = h_back[0], M = C + n_sets;
+  const uint32_t* rows = rows_wanted && h_back[1] == 0 ? m.lines : nullptr;      // one plan per call: a named entry without usable rows makes every item walk
+  if (C > T) return fail(BLSGPU_E_HIP, "internal: more classes than pairs");
+  // c., d. members in class order and the class key sums -- unless every class is a singleton: then the pairs are the class items
+  const bool merged = C < T;
+  if (merged) {
+    if ((rc = run_scan_u32(c, KID_AGGM_CLASS, C + 1, d_count, d_isrep, d_tiles))) return rc;
+    KL(KID_AGGM_CLASS, k_aggm_widen, dim3(blocks_for(C + 1)), dim3(BLS_BLOCK), C + 1, (const uint32_t*)d_isrep, d_moffs);
+    KL(KID_AGGM_CLASS, k_aggm_scatter, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, (const uint32_t*)d_cid, (const uint64_t*)d_moffs, d_cursor, d_perm);
+    hm.resize(C + 1);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(hm.data(), d_moffs, 8 * (C + 1), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (hm[0] != 0 || hm[C] != T) return fail(BLSGPU_E_HIP, "internal: the class member offsets do not cover the pairs");
+    const uint64_t qmax = multi_strip_plan(hm.data(), C, multi_strip_len(T, accumulate_lanes(T), (uint64_t)knobs().multi_strip), soffs, ssid);
+    const size_t Q = ssid.size();
+    if (Q > T) return fail(BLSGPU_E_HIP, "internal: more strips than pairs");
+    HIPCK(hipMemcpyAsync(d_so, soffs.data(), 8 * (C + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(d_ssid, ssid.data(), 4 * Q, hipMemcpyHostToDevice, c->stream));
+    with_group(key_group(sg), [&](auto G) {
+      KL(KID_AGGM_SUM, k_aggm_sum<G()>, dim3(blocks_for(G() * Q)), dim3(BLS_BLOCK), Q, kp, fmt, (const uint32_t*)d_perm, (const uint64_t*)d_moffs,
+         (const uint64_t*)d_so, (const uint32_t*)d_ssid, d_part);
+      for (uint64_t step = 1; step < qmax; step <<= 1)
+        KL(KID_SHARE_FOLD, k_share_fold<G()>, dim3(blocks_for(Q)), dim3(BLS_BLOCK), Q, step, (const uint64_t*)d_so, (const uint32_t*)d_ssid, d_part);
+    });
+  }
+  // e. the flat list: class items, then one signature item per set
+  with_group(sg, [&](auto G) {
+    KL(KID_AGGM_ITEMS, k_aggm_items<G()>, dim3(blocks_for(M)), dim3(BLS_BLOCK), M, C, (const uint32_t*)d_csid, (const uint32_t*)d_cent, (const uint32_t*)d_crep,
+       (const uint32_t*)d_skipped, (const uint32_t*)d_first, best, kp, fmt, merged ? (const uint8_t*)d_part : (const uint8_t*)nullptr, (const uint64_t*)d_so,
+       (const uint8_t*)m.aff, (const uint8_t*)d_sigs, d_pairs, d_bad, d_sigid);
+  });
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a class kernel failed to launch"));
+  // f., g. one Miller value per item in rounds of at most one machine round, as aggregate_batch_run forms them
+  const size_t per_round = agg_round_size(M, round);
+  const size_t lanes_round = row_stride(lanes_for(per_round)), lanes_fx = row_stride(lanes_for(fx_chunk));
+  if (lines_reserve(c, std::max((size_t)MILLER_ENTRIES * LINE3_WORDS_H * 4 * lanes_round, (size_t)FX_STORE_WORDS * 4 * lanes_fx)))
+    return drain(fail(BLSGPU_E_HIP, "no room for the line workspace"));
+  for (size_t first = 0; first < M; first += per_round) {
+    const size_t cnt = std::min(per_round, M - first), nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
+    const size_t cnt_rows = rows && first < C ? std::min(cnt, C - first) : 0, cnt_walk = cnt - cnt_rows, walk0 = first + cnt_rows;
+    if (cnt_rows)         // both lines of every step from the entry's rows: lane pair j is flat item first + j
+      KL(KID_LINESP_KEYED, k_linesp_keyed, dim3((unsigned)(lanes_for(cnt_rows) / BLS_BLOCK)), dim3(BLS_BLOCK), C, first, cnt_rows, M, (const uint32_t*)d_pairs,
+         (const int32_t*)d_bad, c->lines_ws, lanes, rows, (const uint32_t*)d_cent);
+    if (cnt_walk) {       // the walk, its lane pairs behind those of the row items (two words per row for each of them)
+      uint32_t* lw = c->lines_ws + 2 * cnt_rows;
+      KL(KID_LINESP, k_linesp, dim3((unsigned)(lanes_for(cnt_walk) / BLS_BLOCK)), dim3(BLS_BLOCK), cnt_walk, cnt_walk, M, (const uint32_t*)(d_pairs + walk0),
+         (const int32_t*)(d_bad + walk0), lw, lw, lanes, (size_t)0, cnt_walk, 1);
+    }
+    KL(KID_MILLERFP, k_millerfp3, dim3((unsigned)(nlanes / BLS_BLOCK)), dim3(BLS_BLOCK), cnt, cnt, 1, (const int32_t*)(d_bad + first), (const uint32_t*)c->lines_ws,
+       lanes, d_f + first, M, (size_t)0);
+  }
+  // every set's product over its class items (a set has at most as many classes as pairs), times the signature's value
+  if (C)
+    for (int r = 0, nr = agg_fold_rounds(std::min<uint64_t>(tmax, C)); r < nr; r++)
+      KL(KID_AGG_SEG_FOLD, k_f12_fold_seg, dim3(blocks_for(C)), dim3(BLS_BLOCK), C, r, (const uint32_t*)d_csid, (const uint64_t*)d_coffs, d_f, M);
+  KL(KID_AGG_SEG_FOLD, k_f12_fold_seg_out, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, C, (const uint64_t*)d_coffs, (const uint32_t*)d_f, M, d_rec);
+  // the rules (their inputs: the pairs), the final exponentiation of the sets they leave open, the precedence
+  KL(KID_AGG_SEG_FIN, k_agg_batch_mark, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, best, (const uint32_t*)d_slot, (const uint32_t*)d_minidx,
+     (const uint32_t*)d_first, (const uint32_t*)d_sigid, d_stb);
+  KL(KID_AGG_SEG_FIN, k_aggm_mark, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const uint32_t*)d_skipped, d_stb);
+  for (size_t first = 0; first < n_sets; first += fx_chunk)
+    launch_finalexp_chunk(c, n_sets, first, std::min(fx_chunk, n_sets - first), d_rec, d_stb, knobs().finalexp_seg != 0);
+  KL(KID_AGG_SEG_FIN, k_agg_batch_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_bset, best, (const uint32_t*)d_slot,
+     (const uint32_t*)d_minidx, (const uint32_t*)d_first, (const uint32_t*)d_sigid, (const int32_t*)d_stb, d_status, d_aux);
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a kernel of the aggregate verify failed to launch"));
+  if ((rc = keys.fin(c, d_status, d_aux))) return drain(rc);
+  KL(KID_AGG_SEG_FIN, k_aggm_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const uint32_t*)d_skipped, d_status, d_aux);
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_aggm_fin failed to launch"));
+  if (aux && (rc = stage_back(c, aux, d_aux, 16 * n_sets))) return drain(rc);
+  return drain(status_out_and_sync(c, status, d_status, n_sets));
+}
+}  // extern "C++"
+static int aggregate_msgset_entry(uint64_t msgset, const uint32_t* msg_idx, bool indexed, uint64_t keyset, const uint32_t* idx, const void* pks,
+                                  const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) {
+  MsgSet m;
+  int rc = msgset_find(msgset, m);
+  if (rc) return rc;
+  KeySet k;
+  if (indexed) {
+    if ((rc = keyset_find(keyset, k))) return rc;
+    if (k.sig_group != m.sig_group) return fail(BLSGPU_E_ARG, "the key set belongs to the other orientation");
+    if (k.dev != m.dev || k.devidx != m.devidx) return fail(BLSGPU_E_ARG, "the key set and the message set live on different devices");
+  }
+  const int sg = m.sig_group;
+  if ((rc = check_common(sg, m.scheme, fmt))) return rc;
+  if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
+  if (n_sets && (!sigs || !status)) return fail(BLSGPU_E_ARG, "null argument");
+  std::vector<uint64_t> offs;
+  if ((rc = read_offsets(set_offsets, n_sets, "set_offsets", offs))) return rc;
+  const size_t T = (size_t)offs[n_sets];
+  if (T >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more pairs in one call");
+  if (T && (!msg_idx || (indexed ? !idx : !pks))) return fail(BLSGPU_E_ARG, "null argument");
+  if (n_sets == 0) return 0;
+  CTX_ACQUIRE_ON(c, m.devidx);                 // on the message set's device, without sharding
+  if (indexed) {
+    const agg_keys_indexed keys = {k, idx, offs, n_sets, fmt, false, agg_keys_indexed::bytes_for(k, T, n_sets, fmt)};
+    return aggregate_msgset_run(c, m, keys, msg_idx, offs, n_sets, sigs, fmt, status, aux);
+  }
+  const size_t psz = pk_size(sg, fmt);
+  const agg_keys_by_value keys = {pks, psz * T, pad256(psz * T)};
+  return aggregate_msgset_run(c, m, keys, msg_idx, offs, n_sets, sigs, fmt, status, aux);
+}
+int blsgpu_aggregate_verify_msgset_batch(uint64_t msgset, const uint32_t* msg_idx, const void* pks, const uint64_t* set_offsets, size_t n_sets, const void* sigs,
+                                         int fmt, int32_t* status, uint64_t* aux) try {
+  return aggregate_msgset_entry(msgset, msg_idx, false, 0, nullptr, pks, set_offsets, n_sets, sigs, fmt, status, aux);
+}
+API_CATCH
+int blsgpu_aggregate_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx, const uint64_t* set_offsets,
+                                                 size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) try {
+  return aggregate_msgset_entry(msgset, msg_idx, true, keyset, idx, nullptr, set_offsets, n_sets, sigs, fmt, status, aux);
 }
 API_CATCH
 

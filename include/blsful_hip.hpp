@@ -349,6 +349,30 @@ struct AggregateSignature {
     if (rc) return detail::runtime_error(rc);
     return detail::from_status(st, aux, true);
   }
+  // The same with every message named as an entry of a registered message set (blsgpu_msgset_create, include/blsgpu.h) of this
+  // orientation and the signature's scheme: blsgpu_aggregate_verify_msgset_batch with one set.  The keys of equal messages are summed
+  // and paired once and nothing is hashed; the verdict is verify()'s under the entries' message bytes.  (Over a registered key set
+  // too: blsgpu_aggregate_verify_msgset_indexed_batch.)
+  BlsResult<Unit> verify_msgset(uint64_t msgset, const std::vector<std::pair<PublicKey<C>, uint32_t>>& data) const {
+    if (int rc = detail::ensure_init()) return detail::runtime_error(rc);
+    int set_group = 0, set_scheme = 0;
+    if (int rc = blsgpu_msgset_info(msgset, &set_group, &set_scheme, nullptr, nullptr, nullptr)) return detail::runtime_error(rc);
+    if (set_group != C::SIG_GROUP || set_scheme != (int)sig.scheme) return BlsError{BlsError::Kind::InvalidSignatureScheme, ""};
+    const size_t n = data.size();
+    Bytes pks(n * C::PK_RAW);
+    std::vector<uint32_t> idx(n);
+    for (size_t i = 0; i < n; i++) {
+      std::memcpy(&pks[i * C::PK_RAW], data[i].first.raw.data(), C::PK_RAW);
+      idx[i] = data[i].second;
+    }
+    const uint64_t offs[2] = {0, (uint64_t)n};
+    int32_t st = 0;
+    uint64_t aux[2] = {0, 0};
+    int rc = blsgpu_aggregate_verify_msgset_batch(msgset, idx.data(), pks.data(), offs, 1, sig.raw.data(), BLSGPU_FMT_RAW_PROJ, &st, aux);
+    if (rc) return detail::runtime_error(rc);
+    if (st == BLSGPU_E_ARG) return BlsError{BlsError::Kind::InvalidInputs, "Message index outside the message set"};
+    return detail::from_status(st, aux, true);
+  }
 };
 
 template <class C>

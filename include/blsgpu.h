@@ -782,6 +782,36 @@ int blsgpu_verify_msgset_batch(uint64_t msgset, const uint32_t* msg_idx, const v
  * BLSGPU_WIDE_MAX items needs nothing but its signature. */
 int blsgpu_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx, const void* sigs,
                                        const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status);
+/* blsgpu_aggregate_verify_batch with pair i's message named as entry msg_idx[i] of a message set (msg_idx has set_offsets[n_sets] =
+ * T entries): AggregateSignature::verify over registered messages.  sig_group and scheme (Basic or ProofOfPossession) come from the
+ * set; pks, set_offsets, sigs, fmt, status, aux (NULL or 2 n_sets entries) and the T < 2^32 rule are the by-value entry point's.
+ * Every pointer may be host or device memory; a device status / aux stays on the device.  set_offsets is read and checked on the
+ * host, msg_idx on the device.  n_sets == 0 returns 0.  An unknown or destroyed handle, offsets that decrease or do not start at
+ * 0, and a null required argument are BLSGPU_E_ARG, and nothing is written.  The call runs on the message set's device.
+ * By bilinearity the pairs of a set that name one message are ONE factor e(sum of their keys, H(m)): the call forms one Miller
+ * value per (set, message) class and one per signature, sums the keys of a class with the complete additions of the batched multi
+ * verify (the same key twice is a doubling; P and -P give the identity, whose factor is 1 -- not an error), and hashes nothing.
+ * status[s] / aux[2 s ..] is the first of: BLSGPU_E_ARG in the slot, aux (0, 0), when the set names a message index outside the
+ * message set (nothing outside the table is read, other sets are unaffected, the call returns 0); otherwise exactly what
+ * blsgpu_aggregate_verify_batch returns for those keys under the entries' message bytes -- Basic's duplicate rule with aux
+ * (earlier, i), the identity signature, the first identity key with its 1-based index in INPUT order, the pairing product, the
+ * empty-set rules.  All of these are decided on the pairs before anything is merged.
+ * The duplicate rule without message bytes: a message set keeps no bytes, so under Basic two pairs of one set have "the same
+ * message" when their entries hold equal affine hash records -- the same position named twice, or two positions created from
+ * equal bytes.  The one assumption: unequal bytes never give equal records (that would be a hash-to-curve collision).  Under
+ * ProofOfPossession classes go by position; two positions of equal bytes may stay two classes, the product is the same.
+ * Every set runs through the segmented kernels whatever its size: BLSGPU_AGG_BATCH_MAX does not apply, because there are no
+ * message bytes to hand to the single call's path.  With BLSGPU_MSGSET_LINES (Bls12381G2Impl) the class items take both lines of
+ * every step from the entries' rows and only the n_sets signature items walk a G2 point; a call that names an entry without usable
+ * rows walks all its items.  Rows change the plan, never a status or an aux value. */
+int blsgpu_aggregate_verify_msgset_batch(uint64_t msgset, const uint32_t* msg_idx, const void* pks, const uint64_t* set_offsets, size_t n_sets,
+                                         const void* sigs, int fmt, int32_t* status, uint64_t* aux);
+/* The same with pair i's key at position idx[i] of a registered key set of the same orientation on the same device (anything else:
+ * BLSGPU_E_ARG).  status[s]: the message index rule above first; then the key set's two rules in their order (a position outside
+ * the table, then the creation status of the first invalid entry in input order; aux (0, 0)); then the verification.  Key set
+ * line tables are not used by these entry points: a summed key has no table. */
+int blsgpu_aggregate_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx,
+                                                 const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux);
 
 #ifdef __cplusplus
 }
