@@ -42,7 +42,7 @@ EXPORTS = [
     'blsgpu_aggregate_partial', 'blsgpu_fp12_product_is_one', 'blsgpu_core_verify', 'blsgpu_deserialize', 'blsgpu_pop_verify_batch', 'blsgpu_aggregate_secure',
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
-    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_map_to_curve', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_wide_steps', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_map_to_curve', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
@@ -167,6 +167,7 @@ def load_library(path=None):
         lib.blsgpu_core_verify_hashed.argtypes = [ci, vp, vp, vp, sz, i32p]
         lib.blsgpu_debug_wide_mul.argtypes = [u8p, u8p, sz, ci, u8p]
         lib.blsgpu_debug_wide_program.argtypes = [vp, sz, ci, u8p, u8p]
+        lib.blsgpu_debug_wide_steps.argtypes = [ci, vp, sz, ci, sz, vp, sz, vp, ctypes.c_int32, vp, sz, vp]
         lib.blsgpu_debug_finalexp_batch.argtypes = [vp, sz, ci, sz, i32p]
         lib.blsgpu_debug_field_op_shape.argtypes = [ci] + [ctypes.POINTER(ctypes.c_int)] * 5
         lib.blsgpu_debug_field_op.argtypes = [ci, i32p, sz, ci, i32p]
@@ -1474,6 +1475,38 @@ def debug_wide_program(steps, f_raw, reps=1):
     out = ctypes.create_string_buffer(576)
     _check(lib.blsgpu_debug_wide_program(ctypes.cast(arr, ctypes.c_void_p), len(steps), reps, _ptr(b''.join(f_raw)), ctypes.cast(out, ctypes.c_void_p)))
     return [out.raw[48 * i:48 * (i + 1)] for i in range(12)]
+
+
+WIDE_SET_F12, WIDE_SET_PT = 0, 1
+
+
+def debug_wide_steps(table_set, steps, in_idx, items, out_idx, fill=0, reps=1):
+    """Any table operation of the row-wide engine on caller-supplied limbs (blsgpu_debug_wide_steps).  table_set: WIDE_SET_F12 /
+    WIDE_SET_PT; steps: [(operation id, dst, a, b)] as numbers (value-store indices, the program format of csrc/wide_tables.cuh);
+    in_idx: the value indices that take an item's inputs; items: per item one sixteen-word vector (signed 32-bit) per input value;
+    out_idx: the value indices to read back.  Every other word of the store is `fill` before staging.  Returns per item the
+    sixteen-word vectors of the out_idx values after `reps` runs of the program, one 256-thread workgroup per item."""
+    lib = init()
+    words = []
+    for op, dst, a, b in steps:
+        words += [(op & 0xffff) | (dst & 0xffff) << 16, (a & 0xffff) | (b & 0xffff) << 16]
+    n, n_in, n_out = len(items), len(in_idx), len(out_idx)
+    flat = []
+    for vecs in items:
+        assert len(vecs) == n_in and all(len(v) == 16 for v in vecs)
+        for v in vecs:
+            flat += v
+    prog = (ctypes.c_uint32 * max(len(words), 1))(*words)
+    ii = (ctypes.c_uint32 * max(n_in, 1))(*in_idx)
+    oi = (ctypes.c_uint32 * max(n_out, 1))(*out_idx)
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    out = (ctypes.c_int32 * max(16 * n_out * n, 1))()
+    if fill >= 2**31:
+        fill -= 2**32
+    _check(lib.blsgpu_debug_wide_steps(table_set, ctypes.cast(prog, ctypes.c_void_p), len(steps), reps, n, ctypes.cast(ii, ctypes.c_void_p), n_in,
+                                       ctypes.cast(arr, ctypes.c_void_p), fill, ctypes.cast(oi, ctypes.c_void_p), n_out, ctypes.cast(out, ctypes.c_void_p)))
+    o = list(out)
+    return [[o[16 * (n_out * i + k):16 * (n_out * i + k + 1)] for k in range(n_out)] for i in range(n)]
 
 
 def first_duplicate_message(msgs):

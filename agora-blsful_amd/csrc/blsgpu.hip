@@ -3514,6 +3514,47 @@ int blsgpu_debug_wide_program(const uint32_t* prog, size_t len, int reps, const 
 }
 API_CATCH
 
+/* Self-test hook of the row-wide engine, operation by operation (include/blsgpu.h): k_wide_steps_test on n workgroups.  The program
+ * is validated here -- wide_steps_ok: table operations and FPINV only, every reference inside the store -- so that nothing a caller
+ * passes can make a workgroup wait on a partner or address LDS outside its value store. */
+int blsgpu_debug_wide_steps(int set, const uint32_t* prog, size_t len, int reps, size_t n, const uint32_t* in_idx, size_t n_in, const int32_t* in,
+                            int32_t fill, const uint32_t* out_idx, size_t n_out, int32_t* out) try {
+  if (!initialised()) return NOT_INIT();
+  if ((set != 0 && set != 1) || !prog || reps < 1 || reps > 4096 || n < 1 || n > 4096 || n_out < 1 || !out_idx || !out || (n_in && (!in_idx || !in)) ||
+      is_device_ptr(prog) || is_device_ptr(in_idx) || is_device_ptr(out_idx))
+    return fail(BLSGPU_E_ARG, "bad argument");
+  if (!wide_steps_ok(set, prog, len)) return fail(BLSGPU_E_ARG, "program: empty, too long, not a table operation of the set, or a reference past the value store");
+  const size_t nv = (size_t)wide_steps_nv(set);
+  if (n_in > nv || n_out > nv) return fail(BLSGPU_E_ARG, "more values than the store holds");
+  for (size_t k = 0; k < n_in; k++)
+    if (in_idx[k] >= nv) return fail(BLSGPU_E_ARG, "input value index past the value store");
+  for (size_t k = 0; k < n_out; k++)
+    if (out_idx[k] >= nv) return fail(BLSGPU_E_ARG, "output value index past the value store");
+  CTX_ACQUIRE(c);
+  const size_t in_bytes = 64 * n_in * n, out_bytes = 64 * n_out * n;
+  int rc = arena_reserve(c, pad256(8 * len) + pad256(4 * n_in + 4) + pad256(4 * n_out) + pad256(in_bytes + 4) + pad256(out_bytes) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_prog, *d_ii = nullptr, *d_oi, *d_in = nullptr;
+  if ((rc = stage_in(c, prog, 8 * len, &d_prog))) return rc;
+  if (n_in && (rc = stage_in(c, in_idx, 4 * n_in, &d_ii))) return rc;
+  if ((rc = stage_in(c, out_idx, 4 * n_out, &d_oi))) return rc;
+  if (n_in && (rc = stage_in(c, in, in_bytes, &d_in))) return rc;
+  int32_t* d_out = stage_out<int32_t>(c, out, out_bytes);
+  if (!d_out) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (set == 0)
+    KL(KID_WIDE, k_wide_steps_test<0>, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), (const uint32_t*)d_prog, (int)len, reps, (int)n_in, (const uint32_t*)d_ii,
+       (const int32_t*)d_in, (uint32_t)fill, (int)n_out, (const uint32_t*)d_oi, d_out);
+  else
+    KL(KID_WIDE, k_wide_steps_test<1>, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), (const uint32_t*)d_prog, (int)len, reps, (int)n_in, (const uint32_t*)d_ii,
+       (const int32_t*)d_in, (uint32_t)fill, (int)n_out, (const uint32_t*)d_oi, d_out);
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out, d_out, out_bytes))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
 /* Self-test hook of the batch final exponentiation + verdict (run_pairing2's two-lane forms) on caller-supplied Fp12 records (576
  * bytes, the record format of blsgpu_fp12_product_is_one).  form 0: k_finalexp2s, 1: k_finalexp_seg + k_cyc_run4, both chunk by
  * chunk through launch_finalexp_chunk with the line workspace as the value store, as the verify path runs them; 2: k_finalexps.

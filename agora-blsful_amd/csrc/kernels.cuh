@@ -365,6 +365,12 @@ __global__ void k_f12_tree_seg(size_t qin, const uint32_t* fin, size_t sin, size
 __global__ void k_f12_horner_wide(const uint32_t* fin, size_t sin, uint32_t* fout, size_t sout);
 __global__ void k_wide_prog_test(const uint32_t* prog, int len, int reps, const uint8_t* fin, uint8_t* tout);
 bool wide_prog_is_fp12(const uint32_t* prog, size_t len);   // host: what k_wide_prog_test may be given
+// self-test: any table operation of either set (SET 0: F12, 1: PT) on caller-supplied limbs, one workgroup per item
+template <int SET>
+__global__ void k_wide_steps_test(const uint32_t* prog, int len, int reps, int n_in, const uint32_t* in_idx, const int32_t* in, uint32_t fill, int n_out,
+                                  const uint32_t* out_idx, int32_t* out);
+bool wide_steps_ok(int set, const uint32_t* prog, size_t len);   // host: what k_wide_steps_test may be given
+int wide_steps_nv(int set);                                       // host: values of the set's store
 __global__ void k_pairing_wide(size_t n, const uint32_t* pairs, int32_t* status, int fixed_g2);
 template <bool UB>
 __global__ void k_hash_to_g1_wide(size_t n, const uint8_t* msgs, const uint64_t* offs, int single_msg, dst_arg dst, uint8_t* out, uint32_t* rec);
@@ -3466,6 +3472,21 @@ __global__ void __launch_bounds__(WIDE_BLOCK) k_wide_mul_test(size_t n, const ui
 #endif
 #if defined(BLS_TU_WIDE) || defined(BLS_TU_DEBUG_H2C_WIDE)
 #include "wide_engine.cuh"
+// the constants of table set PT -> their values of the store (set F12's Frobenius constants travel inside wide_stage); the caller's
+// barrier publishes them.  psi's cx, cy (real, imaginary limbs): thread t of 64
+__device__ __forceinline__ void wide_stage_psi(wide_lds_t<wide_tb_pt>& S, int t) {
+  const int v = t >> 4, l = t & 15;
+  const uint32_t* src = v < 2 ? PSI_CX : PSI_CY;
+  S.V[WPV_CONST + v][l] = l < FP_NL ? src[(v & 1) * FP_NL + l] : 0u;
+}
+// the 11-isogeny's 55 coefficients (xnum, xden, ynum, yden): thread t of nthreads
+__device__ __forceinline__ void wide_stage_iso(wide_lds_t<wide_tb_pt>& S, int t0, int nthreads) {
+  for (int t = t0; t < 55 * 16; t += nthreads) {
+    const int v = t >> 4, ll = t & 15;
+    const uint32_t* src = v < 12 ? ISO1_XNUM[v] : (v < 23 ? ISO1_XDEN[v - 12] : (v < 39 ? ISO1_YNUM[v - 23] : ISO1_YDEN[v - 39]));
+    S.V[WPV_CONST + WIDE_PT_ISO_K + v][ll] = ll < FP_NL ? src[ll] : 0u;
+  }
+}
 #endif
 #if defined(BLS_TU_WIDE)
 bool wide_prog_is_fp12(const uint32_t* prog, size_t len) {
@@ -3509,6 +3530,55 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_wide_prog_test(const uint
     fp_to_raw((uint32_t*)(tout + 48 * threadIdx.x), x);
   }
 }
+// self-test: ANY operation of either table set on caller-supplied limbs (blsgpu_debug_wide_steps; tests/test_gpu_wide_ops.py).  One
+// workgroup per item, all running the same program `reps` times.  Every word of the store is `fill` first; then the set's constants
+// are staged as the shipped kernels stage them, the caller's n_in values (sixteen words each, item-major) go to the values in_idx
+// names, and after the run the n_out values out_idx names come back.  The host entry has validated the program (wide_steps_ok):
+// table operations and FPINV only, every reference inside the store.
+template <int SET>
+struct wide_tb_of { typedef wide_tb_f12 type; };
+template <>
+struct wide_tb_of<1> { typedef wide_tb_pt type; };
+#if !defined(__HIP_DEVICE_COMPILE__)          // host only: the extent arrays do not exist in the device pass
+template <class TB>
+static bool wide_steps_ok_tb(const uint32_t* prog, size_t len) {
+  if (len < 1 || len > (size_t)TB::PROG_MAX) return false;
+  for (size_t k = 0; k < len; k++) {
+    const uint32_t w0 = prog[2 * k], w1 = prog[2 * k + 1], op = w0 & 0xffffu, d = w0 >> 16, a = w1 & 0xffffu, b = w1 >> 16;
+    if (d >= (uint32_t)TB::NV || a >= (uint32_t)TB::NV || b >= (uint32_t)TB::NV) return false;
+    if ((int)TB::OP_INV >= 0 && op == (uint32_t)TB::OP_INV) continue;        // FPINV: single values
+    if (op >= (uint32_t)TB::NOPS) return false;                              // past the table; the hand-over built-ins wait on a partner
+    const uint16_t* e = TB::extent(op);
+    if (d + e[0] > (uint32_t)TB::NV || a + e[1] > (uint32_t)TB::NV || b + e[2] > (uint32_t)TB::NV) return false;
+  }
+  return true;
+}
+bool wide_steps_ok(int set, const uint32_t* prog, size_t len) { return set == 0 ? wide_steps_ok_tb<wide_tb_f12>(prog, len) : wide_steps_ok_tb<wide_tb_pt>(prog, len); }
+int wide_steps_nv(int set) { return set == 0 ? (int)wide_tb_f12::NV : (int)wide_tb_pt::NV; }
+#endif
+template <int SET>
+__global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_wide_steps_test(const uint32_t* prog, int len, int reps, int n_in, const uint32_t* in_idx, const int32_t* in,
+                                                                     uint32_t fill, int n_out, const uint32_t* out_idx, int32_t* out) {
+  typedef typename wide_tb_of<SET>::type TB;
+  __shared__ wide_lds_t<TB> S;
+  const size_t item = blockIdx.x;
+  wide_consts K;
+  wide_init(K);
+  for (int t = threadIdx.x; t < (int)TB::NV * 16; t += WIDE_ENGINE_BLOCK) S.V[t >> 4][t & 15] = fill;
+  __syncthreads();
+  wide_stage(S, prog, len);
+  if constexpr (SET == 1) {
+    if (threadIdx.x < 64) wide_stage_psi(S, (int)threadIdx.x);
+    else wide_stage_iso(S, (int)threadIdx.x - 64, WIDE_ENGINE_BLOCK - 64);
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < n_in * 16; t += WIDE_ENGINE_BLOCK) S.V[in_idx[t >> 4]][t & 15] = (uint32_t)in[(item * (size_t)n_in + (t >> 4)) * 16 + (t & 15)];
+  __syncthreads();
+  for (int r = 0; r < reps; r++) wide_exec(S, len, K);
+  for (int t = threadIdx.x; t < n_out * 16; t += WIDE_ENGINE_BLOCK) out[(item * (size_t)n_out + (t >> 4)) * 16 + (t & 15)] = (int32_t)S.V[out_idx[t >> 4]][t & 15];
+}
+template __global__ void k_wide_steps_test<0>(const uint32_t*, int, int, int, const uint32_t*, const int32_t*, uint32_t, int, const uint32_t*, int32_t*);
+template __global__ void k_wide_steps_test<1>(const uint32_t*, int, int, int, const uint32_t*, const int32_t*, uint32_t, int, const uint32_t*, int32_t*);
 // the hard part of the final exponentiation and the comparison with one, one 256-thread workgroup per item
 __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_finalexp_wide(size_t n, const uint32_t* easy, int32_t* status) {
   __shared__ wide_lds_t<wide_tb_f12> S;
@@ -4027,11 +4097,7 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_g2_clear_wide(size_t n, u
     fp_reduce(x, x);
     w_store_local(S.V[WPV_R0 + v], x);
   }
-  if (threadIdx.x >= 64 && threadIdx.x < 64 + 4 * 16) {   // psi's constants cx, cy (real, imaginary limbs)
-    const int t = (int)threadIdx.x - 64, v = t >> 4, l = t & 15;
-    const uint32_t* src = v < 2 ? PSI_CX : PSI_CY;
-    S.V[WPV_CONST + v][l] = l < FP_NL ? src[(v & 1) * FP_NL + l] : 0u;
-  }
+  if (threadIdx.x >= 64 && threadIdx.x < 64 + 4 * 16) wide_stage_psi(S, (int)threadIdx.x - 64);   // psi's constants cx, cy
   __syncthreads();
   wide_exec(S, WIDE_PROG_G2_CLEAR_LEN, K);
   if (threadIdx.x < 6) {
@@ -4365,11 +4431,7 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g1_engine(size_t 
       iso[2][l] = (uint32_t)t.v;
     }
   } else {                                                  // meanwhile: the isogeny's 55 coefficients into the constants (xnum, xden, ynum, yden)
-    for (int t = (int)threadIdx.x - 64; t < 55 * 16; t += WIDE_ENGINE_BLOCK - 64) {
-      const int v = t >> 4, ll = t & 15;
-      const uint32_t* src = v < 12 ? ISO1_XNUM[v] : (v < 23 ? ISO1_XDEN[v - 12] : (v < 39 ? ISO1_YNUM[v - 23] : ISO1_YDEN[v - 39]));
-      S.V[WPV_CONST + WIDE_PT_ISO_K + v][ll] = ll < FP_NL ? src[ll] : 0u;
-    }
+    wide_stage_iso(S, (int)threadIdx.x - 64, WIDE_ENGINE_BLOCK - 64);
   }
   __syncthreads();
   for (int pass = 0;; pass++) {
@@ -4472,9 +4534,7 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_hash_to_g2_engine(size_t 
     else expand_message_xmd_wave<256>(ubw, msgs + offs[mi], (uint32_t)(offs[mi + 1] - offs[mi]), dst, shablk);   // the whole wave
     if (row < 2) hash_g2_map_row(ubw, row, l, &S.V[row == 1 ? WPV_R1 : WPV_R0]);
   } else if (threadIdx.x < 64 + 4 * 16) {                   // meanwhile: psi's constants cx, cy (real, imaginary limbs)
-    const int t = (int)threadIdx.x - 64, v = t >> 4;
-    const uint32_t* src = v < 2 ? PSI_CX : PSI_CY;
-    S.V[WPV_CONST + v][l] = l < FP_NL ? src[(v & 1) * FP_NL + l] : 0u;
+    wide_stage_psi(S, (int)threadIdx.x - 64);
   }
   __syncthreads();
   wide_exec(S, WIDE_PROG_G2_HASH_TAIL_LEN, K);
@@ -4517,10 +4577,7 @@ __global__ void __launch_bounds__(WIDE_ENGINE_BLOCK) k_g2_hash_tail_wide(size_t 
   wide_stage(S, WIDE_PROG_G2_HASH_TAIL, WIDE_PROG_G2_HASH_TAIL_LEN);
   const int v = (int)(threadIdx.x >> 4), l = (int)(threadIdx.x & 15u);
   if (v < 12) S.V[(v < 6 ? WPV_R0 : WPV_R1 - 6) + v][l] = pts[(i * 12 + v) * 16 + l];
-  else if (v < 16) {
-    const uint32_t* src = v < 14 ? PSI_CX : PSI_CY;
-    S.V[WPV_CONST + v - 12][l] = l < FP_NL ? src[(v & 1) * FP_NL + l] : 0u;
-  }
+  else if (v < 16) wide_stage_psi(S, (int)threadIdx.x - 12 * 16);
   __syncthreads();
   wide_exec(S, WIDE_PROG_G2_HASH_TAIL_LEN, K);
   if (rec && (threadIdx.x >> 4) < 6)     // the cut check's record takes H(m) as it stands here: six engine values, Jacobian (what k_prepare_keys part 4 would write)

@@ -13,7 +13,9 @@
 // partial-product column pair.  Montgomery reduction (R = 2^392, as fp.cuh) word by word: step s broadcasts column s,
 // every lane derives the same quotient digit q_s and adds q_s * p into its two columns; the running carry lives replicated
 // on every lane, so no lane-selective operation is needed.  Two parallel carry passes leave the limbs normalised.
-// Device only (DPP); checked against the oracle through blsgpu_debug_wide_mul (tests/test_gpu_wide.py).
+// Device only (DPP); checked against the oracle through blsgpu_debug_wide_mul (tests/test_gpu_wide.py) and, as the engine's product
+// and reduction halves (w_mul_cols, w_redc_cols) at extreme limbs, through blsgpu_debug_wide_steps (tests/test_gpu_wide_ops.py); the
+// bounds stated below are checked against every table row by tests/test_wide_bounds.py.
 #pragma once
 #include "fp.cuh"
 
@@ -153,7 +155,8 @@ __device__ __forceinline__ void w_mul_cols(int32_t& clo, int32_t& chi, wfp a, wf
   chi = hf0 + w_shr<1>(hf1) + w_shr<2>(hf2) + w_shl<15>(lf1) + w_shl<14>(lf2);   // columns 15 -> 16, 14 -> 16, 15 -> 17
 }
 // w_redc_cols: Montgomery reduction of 28 columns (lane k: column k in lo, column 16 + k in hi; magnitudes below 2^62) to
-// the 64-bit limb sums of T / R mod p (lane j: limb j, below 2^40), ready for w_finish / a carry pass
+// the 64-bit limb sums of T / R mod p (lane j: limb j, below 2^59: a column that survives grows by up to sum q_s p_(14+j-s) = 2^58.91),
+// ready for w_finish
 __device__ __forceinline__ int64_t w_redc_cols(int64_t lo, int64_t hi, const wide_consts& K) {
   int64_t cy = 0;
   w_mul_redc_step<0>(lo, hi, cy, K);
@@ -255,7 +258,8 @@ __device__ __forceinline__ void fp_dbl(wf& r, const wf& a) { r.v = a.v + a.v; }
 __device__ __forceinline__ void fp_norm(wf& r, const wf& a) { r.v = wf_norm1(a.v); }
 __device__ __forceinline__ void fp_cmov(wf& r, const wf& a, bool c) { r.v = c ? a.v : r.v; }
 // value brought back to (-0.6 p, 0.6 p) (nearest multiple of p estimated from the top limb), limbs normalised; the input may
-// carry limbs up to 2^31 in magnitude and a value of a few dozen p
+// carry limbs up to 2^31 in magnitude and a value of up to 20,000 p: the top limb after the carry pass (unit p / 106,513.1) must fit
+// 32 bits, and the float estimate stays within 0.6 of value / p beyond that (the derivation is in tests/test_wide_bounds.py)
 __device__ __forceinline__ void fp_reduce(wf& r, const wf& a) {
   const wfp v1 = wf_norm1(a.v);
   const int32_t top = w_bcast<13>(v1);

@@ -318,6 +318,20 @@ int blsgpu_debug_wide_mul(const uint8_t* a, const uint8_t* b, size_t n, int reps
  * format of csrc/wide_tables.cuh, Fp12 operations on the arrays F, T, U, W, ACC only) `reps` times on one workgroup with
  * F = U = W = ACC = the Fp12 at f_in (twelve 48-byte Montgomery elements) and T = 0; t_out <- T.  prog: host memory. */
 int blsgpu_debug_wide_program(const uint32_t* prog, size_t len, int reps, const uint8_t* f_in, uint8_t* t_out);
+/* Self-test hook of the engine operation by operation (not part of the reference interface): ANY table operation of either set on
+ * caller-supplied limbs.  set: 0 = F12 (wide_tb_f12), 1 = PT (wide_tb_pt).  prog: len steps of two words, the format of
+ * csrc/wide_tables.cuh, len <= the set's PROG_MAX; it runs `reps` times on each of n 256-thread workgroups (n <= 4096), one item
+ * each.  Before staging every word of every value of an item's store is `fill`; then the set's constants are staged as the shipped
+ * kernels stage them, and the n_in values in_idx names take the item's inputs: `in` is n x n_in x sixteen signed 32-bit words, the
+ * internal form (28-bit limbs at words 0..13, R = 2^392, as blsgpu_debug_field_op passes them; words 14 and 15 as given).  After the
+ * run the n_out values out_idx names come back the same way (out: n x n_out x sixteen words); the whole store may be asked for.
+ * BLSGPU_E_ARG, and nothing is launched: an operation id that is neither in the set's table nor FPINV (set F12 only) -- the
+ * hand-over built-ins ACQ, PUB, ACQF, PUBF are always refused --, a step whose destination or operand reference, extended by what
+ * the operation reads or writes from it, passes the set's value count, an empty program or one longer than PROG_MAX, a value index
+ * past the store.  The caller keeps the operands inside the engine's input contract (|value| < 0.6 p, limbs after a carry pass);
+ * nothing else is checked here.  Host pointers. */
+int blsgpu_debug_wide_steps(int set, const uint32_t* prog, size_t len, int reps, size_t n, const uint32_t* in_idx, size_t n_in, const int32_t* in,
+                            int32_t fill, const uint32_t* out_idx, size_t n_out, int32_t* out);
 /* Self-test hook of the batch final exponentiation + verdict on caller-supplied Fp12 records (576 B, the record format of
  * blsgpu_fp12_product_is_one).  form 0 = k_finalexp2s, 1 = k_finalexp_seg + k_cyc_run4, 2 = k_finalexps; chunk = items per chunk
  * of the chunked forms (0: the library's).  status is in/out: an entry that is not BLSGPU_OK on entry is skipped and left as it

@@ -28,8 +28,37 @@ X_ABS = 0xd201000000010000       # |x| of the curve (x < 0)
 NSTEPS = 68                      # Miller steps: 63 doublings interleaved with 5 additions
 
 
+# Magnitudes the engine's arithmetic is written for (csrc/wide.cuh, csrc/wide_engine.cuh); every row is checked against them when it
+# is built, and tests/test_wide_bounds.py derives the same figures from the device code and walks every row of both sets again.
+LIMB_MAX = 2**28 + 8             # a limb after a carry pass (w_norm)
+COL_MAX = int(2**29.6) + 1       # a column of an unreduced product as w_mul_cols leaves it: below 2^29.6
+REDC_COL_MAX = 2**62             # a column sum going into w_redc_cols
+VALUE_MAX = (3, 5)               # every value of the store lies inside (-0.6 p, 0.6 p); the constants (canonical) inside [0, p)
+FINISH_MAX_P = 20000             # |value| / p that w_finish brings back to (-0.6 p, 0.6 p): its top limb (unit p / 106,513.6) fits 32 bits
+
+
 def idx(slot, off):
     return (slot << 12) | off
+
+
+def lin_bounds(op, terms):
+    """(largest column sum going into w_redc_cols, bound on |value| / p going into w_finish) of a linear row: a product term is the
+    28 columns of its scratch entry (value a b / R, |a|, |b| below their coefficient sums times p: a constant may be canonical), a
+    plain term its limbs at columns 14.. (value up to 0.6 p); the reduction adds q p / R < p"""
+    from fractions import Fraction
+    by_out = {o: (a, b) for a, b, o in op.prods}
+    cols, value = 0, Fraction(0)
+    for k, i in terms:
+        if (i >> 12) == TMP:
+            a, b = by_out[i]
+            cols += abs(k) * COL_MAX
+            value += abs(k) * sum(abs(x) for x, _ in a) * sum(abs(x) for x, _ in b) * Fraction(P, 2**392)
+        else:
+            cols += abs(k) * LIMB_MAX
+            value += abs(k) * Fraction(*VALUE_MAX)
+    if any((i >> 12) == TMP for _, i in terms):
+        value += 1
+    return cols, value
 
 
 class Op:
@@ -45,6 +74,10 @@ class Op:
 
     def prod(self, a, b):
         assert 1 <= len(a) <= 2 and 1 <= len(b) <= 2
+        sa, sb = sum(abs(k) for k, _ in a), sum(abs(k) for k, _ in b)
+        assert all(-128 <= k < 128 for k, _ in a + b), (self.name, a, b)                 # packed as signed bytes
+        assert max(sa, sb) * LIMB_MAX < 2**31, (self.name, a, b)                          # the operand sum is cast to 32 bits
+        assert 14 * (sa * LIMB_MAX) * (sb * LIMB_MAX) < 2**62, (self.name, a, b)           # w_mul_cols: column sums below 2^62
         t = self.tmp()
         self.prods.append((a, b, t))
         return t
@@ -52,6 +85,10 @@ class Op:
     def lin(self, terms, out):
         terms = [(k, i) for k, i in terms if k]        # an empty list writes zero
         assert len(terms) <= MAXLIN, (self.name, len(terms))
+        assert all(-32768 <= k < 32768 for k, _ in terms), (self.name, terms)              # packed as signed 16-bit fields
+        cols, value = lin_bounds(self, terms)
+        assert cols < REDC_COL_MAX, (self.name, terms)                                    # w_redc_cols: column sums below 2^62
+        assert value < FINISH_MAX_P, (self.name, terms)                                   # w_finish: the top limb and its estimate
         self.lins.append((terms, out))
 
     # Fp2 helpers on symbolic values: an Fp2 is a pair of term lists (re, im), each a list of (coef, idx)
@@ -1126,6 +1163,24 @@ def layout_pt():
 
 
 # ------------------------------------------------------------------ emission
+def op_extents(op):
+    """(DST, A, B): one past the largest offset the operation touches from each of a step's three references.  A product's second
+    operand is addressed from B only when it names the slot SB: constants are absolute, and an operation whose second operands all
+    name SA reads them from A (bsel 2)"""
+    ext = {DST: 0, SA: 0, SB: 0}
+    for a, b, _ in op.prods:
+        for _, i in a + b:
+            if (i >> 12) in ext:
+                ext[i >> 12] = max(ext[i >> 12], (i & 0xfff) + 1)
+    for terms, o in op.lins:
+        ext[DST] = max(ext[DST], (o & 0xfff) + 1)
+        for _, i in terms:
+            if (i >> 12) == SA:
+                ext[SA] = max(ext[SA], (i & 0xfff) + 1)
+    ext[SA] = max(ext[SA], 1)          # an unused plain-value slot of a linear row still loads offset 0 of A
+    return ext[DST], ext[SA], ext[SB]
+
+
 def emit_set(out, ops, lay, programs, prefix, vprefix, trait, has_inv):
     """one table set in the interpreter's format (csrc/wide_engine.cuh): byte offsets into the value store, pre-resolved"""
     tmp_base = lay.base['TMP']
@@ -1181,6 +1236,14 @@ def emit_set(out, ops, lay, programs, prefix, vprefix, trait, has_inv):
     for name, po, lo, ns, nl, stv, bs, np_ in oprows:
         out.append('    {%d, %d, %d, %d, %d, %d},   // WOP_%s: %d products' % (po, lo, ns, nl, stv, bs, name, np_))
     out.append('};')
+    # host side only: how many values past a step's DST, A and B references the operation reads or writes (0: the reference is not
+    # used) -- what a caller-supplied program is checked against before it may run (blsgpu_debug_wide_steps)
+    out.append('#if !defined(__HIP_DEVICE_COMPILE__)')
+    out.append('static const uint16_t %s_EXTENT[%d][3] = {' % (prefix, len(ops)))
+    for op in ops:
+        out.append('    {%d, %d, %d},   // WOP_%s' % (op_extents(op) + (op.name,)))
+    out.append('};')
+    out.append('#endif')
     names = [o[0] for o in oprows]
     for k, name in enumerate(names):
         out.append('#define WOP_%s %d' % (name, k))
@@ -1219,6 +1282,9 @@ def emit_set(out, ops, lay, programs, prefix, vprefix, trait, has_inv):
     out.append('  WIDE_TB_FN const wide_prod* prods() { return %s_PROD; }' % prefix)
     out.append('  WIDE_TB_FN const uint32_t* lins() { return %s_LIN; }' % prefix)
     out.append('  WIDE_TB_FN const wide_op* ops() { return %s_OPS; }' % prefix)
+    out.append('#if !defined(__HIP_DEVICE_COMPILE__)')
+    out.append('  static inline const uint16_t* extent(unsigned op) { return %s_EXTENT[op]; }' % prefix)
+    out.append('#endif')
     out.append('};')
     return pmax
 
