@@ -56,6 +56,7 @@ EXPORTS = [
     'blsgpu_msgset_create', 'blsgpu_msgset_destroy', 'blsgpu_msgset_info', 'blsgpu_msgset_update', 'blsgpu_msgset_append',
     'blsgpu_verify_msgset_batch', 'blsgpu_verify_msgset_indexed_batch', 'blsgpu_debug_msgset_from_points', 'blsgpu_debug_coop_pairing_rows',
     'blsgpu_aggregate_verify_msgset_batch', 'blsgpu_aggregate_verify_msgset_indexed_batch',
+    'blsgpu_debug_lines',
 ]
 
 
@@ -204,6 +205,7 @@ def load_library(path=None):
         lib.blsgpu_verify_shared_indexed_batch.argtypes = [ci, h, u32p, vp, u64p, sz, u8p, u64p, ci, i32p]
         lib.blsgpu_aggregate_verify_indexed_batch.argtypes = [ci, h, u32p, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
         lib.blsgpu_debug_coop_pairing_keyed.argtypes = [ci, h, u32p, i32p, sz, i32p, i32p]
+        lib.blsgpu_debug_lines.argtypes = [ci, ci, i32p, sz, i32p, sz, h, u32p, sz, i32p, u64p]
         lib.blsgpu_hash_to_scalar.argtypes = [u8p, u64p, sz, u8p, sz, u8p]
         lib.blsgpu_sig_proof_challenge_batch.argtypes = [ci, vp, u64p, sz, ci, u8p]
         lib.blsgpu_sig_proof_timestamp_verify_batch.argtypes = [ci, ci, vp, vp, vp, u64p, u8p, u64p, sz, ci, ctypes.c_uint64, ctypes.c_int64, i32p]
@@ -1413,6 +1415,45 @@ def debug_coop_pairing_keyed(mode, keyset, idx, items, status=None):
         return list(st[:n])
     o = list(out)
     return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n)]
+
+
+# the kernels of blsgpu_debug_lines (include/blsgpu.h BLSGPU_LINES_*): name -> (id, limb vectors per item, Fp2 coefficients per entry)
+LINES_KERNELS = {'lines2s': (0, 12, 5), 'lines2s_keyed': (1, 12, 5), 'linesp1': (2, 6, 3), 'linesp12': (3, 6, 5), 'linesp4': (4, 6, 3),
+                 'lines_fixed': (5, 6, 3), 'linesp_keyed': (6, 6, 3), 'miller2s': (7, 12, 0)}
+
+
+def debug_lines(kernel, items, variant=0, status=None, chunk=0, keyset=None, idx=None, t_b=0):
+    """One shipped line kernel (a name of LINES_KERNELS), launched as the library launches it, chunk after chunk, on caller-supplied
+    items: twelve limb vectors per two-pair item, six per one-pair item of the product kernels.  Returns (per output item its 68
+    entries, each a list of five or three Fp2 coefficients as pairs of limb vectors -- 'linesp12': per virtual item, 'lines_fixed':
+    item 0 alone, 'miller2s': the twelve limb vectors of the value -- and the number of words the kernel wrote on lanes beyond a chunk's
+    items).  Every limb of an item the kernel skipped is COOP_SENTINEL."""
+    lib = init()
+    kid, nvec, ncoef = LINES_KERNELS[kernel]
+    n = len(items)
+    flat = []
+    for vecs in items:
+        assert len(vecs) == nvec and all(len(v) == 14 for v in vecs)
+        for v in vecs:
+            flat += v
+    n_out = (n + 1) // 2 if kernel == 'linesp12' else min(n, 1) if kernel == 'lines_fixed' else n
+    per = 168 if kernel == 'miller2s' else 68 * ncoef * 28
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
+    out = (ctypes.c_int32 * max(per * n_out, 1))()
+    stray = ctypes.c_uint64(0)
+    ix = _u32(idx if idx is not None else [0] * n)
+    _check(lib.blsgpu_debug_lines(kid, variant, ctypes.cast(arr, ctypes.c_void_p), n, ctypes.cast(st, ctypes.c_void_p), chunk, keyset.handle if keyset is not None else 0,
+                                  ctypes.cast(ix, ctypes.c_void_p), t_b, ctypes.cast(out, ctypes.c_void_p), ctypes.cast(ctypes.pointer(stray), ctypes.c_void_p)))
+    o = list(out)
+    if kernel == 'miller2s':
+        return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(n_out)], stray.value
+    res = []
+    for i in range(n_out):
+        base = per * i
+        res.append([[(o[base + (e * ncoef + k) * 28:base + (e * ncoef + k) * 28 + 14], o[base + (e * ncoef + k) * 28 + 14:base + (e * ncoef + k) * 28 + 28])
+                     for k in range(ncoef)] for e in range(68)])
+    return res, stray.value
 
 
 def debug_msgset_from_points(sig_group, points, lines=False):

@@ -3635,7 +3635,10 @@ int blsgpu_debug_field_op(int op, const int32_t* in, size_t n, int reps, int32_t
   const dim3 grid(blocks_for((size_t)s->lanes * n)), block(BLS_BLOCK);
 #define DBG_LAUNCH(kern) KL(KID_DEBUG_OPS, kern, grid, block, op, n, reps, (const int32_t*)d_in, rec_in, d_out, rec_out)
   if (s->lanes == 64) DBG_LAUNCH(k_dbg_coop);      // one workgroup per item: blocks_for(64 n) = n
-  else if (op >= DBG_G1_DBL) {                     // the curve layer
+  else if (op >= DBG_MILLER1_DBL) {                // the Miller steps, the merges and the row evaluation
+    if (s->lanes == 1) DBG_LAUNCH(k_dbg_miller1);
+    else DBG_LAUNCH(k_dbg_miller2s);
+  } else if (op >= DBG_G1_DBL) {                   // the curve layer
     if (s->lanes == 1) DBG_LAUNCH(k_dbg_pt1);
     else if (s->lanes == 2) DBG_LAUNCH(k_dbg_pt2s);
     else DBG_LAUNCH(k_dbg_g2q);
@@ -6331,6 +6334,147 @@ int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* i
       for (size_t comp = 0; comp < 2; comp++)
         for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * kk + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
     }
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* Self-test hook of the kernels that PRODUCE line values (include/blsgpu.h): each shipped line kernel, launched with the grid, row stride,
+ * first / count, lines3 offset and pass order of run_pairing2 / the product paths, one chunk after another, on caller-supplied items in
+ * the pair-workspace layout (word w = 14 * vector + limb of item i at ws[w * n + i]).  The line workspace is filled with the sentinel
+ * byte before every chunk and the chunk's rows are read back whole before the next one: what a kernel did not write reads as the
+ * sentinel, and *stray counts the words it wrote on lanes beyond the chunk's items, in pass 1's lines3 rows for a skipped item, or
+ * behind the rows it owns. */
+int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, const int32_t* status, size_t chunk, uint64_t keyset, const uint32_t* idx, size_t t_b,
+                       int32_t* out, uint64_t* stray) try {
+  if (!initialised()) return NOT_INIT();
+  const bool keyed = kernel == BLSGPU_LINES_2S_KEYED || kernel == BLSGPU_LINES_P_KEYED;
+  const bool two_pairs = kernel == BLSGPU_LINES_2S || kernel == BLSGPU_LINES_2S_KEYED || kernel == BLSGPU_LINES_MILLER2S;
+  const bool fixed_arg = kernel == BLSGPU_LINES_2S || kernel == BLSGPU_LINES_MILLER2S;
+  if (kernel < BLSGPU_LINES_2S || kernel > BLSGPU_LINES_MILLER2S || (fixed_arg && (variant < 0 || variant > 2)) || (kernel == BLSGPU_LINES_FIXED && variant != 1 && variant != 2))
+    return fail(BLSGPU_E_ARG, "unknown kernel or variant");
+  KeySet k;
+  if (keyed) {
+    int rc = keyset_find(keyset, k);
+    if (rc) return rc;
+    if (!k.lines || k.sig_group != 1) return fail(BLSGPU_E_ARG, "the key set has no line tables");
+  }
+  if (n == 0) return 0;
+  if (!items || !status || !out || !stray || n > 4096 || (keyed && !idx) || is_device_ptr(items) || is_device_ptr(status) || is_device_ptr(out) || is_device_ptr(idx) ||
+      (kernel == BLSGPU_LINES_P_KEYED && t_b > n))
+    return fail(BLSGPU_E_ARG, "bad argument");
+  if (keyed)
+    for (size_t i = 0; i < n; i++)
+      if ((kernel == BLSGPU_LINES_2S_KEYED || i < t_b) && (uint64_t)idx[i] >= (uint64_t)k.n) return fail(BLSGPU_E_ARG, "index outside the key set");
+  CTX_ACQUIRE_ON(c, keyed ? k.devidx : t_devidx);
+  const size_t rec = two_pairs ? WS_PAIRS_WORDS : WS_PAIRS_WORDS / 2, E = MILLER_ENTRIES;
+  int rc = arena_reserve(c, pad256(rec * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WS_F_WORDS * 4 * n) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  std::vector<uint32_t> h(rec * n);
+  for (size_t i = 0; i < n; i++)
+    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)items[i * rec + w];
+  const void *d_in, *d_st, *d_idx = nullptr;
+  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  if (keyed && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
+  const uint32_t* d_pairs = (const uint32_t*)d_in;
+  const int32_t* d_status = (const int32_t*)d_st;
+  const uint32_t sentinel = (uint32_t)BLSGPU_DEBUG_COOP_SENTINEL;
+  *stray = 0;
+  if (kernel == BLSGPU_LINES_MILLER2S) {              // the one-kernel loop run_pairing2 falls back to
+    uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
+    if (!d_f) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    HIPCK(hipMemsetAsync(d_f, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WS_F_WORDS * 4 * n, c->stream));
+    KL(KID_MILLER2_V1, k_miller2s, dim3(blocks_for(2 * n)), dim3(BLS_BLOCK), n, d_pairs, d_status, d_f, variant);
+    HIPCK(hipGetLastError());
+    std::vector<uint32_t> f((size_t)WS_F_WORDS * n);
+    HIPCK(hipMemcpyAsync(f.data(), d_f, f.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; i++)
+      for (size_t w = 0; w < WS_F_WORDS; w++) out[i * WS_F_WORDS + w] = (int32_t)f[w * n + i];
+    SYNC_FLUSH(c);
+    return 0;
+  }
+  // the items a chunk covers (virtual items for the two-pass product form, which is one chunk: item v pairs with item v + half)
+  const size_t half = (n + 1) / 2;
+  const size_t total = kernel == BLSGPU_LINES_P12 ? half : kernel == BLSGPU_LINES_FIXED ? 1 : n;
+  size_t per = chunk ? chunk : miller_chunk_items() ? miller_chunk_items() : total;
+  if (per > total || kernel == BLSGPU_LINES_P12 || kernel == BLSGPU_LINES_FIXED) per = total;
+  const bool five = kernel == BLSGPU_LINES_2S || kernel == BLSGPU_LINES_2S_KEYED || kernel == BLSGPU_LINES_P12;
+  const size_t out_words = five ? LINE5_WORDS : LINE3_WORDS_H;        // per lane and entry
+  const size_t lanes_max = row_stride(lanes_for(per));
+  const size_t ws_words = E * (LINE5_WORDS + LINE3_WORDS_H) * lanes_max;
+  if (lines_reserve(c, ws_words * 4)) return fail(BLSGPU_E_HIP, "no room for the line workspace");
+  std::vector<uint32_t> rows;
+  for (size_t first = 0; first < total; first += per) {
+    const size_t cnt = total - first < per ? total - first : per;
+    const size_t nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
+    uint32_t* lines3 = c->lines_ws + E * LINE5_WORDS * lanes;
+    const dim3 grid((unsigned)(nlanes / BLS_BLOCK)), block(BLS_BLOCK);
+    HIPCK(hipMemsetAsync(c->lines_ws, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, ws_words * 4, c->stream));
+    switch (kernel) {
+      case BLSGPU_LINES_2S:
+        if (variant) {
+          KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, variant, 0);
+        } else {
+          KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, 0, 1);
+          KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, 0, 2);
+        }
+        break;
+      case BLSGPU_LINES_2S_KEYED:
+        KL(KID_LINES_KEYED, k_lines2s_keyed, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lanes, (const uint32_t*)k.lines, (const uint32_t*)d_idx);
+        break;
+      case BLSGPU_LINES_P1:
+        KL(KID_LINESP, k_linesp, grid, block, cnt, cnt, n, d_pairs + first, d_status + first, c->lines_ws, c->lines_ws, lanes, (size_t)0, cnt, 1);
+        break;
+      case BLSGPU_LINES_P12:
+        KL(KID_LINESP, k_linesp, grid, block, n, half, n, d_pairs, d_status, c->lines_ws, lines3, lanes, (size_t)0, cnt, 1);
+        KL(KID_LINESP, k_linesp, grid, block, n, half, n, d_pairs, d_status, c->lines_ws, lines3, lanes, (size_t)0, cnt, 2);
+        break;
+      case BLSGPU_LINES_P4:
+        KL(KID_LINESP4, k_linesp4, dim3(blocks_for(4 * cnt)), block, cnt, n, d_pairs + first, d_status + first, c->lines_ws, lanes);
+        break;
+      case BLSGPU_LINES_FIXED:
+        KL(KID_TAIL, k_lines_fixed, dim3(1), block, n, d_pairs, d_status, c->lines_ws, lanes, variant);
+        break;
+      default:   // BLSGPU_LINES_P_KEYED
+        KL(KID_LINESP_KEYED, k_linesp_keyed, grid, block, t_b, first, cnt, n, d_pairs, d_status, c->lines_ws, lanes, (const uint32_t*)k.lines, (const uint32_t*)d_idx);
+        break;
+    }
+    HIPCK(hipGetLastError());
+    const size_t nrows = E * out_words;
+    rows.resize(ws_words);                              // the whole workspace: the output rows, pass 1's lines3 rows, the rest
+    HIPCK(hipMemcpyAsync(rows.data(), c->lines_ws, ws_words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    {
+      // behind the output rows: the lines3 rows of the two-pass forms (pass 1 writes the lanes of its live items there, nothing for
+      // an item it skips and nothing beyond the chunk's items), then words no launch may touch; for every other kernel all of it
+      const bool two_pass = (kernel == BLSGPU_LINES_2S && variant == 0) || kernel == BLSGPU_LINES_P12;
+      size_t at = nrows * lanes;
+      if (two_pass) {
+        for (size_t r = 0; r < E * LINE3_WORDS_H; r++, at += lanes)
+          for (size_t t = 0; t < lanes; t++) {
+            const size_t j = t >> 1;
+            const bool live = j < cnt && status[first + j] == 0;      // (BLS_OK = 0: both kernels skip on a non-zero entry)
+            if (!live && rows[at + t] != sentinel) ++*stray;
+          }
+      }
+      for (; at < ws_words; at++)
+        if (rows[at] != sentinel) ++*stray;
+    }
+    // rows[(e * out_words + w) * lanes + t]: word w = 14 * (coefficient number) + limb, lane t = 2 * item + component
+    for (size_t r = 0; r < nrows; r++) {
+      const uint32_t* row = rows.data() + r * lanes;
+      const size_t e = r / out_words, w = r % out_words, kk = w / FP_NL, l = w % FP_NL;
+      for (size_t j = 0; j < cnt; j++)
+        for (size_t comp = 0; comp < 2; comp++)
+          out[((((first + j) * E + e) * (out_words / FP_NL) + kk) * 2 + comp) * FP_NL + l] = (int32_t)row[2 * j + comp];
+      for (size_t t = 2 * cnt; t < lanes; t++)
+        if (row[t] != sentinel) ++*stray;
+    }
+  }
   SYNC_FLUSH(c);
   return 0;
 }

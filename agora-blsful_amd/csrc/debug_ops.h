@@ -98,7 +98,19 @@
   X(G2S_PSI2, 104, 2, 6, 6, 0, 0)      /* g2_psi2 */                                                                 \
   X(G2S_CLEAR, 105, 2, 6, 6, 0, 0)     /* g2_clear_cofactor<hfp2> */                                                 \
   /* ---- four lanes per item: jac_dbl_quad (curve_quad.cuh) */                                                     \
-  X(G2Q_DBL, 110, 4, 6, 12, 0, 1)      /* out = the point as lane pair 0 holds it, then as lane pair 1 holds it */
+  X(G2Q_DBL, 110, 4, 6, 12, 0, 1)      /* out = the point as lane pair 0 holds it, then as lane pair 1 holds it */ \
+  /* ---- the Miller steps (pairing.cuh) on g2_hom_t<fp2>, one lane per item: in = T (X, Y, Z), [xq, yq,] xp, yp; out = T', l0, l2, l3; */ \
+  /* par = form (0: the non-inlined miller_*_step, 1: miller_*_step_at inlined through miller_regs); chain: T feeds back */ \
+  X(MILLER1_DBL, 111, 1, 8, 12, 1, 1)  /* miller_dbl_step */                                                          \
+  X(MILLER1_ADD, 112, 1, 12, 12, 1, 1) /* miller_add_step */                                                          \
+  /* ---- ... and on g2_hom_t<hfp2>, two lanes per item: the same records and forms */                               \
+  X(MILLER2_DBL, 113, 2, 8, 12, 1, 1)  /* miller_dbl_step */                                                          \
+  X(MILLER2_ADD, 114, 2, 12, 12, 1, 1) /* miller_add_step */                                                          \
+  /* ---- two lanes per item: merged line values (tower.cuh) and the row evaluation; out = c0, c2, c4, c3, c5 */      \
+  X(LINES_MERGE, 115, 2, 12, 10, 0, 0)    /* lines_merge(a0, a2, a3, b0, b2, b3) */                                   \
+  X(LINES_MERGE_Y, 116, 2, 11, 10, 0, 0)  /* lines_merge_y(a0, a2, a3, b0, b2, y): y one vector over Fp */            \
+  X(LINES_MERGE_YY, 117, 2, 10, 10, 0, 0) /* lines_merge_yy(a0, a2, ya, b0, b2, yb): in = a0, a2, ya, b0, b2, yb */   \
+  X(LINE3_ROW, 118, 2, 6, 6, 0, 0)        /* miller_line3_row(n0, c, x, y): in = n0, c, x, y; out = l0, l2, l3 */
 
 enum {
 #define X(name, id, lanes, nin, nout, npar, chain) DBG_##name = id,
@@ -125,6 +137,8 @@ __global__ void k_dbg_coop(int op, size_t n, int reps, const int32_t* in, int re
 __global__ void k_dbg_pt1(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_pt2s(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 __global__ void k_dbg_g2q(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_miller1(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
+__global__ void k_dbg_miller2s(int op, size_t n, int reps, const int32_t* in, int rec_in, int32_t* out, int rec_out);
 // blsgpu_debug_map_to_curve: the G1 point at WREC_P0 of n cut-check records (engine values, Jacobian) -> RAW_PROJ
 __global__ void k_dbg_rec_g1_to_raw(size_t n, const uint32_t* rec, uint8_t* out);
 #endif

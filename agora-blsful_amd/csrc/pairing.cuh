@@ -26,9 +26,12 @@ struct g2_hom_t {
 };
 typedef g2_hom_t<fp2> g2_hom;
 
-// Bounds (fp.cuh): T enters and leaves the steps reduced; the line coefficients leave normalised (what
-// fp12_mul_by_line expects).  The small-constant multiples (3b' = 12 (1 + u), 3, 4, 12) are limb-wise additions, so
-// the steps fp_norm / fp_reduce where a chain would pass 2^31 or feed a product with more than 2^29 per limb.
+// Bounds (fp.cuh): a doubling leaves T reduced; an addition leaves Y3 reduced and X3, Z3 as the plain products fp2_mul returns
+// (lane-split: multiplier outputs; one-lane: the normalised Karatsuba differences), and both steps take T in either form.  Of the
+// line, l0 leaves normalised and l2, l3 as multiplier outputs (what fp12_mul_by_line and the merges of tower.cuh expect;
+// tests/miller_cases.py asserts these forms on the device and on the tracked host build).  The small-constant multiples
+// (3b' = 12 (1 + u), 3, 4, 12) are limb-wise additions, so the steps fp_norm / fp_reduce where a chain would pass 2^31 or feed a
+// product with more than 2^29 per limb.
 
 // Where a step finds and leaves its state: the steps below read T, P (and Q for additions) through an accessor, so that the same
 // arithmetic runs on values held in registers (miller_regs: every caller but one) or in LDS (kernels.cuh k_lines2s, whose step

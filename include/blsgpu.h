@@ -391,6 +391,36 @@ int blsgpu_debug_coop_pairing(int mode, int fixed_g2, const int32_t* pairs, size
  *         left as it is.   mode 1: status becomes BLSGPU_OK or BLSGPU_ERR_INVALID_SIGNATURE; out_f12 is not used.
  * BLSGPU_E_ARG: a set without line tables, an index that is not below the set's size, n > 4096, any other mode.  Host pointers. */
 int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* idx, const int32_t* pairs, size_t n, int32_t* status, int32_t* out_f12);
+/* Self-test hook of the kernels that PRODUCE line values on the lane-split path (not part of the reference interface): one shipped
+ * kernel, launched with the grid, row stride, first / count, lines3 offset and pass order of the verify path / the product paths, one
+ * chunk of `chunk` items after another (0: the library's own chunk).  items: n records of limb vectors in reduced form -- twelve per
+ * two-pair item as blsgpu_debug_coop_pairing takes them, six (P.x, P.y, Q.x.c0, Q.x.c1, Q.y.c0, Q.y.c1) per one-pair item of the
+ * product kernels.  status: an item that is not BLSGPU_OK (the product kernels: not zero) is skipped.  The line workspace holds the
+ * byte pattern of BLSGPU_DEBUG_COOP_SENTINEL before every chunk and is read back before the next: every limb of a skipped item is the
+ * sentinel, and *stray counts the words written where nothing may be: on lanes beyond a chunk's items, in the lines3 rows of the
+ * two-pass forms for an item pass 1 skips, and anywhere else in the workspace behind the output rows.  out, per item and entry (68 entries in loop order):
+ *   line5: five Fp2 coefficients c0, c2, c4, c3, c5 (c0 then c1 of each, fourteen limbs each) -- the layout blsgpu_debug_millerf takes;
+ *   line3: three, l0, l2, l3.
+ *   BLSGPU_LINES_2S        k_lines2s; variant = fixed_g2: 1, 2 one launch (pass 0), 0 passes 1 then 2                  -> line5 per item
+ *   BLSGPU_LINES_2S_KEYED  k_lines2s_keyed: pair 0's G2 member is entry idx[i] of `keyset` (BLSGPU_KEYSET_LINES)         -> line5 per item
+ *   BLSGPU_LINES_P1        k_linesp pass 1 (half = the chunk's count: no partners)                                      -> line3 per item
+ *   BLSGPU_LINES_P12       k_linesp passes 1 and 2 over all n items, half = ceil(n / 2): virtual item v merges item v with item
+ *                          v + half (absent for the last one when n is odd)                                             -> line5 per virtual item
+ *   BLSGPU_LINES_P4        k_linesp4                                                                                    -> line3 per item
+ *   BLSGPU_LINES_FIXED     k_lines_fixed; variant = fixed_g2 1, 2                                                       -> line3 of item 0
+ *   BLSGPU_LINES_P_KEYED   k_linesp_keyed: item i < t_b reads the rows of entry idx[i], item i >= t_b the constant's     -> line3 per item
+ *   BLSGPU_LINES_MILLER2S  k_miller2s, the one-kernel loop; variant = fixed_g2 0, 1, 2          -> twelve limb vectors per item, tower order
+ * BLSGPU_E_ARG: another kernel or variant, a set without line tables, an index that is not below the set's size, n > 4096.  Host pointers. */
+#define BLSGPU_LINES_2S 0
+#define BLSGPU_LINES_2S_KEYED 1
+#define BLSGPU_LINES_P1 2
+#define BLSGPU_LINES_P12 3
+#define BLSGPU_LINES_P4 4
+#define BLSGPU_LINES_FIXED 5
+#define BLSGPU_LINES_P_KEYED 6
+#define BLSGPU_LINES_MILLER2S 7
+int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, const int32_t* status, size_t chunk, uint64_t keyset, const uint32_t* idx, size_t t_b,
+                       int32_t* out, uint64_t* stray);
 /* Self-test hooks of the one-wave pairing kernel that reads a registered message's line rows (not part of the reference interface).
  * blsgpu_debug_msgset_from_points: a message set (below: blsgpu_msgset_*) of scheme Basic whose n entries are the given RAW_AFFINE
  *   points of group sig_group (host or device memory) instead of hash outputs, so that crafted G2 points can reach the rows; flags as

@@ -350,6 +350,8 @@ def build():
     coop_lists(L, ops12, cyc, accs, mv, ext2)
     import point_cases                       # the curve-layer rows (G1_*, G2L_*, G2S_*, G2Q_DBL): tests/point_cases.py
     L.update(point_cases.build())
+    import miller_cases                      # the Miller steps, the merged lines and the row evaluation: tests/miller_cases.py
+    L.update(miller_cases.build())
     _cache.update(L)
     return _cache
 
@@ -691,6 +693,9 @@ def check(op, cs, outs, reps=1):
     import point_cases
     if op in point_cases.ROWS:               # a point row: judged by the chord-and-tangent rule and the oracle's curve (tests/point_cases.py)
         return point_cases.check(op, cs, outs, reps)
+    import miller_cases
+    if op in miller_cases.ROWS:              # a step, merge or row operation: judged by the restated formulas (tests/miller_cases.py)
+        return miller_cases.check(op, cs, outs, reps)
     tag = '%s%s, case "%s": ' % (op, ' x%d' % reps if reps > 1 else '', cs['name'])
     # (a lanes = 64 case run with another fill shares its operand vectors, and so its expected value, with the case of the list)
     key = (op, id(cs['vecs']), tuple(cs['par'][:-1]), reps) if op.startswith('COOP_') else (op, id(cs), reps)
@@ -988,7 +993,8 @@ def check_easy(cs, out):
 
 CHAINS = ('FP_MUL', 'FP_SQR', 'FP2_MUL', 'FP2_SQR', 'F12_SH_SQR', 'F12_SH_MUL', 'F12_SH_MUL_LINE', 'F12_SH_MUL_2LINES', 'F12_SH_MUL_LINE5', 'F12_SH_CYC_SQR',
           'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'COOP_MUL', 'COOP_SQR', 'COOP_MUL_LINE', 'COOP_CYC_SQR',
-          'G1_ADD', 'G1_DBL', 'G1_MADD', 'G2L_ADD', 'G2L_DBL', 'G2L_MADD', 'G2Q_DBL', 'G2S_ADD', 'G2S_DBL', 'G2S_MADD')      # (point_cases.CHAINS)
+          'G1_ADD', 'G1_DBL', 'G1_MADD', 'G2L_ADD', 'G2L_DBL', 'G2L_MADD', 'G2Q_DBL', 'G2S_ADD', 'G2S_DBL', 'G2S_MADD',      # (point_cases.CHAINS)
+          'MILLER1_ADD', 'MILLER1_DBL', 'MILLER2_ADD', 'MILLER2_DBL')                                                         # (miller_cases.CHAINS)
 CHAIN_REPS = ((2, 1), (17, 5), (63, 11))       # (reps, stride through the list)
 
 
@@ -998,6 +1004,9 @@ def chain_cases(op, stride):
     import point_cases
     if op in point_cases.ROWS:               # P + Q, P + 2Q, ...: the marked cases (through the identity, from a doubling) and every stride-th
         return point_cases.chain_cases(op, stride)
+    import miller_cases
+    if op in miller_cases.ROWS:
+        return miller_cases.chain_cases(op, stride)
     lst = build()[op]
     cases = lst[::stride][:24]
     if op in ('F12_SH_CYC_SQR', 'CYC_C_SQR', 'CYC_C_SQR_UNPACKED', 'CYC_C_SQR_KARA', 'COOP_CYC_SQR'):

@@ -717,8 +717,70 @@ static int fo_point_row(int row, const fo_rec& R, const int32_t* par, int reps, 
   }
   return -1;
 }
+// ---- what produces line values (MILLER1_* on g2_hom_t<fp2>, MILLER2_* on the host emulation of g2_hom_t<hfp2>, the merges and
+// miller_line3_row), as csrc/tu_debug_ops7.hip runs them.  These records mix Fp2 and Fp operands: fo_ldv / fo_stv count limb VECTORS.
+static void fo_ldv(fp& r, const fo_rec& R, int v) { fo_ld(r, R.in, R.lb, R.vb, R.nn, v); }
+static void fo_ldv(fp2& r, const fo_rec& R, int v) { fo_ld(r.c0, R.in, R.lb, R.vb, R.nn, v); fo_ld(r.c1, R.in, R.lb, R.vb, R.nn, v + 1); }
+static void fo_ldv(hfp2& r, const fo_rec& R, int v) { fo_ld(r.c[0], R.in, R.lb, R.vb, R.nn, v); fo_ld(r.c[1], R.in, R.lb, R.vb, R.nn, v + 1); }
+static void fo_stv(int32_t* out, int v, const fp2& a) { fo_st(out, v, a.c0); fo_st(out, v + 1, a.c1); }
+static void fo_stv(int32_t* out, int v, const hfp2& a) { fo_st(out, v, a.c[0]); fo_st(out, v + 1, a.c[1]); }
+template <class F2>
+static int fo_miller_row(bool add, const fo_rec& R, const int32_t* par, int reps, int32_t* out) {
+  g2_hom_t<F2> t;
+  F2 xq, yq, l0, l2, l3;
+  fp xp, yp;
+  fo_ldv(t.x, R, 0); fo_ldv(t.y, R, 2); fo_ldv(t.z, R, 4);
+  int v = 6;
+  if (add) { fo_ldv(xq, R, 6); fo_ldv(yq, R, 8); v = 10; }
+  fo_ldv(xp, R, v); fo_ldv(yp, R, v + 1);
+  for (int k = 0; k < reps; k++) {
+    if (par[0]) {
+      const miller_regs<F2> st = {t, xp, yp, &xq, &yq};
+      if (add) miller_add_step_at(st, l0, l2, l3); else miller_dbl_step_at(st, l0, l2, l3);
+    } else {
+      if (add) miller_add_step(t, l0, l2, l3, xq, yq, xp, yp); else miller_dbl_step(t, l0, l2, l3, xp, yp);
+    }
+  }
+  fo_stv(out, 0, t.x); fo_stv(out, 2, t.y); fo_stv(out, 4, t.z);
+  fo_stv(out, 6, l0); fo_stv(out, 8, l2); fo_stv(out, 10, l3);
+  return 0;
+}
+static int fo_lines_row(int op, const fo_rec& R, int32_t* out) {
+  hfp2 a0, a2, a3, b0, b2, b3;
+  fp ya, yb;
+  line5_t<hfp2> L;
+  fo_ldv(a0, R, 0); fo_ldv(a2, R, 2);
+  switch (op) {
+    case DBG_LINES_MERGE:
+      fo_ldv(a3, R, 4); fo_ldv(b0, R, 6); fo_ldv(b2, R, 8); fo_ldv(b3, R, 10);
+      lines_merge(L, a0, a2, a3, b0, b2, b3);
+      break;
+    case DBG_LINES_MERGE_Y:
+      fo_ldv(a3, R, 4); fo_ldv(b0, R, 6); fo_ldv(b2, R, 8); fo_ldv(yb, R, 10);
+      lines_merge_y(L, a0, a2, a3, b0, b2, yb);
+      break;
+    case DBG_LINES_MERGE_YY:
+      fo_ldv(ya, R, 4); fo_ldv(b0, R, 5); fo_ldv(b2, R, 7); fo_ldv(yb, R, 9);
+      lines_merge_yy(L, a0, a2, ya, b0, b2, yb);
+      break;
+    case DBG_LINE3_ROW:
+      fo_ldv(ya, R, 4); fo_ldv(yb, R, 5);
+      miller_line3_row(b0, b2, b3, a0, a2, ya, yb);
+      fo_stv(out, 0, b0); fo_stv(out, 2, b2); fo_stv(out, 4, b3);
+      return 0;
+    default: return -1;
+  }
+  fo_stv(out, 0, L.c0); fo_stv(out, 2, L.c2); fo_stv(out, 4, L.c4); fo_stv(out, 6, L.c3); fo_stv(out, 8, L.c5);
+  return 0;
+}
 extern "C" {
 int hs_field_op(int op, const int32_t* in, const double* lb, const double* vb, const int32_t* nn, const int32_t* par, int reps, int32_t* out) {
+  if (op >= DBG_MILLER1_DBL) {
+    const fo_rec R = {in, lb, vb, nn};
+    if (op <= DBG_MILLER1_ADD) return fo_miller_row<fp2>(op == DBG_MILLER1_ADD, R, par, reps, out);
+    if (op <= DBG_MILLER2_ADD) return fo_miller_row<hfp2>(op == DBG_MILLER2_ADD, R, par, reps, out);
+    return fo_lines_row(op, R, out);
+  }
   if (op >= DBG_G1_DBL) {
     const fo_rec R = {in, lb, vb, nn};
     if (op >= DBG_G2S_DBL && op <= DBG_G2S_MADD) return fo_point_row<hfp2, 0, true>(op - DBG_G2S_DBL, R, par, reps, out);

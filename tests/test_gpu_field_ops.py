@@ -16,7 +16,8 @@ import field_cases as fc
 pytestmark = pytest.mark.gpu
 
 COUNTS = (1, 2, 31, 32, 33, 65)
-OPS = sorted(op for op in fc.build() if not op.startswith('COOP_'))      # the rows of the wave-cooperative engine: tests/test_gpu_coop_ops.py
+ELSEWHERE = ('COOP_', 'MILLER', 'LINES_', 'LINE3_')      # the wave-cooperative engine: tests/test_gpu_coop_ops.py; the line producers: tests/test_gpu_miller_ops.py
+OPS = sorted(op for op in fc.build() if not op.startswith(ELSEWHERE))
 
 def run(api, op, cases, reps=1):
     return api.debug_field_op(op, [(cs['vecs'], cs['par']) for cs in cases], reps)
@@ -66,7 +67,7 @@ def test_both_quad_positions(api, op):
         assert a == b, '%s, case "%s": the result depends on the position in the quad' % (op, cs['name'])
 
 
-@pytest.mark.parametrize('op', [op for op in fc.CHAINS if not op.startswith('COOP_')])
+@pytest.mark.parametrize('op', [op for op in fc.CHAINS if not op.startswith(ELSEWHERE)])
 def test_chains(api, op):
     """reps = 2, 17, 63: the lazy output of an operation as its own next operand.  The squarings of the cyclotomic subgroup run every
     cyclotomic element of the list at every length: 63 compressed squarings are those of one a^x"""
