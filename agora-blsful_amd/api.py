@@ -29,8 +29,8 @@ OK, INVALID_SIGNATURE, SIG_IDENTITY, PK_IDENTITY, DUPLICATE_MESSAGE, INVALID_COE
 E_ARG = -3                                                          # in a status slot: blsgpu_sig_proof_timestamp_verify_batch only
 KEYGEN_SALT = b'BLS-SIG-KEYGEN-SALT-'                               # reference src/helpers.rs:7
 COMMITMENT_IDENTITY, PROOF_IDENTITY, ZERO_CHALLENGE = 9, 10, 11    # blsgpu_sig_proof_verify_batch only
-INVALID_SCHEME, VSSS_ERROR = 12, 13                                  # blsgpu_combine_shares only
-INVALID_DECRYPTION_SHARE, BAD_FRAME = 14, 15                        # the threshold signcryption calls only
+INVALID_SCHEME, VSSS_ERROR = 12, 13                                  # blsgpu_combine_shares; 12 also blsgpu_timecrypt_open_batch
+INVALID_DECRYPTION_SHARE, BAD_FRAME = 14, 15                        # the threshold signcryption calls; 15 also blsgpu_timecrypt_open_batch
 ELGAMAL_IDENTITY, ELGAMAL_ZERO_PROOF, CHALLENGE_MISMATCH = 16, 17, 18   # blsgpu_elgamal_proof_verify_batch only
 
 EXPORTS = [
@@ -57,6 +57,7 @@ EXPORTS = [
     'blsgpu_verify_msgset_batch', 'blsgpu_verify_msgset_indexed_batch', 'blsgpu_debug_msgset_from_points', 'blsgpu_debug_coop_pairing_rows',
     'blsgpu_aggregate_verify_msgset_batch', 'blsgpu_aggregate_verify_msgset_indexed_batch',
     'blsgpu_debug_lines',
+    'blsgpu_pairing_batch', 'blsgpu_timecrypt_open_batch',
 ]
 
 
@@ -220,6 +221,8 @@ def load_library(path=None):
         lib.blsgpu_debug_coop_pairing_rows.argtypes = [ci, h, u32p, i32p, sz, i32p, i32p]
         lib.blsgpu_aggregate_verify_msgset_batch.argtypes = [h, u32p, vp, u64p, sz, vp, ci, i32p, u64p]
         lib.blsgpu_aggregate_verify_msgset_indexed_batch.argtypes = [h, u32p, h, u32p, u64p, sz, vp, ci, i32p, u64p]
+        lib.blsgpu_pairing_batch.argtypes = [vp, vp, sz, ci, u8p, i32p]
+        lib.blsgpu_timecrypt_open_batch.argtypes = [ci, vp, u8p, u64p, sz, vp, u8p, u8p, u64p, u8p, ci, u8p, u64p, i32p]
         _lib = lib
     return _lib
 
@@ -695,6 +698,46 @@ def pairing2_check_batch(g1a, g2a, g1b, g2b, fmt=FMT_RAW_PROJ):
     _check(lib.blsgpu_pairing2_check_batch(_ptr(b''.join(g1a)), _ptr(b''.join(g2a)), _ptr(b''.join(g1b)), _ptr(b''.join(g2b)), n, fmt,
                                            ctypes.cast(out, ctypes.c_void_p)))
     return [bool(x) for x in list(out)[:n]]
+
+
+GT_BYTES = 576
+
+
+def pairing_batch(g1s, g2s, fmt=FMT_RAW_PROJ):
+    """([Pairing::pairing(&[(a, b)]).to_bytes()] as 576-byte strings -- the byte order include/blsgpu.h states as an assumption --,
+    [status]) for n independent pairs; an identity member gives Gt one, an undecodable wire point its status and 576 zero bytes."""
+    lib = init()
+    n = len(g1s)
+    out = ctypes.create_string_buffer(GT_BYTES * max(n, 1))
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(lib.blsgpu_pairing_batch(_ptr(b''.join(g1s)), _ptr(b''.join(g2s)), n, fmt, ctypes.cast(out, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[GT_BYTES * i:GT_BYTES * (i + 1)] for i in range(n)], list(st)[:n]
+
+
+def timecrypt_open_batch(sig_group, groups, fmt=FMT_RAW_PROJ, with_status=False):
+    """TimeCryptCiphertext::decrypt for many ciphertexts grouped under one signature each (blsgpu_timecrypt_open_batch): `groups` is a
+    list of (signature point, its scheme tag, [(u, v, w, scheme tag)]).  Returns [plaintext bytes or None] over the items of all
+    groups in order (None <=> the reference's CtOption is none); with_status=True: (that list, the statuses)."""
+    lib = init()
+    items = [ct for _, _, cts in groups for ct in cts]
+    n = len(items)
+    ioffs = _count_offsets([cts for _, _, cts in groups])
+    woffs, wblob = _offsets([bytes(w) for _, _, w, _ in items])
+    frames = ctypes.create_string_buffer(max(len(wblob), 1))
+    rng = (ctypes.c_uint64 * (2 * max(n, 1)))()
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(lib.blsgpu_timecrypt_open_batch(sig_group, _ptr(b''.join(s for s, _, _ in groups) or b'\0'), _ptr(bytes(t for _, t, _ in groups) or b'\0'),
+                                           ctypes.cast(ioffs, ctypes.c_void_p), len(groups), _ptr(b''.join(u for u, _, _, _ in items) or b'\0'),
+                                           _ptr(b''.join(bytes(v) for _, v, _, _ in items) or b'\0'), _ptr(wblob or b'\0'),
+                                           ctypes.cast(woffs, ctypes.c_void_p), _ptr(bytes(t for _, _, _, t in items) or b'\0'), fmt,
+                                           ctypes.cast(frames, ctypes.c_void_p), ctypes.cast(rng, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
+    raw = frames.raw
+    out = []
+    for i in range(n):
+        lo = woffs[i] + rng[2 * i]
+        out.append(raw[lo:lo + rng[2 * i + 1]] if st[i] == OK else None)
+    return (out, list(st)[:n]) if with_status else out
 
 
 def aggregate_secure(sig_group, pks, sigs, ser_format=MODERN, fmt=FMT_RAW_PROJ):
@@ -1623,6 +1666,26 @@ class TensorOps:
                                                                 fmt, now_ms, -1 if timeout_ms is None else timeout_ms, self._p(st)))
         return st[:n]
 
+    def pairing_batch(self, g1s, g2s, n, fmt=FMT_RAW_PROJ):
+        """(uint8 tensor of n x 576 Gt bytes, int32 statuses), both on the device, of n single pairings over device-resident points"""
+        self._sync()
+        out = self.empty(GT_BYTES * max(n, 1))
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_pairing_batch(self._p(g1s), self._p(g2s), n, fmt, self._p(out), self._p(st)))
+        return out[:GT_BYTES * n], st[:n]
+
+    def timecrypt_open_batch(self, sg, sigs, sig_schemes, item_offs, n_groups, us, vs, ws, w_offs, ct_schemes, n, fmt=FMT_RAW_PROJ):
+        """(frames: uint8 like ws, pt_range: int64 of shape (n, 2), int32 statuses), all on the device, over device-resident signatures
+        (one per group, uint8 scheme tags, int64 item_offs of n_groups + 1 entries) and ciphertexts (us, vs of n x 32 bytes, ws with
+        int64 w_offs of n + 1 entries, uint8 scheme tags)"""
+        self._sync()
+        frames = self.empty(max(ws.numel() if ws is not None else 0, 1))
+        rng = self.empty(2 * max(n, 1), self.torch.int64)
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_timecrypt_open_batch(sg, self._p(sigs), self._p(sig_schemes), self._p(item_offs), n_groups, self._p(us), self._p(vs), self._p(ws),
+                                                    self._p(w_offs), self._p(ct_schemes), fmt, self._p(frames), self._p(rng), self._p(st)))
+        return frames[:ws.numel() if ws is not None else 0], rng[:2 * n].view(n, 2), st[:n]
+
     def signcrypt_valid_batch(self, sg, scheme, us, ws, vs, offs, n):
         self._sync()
         st = self.empty(max(n, 1), self.torch.int32)
@@ -2347,6 +2410,29 @@ def open_many(items):
         for i, r in zip(idx, res):
             out[i] = r
     return out
+
+
+class TimeCryptCiphertext:
+    """TimeCryptCiphertext<C> {u, v, w, scheme}: reference src/time_crypt_ciphertext.rs:6-17.  u: pk group, RAW_PROJ; v: 32 bytes."""
+
+    def __init__(self, impl, scheme, u, v, w):
+        self.impl, self.scheme, self.u, self.v, self.w = impl, scheme, bytes(u), bytes(v), bytes(w)
+
+    def decrypt(self, sig):
+        """reference src/time_crypt_ciphertext.rs:38-50: the plaintext, or None."""
+        return timecrypt_decrypt_many([(sig, [self])])[0]
+
+
+def timecrypt_decrypt_many(groups):
+    """TimeCryptCiphertext.decrypt over many ciphertexts at once: `groups` is a list of (Signature, [TimeCryptCiphertext]) that share
+    one impl -- one published signature per round, and the ciphertexts sealed to it.  One blsgpu_timecrypt_open_batch call.  Returns
+    one plaintext or None per ciphertext, in order."""
+    if not groups:
+        return []
+    sg = groups[0][0].impl.sig_group
+    if any(sig.impl.sig_group != sg or any(ct.impl.sig_group != sg for ct in cts) for sig, cts in groups):
+        raise ValueError('timecrypt_decrypt_many: every signature and ciphertext must use the same impl')
+    return timecrypt_open_batch(sg, [(sig.raw, sig.scheme, [(ct.u, ct.v, ct.w, ct.scheme) for ct in cts]) for sig, cts in groups])
 
 
 class ElGamalCiphertext:

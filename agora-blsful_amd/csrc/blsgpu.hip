@@ -28,6 +28,7 @@
 #include "msgset.cuh"
 #include "agg_msgset.cuh"
 #include "hkdf.cuh"
+#include "timecrypt.cuh"
 #include "debug_ops.h"
 #include "host_sha256.h"
 
@@ -62,6 +63,8 @@ enum {
   KID_MSGSET_SEAL, KID_MSGSET_CHECK,     // registered message sets (msgset.cuh; k_msgset_mark counts under k_msgset_check, the rows' build under k_keyset_lines[_at])
   KID_PAIRING_COOP_ROWS,                 // the one-wave pairing that reads a registered message's rows (in the place of k_pairing_coop)
   KID_AGGM_CLASS, KID_AGGM_SUM, KID_AGGM_ITEMS,   // aggregate verify by message index (agg_msgset.cuh): check / class table / numbering, the class key sum, the flat items
+  KID_PAIRING_VALUE_PREP, KID_PAIRING_VALUE,      // blsgpu_pairing_batch (timecrypt.cuh): pairs to affine and flags, the one-wave pairing that exports Gt bytes
+  KID_TIMECRYPT_PREP, KID_TIMECRYPT_OPEN,         // blsgpu_timecrypt_open_batch: statuses and pairs before the pairing, the time-lock tail after it
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -85,7 +88,9 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_hash_to_scalar", "k_proof_challenge", "k_proof_timeout",
                                     "k_msgset_seal", "k_msgset_check",
                                     "k_pairing_coop_rows",
-                                    "k_agg_msgset_class", "k_agg_msgset_sum", "k_agg_msgset_items"};
+                                    "k_agg_msgset_class", "k_agg_msgset_sum", "k_agg_msgset_items",
+                                    "k_pairing_value_prepare", "k_pairing_value",
+                                    "k_timecrypt_prepare", "k_timecrypt_open"};
 
 struct Ctx {
   int dev = -1;
@@ -4194,6 +4199,151 @@ int blsgpu_pairing2_check_batch(const void* g1a, const void* g2a, const void* g1
   if ((rc = copy_out(c, is_one, d_status, 4 * n))) return rc;
   SYNC_FLUSH(c);
   return 0;
+}
+API_CATCH
+
+/* Pairing::pairing(&[(g1s[i], g2s[i])]) for n independent single pairs (reference src/helpers.rs:41-63), the VALUE: out_gt = n x 576
+ * bytes, Gt::to_bytes() as include/blsgpu.h states the assumption.  All four point formats; a COMPRESSED / LEGACY pair that does not
+ * decode gets its decode status (the G1 member's first) and 576 zero bytes; a pair with an identity member gets Gt one and BLSGPU_OK,
+ * as multi_miller_loop skips it.  Launch sequence: k_decompress x 2 (wire formats only), k_pairing_value_prepare, then
+ * k_pairing_value -- one wave per item (coop_miller1, coop_final_value, coop_gt_bytes) -- over chunks of at most 4,096 items. */
+const size_t PAIRING_VALUE_CHUNK = 4096;
+int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, uint8_t* out_gt, int32_t* status) try {
+  if (!initialised()) return NOT_INIT();
+  if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE && fmt != BLSGPU_FMT_COMPRESSED && fmt != BLSGPU_FMT_LEGACY)
+    return fail(BLSGPU_E_ARG, "fmt must be one of the four BLSGPU_FMT_* point formats");
+  if (n == 0) return 0;
+  if (!g1s || !g2s || !out_gt || !status) return fail(BLSGPU_E_ARG, "null argument");
+  CTX_ACQUIRE(c);
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  const size_t b1 = point_bytes(1, fmt) * n, b2 = point_bytes(2, fmt) * n;
+  const size_t r1 = point_bytes(1, BLSGPU_FMT_RAW_PROJ) * n, r2 = point_bytes(2, BLSGPU_FMT_RAW_PROJ) * n;
+  size_t need = pad256(b1) + pad256(b2) + pad256((size_t)GT_BYTES * n) + 2 * pad256(4 * n) + pad256((size_t)WS_PAIR1_WORDS * 4 * n) + 4096;
+  if (wire) need += pad256(r1) + pad256(r2);
+  int rc = arena_reserve(c, need);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d1, *d2;
+  if ((rc = stage_in(c, g1s, b1, &d1))) return rc;
+  if ((rc = stage_in(c, g2s, b2, &d2))) return rc;
+  Carver mem{c};
+  uint8_t* d_out = mem.stage_out<uint8_t>(out_gt, (size_t)GT_BYTES * n);
+  int32_t* d_status = mem.stage_out<int32_t>(status, 4 * n);
+  int32_t* d_flag = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * n);
+  uint8_t* d_r1 = wire ? mem.take<uint8_t>(r1) : nullptr;
+  uint8_t* d_r2 = wire ? mem.take<uint8_t>(r2) : nullptr;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  int kfmt = fmt;
+  if (wire) {
+    // checked decompression (subgroup test included): the first failure of the G1 member, then of the G2 member, is the pair's status
+    const int legacy = fmt == BLSGPU_FMT_LEGACY;
+    KL(KID_DECOMPRESS, k_decompress<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d1, legacy, d_r1, d_status, 0);
+    KL(KID_DECOMPRESS, k_decompress<2>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d2, legacy, d_r2, d_status, 1);
+    d1 = d_r1;
+    d2 = d_r2;
+    kfmt = BLSGPU_FMT_RAW_PROJ;
+  } else {
+    HIPCK(hipMemsetAsync(d_status, 0, 4 * n, c->stream));   // BLSGPU_OK: raw points are taken as they come
+  }
+  KL(KID_PAIRING_VALUE_PREP, k_pairing_value_prepare, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d1, (const uint8_t*)d2, kfmt,
+     wire ? (const int32_t*)d_status : (const int32_t*)nullptr, d_pairs, d_flag);
+  for (size_t first = 0; first < n; first += PAIRING_VALUE_CHUNK) {
+    const size_t count = std::min(PAIRING_VALUE_CHUNK, n - first);
+    KL(KID_PAIRING_VALUE, k_pairing_value, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, d_out);
+  }
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out_gt, d_out, (size_t)GT_BYTES * n))) return rc;
+  if ((rc = stage_back(c, status, d_status, 4 * n))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* TimeCryptCiphertext::decrypt(sig) for many ciphertexts grouped under one signature each (reference src/time_crypt_ciphertext.rs:38-50
+ * -> BlsTimeCrypt::unseal, src/traits/time_crypt.rs:76-116); include/blsgpu.h has the contract.  Launch sequence: k_decompress x 2
+ * (wire formats only: the u of every item, the signature of every group), k_timecrypt_prepare (statuses up to the identity checks,
+ * the pair of every item that passes them), k_pairing_value over chunks of at most 4,096 items (K = e(sig, u) as 576 bytes per item,
+ * in the arena), k_timecrypt_open (SHA-256, SHAKE128, the frame, the scalar and g r == u, one item per lane). */
+int blsgpu_timecrypt_open_batch(int sig_group, const void* sigs, const uint8_t* sig_schemes, const uint64_t* item_offsets, size_t n_groups, const void* us,
+                                const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets, const uint8_t* ct_schemes, int fmt, uint8_t* frames,
+                                uint64_t* pt_range, int32_t* status) try {
+  if (!initialised()) return NOT_INIT();
+  if (sig_group != 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "sig_group must be 1 (Bls12381G1Impl) or 2 (Bls12381G2Impl)");
+  if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE && fmt != BLSGPU_FMT_COMPRESSED && fmt != BLSGPU_FMT_LEGACY)
+    return fail(BLSGPU_E_ARG, "fmt must be one of the four BLSGPU_FMT_* point formats");
+  if (!item_offsets) return fail(BLSGPU_E_ARG, "null item_offsets");
+  CTX_ACQUIRE(c);
+  std::vector<uint64_t> ioffs, woffs;
+  int rc = read_offsets(item_offsets, n_groups, "item_offsets", ioffs);
+  if (rc) return rc;
+  const size_t n = (size_t)ioffs[n_groups];
+  if (n == 0) return 0;
+  if (!w_offsets) return fail(BLSGPU_E_ARG, "null w_offsets");
+  if ((rc = read_offsets(w_offsets, n, "w_offsets", woffs))) return rc;
+  const size_t total = (size_t)woffs[n];
+  for (size_t i = 0; i < n; i++)
+    if ((woffs[i + 1] - woffs[i]) >> 29) return fail(BLSGPU_E_ARG, "a w of 512 MiB or more");
+  if (!sigs || !sig_schemes || !us || !vs || !ct_schemes || !pt_range || !status || (total && (!ws || !frames))) return fail(BLSGPU_E_ARG, "null argument");
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  const int pkg = key_group(sig_group);
+  const size_t ub = pk_size(sig_group, fmt) * n, sb = sig_size(sig_group, fmt) * n_groups;
+  const size_t u_raw = pk_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n, s_raw = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n_groups;
+  size_t need = pad256(ub) + pad256(sb) + pad256(n_groups) + pad256(8 * (n_groups + 1)) + pad256(32 * n) + 2 * pad256(total) + pad256(8 * (n + 1)) + pad256(n) +
+                pad256(16 * n) + 2 * pad256(4 * n) + pad256((size_t)WS_PAIR1_WORDS * 4 * n) + pad256((size_t)GT_BYTES * n) + 8192;
+  if (wire) need += pad256(u_raw) + pad256(s_raw) + pad256(4 * n) + pad256(4 * n_groups);
+  if ((rc = arena_reserve(c, need))) return rc;
+  c->arena_off = 0;
+  const void *d_sigs, *d_ss, *d_us, *d_vs, *d_ws, *d_cs;
+  const uint64_t *d_ioffs, *d_woffs;
+  if ((rc = stage_in(c, sigs, sb, &d_sigs))) return rc;
+  if ((rc = stage_in(c, sig_schemes, n_groups, &d_ss))) return rc;
+  if ((rc = stage_in(c, us, ub, &d_us))) return rc;
+  if ((rc = stage_in(c, vs, 32 * n, &d_vs))) return rc;
+  if ((rc = stage_in(c, ws, total, &d_ws))) return rc;
+  if ((rc = stage_in(c, ct_schemes, n, &d_cs))) return rc;
+  if ((rc = upload_offsets(c, ioffs, &d_ioffs))) return rc;
+  if ((rc = upload_offsets(c, woffs, &d_woffs))) return rc;
+  Carver mem{c};
+  uint8_t* d_frames = total ? mem.stage_out<uint8_t>(frames, total) : c->arena;
+  uint64_t* d_range = mem.stage_out<uint64_t>(pt_range, 16 * n);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  int32_t* d_flag = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * n);
+  uint8_t* d_gt = mem.take<uint8_t>((size_t)GT_BYTES * n);
+  uint8_t* d_u_raw = wire ? mem.take<uint8_t>(u_raw) : nullptr;
+  uint8_t* d_s_raw = wire ? mem.take<uint8_t>(s_raw) : nullptr;
+  int32_t* d_dec_u = wire ? mem.take<int32_t>(4 * n) : nullptr;
+  int32_t* d_dec_s = wire ? mem.take<int32_t>(4 * n_groups) : nullptr;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  if (total && d_frames != frames) HIPCK(hipMemsetAsync(d_frames, 0, total, c->stream));   // an item that is not opened hands back zeros, not arena bytes
+  int kfmt = fmt;
+  if (wire) {
+    const int legacy = fmt == BLSGPU_FMT_LEGACY;
+    with_group(pkg, [&](auto G) { KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_us, legacy, d_u_raw, d_dec_u, 0); });
+    with_group(sig_group, [&](auto G) {
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n_groups)), dim3(BLS_BLOCK), n_groups, (const uint8_t*)d_sigs, legacy, d_s_raw, d_dec_s, 0);
+    });
+    d_us = d_u_raw;
+    d_sigs = d_s_raw;
+    kfmt = BLSGPU_FMT_RAW_PROJ;
+  }
+  with_group(sig_group, [&](auto G) {
+    KL(KID_TIMECRYPT_PREP, k_timecrypt_prepare<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, (const uint8_t*)d_us, (const uint8_t*)d_sigs, kfmt,
+       (const uint8_t*)d_ss, (const uint8_t*)d_cs, (const int32_t*)d_dec_u, (const int32_t*)d_dec_s, d_pairs, d_flag, d_status);
+  });
+  for (size_t first = 0; first < n; first += PAIRING_VALUE_CHUNK) {
+    const size_t count = std::min(PAIRING_VALUE_CHUNK, n - first);
+    KL(KID_PAIRING_VALUE, k_pairing_value, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, d_gt);
+  }
+  with_group(sig_group, [&](auto G) {
+    KL(KID_TIMECRYPT_OPEN, k_timecrypt_open<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_gt, (const uint8_t*)d_us, kfmt, (const uint8_t*)d_vs,
+       (const uint8_t*)d_ws, d_woffs, d_frames, d_range, d_status);
+  });
+  HIPCK(hipGetLastError());
+  if (total && (rc = stage_back(c, frames, d_frames, total))) return rc;
+  if ((rc = stage_back(c, pt_range, d_range, 16 * n))) return rc;
+  return status_out_and_sync(c, status, d_status, n);
 }
 API_CATCH
 

@@ -735,8 +735,9 @@ __device__ __noinline__ void coop_final_easy(coop_shared& S) {
   coop_frob<2>(S.t, S.f);
   coop_mul(S, S.f, S.t, S.f);
 }
-// final exponentiation of S.f (as pairing.cuh final_exponentiation) and comparison with 1; returns the status code
-__device__ __noinline__ int coop_final_verdict(coop_shared& S) {
+// final exponentiation of S.f (as pairing.cuh final_exponentiation): the value, t f^3 = f^(3 (p^4 - p^2 + 1) / r) of the easy-part
+// result f, is left in S.t.  Inlined into its two callers, so that coop_final_verdict is operation for operation what it was.
+__device__ __forceinline__ void coop_final_hard_body(coop_shared& S) {
   coop_final_easy(S);
   // hard part: t = f^((x-1)^2 (x+p) (x^2+p^2-1)) * f^3
   coop_pow_x(S, S.t, S.f);
@@ -757,6 +758,12 @@ __device__ __noinline__ int coop_final_verdict(coop_shared& S) {
   coop_sqr(S, S.u, S.f);
   coop_mul(S, S.u, S.u, S.f);      // f^3
   coop_mul(S, S.t, S.t, S.u);
+}
+// the pairing VALUE of S.f in S.t (timecrypt.cuh exports it as Gt bytes)
+__device__ __noinline__ void coop_final_value(coop_shared& S) { coop_final_hard_body(S); }
+// ... and its comparison with 1; returns the status code
+__device__ __noinline__ int coop_final_verdict(coop_shared& S) {
+  coop_final_hard_body(S);
   // == 1 ?
   if (threadIdx.x == 0) S.flag = 1;
   __syncthreads();

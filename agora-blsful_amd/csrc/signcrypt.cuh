@@ -20,21 +20,29 @@ typedef uint64_t __attribute__((may_alias, aligned(8))) signcrypt_u64;
 // last; `peek` looks at up to 19 bytes (the longest encoding of a u128) and fails when none of them terminates or the frame ends
 // first; the value is taken modulo 2^64 (`as usize`).  Success iff len <= frame_len - overhead.
 #define SIGNCRYPT_VARINT_MAX 19
-KECCAK_FN bool signcrypt_parse_frame(const uint8_t* frame, uint64_t frame_len, uint64_t* pt_off, uint64_t* pt_len) {
+// The two ways a frame has no message are told apart for the time-lock call (timecrypt.cuh), whose reference goes on with an EMPTY
+// message when `peek` fails (src/traits/time_crypt.rs:89-102) and returns None only for a length beyond the frame.
+#define SIGNCRYPT_FRAME_OK 0          // *pt_off, *pt_len are set
+#define SIGNCRYPT_FRAME_NO_PREFIX 1   // `peek` fails: no byte of the first 19 (or of the frame) ends a varint
+#define SIGNCRYPT_FRAME_BEYOND 2      // a length beyond the frame
+KECCAK_FN int signcrypt_parse_frame_kind(const uint8_t* frame, uint64_t frame_len, uint64_t* pt_off, uint64_t* pt_len) {
   uint64_t value = 0;
   for (int i = 0; i < SIGNCRYPT_VARINT_MAX; i++) {
-    if ((uint64_t)i >= frame_len) return false;
+    if ((uint64_t)i >= frame_len) return SIGNCRYPT_FRAME_NO_PREFIX;
     const uint8_t b = frame[i];
     if (7 * i < 64) value |= (uint64_t)(b & 0x7f) << (7 * i);
     if (!(b & 0x80)) {
       const uint64_t overhead = (uint64_t)i + 1;
-      if (value > frame_len - overhead) return false;
+      if (value > frame_len - overhead) return SIGNCRYPT_FRAME_BEYOND;
       *pt_off = overhead;
       *pt_len = value;
-      return true;
+      return SIGNCRYPT_FRAME_OK;
     }
   }
-  return false;
+  return SIGNCRYPT_FRAME_NO_PREFIX;
+}
+KECCAK_FN bool signcrypt_parse_frame(const uint8_t* frame, uint64_t frame_len, uint64_t* pt_off, uint64_t* pt_len) {
+  return signcrypt_parse_frame_kind(frame, frame_len, pt_off, pt_len) == SIGNCRYPT_FRAME_OK;
 }
 
 // frame[0, len) = SHAKE128(g[0, GLEN)) xor v[0, len).  A long frame is a sequential squeeze: one permutation per 168 bytes.

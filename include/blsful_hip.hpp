@@ -16,6 +16,7 @@
 //   verify_batch (additive; no reference entry)    n independent Signature::verify calls in one launch
 //   ProofCommitmentChallenge<C>                    src/proof_commitment.rs:256-261 (from_hash)
 //   ProofOfKnowledge<C>, ProofOfKnowledgeTimestamp<C>   src/proof_of_knowledge.rs:132-164, 287-326
+//   TimeCryptCiphertext<C>                         src/time_crypt_ciphertext.rs:6-17, 38-50 (decrypt)
 //
 // Header-only; link with -lblsgpu.  Every call goes to the GPU: there is no CPU path behind these types, and a missing
 // device surfaces as BlsError{Kind::Runtime} from the first call.
@@ -479,6 +480,29 @@ struct ProofOfKnowledgeTimestamp {
     ProofCommitmentChallenge<C> y;
     if (int rc = blsgpu_sig_proof_challenge_batch(C::SIG_GROUP, u.data(), &t, 1, BLSGPU_FMT_RAW_PROJ, y.le.data())) return detail::runtime_error(rc);
     return y;
+  }
+};
+
+template <class C>
+struct TimeCryptCiphertext {
+  std::array<uint8_t, C::PK_RAW> u;        // src/time_crypt_ciphertext.rs:6-17
+  std::array<uint8_t, 32> v;
+  Bytes w;
+  SignatureSchemes scheme;
+  // TimeCryptCiphertext::decrypt(sig), src/time_crypt_ciphertext.rs:38-50: Ok(Some(plaintext)) / Ok(None) are the reference's
+  // CtOption; an error is a failure of the library alone (no device, ...), which the reference has no value for
+  BlsResult<std::optional<Bytes>> decrypt(const Signature<C>& sig) const {
+    if (int rc = detail::ensure_init()) return detail::runtime_error(rc);
+    const uint64_t item_offs[2] = {0, 1}, w_offs[2] = {0, w.size()};
+    const uint8_t sig_tag = (uint8_t)sig.scheme, ct_tag = (uint8_t)scheme;
+    Bytes frame(w.size() + 1);
+    uint64_t range[2] = {0, 0};
+    int32_t st = 0;
+    int rc = blsgpu_timecrypt_open_batch(C::SIG_GROUP, sig.raw.data(), &sig_tag, item_offs, 1, u.data(), v.data(), w.data(), w_offs, &ct_tag,
+                                         BLSGPU_FMT_RAW_PROJ, frame.data(), range, &st);
+    if (rc) return detail::runtime_error(rc);
+    if (st != BLSGPU_OK) return std::optional<Bytes>();
+    return std::optional<Bytes>(Bytes(frame.begin() + (size_t)range[0], frame.begin() + (size_t)(range[0] + range[1])));
   }
 };
 

@@ -304,6 +304,47 @@ int blsgpu_sig_proof_timestamp_verify_batch(int sig_group, int scheme, const voi
 int blsgpu_pairing2_check_batch(const void* g1a, const void* g2a, const void* g1b, const void* g2b, size_t n, int fmt,
                                 int32_t* is_one);
 
+/* n independent single pairings, the VALUE: out_gt[576 i ..) = Pairing::pairing(&[(g1s_i, g2s_i)]).to_bytes() (src/helpers.rs:41-63:
+ * multi_miller_loop, then final_exponentiation) -- what TimeCryptCiphertext::decrypt (src/traits/time_crypt.rs:76-141) hashes.
+ * Two facts fix these bytes, and they are pinned to different degrees:
+ *   the value   The backend's final exponentiation raises to 3 (p^12 - 1) / r (its hard part is the chain whose exponent is
+ *               (x - 1)^2 (x + p) (x^2 + p^2 - 1) + 3), so Gt is the CUBE of the textbook reduced pairing.  This library's chains are
+ *               that chain; tests/test_timecrypt_cases.py checks the cube against a plain power, bilinearity and the order r.
+ *   the bytes   ASSUMED, and not verifiable without the backend: the six Fp2 coefficients over w^0 .. w^5 (w^6 = xi; in tower terms
+ *               c0.a0, c1.a0, c0.a1, c1.a1, c0.a2, c1.a2), each its real part, then its imaginary part, each part 48 bytes
+ *               big-endian, the canonical residue (not Montgomery).  One device function (csrc/timecrypt.cuh coop_gt_bytes) and one
+ *               test function (tests/timecrypt_ref.py gt_bytes) know this order; should it be wrong, the fix is a permutation there.
+ * fmt: any of the four BLSGPU_FMT_* (both members in the same format).  A COMPRESSED / LEGACY pair that does not decode gets its
+ * decode status (the G1 member's first, then the G2 member's) and 576 zero bytes.  A pair with an identity member gets Gt one
+ * (00 .. 01 in the first 48 bytes, then zeros) and BLSGPU_OK, as multi_miller_loop skips it.  RAW formats are not subgroup-checked,
+ * as everywhere else.  status: n entries, BLSGPU_OK or a decode status.  Pointers may be host or device memory.  One wave per item
+ * (k_pairing_value), launched over chunks of at most 4,096 items; the call runs on the first bound device. */
+int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, uint8_t* out_gt, int32_t* status);
+
+/* TimeCryptCiphertext::decrypt(sig) (src/time_crypt_ciphertext.rs:38-50 -> BlsTimeCrypt::unseal, src/traits/time_crypt.rs:76-116) for
+ * many ciphertexts grouped under one signature each -- a time-lock service publishes one signature per round, and every ciphertext
+ * sealed to that round opens with it.  Group g is items item_offsets[g] .. item_offsets[g + 1] - 1 (n_groups + 1 offsets, from 0,
+ * never decreasing, else BLSGPU_E_ARG; n = item_offsets[n_groups]), with signature sigs[g] (sig_group's group) and its scheme tag
+ * sig_schemes[g] (0 / 1 / 2).  Item i has u_i (us, the key group), v_i (vs, n x 32 bytes), w_i = ws[w_offsets[i] .. w_offsets[i + 1])
+ * (n + 1 offsets, as above; any length below 512 MiB, zero included) and its scheme tag ct_schemes[i].  fmt: any of the four
+ * BLSGPU_FMT_* (signatures and u in the same format).  frames is as large as ws, with the same offsets; pt_range holds
+ * (offset, length) per item, as in blsgpu_signcrypt_open_batch: the message of item i is frames[w_offsets[i] + offset ..) of that
+ * length.  Pointers may be host or device memory.  Per item, exactly the reference:
+ *   K = e(sig, u) (the G1 member first);  alpha = SHA-256(K.to_bytes()) xor v -- K.to_bytes() as blsgpu_pairing_batch states the
+ *   assumption --;  frame = SHAKE128(alpha) xor w;  the frame's length prefix (the varint of blsgpu_signcrypt_open_batch): when
+ *   `peek` FAILS the message is EMPTY and the check goes on (time_crypt.rs:89-102 -- not the signcryption rule), a length beyond the
+ *   frame is None, otherwise the message is frame[overhead .. overhead + len);  r = hash_to_scalar(alpha || SHA-256(message)) under
+ *   the salt "TIMELOCK_BLS12381_XOF:HKDF-SHA2-256_" (a zero r is kept as zero, as blsgpu_hash_to_scalar writes it, and fails);
+ *   Some <=> g r == u, the scheme tags are equal, and neither sig nor u is the identity.
+ * status[i] is the first that applies of: the decode status of u_i, then of sig_g (wire formats); BLSGPU_INVALID_SCHEME
+ * (ct_schemes[i] != sig_schemes[g]); BLSGPU_SIG_IDENTITY; BLSGPU_PK_IDENTITY (u is the identity); BLSGPU_BAD_FRAME (a length beyond
+ * the frame, only); BLSGPU_INVALID_SIGNATURE (g r != u); BLSGPU_OK.  status[i] == BLSGPU_OK <=> is_some().  An item that is not OK
+ * gets pt_range (0, 0), and its frame bytes are not part of the contract.  One wave per item for the pairing, in chunks of at most
+ * 4,096 items, then one lane per item; the call runs on the first bound device. */
+int blsgpu_timecrypt_open_batch(int sig_group, const void* sigs, const uint8_t* sig_schemes, const uint64_t* item_offsets, size_t n_groups,
+                                const void* us, const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets, const uint8_t* ct_schemes,
+                                int fmt, uint8_t* frames, uint64_t* pt_range, int32_t* status);
+
 /* Measurement hooks (not part of the reference interface): when enabled, every kernel launch of the library is
  * bracketed by HIP events on the library's own stream; blsgpu_profile_get returns the accumulated device time and
  * launch count per kernel since the last enable.  bench.py derives the roofline figures from these. */
