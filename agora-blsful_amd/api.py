@@ -58,6 +58,8 @@ EXPORTS = [
     'blsgpu_aggregate_verify_msgset_batch', 'blsgpu_aggregate_verify_msgset_indexed_batch',
     'blsgpu_debug_lines',
     'blsgpu_pairing_batch', 'blsgpu_timecrypt_open_batch',
+    'blsgpu_sigset_create', 'blsgpu_sigset_destroy', 'blsgpu_sigset_info', 'blsgpu_sigset_append',
+    'blsgpu_pairing_sigset_batch', 'blsgpu_timecrypt_open_indexed_batch',
 ]
 
 
@@ -223,6 +225,12 @@ def load_library(path=None):
         lib.blsgpu_aggregate_verify_msgset_indexed_batch.argtypes = [h, u32p, h, u32p, u64p, sz, vp, ci, i32p, u64p]
         lib.blsgpu_pairing_batch.argtypes = [vp, vp, sz, ci, u8p, i32p]
         lib.blsgpu_timecrypt_open_batch.argtypes = [ci, vp, u8p, u64p, sz, vp, u8p, u8p, u64p, u8p, ci, u8p, u64p, i32p]
+        lib.blsgpu_sigset_create.argtypes = [ci, vp, u8p, sz, ci, ci, i32p, ctypes.POINTER(h)]
+        lib.blsgpu_sigset_destroy.argtypes = [h]
+        lib.blsgpu_sigset_info.argtypes = [h, ctypes.POINTER(ci), ctypes.POINTER(h), ctypes.POINTER(ci), ctypes.POINTER(h)]
+        lib.blsgpu_sigset_append.argtypes = [h, vp, u8p, sz, ci, i32p, ctypes.POINTER(h)]
+        lib.blsgpu_pairing_sigset_batch.argtypes = [h, u32p, vp, sz, ci, u8p, i32p]
+        lib.blsgpu_timecrypt_open_indexed_batch.argtypes = [h, u32p, vp, u8p, u8p, u64p, u8p, sz, ci, u8p, u64p, i32p]
         _lib = lib
     return _lib
 
@@ -732,6 +740,111 @@ def timecrypt_open_batch(sig_group, groups, fmt=FMT_RAW_PROJ, with_status=False)
                                            _ptr(b''.join(bytes(v) for _, v, _, _ in items) or b'\0'), _ptr(wblob or b'\0'),
                                            ctypes.cast(woffs, ctypes.c_void_p), _ptr(bytes(t for _, _, _, t in items) or b'\0'), fmt,
                                            ctypes.cast(frames, ctypes.c_void_p), ctypes.cast(rng, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
+    raw = frames.raw
+    out = []
+    for i in range(n):
+        lo = woffs[i] + rng[2 * i]
+        out.append(raw[lo:lo + rng[2 * i + 1]] if st[i] == OK else None)
+    return (out, list(st)[:n]) if with_status else out
+
+
+SIGSET_LINES = 1    # Bls12381G2Impl: every signature's Miller-loop rows, evaluated at u instead of a walk
+
+
+class SignatureSet:
+    """A growing table of round signatures that stays on the device (blsgpu_sigset_*): every signature is shipped, decoded and
+    subgroup-checked once, and later named by position in pairing_sigset_batch / timecrypt_open_indexed_batch.  append() adds entries
+    in place; afterwards the set is what create() gives for the final list.  Neither it nor close() (or leaving the `with` block,
+    which releases the device memory) takes a lock against readers: neither may run while another thread's call still uses the set.
+    There is no update: a published round signature does not change."""
+
+    def __init__(self, handle, status=None):
+        self.handle = handle
+        self.status = status          # the creation statuses of create()
+
+    @classmethod
+    def create(cls, sig_group, sigs, schemes, fmt=FMT_RAW_PROJ, lines=False):
+        """`sigs`: a list of points of sig_group in format fmt (an empty list is fine), `schemes` their scheme tags.  lines: the
+        per-entry line rows (SIGSET_LINES; built for sig_group 2 only).  info() says what was built; .status holds the entries'
+        creation statuses."""
+        if len(sigs) != len(schemes):
+            raise ValueError('one scheme tag per signature')
+        n = len(sigs)
+        h = ctypes.c_uint64(0)
+        st = (ctypes.c_int32 * max(n, 1))()
+        _check(init().blsgpu_sigset_create(sig_group, _ptr(b''.join(sigs)) if n else None, _ptr(bytes(schemes)) if n else None, n, fmt,
+                                           SIGSET_LINES if lines else 0, ctypes.cast(st, ctypes.c_void_p), ctypes.byref(h)))
+        return cls(h.value, list(st)[:n])
+
+    @classmethod
+    def create_device(cls, sig_group, sigs_ptr, schemes_ptr, n, fmt=FMT_RAW_PROJ, lines=False):
+        """From n signatures already on the device (integer addresses of the points and of the n tag bytes)."""
+        h = ctypes.c_uint64(0)
+        _check(init().blsgpu_sigset_create(sig_group, ctypes.c_void_p(sigs_ptr), ctypes.c_void_p(schemes_ptr), n, fmt, SIGSET_LINES if lines else 0, None,
+                                           ctypes.byref(h)))
+        return cls(h.value)
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, 0
+            _check(_lib.blsgpu_sigset_destroy(h))
+
+    destroy = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def info(self):
+        """dict(sig_group, n, has_lines, device_bytes)"""
+        sg, hl, n, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(init().blsgpu_sigset_info(self.handle, ctypes.byref(sg), ctypes.byref(n), ctypes.byref(hl), ctypes.byref(b)))
+        return {'sig_group': sg.value, 'n': n.value, 'has_lines': bool(hl.value), 'device_bytes': b.value}
+
+    def append(self, sigs, schemes, fmt=FMT_RAW_PROJ):
+        """The set grows by `sigs`; returns (the first new position, the new entries' creation statuses).  Rows the grown set has no
+        room for are dropped: see info()."""
+        if len(sigs) != len(schemes):
+            raise ValueError('one scheme tag per signature')
+        n = len(sigs)
+        first = ctypes.c_uint64(0)
+        st = (ctypes.c_int32 * max(n, 1))()
+        _check(init().blsgpu_sigset_append(self.handle, _ptr(b''.join(sigs)) if n else None, _ptr(bytes(schemes)) if n else None, n, fmt,
+                                           ctypes.cast(st, ctypes.c_void_p), ctypes.byref(first)))
+        return first.value, list(st)[:n]
+
+
+def pairing_sigset_batch(sigset, idx, points, fmt=FMT_RAW_PROJ):
+    """pairing_batch with the signature-group member of pair i at entry idx[i] of `sigset` and the other member in `points`:
+    ([576-byte strings], [status]); E_ARG with 576 zero bytes for an index outside the set."""
+    n = len(points)
+    if len(idx) != n:
+        raise ValueError('one index per point')
+    out = ctypes.create_string_buffer(GT_BYTES * max(n, 1))
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(init().blsgpu_pairing_sigset_batch(sigset.handle, ctypes.cast(_u32(idx), ctypes.c_void_p), _ptr(b''.join(points) or b'\0'), n, fmt,
+                                              ctypes.cast(out, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[GT_BYTES * i:GT_BYTES * (i + 1)] for i in range(n)], list(st)[:n]
+
+
+def timecrypt_open_indexed_batch(sigset, items, fmt=FMT_RAW_PROJ, with_status=False):
+    """timecrypt_open_batch with the signatures named by position: `items` is a list of (idx, u, v, w, scheme tag), idx a position in
+    `sigset`, in any order.  Returns [plaintext bytes or None] over the items; with_status=True: (that list, the statuses) -- E_ARG
+    for an index outside the set, else what timecrypt_open_batch gives under the entry's signature and tag."""
+    lib = init()
+    n = len(items)
+    woffs, wblob = _offsets([bytes(w) for _, _, _, w, _ in items])
+    frames = ctypes.create_string_buffer(max(len(wblob), 1))
+    rng = (ctypes.c_uint64 * (2 * max(n, 1)))()
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(lib.blsgpu_timecrypt_open_indexed_batch(sigset.handle, ctypes.cast(_u32([k for k, _, _, _, _ in items]), ctypes.c_void_p),
+                                                   _ptr(b''.join(u for _, u, _, _, _ in items) or b'\0'), _ptr(b''.join(bytes(v) for _, _, v, _, _ in items) or b'\0'),
+                                                   _ptr(wblob or b'\0'), ctypes.cast(woffs, ctypes.c_void_p), _ptr(bytes(t for _, _, _, _, t in items) or b'\0'), n, fmt,
+                                                   ctypes.cast(frames, ctypes.c_void_p), ctypes.cast(rng, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
     raw = frames.raw
     out = []
     for i in range(n):
@@ -1686,6 +1799,26 @@ class TensorOps:
                                                     self._p(w_offs), self._p(ct_schemes), fmt, self._p(frames), self._p(rng), self._p(st)))
         return frames[:ws.numel() if ws is not None else 0], rng[:2 * n].view(n, 2), st[:n]
 
+    def pairing_sigset_batch(self, sigset, idx, points, n, fmt=FMT_RAW_PROJ):
+        """pairing_batch over a SignatureSet: idx an int32 tensor holding the u32 positions' bits, points the other members; (uint8
+        tensor of n x 576 Gt bytes, int32 statuses), both on the device"""
+        self._sync()
+        out = self.empty(GT_BYTES * max(n, 1))
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_pairing_sigset_batch(sigset.handle, self._p(idx), self._p(points), n, fmt, self._p(out), self._p(st)))
+        return out[:GT_BYTES * n], st[:n]
+
+    def timecrypt_open_indexed_batch(self, sigset, idx, us, vs, ws, w_offs, ct_schemes, n, fmt=FMT_RAW_PROJ):
+        """timecrypt_open_batch over a SignatureSet, every argument on the device: idx an int32 tensor holding the u32 positions' bits,
+        the ciphertexts as in timecrypt_open_batch; (frames: uint8 like ws, pt_range: int64 of shape (n, 2), int32 statuses)"""
+        self._sync()
+        frames = self.empty(max(ws.numel() if ws is not None else 0, 1))
+        rng = self.empty(2 * max(n, 1), self.torch.int64)
+        st = self.empty(max(n, 1), self.torch.int32)
+        _check(self.lib.blsgpu_timecrypt_open_indexed_batch(sigset.handle, self._p(idx), self._p(us), self._p(vs), self._p(ws), self._p(w_offs), self._p(ct_schemes),
+                                                            n, fmt, self._p(frames), self._p(rng), self._p(st)))
+        return frames[:ws.numel() if ws is not None else 0], rng[:2 * n].view(n, 2), st[:n]
+
     def signcrypt_valid_batch(self, sg, scheme, us, ws, vs, offs, n):
         self._sync()
         st = self.empty(max(n, 1), self.torch.int32)
@@ -2433,6 +2566,18 @@ def timecrypt_decrypt_many(groups):
     if any(sig.impl.sig_group != sg or any(ct.impl.sig_group != sg for ct in cts) for sig, cts in groups):
         raise ValueError('timecrypt_decrypt_many: every signature and ciphertext must use the same impl')
     return timecrypt_open_batch(sg, [(sig.raw, sig.scheme, [(ct.u, ct.v, ct.w, ct.scheme) for ct in cts]) for sig, cts in groups])
+
+
+def timecrypt_decrypt_indexed_many(sigset, items):
+    """TimeCryptCiphertext.decrypt over many ciphertexts whose round signatures are registered: `items` is a list of (position in
+    `sigset`, TimeCryptCiphertext), in any order, all of the set's impl.  One blsgpu_timecrypt_open_indexed_batch call.  Returns one
+    plaintext or None per ciphertext, in order."""
+    if not items:
+        return []
+    sg = sigset.info()['sig_group']
+    if any(ct.impl.sig_group != sg for _, ct in items):
+        raise ValueError("timecrypt_decrypt_indexed_many: every ciphertext must use the set's impl")
+    return timecrypt_open_indexed_batch(sigset, [(k, ct.u, ct.v, ct.w, ct.scheme) for k, ct in items])
 
 
 class ElGamalCiphertext:

@@ -29,6 +29,7 @@
 #include "agg_msgset.cuh"
 #include "hkdf.cuh"
 #include "timecrypt.cuh"
+#include "sigset.cuh"
 #include "debug_ops.h"
 #include "host_sha256.h"
 
@@ -65,6 +66,8 @@ enum {
   KID_AGGM_CLASS, KID_AGGM_SUM, KID_AGGM_ITEMS,   // aggregate verify by message index (agg_msgset.cuh): check / class table / numbering, the class key sum, the flat items
   KID_PAIRING_VALUE_PREP, KID_PAIRING_VALUE,      // blsgpu_pairing_batch (timecrypt.cuh): pairs to affine and flags, the one-wave pairing that exports Gt bytes
   KID_TIMECRYPT_PREP, KID_TIMECRYPT_OPEN,         // blsgpu_timecrypt_open_batch: statuses and pairs before the pairing, the time-lock tail after it
+  KID_SIGSET_SEAL, KID_SIGSET_PREP,                // registered signature sets (sigset.cuh): create / append, the prepare kernel of both calls over a set
+  KID_PAIRING_VALUE_ROWS,                          // the one-wave pairing value that reads a registered signature's rows (in the place of k_pairing_value)
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -90,7 +93,9 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_pairing_coop_rows",
                                     "k_agg_msgset_class", "k_agg_msgset_sum", "k_agg_msgset_items",
                                     "k_pairing_value_prepare", "k_pairing_value",
-                                    "k_timecrypt_prepare", "k_timecrypt_open"};
+                                    "k_timecrypt_prepare", "k_timecrypt_open",
+                                    "k_sigset_seal", "k_sigset_prepare",
+                                    "k_pairing_value_rows"};
 
 struct Ctx {
   int dev = -1;
@@ -1903,6 +1908,44 @@ void msgset_publish(uint64_t handle, const MsgSet& m) {
   auto it = g_msgsets.find(handle);
   if (it != g_msgsets.end()) it->second = m;
 }
+// ---- registered signature sets (sigset.cuh): the same registry rules and the same id counter
+struct SigSet {
+  int sig_group = 0;
+  int flags = 0;                      // BLSGPU_SIGSET_* the creator asked for
+  size_t n = 0, devidx = 0;
+  int dev = -1;
+  uint8_t* aff = nullptr;             // RAW_AFFINE records of the signatures (group sig_group)
+  uint8_t* tags = nullptr;            // their scheme tags
+  int32_t* status = nullptr;          // their creation statuses
+  uint32_t* lines = nullptr;          // their rows (Bls12381G2Impl, BLSGPU_SIGSET_LINES; or none) ...
+  int32_t* nolines = nullptr;         // ... and per entry 0 or KEYSET_NOLINES_*
+  uint64_t bytes = 0;
+};
+std::unordered_map<uint64_t, SigSet> g_sigsets;       // under g_keyset_mu
+void sigset_free(SigSet& s) {
+  if (s.dev >= 0) (void)hipSetDevice(s.dev);
+  for (void* p : {(void*)s.aff, (void*)s.tags, (void*)s.status, (void*)s.lines, (void*)s.nolines})
+    if (p) (void)hipFree(p);
+  s = SigSet();
+}
+void sigset_release_all() {
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  for (auto& kv : g_sigsets) sigset_free(kv.second);
+  g_sigsets.clear();
+}
+int sigset_find(uint64_t handle, SigSet& s) {
+  if (!initialised()) return NOT_INIT();
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  auto it = g_sigsets.find(handle);
+  if (handle == 0 || it == g_sigsets.end()) return fail(BLSGPU_E_ARG, "unknown signature set handle (never issued, or destroyed)");
+  s = it->second;
+  return 0;
+}
+void sigset_publish(uint64_t handle, const SigSet& s) {
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  auto it = g_sigsets.find(handle);
+  if (it != g_sigsets.end()) it->second = s;
+}
 template <int G>
 size_t keyset_table_bytes_g(size_t n) { return n * (size_t)keyset_shape<G>::POINTS * 2 * G * FP_NL * 4; }
 size_t keyset_table_bytes(int group, size_t n) { return group == 1 ? keyset_table_bytes_g<1>(n) : keyset_table_bytes_g<2>(n); }
@@ -2082,6 +2125,7 @@ void blsgpu_shutdown(void) {
   if (!initialised()) return;
   keyset_release_all();
   msgset_release_all();
+  sigset_release_all();
   release_devices();
 }
 
@@ -7282,6 +7326,338 @@ int blsgpu_debug_coop_pairing_rows(int mode, uint64_t msgset, const uint32_t* ms
     }
   SYNC_FLUSH(c);
   return 0;
+}
+API_CATCH
+
+// =========================================================================================================
+// Registered signature sets (sigset.cuh): a table of round SIGNATURES that stays on the device, items named by positions in it
+static size_t sigset_rec_bytes(const SigSet& s) { return point_bytes(s.sig_group, BLSGPU_FMT_RAW_AFFINE); }
+static uint64_t sigset_bytes(const SigSet& s) {
+  return (uint64_t)(sigset_rec_bytes(s) + 1 + 4) * s.n + (s.lines ? s.n * (uint64_t)(SIGSET_ENTRY_LINE_BYTES + 4) : 0);
+}
+static int sigset_fmt_check(int fmt) {
+  if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE && fmt != BLSGPU_FMT_COMPRESSED && fmt != BLSGPU_FMT_LEGACY)
+    return fail(BLSGPU_E_ARG, "fmt must be one of the four BLSGPU_FMT_* point formats");
+  return 0;
+}
+// the rows of a whole set (Bls12381G2Impl), as msgset_build_lines builds a message set's: leaves s.lines null (and the set without
+// rows) when the size rule (keyset_lines_fit) or the device's memory says no
+static int sigset_build_lines(Ctx* c, SigSet& s) {
+  if (s.sig_group != 2 || !keyset_lines_fit(s.n, 0, (uint64_t)knobs().keyset_table_mb)) return 0;
+  const size_t lb = s.n * (size_t)SIGSET_ENTRY_LINE_BYTES, chunk = std::min<size_t>(s.n, 4096);
+  uint32_t *lines = nullptr, *scratch = nullptr;
+  int32_t* nolines = nullptr;
+  if (hipMalloc((void**)&lines, lb) != hipSuccess || hipMalloc((void**)&scratch, chunk * (size_t)SIGSET_ENTRY_LINE_BYTES) != hipSuccess ||
+      hipMalloc((void**)&nolines, 4 * s.n) != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)lines, (void*)scratch, (void*)nolines})
+      if (p) (void)hipFree(p);
+    return 0;
+  }
+  for (size_t k0 = 0; k0 < s.n; k0 += chunk) {
+    const size_t cnt = std::min(chunk, s.n - k0);
+    KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), k0, cnt, (const uint8_t*)s.aff, lines, scratch, nolines);
+  }
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(scratch);
+  if (e1 != hipSuccess || e2 != hipSuccess) {
+    (void)hipFree(lines);
+    (void)hipFree(nolines);
+    return fail(BLSGPU_E_HIP, std::string("k_keyset_lines: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+  }
+  s.lines = lines;
+  s.nolines = nolines;
+  s.bytes = sigset_bytes(s);
+  return 0;
+}
+// `count` signatures become the entries [first, first + count) of s, whose arrays have room for them: k_decompress on the wire formats
+// (the creation status), k_sigset_seal, the tags, and for a set that has rows k_keyset_lines on those entries alone, through a
+// scratch that lives for this call only and is allocated before anything is written.  status (may be null): the new entries' statuses.
+static int sigset_apply(Ctx* c, const SigSet& s, size_t first, const void* sigs, const uint8_t* schemes, size_t count, int fmt, int32_t* status) {
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  const size_t sb = point_bytes(s.sig_group, fmt) * count, raw = point_bytes(s.sig_group, BLSGPU_FMT_RAW_PROJ) * count, chunk = std::min<size_t>(count, 4096);
+  int rc = arena_reserve(c, pad256(sb) + pad256(count) + (wire ? pad256(raw) + pad256(4 * count) : 0) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  struct Work {
+    void* scratch = nullptr;
+    ~Work() {
+      if (scratch) (void)hipFree(scratch);
+    }
+  } ws;
+  if (s.lines) HIPCK(hipMalloc(&ws.scratch, chunk * (size_t)SIGSET_ENTRY_LINE_BYTES));
+  const void *d_sigs, *d_tags;
+  if ((rc = stage_in(c, sigs, sb, &d_sigs))) return rc;
+  if ((rc = stage_in(c, schemes, count, &d_tags))) return rc;
+  Carver mem{c};
+  uint8_t* d_raw = wire ? mem.take<uint8_t>(raw) : nullptr;
+  int32_t* d_dec = wire ? mem.take<int32_t>(4 * count) : nullptr;
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  int kfmt = fmt;
+  if (wire) {
+    const int legacy = fmt == BLSGPU_FMT_LEGACY;
+    with_group(s.sig_group, [&](auto G) {
+      KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_sigs, legacy, d_raw, d_dec, 0);
+    });
+    d_sigs = d_raw;
+    kfmt = BLSGPU_FMT_RAW_PROJ;
+  }
+  with_group(s.sig_group, [&](auto G) {
+    KL(KID_SIGSET_SEAL, k_sigset_seal<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_sigs, kfmt, (const int32_t*)d_dec, first, s.aff, s.status);
+  });
+  HIPCK(hipMemcpyAsync(s.tags + first, d_tags, count, hipMemcpyDeviceToDevice, c->stream));
+  if (s.lines)
+    for (size_t l0 = 0; l0 < count; l0 += chunk) {
+      const size_t cnt = std::min(chunk, count - l0);
+      KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), first + l0, cnt, (const uint8_t*)s.aff, s.lines, (uint32_t*)ws.scratch, s.nolines);
+    }
+  HIPCK(hipGetLastError());
+  if (status && (rc = copy_out(c, status, s.status + first, 4 * count))) return rc;
+  SYNC_FLUSH(c);                      // before the scratch goes
+  return 0;
+}
+
+int blsgpu_sigset_create(int sig_group, const void* sigs, const uint8_t* schemes, size_t n, int fmt, int flags, int32_t* status, uint64_t* out_handle) try {
+  if (!initialised()) return NOT_INIT();
+  if (sig_group != 1 && sig_group != 2) return fail(BLSGPU_E_ARG, "sig_group must be 1 (Bls12381G1Impl) or 2 (Bls12381G2Impl)");
+  int rc = sigset_fmt_check(fmt);
+  if (rc) return rc;
+  if (!out_handle || (n && (!sigs || !schemes))) return fail(BLSGPU_E_ARG, "null argument");
+  if (flags & ~BLSGPU_SIGSET_LINES) return fail(BLSGPU_E_ARG, "unknown flag");
+  if (n >= 0xffffffffull) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 signatures");
+  *out_handle = 0;
+  CTX_ACQUIRE(c);
+  SigSet s;
+  s.sig_group = sig_group;
+  s.flags = flags;
+  s.n = n;
+  s.devidx = t_devidx;
+  s.dev = c->dev;
+  const size_t room = std::max<size_t>(n, 1);
+  if (hipMalloc((void**)&s.aff, sigset_rec_bytes(s) * room) != hipSuccess || hipMalloc((void**)&s.tags, room) != hipSuccess ||
+      hipMalloc((void**)&s.status, 4 * room) != hipSuccess) {
+    (void)hipGetLastError();
+    sigset_free(s);
+    return fail(BLSGPU_E_HIP, "no device memory for the signature set");
+  }
+  s.bytes = sigset_bytes(s);
+  if ((n && (rc = sigset_apply(c, s, 0, sigs, schemes, n, fmt, status))) || (n && (flags & BLSGPU_SIGSET_LINES) && (rc = sigset_build_lines(c, s)))) {
+    sigset_free(s);
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_keyset_mu);
+  const uint64_t id = g_keyset_next++;
+  g_sigsets[id] = s;
+  *out_handle = id;
+  return 0;
+}
+API_CATCH
+
+int blsgpu_sigset_destroy(uint64_t handle) try {
+  if (!initialised()) return NOT_INIT();
+  SigSet s;
+  {
+    std::lock_guard<std::mutex> lk(g_keyset_mu);
+    auto it = g_sigsets.find(handle);
+    if (handle == 0 || it == g_sigsets.end()) return fail(BLSGPU_E_ARG, "unknown signature set handle (never issued, or destroyed)");
+    s = it->second;
+    g_sigsets.erase(it);
+  }
+  sigset_free(s);
+  return 0;
+}
+API_CATCH
+
+int blsgpu_sigset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_lines, uint64_t* device_bytes) try {
+  SigSet s;
+  int rc = sigset_find(handle, s);
+  if (rc) return rc;
+  if (sig_group) *sig_group = s.sig_group;
+  if (n) *n = s.n;
+  if (has_lines) *has_lines = s.lines ? 1 : 0;
+  if (device_bytes) *device_bytes = s.bytes;
+  return 0;
+}
+API_CATCH
+
+int blsgpu_sigset_append(uint64_t handle, const void* sigs, const uint8_t* schemes, size_t count, int fmt, int32_t* status, uint64_t* out_first) try {
+  SigSet s;
+  int rc = sigset_find(handle, s);
+  if (rc) return rc;
+  if ((rc = sigset_fmt_check(fmt))) return rc;
+  if (count && (!sigs || !schemes)) return fail(BLSGPU_E_ARG, "null argument");
+  if (keyset_positions_check(nullptr, count, s.n) != KEYSET_POS_OK) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 signatures");
+  if (out_first) *out_first = s.n;
+  if (count == 0) return 0;
+  CTX_ACQUIRE_ON(c, s.devidx);
+  const size_t n0 = s.n, n1 = s.n + count, asz = sigset_rec_bytes(s);
+  {  // the three arrays of the entries: all new ones before an old one goes, so that a refusal leaves the set as it was; the record keeps
+     // n0 until the tail is written
+    SigSet g = s;
+    void *old_a = nullptr, *old_t = nullptr, *old_s = nullptr;
+    const bool a = keyset_grow(c, (void**)&g.aff, asz * n0, asz * n1, &old_a), t = a && keyset_grow(c, (void**)&g.tags, n0, n1, &old_t),
+               u = t && keyset_grow(c, (void**)&g.status, 4 * n0, 4 * n1, &old_s);
+    if (!u) {
+      if (a) (void)hipFree(g.aff);
+      if (t) (void)hipFree(g.tags);
+      return fail(BLSGPU_E_HIP, "no device memory for the grown signature set");
+    }
+    s = g;
+    sigset_publish(handle, s);
+    for (void* p : {old_a, old_t, old_s}) (void)hipFree(p);
+  }
+  if (s.lines) {  // rows by the creation rule on the final size: grown, or dropped (the set works without them)
+    void *old = nullptr, *old_no = nullptr, *unused = nullptr;
+    bool keep = keyset_lines_fit(n1, 0, (uint64_t)knobs().keyset_table_mb) &&
+                keyset_grow(c, (void**)&s.lines, n0 * (size_t)SIGSET_ENTRY_LINE_BYTES, n1 * (size_t)SIGSET_ENTRY_LINE_BYTES, &old);
+    if (keep && !keyset_grow(c, (void**)&s.nolines, 4 * n0, 4 * n1, &old_no)) {
+      unused = s.lines;                         // the grown rows go with the old ones
+      s.lines = (uint32_t*)old;
+      keep = false;
+    }
+    if (!keep) {
+      old = s.lines;
+      old_no = s.nolines;
+      s.lines = nullptr;
+      s.nolines = nullptr;
+    }
+    s.bytes = sigset_bytes(s);
+    sigset_publish(handle, s);
+    for (void* p : {old, old_no, unused}) (void)hipFree(p);
+  }
+  if ((rc = sigset_apply(c, s, n0, sigs, schemes, count, fmt, status))) return rc;
+  s.n = n1;
+  s.bytes = sigset_bytes(s);
+  sigset_publish(handle, s);
+  // rows the creator asked for and the set does not have (an empty set has none) are built whole where creation would build them
+  if ((s.flags & BLSGPU_SIGSET_LINES) && !s.lines) {
+    if ((rc = sigset_build_lines(c, s))) return rc;
+    if (s.lines) sigset_publish(handle, s);
+  }
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+// ---- the two calls over a signature set.  Launch sequence: k_decompress of the callers' points (wire formats only), k_sigset_prepare
+// (index check, statuses up to the identity checks, the pair made affine, the item's entry, and one word back to the host where the
+// plan may read rows: whether any named entry lacks usable rows), the pairing over chunks of at most 4,096 items -- k_pairing_value_rows
+// for a Bls12381G2Impl set whose named entries all have rows, else k_pairing_value as it is --, and for the opening call
+// k_timecrypt_open unchanged.  ct == false: blsgpu_pairing_sigset_batch.
+static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool ct, const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets,
+                      const uint8_t* ct_schemes, size_t n, int fmt, uint8_t* out_gt, uint8_t* frames, uint64_t* pt_range, int32_t* status) {
+  SigSet s;
+  int rc = sigset_find(sigset, s);
+  if (rc) return rc;
+  if ((rc = sigset_fmt_check(fmt))) return rc;
+  if (n == 0) return 0;
+  if (n >= ((uint64_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more items in one call");
+  CTX_ACQUIRE_ON(c, s.devidx);
+  std::vector<uint64_t> woffs;
+  size_t total = 0;
+  if (ct) {
+    if (!w_offsets) return fail(BLSGPU_E_ARG, "null w_offsets");
+    if ((rc = read_offsets(w_offsets, n, "w_offsets", woffs))) return rc;
+    total = (size_t)woffs[n];
+    for (size_t i = 0; i < n; i++)
+      if ((woffs[i + 1] - woffs[i]) >> 29) return fail(BLSGPU_E_ARG, "a w of 512 MiB or more");
+    if (!vs || !ct_schemes || !pt_range || (total && (!ws || !frames))) return fail(BLSGPU_E_ARG, "null argument");
+  } else if (!out_gt) {
+    return fail(BLSGPU_E_ARG, "null argument");
+  }
+  if (!idx || !us || !status) return fail(BLSGPU_E_ARG, "null argument");
+  const int sg = s.sig_group, pg = key_group(sg);
+  const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
+  const size_t ub = point_bytes(pg, fmt) * n, u_raw = point_bytes(pg, BLSGPU_FMT_RAW_PROJ) * n;
+  size_t need = pad256(4 * n) + pad256(ub) + 4 * pad256(4 * n) + pad256((size_t)WS_PAIR1_WORDS * 4 * n) + pad256((size_t)GT_BYTES * n) + 512 + 8192;
+  if (ct) need += pad256(32 * n) + 2 * pad256(total) + pad256(8 * (n + 1)) + pad256(n) + pad256(16 * n);
+  if (wire) need += pad256(u_raw) + pad256(4 * n);
+  if ((rc = arena_reserve(c, need))) return rc;
+  c->arena_off = 0;
+  const void *d_idx, *d_us, *d_vs = nullptr, *d_ws = nullptr, *d_cs = nullptr;
+  const uint64_t* d_woffs = nullptr;
+  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  if ((rc = stage_in(c, us, ub, &d_us))) return rc;
+  auto drain = [&](int r) {
+    (void)hipStreamSynchronize(c->stream);      // the upload reads woffs
+    return r;
+  };
+  if (ct) {
+    if ((rc = stage_in(c, vs, 32 * n, &d_vs))) return rc;
+    if ((rc = stage_in(c, ws, total, &d_ws))) return rc;
+    if ((rc = stage_in(c, ct_schemes, n, &d_cs))) return rc;
+    if ((rc = upload_offsets(c, woffs, &d_woffs))) return drain(rc);
+  }
+  Carver mem{c};
+  uint8_t* d_frames = ct ? (total ? mem.stage_out<uint8_t>(frames, total) : c->arena) : nullptr;
+  uint64_t* d_range = ct ? mem.stage_out<uint64_t>(pt_range, 16 * n) : nullptr;
+  uint8_t* d_gt = ct ? mem.take<uint8_t>((size_t)GT_BYTES * n) : mem.stage_out<uint8_t>(out_gt, (size_t)GT_BYTES * n);
+  int32_t* d_status = ct ? mem.take<int32_t>(4 * n) : mem.stage_out<int32_t>(status, 4 * n);
+  int32_t* d_flag = mem.take<int32_t>(4 * n);
+  uint32_t* d_ent = mem.take<uint32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * n);
+  uint32_t* d_walk = mem.take<uint32_t>(4);
+  uint8_t* d_u_raw = wire ? mem.take<uint8_t>(u_raw) : nullptr;
+  int32_t* d_dec_u = wire ? mem.take<int32_t>(4 * n) : nullptr;
+  if (!mem.ok) return drain(fail(BLSGPU_E_HIP, "internal: arena too small"));
+  if (ct && total && d_frames != frames && hipMemsetAsync(d_frames, 0, total, c->stream) != hipSuccess)   // an item that is not opened hands back zeros
+    return drain(fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
+  if (hipMemsetAsync(d_walk, 0, 4, c->stream) != hipSuccess) return drain(fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
+  int kfmt = fmt;
+  if (wire) {
+    const int legacy = fmt == BLSGPU_FMT_LEGACY;
+    with_group(pg, [&](auto G) { KL(KID_DECOMPRESS, k_decompress<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_us, legacy, d_u_raw, d_dec_u, 0); });
+    d_us = d_u_raw;
+    kfmt = BLSGPU_FMT_RAW_PROJ;
+  }
+  const bool rows_wanted = s.lines && sg == 2;
+  with_group(sg, [&](auto G) {
+    KL(KID_SIGSET_PREP, k_sigset_prepare<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_idx, (uint64_t)s.n, (const uint8_t*)s.aff,
+       (const uint8_t*)s.tags, (const int32_t*)s.status, rows_wanted ? (const int32_t*)s.nolines : (const int32_t*)nullptr, (const uint8_t*)d_us, kfmt,
+       (const int32_t*)d_dec_u, (const uint8_t*)d_cs, d_pairs, d_flag, d_status, d_ent, d_walk);
+  });
+  const uint32_t* rows = nullptr;
+  if (rows_wanted) {  // one plan per call: a named entry without usable rows makes every item walk
+    uint32_t* h_walk = (uint32_t*)hsmall_take(c, 4);
+    if (!h_walk) return drain(fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted"));
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_walk, d_walk, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+      return drain(fail(BLSGPU_E_HIP, "k_sigset_prepare failed"));
+    rows = *h_walk == 0 ? s.lines : nullptr;
+  }
+  for (size_t first = 0; first < n; first += PAIRING_VALUE_CHUNK) {
+    const size_t count = std::min(PAIRING_VALUE_CHUNK, n - first);
+    if (rows)
+      KL(KID_PAIRING_VALUE_ROWS, k_pairing_value_rows, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, rows,
+         (const uint32_t*)d_ent, d_gt);
+    else
+      KL(KID_PAIRING_VALUE, k_pairing_value, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, d_gt);
+  }
+  if (!ct) {
+    if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a pairing-value kernel failed to launch"));
+    if ((rc = stage_back(c, out_gt, d_gt, (size_t)GT_BYTES * n))) return drain(rc);
+    if ((rc = stage_back(c, status, d_status, 4 * n))) return drain(rc);
+    SYNC_FLUSH(c);
+    return 0;
+  }
+  with_group(sg, [&](auto G) {
+    KL(KID_TIMECRYPT_OPEN, k_timecrypt_open<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_gt, (const uint8_t*)d_us, kfmt, (const uint8_t*)d_vs,
+       (const uint8_t*)d_ws, d_woffs, d_frames, d_range, d_status);
+  });
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_timecrypt_open failed to launch"));
+  if (total && (rc = stage_back(c, frames, d_frames, total))) return drain(rc);
+  if ((rc = stage_back(c, pt_range, d_range, 16 * n))) return drain(rc);
+  return status_out_and_sync(c, status, d_status, n);
+}
+
+int blsgpu_pairing_sigset_batch(uint64_t sigset, const uint32_t* idx, const void* points, size_t n, int fmt, uint8_t* out_gt, int32_t* status) try {
+  return sigset_run(sigset, idx, points, false, nullptr, nullptr, nullptr, nullptr, n, fmt, out_gt, nullptr, nullptr, status);
+}
+API_CATCH
+
+int blsgpu_timecrypt_open_indexed_batch(uint64_t sigset, const uint32_t* idx, const void* us, const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets,
+                                        const uint8_t* ct_schemes, size_t n, int fmt, uint8_t* frames, uint64_t* pt_range, int32_t* status) try {
+  return sigset_run(sigset, idx, us, true, vs, ws, w_offsets, ct_schemes, n, fmt, nullptr, frames, pt_range, status);
 }
 API_CATCH
 }  // extern "C"

@@ -898,6 +898,59 @@ int blsgpu_aggregate_verify_msgset_batch(uint64_t msgset, const uint32_t* msg_id
 int blsgpu_aggregate_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx,
                                                  const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux);
 
+/* ---- Registered signature sets: the third member beside key sets and message sets.  A time-lock service keeps a growing list of
+ * round signatures; ciphertexts arrive for any of those rounds, in any order, over many calls.  blsgpu_timecrypt_open_batch makes
+ * the caller sort them into groups, ship every signature again and have it decoded and subgroup-checked again, and under
+ * Bls12381G2Impl walks the same G2 point through the 68 Miller entries once per ciphertext.  A set keeps per signature what that call
+ * works out per group before its items start -- the point as a RAW_AFFINE record of its group (96 or 192 bytes, all-zero for the
+ * identity), its scheme tag (0 / 1 / 2; any byte is kept as it comes and compared as the by-value call compares it) and its
+ * creation status -- and later calls name an item's signature by its position.
+ *
+ * Handles follow the key sets' rules: an opaque non-zero id, never a pointer; a stale or unknown id (a key set's or a message set's
+ * included) returns BLSGPU_E_ARG; hipMalloc'd outside the context arenas on the device of the context that ran the creation, freed
+ * by blsgpu_sigset_destroy or blsgpu_shutdown; append takes no lock against readers (running any call on a set while another thread
+ * appends to or destroys it is the caller's error).  There is no update: a published round signature does not change.
+ *
+ * create: n signatures of sig_group in format fmt (any of the four) with one scheme tag each; n == 0 is valid.  status (may be null)
+ *   gets the n creation statuses: on COMPRESSED / LEGACY the decode status, subgroup test included (BLSGPU_OK, BLSGPU_BAD_ENCODING,
+ *   BLSGPU_LEGACY_FORMAT); the raw formats are not subgroup-checked, as everywhere else, and every entry is BLSGPU_OK.  An identity
+ *   signature is a valid entry with status BLSGPU_OK: the items that name it get BLSGPU_SIG_IDENTITY.  Nothing of the caller's
+ *   buffers is retained.  flags & BLSGPU_SIGSET_LINES (Bls12381G2Impl; accepted and without effect for sig_group 1, whose signatures
+ *   are G1 points and have no lines): every entry also gets the 68 normalised Miller rows of its point, 15,232 bytes, so that
+ *   K = e(u, sig) evaluates the rows at u and walks nothing (k_pairing_value_rows).  The rows are not built, and the set works
+ *   without them, when they would reach 2^32 bytes (281,970 entries), exceed BLSGPU_KEYSET_TABLE_MB MiB, or find no room on the
+ *   device.  An entry that did not decode, is the identity, or whose walk meets a vanishing denominator has no usable rows: a call
+ *   that names it walks all its items.  Rows change the plan, never a status or a byte.
+ * info: *has_lines is 1 when the set has rows.
+ * append: the set grows by `count` signatures, *out_first (may be null) gets the first new position, status (may be null) the new
+ *   entries' creation statuses; when the device has no room for the grown records the set is unchanged.  Only the new entries are
+ *   decoded and built; afterwards the set is what creation of the final list gives (rows the grown set has no room for are dropped,
+ *   rows the creator asked for and an empty set could not have are built).  sigs, schemes and status may be host or device memory. */
+#define BLSGPU_SIGSET_LINES 1
+int blsgpu_sigset_create(int sig_group, const void* sigs, const uint8_t* schemes, size_t n, int fmt, int flags, int32_t* status, uint64_t* out_handle);
+int blsgpu_sigset_destroy(uint64_t handle);
+int blsgpu_sigset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_lines, uint64_t* device_bytes);
+int blsgpu_sigset_append(uint64_t handle, const void* sigs, const uint8_t* schemes, size_t count, int fmt, int32_t* status, uint64_t* out_first);
+/* blsgpu_pairing_batch with the signature-group member of pair i at entry idx[i] of a signature set and the other member (G2 under
+ * Bls12381G1Impl, G1 under Bls12381G2Impl) in `points`, n of them in format fmt.  The same three outcomes: the 576 bytes of
+ * Gt::to_bytes() with BLSGPU_OK; Gt one with BLSGPU_OK when a member is the identity; 576 zero bytes with the decode status when a
+ * member did not decode (the G1 member's first; the entry's is its creation status).  And one more, before them: BLSGPU_E_ARG in the
+ * slot, with 576 zero bytes, for an index outside the set; other items are unaffected and the call returns 0.  There are no groups
+ * and the caller owes no order.  Every pointer may be host or device memory; the call runs on the set's device. */
+int blsgpu_pairing_sigset_batch(uint64_t sigset, const uint32_t* idx, const void* points, size_t n, int fmt, uint8_t* out_gt, int32_t* status);
+/* blsgpu_timecrypt_open_batch with item i's signature named as entry idx[i] of a signature set: no groups, no item offsets, no order.
+ * us, vs, ws, w_offsets, ct_schemes, fmt, frames, pt_range and the w_offsets rule are that call's.  status[i] is the first of:
+ * BLSGPU_E_ARG in the slot for an index outside the set (other items are unaffected and the call returns 0); otherwise exactly what
+ * blsgpu_timecrypt_open_batch returns for the item in a group under the entry's signature and tag -- in order the decode status of
+ * u_i, the entry's creation status, BLSGPU_INVALID_SCHEME, BLSGPU_SIG_IDENTITY, BLSGPU_PK_IDENTITY, BLSGPU_BAD_FRAME,
+ * BLSGPU_INVALID_SIGNATURE, BLSGPU_OK.  A failed item's pt_range is (0, 0).  Every pointer may be host or device memory; w_offsets is
+ * read and checked on the host; the call runs on the set's device.  Launch sequence: k_decompress of the u (wire formats),
+ * k_sigset_prepare, the pairing in chunks of at most 4,096 items -- k_pairing_value_rows over a Bls12381G2Impl set with rows,
+ * k_pairing_value otherwise -- and k_timecrypt_open. */
+int blsgpu_timecrypt_open_indexed_batch(uint64_t sigset, const uint32_t* idx, const void* us, const uint8_t* vs, const uint8_t* ws,
+                                        const uint64_t* w_offsets, const uint8_t* ct_schemes, size_t n, int fmt, uint8_t* frames, uint64_t* pt_range,
+                                        int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
