@@ -751,12 +751,31 @@ def timecrypt_open_batch(sig_group, groups, fmt=FMT_RAW_PROJ, with_status=False)
 SIGSET_LINES = 1    # Bls12381G2Impl: every signature's Miller-loop rows, evaluated at u instead of a walk
 
 
-class SignatureSet:
+class _RegisteredSet:
+    """What KeySet, MessageSet and SignatureSet share: close() releases the set's device memory (once), and so does leaving the
+    `with` block.  DESTROY names the kind's blsgpu_*_destroy."""
+    DESTROY = None
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, 0
+            _check(getattr(_lib, self.DESTROY)(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class SignatureSet(_RegisteredSet):
     """A growing table of round signatures that stays on the device (blsgpu_sigset_*): every signature is shipped, decoded and
     subgroup-checked once, and later named by position in pairing_sigset_batch / timecrypt_open_indexed_batch.  append() adds entries
     in place; afterwards the set is what create() gives for the final list.  Neither it nor close() (or leaving the `with` block,
     which releases the device memory) takes a lock against readers: neither may run while another thread's call still uses the set.
     There is no update: a published round signature does not change."""
+    DESTROY = 'blsgpu_sigset_destroy'
 
     def __init__(self, handle, status=None):
         self.handle = handle
@@ -784,19 +803,7 @@ class SignatureSet:
                                            ctypes.byref(h)))
         return cls(h.value)
 
-    def close(self):
-        if self.handle:
-            h, self.handle = self.handle, 0
-            _check(_lib.blsgpu_sigset_destroy(h))
-
-    destroy = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+    destroy = _RegisteredSet.close
 
     def info(self):
         """dict(sig_group, n, has_lines, device_bytes)"""
@@ -925,11 +932,12 @@ def _u32(idx):
     return (ctypes.c_uint32 * max(len(idx), 1))(*idx)
 
 
-class KeySet:
+class KeySet(_RegisteredSet):
     """A table of public keys that stays on the device (blsgpu_keyset_*): created once from wire bytes or raw points, then named by
     position in the *_indexed_batch calls.  update() replaces entries and append() adds entries in place; afterwards the set is
     what create() gives for the final key list.  Neither they nor close() (or leaving the `with` block, which releases the device
     memory) take a lock against readers: none of the three may run while another thread's call still uses the set."""
+    DESTROY = 'blsgpu_keyset_destroy'
 
     def __init__(self, handle, statuses):
         self.handle, self.statuses = handle, statuses
@@ -959,18 +967,6 @@ class KeySet:
     @staticmethod
     def _flags(tables, lines):
         return (KEYSET_TABLES if tables else 0) | (KEYSET_LINES if lines else 0)
-
-    def close(self):
-        if self.handle:
-            h, self.handle = self.handle, 0
-            _check(_lib.blsgpu_keyset_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     def info(self):
         """dict(sig_group, n, has_tables, has_lines, device_bytes): what creation built (bit 0 / bit 1 of the C call's mask)"""
@@ -1161,12 +1157,13 @@ def verify_shared_indexed_batch(keyset, scheme, groups, fmt=FMT_RAW_PROJ):
 MSGSET_LINES = 1    # Bls12381G2Impl: every message point's Miller-loop rows, read above BLSGPU_WIDE_MAX items
 
 
-class MessageSet:
+class MessageSet(_RegisteredSet):
     """A table of hashed messages that stays on the device (blsgpu_msgset_*): every message is hashed once, under the scheme's DST, and
     later named by position in verify_msgset_batch / verify_msgset_indexed_batch.  update() replaces entries and append() adds
     entries in place; afterwards the set is what create() gives for the final message list.  Neither they nor close() (or leaving
     the `with` block, which releases the device memory) take a lock against readers: none of the three may run while another
     thread's call still uses the set."""
+    DESTROY = 'blsgpu_msgset_destroy'
 
     def __init__(self, handle):
         self.handle = handle
@@ -1189,18 +1186,6 @@ class MessageSet:
         _check(init().blsgpu_msgset_create(sig_group, scheme, ctypes.c_void_p(msgs_ptr), ctypes.c_void_p(offs_ptr), n, MSGSET_LINES if lines else 0,
                                            ctypes.byref(h)))
         return cls(h.value)
-
-    def close(self):
-        if self.handle:
-            h, self.handle = self.handle, 0
-            _check(_lib.blsgpu_msgset_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     def info(self):
         """dict(sig_group, scheme, n, has_lines, device_bytes)"""

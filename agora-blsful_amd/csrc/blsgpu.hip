@@ -1827,128 +1827,134 @@ int run_first_duplicate(Ctx* c, const uint8_t* d_msgs, const uint64_t* d_offs, s
   return 0;
 }
 
-// ---- registered key sets (keyset.cuh): the registry.  A handle is an id, never a pointer: a stale one is simply not found.
-// A call works on a copy of the record taken under the lock.  blsgpu_keyset_update rewrites entries behind unchanged pointers;
-// blsgpu_keyset_append moves the arrays and replaces the record under the lock (keyset_publish), freeing an old array only after
-// the record has stopped naming it.  Neither waits for calls that hold a copy: running one while another thread updates, appends
-// to or destroys the same set is the caller's error.
-struct KeySet {
-  int sig_group = 0, group = 0;       // group: where the keys live
-  int flags = 0;                      // BLSGPU_KEYSET_* the creator asked for (what is built: table, lines)
-  size_t n = 0, devidx = 0;
-  int dev = -1;
-  uint8_t *aff = nullptr, *comp = nullptr, *table = nullptr;     // RAW_AFFINE records, Modern bytes, fixed-base tables (or none)
-  uint32_t* lines = nullptr;          // line tables (G2 keys, BLSGPU_KEYSET_LINES; or none) ...
-  int32_t* nolines = nullptr;         // ... and per entry 0 or KEYSET_NOLINES_*
-  int32_t* status = nullptr;
-  uint64_t bytes = 0;
-};
-std::mutex g_keyset_mu;
-std::unordered_map<uint64_t, KeySet> g_keysets;
-uint64_t g_keyset_next = 1;
-void keyset_free(KeySet& k) {
-  if (k.dev >= 0) (void)hipSetDevice(k.dev);
-  for (void* p : {(void*)k.aff, (void*)k.comp, (void*)k.table, (void*)k.lines, (void*)k.nolines, (void*)k.status})
-    if (p) (void)hipFree(p);
-  k = KeySet();
-}
-void keyset_release_all() {
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  for (auto& kv : g_keysets) keyset_free(kv.second);
-  g_keysets.clear();
-}
-int keyset_find(uint64_t handle, KeySet& k) {
-  if (!initialised()) return NOT_INIT();
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  auto it = g_keysets.find(handle);
-  if (handle == 0 || it == g_keysets.end()) return fail(BLSGPU_E_ARG, "unknown key set handle (never issued, or destroyed)");
-  k = it->second;
-  return 0;
-}
-// the record of a live set after an append moved its arrays; a handle destroyed meanwhile (the caller's error) stays gone
-void keyset_publish(uint64_t handle, const KeySet& k) {
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  auto it = g_keysets.find(handle);
-  if (it != g_keysets.end()) it->second = k;
-}
-// ---- registered message sets (msgset.cuh): the same registry rules.  Ids come from the key sets' counter, so a handle of one kind
-// is never found as the other.
-struct MsgSet {
-  int sig_group = 0, scheme = 0;
-  int flags = 0;                      // BLSGPU_MSGSET_* the creator asked for
-  size_t n = 0, devidx = 0;
-  int dev = -1;
-  uint8_t* aff = nullptr;             // RAW_AFFINE records of the hashed messages (group sig_group)
-  uint32_t* lines = nullptr;          // their rows (Bls12381G2Impl, BLSGPU_MSGSET_LINES; or none) ...
-  int32_t* nolines = nullptr;         // ... and per entry 0 or KEYSET_NOLINES_*
-  uint64_t bytes = 0;
-};
-std::unordered_map<uint64_t, MsgSet> g_msgsets;       // under g_keyset_mu
-void msgset_free(MsgSet& m) {
-  if (m.dev >= 0) (void)hipSetDevice(m.dev);
-  for (void* p : {(void*)m.aff, (void*)m.lines, (void*)m.nolines})
-    if (p) (void)hipFree(p);
-  m = MsgSet();
-}
-void msgset_release_all() {
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  for (auto& kv : g_msgsets) msgset_free(kv.second);
-  g_msgsets.clear();
-}
-int msgset_find(uint64_t handle, MsgSet& m) {
-  if (!initialised()) return NOT_INIT();
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  auto it = g_msgsets.find(handle);
-  if (handle == 0 || it == g_msgsets.end()) return fail(BLSGPU_E_ARG, "unknown message set handle (never issued, or destroyed)");
-  m = it->second;
-  return 0;
-}
-void msgset_publish(uint64_t handle, const MsgSet& m) {
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  auto it = g_msgsets.find(handle);
-  if (it != g_msgsets.end()) it->second = m;
-}
-// ---- registered signature sets (sigset.cuh): the same registry rules and the same id counter
-struct SigSet {
-  int sig_group = 0;
-  int flags = 0;                      // BLSGPU_SIGSET_* the creator asked for
-  size_t n = 0, devidx = 0;
-  int dev = -1;
-  uint8_t* aff = nullptr;             // RAW_AFFINE records of the signatures (group sig_group)
-  uint8_t* tags = nullptr;            // their scheme tags
-  int32_t* status = nullptr;          // their creation statuses
-  uint32_t* lines = nullptr;          // their rows (Bls12381G2Impl, BLSGPU_SIGSET_LINES; or none) ...
-  int32_t* nolines = nullptr;         // ... and per entry 0 or KEYSET_NOLINES_*
-  uint64_t bytes = 0;
-};
-std::unordered_map<uint64_t, SigSet> g_sigsets;       // under g_keyset_mu
-void sigset_free(SigSet& s) {
-  if (s.dev >= 0) (void)hipSetDevice(s.dev);
-  for (void* p : {(void*)s.aff, (void*)s.tags, (void*)s.status, (void*)s.lines, (void*)s.nolines})
-    if (p) (void)hipFree(p);
-  s = SigSet();
-}
-void sigset_release_all() {
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  for (auto& kv : g_sigsets) sigset_free(kv.second);
-  g_sigsets.clear();
-}
-int sigset_find(uint64_t handle, SigSet& s) {
-  if (!initialised()) return NOT_INIT();
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  auto it = g_sigsets.find(handle);
-  if (handle == 0 || it == g_sigsets.end()) return fail(BLSGPU_E_ARG, "unknown signature set handle (never issued, or destroyed)");
-  s = it->second;
-  return 0;
-}
-void sigset_publish(uint64_t handle, const SigSet& s) {
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  auto it = g_sigsets.find(handle);
-  if (it != g_sigsets.end()) it->second = s;
-}
 template <int G>
 size_t keyset_table_bytes_g(size_t n) { return n * (size_t)keyset_shape<G>::POINTS * 2 * G * FP_NL * 4; }
 size_t keyset_table_bytes(int group, size_t n) { return group == 1 ? keyset_table_bytes_g<1>(n) : keyset_table_bytes_g<2>(n); }
+
+// ---- registered sets (keyset.cuh, msgset.cuh, sigset.cuh): the records and the registry.  A handle is an id, never a pointer: a
+// stale one is simply not found.  The three kinds have a map each and share one mutex and one id counter, so a handle of one kind
+// is never found as another.  A call works on a copy of the record taken under the lock (set_find).  An update rewrites entries
+// behind unchanged pointers; an append moves the arrays and replaces the record under the lock (set_publish), freeing an old array
+// only after a record that no longer names it has been published.  Neither waits for calls that hold a copy: running one while
+// another thread updates, appends to or destroys the same set is the caller's error.
+struct DevSet {
+  int sig_group = 0;
+  int flags = 0;                      // BLSGPU_{KEYSET,MSGSET,SIGSET}_* the creator asked for (what is built: table, lines)
+  size_t n = 0, devidx = 0;
+  int dev = -1;
+  uint8_t* aff = nullptr;             // RAW_AFFINE records of the entries
+  uint32_t* lines = nullptr;          // their rows (entries in G2, the kind's LINES flag; or none) ...
+  int32_t* nolines = nullptr;         // ... and per entry 0 or KEYSET_NOLINES_*
+  uint64_t bytes = 0;
+};
+struct KeySet : DevSet {
+  int group = 0;                      // where the keys live
+  uint8_t *comp = nullptr, *table = nullptr;     // Modern bytes, fixed-base tables (or none)
+  int32_t* status = nullptr;
+};
+struct MsgSet : DevSet {              // aff: the hashed messages (group sig_group)
+  int scheme = 0;
+};
+struct SigSet : DevSet {              // aff: the signatures (group sig_group)
+  uint8_t* tags = nullptr;            // their scheme tags
+  int32_t* status = nullptr;          // their creation statuses
+};
+std::mutex g_sets_mu;
+uint64_t g_sets_next = 1;
+std::unordered_map<uint64_t, KeySet> g_keysets;       // all three under g_sets_mu
+std::unordered_map<uint64_t, MsgSet> g_msgsets;
+std::unordered_map<uint64_t, SigSet> g_sigsets;
+
+// what a kind states about itself: its map, its name and its entries' noun in messages, the arrays that hold one record per entry
+// (with a record's bytes), the group its rows need to be 2 and the flag that asks for them; a key set alone has tables, which
+// share the rows' cap
+struct SetArray {
+  void** p;
+  size_t entry_bytes;
+};
+std::unordered_map<uint64_t, KeySet>& set_map(const KeySet&) { return g_keysets; }
+std::unordered_map<uint64_t, MsgSet>& set_map(const MsgSet&) { return g_msgsets; }
+std::unordered_map<uint64_t, SigSet>& set_map(const SigSet&) { return g_sigsets; }
+const char* set_name(const KeySet&) { return "key set"; }
+const char* set_name(const MsgSet&) { return "message set"; }
+const char* set_name(const SigSet&) { return "signature set"; }
+const char* set_noun(const KeySet&) { return "keys"; }
+const char* set_noun(const MsgSet&) { return "messages"; }
+const char* set_noun(const SigSet&) { return "signatures"; }
+std::vector<SetArray> set_arrays(KeySet& k) {
+  return {{(void**)&k.aff, point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE)}, {(void**)&k.comp, point_bytes(k.group, BLSGPU_FMT_COMPRESSED)}, {(void**)&k.status, 4}};
+}
+std::vector<SetArray> set_arrays(MsgSet& m) { return {{(void**)&m.aff, point_bytes(m.sig_group, BLSGPU_FMT_RAW_AFFINE)}}; }
+std::vector<SetArray> set_arrays(SigSet& s) {
+  return {{(void**)&s.aff, point_bytes(s.sig_group, BLSGPU_FMT_RAW_AFFINE)}, {(void**)&s.tags, 1}, {(void**)&s.status, 4}};
+}
+int set_rows_group(const DevSet& s) { return s.sig_group; }
+int set_rows_group(const KeySet& k) { return k.group; }
+int set_rows_flag(const KeySet&) { return BLSGPU_KEYSET_LINES; }
+int set_rows_flag(const MsgSet&) { return BLSGPU_MSGSET_LINES; }
+int set_rows_flag(const SigSet&) { return BLSGPU_SIGSET_LINES; }
+void* set_table(const DevSet&) { return nullptr; }
+void* set_table(const KeySet& k) { return k.table; }
+uint64_t set_other_bytes(const DevSet&, size_t) { return 0; }          // what shares the cap of keyset_lines_fit with n entries' rows
+uint64_t set_other_bytes(const KeySet& k, size_t n) { return k.table ? keyset_table_bytes(k.group, n) : 0; }
+
+// device_bytes of a set as it stands: the records, the tables and the rows with their per-entry words
+template <class T>
+uint64_t set_bytes(const T& s) {
+  uint64_t per_entry = s.lines ? KEYSET_LINES_KEY_BYTES + 4 : 0;
+  for (const SetArray& a : set_arrays(const_cast<T&>(s))) per_entry += a.entry_bytes;
+  return per_entry * s.n + set_other_bytes(s, s.n);
+}
+template <class T>
+void set_free(T& s) {
+  if (s.dev >= 0) (void)hipSetDevice(s.dev);
+  for (const SetArray& a : set_arrays(s))
+    if (*a.p) (void)hipFree(*a.p);
+  for (void* p : {(void*)s.lines, (void*)s.nolines, set_table(s)})
+    if (p) (void)hipFree(p);
+  s = T();
+}
+template <class T>
+void set_release_all() {
+  std::lock_guard<std::mutex> lk(g_sets_mu);
+  auto& map = set_map(T());
+  for (auto& kv : map) set_free(kv.second);
+  map.clear();
+}
+template <class T>
+int set_find(uint64_t handle, T& s, bool take = false) {       // take: the record leaves the registry (destroy)
+  if (!initialised()) return NOT_INIT();
+  std::lock_guard<std::mutex> lk(g_sets_mu);
+  auto& map = set_map(s);
+  auto it = map.find(handle);
+  if (handle == 0 || it == map.end()) return fail(BLSGPU_E_ARG, std::string("unknown ") + set_name(s) + " handle (never issued, or destroyed)");
+  s = it->second;
+  if (take) map.erase(it);
+  return 0;
+}
+// the record of a live set after an append moved its arrays; a handle destroyed meanwhile (the caller's error) stays gone
+template <class T>
+void set_publish(uint64_t handle, const T& s) {
+  std::lock_guard<std::mutex> lk(g_sets_mu);
+  auto& map = set_map(s);
+  auto it = map.find(handle);
+  if (it != map.end()) it->second = s;
+}
+template <class T>
+uint64_t set_issue(const T& s) {
+  std::lock_guard<std::mutex> lk(g_sets_mu);
+  const uint64_t id = g_sets_next++;
+  set_map(s)[id] = s;
+  return id;
+}
+template <class T>
+int set_destroy(uint64_t handle) {
+  T s;
+  int rc = set_find(handle, s, true);
+  if (rc) return rc;
+  set_free(s);
+  return 0;
+}
 
 }  // namespace
 
@@ -2123,9 +2129,9 @@ int blsgpu_device_count(void) { return (int)g_devices.size(); }
 void blsgpu_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_init_mu);
   if (!initialised()) return;
-  keyset_release_all();
-  msgset_release_all();
-  sigset_release_all();
+  set_release_all<KeySet>();
+  set_release_all<MsgSet>();
+  set_release_all<SigSet>();
   release_devices();
 }
 
@@ -5592,37 +5598,168 @@ static int keyset_build_tables(Ctx* c, KeySet& k) {
   k.bytes += tb;
   return 0;
 }
-// the line tables of a new set of G2 keys, in chunks of 4,096 keys so that the scratch rows k_keyset_lines needs (as much again as
-// the rows it writes) stay at 62 MB; leaves k.lines null (and the set without them) when the size rule (keyset_lines_fit: the
-// 32-bit offset of k_lines2s_keyed, and the knob's cap together with the fixed-base tables) or the device's memory says no
-static int keyset_build_lines(Ctx* c, KeySet& k) {
-  if (k.group != 2 || !keyset_lines_fit(k.n, k.table ? keyset_table_bytes(k.group, k.n) : 0, (uint64_t)knobs().keyset_table_mb)) return 0;
-  const size_t lb = k.n * (size_t)KEYSET_LINES_KEY_BYTES, chunk = std::min<size_t>(k.n, 4096);
+// ---- what the three kinds of registered set share: rows, growth, the tail of an append, the positions of an update
+extern "C++" {
+// a device buffer that lives for one call
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+// k_keyset_lines[_at] work in chunks of 4,096 entries so that the scratch rows they need (as much again as the rows they write)
+// stay at 62 MB
+static size_t set_lines_scratch_bytes(size_t count) { return std::min<size_t>(count, 4096) * (size_t)KEYSET_LINES_KEY_BYTES; }
+// the rows of `count` entries of a set that has rows, through a scratch of set_lines_scratch_bytes(count): the entries d_pos[0 .. count)
+// (k_keyset_lines_at) or -- d_pos == nullptr -- the entries [first, first + count) (k_keyset_lines)
+static void set_launch_lines(Ctx* c, const DevSet& s, const uint32_t* d_pos, size_t first, size_t count, void* scratch) {
+  const size_t chunk = std::min<size_t>(count, 4096);
+  for (size_t l0 = 0; l0 < count; l0 += chunk) {
+    const size_t cnt = std::min(chunk, count - l0);
+    if (d_pos)
+      KL(KID_KEYSET_LINES_AT, k_keyset_lines_at, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), cnt, d_pos + l0, (const uint8_t*)s.aff, s.lines, (uint32_t*)scratch,
+         s.nolines);
+    else
+      KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), first + l0, cnt, (const uint8_t*)s.aff, s.lines, (uint32_t*)scratch, s.nolines);
+  }
+}
+// One array of a growing set: `bytes_new` bytes with the first `bytes_old` copied from *p; *p is replaced and the old array left in
+// *old for the caller to free once no record names it.  false: the device has no room (or the copy failed) and *p is untouched.
+static bool set_grow(Ctx* c, void** p, size_t bytes_old, size_t bytes_new, void** old) {
+  void* q = nullptr;
+  if (hipMalloc(&q, std::max<size_t>(bytes_new, 1)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (bytes_old && (hipMemcpyAsync(q, *p, bytes_old, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) {
+    (void)hipGetLastError();
+    (void)hipFree(q);
+    return false;
+  }
+  *old = *p;
+  *p = q;
+  return true;
+}
+// what a kind builds besides rows once the tail of an append is published: a key set the tables its creator asked for and it lacks.
+// They share the rows' cap, so rows that no longer fit beside them are dropped.
+static int set_build_others(Ctx*, uint64_t, DevSet&) { return 0; }
+static int set_build_others(Ctx* c, uint64_t handle, KeySet& k) {
+  if (!(k.flags & BLSGPU_KEYSET_TABLES) || k.table) return 0;
+  int rc = keyset_build_tables(c, k);
+  if (rc) return rc;
+  if (k.table && k.lines && !keyset_lines_fit(k.n, keyset_table_bytes(k.group, k.n), (uint64_t)knobs().keyset_table_mb)) {
+    void *old = k.lines, *old_no = k.nolines;
+    k.lines = nullptr;
+    k.nolines = nullptr;
+    k.bytes = set_bytes(k);
+    set_publish(handle, k);
+    (void)hipFree(old);
+    (void)hipFree(old_no);
+  } else if (k.table) {
+    set_publish(handle, k);
+  }
+  return 0;
+}
+// the rows of a whole set whose entries are in G2, in chunks of 4,096 entries; leaves s.lines null (and the set without rows) when
+// the size rule (keyset_lines_fit: the 32-bit offset of the kernels that read them, and the cap of BLSGPU_KEYSET_TABLE_MB together
+// with a key set's fixed-base tables) or the device's memory says no
+template <class T>
+static int set_build_lines(Ctx* c, T& s) {
+  if (set_rows_group(s) != 2 || !keyset_lines_fit(s.n, set_other_bytes(s, s.n), (uint64_t)knobs().keyset_table_mb)) return 0;
   uint32_t *lines = nullptr, *scratch = nullptr;
   int32_t* nolines = nullptr;
-  if (hipMalloc((void**)&lines, lb) != hipSuccess || hipMalloc((void**)&scratch, chunk * (size_t)KEYSET_LINES_KEY_BYTES) != hipSuccess ||
-      hipMalloc((void**)&nolines, 4 * k.n) != hipSuccess) {
+  if (hipMalloc((void**)&lines, s.n * (size_t)KEYSET_LINES_KEY_BYTES) != hipSuccess || hipMalloc((void**)&scratch, set_lines_scratch_bytes(s.n)) != hipSuccess ||
+      hipMalloc((void**)&nolines, 4 * s.n) != hipSuccess) {
     (void)hipGetLastError();
     for (void* p : {(void*)lines, (void*)scratch, (void*)nolines})
       if (p) (void)hipFree(p);
     return 0;
   }
-  for (size_t k0 = 0; k0 < k.n; k0 += chunk) {
-    const size_t cnt = std::min(chunk, k.n - k0);
-    KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), k0, cnt, (const uint8_t*)k.aff, lines, scratch, nolines);
-  }
+  s.lines = lines;
+  s.nolines = nolines;
+  set_launch_lines(c, s, nullptr, 0, s.n, scratch);
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
   (void)hipFree(scratch);
   if (e1 != hipSuccess || e2 != hipSuccess) {
     (void)hipFree(lines);
     (void)hipFree(nolines);
+    s.lines = nullptr;
+    s.nolines = nullptr;
     return fail(BLSGPU_E_HIP, std::string("k_keyset_lines: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
   }
-  k.lines = lines;
-  k.nolines = nolines;
-  k.bytes += lb + 4 * (uint64_t)k.n;
+  s.bytes = set_bytes(s);
   return 0;
 }
+// An append, step 1: room for n1 entries in the arrays that hold a record per entry -- all of the new arrays before any of the old
+// ones goes, so that a refusal leaves the set as it was; the published record keeps n0 until the tail is written.
+template <class T>
+static int set_grow_base(Ctx* c, uint64_t handle, T& s, size_t n0, size_t n1) {
+  T g = s;
+  const std::vector<SetArray> arrays = set_arrays(g);
+  std::vector<void*> old(arrays.size(), nullptr);
+  for (size_t i = 0; i < arrays.size(); i++)
+    if (!set_grow(c, arrays[i].p, arrays[i].entry_bytes * n0, arrays[i].entry_bytes * n1, &old[i])) {
+      for (size_t j = 0; j < i; j++) (void)hipFree(*arrays[j].p);
+      return fail(BLSGPU_E_HIP, std::string("no device memory for the grown ") + set_name(s));
+    }
+  s = g;
+  set_publish(handle, s);
+  for (void* p : old) (void)hipFree(p);
+  return 0;
+}
+// step 2: rows by the creation rule on the final size: grown, or dropped (the set works without them)
+template <class T>
+static void set_grow_or_drop_lines(Ctx* c, uint64_t handle, T& s, size_t n0, size_t n1) {
+  if (!s.lines) return;
+  void *old = nullptr, *old_no = nullptr, *unused = nullptr;
+  bool keep = keyset_lines_fit(n1, set_other_bytes(s, n1), (uint64_t)knobs().keyset_table_mb) &&
+              set_grow(c, (void**)&s.lines, n0 * (size_t)KEYSET_LINES_KEY_BYTES, n1 * (size_t)KEYSET_LINES_KEY_BYTES, &old);
+  if (keep && !set_grow(c, (void**)&s.nolines, 4 * n0, 4 * n1, &old_no)) {
+    unused = s.lines;                         // the grown rows go with the old ones
+    s.lines = (uint32_t*)old;
+    keep = false;
+  }
+  if (!keep) {
+    old = s.lines;
+    old_no = s.nolines;
+    s.lines = nullptr;
+    s.nolines = nullptr;
+  }
+  s.bytes = set_bytes(s);
+  set_publish(handle, s);
+  for (void* p : {old, old_no, unused}) (void)hipFree(p);
+}
+// step 4, once the kind's apply has written the tail (the published record still said n0, so nothing named the new entries before
+// they were whole): the record says n1; then what the creator asked for and the set does not have (an empty set has nothing) is
+// built whole where creation would build it -- a key set's tables first, then the rows in what the cap leaves.  Every record
+// published on the way is a whole set.
+template <class T>
+static int set_finish_append(Ctx* c, uint64_t handle, T& s, size_t n1) {
+  s.n = n1;
+  s.bytes = set_bytes(s);
+  set_publish(handle, s);
+  int rc = set_build_others(c, handle, s);
+  if (rc) return rc;
+  if ((s.flags & set_rows_flag(s)) && !s.lines) {
+    if ((rc = set_build_lines(c, s))) return rc;
+    if (s.lines) set_publish(handle, s);
+  }
+  SYNC_FLUSH(c);
+  return 0;
+}
+// the position list of an update, on the host (copied down first when it lives on the device) and checked: in range, no two equal
+template <class T>
+static int set_read_checked_positions(const T& s, const uint32_t* pos, size_t count, std::vector<uint32_t>& h) {
+  h.resize(count);
+  if (is_device_ptr(pos)) HIPCK(hipMemcpy(h.data(), pos, 4 * count, hipMemcpyDeviceToHost));
+  else memcpy(h.data(), pos, 4 * count);
+  switch (keyset_positions_check(h.data(), count, s.n)) {
+    case KEYSET_POS_RANGE: return fail(BLSGPU_E_ARG, std::string("a position is outside the ") + set_name(s));
+    case KEYSET_POS_DUP: return fail(BLSGPU_E_ARG, "the same position twice in one update");
+  }
+  return 0;
+}
+}  // extern "C++"
 int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int flags, int32_t* status, uint64_t* out_handle) try {
   if (!initialised()) return NOT_INIT();
   int rc = keyset_fmt_check(sig_group, fmt);
@@ -5645,13 +5782,13 @@ int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int
   struct Guard {
     KeySet* k;
     ~Guard() {
-      if (k) keyset_free(*k);
+      if (k) set_free(*k);
     }
   } guard{&k};
   HIPCK(hipMalloc((void**)&k.aff, asz * m));
   HIPCK(hipMalloc((void**)&k.comp, csz * m));
   HIPCK(hipMalloc((void**)&k.status, 4 * m));
-  k.bytes = (asz + csz + 4) * (uint64_t)n;
+  k.bytes = set_bytes(k);
   if (n) {
     if ((rc = arena_reserve(c, pad256(isz * n) + pad256(osz * n) + 4096))) return rc;
     c->arena_off = 0;
@@ -5677,31 +5814,16 @@ int blsgpu_keyset_create(int sig_group, const void* keys, size_t n, int fmt, int
     HIPCK(hipGetLastError());
     if (status && (rc = copy_out(c, status, k.status, 4 * n))) return rc;
     if ((flags & BLSGPU_KEYSET_TABLES) && (rc = keyset_build_tables(c, k))) return rc;
-    if ((flags & BLSGPU_KEYSET_LINES) && (rc = keyset_build_lines(c, k))) return rc;
+    if ((flags & BLSGPU_KEYSET_LINES) && (rc = set_build_lines(c, k))) return rc;
     SYNC_FLUSH(c);
   }
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  const uint64_t id = g_keyset_next++;
-  g_keysets[id] = k;
+  *out_handle = set_issue(k);
   guard.k = nullptr;
-  *out_handle = id;
   return 0;
 }
 API_CATCH
 
-int blsgpu_keyset_destroy(uint64_t handle) try {
-  if (!initialised()) return NOT_INIT();
-  KeySet k;
-  {
-    std::lock_guard<std::mutex> lk(g_keyset_mu);
-    auto it = g_keysets.find(handle);
-    if (handle == 0 || it == g_keysets.end()) return fail(BLSGPU_E_ARG, "unknown key set handle (never issued, or destroyed)");
-    k = it->second;
-    g_keysets.erase(it);
-  }
-  keyset_free(k);
-  return 0;
-}
+int blsgpu_keyset_destroy(uint64_t handle) try { return set_destroy<KeySet>(handle); }
 API_CATCH
 
 // ---- blsgpu_keyset_update / blsgpu_keyset_append: `count` keys in `fmt` become the entries h_pos[0 .. count) of k (positions the
@@ -5716,18 +5838,12 @@ static int keyset_apply(Ctx* c, const KeySet& k, const uint32_t* h_pos, const vo
   int rc = arena_reserve(c, pad256(isz * count) + pad256(osz * count) + 2 * pad256(4 * count) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
-  struct Work {
-    void *jac = nullptr, *prod = nullptr, *scratch = nullptr;
-    ~Work() {
-      for (void* p : {jac, prod, scratch})
-        if (p) (void)hipFree(p);
-    }
-  } ws;
+  DevBuf jac, prod, scratch;
   if (k.table) {
-    HIPCK(hipMalloc(&ws.jac, chunk * (rec / 2 * 3)));
-    HIPCK(hipMalloc(&ws.prod, chunk * (rec / 2)));
+    HIPCK(hipMalloc(&jac.p, chunk * (rec / 2 * 3)));
+    HIPCK(hipMalloc(&prod.p, chunk * (rec / 2)));
   }
-  if (k.lines) HIPCK(hipMalloc(&ws.scratch, chunk * (size_t)KEYSET_LINES_KEY_BYTES));
+  if (k.lines) HIPCK(hipMalloc(&scratch.p, set_lines_scratch_bytes(count)));
   Carver mem{c};
   uint32_t* d_pos = mem.take<uint32_t>(4 * count);
   int32_t* d_st = mem.take<int32_t>(4 * count);
@@ -5757,28 +5873,19 @@ static int keyset_apply(Ctx* c, const KeySet& k, const uint32_t* h_pos, const vo
     if (k.table)
       with_group(k.group, [&](auto G) {
         KL(KID_KEYSET_BUILD_AT, k_keyset_build_at<G()>, dim3(blocks_for(cnt)), dim3(BLS_BLOCK), cnt, (const uint32_t*)d_pos + l0, (const uint8_t*)k.aff,
-           (uint8_t*)ws.jac, (uint8_t*)ws.prod, k.table);
+           (uint8_t*)jac.p, (uint8_t*)prod.p, k.table);
       });
-    if (k.lines)
-      KL(KID_KEYSET_LINES_AT, k_keyset_lines_at, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), cnt, (const uint32_t*)d_pos + l0, (const uint8_t*)k.aff, k.lines,
-         (uint32_t*)ws.scratch, k.nolines);
+    if (k.lines) set_launch_lines(c, k, d_pos + l0, 0, cnt, scratch.p);       // this chunk's rows, after its tables
   }
   HIPCK(hipGetLastError());
   if (status && (rc = copy_out(c, status, d_st, 4 * count))) return rc;
   SYNC_FLUSH(c);                      // before the workspaces go
   return 0;
 }
-// the position list of an update, on the host (copied down first when it lives on the device)
-static int keyset_read_positions(const uint32_t* pos, size_t count, std::vector<uint32_t>& h) {
-  h.resize(count);
-  if (is_device_ptr(pos)) HIPCK(hipMemcpy(h.data(), pos, 4 * count, hipMemcpyDeviceToHost));
-  else memcpy(h.data(), pos, 4 * count);
-  return 0;
-}
 
 int blsgpu_keyset_update(uint64_t handle, const uint32_t* pos, const void* keys, size_t count, int fmt, int32_t* status) try {
   KeySet k;
-  int rc = keyset_find(handle, k);
+  int rc = set_find(handle, k);
   if (rc) return rc;
   if ((rc = keyset_fmt_check(k.sig_group, fmt))) return rc;
   if (count == 0) return 0;
@@ -5786,40 +5893,14 @@ int blsgpu_keyset_update(uint64_t handle, const uint32_t* pos, const void* keys,
   if (count > k.n) return fail(BLSGPU_E_ARG, "more positions than the key set has entries");
   CTX_ACQUIRE_ON(c, k.devidx);
   std::vector<uint32_t> h_pos;
-  if ((rc = keyset_read_positions(pos, count, h_pos))) return rc;
-  switch (keyset_positions_check(h_pos.data(), count, k.n)) {
-    case KEYSET_POS_RANGE: return fail(BLSGPU_E_ARG, "a position is outside the key set");
-    case KEYSET_POS_DUP: return fail(BLSGPU_E_ARG, "the same position twice in one update");
-  }
+  if ((rc = set_read_checked_positions(k, pos, count, h_pos))) return rc;
   return keyset_apply(c, k, h_pos.data(), keys, count, fmt, status);
 }
 API_CATCH
 
-// One array of a growing set: `bytes_new` bytes with the first `bytes_old` copied from *p; *p is replaced and the old array left in
-// *old for the caller to free once no record names it.  false: the device has no room (or the copy failed) and *p is untouched.
-static bool keyset_grow(Ctx* c, void** p, size_t bytes_old, size_t bytes_new, void** old) {
-  void* q = nullptr;
-  if (hipMalloc(&q, std::max<size_t>(bytes_new, 1)) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (bytes_old && (hipMemcpyAsync(q, *p, bytes_old, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) {
-    (void)hipGetLastError();
-    (void)hipFree(q);
-    return false;
-  }
-  *old = *p;
-  *p = q;
-  return true;
-}
-static uint64_t keyset_bytes(const KeySet& k) {
-  const uint64_t base = point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE) + point_bytes(k.group, BLSGPU_FMT_COMPRESSED) + 4;
-  return base * k.n + (k.table ? keyset_table_bytes(k.group, k.n) : 0) + (k.lines ? k.n * (KEYSET_LINES_KEY_BYTES + 4) : 0);
-}
-
 int blsgpu_keyset_append(uint64_t handle, const void* keys, size_t count, int fmt, int32_t* status, uint64_t* out_first) try {
   KeySet k;
-  int rc = keyset_find(handle, k);
+  int rc = set_find(handle, k);
   if (rc) return rc;
   if ((rc = keyset_fmt_check(k.sig_group, fmt))) return rc;
   if (count && !keys) return fail(BLSGPU_E_ARG, "null argument");
@@ -5827,88 +5908,31 @@ int blsgpu_keyset_append(uint64_t handle, const void* keys, size_t count, int fm
   if (out_first) *out_first = k.n;
   if (count == 0) return 0;
   CTX_ACQUIRE_ON(c, k.devidx);
-  const size_t n0 = k.n, n1 = k.n + count, asz = point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE), csz = point_bytes(k.group, BLSGPU_FMT_COMPRESSED);
-  const uint64_t cap_mib = (uint64_t)knobs().keyset_table_mb;
-  // the three base arrays: all of the new ones before any of the old ones goes; the record keeps n0 until the tail is written
-  {
-    KeySet g = k;
-    void* old[3] = {nullptr, nullptr, nullptr};
-    if (!keyset_grow(c, (void**)&g.aff, asz * n0, asz * n1, &old[0]) || !keyset_grow(c, (void**)&g.comp, csz * n0, csz * n1, &old[1]) ||
-        !keyset_grow(c, (void**)&g.status, 4 * n0, 4 * n1, &old[2])) {
-      if (old[0]) (void)hipFree(g.aff);
-      if (old[1]) (void)hipFree(g.comp);
-      return fail(BLSGPU_E_HIP, "no device memory for the grown key set");
-    }
-    k = g;
-    keyset_publish(handle, k);
-    for (void* p : old) (void)hipFree(p);
-  }
-  // tables and lines by the creation rule on the final size: grown, or dropped (the set works without them)
-  if (k.table) {
+  const size_t n0 = k.n, n1 = k.n + count;
+  if ((rc = set_grow_base(c, handle, k, n0, n1))) return rc;
+  if (k.table) {  // the tables by the creation rule on the final size: grown, or dropped (the set works without them)
     void* old = nullptr;
     const size_t tb = keyset_table_bytes(k.group, n1);
-    if (tb > (size_t)cap_mib << 20 || !keyset_grow(c, (void**)&k.table, keyset_table_bytes(k.group, n0), tb, &old)) {
+    if (tb > (size_t)knobs().keyset_table_mb << 20 || !set_grow(c, (void**)&k.table, keyset_table_bytes(k.group, n0), tb, &old)) {
       old = k.table;
       k.table = nullptr;
     }
-    k.bytes = keyset_bytes(k);
-    keyset_publish(handle, k);
+    k.bytes = set_bytes(k);
+    set_publish(handle, k);
     (void)hipFree(old);
   }
-  if (k.lines) {
-    void *old = nullptr, *old_no = nullptr, *unused = nullptr;
-    bool keep = keyset_lines_fit(n1, k.table ? keyset_table_bytes(k.group, n1) : 0, cap_mib) &&
-                keyset_grow(c, (void**)&k.lines, n0 * (size_t)KEYSET_LINES_KEY_BYTES, n1 * (size_t)KEYSET_LINES_KEY_BYTES, &old);
-    if (keep && !keyset_grow(c, (void**)&k.nolines, 4 * n0, 4 * n1, &old_no)) {
-      unused = k.lines;                         // the grown rows go with the old ones
-      k.lines = (uint32_t*)old;
-      keep = false;
-    }
-    if (!keep) {
-      old = k.lines;
-      old_no = k.nolines;
-      k.lines = nullptr;
-      k.nolines = nullptr;
-    }
-    k.bytes = keyset_bytes(k);
-    keyset_publish(handle, k);
-    for (void* p : {old, old_no, unused}) (void)hipFree(p);
-  }
-  // the tail through the update path; the published record still says n0, so nothing names the new entries before they are whole
+  set_grow_or_drop_lines(c, handle, k, n0, n1);
+  // the tail through the update path
   std::vector<uint32_t> h_pos(count);
   for (size_t i = 0; i < count; i++) h_pos[i] = (uint32_t)(n0 + i);
   if ((rc = keyset_apply(c, k, h_pos.data(), keys, count, fmt, status))) return rc;
-  k.n = n1;
-  k.bytes = keyset_bytes(k);
-  keyset_publish(handle, k);
-  // what the creator asked for and the set does not have (an empty set has neither) is built whole where creation would build it:
-  // tables first, then the lines in what the cap leaves.  Every record published on the way is a whole set.
-  if ((k.flags & BLSGPU_KEYSET_TABLES) && !k.table) {
-    if ((rc = keyset_build_tables(c, k))) return rc;
-    if (k.table && k.lines && !keyset_lines_fit(n1, keyset_table_bytes(k.group, n1), cap_mib)) {
-      void *old = k.lines, *old_no = k.nolines;
-      k.lines = nullptr;
-      k.nolines = nullptr;
-      k.bytes = keyset_bytes(k);
-      keyset_publish(handle, k);
-      (void)hipFree(old);
-      (void)hipFree(old_no);
-    } else if (k.table) {
-      keyset_publish(handle, k);
-    }
-  }
-  if ((k.flags & BLSGPU_KEYSET_LINES) && !k.lines) {
-    if ((rc = keyset_build_lines(c, k))) return rc;
-    if (k.lines) keyset_publish(handle, k);
-  }
-  SYNC_FLUSH(c);
-  return 0;
+  return set_finish_append(c, handle, k, n1);
 }
 API_CATCH
 
 int blsgpu_keyset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_tables, uint64_t* device_bytes) try {
   KeySet k;
-  int rc = keyset_find(handle, k);
+  int rc = set_find(handle, k);
   if (rc) return rc;
   if (sig_group) *sig_group = k.sig_group;
   if (n) *n = k.n;
@@ -5974,7 +5998,7 @@ static int keyset_check_whole(Ctx* c, const KeySet& k, const void* idx, size_t n
 
 int blsgpu_keyset_get(uint64_t handle, const uint32_t* idx, size_t count, int fmt_out, void* out, int32_t* status) try {
   KeySet k;
-  int rc = keyset_find(handle, k);
+  int rc = set_find(handle, k);
   if (rc) return rc;
   if ((rc = keyset_fmt_check(k.sig_group, fmt_out))) return rc;
   if (count == 0) return 0;
@@ -6015,7 +6039,7 @@ API_CATCH
 
 int blsgpu_keyset_mul(uint64_t handle, const uint32_t* idx, const uint8_t* scalars, size_t count, void* out) try {
   KeySet k;
-  int rc = keyset_find(handle, k);
+  int rc = set_find(handle, k);
   if (rc) return rc;
   if (count == 0) return 0;
   if (!idx || !scalars || !out) return fail(BLSGPU_E_ARG, "null argument");
@@ -6049,7 +6073,7 @@ struct indexed_args : set_args {
 };
 static int indexed_begin(indexed_args& a, int scheme, uint64_t keyset, const uint32_t* idx, const uint64_t* key_offsets, size_t n_sets, const void* sigs,
                          const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) {
-  int rc = keyset_find(keyset, a.k);
+  int rc = set_find(keyset, a.k);
   if (rc) return rc;
   if ((rc = check_common(a.k.sig_group, scheme, fmt))) return rc;
   return set_args_read(a, idx, key_offsets, n_sets, sigs, msgs, msg_offsets, status);
@@ -6122,7 +6146,7 @@ API_CATCH
 
 int blsgpu_sum_indexed_batch(uint64_t keyset, const uint32_t* idx, const uint64_t* offsets, size_t n_sets, void* out) try {
   KeySet k;
-  int rc = keyset_find(keyset, k);
+  int rc = set_find(keyset, k);
   if (rc) return rc;
   std::vector<uint64_t> offs;
   rc = sum_args_read(offs, idx, offsets, n_sets, out);
@@ -6147,7 +6171,7 @@ API_CATCH
 int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
                                 size_t n, int fmt, int32_t* status) try {
   KeySet k;
-  int rc = keyset_find(keyset, k);
+  int rc = set_find(keyset, k);
   if (rc) return rc;
   const int sig_group = k.sig_group;
   if ((rc = check_common(sig_group, scheme, fmt))) return rc;
@@ -6251,7 +6275,7 @@ struct agg_keys_indexed {
 int blsgpu_aggregate_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const uint8_t* msgs, const uint64_t* msg_offsets,
                                           const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) try {
   KeySet k;
-  int rc = keyset_find(keyset, k);
+  int rc = set_find(keyset, k);
   if (rc) return rc;
   const int sig_group = k.sig_group;
   if ((rc = check_common(sig_group, scheme, fmt))) return rc;
@@ -6423,7 +6447,7 @@ API_CATCH
 int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
                                        const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
   KeySet k;
-  int rc = keyset_find(keyset, k);
+  int rc = set_find(keyset, k);
   if (rc) return rc;
   const int sig_group = k.sig_group;
   if ((rc = check_common(sig_group, scheme, fmt))) return rc;
@@ -6484,7 +6508,7 @@ API_CATCH
  * the export of the easy-part value (mode 0). */
 int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* idx, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
   KeySet k;
-  int rc = keyset_find(keyset, k);
+  int rc = set_find(keyset, k);
   if (rc) return rc;
   if (n == 0) return 0;
   if (!in || !idx || !status || mode < 0 || mode > 1 || n > 4096 || (mode == 0 && !out_f12) || is_device_ptr(in) || is_device_ptr(idx) || is_device_ptr(status) ||
@@ -6549,7 +6573,7 @@ int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, 
     return fail(BLSGPU_E_ARG, "unknown kernel or variant");
   KeySet k;
   if (keyed) {
-    int rc = keyset_find(keyset, k);
+    int rc = set_find(keyset, k);
     if (rc) return rc;
     if (!k.lines || k.sig_group != 1) return fail(BLSGPU_E_ARG, "the key set has no line tables");
   }
@@ -6682,38 +6706,6 @@ static int msgset_kind_check(int sig_group, int scheme) {
   return 0;
 }
 static size_t msgset_rec_bytes(const MsgSet& m) { return point_bytes(m.sig_group, BLSGPU_FMT_RAW_AFFINE); }
-static uint64_t msgset_bytes(const MsgSet& m) { return (uint64_t)msgset_rec_bytes(m) * m.n + (m.lines ? m.n * (uint64_t)(MSGSET_ENTRY_LINE_BYTES + 4) : 0); }
-// the rows of a whole set (Bls12381G2Impl), as keyset_build_lines builds a key set's: chunks of 4,096 entries; leaves m.lines null (and
-// the set without rows) when the size rule (keyset_lines_fit: the 32-bit offset of the kernels that read them, and the cap of
-// BLSGPU_KEYSET_TABLE_MB) or the device's memory says no
-static int msgset_build_lines(Ctx* c, MsgSet& m) {
-  if (m.sig_group != 2 || !keyset_lines_fit(m.n, 0, (uint64_t)knobs().keyset_table_mb)) return 0;
-  const size_t lb = m.n * (size_t)MSGSET_ENTRY_LINE_BYTES, chunk = std::min<size_t>(m.n, 4096);
-  uint32_t *lines = nullptr, *scratch = nullptr;
-  int32_t* nolines = nullptr;
-  if (hipMalloc((void**)&lines, lb) != hipSuccess || hipMalloc((void**)&scratch, chunk * (size_t)MSGSET_ENTRY_LINE_BYTES) != hipSuccess ||
-      hipMalloc((void**)&nolines, 4 * m.n) != hipSuccess) {
-    (void)hipGetLastError();
-    for (void* p : {(void*)lines, (void*)scratch, (void*)nolines})
-      if (p) (void)hipFree(p);
-    return 0;
-  }
-  for (size_t k0 = 0; k0 < m.n; k0 += chunk) {
-    const size_t cnt = std::min(chunk, m.n - k0);
-    KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), k0, cnt, (const uint8_t*)m.aff, lines, scratch, nolines);
-  }
-  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
-  (void)hipFree(scratch);
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    (void)hipFree(lines);
-    (void)hipFree(nolines);
-    return fail(BLSGPU_E_HIP, std::string("k_keyset_lines: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-  }
-  m.lines = lines;
-  m.nolines = nolines;
-  m.bytes = msgset_bytes(m);
-  return 0;
-}
 // `count` messages become the entries h_pos[0 .. count) of m (positions the caller has checked), or -- h_pos == nullptr -- the entries
 // [first, first + count): the hash under the set's DST (run_hash_group; Bls12381G1Impl: uncleared), k_msgset_seal, and for a set that
 // has rows k_keyset_lines[_at] on those entries alone, through a scratch that lives for this call only and is allocated before
@@ -6722,17 +6714,12 @@ static int msgset_apply(Ctx* c, const MsgSet& m, const uint32_t* h_pos, size_t f
   std::vector<uint64_t> moffs;
   int rc = read_offsets(msg_offsets, count, "msg_offsets", moffs);
   if (rc) return rc;
-  const size_t total = (size_t)moffs[count], hsz = point_bytes(m.sig_group, BLSGPU_FMT_RAW_PROJ), chunk = std::min<size_t>(count, 4096);
+  const size_t total = (size_t)moffs[count], hsz = point_bytes(m.sig_group, BLSGPU_FMT_RAW_PROJ);
   if (total && !msgs) return fail(BLSGPU_E_ARG, "null argument");
   if ((rc = arena_reserve(c, pad256(total) + pad256(8 * (count + 1)) + pad256(hsz * count) + pad256(768 * count) + pad256(4 * count) + 4096))) return rc;
   c->arena_off = 0;
-  struct Work {
-    void* scratch = nullptr;
-    ~Work() {
-      if (scratch) (void)hipFree(scratch);
-    }
-  } ws;
-  if (m.lines) HIPCK(hipMalloc(&ws.scratch, chunk * (size_t)MSGSET_ENTRY_LINE_BYTES));
+  DevBuf scratch;
+  if (m.lines) HIPCK(hipMalloc(&scratch.p, set_lines_scratch_bytes(count)));
   const void* d_msgs;
   const uint64_t* d_moffs;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
@@ -6750,16 +6737,7 @@ static int msgset_apply(Ctx* c, const MsgSet& m, const uint32_t* h_pos, size_t f
   with_group(m.sig_group, [&](auto G) {
     KL(KID_MSGSET_SEAL, k_msgset_seal<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_hash, (const uint32_t*)d_pos, first, m.aff);
   });
-  if (m.lines)
-    for (size_t l0 = 0; l0 < count; l0 += chunk) {
-      const size_t cnt = std::min(chunk, count - l0);
-      if (h_pos)
-        KL(KID_KEYSET_LINES_AT, k_keyset_lines_at, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), cnt, (const uint32_t*)d_pos + l0, (const uint8_t*)m.aff, m.lines,
-           (uint32_t*)ws.scratch, m.nolines);
-      else
-        KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), first + l0, cnt, (const uint8_t*)m.aff, m.lines, (uint32_t*)ws.scratch,
-           m.nolines);
-    }
+  if (m.lines) set_launch_lines(c, m, d_pos, first, count, scratch.p);
   if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
   SYNC_FLUSH(c);                      // before the scratch goes
   return 0;
@@ -6770,16 +6748,13 @@ static int msgset_create_begin(Ctx* c, MsgSet& m) {
   m.devidx = t_devidx;
   m.dev = c->dev;
   HIPCK(hipMalloc((void**)&m.aff, msgset_rec_bytes(m) * std::max<size_t>(m.n, 1)));
-  m.bytes = msgset_bytes(m);
+  m.bytes = set_bytes(m);
   return 0;
 }
 static int msgset_create_finish(Ctx* c, MsgSet& m, uint64_t* out_handle) {
   int rc;
-  if (m.n && (m.flags & BLSGPU_MSGSET_LINES) && (rc = msgset_build_lines(c, m))) return rc;
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  const uint64_t id = g_keyset_next++;
-  g_msgsets[id] = m;
-  *out_handle = id;
+  if (m.n && (m.flags & BLSGPU_MSGSET_LINES) && (rc = set_build_lines(c, m))) return rc;
+  *out_handle = set_issue(m);
   return 0;
 }
 int blsgpu_msgset_create(int sig_group, int scheme, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, int flags, uint64_t* out_handle) try {
@@ -6797,29 +6772,17 @@ int blsgpu_msgset_create(int sig_group, int scheme, const uint8_t* msgs, const u
   m.flags = flags;
   m.n = n;
   if ((rc = msgset_create_begin(c, m)) || (n && (rc = msgset_apply(c, m, nullptr, 0, msgs, msg_offsets, n))) || (rc = msgset_create_finish(c, m, out_handle)))
-    msgset_free(m);
+    set_free(m);
   return rc;
 }
 API_CATCH
 
-int blsgpu_msgset_destroy(uint64_t handle) try {
-  if (!initialised()) return NOT_INIT();
-  MsgSet m;
-  {
-    std::lock_guard<std::mutex> lk(g_keyset_mu);
-    auto it = g_msgsets.find(handle);
-    if (handle == 0 || it == g_msgsets.end()) return fail(BLSGPU_E_ARG, "unknown message set handle (never issued, or destroyed)");
-    m = it->second;
-    g_msgsets.erase(it);
-  }
-  msgset_free(m);
-  return 0;
-}
+int blsgpu_msgset_destroy(uint64_t handle) try { return set_destroy<MsgSet>(handle); }
 API_CATCH
 
 int blsgpu_msgset_info(uint64_t handle, int* sig_group, int* scheme, uint64_t* n, int* has_lines, uint64_t* device_bytes) try {
   MsgSet m;
-  int rc = msgset_find(handle, m);
+  int rc = set_find(handle, m);
   if (rc) return rc;
   if (sig_group) *sig_group = m.sig_group;
   if (scheme) *scheme = m.scheme;
@@ -6832,25 +6795,21 @@ API_CATCH
 
 int blsgpu_msgset_update(uint64_t handle, const uint32_t* pos, const uint8_t* msgs, const uint64_t* msg_offsets, size_t count) try {
   MsgSet m;
-  int rc = msgset_find(handle, m);
+  int rc = set_find(handle, m);
   if (rc) return rc;
   if (count == 0) return 0;
   if (!pos || !msg_offsets) return fail(BLSGPU_E_ARG, "null argument");
   if (count > m.n) return fail(BLSGPU_E_ARG, "more positions than the message set has entries");
   CTX_ACQUIRE_ON(c, m.devidx);
   std::vector<uint32_t> h_pos;
-  if ((rc = keyset_read_positions(pos, count, h_pos))) return rc;
-  switch (keyset_positions_check(h_pos.data(), count, m.n)) {
-    case KEYSET_POS_RANGE: return fail(BLSGPU_E_ARG, "a position is outside the message set");
-    case KEYSET_POS_DUP: return fail(BLSGPU_E_ARG, "the same position twice in one update");
-  }
+  if ((rc = set_read_checked_positions(m, pos, count, h_pos))) return rc;
   return msgset_apply(c, m, h_pos.data(), 0, msgs, msg_offsets, count);
 }
 API_CATCH
 
 int blsgpu_msgset_append(uint64_t handle, const uint8_t* msgs, const uint64_t* msg_offsets, size_t count, uint64_t* out_first) try {
   MsgSet m;
-  int rc = msgset_find(handle, m);
+  int rc = set_find(handle, m);
   if (rc) return rc;
   if (count && !msg_offsets) return fail(BLSGPU_E_ARG, "null argument");
   if (keyset_positions_check(nullptr, count, m.n) != KEYSET_POS_OK) return fail(BLSGPU_E_ARG, "more than 2^32 - 2 messages");
@@ -6862,43 +6821,11 @@ int blsgpu_msgset_append(uint64_t handle, const uint8_t* msgs, const uint64_t* m
     if ((rc = read_offsets(msg_offsets, count, "msg_offsets", moffs))) return rc;
     if (moffs[count] && !msgs) return fail(BLSGPU_E_ARG, "null argument");
   }
-  const size_t n0 = m.n, n1 = m.n + count, asz = msgset_rec_bytes(m);
-  {  // the records: the new array before the old one goes; the record keeps n0 until the tail is written
-    void* old = nullptr;
-    if (!keyset_grow(c, (void**)&m.aff, asz * n0, asz * n1, &old)) return fail(BLSGPU_E_HIP, "no device memory for the grown message set");
-    msgset_publish(handle, m);
-    (void)hipFree(old);
-  }
-  if (m.lines) {  // rows by the creation rule on the final size: grown, or dropped (the set works without them)
-    void *old = nullptr, *old_no = nullptr, *unused = nullptr;
-    bool keep = keyset_lines_fit(n1, 0, (uint64_t)knobs().keyset_table_mb) &&
-                keyset_grow(c, (void**)&m.lines, n0 * (size_t)MSGSET_ENTRY_LINE_BYTES, n1 * (size_t)MSGSET_ENTRY_LINE_BYTES, &old);
-    if (keep && !keyset_grow(c, (void**)&m.nolines, 4 * n0, 4 * n1, &old_no)) {
-      unused = m.lines;                         // the grown rows go with the old ones
-      m.lines = (uint32_t*)old;
-      keep = false;
-    }
-    if (!keep) {
-      old = m.lines;
-      old_no = m.nolines;
-      m.lines = nullptr;
-      m.nolines = nullptr;
-    }
-    m.bytes = msgset_bytes(m);
-    msgset_publish(handle, m);
-    for (void* p : {old, old_no, unused}) (void)hipFree(p);
-  }
+  const size_t n0 = m.n, n1 = m.n + count;
+  if ((rc = set_grow_base(c, handle, m, n0, n1))) return rc;
+  set_grow_or_drop_lines(c, handle, m, n0, n1);
   if ((rc = msgset_apply(c, m, nullptr, n0, msgs, msg_offsets, count))) return rc;
-  m.n = n1;
-  m.bytes = msgset_bytes(m);
-  msgset_publish(handle, m);
-  // rows the creator asked for and the set does not have (an empty set has none) are built whole where creation would build them
-  if ((m.flags & BLSGPU_MSGSET_LINES) && !m.lines) {
-    if ((rc = msgset_build_lines(c, m))) return rc;
-    if (m.lines) msgset_publish(handle, m);
-  }
-  SYNC_FLUSH(c);
-  return 0;
+  return set_finish_append(c, handle, m, n1);
 }
 API_CATCH
 
@@ -6920,10 +6847,10 @@ int blsgpu_debug_msgset_from_points(int sig_group, const void* points, size_t n,
   if ((rc = msgset_create_begin(c, m))) return rc;
   if (n && hipMemcpy(m.aff, points, msgset_rec_bytes(m) * n, hipMemcpyDefault) != hipSuccess) {
     (void)hipGetLastError();
-    msgset_free(m);
+    set_free(m);
     return fail(BLSGPU_E_HIP, "the copy of the points failed");
   }
-  if ((rc = msgset_create_finish(c, m, out_handle))) msgset_free(m);
+  if ((rc = msgset_create_finish(c, m, out_handle))) set_free(m);
   return rc;
 }
 API_CATCH
@@ -6935,11 +6862,11 @@ API_CATCH
 static int msgset_verify(uint64_t msgset, const uint32_t* msg_idx, bool indexed, uint64_t keyset, const uint32_t* idx, const void* pks, const void* sigs,
                          const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status) {
   MsgSet m;
-  int rc = msgset_find(msgset, m);
+  int rc = set_find(msgset, m);
   if (rc) return rc;
   KeySet k;
   if (indexed) {
-    if ((rc = keyset_find(keyset, k))) return rc;
+    if ((rc = set_find(keyset, k))) return rc;
     if (k.sig_group != m.sig_group) return fail(BLSGPU_E_ARG, "the key set belongs to the other orientation");
     if (k.dev != m.dev || k.devidx != m.devidx) return fail(BLSGPU_E_ARG, "the key set and the message set live on different devices");
   }
@@ -7237,11 +7164,11 @@ static int aggregate_msgset_run(Ctx* c, const MsgSet& m, const Keys& keys, const
 static int aggregate_msgset_entry(uint64_t msgset, const uint32_t* msg_idx, bool indexed, uint64_t keyset, const uint32_t* idx, const void* pks,
                                   const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) {
   MsgSet m;
-  int rc = msgset_find(msgset, m);
+  int rc = set_find(msgset, m);
   if (rc) return rc;
   KeySet k;
   if (indexed) {
-    if ((rc = keyset_find(keyset, k))) return rc;
+    if ((rc = set_find(keyset, k))) return rc;
     if (k.sig_group != m.sig_group) return fail(BLSGPU_E_ARG, "the key set belongs to the other orientation");
     if (k.dev != m.dev || k.devidx != m.devidx) return fail(BLSGPU_E_ARG, "the key set and the message set live on different devices");
   }
@@ -7280,7 +7207,7 @@ API_CATCH
  * export of the easy-part value (mode 0). */
 int blsgpu_debug_coop_pairing_rows(int mode, uint64_t msgset, const uint32_t* msg_of, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
   MsgSet m;
-  int rc = msgset_find(msgset, m);
+  int rc = set_find(msgset, m);
   if (rc) return rc;
   if (n == 0) return 0;
   if (!in || !msg_of || !status || mode < 0 || mode > 1 || n > 4096 || (mode == 0 && !out_f12) || is_device_ptr(in) || is_device_ptr(msg_of) ||
@@ -7332,42 +7259,9 @@ API_CATCH
 // =========================================================================================================
 // Registered signature sets (sigset.cuh): a table of round SIGNATURES that stays on the device, items named by positions in it
 static size_t sigset_rec_bytes(const SigSet& s) { return point_bytes(s.sig_group, BLSGPU_FMT_RAW_AFFINE); }
-static uint64_t sigset_bytes(const SigSet& s) {
-  return (uint64_t)(sigset_rec_bytes(s) + 1 + 4) * s.n + (s.lines ? s.n * (uint64_t)(SIGSET_ENTRY_LINE_BYTES + 4) : 0);
-}
 static int sigset_fmt_check(int fmt) {
   if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE && fmt != BLSGPU_FMT_COMPRESSED && fmt != BLSGPU_FMT_LEGACY)
     return fail(BLSGPU_E_ARG, "fmt must be one of the four BLSGPU_FMT_* point formats");
-  return 0;
-}
-// the rows of a whole set (Bls12381G2Impl), as msgset_build_lines builds a message set's: leaves s.lines null (and the set without
-// rows) when the size rule (keyset_lines_fit) or the device's memory says no
-static int sigset_build_lines(Ctx* c, SigSet& s) {
-  if (s.sig_group != 2 || !keyset_lines_fit(s.n, 0, (uint64_t)knobs().keyset_table_mb)) return 0;
-  const size_t lb = s.n * (size_t)SIGSET_ENTRY_LINE_BYTES, chunk = std::min<size_t>(s.n, 4096);
-  uint32_t *lines = nullptr, *scratch = nullptr;
-  int32_t* nolines = nullptr;
-  if (hipMalloc((void**)&lines, lb) != hipSuccess || hipMalloc((void**)&scratch, chunk * (size_t)SIGSET_ENTRY_LINE_BYTES) != hipSuccess ||
-      hipMalloc((void**)&nolines, 4 * s.n) != hipSuccess) {
-    (void)hipGetLastError();
-    for (void* p : {(void*)lines, (void*)scratch, (void*)nolines})
-      if (p) (void)hipFree(p);
-    return 0;
-  }
-  for (size_t k0 = 0; k0 < s.n; k0 += chunk) {
-    const size_t cnt = std::min(chunk, s.n - k0);
-    KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), k0, cnt, (const uint8_t*)s.aff, lines, scratch, nolines);
-  }
-  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
-  (void)hipFree(scratch);
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    (void)hipFree(lines);
-    (void)hipFree(nolines);
-    return fail(BLSGPU_E_HIP, std::string("k_keyset_lines: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-  }
-  s.lines = lines;
-  s.nolines = nolines;
-  s.bytes = sigset_bytes(s);
   return 0;
 }
 // `count` signatures become the entries [first, first + count) of s, whose arrays have room for them: k_decompress on the wire formats
@@ -7375,17 +7269,12 @@ static int sigset_build_lines(Ctx* c, SigSet& s) {
 // scratch that lives for this call only and is allocated before anything is written.  status (may be null): the new entries' statuses.
 static int sigset_apply(Ctx* c, const SigSet& s, size_t first, const void* sigs, const uint8_t* schemes, size_t count, int fmt, int32_t* status) {
   const bool wire = fmt == BLSGPU_FMT_COMPRESSED || fmt == BLSGPU_FMT_LEGACY;
-  const size_t sb = point_bytes(s.sig_group, fmt) * count, raw = point_bytes(s.sig_group, BLSGPU_FMT_RAW_PROJ) * count, chunk = std::min<size_t>(count, 4096);
+  const size_t sb = point_bytes(s.sig_group, fmt) * count, raw = point_bytes(s.sig_group, BLSGPU_FMT_RAW_PROJ) * count;
   int rc = arena_reserve(c, pad256(sb) + pad256(count) + (wire ? pad256(raw) + pad256(4 * count) : 0) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
-  struct Work {
-    void* scratch = nullptr;
-    ~Work() {
-      if (scratch) (void)hipFree(scratch);
-    }
-  } ws;
-  if (s.lines) HIPCK(hipMalloc(&ws.scratch, chunk * (size_t)SIGSET_ENTRY_LINE_BYTES));
+  DevBuf scratch;
+  if (s.lines) HIPCK(hipMalloc(&scratch.p, set_lines_scratch_bytes(count)));
   const void *d_sigs, *d_tags;
   if ((rc = stage_in(c, sigs, sb, &d_sigs))) return rc;
   if ((rc = stage_in(c, schemes, count, &d_tags))) return rc;
@@ -7406,11 +7295,7 @@ static int sigset_apply(Ctx* c, const SigSet& s, size_t first, const void* sigs,
     KL(KID_SIGSET_SEAL, k_sigset_seal<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_sigs, kfmt, (const int32_t*)d_dec, first, s.aff, s.status);
   });
   HIPCK(hipMemcpyAsync(s.tags + first, d_tags, count, hipMemcpyDeviceToDevice, c->stream));
-  if (s.lines)
-    for (size_t l0 = 0; l0 < count; l0 += chunk) {
-      const size_t cnt = std::min(chunk, count - l0);
-      KL(KID_KEYSET_LINES, k_keyset_lines, dim3(blocks_for(2 * cnt)), dim3(BLS_BLOCK), first + l0, cnt, (const uint8_t*)s.aff, s.lines, (uint32_t*)ws.scratch, s.nolines);
-    }
+  if (s.lines) set_launch_lines(c, s, nullptr, first, count, scratch.p);
   HIPCK(hipGetLastError());
   if (status && (rc = copy_out(c, status, s.status + first, 4 * count))) return rc;
   SYNC_FLUSH(c);                      // before the scratch goes
@@ -7437,40 +7322,25 @@ int blsgpu_sigset_create(int sig_group, const void* sigs, const uint8_t* schemes
   if (hipMalloc((void**)&s.aff, sigset_rec_bytes(s) * room) != hipSuccess || hipMalloc((void**)&s.tags, room) != hipSuccess ||
       hipMalloc((void**)&s.status, 4 * room) != hipSuccess) {
     (void)hipGetLastError();
-    sigset_free(s);
+    set_free(s);
     return fail(BLSGPU_E_HIP, "no device memory for the signature set");
   }
-  s.bytes = sigset_bytes(s);
-  if ((n && (rc = sigset_apply(c, s, 0, sigs, schemes, n, fmt, status))) || (n && (flags & BLSGPU_SIGSET_LINES) && (rc = sigset_build_lines(c, s)))) {
-    sigset_free(s);
+  s.bytes = set_bytes(s);
+  if ((n && (rc = sigset_apply(c, s, 0, sigs, schemes, n, fmt, status))) || (n && (flags & BLSGPU_SIGSET_LINES) && (rc = set_build_lines(c, s)))) {
+    set_free(s);
     return rc;
   }
-  std::lock_guard<std::mutex> lk(g_keyset_mu);
-  const uint64_t id = g_keyset_next++;
-  g_sigsets[id] = s;
-  *out_handle = id;
+  *out_handle = set_issue(s);
   return 0;
 }
 API_CATCH
 
-int blsgpu_sigset_destroy(uint64_t handle) try {
-  if (!initialised()) return NOT_INIT();
-  SigSet s;
-  {
-    std::lock_guard<std::mutex> lk(g_keyset_mu);
-    auto it = g_sigsets.find(handle);
-    if (handle == 0 || it == g_sigsets.end()) return fail(BLSGPU_E_ARG, "unknown signature set handle (never issued, or destroyed)");
-    s = it->second;
-    g_sigsets.erase(it);
-  }
-  sigset_free(s);
-  return 0;
-}
+int blsgpu_sigset_destroy(uint64_t handle) try { return set_destroy<SigSet>(handle); }
 API_CATCH
 
 int blsgpu_sigset_info(uint64_t handle, int* sig_group, uint64_t* n, int* has_lines, uint64_t* device_bytes) try {
   SigSet s;
-  int rc = sigset_find(handle, s);
+  int rc = set_find(handle, s);
   if (rc) return rc;
   if (sig_group) *sig_group = s.sig_group;
   if (n) *n = s.n;
@@ -7482,7 +7352,7 @@ API_CATCH
 
 int blsgpu_sigset_append(uint64_t handle, const void* sigs, const uint8_t* schemes, size_t count, int fmt, int32_t* status, uint64_t* out_first) try {
   SigSet s;
-  int rc = sigset_find(handle, s);
+  int rc = set_find(handle, s);
   if (rc) return rc;
   if ((rc = sigset_fmt_check(fmt))) return rc;
   if (count && (!sigs || !schemes)) return fail(BLSGPU_E_ARG, "null argument");
@@ -7490,52 +7360,11 @@ int blsgpu_sigset_append(uint64_t handle, const void* sigs, const uint8_t* schem
   if (out_first) *out_first = s.n;
   if (count == 0) return 0;
   CTX_ACQUIRE_ON(c, s.devidx);
-  const size_t n0 = s.n, n1 = s.n + count, asz = sigset_rec_bytes(s);
-  {  // the three arrays of the entries: all new ones before an old one goes, so that a refusal leaves the set as it was; the record keeps
-     // n0 until the tail is written
-    SigSet g = s;
-    void *old_a = nullptr, *old_t = nullptr, *old_s = nullptr;
-    const bool a = keyset_grow(c, (void**)&g.aff, asz * n0, asz * n1, &old_a), t = a && keyset_grow(c, (void**)&g.tags, n0, n1, &old_t),
-               u = t && keyset_grow(c, (void**)&g.status, 4 * n0, 4 * n1, &old_s);
-    if (!u) {
-      if (a) (void)hipFree(g.aff);
-      if (t) (void)hipFree(g.tags);
-      return fail(BLSGPU_E_HIP, "no device memory for the grown signature set");
-    }
-    s = g;
-    sigset_publish(handle, s);
-    for (void* p : {old_a, old_t, old_s}) (void)hipFree(p);
-  }
-  if (s.lines) {  // rows by the creation rule on the final size: grown, or dropped (the set works without them)
-    void *old = nullptr, *old_no = nullptr, *unused = nullptr;
-    bool keep = keyset_lines_fit(n1, 0, (uint64_t)knobs().keyset_table_mb) &&
-                keyset_grow(c, (void**)&s.lines, n0 * (size_t)SIGSET_ENTRY_LINE_BYTES, n1 * (size_t)SIGSET_ENTRY_LINE_BYTES, &old);
-    if (keep && !keyset_grow(c, (void**)&s.nolines, 4 * n0, 4 * n1, &old_no)) {
-      unused = s.lines;                         // the grown rows go with the old ones
-      s.lines = (uint32_t*)old;
-      keep = false;
-    }
-    if (!keep) {
-      old = s.lines;
-      old_no = s.nolines;
-      s.lines = nullptr;
-      s.nolines = nullptr;
-    }
-    s.bytes = sigset_bytes(s);
-    sigset_publish(handle, s);
-    for (void* p : {old, old_no, unused}) (void)hipFree(p);
-  }
+  const size_t n0 = s.n, n1 = s.n + count;
+  if ((rc = set_grow_base(c, handle, s, n0, n1))) return rc;
+  set_grow_or_drop_lines(c, handle, s, n0, n1);
   if ((rc = sigset_apply(c, s, n0, sigs, schemes, count, fmt, status))) return rc;
-  s.n = n1;
-  s.bytes = sigset_bytes(s);
-  sigset_publish(handle, s);
-  // rows the creator asked for and the set does not have (an empty set has none) are built whole where creation would build them
-  if ((s.flags & BLSGPU_SIGSET_LINES) && !s.lines) {
-    if ((rc = sigset_build_lines(c, s))) return rc;
-    if (s.lines) sigset_publish(handle, s);
-  }
-  SYNC_FLUSH(c);
-  return 0;
+  return set_finish_append(c, handle, s, n1);
 }
 API_CATCH
 
@@ -7547,7 +7376,7 @@ API_CATCH
 static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool ct, const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets,
                       const uint8_t* ct_schemes, size_t n, int fmt, uint8_t* out_gt, uint8_t* frames, uint64_t* pt_range, int32_t* status) {
   SigSet s;
-  int rc = sigset_find(sigset, s);
+  int rc = set_find(sigset, s);
   if (rc) return rc;
   if ((rc = sigset_fmt_check(fmt))) return rc;
   if (n == 0) return 0;

@@ -10,7 +10,8 @@ kernels being those of the call alone (blsgpu_profile_get).
   op 'sigset_pairing_device'  the same through TensorOps, every argument and result in device memory
   op 'sigset_open'    api.timecrypt_open_indexed_batch(set, items, fmt, with_status=True) -> (head, messages or None, statuses)
   op 'sigset_open_device'     the same through TensorOps -> (head, messages or None, statuses, ranges)
-  op 'handles'        the C entry points on a destroyed id, a key set's id and a message set's id -> the return codes"""
+  op 'handles'        the C entry points on a destroyed id, a key set's id and a message set's id, and every kind's destroy, info,
+                      update and append on the other two kinds' live ids -> the return codes"""
 import ctypes
 import os
 import pickle
@@ -75,6 +76,22 @@ def handles(api):
     # a key set's and a message set's own calls refuse a signature set's id
     s2 = api.SignatureSet.create(2, [g2], [0], api.FMT_RAW_AFFINE)
     rcs['as key set'] = [lib.blsgpu_keyset_destroy(s2.handle), lib.blsgpu_msgset_destroy(s2.handle)]
+    # every kind's destroy, info, update (where it exists) and append, with the live ids of the other two kinds; then the three sets
+    # are what they were
+    P = lambda x: ctypes.cast(x, ctypes.c_void_p)  # noqa: E731
+    pos, offs, first = (ctypes.c_uint32 * 1)(0), (ctypes.c_uint64 * 2)(0, 1), ctypes.c_uint64(0)
+    before = [ks.info(), ms.info(), s2.info()]
+    calls = {'key set': lambda h: [lib.blsgpu_keyset_destroy(h), lib.blsgpu_keyset_info(h, None, None, None, None),
+                                   lib.blsgpu_keyset_update(h, P(pos), api._ptr(bytes(96)), 1, api.FMT_RAW_AFFINE, None),
+                                   lib.blsgpu_keyset_append(h, api._ptr(bytes(96)), 1, api.FMT_RAW_AFFINE, None, ctypes.byref(first))],
+             'message set': lambda h: [lib.blsgpu_msgset_destroy(h), lib.blsgpu_msgset_info(h, None, None, None, None, None),
+                                       lib.blsgpu_msgset_update(h, P(pos), api._ptr(b'x'), P(offs), 1),
+                                       lib.blsgpu_msgset_append(h, api._ptr(b'x'), P(offs), 1, ctypes.byref(first))],
+             'signature set': lambda h: [lib.blsgpu_sigset_destroy(h), lib.blsgpu_sigset_info(h, None, None, None, None),
+                                         lib.blsgpu_sigset_append(h, api._ptr(g2), api._ptr(b'\0'), 1, api.FMT_RAW_AFFINE, None, ctypes.byref(first))]}
+    ids = {'key set': ks.handle, 'message set': ms.handle, 'signature set': s2.handle}
+    rcs['wrong kind'] = {(kind, other): calls[kind](h) for kind in calls for other, h in ids.items() if other != kind}
+    rcs['intact'] = [ks.info(), ms.info(), s2.info()] == before and [x['n'] for x in before] == [1, 1, 1]
     rcs['live'] = [lib.blsgpu_sigset_info(s2.handle, None, None, None, None), lib.blsgpu_sigset_destroy(s2.handle)]
     s2.handle = 0
     ks.close()

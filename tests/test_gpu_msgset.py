@@ -317,6 +317,56 @@ def test_case_list_on_the_other_paths_and_after_update_and_append(api, bo, tmp_p
         assert info2['device_bytes'] == info0['device_bytes'] + 96 * sg + (ENTRY_LINE_BYTES + 4 if sg == 2 else 0)
 
 
+def test_append_across_the_row_cap(api, tmp_path):
+    """BLSGPU_KEYSET_TABLE_MB=1 (and the one-wave path, which reads rows): an entry's rows are 15,232 bytes, so 68 entries' rows fit in
+    1,048,576 bytes and 69 entries' do not.  64 entries with rows; 4 appended: the rows grow; 1 more: the rows are dropped and the set
+    works without them.  After each step info equals that of a set created whole from the same list in the same process, and the
+    case list with its groups on the first, the last old, the first new and the last entry gives the oracle's statuses on both sets.
+    Entry p holds what entry (p + 3) mod 5 of the case list holds, which keeps the entry no group names off those four."""
+    sg, E = 2, len(mc.ENTRIES)
+    _, groups, expect = mc.batch(sg, ref.POP)
+    raw = mc.raw_groups(sg, groups, random.Random(5))
+    entries = [mc.ENTRIES[(p + 3) % E] for p in range(69)]
+    assert 68 * ENTRY_LINE_BYTES <= 1 << 20 < 69 * ENTRY_LINE_BYTES
+
+    def moved(n, named):
+        """the case list's groups over the first n entries: a group on entry e names one of `named` that holds e's message (the groups
+        of an entry taking turns), else the first such entry; the index past the end is n"""
+        out, turn = [], {}
+        for idx, pks, sigs in raw:
+            if idx == mc.PAST_END:
+                out.append((n, pks, sigs))
+            elif idx >= E:
+                out.append((idx, pks, sigs))
+            else:
+                at = [p for p in named if (p + 3) % E == idx] or [next(p for p in range(n) if (p + 3) % E == idx)]
+                out.append((at[turn.get(idx, 0) % len(at)], pks, sigs))
+                turn[idx] = turn.get(idx, 0) + 1
+        return out
+
+    steps_of = ((64, (0, 63)), (68, (0, 63, 64, 67)), (69, (0, 67, 68)))
+    for n, named in steps_of:
+        assert set(named) <= {idx for idx, pks, _ in moved(n, named) if pks}, (n, named)
+    msgsets = {'grown': {'sg': sg, 'scheme': ref.POP, 'msgs': entries[:64], 'lines': True}}
+    steps = []
+    for n, named in steps_of:
+        msgsets['whole_%d' % n] = {'sg': sg, 'scheme': ref.POP, 'msgs': entries[:n], 'lines': True}
+        if n > 64:
+            steps.append({'msgset': 'grown', 'append': entries[n - (4 if n == 68 else 1):n]})
+        for name in ('grown', 'whole_%d' % n):
+            steps += [{'msgset': name, 'info': True}, {'msgset': name, 'groups': moved(n, named)}]
+    got = run_worker(tmp_path, 'cap', dict(ONE_WAVE, BLSGPU_KEYSET_TABLE_MB='1'), msgsets, {}, steps)
+    assert got[4] == 64 and got[9] == 68
+    for (n, _), (i_g, v_g, i_w, v_w) in zip(steps_of, (got[0:4], got[5:9], got[10:14])):
+        assert i_g == i_w == dict(i_w, sig_group=2, scheme=ref.POP, n=n, has_lines=n <= 68), (n, i_g, i_w)
+        assert i_g['device_bytes'] == n * (192 + (ENTRY_LINE_BYTES + 4 if n <= 68 else 0))
+        for v in (v_g, v_w):
+            assert v['st'] == expect, n
+            nothing_hashed_nothing_built(v['launches'])
+            pl = pairing_launches(v['launches'])
+            assert (pl['k_pairing_coop_rows'], pl['k_pairing_coop']) == ((1, 0) if n <= 68 else (0, 1)), (n, pl)
+
+
 # ------------------------------------------------------------------ 4. default knobs, every size branch
 @pytest.mark.parametrize('n', [1, 3, 65])
 @pytest.mark.parametrize('sg', [1, 2])

@@ -23,13 +23,13 @@ IMPL_FMT = [(sg, fmt) for sg in (1, 2) for fmt in tc.FMTS]
 IMPL_FMT_IDS = ['sg%d-%s' % (sg, tc.FMT_IDS[fmt]) for sg, fmt in IMPL_FMT]
 
 
-def run_worker(tmp_path, name, calls, timeout=300):
+def run_worker(tmp_path, name, calls, timeout=300, env=None):
     """one attempt: a worker that dies by a signal or outlives its limit fails the test, and nothing further is started"""
     spec, out = str(tmp_path / (name + '.spec.pickle')), str(tmp_path / (name + '.out.pickle'))
     with open(spec, 'wb') as f:
         pickle.dump({'calls': calls}, f)
     keep = {k: v for k, v in os.environ.items() if not k.startswith('BLSGPU_') or k == 'BLSGPU_LIB'}
-    r = subprocess.run([sys.executable, os.path.join(util.ROOT, 'tests', 'sigset_worker.py'), spec, out], env=keep, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(util.ROOT, 'tests', 'sigset_worker.py'), spec, out], env=dict(keep, **(env or {})), capture_output=True, text=True,
                        timeout=timeout)
     assert r.returncode == 0, (name, r.returncode, r.stderr[-3000:])
     with open(out, 'rb') as f:
@@ -203,10 +203,64 @@ def test_append(tmp_path):
     assert st_new == [tc.OK] * 3 and split(blob_new, 3) == [want[k] for k in new_good] and plan(h_new, True)
 
 
+def test_append_onto_an_empty_set_builds_the_rows(tmp_path):
+    """a Bls12381G2Impl set created empty with lines=True has no rows; the first append builds them whole, as creation would: info
+    equals that of the set created from the same list, and a call over the new entries reads their rows"""
+    sg, fmt = 2, tc.RAW_AFFINE
+    entries, items, msgs, sts = sc.tiled(sg, fmt, 9)
+    sigs, tags = [b for b, _ in entries], [t for _, t in entries]
+    call = {'op': 'sigset_open', 'items': items, 'fmt': fmt}
+    (h_empty, m_empty, s_empty), (h_grown, m_grown, s_grown), (h_whole, m_whole, s_whole) = run_worker(tmp_path, 'empty', [
+        dict(call, set=the_set(sg, [], fmt, True)),
+        dict(call, set=the_set(sg, [], fmt, True, append=[(sigs, tags, fmt)])),
+        dict(call, set=the_set(sg, entries, fmt, True))])
+    assert h_empty['info'] == dict(h_empty['info'], n=0, has_lines=False) and s_empty == [sc.E_ARG] * 9 and m_empty == [None] * 9
+    assert h_grown['appended'] == [(0, [tc.OK] * len(entries))]
+    assert h_grown['info'] == h_whole['info'] == dict(h_whole['info'], sig_group=2, n=len(entries), has_lines=True)
+    assert s_grown == s_whole == sts and m_grown == m_whole == msgs and tc.OK in sts
+    assert plan(h_grown, True) and plan(h_whole, True)
+
+
+def test_append_across_the_row_cap(tmp_path):
+    """BLSGPU_KEYSET_TABLE_MB=1: an entry's rows are 15,232 bytes, so 68 entries' rows fit in 1,048,576 bytes and 69 entries' do not.
+    64 entries with rows; 4 appended: the rows grow; 1 more: the rows are dropped and the set works without them.  After each step
+    info equals that of a set created whole from the same list in the same process, and a call naming the first, the last old, the
+    first new and the last entry gives the list's messages and statuses, and the whole set's Gt bytes.  The entries are the list's,
+    repeated: entry p holds what entry p mod E of the list holds, so an item of the list that names p mod E may name p."""
+    sg, fmt = 2, tc.RAW_AFFINE
+    base, items, msgs, sts = sc.tiled(sg, fmt, 40)
+    E = len(base)
+    entries = [base[p % E] for p in range(69)]
+    assert 68 * 15232 <= 1 << 20 < 69 * 15232
+    at = lambda p: next(i for i, it in enumerate(items) if it[0] == p % E and sts[i] == tc.OK)  # noqa: E731
+    calls, want = [], []
+    for n, appends, named in ((64, (), (0, 63)), (68, (4,), (0, 63, 64, 67)), (69, (4, 1), (0, 67, 68))):
+        pick = [at(p) for p in named]
+        its = [(p,) + items[i][1:] for p, i in zip(named, pick)] + [(n,) + items[pick[0]][1:]]
+        app, k = [], 64
+        for c in appends:
+            app.append(([b for b, _ in entries[k:k + c]], [t for _, t in entries[k:k + c]], fmt))
+            k += c
+        for s in (the_set(sg, entries[:64], fmt, True, append=app), the_set(sg, entries[:n], fmt, True)):
+            calls.append({'op': 'sigset_open', 'items': its, 'fmt': fmt, 'set': s})
+            calls.append({'op': 'sigset_pairing', 'idx': [it[0] for it in its], 'points': [it[1] for it in its], 'fmt': fmt, 'set': s})
+        want.append((n, n <= 68, [msgs[i] for i in pick] + [None], [sts[i] for i in pick] + [sc.E_ARG], [(f, [tc.OK] * c) for f, c in zip((64, 68), appends)]))
+    got = run_worker(tmp_path, 'cap', calls, env={'BLSGPU_KEYSET_TABLE_MB': '1'})
+    for k, (n, rows, want_msgs, want_sts, appended) in enumerate(want):
+        (h_go, m_go, s_go), (h_gp, b_gp, s_gp), (h_wo, m_wo, s_wo), (h_wp, b_wp, s_wp) = got[4 * k:4 * k + 4]
+        assert h_go['appended'] == h_gp['appended'] == appended, n
+        assert h_go['info'] == h_gp['info'] == h_wo['info'] == h_wp['info'] == dict(h_wo['info'], sig_group=2, n=n, has_lines=rows), (n, h_go['info'], h_wo['info'])
+        assert s_go == s_wo == want_sts and m_go == m_wo == want_msgs, (n, s_go, s_wo)
+        assert s_gp == s_wp == want_sts and b_gp == b_wp and b_gp[-tr.GT_BYTES:] == tc.ZERO_GT and tc.ZERO_GT not in split(b_gp, len(want_sts))[:-1], (n, s_gp, s_wp)
+        for h in (h_go, h_gp, h_wo, h_wp):
+            assert plan(h, rows), (n, h['kernels'])
+
+
 # ------------------------------------------------------------------ handles
 def test_handles_and_a_u_of_the_wrong_width(tmp_path):
     """a destroyed id, a key set's id, a message set's id and 0 give BLSGPU_E_ARG at every entry point; a signature set's id is no key
-    set's or message set's.  Then a Bls12381G1Impl set under RAW_AFFINE with us that are 96-byte G1 records, two per 192-byte slot:
+    set's or message set's, and every kind's destroy, info, update and append refuse the live ids of the other two kinds and leave the
+    three sets as they were.  Then a Bls12381G1Impl set under RAW_AFFINE with us that are 96-byte G1 records, two per 192-byte slot:
     the indexed call reads the bytes the by-value call reads and answers as it does"""
     sg, fmt = 1, tc.RAW_AFFINE
     entries, est, items, msgs, sts, names = sc.render(sg, fmt, groups=sc.three_groups(sg))
@@ -221,4 +275,9 @@ def test_handles_and_a_u_of_the_wrong_width(tmp_path):
     for name in ('destroyed', 'key set', 'message set', 'zero'):
         assert rcs[name] == [-3] * 5, (name, rcs[name])
     assert rcs['as key set'] == [-3, -3] and rcs['live'] == [0, 0]
+    # destroy, info, update (key and message sets) and append of every kind on the live ids of the other two
+    assert sorted(rcs['wrong kind']) == sorted((a, b) for a in ('key set', 'message set', 'signature set') for b in ('key set', 'message set', 'signature set') if a != b)
+    for pair, codes in rcs['wrong kind'].items():
+        assert codes == [-3] * (3 if pair[0] == 'signature set' else 4), (pair, codes)
+    assert rcs['intact'] is True
     assert got[2][1:] == tuple(got[1]) and all(s != tc.OK for s in got[1][1])
