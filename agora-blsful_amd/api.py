@@ -42,7 +42,7 @@ EXPORTS = [
     'blsgpu_aggregate_partial', 'blsgpu_fp12_product_is_one', 'blsgpu_core_verify', 'blsgpu_deserialize', 'blsgpu_pop_verify_batch', 'blsgpu_aggregate_secure',
     'blsgpu_signcrypt_valid_batch', 'blsgpu_sig_proof_verify_batch', 'blsgpu_pairing2_check_batch',
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
-    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_wide_steps', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_map_to_curve', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
+    'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_wide_steps', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_finalexp_value', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_map_to_curve', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
     'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
@@ -173,6 +173,7 @@ def load_library(path=None):
         lib.blsgpu_debug_wide_program.argtypes = [vp, sz, ci, u8p, u8p]
         lib.blsgpu_debug_wide_steps.argtypes = [ci, vp, sz, ci, sz, vp, sz, vp, ctypes.c_int32, vp, sz, vp]
         lib.blsgpu_debug_finalexp_batch.argtypes = [vp, sz, ci, sz, i32p]
+        lib.blsgpu_debug_finalexp_value.argtypes = [vp, sz, sz, vp, vp]
         lib.blsgpu_debug_field_op_shape.argtypes = [ci] + [ctypes.POINTER(ctypes.c_int)] * 5
         lib.blsgpu_debug_field_op.argtypes = [ci, i32p, sz, ci, i32p]
         lib.blsgpu_debug_millerf.argtypes = [i32p, sz, i32p, i32p]
@@ -1421,6 +1422,17 @@ def debug_finalexp_batch(records, form, chunk=0, status=None):
     st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
     _check(lib.blsgpu_debug_finalexp_batch(_ptr(b''.join(records)), n, form, chunk, ctypes.cast(st, ctypes.c_void_p)))
     return list(st[:n])
+
+
+def debug_finalexp_value(records, chunk=0, flags=None):
+    """[576 bytes] per 576-byte Fp12 record: Gt::to_bytes() of its final exponentiation by k_finalexp2s_value, the lane-split kernel of
+    the pairing-value calls; flags[i] = 1 gives Gt one and any other non-zero flag 576 zero bytes, as those calls' special items get."""
+    lib = init()
+    n = len(records)
+    st = (ctypes.c_int32 * max(n, 1))(*(flags if flags is not None else [0] * n))
+    out = ctypes.create_string_buffer(576 * max(n, 1))
+    _check(lib.blsgpu_debug_finalexp_value(_ptr(b''.join(records)), n, chunk, ctypes.cast(out, ctypes.c_void_p), ctypes.cast(st, ctypes.c_void_p)))
+    return [out.raw[576 * i:576 * (i + 1)] for i in range(n)]
 
 
 _field_op_table = None

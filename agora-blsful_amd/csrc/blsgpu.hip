@@ -68,6 +68,7 @@ enum {
   KID_TIMECRYPT_PREP, KID_TIMECRYPT_OPEN,         // blsgpu_timecrypt_open_batch: statuses and pairs before the pairing, the time-lock tail after it
   KID_SIGSET_SEAL, KID_SIGSET_PREP,                // registered signature sets (sigset.cuh): create / append, the prepare kernel of both calls over a set
   KID_PAIRING_VALUE_ROWS,                          // the one-wave pairing value that reads a registered signature's rows (in the place of k_pairing_value)
+  KID_FINALEXP_VALUE, KID_MILLERF_ROWS1,           // pairing values on the lane-split kernels (run_pairing_values): the final exponentiation with the Gt export, the tabled accumulator
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -95,7 +96,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_pairing_value_prepare", "k_pairing_value",
                                     "k_timecrypt_prepare", "k_timecrypt_open",
                                     "k_sigset_seal", "k_sigset_prepare",
-                                    "k_pairing_value_rows"};
+                                    "k_pairing_value_rows",
+                                    "k_finalexp2s_value", "k_millerf_rows1"};
 
 struct Ctx {
   int dev = -1;
@@ -203,6 +205,10 @@ extern "C" char** environ;
 // group's walk is one serial pass however few groups there are, so it pays where the pass it saves runs more than once)
 #define SHARED_LINES_AUTO_MIN 4
 #define SHARED_LINES_AUTO_ITEMS 98304
+// blsgpu_pairing_batch, blsgpu_timecrypt_open_batch and the two calls over a signature set, BLSGPU_VALUE_SPLIT_MIN unset: from this
+// many items the pairing values run on the lane-split kernels (run_pairing_values).  DESIGN.md section 4, "Pairing values on the
+// lane-split kernels", has the measurement the figure follows from (tools/bench_value_split.py, profiles/value_split_bench.json).
+#define VALUE_SPLIT_MIN_DEFAULT 8192
 struct Knobs {
   long coop_max = 4096, wide_max = 512, shard_min = 8192, contexts = 2, fake_devices = 0, acc_lanes = 57344;
   long msm_c = 0, msm_ch = 0, msm2_c = 0, msm2_ch = 0, msm2_q = 0;          // 0: the library's own choice
@@ -216,6 +222,7 @@ struct Knobs {
   long multi_strip = 0;        // blsgpu_multi_verify_batch: keys per strip of the segmented key sum (0: one strip per lane of a single sum, at least 4)
   long keyset_table_mb = 4096; // blsgpu_keyset_create: fixed-base and line tables above this many MiB together are not built (the set works without them)
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
+  long value_split_min = VALUE_SPLIT_MIN_DEFAULT;   // the pairing-value calls: the smallest item count that takes the lane-split kernels (0: never); never changes a result
   long shared_lines_min = -1; // blsgpu_verify_shared_batch, Bls12381G2Impl: per-group line tables from this many items per group on average (0: never; unset: SHARED_LINES_AUTO_*)
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
@@ -239,6 +246,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_MULTI_STRIP", &Knobs::multi_strip, 0, 1L << 32, false},
     {"BLSGPU_KEYSET_TABLE_MB", &Knobs::keyset_table_mb, 0, 1L << 20, false},
     {"BLSGPU_SHARED_LINES_MIN", &Knobs::shared_lines_min, 0, 1L << 32, false},
+    {"BLSGPU_VALUE_SPLIT_MIN", &Knobs::value_split_min, 0, 1L << 32, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -4256,8 +4264,93 @@ API_CATCH
  * bytes, Gt::to_bytes() as include/blsgpu.h states the assumption.  All four point formats; a COMPRESSED / LEGACY pair that does not
  * decode gets its decode status (the G1 member's first) and 576 zero bytes; a pair with an identity member gets Gt one and BLSGPU_OK,
  * as multi_miller_loop skips it.  Launch sequence: k_decompress x 2 (wire formats only), k_pairing_value_prepare, then
- * k_pairing_value -- one wave per item (coop_miller1, coop_final_value, coop_gt_bytes) -- over chunks of at most 4,096 items. */
+ * run_pairing_values. */
 const size_t PAIRING_VALUE_CHUNK = 4096;
+// does a call of n items take the lane-split plan?  (BLSGPU_VALUE_SPLIT_MIN: the smallest such n, 0 = never; its callers size the
+// arena by the answer -- the plan needs an Fp12 workspace of WS_F_WORDS words per item)
+bool value_split_wanted(size_t n) {
+  const size_t from = (size_t)knobs().value_split_min;
+  return from != 0 && n >= from && miller_chunk_items() != 0;
+}
+// The lane-split plan of items [0, n), `chunk` items at a time (the caller has reserved the line workspace for a chunk): per chunk
+// the Miller value of every PV_RUN item into the Fp12 workspace d_f (stride n) -- d_pairs != nullptr; from the set's rows
+// (k_millerf_rows1) or, walked, k_linesp pass 1 on the one-pair workspace with the flags as its `bad` array and k_millerfp3 with one
+// item per accumulator --, then k_finalexp2s_value with the line workspace, now consumed, as its value store (as run_pairing2).
+// (k_linesp reads P at word 0 and Q at words W2, 2 W2 of its workspace: all inside WS_PAIR1_WORDS.  k_lines2s would not do: it also
+// loads P1 at word 3 W2.)  k_linesp4 is not used: it pays below a machine round of lane pairs, where the one-wave plan runs anyway.
+void launch_value_split(Ctx* c, size_t n, size_t chunk, const uint32_t* d_pairs, const int32_t* d_flag, uint8_t* d_out, uint32_t* d_f, const uint32_t* rows,
+                        const uint32_t* d_ent) {
+  for (size_t first = 0; first < n; first += chunk) {
+    const size_t cnt = std::min(chunk, n - first), nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
+    const dim3 grid((unsigned)(nlanes / BLS_BLOCK));
+    if (d_pairs && rows) {
+      KL(KID_MILLERF_ROWS1, k_millerf_rows1, grid, dim3(BLS_BLOCK), n, first, cnt, d_pairs, d_flag, rows, d_ent, d_f);
+    } else if (d_pairs) {
+      KL(KID_LINESP, k_linesp, grid, dim3(BLS_BLOCK), cnt, cnt, n, d_pairs + first, d_flag + first, c->lines_ws, c->lines_ws, lanes, (size_t)0, cnt, 1);
+      KL(KID_MILLERFP, k_millerfp3, grid, dim3(BLS_BLOCK), cnt, cnt, 1, d_flag + first, (const uint32_t*)c->lines_ws, lanes, d_f + first, n, (size_t)0);
+    }
+    KL(KID_FINALEXP_VALUE, k_finalexp2s_value, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_f, c->lines_ws, lanes, d_flag, d_out);
+  }
+}
+size_t value_split_ws_bytes(size_t chunk, bool walked) {
+  const size_t lanes = row_stride(lanes_for(chunk));
+  return std::max(walked ? (size_t)MILLER_ENTRIES * LINE3_WORDS_H * 4 * lanes : (size_t)0, (size_t)FX_STORE_WORDS * 4 * lanes);
+}
+// The pairing-value step of the four calls: the one-pair workspace d_pairs (stride n) and the flags d_flag (PV_*) -> d_out, 576 bytes
+// per item.  rows / d_ent (a Bls12381G2Impl signature set whose named entries all have rows): the G2 member of item i is entry
+// d_ent[i], its rows in `rows`; null: every pair is walked.  d_f: an Fp12 workspace of n items when value_split_wanted(n), else unused.
+// Below BLSGPU_VALUE_SPLIT_MIN items, or when the line workspace cannot be had (lines_reserve notes it once per process): one wave per
+// item, k_pairing_value_rows / k_pairing_value over chunks of at most 4,096 items.  From it up: launch_value_split in chunks of
+// miller_chunk_items().  Either plan writes the same bytes.  (Rows need the item's and the table's 32-bit offsets: a call of 2^30
+// items or a table of 2^32 bytes walks on the lane-split plan.)
+void run_pairing_values(Ctx* c, size_t n, const uint32_t* d_pairs, const int32_t* d_flag, uint8_t* d_out, uint32_t* d_f, const uint32_t* rows,
+                        const uint32_t* d_ent, size_t table_bytes) {
+  if (d_f && value_split_wanted(n)) {
+    const size_t chunk = std::min(n, miller_chunk_items());
+    const uint32_t* split_rows = rows && n < ((size_t)1 << 30) && table_bytes <= 0xffffffffull ? rows : nullptr;
+    if (lines_reserve(c, value_split_ws_bytes(chunk, !split_rows)) == 0) {
+      launch_value_split(c, n, chunk, d_pairs, d_flag, d_out, d_f, split_rows, d_ent);
+      return;
+    }
+  }
+  for (size_t first = 0; first < n; first += PAIRING_VALUE_CHUNK) {
+    const size_t count = std::min(PAIRING_VALUE_CHUNK, n - first);
+    if (rows) KL(KID_PAIRING_VALUE_ROWS, k_pairing_value_rows, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, d_pairs, d_flag, rows, d_ent, d_out);
+    else KL(KID_PAIRING_VALUE, k_pairing_value, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, d_pairs, d_flag, d_out);
+  }
+}
+
+/* Self-test hook of k_finalexp2s_value on caller-supplied Fp12 records (576 bytes each, the record format of
+ * blsgpu_fp12_product_is_one): k_f12_import, then the kernel chunk by chunk through launch_value_split with the line workspace as the
+ * value store, as the pairing-value calls run it.  chunk: items per chunk (0: the library's).  status[i] on entry is the item's flag:
+ * 0 runs the chain, 1 gives Gt one, anything else 576 zero bytes; it is not written.  out_gt: n x 576 bytes. */
+int blsgpu_debug_finalexp_value(const void* f12s, size_t n, size_t chunk, uint8_t* out_gt, const int32_t* status) try {
+  if (!initialised()) return NOT_INIT();
+  if (n == 0) return 0;
+  if (!f12s || !status || !out_gt) return fail(BLSGPU_E_ARG, "null argument");
+  CTX_ACQUIRE(c);
+  int rc = arena_reserve(c, pad256(576 * n) + pad256(4 * n) + pad256((size_t)GT_BYTES * n) + pad256((size_t)WS_F_WORDS * 4 * n) + 4096);
+  if (rc) return rc;
+  c->arena_off = 0;
+  const void *d_in, *d_st;
+  if ((rc = stage_in(c, f12s, 576 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  Carver mem{c};
+  uint8_t* d_out = mem.stage_out<uint8_t>(out_gt, (size_t)GT_BYTES * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  KL(KID_F12_IO, k_f12_import, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_in, d_f, n);
+  if (chunk == 0) chunk = miller_chunk_items() ? miller_chunk_items() : n;
+  if (chunk > n) chunk = n;
+  if (lines_reserve(c, value_split_ws_bytes(chunk, false))) return fail(BLSGPU_E_HIP, "no room for the value store");
+  launch_value_split(c, n, chunk, nullptr, (const int32_t*)d_st, d_out, d_f, nullptr, nullptr);
+  HIPCK(hipGetLastError());
+  if ((rc = stage_back(c, out_gt, d_out, (size_t)GT_BYTES * n))) return rc;
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
 int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, uint8_t* out_gt, int32_t* status) try {
   if (!initialised()) return NOT_INIT();
   if (fmt != BLSGPU_FMT_RAW_PROJ && fmt != BLSGPU_FMT_RAW_AFFINE && fmt != BLSGPU_FMT_COMPRESSED && fmt != BLSGPU_FMT_LEGACY)
@@ -4270,6 +4363,8 @@ int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, ui
   const size_t r1 = point_bytes(1, BLSGPU_FMT_RAW_PROJ) * n, r2 = point_bytes(2, BLSGPU_FMT_RAW_PROJ) * n;
   size_t need = pad256(b1) + pad256(b2) + pad256((size_t)GT_BYTES * n) + 2 * pad256(4 * n) + pad256((size_t)WS_PAIR1_WORDS * 4 * n) + 4096;
   if (wire) need += pad256(r1) + pad256(r2);
+  const bool split = value_split_wanted(n);
+  if (split) need += pad256((size_t)WS_F_WORDS * 4 * n);
   int rc = arena_reserve(c, need);
   if (rc) return rc;
   c->arena_off = 0;
@@ -4283,6 +4378,7 @@ int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, ui
   uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIR1_WORDS * 4 * n);
   uint8_t* d_r1 = wire ? mem.take<uint8_t>(r1) : nullptr;
   uint8_t* d_r2 = wire ? mem.take<uint8_t>(r2) : nullptr;
+  uint32_t* d_f = split ? mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n) : nullptr;
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   int kfmt = fmt;
   if (wire) {
@@ -4298,10 +4394,7 @@ int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, ui
   }
   KL(KID_PAIRING_VALUE_PREP, k_pairing_value_prepare, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d1, (const uint8_t*)d2, kfmt,
      wire ? (const int32_t*)d_status : (const int32_t*)nullptr, d_pairs, d_flag);
-  for (size_t first = 0; first < n; first += PAIRING_VALUE_CHUNK) {
-    const size_t count = std::min(PAIRING_VALUE_CHUNK, n - first);
-    KL(KID_PAIRING_VALUE, k_pairing_value, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, d_out);
-  }
+  run_pairing_values(c, n, d_pairs, d_flag, d_out, d_f, nullptr, nullptr, 0);
   HIPCK(hipGetLastError());
   if ((rc = stage_back(c, out_gt, d_out, (size_t)GT_BYTES * n))) return rc;
   if ((rc = stage_back(c, status, d_status, 4 * n))) return rc;
@@ -4313,8 +4406,8 @@ API_CATCH
 /* TimeCryptCiphertext::decrypt(sig) for many ciphertexts grouped under one signature each (reference src/time_crypt_ciphertext.rs:38-50
  * -> BlsTimeCrypt::unseal, src/traits/time_crypt.rs:76-116); include/blsgpu.h has the contract.  Launch sequence: k_decompress x 2
  * (wire formats only: the u of every item, the signature of every group), k_timecrypt_prepare (statuses up to the identity checks,
- * the pair of every item that passes them), k_pairing_value over chunks of at most 4,096 items (K = e(sig, u) as 576 bytes per item,
- * in the arena), k_timecrypt_open (SHA-256, SHAKE128, the frame, the scalar and g r == u, one item per lane). */
+ * the pair of every item that passes them), run_pairing_values (K = e(sig, u) as 576 bytes per item, in the arena: one wave per
+ * item below BLSGPU_VALUE_SPLIT_MIN items, the lane-split kernels from it up), k_timecrypt_open (SHA-256, SHAKE128, the frame, the scalar and g r == u, one item per lane). */
 int blsgpu_timecrypt_open_batch(int sig_group, const void* sigs, const uint8_t* sig_schemes, const uint64_t* item_offsets, size_t n_groups, const void* us,
                                 const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets, const uint8_t* ct_schemes, int fmt, uint8_t* frames,
                                 uint64_t* pt_range, int32_t* status) try {
@@ -4342,6 +4435,8 @@ int blsgpu_timecrypt_open_batch(int sig_group, const void* sigs, const uint8_t* 
   size_t need = pad256(ub) + pad256(sb) + pad256(n_groups) + pad256(8 * (n_groups + 1)) + pad256(32 * n) + 2 * pad256(total) + pad256(8 * (n + 1)) + pad256(n) +
                 pad256(16 * n) + 2 * pad256(4 * n) + pad256((size_t)WS_PAIR1_WORDS * 4 * n) + pad256((size_t)GT_BYTES * n) + 8192;
   if (wire) need += pad256(u_raw) + pad256(s_raw) + pad256(4 * n) + pad256(4 * n_groups);
+  const bool split = value_split_wanted(n);
+  if (split) need += pad256((size_t)WS_F_WORDS * 4 * n);
   if ((rc = arena_reserve(c, need))) return rc;
   c->arena_off = 0;
   const void *d_sigs, *d_ss, *d_us, *d_vs, *d_ws, *d_cs;
@@ -4365,6 +4460,7 @@ int blsgpu_timecrypt_open_batch(int sig_group, const void* sigs, const uint8_t* 
   uint8_t* d_s_raw = wire ? mem.take<uint8_t>(s_raw) : nullptr;
   int32_t* d_dec_u = wire ? mem.take<int32_t>(4 * n) : nullptr;
   int32_t* d_dec_s = wire ? mem.take<int32_t>(4 * n_groups) : nullptr;
+  uint32_t* d_f = split ? mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n) : nullptr;
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   if (total && d_frames != frames) HIPCK(hipMemsetAsync(d_frames, 0, total, c->stream));   // an item that is not opened hands back zeros, not arena bytes
   int kfmt = fmt;
@@ -4382,10 +4478,7 @@ int blsgpu_timecrypt_open_batch(int sig_group, const void* sigs, const uint8_t* 
     KL(KID_TIMECRYPT_PREP, k_timecrypt_prepare<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, (const uint8_t*)d_us, (const uint8_t*)d_sigs, kfmt,
        (const uint8_t*)d_ss, (const uint8_t*)d_cs, (const int32_t*)d_dec_u, (const int32_t*)d_dec_s, d_pairs, d_flag, d_status);
   });
-  for (size_t first = 0; first < n; first += PAIRING_VALUE_CHUNK) {
-    const size_t count = std::min(PAIRING_VALUE_CHUNK, n - first);
-    KL(KID_PAIRING_VALUE, k_pairing_value, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, d_gt);
-  }
+  run_pairing_values(c, n, d_pairs, d_flag, d_gt, d_f, nullptr, nullptr, 0);
   with_group(sig_group, [&](auto G) {
     KL(KID_TIMECRYPT_OPEN, k_timecrypt_open<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_gt, (const uint8_t*)d_us, kfmt, (const uint8_t*)d_vs,
        (const uint8_t*)d_ws, d_woffs, d_frames, d_range, d_status);
@@ -7370,9 +7463,8 @@ API_CATCH
 
 // ---- the two calls over a signature set.  Launch sequence: k_decompress of the callers' points (wire formats only), k_sigset_prepare
 // (index check, statuses up to the identity checks, the pair made affine, the item's entry, and one word back to the host where the
-// plan may read rows: whether any named entry lacks usable rows), the pairing over chunks of at most 4,096 items -- k_pairing_value_rows
-// for a Bls12381G2Impl set whose named entries all have rows, else k_pairing_value as it is --, and for the opening call
-// k_timecrypt_open unchanged.  ct == false: blsgpu_pairing_sigset_batch.
+// plan may read rows: whether any named entry lacks usable rows), run_pairing_values -- with the rows of a Bls12381G2Impl set whose
+// named entries all have them, else walked --, and for the opening call k_timecrypt_open unchanged.  ct == false: blsgpu_pairing_sigset_batch.
 static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool ct, const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets,
                       const uint8_t* ct_schemes, size_t n, int fmt, uint8_t* out_gt, uint8_t* frames, uint64_t* pt_range, int32_t* status) {
   SigSet s;
@@ -7401,6 +7493,8 @@ static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool
   size_t need = pad256(4 * n) + pad256(ub) + 4 * pad256(4 * n) + pad256((size_t)WS_PAIR1_WORDS * 4 * n) + pad256((size_t)GT_BYTES * n) + 512 + 8192;
   if (ct) need += pad256(32 * n) + 2 * pad256(total) + pad256(8 * (n + 1)) + pad256(n) + pad256(16 * n);
   if (wire) need += pad256(u_raw) + pad256(4 * n);
+  const bool split = value_split_wanted(n);
+  if (split) need += pad256((size_t)WS_F_WORDS * 4 * n);
   if ((rc = arena_reserve(c, need))) return rc;
   c->arena_off = 0;
   const void *d_idx, *d_us, *d_vs = nullptr, *d_ws = nullptr, *d_cs = nullptr;
@@ -7428,6 +7522,7 @@ static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool
   uint32_t* d_walk = mem.take<uint32_t>(4);
   uint8_t* d_u_raw = wire ? mem.take<uint8_t>(u_raw) : nullptr;
   int32_t* d_dec_u = wire ? mem.take<int32_t>(4 * n) : nullptr;
+  uint32_t* d_f = split ? mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n) : nullptr;
   if (!mem.ok) return drain(fail(BLSGPU_E_HIP, "internal: arena too small"));
   if (ct && total && d_frames != frames && hipMemsetAsync(d_frames, 0, total, c->stream) != hipSuccess)   // an item that is not opened hands back zeros
     return drain(fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
@@ -7454,14 +7549,7 @@ static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool
       return drain(fail(BLSGPU_E_HIP, "k_sigset_prepare failed"));
     rows = *h_walk == 0 ? s.lines : nullptr;
   }
-  for (size_t first = 0; first < n; first += PAIRING_VALUE_CHUNK) {
-    const size_t count = std::min(PAIRING_VALUE_CHUNK, n - first);
-    if (rows)
-      KL(KID_PAIRING_VALUE_ROWS, k_pairing_value_rows, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, rows,
-         (const uint32_t*)d_ent, d_gt);
-    else
-      KL(KID_PAIRING_VALUE, k_pairing_value, dim3((unsigned)count), dim3(BLS_BLOCK), n, first, count, (const uint32_t*)d_pairs, (const int32_t*)d_flag, d_gt);
-  }
+  run_pairing_values(c, n, d_pairs, d_flag, d_gt, d_f, rows, d_ent, (size_t)s.n * SIGSET_ENTRY_LINE_BYTES);
   if (!ct) {
     if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a pairing-value kernel failed to launch"));
     if ((rc = stage_back(c, out_gt, d_gt, (size_t)GT_BYTES * n))) return drain(rc);

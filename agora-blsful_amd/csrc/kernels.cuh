@@ -1212,7 +1212,8 @@ template __global__ void k_prepare_proof<2>(size_t, const uint8_t*, const uint8_
 #endif
 #endif  // BLS_TU_SIGN*
 
-#if defined(BLS_TU_MILLERS) || defined(BLS_TU_FINALEXPS) || defined(BLS_TU_LINES) || defined(BLS_TU_MILLERF) || defined(BLS_TU_FINALEXP2) || defined(BLS_TU_CYCRUN4)
+#if defined(BLS_TU_MILLERS) || defined(BLS_TU_FINALEXPS) || defined(BLS_TU_LINES) || defined(BLS_TU_MILLERF) || defined(BLS_TU_FINALEXP2) || defined(BLS_TU_CYCRUN4) || \
+    defined(BLS_TU_FINALEXP2_VALUE) || defined(BLS_TU_MILLERF_ROWS1)
 // =====================================================================================================
 // lane-split variants (tower_split.cuh): two adjacent lanes per item, 64-thread workgroups = 32 items
 #include "tower_split.cuh"
@@ -2235,7 +2236,7 @@ k_f12_fold4(size_t qin, size_t qout, int fan, const uint32_t* fin, size_t sin, s
 }
 #endif
 
-#if defined(BLS_TU_FINALEXP2)
+#if defined(BLS_TU_FINALEXP2) || defined(BLS_TU_FINALEXP2_VALUE)   // (the second: the same operations under k_finalexp2s_value, tu_finalexp2_value.hip)
 // =====================================================================================================
 // Round 3: the final exponentiation of the lane-split batch path as a sequence of operations on ONE accumulator A in LDS
 // (tower_split.cuh layout: 78 packed words per lane) and a per-lane VALUE STORE in HBM for everything else -- the inputs, the
@@ -2553,6 +2554,8 @@ static __device__ __noinline__ int fx_eq_conj(lds_u32* sh, uint32_t* vp, size_t 
   }
   return eq && !zero ? BLS_OK : BLS_ERR_INVALID_SIGNATURE;
 }
+#endif
+#if defined(BLS_TU_FINALEXP2)
 // items [first, first + count) of the Fp12 workspace fws (stride n, as k_millerf2s / k_miller2s leave it)
 __global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES) __attribute__((disable_tail_calls))
 k_finalexp2s(size_t n, size_t first, size_t count, const uint32_t* fws, uint32_t* vp, size_t lanes, int32_t* status) {

@@ -45,4 +45,11 @@ __global__ void k_sigset_prepare(size_t n, const uint32_t* idx, uint64_t n_entri
 // table and gets k_pairing_value's constants.
 __global__ void k_pairing_value_rows(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* flag, const uint32_t* table,
                                      const uint32_t* ent, uint8_t* out_gt);
+// The Miller loop of the same tabled pair on the lane-split kernels (tu_millerf_rows1.hip), two lanes per item: items
+// [first, first + count) of a batch of n, item i's line of entry e being n0 + (c xP) w^2 + (yP, 0) w^3 with (n0, c) row e of set entry
+// ent[i], read at the same 32-bit word offset from a wave-uniform base.  Nothing is walked and nothing passes through the line
+// workspace; conj(f) goes to item i of the Fp12 workspace fws (stride n), as k_millerfp3 leaves it.  An item whose flag is not PV_RUN
+// returns before any table read.
+__global__ void k_millerf_rows1(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* flag, const uint32_t* table, const uint32_t* ent,
+                                uint32_t* fws);
 #endif

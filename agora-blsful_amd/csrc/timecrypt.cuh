@@ -3,11 +3,36 @@
 //   * coop_miller1: the Miller loop of ONE walked pair into S.f -- coop_miller2's rounds with the second owner and the second line
 //     multiplication dropped;
 //   * coop_final_value (coop.cuh): coop_final_verdict without the comparison, the value in S.t;
-//   * coop_gt_bytes: the 576 bytes of Gt::to_bytes() as this library ASSUMES them (include/blsgpu.h) -- the ONE device function that
-//     knows the byte order.
+//   * coop_gt_bytes: the 576 bytes of Gt::to_bytes() as this library ASSUMES them (include/blsgpu.h), placed by gt_part_offset --
+//     the one place that knows the byte order, which the lane-split export (k_finalexp2s_value) shares.
 // Device code; tests/hostsim_timecrypt compiles the same functions on the host (one thread per lane pair) under the bound tracker.
 #pragma once
+#include "fp.cuh"
 #define GT_BYTES 576
+
+// ---- Gt::to_bytes(), 576 bytes, AS THIS LIBRARY ASSUMES IT (include/blsgpu.h, DESIGN.md section 7): the six Fp2 coefficients over
+// w^0..w^5 -- in tower terms c0.a0, c1.a0, c0.a1, c1.a1, c0.a2, c1.a2, the order of coop_f12 --, each its real part, then its
+// imaginary part, each part 48 bytes big-endian of the canonical residue (not Montgomery).  No reference vector pins this order; if
+// it turns out wrong, the fix is a permutation in the two functions below and in tests/timecrypt_ref.py gt_bytes.  They are the ONE
+// place on the device that knows the order: both exports -- coop_gt_bytes on the one-wave engine, whose coop_f12 holds the
+// coefficients by w-power, and fx_export of k_finalexp2s_value on the lane-split kernels, whose accumulator is in tower order --
+// place every part through them.
+//   gt_part_offset(k, imag): where the real (imag = false) or imaginary part of the coefficient over w^k starts;
+//   gt_tower_wpow(j): the w-power of tower slot j (0..5: c0.a0, c0.a1, c0.a2, c1.a0, c1.a1, c1.a2), since w^2 = v.
+BLS_FN int gt_part_offset(int k, bool imag) { return 96 * k + (imag ? 48 : 0); }
+BLS_FN int gt_tower_wpow(int j) { return j < 3 ? 2 * j : 2 * (j - 3) + 1; }
+// One Fp part: the canonical integer (fp_from_mont) as twelve byte-swapped 32-bit words, assembled in registers.
+BLS_FN void coop_gt_put(uint8_t* dst, const fp& a) {
+  fp t;
+  uint32_t ww[12];
+  fp_from_mont(t, a);
+  fp_get_words(ww, t);
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    const uint32_t w = __builtin_bswap32(ww[11 - i]);
+    __builtin_memcpy(dst + 4 * i, &w, 4);           // dst may be any caller address: no alignment is assumed
+  }
+}
 
 // the engine part: the translation unit of the kernels (BLS_TU_TIMECRYPT, after kernels.cuh) and the host harness
 #if defined(BLS_TU_TIMECRYPT) || !defined(__HIPCC__)
@@ -133,22 +158,6 @@ __device__ __noinline__ void coop_miller1(coop_shared& S, const g1_aff& P, const
   coop_conj(S.f, S.f);
 }
 
-// ---- Gt::to_bytes(), 576 bytes, AS THIS LIBRARY ASSUMES IT (include/blsgpu.h, DESIGN.md section 7): the six Fp2 coefficients over
-// w^0..w^5 -- in tower terms c0.a0, c1.a0, c0.a1, c1.a1, c0.a2, c1.a2, the order of coop_f12 --, each its real part, then its
-// imaginary part, each part 48 bytes big-endian of the canonical residue (not Montgomery).  No reference vector pins this order; if
-// it turns out wrong, the fix is a permutation here and in tests/timecrypt_ref.py gt_bytes.
-// One Fp part: the canonical integer (fp_from_mont) as twelve byte-swapped 32-bit words, assembled in registers.
-__device__ __forceinline__ void coop_gt_put(uint8_t* dst, const fp& a) {
-  fp t;
-  uint32_t ww[12];
-  fp_from_mont(t, a);
-  fp_get_words(ww, t);
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    const uint32_t w = __builtin_bswap32(ww[11 - i]);
-    __builtin_memcpy(dst + 4 * i, &w, 4);           // dst may be any caller address: no alignment is assumed
-  }
-}
 // the value a (reduced coefficients, as every coop_* function leaves them) -> out[0, 576): lane pair k < 6 writes coefficient k, the
 // even lane its real part and the odd lane its imaginary part, 48 bytes each
 __device__ __forceinline__ void coop_gt_bytes(uint8_t* out, const coop_f12& a) {
@@ -157,10 +166,10 @@ __device__ __forceinline__ void coop_gt_bytes(uint8_t* out, const coop_f12& a) {
     hfp2 x;
     coop_ld(x, a.c[k]);
 #if defined(__HIPCC__)
-    coop_gt_put(out + 96 * k + (lane_hi() ? 48 : 0), x.v);
+    coop_gt_put(out + gt_part_offset(k, lane_hi()), x.v);
 #else
-    coop_gt_put(out + 96 * k, x.c[0]);
-    coop_gt_put(out + 96 * k + 48, x.c[1]);
+    coop_gt_put(out + gt_part_offset(k, false), x.c[0]);
+    coop_gt_put(out + gt_part_offset(k, true), x.c[1]);
 #endif
   }
 }
@@ -249,6 +258,11 @@ BLS_FN bool timecrypt_check(const aff<F>& g, const uint32_t* r, const jac<F>& u)
 __global__ void k_pairing_value_prepare(size_t n, const uint8_t* g1s, const uint8_t* g2s, int fmt, const int32_t* status, uint32_t* pairs, int32_t* flag);
 // items first .. first + count - 1, one wave each: coop_miller1, coop_final_value, coop_gt_bytes -> out_gt[576 i ..)
 __global__ void k_pairing_value(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* flag, uint8_t* out_gt);
+// The same value on the lane-split kernels (tu_finalexp2_value.hip), two lanes per item: the final exponentiation of items
+// [first, first + count) of the Fp12 workspace fws (stride n; conj(f) as k_millerfp3 / k_millerf_rows1 leave it) with k_finalexp2s's
+// operations and value store vp, ended as a VALUE -- t f^3 -- whose 576 bytes go to out_gt[576 i ..).  An item whose flag is not PV_RUN
+// reads nothing and gets k_pairing_value's constants, written by its lane pair.
+__global__ void k_finalexp2s_value(size_t n, size_t first, size_t count, const uint32_t* fws, uint32_t* vp, size_t lanes, const int32_t* flag, uint8_t* out_gt);
 // blsgpu_timecrypt_open_batch, one lane per item.  Item i belongs to the group g with item_offs[g] <= i < item_offs[g + 1] (found by
 // bisection; empty groups own nothing).  status[i] = the first that applies of: the decode status of u_i (dec_u), of sig_g (dec_sig;
 // both null for the raw formats), BLS_ERR_INVALID_SCHEME (ct_schemes[i] != sig_schemes[g]), BLS_ERR_SIG_IDENTITY, BLS_ERR_PK_IDENTITY,

@@ -312,13 +312,18 @@ int blsgpu_pairing2_check_batch(const void* g1a, const void* g2a, const void* g1
  *               that chain; tests/test_timecrypt_cases.py checks the cube against a plain power, bilinearity and the order r.
  *   the bytes   ASSUMED, and not verifiable without the backend: the six Fp2 coefficients over w^0 .. w^5 (w^6 = xi; in tower terms
  *               c0.a0, c1.a0, c0.a1, c1.a1, c0.a2, c1.a2), each its real part, then its imaginary part, each part 48 bytes
- *               big-endian, the canonical residue (not Montgomery).  One device function (csrc/timecrypt.cuh coop_gt_bytes) and one
- *               test function (tests/timecrypt_ref.py gt_bytes) know this order; should it be wrong, the fix is a permutation there.
+ *               big-endian, the canonical residue (not Montgomery).  One place on the device (csrc/timecrypt.cuh gt_part_offset and
+ *               gt_tower_wpow, through which both exports -- coop_gt_bytes of the one-wave kernels, fx_export of k_finalexp2s_value
+ *               -- place every part) and one test function (tests/timecrypt_ref.py gt_bytes) know this order; should it be wrong,
+ *               the fix is a permutation there.
  * fmt: any of the four BLSGPU_FMT_* (both members in the same format).  A COMPRESSED / LEGACY pair that does not decode gets its
  * decode status (the G1 member's first, then the G2 member's) and 576 zero bytes.  A pair with an identity member gets Gt one
  * (00 .. 01 in the first 48 bytes, then zeros) and BLSGPU_OK, as multi_miller_loop skips it.  RAW formats are not subgroup-checked,
- * as everywhere else.  status: n entries, BLSGPU_OK or a decode status.  Pointers may be host or device memory.  One wave per item
- * (k_pairing_value), launched over chunks of at most 4,096 items; the call runs on the first bound device. */
+ * as everywhere else.  status: n entries, BLSGPU_OK or a decode status.  Pointers may be host or device memory.  Launch sequence:
+ * k_decompress x 2 (wire formats), k_pairing_value_prepare, then the pairing-value step.  Below BLSGPU_VALUE_SPLIT_MIN items (default
+ * 8,192; 0: always) that is one wave per item (k_pairing_value) over chunks of at most 4,096 items; from it up, two lanes per item in
+ * chunks of BLSGPU_MILLER_CHUNK items: k_linesp (pass 1), k_millerfp3, k_finalexp2s_value.  Both plans write the same bytes.  The call
+ * runs on the first bound device. */
 int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, uint8_t* out_gt, int32_t* status);
 
 /* TimeCryptCiphertext::decrypt(sig) (src/time_crypt_ciphertext.rs:38-50 -> BlsTimeCrypt::unseal, src/traits/time_crypt.rs:76-116) for
@@ -339,8 +344,9 @@ int blsgpu_pairing_batch(const void* g1s, const void* g2s, size_t n, int fmt, ui
  * status[i] is the first that applies of: the decode status of u_i, then of sig_g (wire formats); BLSGPU_INVALID_SCHEME
  * (ct_schemes[i] != sig_schemes[g]); BLSGPU_SIG_IDENTITY; BLSGPU_PK_IDENTITY (u is the identity); BLSGPU_BAD_FRAME (a length beyond
  * the frame, only); BLSGPU_INVALID_SIGNATURE (g r != u); BLSGPU_OK.  status[i] == BLSGPU_OK <=> is_some().  An item that is not OK
- * gets pt_range (0, 0), and its frame bytes are not part of the contract.  One wave per item for the pairing, in chunks of at most
- * 4,096 items, then one lane per item; the call runs on the first bound device. */
+ * gets pt_range (0, 0), and its frame bytes are not part of the contract.  Launch sequence: k_decompress x 2 (wire formats),
+ * k_timecrypt_prepare, the pairing-value step of blsgpu_pairing_batch (either plan), then k_timecrypt_open, one lane per item; the
+ * call runs on the first bound device. */
 int blsgpu_timecrypt_open_batch(int sig_group, const void* sigs, const uint8_t* sig_schemes, const uint64_t* item_offsets, size_t n_groups,
                                 const void* us, const uint8_t* vs, const uint8_t* ws, const uint64_t* w_offsets, const uint8_t* ct_schemes,
                                 int fmt, uint8_t* frames, uint64_t* pt_range, int32_t* status);
@@ -379,6 +385,11 @@ int blsgpu_debug_wide_steps(int set, const uint32_t* prog, size_t len, int reps,
  * is, as the verify path skips identity items; the others become BLSGPU_OK (fin^(3 (p^12 - 1) / r) == 1) or
  * BLSGPU_ERR_INVALID_SIGNATURE. */
 int blsgpu_debug_finalexp_batch(const void* f12s, size_t n, int form, size_t chunk, int32_t* status);
+/* Self-test hook of the final exponentiation WITH THE Gt EXPORT (k_finalexp2s_value, the lane-split kernel of the pairing-value
+ * calls from BLSGPU_VALUE_SPLIT_MIN items up) on the same records: out_gt = n x 576 bytes, Gt::to_bytes() of fin^(3 (p^12 - 1) / r)
+ * as assumed below.  chunk = items per chunk (0: the library's).  status[i] is read only, the item's flag as those calls set it:
+ * 0 runs the chain, 1 gives Gt one, any other value 576 zero bytes. */
+int blsgpu_debug_finalexp_value(const void* f12s, size_t n, size_t chunk, uint8_t* out_gt, const int32_t* status);
 /* Self-test hook of the field leaves and the lane-split tower (not part of the reference interface): ONE operation of
  * csrc/debug_ops.h on n caller-supplied records.  Elements cross in the internal form -- fourteen signed 32-bit limbs of 28 bits
  * per Fp, R = 2^392 -- so that lazy, redundant and negative operands can be injected.  A record of `in` is n_in limb vectors
@@ -945,8 +956,10 @@ int blsgpu_pairing_sigset_batch(uint64_t sigset, const uint32_t* idx, const void
  * u_i, the entry's creation status, BLSGPU_INVALID_SCHEME, BLSGPU_SIG_IDENTITY, BLSGPU_PK_IDENTITY, BLSGPU_BAD_FRAME,
  * BLSGPU_INVALID_SIGNATURE, BLSGPU_OK.  A failed item's pt_range is (0, 0).  Every pointer may be host or device memory; w_offsets is
  * read and checked on the host; the call runs on the set's device.  Launch sequence: k_decompress of the u (wire formats),
- * k_sigset_prepare, the pairing in chunks of at most 4,096 items -- k_pairing_value_rows over a Bls12381G2Impl set with rows,
- * k_pairing_value otherwise -- and k_timecrypt_open. */
+ * k_sigset_prepare, the pairing-value step and k_timecrypt_open.  The step, below BLSGPU_VALUE_SPLIT_MIN items: chunks of at most
+ * 4,096 items on k_pairing_value_rows over a Bls12381G2Impl set with rows, on k_pairing_value otherwise; from it up, chunks of
+ * BLSGPU_MILLER_CHUNK items on k_millerf_rows1 (such a set) or k_linesp and k_millerfp3 (otherwise), then k_finalexp2s_value.  A call
+ * that names an entry without usable rows walks, on either plan. */
 int blsgpu_timecrypt_open_indexed_batch(uint64_t sigset, const uint32_t* idx, const void* us, const uint8_t* vs, const uint8_t* ws,
                                         const uint64_t* w_offsets, const uint8_t* ct_schemes, size_t n, int fmt, uint8_t* frames, uint64_t* pt_range,
                                         int32_t* status);
