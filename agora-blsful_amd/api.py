@@ -44,7 +44,7 @@ EXPORTS = [
     'blsgpu_init_devices', 'blsgpu_device_count', 'blsgpu_sort_keys', 'blsgpu_sorted_keys_digest',
     'blsgpu_coefficients_for_range', 'blsgpu_first_duplicate_message', 'blsgpu_first_occurrence', 'blsgpu_core_verify_hashed', 'blsgpu_debug_wide_mul', 'blsgpu_debug_wide_program', 'blsgpu_debug_wide_steps', 'blsgpu_debug_finalexp_batch', 'blsgpu_debug_finalexp_value', 'blsgpu_debug_field_op_shape', 'blsgpu_debug_field_op', 'blsgpu_debug_millerf', 'blsgpu_debug_map_to_curve', 'blsgpu_debug_coop_pairing', 'blsgpu_debug_coop_pairing_keyed', 'blsgpu_verify_batch_grouped', 'blsgpu_signatures_from_tagged', 'blsgpu_signatures_to_tagged',
     'blsgpu_combine_shares', 'blsgpu_verify_secure_batch', 'blsgpu_aggregate_verify_batch', 'blsgpu_multi_verify_batch',
-    'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch',
+    'blsgpu_signcrypt_share_verify_batch', 'blsgpu_signcrypt_open_batch', 'blsgpu_signcrypt_share_verify_indexed_batch',
     'blsgpu_aggregate_secure_batch', 'blsgpu_sum_batch',
     'blsgpu_keyset_create', 'blsgpu_keyset_destroy', 'blsgpu_keyset_info', 'blsgpu_keyset_get', 'blsgpu_keyset_mul',
     'blsgpu_keyset_update', 'blsgpu_keyset_append',
@@ -56,7 +56,7 @@ EXPORTS = [
     'blsgpu_msgset_create', 'blsgpu_msgset_destroy', 'blsgpu_msgset_info', 'blsgpu_msgset_update', 'blsgpu_msgset_append',
     'blsgpu_verify_msgset_batch', 'blsgpu_verify_msgset_indexed_batch', 'blsgpu_debug_msgset_from_points', 'blsgpu_debug_coop_pairing_rows',
     'blsgpu_aggregate_verify_msgset_batch', 'blsgpu_aggregate_verify_msgset_indexed_batch',
-    'blsgpu_debug_lines',
+    'blsgpu_debug_lines', 'blsgpu_debug_tables2',
     'blsgpu_pairing_batch', 'blsgpu_timecrypt_open_batch',
     'blsgpu_sigset_create', 'blsgpu_sigset_destroy', 'blsgpu_sigset_info', 'blsgpu_sigset_append',
     'blsgpu_pairing_sigset_batch', 'blsgpu_timecrypt_open_indexed_batch',
@@ -208,8 +208,10 @@ def load_library(path=None):
         lib.blsgpu_verify_shared_batch.argtypes = [ci, ci, vp, vp, u64p, sz, u8p, u64p, ci, i32p]
         lib.blsgpu_verify_shared_indexed_batch.argtypes = [ci, h, u32p, vp, u64p, sz, u8p, u64p, ci, i32p]
         lib.blsgpu_aggregate_verify_indexed_batch.argtypes = [ci, h, u32p, u8p, u64p, u64p, sz, vp, ci, i32p, u64p]
+        lib.blsgpu_signcrypt_share_verify_indexed_batch.argtypes = [ci, h, u32p, vp, vp, u8p, u64p, sz, vp, u64p, ci, i32p]
         lib.blsgpu_debug_coop_pairing_keyed.argtypes = [ci, h, u32p, i32p, sz, i32p, i32p]
         lib.blsgpu_debug_lines.argtypes = [ci, ci, i32p, sz, i32p, sz, h, u32p, sz, i32p, u64p]
+        lib.blsgpu_debug_tables2.argtypes = [ci, vp, sz, u32p, u32p, i32p, sz, i32p, sz, i32p, u64p]
         lib.blsgpu_hash_to_scalar.argtypes = [u8p, u64p, sz, u8p, sz, u8p]
         lib.blsgpu_sig_proof_challenge_batch.argtypes = [ci, vp, u64p, sz, ci, u8p]
         lib.blsgpu_sig_proof_timestamp_verify_batch.argtypes = [ci, ci, vp, vp, vp, u64p, u8p, u64p, sz, ci, ctypes.c_uint64, ctypes.c_int64, i32p]
@@ -1155,6 +1157,28 @@ def verify_shared_indexed_batch(keyset, scheme, groups, fmt=FMT_RAW_PROJ):
     return [flat[ioffs[g]:ioffs[g + 1]] for g in range(n_groups)]
 
 
+def signcrypt_share_verify_indexed_batch(scheme, keyset, cts, shares, fmt=FMT_RAW_PROJ):
+    """signcrypt_share_verify_batch with the public-key shares named by position (blsgpu_signcrypt_share_verify_indexed_batch): `cts`
+    is a list of (u, v, w), `shares` one list per ciphertext of (position in `keyset`, decryption share raw point).  One list of
+    statuses per ciphertext: E_ARG for a position outside the table, the creation status of an invalid entry, else what
+    signcrypt_share_verify_batch gives for that share with the entry's key."""
+    n_ct = len(cts)
+    if len(shares) != n_ct:
+        raise ValueError('one list of shares per ciphertext')
+    voffs, vblob = _offsets([bytes(v) for _, v, _ in cts])
+    soffs = _count_offsets(shares)
+    n = soffs[n_ct]
+    ub, wb = b''.join(u for u, _, _ in cts), b''.join(w for _, _, w in cts)
+    idx = _u32([i for g in shares for i, _ in g])
+    shb = b''.join(s for g in shares for _, s in g)
+    st = (ctypes.c_int32 * max(n, 1))()
+    _check(init().blsgpu_signcrypt_share_verify_indexed_batch(scheme, keyset.handle, ctypes.cast(idx, ctypes.c_void_p), _ptr(ub), _ptr(wb), _ptr(vblob),
+                                                              ctypes.cast(voffs, ctypes.c_void_p), n_ct, _ptr(shb), ctypes.cast(soffs, ctypes.c_void_p), fmt,
+                                                              ctypes.cast(st, ctypes.c_void_p)))
+    flat = list(st)[:n]
+    return [flat[soffs[c]:soffs[c + 1]] for c in range(n_ct)]
+
+
 MSGSET_LINES = 1    # Bls12381G2Impl: every message point's Miller-loop rows, read above BLSGPU_WIDE_MAX items
 
 
@@ -1609,6 +1633,54 @@ def debug_lines(kernel, items, variant=0, status=None, chunk=0, keyset=None, idx
     return res, stray.value
 
 
+def _debug_tables2(mode, points, t0, t1, items, status, chunk):
+    lib = init()
+    n = len(items)
+    assert len(t0) == n and len(t1) == n and all(len(p) == 192 for p in points)
+    flat = []
+    for vecs in items:
+        assert len(vecs) == 12 and all(len(v) == 14 for v in vecs)
+        for v in vecs:
+            flat += v
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    st = (ctypes.c_int32 * max(n, 1))(*(status if status is not None else [OK] * n))
+    per = 68 * 5 * 28 if mode == 2 else 168
+    out = (ctypes.c_int32 * max(per * n, 1))()
+    stray = ctypes.c_uint64(0)
+    blob = b''.join(points)
+    _check(lib.blsgpu_debug_tables2(mode, _ptr(blob) if blob else None, len(points), ctypes.cast(_u32(t0), ctypes.c_void_p), ctypes.cast(_u32(t1), ctypes.c_void_p),
+                                    ctypes.cast(arr, ctypes.c_void_p), n, ctypes.cast(st, ctypes.c_void_p), chunk, ctypes.cast(out, ctypes.c_void_p),
+                                    ctypes.cast(ctypes.pointer(stray), ctypes.c_void_p)))
+    return list(st[:n]), list(out), stray.value
+
+
+def debug_coop_pairing_tables2(mode, points, t0, t1, items, status=None):
+    """k_pairing_coop_tables2 on caller-supplied operands: the records of debug_coop_pairing with fixed_g2 = 0, pair 0's G2 member being
+    entry t0[i] and pair 1's entry t1[i] of the table the row builder makes of `points` (RAW_AFFINE G2 byte strings; the records' own Q
+    members are not read).  mode 0 returns per item the twelve limb vectors of the easy-part value in tower order (every limb
+    COOP_SENTINEL for an item whose status is not OK), mode 1 the statuses.  An index outside the table, a point without usable rows
+    and more than 4,096 items raise (BLSGPU_E_ARG)."""
+    if mode not in (0, 1):
+        raise ValueError('mode 0 or 1')
+    st, o, _ = _debug_tables2(mode, points, t0, t1, items, status, 0)
+    if mode == 1:
+        return st
+    return [[o[168 * i + 14 * k:168 * i + 14 * (k + 1)] for k in range(12)] for i in range(len(items))]
+
+
+def debug_lines_tables2(points, t0, t1, items, status=None, chunk=0):
+    """k_lines2s_tables2, launched as the library launches it, chunk after chunk: (per item its 68 entries of five Fp2 coefficients as
+    pairs of limb vectors, the stray count), as debug_lines('lines2s_keyed', ...) with both pairs' rows from the table of `points`."""
+    _, o, stray = _debug_tables2(2, points, t0, t1, items, status, chunk)
+    per = 68 * 5 * 28
+    res = []
+    for i in range(len(items)):
+        base = per * i
+        res.append([[(o[base + (e * 5 + k) * 28:base + (e * 5 + k) * 28 + 14], o[base + (e * 5 + k) * 28 + 14:base + (e * 5 + k) * 28 + 28])
+                     for k in range(5)] for e in range(68)])
+    return res, stray
+
+
 def debug_msgset_from_points(sig_group, points, lines=False):
     """A MessageSet (scheme BASIC) whose entries are the given RAW_AFFINE points (byte strings of 96 * sig_group bytes) instead of hash
     outputs: crafted G2 points for the rows of debug_coop_pairing_rows.  Nothing is checked."""
@@ -1829,6 +1901,15 @@ class TensorOps:
         st = self.empty(max(n_shares, 1), self.torch.int32)
         _check(self.lib.blsgpu_signcrypt_share_verify_batch(sg, scheme, self._p(us), self._p(ws), self._p(vs), self._p(v_offs), n_ct, self._p(shares),
                                                             self._p(pk_shares), self._p(share_offs), FMT_RAW_PROJ, self._p(st)))
+        return st[:n_shares]
+
+    def signcrypt_share_verify_indexed_batch(self, keyset, scheme, idx, us, ws, vs, v_offs, n_ct, shares, share_offs, n_shares):
+        """the same with share i's public-key share at position idx[i] of `keyset` (idx: an int32 tensor whose bits are the uint32
+        positions)."""
+        self._sync()
+        st = self.empty(max(n_shares, 1), self.torch.int32)
+        _check(self.lib.blsgpu_signcrypt_share_verify_indexed_batch(scheme, keyset.handle, self._p(idx), self._p(us), self._p(ws), self._p(vs), self._p(v_offs),
+                                                                    n_ct, self._p(shares), self._p(share_offs), FMT_RAW_PROJ, self._p(st)))
         return st[:n_shares]
 
     def signcrypt_open_batch(self, sg, scheme, us, ws, vs, v_offs, n_ct, ids, shares, share_offs):
@@ -2540,6 +2621,20 @@ def open_many(items):
         for i, r in zip(idx, res):
             out[i] = r
     return out
+
+
+def verify_shares_many(keyset, items):
+    """SignDecryptionShare.verify over many ciphertexts at once, the members' public-key shares registered once: `keyset` is a
+    KeySet of the committee's key shares and `items` a list of (SignCryptCiphertext, [(member position, SignDecryptionShare)]).  One
+    blsgpu_signcrypt_share_verify_indexed_batch call, under the Basic DST as SignDecryptionShare.verify (reference
+    src/sign_decryption_share.rs:54).  Returns one list per item with None or the BlsError of every share, in order."""
+    if not items:
+        return []
+    sg = keyset.info()['sig_group']
+    if any(ct.impl.sig_group != sg or any(s.impl.sig_group != sg for _, s in sh) for ct, sh in items):
+        raise ValueError('verify_shares_many: every ciphertext and share must use the impl of the key set')
+    st = signcrypt_share_verify_indexed_batch(BASIC, keyset, [(ct.u, ct.v, ct.w) for ct, _ in items], [[(int(p), s.raw) for p, s in sh] for _, sh in items])
+    return [[error_from_status(x) for x in row] for row in st]
 
 
 class TimeCryptCiphertext:

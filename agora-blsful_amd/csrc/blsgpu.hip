@@ -69,6 +69,7 @@ enum {
   KID_SIGSET_SEAL, KID_SIGSET_PREP,                // registered signature sets (sigset.cuh): create / append, the prepare kernel of both calls over a set
   KID_PAIRING_VALUE_ROWS,                          // the one-wave pairing value that reads a registered signature's rows (in the place of k_pairing_value)
   KID_FINALEXP_VALUE, KID_MILLERF_ROWS1,           // pairing values on the lane-split kernels (run_pairing_values): the final exponentiation with the Gt export, the tabled accumulator
+  KID_PAIRING_COOP_TABLES2, KID_LINES_TABLES2,     // two tabled pairs with both tables in global memory (blsgpu_signcrypt_share_verify_indexed_batch): one wave per item, the lane-split line kernel
   KID_COUNT
 };
 #define KID_DEBUG_OPS KID_WIDE   // the self-test hooks share one profile id
@@ -97,7 +98,8 @@ const char* KID_NAMES[KID_COUNT] = {"k_prepare", "k_millerf2s", "k_finalexp2s", 
                                     "k_timecrypt_prepare", "k_timecrypt_open",
                                     "k_sigset_seal", "k_sigset_prepare",
                                     "k_pairing_value_rows",
-                                    "k_finalexp2s_value", "k_millerf_rows1"};
+                                    "k_finalexp2s_value", "k_millerf_rows1",
+                                    "k_pairing_coop_tables2", "k_lines2s_tables2"};
 
 struct Ctx {
   int dev = -1;
@@ -209,6 +211,11 @@ extern "C" char** environ;
 // many items the pairing values run on the lane-split kernels (run_pairing_values).  DESIGN.md section 4, "Pairing values on the
 // lane-split kernels", has the measurement the figure follows from (tools/bench_value_split.py, profiles/value_split_bench.json).
 #define VALUE_SPLIT_MIN_DEFAULT 8192
+// blsgpu_signcrypt_share_verify_indexed_batch, Bls12381G2Impl, BLSGPU_SIGNCRYPT_LINES_MIN unset: the ciphertexts' line tables are built
+// from this many shares per ciphertext on average.  DESIGN.md section 4, "Signcryption shares by key index", has the measurement the figure
+// follows from (tools/bench_signcrypt_indexed.py, profiles/signcrypt_indexed_bench.json): the row builder's one serial walk costs
+// 1.9 ms however few points it takes, which the tabled kernels win back at 256 x 16 and 1,024 x 64 shares and not at 64 x 32.
+#define SIGNCRYPT_LINES_MIN_DEFAULT 64
 struct Knobs {
   long coop_max = 4096, wide_max = 512, shard_min = 8192, contexts = 2, fake_devices = 0, acc_lanes = 57344;
   long msm_c = 0, msm_ch = 0, msm2_c = 0, msm2_ch = 0, msm2_q = 0;          // 0: the library's own choice
@@ -224,6 +231,7 @@ struct Knobs {
   long ws_keep_mb = 4096;     // a context's line workspace above this many MiB is released when the call that grew it returns
   long value_split_min = VALUE_SPLIT_MIN_DEFAULT;   // the pairing-value calls: the smallest item count that takes the lane-split kernels (0: never); never changes a result
   long shared_lines_min = -1; // blsgpu_verify_shared_batch, Bls12381G2Impl: per-group line tables from this many items per group on average (0: never; unset: SHARED_LINES_AUTO_*)
+  long signcrypt_lines_min = SIGNCRYPT_LINES_MIN_DEFAULT;   // blsgpu_signcrypt_share_verify_indexed_batch, Bls12381G2Impl: the ciphertexts' line tables from this many shares per ciphertext on average (0: never); never changes a result
   // A/B
   long miller_chunk = 65536, miller_v1 = 0, row_pad = 192, wide_mode = 2, finalexp_seg = 0, finalexp_v1 = 0, prepare_lanes = 0, product_tree = 1,
        tree_local = 0, lines4_max = -1, tree_engine_from = 0, agg_lanes = 0, msm_v1 = 0, msm_naive = 0, wide_test_block = 64;
@@ -247,6 +255,7 @@ const KnobSpec KNOB_TABLE[] = {
     {"BLSGPU_KEYSET_TABLE_MB", &Knobs::keyset_table_mb, 0, 1L << 20, false},
     {"BLSGPU_SHARED_LINES_MIN", &Knobs::shared_lines_min, 0, 1L << 32, false},
     {"BLSGPU_VALUE_SPLIT_MIN", &Knobs::value_split_min, 0, 1L << 32, false},
+    {"BLSGPU_SIGNCRYPT_LINES_MIN", &Knobs::signcrypt_lines_min, 0, 1L << 32, false},
     {"BLSGPU_MILLER_CHUNK", &Knobs::miller_chunk, 0, 65536, true},      {"BLSGPU_MILLER_V1", &Knobs::miller_v1, 0, 1, true},
     {"BLSGPU_ROW_PAD", &Knobs::row_pad, 0, 4096, true},                 {"BLSGPU_WIDE_MODE", &Knobs::wide_mode, 1, 2, true},
     {"BLSGPU_FINALEXP_SEG", &Knobs::finalexp_seg, 0, 1, true},          {"BLSGPU_FINALEXP_V1", &Knobs::finalexp_v1, 0, 1, true},
@@ -802,9 +811,12 @@ void launch_finalexp_chunk(Ctx* c, size_t n, size_t first, size_t cnt, const uin
 // ms_rows / ms_of (fixed_g2 = 0, registered message sets with rows, Bls12381G2Impl; records in their usual pair order): on the one-wave
 // path pair 0's G2 member is entry ms_of[i] of a set whose rows are in ms_rows, and k_pairing_coop_rows reads them while it walks the
 // signature (coop_rows.cuh).  Every other path ignores them (the lane-split path takes such a set as sh_table / sh_group).
+// t2_rows / t2_of (fixed_g2 = 0, Bls12381G2Impl signcryption shares by key index): BOTH G2 members are entries of one table in global
+// memory, pair 0's at t2_of[i] and pair 1's at t2_of[n + i].  Above the row-wide engine's range nothing is walked: k_pairing_coop_tables2
+// on the one-wave path, k_lines2s_tables2 as the chunk's line launch on the lane-split path (signcrypt.cuh).
 int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2, const uint32_t* sh_table = nullptr,
                  const uint32_t* sh_group = nullptr, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr,
-                 const uint32_t* ms_rows = nullptr, const uint32_t* ms_of = nullptr) {
+                 const uint32_t* ms_rows = nullptr, const uint32_t* ms_of = nullptr, const uint32_t* t2_rows = nullptr, const uint32_t* t2_of = nullptr) {
   if (n <= wide_max_items() && n <= coop_max_items()) {
     // single verifications and the one-verdict tails on the row-wide engine (csrc/wide_engine.cuh): one 256-thread workgroup
     // per item runs line coefficients, Miller loop, final exponentiation and verdict as one table program.
@@ -822,6 +834,9 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
       KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, key_table, key_of, (uint32_t*)nullptr);
     else if (fixed_g2 == 0 && ms_rows)
       KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, ms_rows, ms_of, (uint32_t*)nullptr);
+    else if (fixed_g2 == 0 && t2_rows)
+      KL(KID_PAIRING_COOP_TABLES2, k_pairing_coop_tables2, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, t2_rows, t2_of, t2_of + n,
+         (uint32_t*)nullptr);
     else
       KL(KID_PAIRING_COOP, k_pairing_coop, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, fixed_g2);
   } else {                      // two lanes per item (tower_split.cuh)
@@ -834,7 +849,7 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
     const bool finalexp_seg = knobs().finalexp_seg != 0;
     const bool finalexp_v1 = knobs().finalexp_v1 != 0;   // A/B: the one-kernel final exponentiation of rounds 1 and 2
     const size_t chunk = n < miller_chunk_items() ? n : miller_chunk_items();
-    const size_t words_per_lane = (size_t)MILLER_ENTRIES * (LINE5_WORDS + (fixed_g2 || sh_table ? 0 : LINE3_WORDS_H));   // two general pairs: pair 0's plain lines too
+    const size_t words_per_lane = (size_t)MILLER_ENTRIES * (LINE5_WORDS + (fixed_g2 || sh_table || t2_rows ? 0 : LINE3_WORDS_H));   // two general pairs: pair 0's plain lines too
     if (chunk && lines_reserve(c, words_per_lane * 4 * row_stride(lanes_for(chunk))) == 0) {
       for (size_t first = 0; first < n; first += chunk) {
         const size_t cnt = n - first < chunk ? n - first : chunk;
@@ -847,6 +862,9 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
           KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, fixed_g2, 0);
         } else if (sh_table) {
           KL(KID_LINES, k_lines2s_shared, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, sh_table, sh_group);
+        } else if (t2_rows) {
+          KL(KID_LINES_TABLES2, k_lines2s_tables2, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, t2_rows,
+             t2_of, t2_of + n);
         } else {
           KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, 0, 1);
           KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, 0, 2);
@@ -6596,6 +6614,129 @@ int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32
 }
 API_CATCH
 
+/* blsgpu_signcrypt_share_verify_batch with share i's public-key share at position idx[i] of a registered key set (every share its own
+ * set: the status precedence of blsgpu_verify_indexed_batch).  Launch sequence: k_keyset_check, k_keyset_gather, the by-value call's
+ * message and hash stages, [plan T2: k_signcrypt_ct_affine, k_group_lines over 2 n_ct points and one word back, k_signcrypt_tab_of],
+ * k_signcrypt_share_pairs on the gathered keys, [plan ROWS on the one-wave path: k_signcrypt_swap_pairs], run_pairing2,
+ * k_signcrypt_share_status, k_keyset_fin.  The plan comes from the call's shape and the set's flags alone:
+ *   ROWS  Bls12381G1Impl over a set whose named entries have line rows, above BLSGPU_WIDE_MAX shares: the pair (w, pk) reads the key's
+ *         rows and only the share is walked -- k_pairing_coop_rows / k_lines2s_shared with the set's rows in the place of a message
+ *         set's / the groups' table;
+ *   T2    Bls12381G2Impl above BLSGPU_WIDE_MAX shares with at least BLSGPU_SIGNCRYPT_LINES_MIN shares per ciphertext on average: the
+ *         rows of -W' and w are built once per ciphertext and a share walks nothing (k_pairing_coop_tables2 / k_lines2s_tables2);
+ *   else  the by-value stages on the gathered keys. */
+int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* us, const void* ws, const uint8_t* vs,
+                                                const uint64_t* v_offsets, size_t n_ct, const void* shares, const uint64_t* share_offsets, int fmt,
+                                                int32_t* status) try {
+  KeySet k;
+  int rc = set_find(keyset, k);
+  if (rc) return rc;
+  const int sig_group = k.sig_group;
+  if ((rc = check_common(sig_group, scheme, fmt))) return rc;
+  if (!v_offsets || !share_offsets) return fail(BLSGPU_E_ARG, "null offsets");
+  CTX_ACQUIRE_ON(c, k.devidx);                 // on the key set's device, without sharding
+  std::vector<uint64_t> voffs, soffs;
+  if ((rc = read_offsets(v_offsets, n_ct, "v_offsets", voffs))) return rc;
+  if ((rc = read_offsets(share_offsets, n_ct, "share_offsets", soffs))) return rc;
+  const size_t n = (size_t)soffs[n_ct], total = (size_t)voffs[n_ct];
+  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
+  if (n == 0) return 0;
+  if (!idx || !us || !ws || !shares || !status || (total && !vs)) return fail(BLSGPU_E_ARG, "null argument");
+  const size_t K = point_bytes(k.group, BLSGPU_FMT_COMPRESSED), ub = pk_size(sig_group, fmt) * n_ct, wb = sig_size(sig_group, fmt) * n_ct,
+               shb = pk_size(sig_group, fmt) * n, wtb = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n_ct, mtotal = total + K * n_ct,
+               psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt);
+  std::vector<uint64_t> moffs(n_ct + 1);
+  for (size_t s = 0; s <= n_ct; s++) moffs[s] = voffs[s] + K * s;
+  // plan T2, from the shape alone (the knob prices the 2 n_ct walks of the row builder against the two walks a share saves)
+  const size_t t2_bytes = 2 * n_ct * (size_t)SHARED_TABLE_WORDS * 4;
+  const long knob = knobs().signcrypt_lines_min;
+  const bool above_wide = n > coop_max_items() ? miller_chunk_items() != 0 : n > wide_max_items();
+  const bool t2_plan = sig_group == 2 && knob > 0 && n / n_ct >= (size_t)knob && above_wide && t2_bytes <= 0xffffffffull;
+  const size_t t2_ws = t2_plan ? pad256(2 * 192 * n_ct) + 2 * pad256(t2_bytes) + pad256(4 * (2 * n_ct + 1)) + pad256(8 * n) : 0;
+  if ((rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(ub) + pad256(wb) + pad256(total) + pad256(shb) +
+                                 3 * pad256(8 * (n_ct + 1)) + pad256(mtotal) + pad256(wtb) + pad256(768 * n_ct) + pad256(4 * n) +
+                                 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + t2_ws + 256 + 8192)))
+    return rc;
+  c->arena_off = 0;
+  const void *d_idx, *d_us, *d_ws, *d_vs, *d_sh;
+  const uint64_t *d_voffs, *d_soffs, *d_moffs;
+  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  if ((rc = stage_in(c, us, ub, &d_us))) return rc;
+  if ((rc = stage_in(c, ws, wb, &d_ws))) return rc;
+  if ((rc = stage_in(c, vs, total, &d_vs))) return rc;
+  if ((rc = stage_in(c, shares, shb, &d_sh))) return rc;
+  if ((rc = upload_offsets(c, voffs, &d_voffs)) || (rc = upload_offsets(c, soffs, &d_soffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
+  auto drain = [&](int r) {
+    (void)hipStreamSynchronize(c->stream);      // the uploads read voffs / soffs / moffs
+    return r;
+  };
+  Carver mem{c};
+  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
+  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n);
+  uint8_t* d_aff = mem.take<uint8_t>(psz * n);
+  uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(ksz * n);
+  uint8_t* d_msgs = mem.take<uint8_t>(mtotal);
+  uint8_t* d_wt = mem.take<uint8_t>(wtb);
+  int32_t* d_status = mem.take<int32_t>(4 * n);
+  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
+  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
+  uint32_t* d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
+  uint8_t* d_caff = nullptr;
+  uint32_t *d_table = nullptr, *d_scratch = nullptr, *d_tof = nullptr;
+  int32_t* d_flags = nullptr;
+  if (t2_plan) {
+    d_caff = mem.take<uint8_t>(2 * 192 * n_ct);
+    d_table = mem.take<uint32_t>(t2_bytes);
+    d_scratch = mem.take<uint32_t>(t2_bytes);
+    d_flags = mem.take<int32_t>(4 * (2 * n_ct + 1));
+    d_tof = mem.take<uint32_t>(8 * n);
+  }
+  if (!mem.ok) return drain(fail(BLSGPU_E_HIP, "internal: arena too small"));
+  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
+  const uint32_t* key_rows = nullptr;              // plan ROWS: a named finite entry without rows makes every share walk
+  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_rows))) return drain(rc);
+  const size_t cnt_ = n;
+  KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
+  if (d_keys != d_aff)
+    with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
+  // the messages U.to_bytes() || V, one per ciphertext, and their hash, as the by-value call launches them
+  with_group(sig_group, [&](auto G) {
+    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_prefix<G()>, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_us, fmt, d_voffs, d_msgs);
+  });
+  if (total) KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_copy, dim3(blocks_for(total)), dim3(BLS_BLOCK), total, n_ct, (const uint8_t*)d_vs, d_voffs, K, d_msgs);
+  if ((rc = run_hash_group(c, sig_group, n_ct, d_msgs, d_moffs, scheme_dst(sig_group, scheme), d_wt))) return drain(rc);
+  bool t2 = t2_plan;
+  if (t2) {
+    // a FINITE w or W' whose walk meets h = 0 has no usable rows: the call then takes the general form for every share -- one word
+    // read back decides it.  (An identity w never raises it: k_signcrypt_ct_affine.)
+    int32_t* h_any = (int32_t*)hsmall_take(c, 4);
+    if (!h_any) return drain(fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted"));
+    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_ct_affine, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_caff);
+    HIPCK(hipMemsetAsync(d_flags + 2 * n_ct, 0, 4, c->stream));
+    KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(4 * n_ct)), dim3(BLS_BLOCK), 2 * n_ct, (const uint8_t*)d_caff, d_table, d_scratch, d_flags);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(h_any, d_flags + 2 * n_ct, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    t2 = *h_any == 0;
+    if (t2) KL(KID_SIGNCRYPT_GATHER, k_signcrypt_tab_of, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, d_tof, d_tof + n);
+  }
+  with_group(sig_group, [&](auto G) {
+    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_pairs<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, (const uint8_t*)d_sh, (const uint8_t*)d_keys,
+       (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_pairs, d_status);
+  });
+  const bool one_wave = n <= coop_max_items();
+  if (key_rows && one_wave)
+    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_swap_pairs, dim3(blocks_for(n * (size_t)WS_PAIR1_WORDS)), dim3(BLS_BLOCK), n, d_pairs);
+  rc = run_pairing2(c, n, d_pairs, d_f, d_status, 0, one_wave ? nullptr : key_rows, d_cidx, nullptr, nullptr, one_wave ? key_rows : nullptr, d_cidx,
+                    t2 ? d_table : nullptr, d_tof);
+  if (rc) return drain(rc);
+  KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_status, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_status);
+  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
+  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
+  return status_out_and_sync(c, status, d_status, n);
+}
+API_CATCH
+
 /* Self-test hook of k_pairing_coop_keyed (include/blsgpu.h): the records of blsgpu_debug_coop_pairing with fixed_g2 = 2, pair 0's G2
  * member being entry idx[i] of a set with line tables.  The kernel is launched exactly as run_pairing2 launches it (mode 1), or with
  * the export of the easy-part value (mode 0). */
@@ -6782,6 +6923,110 @@ int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, 
       for (size_t j = 0; j < cnt; j++)
         for (size_t comp = 0; comp < 2; comp++)
           out[((((first + j) * E + e) * (out_words / FP_NL) + kk) * 2 + comp) * FP_NL + l] = (int32_t)row[2 * j + comp];
+      for (size_t t = 2 * cnt; t < lanes; t++)
+        if (row[t] != sentinel) ++*stray;
+    }
+  }
+  SYNC_FLUSH(c);
+  return 0;
+}
+API_CATCH
+
+/* Self-test hook of the two kernels that read BOTH pairs' rows from one table in global memory (include/blsgpu.h): the m affine G2
+ * points become a table through the row builder (k_group_lines), and item i's pairs are (P0, entry t0[i]), (P1, entry t1[i]) -- the
+ * records of blsgpu_debug_coop_pairing, whose Q members are not read.  Modes 0 and 1: k_pairing_coop_tables2 as run_pairing2 launches
+ * it, with the easy-part export / the verdict, as blsgpu_debug_coop_pairing_keyed.  Mode 2: k_lines2s_tables2 chunk after chunk, the
+ * line5 entries and *stray as BLSGPU_LINES_2S_KEYED of blsgpu_debug_lines. */
+int blsgpu_debug_tables2(int mode, const void* points, size_t m, const uint32_t* t0, const uint32_t* t1, const int32_t* in, size_t n, int32_t* status, size_t chunk,
+                         int32_t* out, uint64_t* stray) try {
+  if (!initialised()) return NOT_INIT();
+  if (n == 0) return 0;
+  if (!points || !t0 || !t1 || !in || !status || mode < 0 || mode > 2 || n > 4096 || m == 0 || m > 4096 || (mode != 1 && !out) || (mode == 2 && !stray) ||
+      is_device_ptr(points) || is_device_ptr(t0) || is_device_ptr(t1) || is_device_ptr(in) || is_device_ptr(status) || is_device_ptr(out))
+    return fail(BLSGPU_E_ARG, "bad argument");
+  for (size_t i = 0; i < n; i++)
+    if ((uint64_t)t0[i] >= (uint64_t)m || (uint64_t)t1[i] >= (uint64_t)m) return fail(BLSGPU_E_ARG, "index outside the table");
+  CTX_ACQUIRE(c);
+  const size_t rec = WS_PAIRS_WORDS, E = MILLER_ENTRIES, tb = m * (size_t)SHARED_TABLE_WORDS * 4;
+  int rc = arena_reserve(c, pad256(192 * m) + 2 * pad256(tb) + pad256(4 * (m + 1)) + pad256(rec * 4 * n) + 2 * pad256(8 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 8192);
+  if (rc) return rc;
+  c->arena_off = 0;
+  std::vector<uint32_t> h(rec * n), tt(2 * n);
+  for (size_t i = 0; i < n; i++) {
+    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
+    tt[i] = t0[i];
+    tt[n + i] = t1[i];
+  }
+  const void *d_pts, *d_in, *d_st, *d_tt;
+  if ((rc = stage_in(c, points, 192 * m, &d_pts))) return rc;
+  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  if ((rc = stage_in(c, tt.data(), 8 * n, &d_tt))) return rc;
+  Carver mem{c};
+  uint32_t* d_table = mem.take<uint32_t>(tb);
+  uint32_t* d_scratch = mem.take<uint32_t>(tb);
+  int32_t* d_flags = mem.take<int32_t>(4 * (m + 1));
+  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemsetAsync(d_flags + m, 0, 4, c->stream));
+  KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(2 * m)), dim3(BLS_BLOCK), m, (const uint8_t*)d_pts, d_table, d_scratch, d_flags);
+  HIPCK(hipGetLastError());
+  int32_t any = 0;
+  HIPCK(hipMemcpyAsync(&any, d_flags + m, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));             // h and tt leave scope after the call; pageable memory
+  if (any) return fail(BLSGPU_E_ARG, "a point has no usable rows");
+  const uint32_t *d_pairs = (const uint32_t*)d_in, *d_t0 = (const uint32_t*)d_tt, *d_t1 = d_t0 + n;
+  int32_t* d_status = (int32_t*)d_st;
+  if (mode == 1) {
+    KL(KID_PAIRING_COOP_TABLES2, k_pairing_coop_tables2, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, (const uint32_t*)d_table, d_t0, d_t1, (uint32_t*)nullptr);
+    HIPCK(hipGetLastError());
+    return copy_out_and_sync(c, status, d_status, 4 * n);
+  }
+  if (mode == 0) {
+    uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
+    if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
+    KL(KID_PAIRING_COOP_TABLES2, k_pairing_coop_tables2, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, (const uint32_t*)d_table, d_t0, d_t1, d_easy);
+    HIPCK(hipGetLastError());
+    std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
+    HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    // the engine's value layout -> tower order, fourteen limbs each, as blsgpu_debug_coop_pairing
+    for (size_t i = 0; i < n; i++)
+      for (size_t kk = 0; kk < 6; kk++) {
+        const size_t pw = kk < 3 ? 2 * kk : 2 * (kk - 3) + 1;
+        for (size_t comp = 0; comp < 2; comp++)
+          for (size_t l = 0; l < FP_NL; l++) out[i * WS_F_WORDS + (2 * kk + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
+      }
+    SYNC_FLUSH(c);
+    return 0;
+  }
+  // mode 2: the line kernel, the chunk loop and the stray count of blsgpu_debug_lines
+  const uint32_t sentinel = (uint32_t)BLSGPU_DEBUG_COOP_SENTINEL;
+  *stray = 0;
+  size_t per = chunk ? chunk : miller_chunk_items() ? miller_chunk_items() : n;
+  if (per > n) per = n;
+  const size_t lanes_max = row_stride(lanes_for(per));
+  const size_t ws_words = E * (LINE5_WORDS + LINE3_WORDS_H) * lanes_max;       // (the tail: words no launch may touch)
+  if (lines_reserve(c, ws_words * 4)) return fail(BLSGPU_E_HIP, "no room for the line workspace");
+  std::vector<uint32_t> rows;
+  for (size_t first = 0; first < n; first += per) {
+    const size_t cnt = n - first < per ? n - first : per;
+    const size_t nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
+    HIPCK(hipMemsetAsync(c->lines_ws, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, ws_words * 4, c->stream));
+    KL(KID_LINES_TABLES2, k_lines2s_tables2, dim3((unsigned)(nlanes / BLS_BLOCK)), dim3(BLS_BLOCK), n, first, cnt, d_pairs, (const int32_t*)d_status, c->lines_ws, lanes,
+       (const uint32_t*)d_table, d_t0, d_t1);
+    HIPCK(hipGetLastError());
+    const size_t nrows = E * LINE5_WORDS;
+    rows.resize(ws_words);
+    HIPCK(hipMemcpyAsync(rows.data(), c->lines_ws, ws_words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    for (size_t at = nrows * lanes; at < ws_words; at++)
+      if (rows[at] != sentinel) ++*stray;
+    for (size_t r = 0; r < nrows; r++) {
+      const uint32_t* row = rows.data() + r * lanes;
+      const size_t e = r / LINE5_WORDS, w = r % LINE5_WORDS, kk = w / FP_NL, l = w % FP_NL;
+      for (size_t j = 0; j < cnt; j++)
+        for (size_t comp = 0; comp < 2; comp++) out[((((first + j) * E + e) * 5 + kk) * 2 + comp) * FP_NL + l] = (int32_t)row[2 * j + comp];
       for (size_t t = 2 * cnt; t < lanes; t++)
         if (row[t] != sentinel) ++*stray;
     }

@@ -1213,7 +1213,7 @@ template __global__ void k_prepare_proof<2>(size_t, const uint8_t*, const uint8_
 #endif  // BLS_TU_SIGN*
 
 #if defined(BLS_TU_MILLERS) || defined(BLS_TU_FINALEXPS) || defined(BLS_TU_LINES) || defined(BLS_TU_MILLERF) || defined(BLS_TU_FINALEXP2) || defined(BLS_TU_CYCRUN4) || \
-    defined(BLS_TU_FINALEXP2_VALUE) || defined(BLS_TU_MILLERF_ROWS1)
+    defined(BLS_TU_FINALEXP2_VALUE) || defined(BLS_TU_MILLERF_ROWS1) || defined(BLS_TU_LINES_TABLES2)
 // =====================================================================================================
 // lane-split variants (tower_split.cuh): two adjacent lanes per item, 64-thread workgroups = 32 items
 #include "tower_split.cuh"
@@ -1318,7 +1318,7 @@ __global__ void __launch_bounds__(BLS_BLOCK, BLS_SPLIT_WAVES) k_miller1s(size_t 
 }
 #endif
 
-#if defined(BLS_TU_LINES) || defined(BLS_TU_MILLERF)
+#if defined(BLS_TU_LINES) || defined(BLS_TU_MILLERF) || defined(BLS_TU_LINES_TABLES2)
 // =====================================================================================================
 // Round 3: the two-pair Miller loop cut in two kernels so that neither holds more state than its registers and LDS take
 // ("The Miller loop in two kernels").  k_lines2s walks the G2 point(s), evaluates the lines, merges the two
@@ -1356,7 +1356,7 @@ __device__ __forceinline__ void line5_ld(line5_t<hfp2>& L, const uint32_t* lines
 }
 #endif
 
-#if defined(BLS_TU_LINES)
+#if defined(BLS_TU_LINES) || defined(BLS_TU_LINES_TABLES2)   // (the second: the LDS accessors alone, tu_lines_tables2.hip)
 // State of the point walk in LDS, one column per lane (word k at sh[k * 64]), unpacked: T = (X, Y, Z) 3 x 14 words, then one Fp
 // of P0 and one of P1 -- the even lane keeps the x coordinates, the odd lane the y coordinates, and the partner's word comes by
 // DPP where the other one is needed.  70 of the 80 dwords a lane may use at two waves per SIMD.
@@ -1381,6 +1381,8 @@ __device__ __forceinline__ void ls_ld_coord(fp& r, const lds_u32* sh, int w0, bo
   fp_partner(other, own);
   fp_sel(r, lane_hi() == want_y, own, other);
 }
+#endif
+#if defined(BLS_TU_LINES)
 struct miller_lds {
   lds_u32* sh;
   const uint32_t* pairs;   // the pairs workspace: Q0 is read from it at the five addition steps

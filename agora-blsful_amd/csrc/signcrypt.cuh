@@ -106,4 +106,23 @@ __global__ void k_signcrypt_share_status(size_t n, int32_t* status);
 // validity verdicts on entry).  share_offs == nullptr: a key per ciphertext, no share-count rule.
 __global__ void k_signcrypt_keystream(size_t n_ct, const uint64_t* v_offs, const uint8_t* vs, const uint8_t* gbytes, int glen,
                                       const uint64_t* share_offs, uint8_t* frames, uint64_t* pt_range, int32_t* status);
+
+// ---- blsgpu_signcrypt_share_verify_indexed_batch: the key shares are entries of a registered key set (tu_signcrypt_indexed.hip)
+// Bls12381G2Impl's table plan.  Both G2 members of a share's check belong to its CIPHERTEXT, so their normalised rows are built once per
+// ciphertext (verify_shared.cuh k_group_lines over 2 n_ct points) and a share walks nothing.  aff: 192-byte affine records, -W'_c at
+// 2 c and w_c at 2 c + 1 (an identity w_c: -W'_c again -- its shares are decided before any row is read and must not look like an
+// entry without rows)
+__global__ void k_signcrypt_ct_affine(size_t n_ct, const uint8_t* ws, int fmt, const uint8_t* wt, uint8_t* aff);
+// share i of ciphertext c reads the entries t0[i] = 2 c and t1[i] = 2 c + 1
+__global__ void k_signcrypt_tab_of(size_t n, size_t n_ct, const uint64_t* share_offs, uint32_t* t0, uint32_t* t1);
+// Bls12381G1Impl over a set with line rows, one-wave path: k_pairing_coop_rows takes its tabled pair FIRST, so the two pairs of every
+// record trade places (the lane-split k_lines2s_shared takes it second, which is the order k_signcrypt_share_pairs writes)
+__global__ void k_signcrypt_swap_pairs(size_t n, uint32_t* pairs);
+// The Miller loop of two TABLED pairs whose rows both lie in `table` (68 rows of 4 FP_NL words per entry, the *_LINES_N layout): pair k
+// of item i is (P_k, entry tk[i]); the records' Q members are not read.  One wave per item (tu_coop_tables2.hip; easy as in
+// k_pairing_coop_keyed), and the lane-split line kernel whose line5 stream k_millerf2s consumes (tu_lines_tables2.hip).
+__global__ void k_pairing_coop_tables2(size_t n, const uint32_t* pairs, int32_t* status, const uint32_t* table, const uint32_t* t0, const uint32_t* t1,
+                                       uint32_t* easy);
+__global__ void k_lines2s_tables2(size_t n, size_t first, size_t count, const uint32_t* pairs, const int32_t* status, uint32_t* lines, size_t lanes,
+                                  const uint32_t* table, const uint32_t* t0, const uint32_t* t1);
 #endif

@@ -473,6 +473,19 @@ int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* i
 #define BLSGPU_LINES_MILLER2S 7
 int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, const int32_t* status, size_t chunk, uint64_t keyset, const uint32_t* idx, size_t t_b,
                        int32_t* out, uint64_t* stray);
+/* Self-test hook of the two kernels whose pairs BOTH read their rows from one table in global memory (not part of the reference
+ * interface): the signcryption share check by key index of Bls12381G2Impl.  points: m RAW_AFFINE G2 points (192 bytes each), made into
+ * a table by the library's row builder; every point must be finite with usable rows.  pairs, status and the sentinel are those of
+ * blsgpu_debug_coop_pairing with fixed_g2 = 0, except that pair 0's G2 member is entry t0[i] of the table and pair 1's entry t1[i]: the
+ * records' own Q members are not read.
+ * mode 0: k_pairing_coop_tables2 with the export: out gets the easy-part value per item (twelve limb vectors, tower order), every limb
+ *         of a skipped item is the sentinel, status is left as it is.
+ * mode 1: k_pairing_coop_tables2 as the verify path launches it: status becomes BLSGPU_OK or BLSGPU_ERR_INVALID_SIGNATURE.
+ * mode 2: k_lines2s_tables2, one chunk of `chunk` items after another (0: the library's own chunk): out gets line5 per item and *stray
+ *         the words written where nothing may be, both as BLSGPU_LINES_2S_KEYED of blsgpu_debug_lines.
+ * BLSGPU_E_ARG: another mode, m = 0 or m > 4096, n > 4096, an index that is not below m, a point without usable rows.  Host pointers. */
+int blsgpu_debug_tables2(int mode, const void* points, size_t m, const uint32_t* t0, const uint32_t* t1, const int32_t* pairs, size_t n, int32_t* status,
+                         size_t chunk, int32_t* out, uint64_t* stray);
 /* Self-test hooks of the one-wave pairing kernel that reads a registered message's line rows (not part of the reference interface).
  * blsgpu_debug_msgset_from_points: a message set (below: blsgpu_msgset_*) of scheme Basic whose n entries are the given RAW_AFFINE
  *   points of group sig_group (host or device memory) instead of hash outputs, so that crafted G2 points can reach the rows; flags as
@@ -600,6 +613,21 @@ int blsgpu_multi_verify_batch(int sig_group, int scheme, const void* pks, const 
 int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs,
                                         const uint64_t* v_offsets, size_t n_ct, const void* shares, const void* pk_shares,
                                         const uint64_t* share_offsets, int fmt, int32_t* status);
+
+/* The same with share i's public-key share at position idx[i] of a registered key set (blsgpu_keyset_create; a committee's key shares
+ * are fixed for hours while its members' decryption shares arrive per ciphertext).  idx has share_offsets[n_ct] entries; the sig group is
+ * the set's; fmt describes us, ws and shares.  BLSGPU_E_ARG with no status written: an unknown handle, offsets that decrease or do not
+ * start at 0, a null required argument, 2^32 or more shares.  No shares: 0.  The call runs on the key set's device and does not shard.
+ * status[i], every share its own set, the first that applies: BLSGPU_E_ARG in the slot for a position outside the table (nothing
+ * outside the table is read); the entry's creation status for an invalid entry; otherwise exactly what the by-value call gives for that
+ * share with the gathered key (the identity entry is a valid entry: BLSGPU_INVALID_DECRYPTION_SHARE).  Repeated indices are repeated keys.
+ * Above BLSGPU_WIDE_MAX shares the call reads line rows where that saves a walk and never where it changes a status: for
+ * Bls12381G1Impl the key's rows of a set created with BLSGPU_KEYSET_LINES (only the share is walked); for Bls12381G2Impl the rows of
+ * -W' and w, built once per ciphertext, when the call has at least BLSGPU_SIGNCRYPT_LINES_MIN shares per ciphertext on average
+ * (a share then walks nothing; 0: never; unset: 64, the measured default). */
+int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* us, const void* ws,
+                                                const uint8_t* vs, const uint64_t* v_offsets, size_t n_ct, const void* shares,
+                                                const uint64_t* share_offsets, int fmt, int32_t* status);
 
 /* Batched BlsSignCrypt::unseal_with_shares = SignCryptCiphertext::decrypt_with_shares (sign_crypt.rs:106-119,
  * sign_crypt_ciphertext.rs:60-72):
