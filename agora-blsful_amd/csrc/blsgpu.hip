@@ -799,46 +799,116 @@ void launch_finalexp_chunk(Ctx* c, size_t n, size_t first, size_t cnt, const uin
   }
 }
 
-// the two-pair pairing check of every item whose status is still BLS_OK: status <- OK / INVALID_SIGNATURE.
-// fixed_g2: the second pair's G2 member is a constant with precomputed lines: 1 = -g2, 2 = -[c] g2 (csrc/g2neg_lines.cuh)
-// sh_table / sh_group (fixed_g2 = 0, shared-message verify): on the lane-split path pair 1's G2 member is the point of item i's group
-// sh_group[i], its normalised rows in sh_table (verify_shared.cuh; the records carry the signature's pair first) -- one line
-// launch per chunk (k_lines2s_shared) instead of two.  Every other path takes the records as two general pairs.
-// key_table / key_of (fixed_g2 = 2, registered key sets with line tables): pair 0's G2 member is the entry key_of[i] of a set whose
-// rows are in key_table (keyset.cuh).  On the lane-split path the chunk's line launch reads both rows and walks nothing
-// (k_lines2s_keyed); on the one-wave path k_pairing_coop_keyed runs the Miller loop of two tabled pairs (coop.cuh
-// coop_miller2_tables).  The row-wide engine and the BLSGPU_WIDE_MODE=1 branch ignore them.
-// ms_rows / ms_of (fixed_g2 = 0, registered message sets with rows, Bls12381G2Impl; records in their usual pair order): on the one-wave
-// path pair 0's G2 member is entry ms_of[i] of a set whose rows are in ms_rows, and k_pairing_coop_rows reads them while it walks the
-// signature (coop_rows.cuh).  Every other path ignores them (the lane-split path takes such a set as sh_table / sh_group).
-// t2_rows / t2_of (fixed_g2 = 0, Bls12381G2Impl signcryption shares by key index): BOTH G2 members are entries of one table in global
-// memory, pair 0's at t2_of[i] and pair 1's at t2_of[n + i].  Above the row-wide engine's range nothing is walked: k_pairing_coop_tables2
-// on the one-wave path, k_lines2s_tables2 as the chunk's line launch on the lane-split path (signcrypt.cuh).
-int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, int fixed_g2, const uint32_t* sh_table = nullptr,
-                 const uint32_t* sh_group = nullptr, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr,
-                 const uint32_t* ms_rows = nullptr, const uint32_t* ms_of = nullptr, const uint32_t* t2_rows = nullptr, const uint32_t* t2_of = nullptr) {
-  if (n <= wide_max_items() && n <= coop_max_items()) {
+// Which kernels the two-pair pairing check of n items runs on -- the ONE statement of the rule; every plan that depends on it asks here.
+enum PairPath {
+  PATH_ENGINE,      // up to BLSGPU_WIDE_MAX items (and BLSGPU_COOP_MAX): the row-wide engine, one 256-thread workgroup per item
+  PATH_ONE_WAVE,    // up to BLSGPU_COOP_MAX items: one wave per item (coop.cuh)
+  PATH_LANE_SPLIT   // above: two lanes per item (tower_split.cuh)
+};
+PairPath pair_path(size_t n) {
+  if (n > coop_max_items()) return PATH_LANE_SPLIT;
+  return n <= wide_max_items() ? PATH_ENGINE : PATH_ONE_WAVE;
+}
+// the lane-split path runs its Miller loop in two kernels, chunk after chunk (else: the one-kernel loop, which reads no table)
+bool lane_split_chunked() { return miller_chunk_items() != 0; }
+// does a call of n items run kernels that can take a G2 member from precomputed rows?  The engine walks every point, and so does
+// the one-kernel Miller loop of the lane-split path.
+bool pair_path_reads_rows(size_t n) {
+  const PairPath path = pair_path(n);
+  return path == PATH_ONE_WAVE || (path == PATH_LANE_SPLIT && lane_split_chunked());
+}
+
+// A G2 member taken from precomputed Miller-loop rows instead of being walked: item i's member is entry of[i] of the table `rows`.
+struct TabledG2 {
+  const uint32_t* rows = nullptr;   // null: the member is walked from the record
+  const uint32_t* of = nullptr;     // device, one entry index per item
+};
+// What run_pairing2 knows about the G2 members of its two pairs beyond the records.  The launchers take the first that
+// applies of: `key` (only with fixed_g2 = 2), then with fixed_g2 = 0 `msg` (one-wave) or `shared` (lane-split), then `both`; with none, two
+// general pairs (or one, with fixed_g2).  So `key` may stand beside `shared` or `msg` -- fixed_g2 says which implementation the call
+// is for -- and a role that the path taken does not read is ignored: a caller sets the role of the path it wrote its records for,
+// asking pair_path(n).
+struct PairTables {
+  // the second pair's G2 member is a constant with precomputed lines: 0 = none, 1 = -g2, 2 = -[c] g2 (csrc/g2neg_lines.cuh).  Every path.
+  int fixed_g2 = 0;
+  // fixed_g2 = 0, shared-message verify (verify_shared.cuh): PAIR 1's G2 member is the point of item i's group shared.of[i], its
+  // normalised rows in shared.rows; the records carry the SIGNATURE'S PAIR FIRST.  Read on the lane-split path only, where the chunk's
+  // line launch is one k_lines2s_shared instead of two k_lines2s.
+  TabledG2 shared;
+  // fixed_g2 = 2, registered key sets with line tables (keyset.cuh): PAIR 0's G2 member is entry key.of[i] of the set; records in
+  // their usual order.  Read on the lane-split path (k_lines2s_keyed reads both rows and walks nothing) and on the one-wave path
+  // (k_pairing_coop_keyed, coop.cuh coop_miller2_tables); the engine and its BLSGPU_WIDE_MODE=1 branch ignore it.
+  TabledG2 key;
+  // fixed_g2 = 0, registered message sets with rows, Bls12381G2Impl (coop_rows.cuh): PAIR 0's G2 member is entry msg.of[i] of the set;
+  // records in their usual pair order.  Read on the one-wave path only (k_pairing_coop_rows reads the rows while it walks the
+  // signature); the lane-split path takes such a set as `shared`.
+  TabledG2 msg;
+  // fixed_g2 = 0, Bls12381G2Impl signcryption shares by key index (signcrypt.cuh): BOTH G2 members are entries of one table, pair 0's at
+  // both.of[i] and pair 1's at both.of[n + i]; records in their usual order.  Read on the one-wave path (k_pairing_coop_tables2) and on
+  // the lane-split path (k_lines2s_tables2 as the chunk's line launch): above the engine's range nothing is walked.
+  TabledG2 both;
+};
+// no tabled member: both pairs as the records give them, the second one's G2 member the constant that fixed_g2 names
+PairTables pairs_walked(int fixed_g2) {
+  PairTables t;
+  t.fixed_g2 = fixed_g2;
+  return t;
+}
+
+// The only launch of the one-wave family: the kernel the descriptor names, one wave per item.  d_easy = null: final exponentiation and
+// verdict into d_status; else the easy-part value of item i into d_easy + i * WIDE_EASY_WORDS (the BLSGPU_WIDE_MODE=1 branch, the hooks).
+void launch_pairing_coop(Ctx* c, size_t n, const uint32_t* d_pairs, int32_t* d_status, const PairTables& t, uint32_t* d_easy = nullptr) {
+  const dim3 grid((unsigned)n), block(BLS_BLOCK);
+  if (t.fixed_g2 == 2 && t.key.rows)
+    KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, grid, block, n, d_pairs, d_status, t.key.rows, t.key.of, d_easy);
+  else if (t.fixed_g2 == 0 && t.msg.rows)
+    KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, grid, block, n, d_pairs, d_status, t.msg.rows, t.msg.of, d_easy);
+  else if (t.fixed_g2 == 0 && t.both.rows)
+    KL(KID_PAIRING_COOP_TABLES2, k_pairing_coop_tables2, grid, block, n, d_pairs, d_status, t.both.rows, t.both.of, t.both.of + n, d_easy);
+  else if (d_easy)
+    KL(KID_PAIRING_COOP, k_pairing_coop_easy, grid, block, n, d_pairs, (const int32_t*)d_status, t.fixed_g2, d_easy);
+  else
+    KL(KID_PAIRING_COOP, k_pairing_coop, grid, block, n, d_pairs, d_status, t.fixed_g2);
+}
+// Do the merged line values of a chunk need pass 1's plain lines of pair 0 behind them (two general pairs: k_lines2s in two passes)?
+bool lines_two_pass(const PairTables& t) { return !t.fixed_g2 && !t.shared.rows && !t.both.rows; }
+// The only line launch of a lane-split chunk: the merged line values of items [first, first + cnt) into the context's line workspace,
+// rows `lanes` words apart (row_stride(lanes_for(cnt))), by the kernel the descriptor names.
+void launch_lines2s(Ctx* c, size_t n, size_t first, size_t cnt, const uint32_t* d_pairs, const int32_t* d_status, const PairTables& t, size_t lanes) {
+  const dim3 grid((unsigned)(lanes_for(cnt) / BLS_BLOCK)), block(BLS_BLOCK);
+  uint32_t* lines3 = c->lines_ws + (size_t)MILLER_ENTRIES * LINE5_WORDS * lanes;
+  if (t.fixed_g2 == 2 && t.key.rows) {
+    KL(KID_LINES_KEYED, k_lines2s_keyed, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lanes, t.key.rows, t.key.of);
+  } else if (t.fixed_g2) {
+    KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, t.fixed_g2, 0);
+  } else if (t.shared.rows) {
+    KL(KID_LINES, k_lines2s_shared, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lanes, t.shared.rows, t.shared.of);
+  } else if (t.both.rows) {
+    KL(KID_LINES_TABLES2, k_lines2s_tables2, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lanes, t.both.rows, t.both.of, t.both.of + n);
+  } else {
+    KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, 0, 1);
+    KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, 0, 2);
+  }
+}
+
+// the two-pair pairing check of every item whose status is still BLS_OK: status <- OK / INVALID_SIGNATURE
+int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_status, const PairTables& t) {
+  const int fixed_g2 = t.fixed_g2;
+  const PairPath path = pair_path(n);
+  if (path == PATH_ENGINE) {
     // single verifications and the one-verdict tails on the row-wide engine (csrc/wide_engine.cuh): one 256-thread workgroup
     // per item runs line coefficients, Miller loop, final exponentiation and verdict as one table program.
     // BLSGPU_WIDE_MODE=1: only the hard part of the final exponentiation on the engine, Miller loop + easy part per wave.
     if (knobs().wide_mode == 1) {
       uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);   // arena_reserve keeps 1 MiB of headroom: 768 B per item
       if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
-      KL(KID_PAIRING_COOP, k_pairing_coop_easy, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, (const int32_t*)d_status, fixed_g2, d_easy);
+      launch_pairing_coop(c, n, d_pairs, d_status, pairs_walked(fixed_g2), d_easy);
       KL(KID_WIDE, k_finalexp_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), n, (const uint32_t*)d_easy, d_status);
     } else {
       KL(KID_WIDE, k_pairing_wide, dim3((unsigned)n), dim3(WIDE_ENGINE_BLOCK), n, (const uint32_t*)d_pairs, d_status, fixed_g2);
     }
-  } else if (n <= coop_max_items()) {  // small batches: one wave per item
-    if (fixed_g2 == 2 && key_table)
-      KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, key_table, key_of, (uint32_t*)nullptr);
-    else if (fixed_g2 == 0 && ms_rows)
-      KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, ms_rows, ms_of, (uint32_t*)nullptr);
-    else if (fixed_g2 == 0 && t2_rows)
-      KL(KID_PAIRING_COOP_TABLES2, k_pairing_coop_tables2, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_pairs, d_status, t2_rows, t2_of, t2_of + n,
-         (uint32_t*)nullptr);
-    else
-      KL(KID_PAIRING_COOP, k_pairing_coop, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, fixed_g2);
+  } else if (path == PATH_ONE_WAVE) {  // small batches: one wave per item
+    launch_pairing_coop(c, n, d_pairs, d_status, t);
   } else {                      // two lanes per item (tower_split.cuh)
     // The Miller loop in two kernels (kernels.cuh k_lines2s / k_millerf2s), a chunk of at most miller_chunk_items() items at a
     // time: the chunk's merged line values pass through the context's line workspace.  BLSGPU_MILLER_V1=1, or no memory for
@@ -849,26 +919,13 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
     const bool finalexp_seg = knobs().finalexp_seg != 0;
     const bool finalexp_v1 = knobs().finalexp_v1 != 0;   // A/B: the one-kernel final exponentiation of rounds 1 and 2
     const size_t chunk = n < miller_chunk_items() ? n : miller_chunk_items();
-    const size_t words_per_lane = (size_t)MILLER_ENTRIES * (LINE5_WORDS + (fixed_g2 || sh_table || t2_rows ? 0 : LINE3_WORDS_H));   // two general pairs: pair 0's plain lines too
-    if (chunk && lines_reserve(c, words_per_lane * 4 * row_stride(lanes_for(chunk))) == 0) {
+    const size_t words_per_lane = (size_t)MILLER_ENTRIES * (LINE5_WORDS + (lines_two_pass(t) ? LINE3_WORDS_H : 0));   // two general pairs: pair 0's plain lines too
+    if (lane_split_chunked() && lines_reserve(c, words_per_lane * 4 * row_stride(lanes_for(chunk))) == 0) {
       for (size_t first = 0; first < n; first += chunk) {
         const size_t cnt = n - first < chunk ? n - first : chunk;
         const size_t nlanes = lanes_for(cnt), lanes = row_stride(nlanes);       // `lanes` below: the row stride the kernels index with
-        uint32_t* lines3 = c->lines_ws + (size_t)MILLER_ENTRIES * LINE5_WORDS * lanes;
         const dim3 grid((unsigned)(nlanes / BLS_BLOCK));
-        if (fixed_g2 == 2 && key_table) {
-          KL(KID_LINES_KEYED, k_lines2s_keyed, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, key_table, key_of);
-        } else if (fixed_g2) {
-          KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, fixed_g2, 0);
-        } else if (sh_table) {
-          KL(KID_LINES, k_lines2s_shared, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, sh_table, sh_group);
-        } else if (t2_rows) {
-          KL(KID_LINES_TABLES2, k_lines2s_tables2, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lanes, t2_rows,
-             t2_of, t2_of + n);
-        } else {
-          KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, 0, 1);
-          KL(KID_LINES, k_lines2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const uint32_t*)d_pairs, (const int32_t*)d_status, c->lines_ws, lines3, lanes, 0, 2);
-        }
+        launch_lines2s(c, n, first, cnt, d_pairs, d_status, t, lanes);
         KL(KID_MILLER2, k_millerf2s, grid, dim3(BLS_BLOCK), n, first, cnt, (const int32_t*)d_status, (const uint32_t*)c->lines_ws, lanes, d_f);
         // the chunk's line values are consumed: the same memory is the value store of the final exponentiation (3.4 KB per lane)
         if (!finalexp_v1) launch_finalexp_chunk(c, n, first, cnt, d_f, d_status, finalexp_seg);
@@ -880,6 +937,103 @@ int run_pairing2(Ctx* c, size_t n, uint32_t* d_pairs, uint32_t* d_f, int32_t* d_
     }
   }
   HIPCK(hipGetLastError());
+  return 0;
+}
+
+// ---- what the self-test hooks of the two-pair kernels share
+// A hook's records (n items of `rec` words, item after item) in the workspace layout -- word w of item i at ws[w * n + i] -- staged with the
+// statuses and, if the hook has one, an index array of of_words words, in that order.  The stream is synchronised before the
+// transposed copy leaves scope (pageable memory).
+struct DebugStaged {
+  const uint32_t* pairs;
+  int32_t* status;
+  const uint32_t* of;      // null: no index array
+};
+static int debug_stage(Ctx* c, const int32_t* in, size_t rec, size_t n, const int32_t* status, DebugStaged* s, const uint32_t* of = nullptr, size_t of_words = 0) {
+  std::vector<uint32_t> h(rec * n);
+  for (size_t i = 0; i < n; i++)
+    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
+  const void *d_in, *d_st, *d_of = nullptr;
+  int rc;
+  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
+  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
+  if (of && (rc = stage_in(c, of, 4 * of_words, &d_of))) return rc;
+  HIPCK(hipStreamSynchronize(c->stream));
+  *s = {(const uint32_t*)d_in, (int32_t*)d_st, (const uint32_t*)d_of};
+  return 0;
+}
+// The body of the one-wave hooks, after their argument checks, arena reservation and debug_stage: the kernel that `t` names runs on
+// the staged records through launch_pairing_coop -- the launch of run_pairing2, by construction.  Mode 1: the verdicts into status.
+// Mode 0: the easy-part values into out_f12, from the engine's value layout (value v = 2 * (power of w) + component, sixteen words
+// each; an item that was skipped keeps the sentinel) to tower order, fourteen limbs each.
+static int debug_pairing_coop(Ctx* c, int mode, const PairTables& t, const DebugStaged& s, size_t n, int32_t* status, int32_t* out_f12) {
+  if (mode == 1) {
+    launch_pairing_coop(c, n, s.pairs, s.status, t);
+    HIPCK(hipGetLastError());
+    return copy_out_and_sync(c, status, s.status, 4 * n);
+  }
+  uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
+  if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
+  HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
+  launch_pairing_coop(c, n, s.pairs, s.status, t, d_easy);
+  HIPCK(hipGetLastError());
+  std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
+  HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n; i++)
+    for (size_t k = 0; k < 6; k++) {
+      const size_t pw = k < 3 ? 2 * k : 2 * (k - 3) + 1;
+      for (size_t comp = 0; comp < 2; comp++)
+        for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * k + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
+    }
+  SYNC_FLUSH(c);
+  return 0;
+}
+
+// The chunk loop of the line-kernel hooks: `total` items in chunks of `chunk` (0: miller_chunk_items(), or all of them).  The line
+// workspace is filled with the sentinel byte before every chunk, launch(first, cnt, lanes) runs the chunk's line launch, and the
+// workspace is read back whole before the next one.  The chunk's output rows -- rows[(e * out_words + w) * lanes + t], word w = 14 *
+// (coefficient number) + limb, lane t = 2 * item + component -- go to `out` item after item; *stray counts the words written on lanes
+// beyond the chunk's items and behind the output rows.  two_pass: the lines3 rows of the two-pass forms lie behind them, where pass 1
+// writes the lanes of its live items, nothing for an item it skips and nothing beyond the chunk's items.
+template <class L>
+static int debug_line_chunks(Ctx* c, size_t total, size_t chunk, size_t out_words, bool two_pass, const int32_t* status, int32_t* out, uint64_t* stray, L&& launch) {
+  const size_t E = MILLER_ENTRIES;
+  const uint32_t sentinel = (uint32_t)BLSGPU_DEBUG_COOP_SENTINEL;
+  size_t per = chunk ? chunk : miller_chunk_items() ? miller_chunk_items() : total;
+  if (per > total) per = total;
+  const size_t ws_words = E * (LINE5_WORDS + LINE3_WORDS_H) * row_stride(lanes_for(per));
+  if (lines_reserve(c, ws_words * 4)) return fail(BLSGPU_E_HIP, "no room for the line workspace");
+  std::vector<uint32_t> rows(ws_words);                 // the whole workspace: the output rows, pass 1's lines3 rows, the rest
+  for (size_t first = 0; first < total; first += per) {
+    const size_t cnt = total - first < per ? total - first : per;
+    const size_t lanes = row_stride(lanes_for(cnt)), nrows = E * out_words;
+    HIPCK(hipMemsetAsync(c->lines_ws, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, ws_words * 4, c->stream));
+    launch(first, cnt, lanes);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(rows.data(), c->lines_ws, ws_words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    size_t at = nrows * lanes;
+    if (two_pass)
+      for (size_t r = 0; r < E * LINE3_WORDS_H; r++, at += lanes)
+        for (size_t t = 0; t < lanes; t++) {
+          const size_t j = t >> 1;
+          const bool live = j < cnt && status[first + j] == 0;      // (BLS_OK = 0: both kernels skip on a non-zero entry)
+          if (!live && rows[at + t] != sentinel) ++*stray;
+        }
+    for (; at < ws_words; at++)
+      if (rows[at] != sentinel) ++*stray;
+    for (size_t r = 0; r < nrows; r++) {
+      const uint32_t* row = rows.data() + r * lanes;
+      const size_t e = r / out_words, w = r % out_words, kk = w / FP_NL, l = w % FP_NL;
+      for (size_t j = 0; j < cnt; j++)
+        for (size_t comp = 0; comp < 2; comp++)
+          out[((((first + j) * E + e) * (out_words / FP_NL) + kk) * 2 + comp) * FP_NL + l] = (int32_t)row[2 * j + comp];
+      for (size_t t = 2 * cnt; t < lanes; t++)
+        if (row[t] != sentinel) ++*stray;
+    }
+  }
+  SYNC_FLUSH(c);
   return 0;
 }
 
@@ -979,11 +1133,12 @@ int launch_lines_and_post(Ctx* c, size_t n, uint32_t* d_rec, int32_t* d_status) 
 // one core_verify per item: statuses end up in d_status (device)
 int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_t* d_sigs, int fmt, const uint8_t* d_msgs,
                      const uint64_t* d_offs, int single_msg, const dst_arg& dst, size_t n, uint32_t* d_pairs, uint32_t* d_f,
-                     int32_t* d_status, int pre_status = 0, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
-  // key_table / key_of: the keys are entries of a registered set with line tables (run_pairing2); the two plans above
-  // BLSGPU_WIDE_MAX items pass them on
+                     int32_t* d_status, int pre_status = 0, const TabledG2& key = {}) {
+  // key: the keys are entries of a registered set with line tables (PairTables::key); the two plans above BLSGPU_WIDE_MAX items
+  // pass it on
   if (n == 0) return 0;
-  if (sg == 1 && aug == 0 && !pre_status && n <= wide_max_items() && n <= coop_max_items()) {
+  const PairPath path = pair_path(n);
+  if (sg == 1 && aug == 0 && !pre_status && path == PATH_ENGINE) {
     // Single verifications of Bls12381G1Impl without a key prefix, cut where the inputs allow (csrc/kernels.cuh k_pairing_pre /
     // k_pairing_post): this stream hashes the messages (row-wide field type) while the side stream checks keys and
     // signatures, derives every key's line coefficients and runs the Miller loop of the (signature, -g2) pair -- two
@@ -1018,7 +1173,7 @@ int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_
     HIPCK(hipGetLastError());
     return 0;
   }
-  if (sg == 2 && aug == 0 && !pre_status && (!single_msg || n == 1) && n <= wide_max_items() && n <= coop_max_items()) {
+  if (sg == 2 && aug == 0 && !pre_status && (!single_msg || n == 1) && path == PATH_ENGINE) {
     // The same cut for Bls12381G2Impl, pairs (key, H(m)) (-g1, signature): this stream carries the long chain -- the hash to G2
     // (row-wide maps, cofactor clearing on the engine), H(m)'s record and lines -- and is enqueued first; the side stream
     // checks keys and signatures and runs the signature's lines and Miller function; after the join the Miller function of
@@ -1059,7 +1214,7 @@ int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_
     HIPCK(hipGetLastError());
     return 0;
   }
-  if (sg == 1 && aug == 0 && !pre_status && n > wide_max_items() && n <= 1024 && n <= coop_max_items() && wide_max_items() > 0) {
+  if (sg == 1 && aug == 0 && !pre_status && path == PATH_ONE_WAVE && n <= 1024 && wide_max_items() > 0) {
     // 513 to 1,024 items (measured: 4.1 / 4.6 ms at 768 / 1,024 against 4.8 / 5.1; at 2,048 the two-lane hash wins): the wave-cooperative pairing, but with the one-wave row-wide hash (0.74 ms while every
     // message has a SIMD to itself, against 1.6 ms for the two-lane hash inside k_prepare) and the shared to-affine inversion after it
     uint8_t* d_hashes = (uint8_t*)arena_take(c, 144 * n);
@@ -1067,7 +1222,9 @@ int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_
     // the hashes stay uncleared (bit 1) and the fixed pair is (sig, -[c] g2) (table 2), as everywhere for this implementation
     KL(KID_HASH, k_hash_to_g1_wide<false>, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_msgs, d_offs, (single_msg & 1) | 2, dst, d_hashes, (uint32_t*)nullptr);
     KL(KID_PREPARE, k_prepare_hashed<1>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_pks, d_sigs, (const uint8_t*)d_hashes, d_pairs, d_status, fmt);
-    return run_pairing2(c, n, d_pairs, d_f, d_status, 2, nullptr, nullptr, key_table, key_of);
+    PairTables t = pairs_walked(2);
+    t.key = key;
+    return run_pairing2(c, n, d_pairs, d_f, d_status, t);
   }
   // two lanes per item (the two SSWU maps side by side, G2 point arithmetic on the lane-split tower) for both implementations
   // and every batch size (rounds 1-2 used one lane per item for full Bls12381G1Impl batches; see below)
@@ -1083,7 +1240,9 @@ int run_verify_items(Ctx* c, int sg, int aug, const uint8_t* d_pks, const uint8_
     KL(KID_PREPARE, k_prepare<1>, dim3(nb), dim3(BLS_BLOCK), n, d_pks, d_sigs, fmt, aug, d_msgs, d_offs, single_msg, dst, d_pairs, d_status, pre_status, two_lanes | 2);
   else
     KL(KID_PREPARE, k_prepare<2>, dim3(nb), dim3(BLS_BLOCK), n, d_pks, d_sigs, fmt, aug, d_msgs, d_offs, single_msg, dst, d_pairs, d_status, pre_status, two_lanes);
-  return run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, nullptr, nullptr, sg == 1 ? key_table : nullptr, key_of);
+  PairTables t = pairs_walked(sg == 1 ? 2 : 0);
+  if (sg == 1) t.key = key;
+  return run_pairing2(c, n, d_pairs, d_f, d_status, t);
 }
 
 // Pairing products, second form (round 3): the product over the items entry by entry, then one Horner chain (kernels.cuh
@@ -2404,7 +2563,7 @@ static int verify_one_tail(Ctx* c, int sig_group, int scheme, int aug_prefix, co
     with_group(sig_group, [&](auto G) {
       KL(KID_PREPARE, k_prepare_hashed<G()>, dim3(1), dim3(BLS_BLOCK), (size_t)1, d_pk_proj, (const uint8_t*)d_sig_proj, d_hash, d_pairs, d_status, 0);
     });
-    rc = run_pairing2(c, 1, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0);
+    rc = run_pairing2(c, 1, d_pairs, d_f, d_status, pairs_walked(sig_group == 1 ? 1 : 0));
   } else {
     rc = run_verify_items(c, sig_group, aug_prefix, d_pk_proj, d_sig_proj, BLSGPU_FMT_RAW_PROJ, (const uint8_t*)d_msg, d_offs, 1,
                           scheme_dst(sig_group, scheme), 1, d_pairs, d_f, d_status);
@@ -3848,8 +4007,8 @@ API_CATCH
 
 /* Self-test hook of the wave-cooperative pairing kernels on caller-supplied pairs (include/blsgpu.h).  pairs: n x twelve limb vectors
  * (P.x, P.y, Q.x.c0, Q.x.c1, Q.y.c0, Q.y.c1 of pair 0, then of pair 1; reduced form), written into a pair workspace in the layout
- * run_pairing2 reads: word w = 14 * vector + limb of item i at pairs_ws[w * n + i].  The kernels are launched exactly as
- * run_pairing2 / run_f12_product_verdict launch them. */
+ * run_pairing2 reads: word w = 14 * vector + limb of item i at pairs_ws[w * n + i].  Modes 0 and 1 go through
+ * launch_pairing_coop, the launch of run_pairing2 (debug_pairing_coop); mode 2 launches k_finalexp_coop as run_f12_product_verdict does. */
 int blsgpu_debug_coop_pairing(int mode, int fixed_g2, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
   if (!initialised()) return NOT_INIT();
   if (n == 0) return 0;
@@ -3861,42 +4020,13 @@ int blsgpu_debug_coop_pairing(int mode, int fixed_g2, const int32_t* in, size_t 
   int rc = arena_reserve(c, pad256(rec * 4 * n) + pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
-  std::vector<uint32_t> h(rec * n);
-  for (size_t i = 0; i < n; i++)
-    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
-  const void *d_in, *d_st;
-  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
-  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
-  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
-  uint32_t* d_ws = (uint32_t*)d_in;
-  int32_t* d_status = (int32_t*)d_st;
-  if (mode == 0) {
-    uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
-    if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
-    HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
-    KL(KID_PAIRING_COOP, k_pairing_coop_easy, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_ws, (const int32_t*)d_status, fixed_g2, d_easy);
-    HIPCK(hipGetLastError());
-    std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
-    HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    // the engine's value layout: value v = 2 * (power of w) + component, sixteen words each -> tower order, fourteen limbs each
-    for (size_t i = 0; i < n; i++)
-      for (size_t k = 0; k < 6; k++) {
-        const size_t pw = k < 3 ? 2 * k : 2 * (k - 3) + 1;
-        for (size_t comp = 0; comp < 2; comp++)
-          for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * k + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
-      }
-    SYNC_FLUSH(c);
-    return 0;
-  }
-  if (mode == 1) {
-    KL(KID_PAIRING_COOP, k_pairing_coop, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_ws, d_status, fixed_g2);
-  } else {                    // one launch per live item: the item's column is slot 0 of a workspace of stride n
-    for (size_t i = 0; i < n; i++)
-      if (status[i] == BLS_OK) KL(KID_FINALEXP_ONE, k_finalexp_coop, dim3(1), dim3(BLS_BLOCK), (const uint32_t*)(d_ws + i), n, d_status + i);
-  }
+  DebugStaged s;
+  if ((rc = debug_stage(c, in, rec, n, status, &s))) return rc;
+  if (mode != 2) return debug_pairing_coop(c, mode, pairs_walked(fixed_g2), s, n, status, out_f12);
+  for (size_t i = 0; i < n; i++)          // one launch per live item: the item's column is slot 0 of a workspace of stride n
+    if (status[i] == BLS_OK) KL(KID_FINALEXP_ONE, k_finalexp_coop, dim3(1), dim3(BLS_BLOCK), s.pairs + i, n, s.status + i);
   HIPCK(hipGetLastError());
-  return copy_out_and_sync(c, status, d_status, 4 * n);
+  return copy_out_and_sync(c, status, s.status, 4 * n);
 }
 API_CATCH
 
@@ -4038,7 +4168,7 @@ int blsgpu_core_verify_hashed(int sig_group, const void* pks, const void* sigs, 
   with_group(sig_group, [&](auto G) {
     KL(KID_PREPARE, k_prepare_hashed<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, (const uint8_t*)d_h, d_pairs, d_status, 0);
   });
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0))) return rc;
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, pairs_walked(sig_group == 1 ? 1 : 0)))) return rc;
   if ((rc = status_out_and_sync(c, status, d_status, n))) return rc;
   return 0;
 }
@@ -4143,7 +4273,7 @@ int sig_proof_entry(bool stamped, int sig_group, int scheme, const void* commitm
   });
   if (stamped && (timeout_ms >= 0 || d_dec))
     KL(KID_PROOF_TIMEOUT, k_proof_timeout, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint64_t*)d_ts, now_ms, timeout_ms, (const int32_t*)d_dec, d_status);
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sig_group == 1 ? 1 : 0))) return rc;
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, pairs_walked(sig_group == 1 ? 1 : 0)))) return rc;
   if ((rc = status_out_and_sync(c, status, d_status, n))) return rc;
   return 0;
 }
@@ -4270,7 +4400,7 @@ int blsgpu_pairing2_check_batch(const void* g1a, const void* g2a, const void* g1
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
   KL(KID_PAIRS_AFF, k_pairs2_to_affine, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d1a, (const uint8_t*)d2a, (const uint8_t*)d1b,
      (const uint8_t*)d2b, fmt, d_pairs, d_status);
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, 0))) return rc;
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, pairs_walked(0)))) return rc;
   KL(KID_PAIRS_AFF, k_status_to_flag, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_status);
   if ((rc = copy_out(c, is_one, d_status, 4 * n))) return rc;
   SYNC_FLUSH(c);
@@ -4705,7 +4835,7 @@ int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* u
     KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_pairs<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, (const uint8_t*)d_sh, (const uint8_t*)d_pk,
        (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_pairs, d_status);
   });
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, 0))) return rc;
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, pairs_walked(0)))) return rc;
   KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_status, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_status);
   HIPCK(hipGetLastError());
   return status_out_and_sync(c, status, d_status, n);
@@ -6070,9 +6200,7 @@ static int keyset_check(Ctx* c, const KeySet& k, const uint32_t* d_idx, size_t n
 // (so: signatures in G1) above the row-wide engine's range -- on the one-wave path (k_pairing_coop_keyed), or on the lane-split
 // path with its two-kernel Miller loop (k_lines2s_keyed).  At and below BLSGPU_WIDE_MAX items a call gains no read-back.
 static bool keyset_lines_wanted(const KeySet& k, size_t n) {
-  if (!k.lines || k.sig_group != 1) return false;
-  if (n > coop_max_items()) return miller_chunk_items() != 0;     // the lane-split path
-  return n > wide_max_items();                                     // one wave per item; the engine below that
+  return k.lines && k.sig_group == 1 && pair_path_reads_rows(n);
 }
 // ... and, after k_keyset_check with d_walk: the one word read back (as run_verify_shared_items reads k_group_lines' word) says
 // whether every named entry has rows; *table = the set's rows, or null: the call walks the keys
@@ -6316,14 +6444,15 @@ int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx
   // one key per item: the gather is a few hundred bytes against a pairing, so the keys go to the arena, in the signatures' format
   // (run_verify_items reads both with one)
   if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return rc;
-  const uint32_t* key_table = nullptr;
-  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_table))) return rc;
+  TabledG2 key;              // rows stay null: the call walks the keys
+  key.of = d_cidx;
+  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key.rows))) return rc;
   const size_t cnt_ = n;
   KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
   if (d_keys != d_aff)
     with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
   rc = run_verify_items(c, sig_group, scheme == BLSGPU_SCHEME_AUG, d_keys, (const uint8_t*)d_sigs, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, 0,
-                        scheme_dst(sig_group, scheme), n, d_pairs, d_f, d_status, 0, key_table, d_cidx);
+                        scheme_dst(sig_group, scheme), n, d_pairs, d_f, d_status, 0, key);
   if (rc) return rc;
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   HIPCK(hipGetLastError());
@@ -6408,6 +6537,19 @@ int blsgpu_aggregate_verify_indexed_batch(int scheme, uint64_t keyset, const uin
 }
 API_CATCH
 
+// The row builder (k_group_lines): the Miller-loop rows of m affine G2 points into d_table (SHARED_TABLE_WORDS per point; d_scratch as
+// large, d_flags m + 1 words), and one word back to the host, *h_any (pinned, or the caller's own word): *usable = every point has
+// rows -- the identity and a point whose walk meets h = 0 have none.  One launch, one synchronisation.
+static int build_rows(Ctx* c, size_t m, const uint8_t* d_aff, uint32_t* d_table, uint32_t* d_scratch, int32_t* d_flags, int32_t* h_any, bool* usable) {
+  HIPCK(hipMemsetAsync(d_flags + m, 0, 4, c->stream));
+  KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(2 * m)), dim3(BLS_BLOCK), m, d_aff, d_table, d_scratch, d_flags);
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(h_any, d_flags + m, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));
+  *usable = *h_any == 0;
+  return 0;
+}
+
 // ---- shared-message verify (verify_shared.cuh): Signature::verify for items that come in groups under one message each
 // What a call needs beyond its inputs, statuses and pair / Fp12 workspaces, decided from its shape alone (never from a result).
 struct shared_plan {
@@ -6440,7 +6582,7 @@ static void shared_make_plan(shared_plan& p, int sg, int scheme, size_t n, size_
   p.table_bytes = n_groups * (size_t)SHARED_TABLE_WORDS * 4;
   const long knob = knobs().shared_lines_min;
   const bool wanted = knob < 0 ? n >= SHARED_LINES_AUTO_ITEMS && n / n_groups >= SHARED_LINES_AUTO_MIN : knob > 0 && n / n_groups >= (size_t)knob;
-  p.table = sg == 2 && wanted && n > coop_max_items() && miller_chunk_items() != 0 && p.table_bytes <= 0xffffffffull;
+  p.table = sg == 2 && wanted && pair_path(n) == PATH_LANE_SPLIT && lane_split_chunked() && p.table_bytes <= 0xffffffffull;
   if (p.table) p.ws_bytes += 2 * pad256(p.table_bytes) + pad256(4 * (n_groups + 1)) + pad256(4 * n);
 }
 // statuses of the n items into d_status (device).  Launch sequence, Basic and ProofOfPossession: the groups' hashes
@@ -6448,8 +6590,8 @@ static void shared_make_plan(shared_plan& p, int sg, int scheme, size_t n, size_
 // run_pairing2 (fixed_g2 = 2 for Bls12381G1Impl; two general pairs, or the groups' tables, for Bls12381G2Impl).
 static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan& p, size_t n, size_t n_groups, const uint8_t* d_pks, const uint8_t* d_sigs,
                                    int fmt, const uint64_t* d_ioffs, const uint8_t* d_msgs, const uint64_t* d_moffs, uint32_t* d_pairs, uint32_t* d_f,
-                                   int32_t* d_status, const uint32_t* key_table = nullptr, const uint32_t* key_of = nullptr) {
-  // key_table / key_of (Bls12381G1Impl over a registered set with line tables): passed on to run_pairing2, all three schemes
+                                   int32_t* d_status, const TabledG2& key = {}) {
+  // key (Bls12381G1Impl over a registered set with line tables): passed on to run_pairing2 as PairTables::key, all three schemes
   int rc;
   const dst_arg dst = scheme_dst(sg, scheme);
   if (p.aug) {
@@ -6459,7 +6601,7 @@ static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan
     if (!d_xmsgs) return fail(BLSGPU_E_HIP, "internal: arena too small");
     if (p.x_total)
       KL(KID_PREPARE_SHARED, k_shared_expand, dim3(blocks_for(p.x_total)), dim3(BLS_BLOCK), p.x_total, d_xoffs, n, d_ioffs, n_groups, d_moffs, d_msgs, d_xmsgs);
-    rc = run_verify_items(c, sg, 1, d_pks, d_sigs, fmt, d_xmsgs, d_xoffs, 0, dst, n, d_pairs, d_f, d_status, 0, key_table, key_of);
+    rc = run_verify_items(c, sg, 1, d_pks, d_sigs, fmt, d_xmsgs, d_xoffs, 0, dst, n, d_pairs, d_f, d_status, 0, key);
     if (rc) (void)hipStreamSynchronize(c->stream);      // the upload above reads p.x_offs
     return rc;
   }
@@ -6485,19 +6627,20 @@ static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan
     // call then takes the general form for every item -- one word read back decides it before the records are written
     int32_t* h_any = (int32_t*)hsmall_take(c, 4);
     if (!h_any) return fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted");
-    HIPCK(hipMemsetAsync(d_flags + n_groups, 0, 4, c->stream));
-    KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(2 * n_groups)), dim3(BLS_BLOCK), n_groups, (const uint8_t*)d_aff, d_table, d_scratch, d_flags);
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(h_any, d_flags + n_groups, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    table = *h_any == 0;
+    if ((rc = build_rows(c, n_groups, d_aff, d_table, d_scratch, d_flags, h_any, &table))) return rc;
   }
   with_group(sg, [&](auto G) {
     KL(KID_PREPARE_SHARED, k_prepare_shared<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, d_pks, d_sigs, fmt, (const uint8_t*)d_aff, d_pairs,
        d_status, table ? 1 : 0, table ? d_group : (uint32_t*)nullptr);
   });
   HIPCK(hipGetLastError());
-  return run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, table ? d_table : nullptr, table ? d_group : nullptr, sg == 1 ? key_table : nullptr, key_of);
+  PairTables t = pairs_walked(sg == 1 ? 2 : 0);
+  if (sg == 1) t.key = key;
+  if (table) {               // (only on the lane-split path: shared_make_plan) the records carry the signature's pair first
+    t.shared.rows = d_table;
+    t.shared.of = d_group;
+  }
+  return run_pairing2(c, n, d_pairs, d_f, d_status, t);
 }
 // the offsets of a shared-message call, read and checked; n = the item count
 static int shared_read_offsets(const uint64_t* item_offsets, const uint64_t* msg_offsets, size_t n_groups, std::vector<uint64_t>& ioffs,
@@ -6599,14 +6742,15 @@ int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32
     return r;
   };
   if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
-  const uint32_t* key_table = nullptr;
-  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_table))) return drain(rc);
+  TabledG2 key;
+  key.of = d_cidx;
+  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key.rows))) return drain(rc);
   const size_t cnt_ = n;
   KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
   if (d_keys != d_aff)
     with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
   rc = run_verify_shared_items(c, sig_group, scheme, plan, n, n_groups, d_keys, (const uint8_t*)d_sigs, fmt, d_ioffs, (const uint8_t*)d_msgs, d_moffs, d_pairs, d_f,
-                               d_status, key_table, d_cidx);
+                               d_status, key);
   if (rc) return drain(rc);
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
@@ -6650,8 +6794,7 @@ int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, con
   // plan T2, from the shape alone (the knob prices the 2 n_ct walks of the row builder against the two walks a share saves)
   const size_t t2_bytes = 2 * n_ct * (size_t)SHARED_TABLE_WORDS * 4;
   const long knob = knobs().signcrypt_lines_min;
-  const bool above_wide = n > coop_max_items() ? miller_chunk_items() != 0 : n > wide_max_items();
-  const bool t2_plan = sig_group == 2 && knob > 0 && n / n_ct >= (size_t)knob && above_wide && t2_bytes <= 0xffffffffull;
+  const bool t2_plan = sig_group == 2 && knob > 0 && n / n_ct >= (size_t)knob && pair_path_reads_rows(n) && t2_bytes <= 0xffffffffull;
   const size_t t2_ws = t2_plan ? pad256(2 * 192 * n_ct) + 2 * pad256(t2_bytes) + pad256(4 * (2 * n_ct + 1)) + pad256(8 * n) : 0;
   if ((rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(ub) + pad256(wb) + pad256(total) + pad256(shb) +
                                  3 * pad256(8 * (n_ct + 1)) + pad256(mtotal) + pad256(wtb) + pad256(768 * n_ct) + pad256(4 * n) +
@@ -6693,8 +6836,9 @@ int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, con
   }
   if (!mem.ok) return drain(fail(BLSGPU_E_HIP, "internal: arena too small"));
   if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
-  const uint32_t* key_rows = nullptr;              // plan ROWS: a named finite entry without rows makes every share walk
-  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_rows))) return drain(rc);
+  TabledG2 key;                                    // plan ROWS: a named finite entry without rows makes every share walk
+  key.of = d_cidx;
+  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key.rows))) return drain(rc);
   const size_t cnt_ = n;
   KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
   if (d_keys != d_aff)
@@ -6712,24 +6856,25 @@ int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, con
     int32_t* h_any = (int32_t*)hsmall_take(c, 4);
     if (!h_any) return drain(fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted"));
     KL(KID_SIGNCRYPT_GATHER, k_signcrypt_ct_affine, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_caff);
-    HIPCK(hipMemsetAsync(d_flags + 2 * n_ct, 0, 4, c->stream));
-    KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(4 * n_ct)), dim3(BLS_BLOCK), 2 * n_ct, (const uint8_t*)d_caff, d_table, d_scratch, d_flags);
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(h_any, d_flags + 2 * n_ct, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    t2 = *h_any == 0;
+    if ((rc = build_rows(c, 2 * n_ct, d_caff, d_table, d_scratch, d_flags, h_any, &t2))) return drain(rc);
     if (t2) KL(KID_SIGNCRYPT_GATHER, k_signcrypt_tab_of, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, d_tof, d_tof + n);
   }
   with_group(sig_group, [&](auto G) {
     KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_pairs<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, (const uint8_t*)d_sh, (const uint8_t*)d_keys,
        (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_pairs, d_status);
   });
-  const bool one_wave = n <= coop_max_items();
-  if (key_rows && one_wave)
+  PairTables t;
+  if (key.rows && pair_path(n) == PATH_LANE_SPLIT) {
+    t.shared = key;           // the records as written: the share's pair first, the key's rows as the groups' table
+  } else if (key.rows) {      // plan ROWS on the one-wave path: the key's pair first, its rows as a message set's
     KL(KID_SIGNCRYPT_GATHER, k_signcrypt_swap_pairs, dim3(blocks_for(n * (size_t)WS_PAIR1_WORDS)), dim3(BLS_BLOCK), n, d_pairs);
-  rc = run_pairing2(c, n, d_pairs, d_f, d_status, 0, one_wave ? nullptr : key_rows, d_cidx, nullptr, nullptr, one_wave ? key_rows : nullptr, d_cidx,
-                    t2 ? d_table : nullptr, d_tof);
-  if (rc) return drain(rc);
+    t.msg = key;
+  }
+  if (t2) {
+    t.both.rows = d_table;
+    t.both.of = d_tof;
+  }
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, t))) return drain(rc);
   KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_status, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_status);
   KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
   if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
@@ -6738,8 +6883,8 @@ int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, con
 API_CATCH
 
 /* Self-test hook of k_pairing_coop_keyed (include/blsgpu.h): the records of blsgpu_debug_coop_pairing with fixed_g2 = 2, pair 0's G2
- * member being entry idx[i] of a set with line tables.  The kernel is launched exactly as run_pairing2 launches it (mode 1), or with
- * the export of the easy-part value (mode 0). */
+ * member being entry idx[i] of a set with line tables.  The kernel goes through run_pairing2's launcher (debug_pairing_coop): mode 1 the
+ * verdict, mode 0 the export of the easy-part value. */
 int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* idx, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
   KeySet k;
   int rc = set_find(keyset, k);
@@ -6752,42 +6897,14 @@ int blsgpu_debug_coop_pairing_keyed(int mode, uint64_t keyset, const uint32_t* i
   for (size_t i = 0; i < n; i++)
     if ((uint64_t)idx[i] >= (uint64_t)k.n) return fail(BLSGPU_E_ARG, "index outside the key set");
   CTX_ACQUIRE_ON(c, k.devidx);
-  const size_t rec = WS_PAIRS_WORDS;
-  if ((rc = arena_reserve(c, pad256(rec * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096))) return rc;
+  if ((rc = arena_reserve(c, pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096))) return rc;
   c->arena_off = 0;
-  std::vector<uint32_t> h(rec * n);
-  for (size_t i = 0; i < n; i++)
-    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
-  const void *d_in, *d_st, *d_idx;
-  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
-  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
-  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
-  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
-  int32_t* d_status = (int32_t*)d_st;
-  if (mode == 1) {
-    KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)k.lines,
-       (const uint32_t*)d_idx, (uint32_t*)nullptr);
-    HIPCK(hipGetLastError());
-    return copy_out_and_sync(c, status, d_status, 4 * n);
-  }
-  uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
-  if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
-  KL(KID_PAIRING_COOP_KEYED, k_pairing_coop_keyed, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)k.lines,
-     (const uint32_t*)d_idx, d_easy);
-  HIPCK(hipGetLastError());
-  std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
-  HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(hipStreamSynchronize(c->stream));
-  // the engine's value layout -> tower order, fourteen limbs each, as blsgpu_debug_coop_pairing
-  for (size_t i = 0; i < n; i++)
-    for (size_t kk = 0; kk < 6; kk++) {
-      const size_t pw = kk < 3 ? 2 * kk : 2 * (kk - 3) + 1;
-      for (size_t comp = 0; comp < 2; comp++)
-        for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * kk + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
-    }
-  SYNC_FLUSH(c);
-  return 0;
+  DebugStaged s;
+  if ((rc = debug_stage(c, in, WS_PAIRS_WORDS, n, status, &s, idx, n))) return rc;
+  PairTables t = pairs_walked(2);
+  t.key.rows = k.lines;
+  t.key.of = s.of;
+  return debug_pairing_coop(c, mode, t, s, n, status, out_f12);
 }
 API_CATCH
 
@@ -6823,17 +6940,10 @@ int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, 
   int rc = arena_reserve(c, pad256(rec * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WS_F_WORDS * 4 * n) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
-  std::vector<uint32_t> h(rec * n);
-  for (size_t i = 0; i < n; i++)
-    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)items[i * rec + w];
-  const void *d_in, *d_st, *d_idx = nullptr;
-  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
-  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
-  if (keyed && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
-  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
-  const uint32_t* d_pairs = (const uint32_t*)d_in;
-  const int32_t* d_status = (const int32_t*)d_st;
-  const uint32_t sentinel = (uint32_t)BLSGPU_DEBUG_COOP_SENTINEL;
+  DebugStaged s;
+  if ((rc = debug_stage(c, items, rec, n, status, &s, keyed ? idx : nullptr, n))) return rc;
+  const uint32_t *d_pairs = s.pairs, *d_idx = s.of;
+  const int32_t* d_status = s.status;
   *stray = 0;
   if (kernel == BLSGPU_LINES_MILLER2S) {              // the one-kernel loop run_pairing2 falls back to
     uint32_t* d_f = (uint32_t*)arena_take(c, (size_t)WS_F_WORDS * 4 * n);
@@ -6852,31 +6962,21 @@ int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, 
   // the items a chunk covers (virtual items for the two-pass product form, which is one chunk: item v pairs with item v + half)
   const size_t half = (n + 1) / 2;
   const size_t total = kernel == BLSGPU_LINES_P12 ? half : kernel == BLSGPU_LINES_FIXED ? 1 : n;
-  size_t per = chunk ? chunk : miller_chunk_items() ? miller_chunk_items() : total;
-  if (per > total || kernel == BLSGPU_LINES_P12 || kernel == BLSGPU_LINES_FIXED) per = total;
+  const bool one_chunk = kernel == BLSGPU_LINES_P12 || kernel == BLSGPU_LINES_FIXED;
   const bool five = kernel == BLSGPU_LINES_2S || kernel == BLSGPU_LINES_2S_KEYED || kernel == BLSGPU_LINES_P12;
-  const size_t out_words = five ? LINE5_WORDS : LINE3_WORDS_H;        // per lane and entry
-  const size_t lanes_max = row_stride(lanes_for(per));
-  const size_t ws_words = E * (LINE5_WORDS + LINE3_WORDS_H) * lanes_max;
-  if (lines_reserve(c, ws_words * 4)) return fail(BLSGPU_E_HIP, "no room for the line workspace");
-  std::vector<uint32_t> rows;
-  for (size_t first = 0; first < total; first += per) {
-    const size_t cnt = total - first < per ? total - first : per;
-    const size_t nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
+  const bool two_pass = (kernel == BLSGPU_LINES_2S && variant == 0) || kernel == BLSGPU_LINES_P12;
+  PairTables t = pairs_walked(kernel == BLSGPU_LINES_2S_KEYED ? 2 : variant);      // BLSGPU_LINES_2S: variant = fixed_g2 (0: two passes)
+  if (kernel == BLSGPU_LINES_2S_KEYED) {
+    t.key.rows = k.lines;
+    t.key.of = d_idx;
+  }
+  return debug_line_chunks(c, total, one_chunk ? total : chunk, five ? LINE5_WORDS : LINE3_WORDS_H, two_pass, status, out, stray, [&](size_t first, size_t cnt, size_t lanes) {
+    const dim3 grid((unsigned)(lanes_for(cnt) / BLS_BLOCK)), block(BLS_BLOCK);
     uint32_t* lines3 = c->lines_ws + E * LINE5_WORDS * lanes;
-    const dim3 grid((unsigned)(nlanes / BLS_BLOCK)), block(BLS_BLOCK);
-    HIPCK(hipMemsetAsync(c->lines_ws, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, ws_words * 4, c->stream));
     switch (kernel) {
       case BLSGPU_LINES_2S:
-        if (variant) {
-          KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, variant, 0);
-        } else {
-          KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, 0, 1);
-          KL(KID_LINES, k_lines2s, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lines3, lanes, 0, 2);
-        }
-        break;
       case BLSGPU_LINES_2S_KEYED:
-        KL(KID_LINES_KEYED, k_lines2s_keyed, grid, block, n, first, cnt, d_pairs, d_status, c->lines_ws, lanes, (const uint32_t*)k.lines, (const uint32_t*)d_idx);
+        launch_lines2s(c, n, first, cnt, d_pairs, d_status, t, lanes);
         break;
       case BLSGPU_LINES_P1:
         KL(KID_LINESP, k_linesp, grid, block, cnt, cnt, n, d_pairs + first, d_status + first, c->lines_ws, c->lines_ws, lanes, (size_t)0, cnt, 1);
@@ -6892,51 +6992,18 @@ int blsgpu_debug_lines(int kernel, int variant, const int32_t* items, size_t n, 
         KL(KID_TAIL, k_lines_fixed, dim3(1), block, n, d_pairs, d_status, c->lines_ws, lanes, variant);
         break;
       default:   // BLSGPU_LINES_P_KEYED
-        KL(KID_LINESP_KEYED, k_linesp_keyed, grid, block, t_b, first, cnt, n, d_pairs, d_status, c->lines_ws, lanes, (const uint32_t*)k.lines, (const uint32_t*)d_idx);
+        KL(KID_LINESP_KEYED, k_linesp_keyed, grid, block, t_b, first, cnt, n, d_pairs, d_status, c->lines_ws, lanes, (const uint32_t*)k.lines, d_idx);
         break;
     }
-    HIPCK(hipGetLastError());
-    const size_t nrows = E * out_words;
-    rows.resize(ws_words);                              // the whole workspace: the output rows, pass 1's lines3 rows, the rest
-    HIPCK(hipMemcpyAsync(rows.data(), c->lines_ws, ws_words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    {
-      // behind the output rows: the lines3 rows of the two-pass forms (pass 1 writes the lanes of its live items there, nothing for
-      // an item it skips and nothing beyond the chunk's items), then words no launch may touch; for every other kernel all of it
-      const bool two_pass = (kernel == BLSGPU_LINES_2S && variant == 0) || kernel == BLSGPU_LINES_P12;
-      size_t at = nrows * lanes;
-      if (two_pass) {
-        for (size_t r = 0; r < E * LINE3_WORDS_H; r++, at += lanes)
-          for (size_t t = 0; t < lanes; t++) {
-            const size_t j = t >> 1;
-            const bool live = j < cnt && status[first + j] == 0;      // (BLS_OK = 0: both kernels skip on a non-zero entry)
-            if (!live && rows[at + t] != sentinel) ++*stray;
-          }
-      }
-      for (; at < ws_words; at++)
-        if (rows[at] != sentinel) ++*stray;
-    }
-    // rows[(e * out_words + w) * lanes + t]: word w = 14 * (coefficient number) + limb, lane t = 2 * item + component
-    for (size_t r = 0; r < nrows; r++) {
-      const uint32_t* row = rows.data() + r * lanes;
-      const size_t e = r / out_words, w = r % out_words, kk = w / FP_NL, l = w % FP_NL;
-      for (size_t j = 0; j < cnt; j++)
-        for (size_t comp = 0; comp < 2; comp++)
-          out[((((first + j) * E + e) * (out_words / FP_NL) + kk) * 2 + comp) * FP_NL + l] = (int32_t)row[2 * j + comp];
-      for (size_t t = 2 * cnt; t < lanes; t++)
-        if (row[t] != sentinel) ++*stray;
-    }
-  }
-  SYNC_FLUSH(c);
-  return 0;
+  });
 }
 API_CATCH
 
 /* Self-test hook of the two kernels that read BOTH pairs' rows from one table in global memory (include/blsgpu.h): the m affine G2
  * points become a table through the row builder (k_group_lines), and item i's pairs are (P0, entry t0[i]), (P1, entry t1[i]) -- the
- * records of blsgpu_debug_coop_pairing, whose Q members are not read.  Modes 0 and 1: k_pairing_coop_tables2 as run_pairing2 launches
- * it, with the easy-part export / the verdict, as blsgpu_debug_coop_pairing_keyed.  Mode 2: k_lines2s_tables2 chunk after chunk, the
- * line5 entries and *stray as BLSGPU_LINES_2S_KEYED of blsgpu_debug_lines. */
+ * records of blsgpu_debug_coop_pairing, whose Q members are not read.  Modes 0 and 1: k_pairing_coop_tables2 through run_pairing2's
+ * launcher, with the easy-part export / the verdict, as blsgpu_debug_coop_pairing_keyed.  Mode 2: k_lines2s_tables2 chunk after chunk
+ * through launch_lines2s, the line5 entries and *stray as BLSGPU_LINES_2S_KEYED of blsgpu_debug_lines (debug_line_chunks). */
 int blsgpu_debug_tables2(int mode, const void* points, size_t m, const uint32_t* t0, const uint32_t* t1, const int32_t* in, size_t n, int32_t* status, size_t chunk,
                          int32_t* out, uint64_t* stray) try {
   if (!initialised()) return NOT_INIT();
@@ -6947,92 +7014,36 @@ int blsgpu_debug_tables2(int mode, const void* points, size_t m, const uint32_t*
   for (size_t i = 0; i < n; i++)
     if ((uint64_t)t0[i] >= (uint64_t)m || (uint64_t)t1[i] >= (uint64_t)m) return fail(BLSGPU_E_ARG, "index outside the table");
   CTX_ACQUIRE(c);
-  const size_t rec = WS_PAIRS_WORDS, E = MILLER_ENTRIES, tb = m * (size_t)SHARED_TABLE_WORDS * 4;
+  const size_t rec = WS_PAIRS_WORDS, tb = m * (size_t)SHARED_TABLE_WORDS * 4;
   int rc = arena_reserve(c, pad256(192 * m) + 2 * pad256(tb) + pad256(4 * (m + 1)) + pad256(rec * 4 * n) + 2 * pad256(8 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 8192);
   if (rc) return rc;
   c->arena_off = 0;
-  std::vector<uint32_t> h(rec * n), tt(2 * n);
+  std::vector<uint32_t> tt(2 * n);
   for (size_t i = 0; i < n; i++) {
-    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
     tt[i] = t0[i];
     tt[n + i] = t1[i];
   }
-  const void *d_pts, *d_in, *d_st, *d_tt;
+  const void* d_pts;
   if ((rc = stage_in(c, points, 192 * m, &d_pts))) return rc;
-  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
-  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
-  if ((rc = stage_in(c, tt.data(), 8 * n, &d_tt))) return rc;
   Carver mem{c};
   uint32_t* d_table = mem.take<uint32_t>(tb);
   uint32_t* d_scratch = mem.take<uint32_t>(tb);
   int32_t* d_flags = mem.take<int32_t>(4 * (m + 1));
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemsetAsync(d_flags + m, 0, 4, c->stream));
-  KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(2 * m)), dim3(BLS_BLOCK), m, (const uint8_t*)d_pts, d_table, d_scratch, d_flags);
-  HIPCK(hipGetLastError());
   int32_t any = 0;
-  HIPCK(hipMemcpyAsync(&any, d_flags + m, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(hipStreamSynchronize(c->stream));             // h and tt leave scope after the call; pageable memory
-  if (any) return fail(BLSGPU_E_ARG, "a point has no usable rows");
-  const uint32_t *d_pairs = (const uint32_t*)d_in, *d_t0 = (const uint32_t*)d_tt, *d_t1 = d_t0 + n;
-  int32_t* d_status = (int32_t*)d_st;
-  if (mode == 1) {
-    KL(KID_PAIRING_COOP_TABLES2, k_pairing_coop_tables2, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, (const uint32_t*)d_table, d_t0, d_t1, (uint32_t*)nullptr);
-    HIPCK(hipGetLastError());
-    return copy_out_and_sync(c, status, d_status, 4 * n);
-  }
-  if (mode == 0) {
-    uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
-    if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
-    HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
-    KL(KID_PAIRING_COOP_TABLES2, k_pairing_coop_tables2, dim3((unsigned)n), dim3(BLS_BLOCK), n, d_pairs, d_status, (const uint32_t*)d_table, d_t0, d_t1, d_easy);
-    HIPCK(hipGetLastError());
-    std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
-    HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    // the engine's value layout -> tower order, fourteen limbs each, as blsgpu_debug_coop_pairing
-    for (size_t i = 0; i < n; i++)
-      for (size_t kk = 0; kk < 6; kk++) {
-        const size_t pw = kk < 3 ? 2 * kk : 2 * (kk - 3) + 1;
-        for (size_t comp = 0; comp < 2; comp++)
-          for (size_t l = 0; l < FP_NL; l++) out[i * WS_F_WORDS + (2 * kk + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
-      }
-    SYNC_FLUSH(c);
-    return 0;
-  }
-  // mode 2: the line kernel, the chunk loop and the stray count of blsgpu_debug_lines
-  const uint32_t sentinel = (uint32_t)BLSGPU_DEBUG_COOP_SENTINEL;
+  bool usable = false;
+  if ((rc = build_rows(c, m, (const uint8_t*)d_pts, d_table, d_scratch, d_flags, &any, &usable))) return rc;
+  if (!usable) return fail(BLSGPU_E_ARG, "a point has no usable rows");
+  DebugStaged s;
+  if ((rc = debug_stage(c, in, WS_PAIRS_WORDS, n, status, &s, tt.data(), 2 * n))) return rc;
+  PairTables t;
+  t.both.rows = d_table;
+  t.both.of = s.of;
+  if (mode != 2) return debug_pairing_coop(c, mode, t, s, n, status, out);
+  // mode 2: the line kernel through the chunk loop and the stray count of blsgpu_debug_lines
   *stray = 0;
-  size_t per = chunk ? chunk : miller_chunk_items() ? miller_chunk_items() : n;
-  if (per > n) per = n;
-  const size_t lanes_max = row_stride(lanes_for(per));
-  const size_t ws_words = E * (LINE5_WORDS + LINE3_WORDS_H) * lanes_max;       // (the tail: words no launch may touch)
-  if (lines_reserve(c, ws_words * 4)) return fail(BLSGPU_E_HIP, "no room for the line workspace");
-  std::vector<uint32_t> rows;
-  for (size_t first = 0; first < n; first += per) {
-    const size_t cnt = n - first < per ? n - first : per;
-    const size_t nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
-    HIPCK(hipMemsetAsync(c->lines_ws, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, ws_words * 4, c->stream));
-    KL(KID_LINES_TABLES2, k_lines2s_tables2, dim3((unsigned)(nlanes / BLS_BLOCK)), dim3(BLS_BLOCK), n, first, cnt, d_pairs, (const int32_t*)d_status, c->lines_ws, lanes,
-       (const uint32_t*)d_table, d_t0, d_t1);
-    HIPCK(hipGetLastError());
-    const size_t nrows = E * LINE5_WORDS;
-    rows.resize(ws_words);
-    HIPCK(hipMemcpyAsync(rows.data(), c->lines_ws, ws_words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    for (size_t at = nrows * lanes; at < ws_words; at++)
-      if (rows[at] != sentinel) ++*stray;
-    for (size_t r = 0; r < nrows; r++) {
-      const uint32_t* row = rows.data() + r * lanes;
-      const size_t e = r / LINE5_WORDS, w = r % LINE5_WORDS, kk = w / FP_NL, l = w % FP_NL;
-      for (size_t j = 0; j < cnt; j++)
-        for (size_t comp = 0; comp < 2; comp++) out[((((first + j) * E + e) * 5 + kk) * 2 + comp) * FP_NL + l] = (int32_t)row[2 * j + comp];
-      for (size_t t = 2 * cnt; t < lanes; t++)
-        if (row[t] != sentinel) ++*stray;
-    }
-  }
-  SYNC_FLUSH(c);
-  return 0;
+  return debug_line_chunks(c, n, chunk, LINE5_WORDS, false, status, out, stray,
+                           [&](size_t first, size_t cnt, size_t lanes) { launch_lines2s(c, n, first, cnt, s.pairs, s.status, t, lanes); });
 }
 API_CATCH
 // =========================================================================================================
@@ -7222,8 +7233,7 @@ static int msgset_verify(uint64_t msgset, const uint32_t* msg_idx, bool indexed,
   if (!msg_idx || !sigs || !status || (indexed ? !idx : !pks)) return fail(BLSGPU_E_ARG, "null argument");
   // the plan, from the call's shape alone: the row-wide engine reads no rows; the one-wave path reads them in k_pairing_coop_rows, the
   // lane-split path in k_lines2s_shared (BLSGPU_SHARED_LINES_MIN prices a build that has already happened: it does not apply)
-  const bool engine = n <= wide_max_items() && n <= coop_max_items(), coop = !engine && n <= coop_max_items();
-  const bool rows_wanted = m.lines && sg == 2 && !engine && (coop || miller_chunk_items() != 0);
+  const bool rows_wanted = m.lines && sg == 2 && pair_path_reads_rows(n);
   const size_t asz = point_bytes(sg, BLSGPU_FMT_RAW_AFFINE), psz = pk_size(sg, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sg, fmt), sgb = sig_size(sg, fmt) * n;
   if ((rc = arena_reserve(c, 4 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(8 * (n_groups + 1)) +
                                  2 * pad256(4 * n_groups) + pad256(asz * n_groups) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 512 + 8192)))
@@ -7275,26 +7285,32 @@ static int msgset_verify(uint64_t msgset, const uint32_t* msg_idx, bool indexed,
   }
   KL(KID_KEYSET_GATHER, k_keyset_gather, dim3(blocks_for(n_groups * (asz / 4))), dim3(BLS_BLOCK), n_groups, asz / 4, (const uint32_t*)d_cmsg, (const uint32_t*)m.aff,
      0, (uint32_t*)d_haff);
-  const uint32_t* key_table = nullptr;
+  PairTables t = pairs_walked(sg == 1 ? 2 : 0);
   if (indexed) {
     if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
-    if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key_table))) return drain(rc);
+    if (sg == 1) {            // (d_walk is set for such a set only: keyset_lines_wanted)
+      t.key.of = d_cidx;
+      if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &t.key.rows))) return drain(rc);
+    }
     const size_t cnt_ = n;
     KEYSET_GATHER(psz / 4, k.aff, 0, d_kaff);
     if (d_keys != d_kaff)
       with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_kaff, d_keys); });
     d_pks = d_keys;
   }
-  const bool split_rows = rows && !coop;        // the table form of the line kernel: the signature's pair first
+  const bool split_rows = rows && pair_path(n) == PATH_LANE_SPLIT;        // the table form of the line kernel: the signature's pair first
   with_group(sg, [&](auto G) {
     KL(KID_PREPARE_SHARED, k_prepare_shared<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, fmt,
        (const uint8_t*)d_haff, d_pairs, d_status, split_rows ? 1 : 0, d_group);
   });
   KL(KID_MSGSET_CHECK, k_msgset_mark, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_group, (const uint32_t*)d_cmsg, d_status, d_msg_of);
   if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, sg == 1 ? 2 : 0, split_rows ? rows : nullptr, split_rows ? d_msg_of : nullptr,
-                         sg == 1 ? key_table : nullptr, d_cidx, rows && coop ? rows : nullptr, d_msg_of)))
-    return drain(rc);
+  if (rows) {
+    TabledG2& role = split_rows ? t.shared : t.msg;
+    role.rows = rows;
+    role.of = d_msg_of;
+  }
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, t))) return drain(rc);
   if (indexed) {
     KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
     KL(KID_MSGSET_CHECK, k_msgset_mark, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_group, (const uint32_t*)d_cmsg, d_status, (uint32_t*)nullptr);
@@ -7541,8 +7557,8 @@ int blsgpu_aggregate_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t
 API_CATCH
 
 /* Self-test hook of k_pairing_coop_rows (include/blsgpu.h): the records of blsgpu_debug_coop_pairing with fixed_g2 = 0, pair 0's G2
- * member being entry msg_of[i] of a set with rows.  The kernel is launched exactly as run_pairing2 launches it (mode 1), or with the
- * export of the easy-part value (mode 0). */
+ * member being entry msg_of[i] of a set with rows.  The kernel goes through run_pairing2's launcher (debug_pairing_coop): mode 1 the verdict,
+ * mode 0 the export of the easy-part value. */
 int blsgpu_debug_coop_pairing_rows(int mode, uint64_t msgset, const uint32_t* msg_of, const int32_t* in, size_t n, int32_t* status, int32_t* out_f12) try {
   MsgSet m;
   int rc = set_find(msgset, m);
@@ -7555,42 +7571,14 @@ int blsgpu_debug_coop_pairing_rows(int mode, uint64_t msgset, const uint32_t* ms
   for (size_t i = 0; i < n; i++)
     if ((uint64_t)msg_of[i] >= (uint64_t)m.n) return fail(BLSGPU_E_ARG, "index outside the message set");
   CTX_ACQUIRE_ON(c, m.devidx);
-  const size_t rec = WS_PAIRS_WORDS;
-  if ((rc = arena_reserve(c, pad256(rec * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096))) return rc;
+  if ((rc = arena_reserve(c, pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 2 * pad256(4 * n) + pad256((size_t)WIDE_EASY_WORDS * 4 * n) + 4096))) return rc;
   c->arena_off = 0;
-  std::vector<uint32_t> h(rec * n);
-  for (size_t i = 0; i < n; i++)
-    for (size_t w = 0; w < rec; w++) h[w * n + i] = (uint32_t)in[i * rec + w];
-  const void *d_in, *d_st, *d_of;
-  if ((rc = stage_in(c, h.data(), rec * 4 * n, &d_in))) return rc;
-  if ((rc = stage_in(c, status, 4 * n, &d_st))) return rc;
-  if ((rc = stage_in(c, msg_of, 4 * n, &d_of))) return rc;
-  HIPCK(hipStreamSynchronize(c->stream));             // h leaves scope after the call; pageable memory
-  int32_t* d_status = (int32_t*)d_st;
-  if (mode == 1) {
-    KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)m.lines,
-       (const uint32_t*)d_of, (uint32_t*)nullptr);
-    HIPCK(hipGetLastError());
-    return copy_out_and_sync(c, status, d_status, 4 * n);
-  }
-  uint32_t* d_easy = (uint32_t*)arena_take(c, (size_t)WIDE_EASY_WORDS * 4 * n);
-  if (!d_easy) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  HIPCK(hipMemsetAsync(d_easy, BLSGPU_DEBUG_COOP_SENTINEL & 0xff, (size_t)WIDE_EASY_WORDS * 4 * n, c->stream));
-  KL(KID_PAIRING_COOP_ROWS, k_pairing_coop_rows, dim3((unsigned)n), dim3(BLS_BLOCK), n, (const uint32_t*)d_in, d_status, (const uint32_t*)m.lines,
-     (const uint32_t*)d_of, d_easy);
-  HIPCK(hipGetLastError());
-  std::vector<uint32_t> e((size_t)WIDE_EASY_WORDS * n);
-  HIPCK(hipMemcpyAsync(e.data(), d_easy, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(hipStreamSynchronize(c->stream));
-  // the engine's value layout -> tower order, fourteen limbs each, as blsgpu_debug_coop_pairing
-  for (size_t i = 0; i < n; i++)
-    for (size_t kk = 0; kk < 6; kk++) {
-      const size_t pw = kk < 3 ? 2 * kk : 2 * (kk - 3) + 1;
-      for (size_t comp = 0; comp < 2; comp++)
-        for (size_t l = 0; l < FP_NL; l++) out_f12[i * WS_F_WORDS + (2 * kk + comp) * FP_NL + l] = (int32_t)e[i * WIDE_EASY_WORDS + (2 * pw + comp) * 16 + l];
-    }
-  SYNC_FLUSH(c);
-  return 0;
+  DebugStaged s;
+  if ((rc = debug_stage(c, in, WS_PAIRS_WORDS, n, status, &s, msg_of, n))) return rc;
+  PairTables t;
+  t.msg.rows = m.lines;
+  t.msg.of = s.of;
+  return debug_pairing_coop(c, mode, t, s, n, status, out_f12);
 }
 API_CATCH
 
