@@ -361,6 +361,24 @@ int h2d_small(Ctx* c, void* d, const void* src, size_t bytes) {
   HIPCK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
   return 0;
 }
+// One device word back to the host, where a plan waits for it: the launches before it checked, one copy into 4 pinned bytes and ONE
+// synchronisation -- the caller's only one before its final copy-out.
+int word_back(Ctx* c, const void* d_word, uint32_t* value) {
+  uint32_t* h = (uint32_t*)hsmall_take(c, 4);
+  if (!h) return fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted");
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h, d_word, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(BLSGPU_E_HIP, "a word's way back to the host failed: a launch before it, its copy or the synchronisation");
+  }
+  *value = *h;
+  return 0;
+}
+// the way out of a call whose pending uploads read host vectors of its frame: nothing returns before the stream has drained
+int drain(Ctx* c, int rc) {
+  (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
 
 // device view of an input buffer: device pointers pass through, host buffers are staged into the arena
 int stage_in(Ctx* c, const void* p, size_t bytes, const void** out) {
@@ -4784,64 +4802,7 @@ int blsgpu_combine_shares(int group, const uint8_t* ids, const void* pts, const 
 API_CATCH
 
 // ---- threshold signcryption (signcrypt.cuh): decryption-share checks and opening with shares, many ciphertexts per call
-/* BlsSignCrypt::verify_share (reference src/traits/sign_crypt.rs:192-207; SignDecryptionShare::verify,
- * src/sign_decryption_share.rs:45-62) for every share of n_ct ciphertexts: W' = H(u.to_bytes() || v) once per CIPHERTEXT, then
- * one two-pair check (-W', share) (w, pk) per share on the stages of blsgpu_pairing2_check_batch. */
-int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs, const uint64_t* v_offsets,
-                                        size_t n_ct, const void* shares, const void* pk_shares, const uint64_t* share_offsets, int fmt,
-                                        int32_t* status) try {
-  int rc = check_common(sig_group, scheme, fmt);
-  if (rc) return rc;
-  if (!v_offsets || !share_offsets) return fail(BLSGPU_E_ARG, "null offsets");
-  CTX_ACQUIRE(c);
-  std::vector<uint64_t> voffs, soffs;
-  if ((rc = read_offsets(v_offsets, n_ct, "v_offsets", voffs))) return rc;
-  if ((rc = read_offsets(share_offsets, n_ct, "share_offsets", soffs))) return rc;
-  const size_t n = (size_t)soffs[n_ct], total = (size_t)voffs[n_ct];
-  if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
-  if (n == 0) return 0;
-  if (!us || !ws || !shares || !pk_shares || !status || (total && !vs)) return fail(BLSGPU_E_ARG, "null argument");
-  const int pkg = key_group(sig_group);
-  const size_t K = point_bytes(pkg, BLSGPU_FMT_COMPRESSED), ub = pk_size(sig_group, fmt) * n_ct, wb = sig_size(sig_group, fmt) * n_ct,
-               shb = pk_size(sig_group, fmt) * n, wtb = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n_ct, mtotal = total + K * n_ct;
-  std::vector<uint64_t> moffs(n_ct + 1);
-  for (size_t s = 0; s <= n_ct; s++) moffs[s] = voffs[s] + K * s;
-  if ((rc = arena_reserve(c, pad256(ub) + pad256(wb) + pad256(total) + 2 * pad256(shb) + 3 * pad256(8 * (n_ct + 1)) + pad256(mtotal) + pad256(wtb) +
-                                 pad256(768 * n_ct) + pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 8192)))
-    return rc;
-  c->arena_off = 0;
-  const void *d_us, *d_ws, *d_vs, *d_sh, *d_pk;
-  const uint64_t *d_voffs, *d_soffs, *d_moffs;
-  if ((rc = stage_in(c, us, ub, &d_us))) return rc;
-  if ((rc = stage_in(c, ws, wb, &d_ws))) return rc;
-  if ((rc = stage_in(c, vs, total, &d_vs))) return rc;
-  if ((rc = stage_in(c, shares, shb, &d_sh))) return rc;
-  if ((rc = stage_in(c, pk_shares, shb, &d_pk))) return rc;
-  if ((rc = upload_offsets(c, voffs, &d_voffs)) || (rc = upload_offsets(c, soffs, &d_soffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
-  Carver mem{c};
-  uint8_t* d_msgs = mem.take<uint8_t>(mtotal);
-  uint8_t* d_wt = mem.take<uint8_t>(wtb);
-  int32_t* d_status = mem.take<int32_t>(4 * n);
-  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  // the messages U.to_bytes() || V, one per ciphertext, and their hash: every share of a ciphertext pairs against the same W'
-  with_group(sig_group, [&](auto G) {
-    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_prefix<G()>, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_us, fmt, d_voffs, d_msgs);
-  });
-  if (total) KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_copy, dim3(blocks_for(total)), dim3(BLS_BLOCK), total, n_ct, (const uint8_t*)d_vs, d_voffs, K, d_msgs);
-  if ((rc = run_hash_group(c, sig_group, n_ct, d_msgs, d_moffs, scheme_dst(sig_group, scheme), d_wt))) return rc;
-  with_group(sig_group, [&](auto G) {
-    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_pairs<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, (const uint8_t*)d_sh, (const uint8_t*)d_pk,
-       (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_pairs, d_status);
-  });
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, pairs_walked(0)))) return rc;
-  KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_status, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_status);
-  HIPCK(hipGetLastError());
-  return status_out_and_sync(c, status, d_status, n);
-}
-API_CATCH
-
+// (blsgpu_signcrypt_share_verify_batch: below, next to its indexed twin -- signcrypt_share_verify_run)
 /* BlsSignCrypt::unseal_with_shares / SignCryptCiphertext::decrypt_with_shares (reference src/traits/sign_crypt.rs:106-136,
  * src/sign_crypt_ciphertext.rs:60-72) for n_ct ciphertexts, or SignCryptDecryptionKey::decrypt (:157-163) when ids and
  * share_offsets are NULL and `shares` holds one key G per ciphertext.  Launch sequence: the validity check of
@@ -6205,13 +6166,10 @@ static bool keyset_lines_wanted(const KeySet& k, size_t n) {
 // ... and, after k_keyset_check with d_walk: the one word read back (as run_verify_shared_items reads k_group_lines' word) says
 // whether every named entry has rows; *table = the set's rows, or null: the call walks the keys
 static int keyset_lines_decide(Ctx* c, const KeySet& k, const uint32_t* d_walk, const uint32_t** table) {
-  uint32_t* h_walk = (uint32_t*)hsmall_take(c, 4);
-  if (!h_walk) return fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted");
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(h_walk, d_walk, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(hipStreamSynchronize(c->stream));
-  *table = *h_walk == 0 ? k.lines : nullptr;
-  return 0;
+  uint32_t walk = 0;
+  const int rc = word_back(c, d_walk, &walk);
+  *table = !rc && walk == 0 ? k.lines : nullptr;
+  return rc;
 }
 // for the calls without a status vector: one set over all positions; after the call's last synchronisation *h_pre == 0 says that
 // some index was outside the table
@@ -6231,9 +6189,17 @@ static int keyset_check_whole(Ctx* c, const KeySet& k, const void* idx, size_t n
   HIPCK(hipMemcpyAsync(*h_pre, d_pre, 8, hipMemcpyDeviceToHost, c->stream));
   return 0;
 }
-#define KEYSET_GATHER(words, src, legacy, dst) \
-  KL(KID_KEYSET_GATHER, k_keyset_gather, dim3(blocks_for((size_t)(cnt_) * (words))), dim3(BLS_BLOCK), (size_t)(cnt_), (size_t)(words), (const uint32_t*)d_cidx, \
+// cnt records of `words` words each, record i from entry d_cidx[i] of the set's array src
+#define KEYSET_GATHER(cnt, words, src, legacy, dst) \
+  KL(KID_KEYSET_GATHER, k_keyset_gather, dim3(blocks_for((size_t)(cnt) * (words))), dim3(BLS_BLOCK), (size_t)(cnt), (size_t)(words), (const uint32_t*)d_cidx, \
      (const uint32_t*)(src), legacy, (uint32_t*)(dst))
+// the keys a call names, in its own order and in its signatures' format: the affine records into d_aff, and for RAW_PROJ
+// (d_keys != d_aff) k_keyset_to_proj of those into d_keys
+static void keyset_gather_keys(Ctx* c, const KeySet& k, const uint32_t* d_cidx, size_t cnt, uint8_t* d_aff, uint8_t* d_keys) {
+  KEYSET_GATHER(cnt, point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE) / 4, k.aff, 0, d_aff);
+  if (d_keys != d_aff)
+    with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(cnt)), dim3(BLS_BLOCK), cnt, (const uint8_t*)d_aff, d_keys); });
+}
 
 int blsgpu_keyset_get(uint64_t handle, const uint32_t* idx, size_t count, int fmt_out, void* out, int32_t* status) try {
   KeySet k;
@@ -6255,18 +6221,11 @@ int blsgpu_keyset_get(uint64_t handle, const uint32_t* idx, size_t count, int fm
   int32_t* d_st = status ? mem.stage_out<int32_t>(status, 4 * count) : nullptr;
   uint8_t* d_aff = fmt_out == BLSGPU_FMT_RAW_PROJ ? mem.take<uint8_t>(asz * count) : nullptr;
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  const size_t cnt_ = count;
-  if (fmt_out == BLSGPU_FMT_RAW_AFFINE) {
-    KEYSET_GATHER(asz / 4, k.aff, 0, d_out);
-  } else if (fmt_out == BLSGPU_FMT_RAW_PROJ) {
-    KEYSET_GATHER(asz / 4, k.aff, 0, d_aff);
-    with_group(k.group, [&](auto G) {
-      KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_aff, d_out);
-    });
-  } else {
-    KEYSET_GATHER(csz / 4, k.comp, (int)(fmt_out == BLSGPU_FMT_LEGACY), d_out);       // the Legacy header is a transcode of byte 0
-  }
-  if (d_st) KEYSET_GATHER(1, k.status, 0, d_st);
+  if (fmt_out == BLSGPU_FMT_RAW_AFFINE || fmt_out == BLSGPU_FMT_RAW_PROJ)
+    keyset_gather_keys(c, k, d_cidx, count, d_aff ? d_aff : d_out, d_out);
+  else
+    KEYSET_GATHER(count, csz / 4, k.comp, (int)(fmt_out == BLSGPU_FMT_LEGACY), d_out);       // the Legacy header is a transcode of byte 0
+  if (d_st) KEYSET_GATHER(count, 1, k.status, 0, d_st);
   HIPCK(hipGetLastError());
   if ((rc = stage_back(c, out, d_out, osz * count))) return rc;
   if (d_st && (rc = stage_back(c, status, d_st, 4 * count))) return rc;
@@ -6344,12 +6303,12 @@ struct keys_indexed {
     if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
     return keyset_check(c, k, (const uint32_t*)d_idx, n, o, n_sets, d_cidx, d_pre);
   }
-  void key_bytes(Ctx* c, size_t cnt_, uint8_t* d_bytes) const { KEYSET_GATHER(point_bytes(k.group, BLSGPU_FMT_COMPRESSED) / 4, k.comp, ser_format, d_bytes); }
+  void key_bytes(Ctx* c, size_t cnt, uint8_t* d_bytes) const { KEYSET_GATHER(cnt, point_bytes(k.group, BLSGPU_FMT_COMPRESSED) / 4, k.comp, ser_format, d_bytes); }
   void mul_small(Ctx* c, size_t cnt, const uint8_t* d_scal, const uint32_t* d_sid, const uint32_t* d_flags, uint8_t* d_part) const {
     (void)keyset_launch_mul(c, k, cnt, d_cidx, d_scal, d_sid, d_flags, d_part);
   }
-  const uint8_t* large_keys(Ctx* c, size_t cnt_, int* kfmt) const {
-    KEYSET_GATHER(asz() / 4, k.aff, 0, d_keys);
+  const uint8_t* large_keys(Ctx* c, size_t cnt, int* kfmt) const {
+    KEYSET_GATHER(cnt, asz() / 4, k.aff, 0, d_keys);
     *kfmt = BLSGPU_FMT_RAW_AFFINE;
     return d_keys;
   }
@@ -6407,6 +6366,76 @@ int blsgpu_verify_secure_indexed_batch(int scheme, uint64_t keyset, const uint32
 }
 API_CATCH
 
+// ---- The keys of a one-key-per-item door -- verify_shared_run, signcrypt_share_verify_run, msgset_verify; blsgpu_verify_indexed_batch
+// keeps its own body on the indexed provider's stages -- n keys, item i's the i-th, by value or as positions in a key set.  The hooks:
+//   indexed           constexpr: are the keys entries of a registered set?  (The plans that read BOTH G2 members from tables exist
+//                     behind the indexed doors only.)
+//   sig_group()       the orientation of the call: the caller's argument, or the key set's
+//   devidx()          the device the call runs on: the calling thread's, or the key set's (CTX_ACQUIRE_ON)
+//   null()            is the argument that stands for the keys missing?  (part of the door's "null argument" check)
+//   arena_bytes(n)    what stage takes from the arena
+//   stage(c, n, &d_keys, &key)  the keys on the device in the signatures' format fmt.  By index: the positions staged, k_keyset_check
+//                     (every item its own set) into d_cidx and d_pre, over a set with line tables where the call's path may read rows
+//                     the one word back that says whether every named entry has them (keyset_lines_decide: the provider's only
+//                     synchronisation), k_keyset_gather of the affine records and k_keyset_to_proj for RAW_PROJ.  key: where a pairing
+//                     kernel may take item i's G2 member from instead of walking it -- key.of = d_cidx, key.rows = the set's rows, or
+//                     null: every key is walked (always so by value, where key stays empty).  run_pairing2 reads key only with
+//                     fixed_g2 = 2 and rows (launch_pairing_coop, launch_lines2s), so Bls12381G2Impl may hand it on as it is.
+//   fin(c, n, d_status)  after the door's own statuses: k_keyset_fin, the precedence of a position outside the set and of an invalid
+//                     entry over them.  Returns whether anything was launched (by value: nothing).  Valid only after a
+//                     successful stage: by index it reads the d_pre that stage carved.
+struct item_keys_by_value {
+  static constexpr bool indexed = false;
+  const void* pks;
+  int sg, fmt;
+  int sig_group() const { return sg; }
+  size_t devidx() const { return t_devidx; }
+  bool null() const { return !pks; }
+  size_t arena_bytes(size_t n) const { return pad256(pk_size(sg, fmt) * n); }
+  int stage(Ctx* c, size_t n, const uint8_t** d_keys, TabledG2*) const { return stage_in(c, pks, pk_size(sg, fmt) * n, (const void**)d_keys); }
+  bool fin(Ctx*, size_t, int32_t*) const { return false; }
+};
+struct item_keys_indexed {
+  static constexpr bool indexed = true;
+  const KeySet& k;
+  const void* idx;
+  int fmt;
+  mutable unsigned long long* d_pre = nullptr;
+  int sig_group() const { return k.sig_group; }
+  size_t devidx() const { return k.devidx; }
+  bool null() const { return !idx; }
+  size_t asz() const { return point_bytes(k.group, BLSGPU_FMT_RAW_AFFINE); }
+  size_t arena_bytes(size_t n) const {
+    return 2 * pad256(4 * n) + pad256(8 * n) + pad256(asz() * n) + (fmt == BLSGPU_FMT_RAW_AFFINE ? 0 : pad256(point_bytes(k.group, fmt) * n)) + 256;
+  }
+  int stage(Ctx* c, size_t n, const uint8_t** keys_out, TabledG2* key) const {
+    const void* d_idx;
+    int rc = stage_in(c, idx, 4 * n, &d_idx);
+    if (rc) return rc;
+    Carver mem{c};
+    uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
+    d_pre = mem.take<unsigned long long>(8 * n);
+    // one key per item: the gather is a few hundred bytes against a pairing, so the keys go to the arena, in the signatures' format
+    uint8_t* d_aff = mem.take<uint8_t>(asz() * n);
+    uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(point_bytes(k.group, fmt) * n);
+    uint32_t* d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
+    if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
+    if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return rc;
+    key->of = d_cidx;
+    key->rows = nullptr;       // ... unless the word says otherwise: a named finite entry without rows makes every item walk
+    if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key->rows))) return rc;
+    keyset_gather_keys(c, k, d_cidx, n, d_aff, d_keys);
+    *keys_out = d_keys;
+    return 0;
+  }
+  bool fin(Ctx* c, size_t n, int32_t* d_status) const {
+    KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
+    return true;
+  }
+};
+
+// Launch sequence: the provider's stage (k_keyset_check, [one word back], k_keyset_gather), run_verify_items with the keys' rows
+// where the set has them, k_keyset_fin.
 int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
                                 size_t n, int fmt, int32_t* status) try {
   KeySet k;
@@ -6421,40 +6450,27 @@ int blsgpu_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx
   uint64_t total = 0;
   if (is_device_ptr(msg_offsets)) HIPCK(hipMemcpy(&total, msg_offsets + n, 8, hipMemcpyDeviceToHost));
   else total = msg_offsets[n];
-  const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt), sgb = sig_size(sig_group, fmt) * n;
-  rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(total) + pad256(8 * (n + 1)) + pad256(4 * n) +
-                            2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 256 + 4096);
+  const item_keys_indexed keys = {k, idx, fmt};
+  const size_t sgb = sig_size(sig_group, fmt) * n;
+  rc = arena_reserve(c, keys.arena_bytes(n) + pad256(sgb) + pad256(total) + pad256(8 * (n + 1)) + pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 4096);
   if (rc) return rc;
   c->arena_off = 0;
-  const void *d_idx, *d_sigs, *d_msgs, *d_offs;
-  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
+  const void *d_sigs, *d_msgs, *d_offs;
   if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
   if ((rc = stage_in(c, msg_offsets, 8 * (n + 1), &d_offs))) return rc;
   Carver mem{c};
-  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
-  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n);
-  uint8_t* d_aff = mem.take<uint8_t>(psz * n);
-  uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(ksz * n);
   int32_t* d_status = mem.take<int32_t>(4 * n);
   uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
   uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
-  uint32_t* d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  // one key per item: the gather is a few hundred bytes against a pairing, so the keys go to the arena, in the signatures' format
-  // (run_verify_items reads both with one)
-  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return rc;
-  TabledG2 key;              // rows stay null: the call walks the keys
-  key.of = d_cidx;
-  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key.rows))) return rc;
-  const size_t cnt_ = n;
-  KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
-  if (d_keys != d_aff)
-    with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
+  const uint8_t* d_keys;
+  TabledG2 key;
+  if ((rc = keys.stage(c, n, &d_keys, &key))) return rc;       // (run_verify_items reads keys and signatures with one format)
   rc = run_verify_items(c, sig_group, scheme == BLSGPU_SCHEME_AUG, d_keys, (const uint8_t*)d_sigs, fmt, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, 0,
                         scheme_dst(sig_group, scheme), n, d_pairs, d_f, d_status, 0, key);
   if (rc) return rc;
-  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
+  keys.fin(c, n, d_status);
   HIPCK(hipGetLastError());
   return status_out_and_sync(c, status, d_status, n);
 }
@@ -6496,10 +6512,7 @@ struct agg_keys_indexed {
     if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, T, o, n_sets, d_cidx, d_pre, d_walk))) return rc;
     if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, key_table))) return rc;      // a named finite entry without rows: every item walks
     if (T) {
-      const size_t cnt_ = T;
-      KEYSET_GATHER(asz / 4, k.aff, 0, d_aff);
-      if (d_keys != d_aff)
-        with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, (const uint8_t*)d_aff, d_keys); });
+      keyset_gather_keys(c, k, d_cidx, T, d_aff, d_keys);
       HIPCK(hipGetLastError());
     }
     *kp = d_keys;
@@ -6538,16 +6551,15 @@ int blsgpu_aggregate_verify_indexed_batch(int scheme, uint64_t keyset, const uin
 API_CATCH
 
 // The row builder (k_group_lines): the Miller-loop rows of m affine G2 points into d_table (SHARED_TABLE_WORDS per point; d_scratch as
-// large, d_flags m + 1 words), and one word back to the host, *h_any (pinned, or the caller's own word): *usable = every point has
-// rows -- the identity and a point whose walk meets h = 0 have none.  One launch, one synchronisation.
-static int build_rows(Ctx* c, size_t m, const uint8_t* d_aff, uint32_t* d_table, uint32_t* d_scratch, int32_t* d_flags, int32_t* h_any, bool* usable) {
+// large, d_flags m + 1 words), and one word back to the host (word_back): *usable = every point has rows -- the identity and a point
+// whose walk meets h = 0 have none.  One launch, one synchronisation.
+static int build_rows(Ctx* c, size_t m, const uint8_t* d_aff, uint32_t* d_table, uint32_t* d_scratch, int32_t* d_flags, bool* usable) {
   HIPCK(hipMemsetAsync(d_flags + m, 0, 4, c->stream));
   KL(KID_GROUP_LINES, k_group_lines, dim3(blocks_for(2 * m)), dim3(BLS_BLOCK), m, d_aff, d_table, d_scratch, d_flags);
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(h_any, d_flags + m, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(hipStreamSynchronize(c->stream));
-  *usable = *h_any == 0;
-  return 0;
+  uint32_t any = 1;
+  const int rc = word_back(c, d_flags + m, &any);
+  *usable = !rc && any == 0;
+  return rc;
 }
 
 // ---- shared-message verify (verify_shared.cuh): Signature::verify for items that come in groups under one message each
@@ -6625,9 +6637,7 @@ static int run_verify_shared_items(Ctx* c, int sg, int scheme, const shared_plan
   if (table) {
     // a group whose point is the identity or whose walk meets h = 0 has no usable rows (never seen for a hash output): the
     // call then takes the general form for every item -- one word read back decides it before the records are written
-    int32_t* h_any = (int32_t*)hsmall_take(c, 4);
-    if (!h_any) return fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted");
-    if ((rc = build_rows(c, n_groups, d_aff, d_table, d_scratch, d_flags, h_any, &table))) return rc;
+    if ((rc = build_rows(c, n_groups, d_aff, d_table, d_scratch, d_flags, &table))) return rc;
   }
   with_group(sg, [&](auto G) {
     KL(KID_PREPARE_SHARED, k_prepare_shared<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, d_pks, d_sigs, fmt, (const uint8_t*)d_aff, d_pairs,
@@ -6654,176 +6664,130 @@ static int shared_read_offsets(const uint64_t* item_offsets, const uint64_t* msg
 }
 
 /* Signature::verify (reference src/signature.rs:130-138) for the items of n_groups groups, every item of a group under the
- * group's message: status[i] is what blsgpu_verify_batch gives for item i with that message. */
-int blsgpu_verify_shared_batch(int sig_group, int scheme, const void* pks, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
-                               const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
+ * group's message: status[i] is what blsgpu_verify_batch gives for item i with that message.  Keys: item_keys_by_value, or over a
+ * registered key set item_keys_indexed -- item i's key is the entry at position idx[i]: the provider's stage (k_keyset_check, every
+ * item its own set, k_keyset_gather), the shared path above, k_keyset_fin -- the sequence and the status precedence of
+ * blsgpu_verify_indexed_batch. */
+extern "C++" {
+template <class Keys>
+static int verify_shared_run(const Keys& keys, int scheme, const void* sigs, const uint64_t* item_offsets, size_t n_groups, const uint8_t* msgs,
+                             const uint64_t* msg_offsets, int fmt, int32_t* status) {
+  const int sig_group = keys.sig_group();
   int rc = check_common(sig_group, scheme, fmt);
   if (rc) return rc;
   if (n_groups == 0) return 0;
   if (!item_offsets || !msg_offsets) return fail(BLSGPU_E_ARG, "null offsets");
-  CTX_ACQUIRE(c);
+  CTX_ACQUIRE_ON(c, keys.devidx());
   std::vector<uint64_t> ioffs, moffs;
   size_t n = 0;
   if ((rc = shared_read_offsets(item_offsets, msg_offsets, n_groups, ioffs, moffs, &n))) return rc;
   if (n == 0) return 0;
   const size_t total = (size_t)moffs[n_groups];
-  if (!pks || !sigs || !status || (total && !msgs)) return fail(BLSGPU_E_ARG, "null argument");
+  if (keys.null() || !sigs || !status || (total && !msgs)) return fail(BLSGPU_E_ARG, "null argument");
   shared_plan plan;
   shared_make_plan(plan, sig_group, scheme, n, n_groups, ioffs, moffs);
-  const size_t pkb = pk_size(sig_group, fmt) * n, sgb = sig_size(sig_group, fmt) * n;
-  if ((rc = arena_reserve(c, pad256(pkb) + pad256(sgb) + pad256(total) + 2 * pad256(8 * (n_groups + 1)) + pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) +
-                                 plan.ws_bytes + 8192)))
+  const size_t sgb = sig_size(sig_group, fmt) * n;
+  if ((rc = arena_reserve(c, keys.arena_bytes(n) + pad256(sgb) + pad256(total) + 2 * pad256(8 * (n_groups + 1)) + pad256(4 * n) +
+                                 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + plan.ws_bytes + 8192)))
     return rc;
   c->arena_off = 0;
-  const void *d_pks, *d_sigs, *d_msgs;
+  const void *d_sigs, *d_msgs;
   const uint64_t *d_ioffs, *d_moffs;
-  if ((rc = stage_in(c, pks, pkb, &d_pks))) return rc;
   if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
   if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
-  if ((rc = upload_offsets(c, ioffs, &d_ioffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
+  if ((rc = upload_offsets(c, ioffs, &d_ioffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return drain(c, rc);
+  // from here on every way out drains: the uploads read ioffs / moffs
   Carver mem{c};
   int32_t* d_status = mem.take<int32_t>(4 * n);
   uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
   uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  rc = run_verify_shared_items(c, sig_group, scheme, plan, n, n_groups, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, fmt, d_ioffs, (const uint8_t*)d_msgs, d_moffs,
-                               d_pairs, d_f, d_status);
-  if (rc) {
-    (void)hipStreamSynchronize(c->stream);      // the uploads read ioffs / moffs
-    return rc;
-  }
+  if (!mem.ok) return drain(c, fail(BLSGPU_E_HIP, "internal: arena too small"));
+  const uint8_t* d_keys;
+  TabledG2 key;
+  if ((rc = keys.stage(c, n, &d_keys, &key))) return drain(c, rc);
+  rc = run_verify_shared_items(c, sig_group, scheme, plan, n, n_groups, d_keys, (const uint8_t*)d_sigs, fmt, d_ioffs, (const uint8_t*)d_msgs, d_moffs, d_pairs, d_f,
+                               d_status, key);
+  if (rc) return drain(c, rc);
+  if (keys.fin(c, n, d_status) && hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
   return status_out_and_sync(c, status, d_status, n);
 }
+}  // extern "C++"
+int blsgpu_verify_shared_batch(int sig_group, int scheme, const void* pks, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
+                               const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
+  const item_keys_by_value keys = {pks, sig_group, fmt};
+  return verify_shared_run(keys, scheme, sigs, item_offsets, n_groups, msgs, msg_offsets, fmt, status);
+}
 API_CATCH
-
-/* The same over a registered key set: item i's key is the entry at position idx[i].  k_keyset_check (every item its own set),
- * k_keyset_gather, the shared path above, k_keyset_fin -- the sequence and the status precedence of blsgpu_verify_indexed_batch. */
 int blsgpu_verify_shared_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* sigs, const uint64_t* item_offsets, size_t n_groups,
                                        const uint8_t* msgs, const uint64_t* msg_offsets, int fmt, int32_t* status) try {
   KeySet k;
   int rc = set_find(keyset, k);
   if (rc) return rc;
-  const int sig_group = k.sig_group;
-  if ((rc = check_common(sig_group, scheme, fmt))) return rc;
-  if (n_groups == 0) return 0;
-  if (!item_offsets || !msg_offsets) return fail(BLSGPU_E_ARG, "null offsets");
-  CTX_ACQUIRE_ON(c, k.devidx);
-  std::vector<uint64_t> ioffs, moffs;
-  size_t n = 0;
-  if ((rc = shared_read_offsets(item_offsets, msg_offsets, n_groups, ioffs, moffs, &n))) return rc;
-  if (n == 0) return 0;
-  const size_t total = (size_t)moffs[n_groups];
-  if (!idx || !sigs || !status || (total && !msgs)) return fail(BLSGPU_E_ARG, "null argument");
-  shared_plan plan;
-  shared_make_plan(plan, sig_group, scheme, n, n_groups, ioffs, moffs);
-  const size_t psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt), sgb = sig_size(sig_group, fmt) * n;
-  if ((rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(total) + 2 * pad256(8 * (n_groups + 1)) +
-                                 pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + plan.ws_bytes + 256 + 8192)))
-    return rc;
-  c->arena_off = 0;
-  const void *d_idx, *d_sigs, *d_msgs;
-  const uint64_t *d_ioffs, *d_moffs;
-  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
-  if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
-  if ((rc = stage_in(c, msgs, total, &d_msgs))) return rc;
-  if ((rc = upload_offsets(c, ioffs, &d_ioffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
-  Carver mem{c};
-  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
-  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n);
-  uint8_t* d_aff = mem.take<uint8_t>(psz * n);
-  uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(ksz * n);
-  int32_t* d_status = mem.take<int32_t>(4 * n);
-  uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
-  uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
-  uint32_t* d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  auto drain = [&](int r) {
-    (void)hipStreamSynchronize(c->stream);      // the uploads read ioffs / moffs
-    return r;
-  };
-  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
-  TabledG2 key;
-  key.of = d_cidx;
-  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key.rows))) return drain(rc);
-  const size_t cnt_ = n;
-  KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
-  if (d_keys != d_aff)
-    with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
-  rc = run_verify_shared_items(c, sig_group, scheme, plan, n, n_groups, d_keys, (const uint8_t*)d_sigs, fmt, d_ioffs, (const uint8_t*)d_msgs, d_moffs, d_pairs, d_f,
-                               d_status, key);
-  if (rc) return drain(rc);
-  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
-  return status_out_and_sync(c, status, d_status, n);
+  const item_keys_indexed keys = {k, idx, fmt};
+  return verify_shared_run(keys, scheme, sigs, item_offsets, n_groups, msgs, msg_offsets, fmt, status);
 }
 API_CATCH
 
-/* blsgpu_signcrypt_share_verify_batch with share i's public-key share at position idx[i] of a registered key set (every share its own
- * set: the status precedence of blsgpu_verify_indexed_batch).  Launch sequence: k_keyset_check, k_keyset_gather, the by-value call's
- * message and hash stages, [plan T2: k_signcrypt_ct_affine, k_group_lines over 2 n_ct points and one word back, k_signcrypt_tab_of],
- * k_signcrypt_share_pairs on the gathered keys, [plan ROWS on the one-wave path: k_signcrypt_swap_pairs], run_pairing2,
- * k_signcrypt_share_status, k_keyset_fin.  The plan comes from the call's shape and the set's flags alone:
- *   ROWS  Bls12381G1Impl over a set whose named entries have line rows, above BLSGPU_WIDE_MAX shares: the pair (w, pk) reads the key's
- *         rows and only the share is walked -- k_pairing_coop_rows / k_lines2s_shared with the set's rows in the place of a message
- *         set's / the groups' table;
- *   T2    Bls12381G2Impl above BLSGPU_WIDE_MAX shares with at least BLSGPU_SIGNCRYPT_LINES_MIN shares per ciphertext on average: the
- *         rows of -W' and w are built once per ciphertext and a share walks nothing (k_pairing_coop_tables2 / k_lines2s_tables2);
- *   else  the by-value stages on the gathered keys. */
-int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* us, const void* ws, const uint8_t* vs,
-                                                const uint64_t* v_offsets, size_t n_ct, const void* shares, const uint64_t* share_offsets, int fmt,
-                                                int32_t* status) try {
-  KeySet k;
-  int rc = set_find(keyset, k);
+// ---- threshold signcryption (signcrypt.cuh): the decryption-share check, many ciphertexts per call
+/* BlsSignCrypt::verify_share (reference src/traits/sign_crypt.rs:192-207; SignDecryptionShare::verify,
+ * src/sign_decryption_share.rs:45-62) for every share of n_ct ciphertexts: W' = H(u.to_bytes() || v) once per CIPHERTEXT, then
+ * one two-pair check (-W', share) (w, pk) per share on the stages of blsgpu_pairing2_check_batch.  Keys: item_keys_by_value (on the
+ * calling thread's device), or item_keys_indexed: share i's public-key share at position idx[i] of a registered key set, every share
+ * its own set (the status precedence of blsgpu_verify_indexed_batch), on the key set's device, without sharding.
+ * Launch sequence: [indexed: k_keyset_check, k_keyset_gather], the message and hash stages (k_signcrypt_hash_prefix,
+ * k_signcrypt_hash_copy, run_hash_group), [plan T2: k_signcrypt_ct_affine, k_group_lines over 2 n_ct points and one word back,
+ * k_signcrypt_tab_of], k_signcrypt_share_pairs, [plan ROWS on the one-wave path: k_signcrypt_swap_pairs], run_pairing2,
+ * k_signcrypt_share_status, [indexed: k_keyset_fin].  The plan comes from the call's shape and the set's flags alone:
+ *   ROWS  Bls12381G1Impl over a set whose named entries have line rows, above BLSGPU_WIDE_MAX shares (the provider hands back rows): the
+ *         pair (w, pk) reads the key's rows and only the share is walked -- k_pairing_coop_rows / k_lines2s_shared with the set's rows in
+ *         the place of a message set's / the groups' table;
+ *   T2    behind the indexed door only (Keys::indexed), Bls12381G2Impl above BLSGPU_WIDE_MAX shares with at least
+ *         BLSGPU_SIGNCRYPT_LINES_MIN shares per ciphertext on average: the rows of -W' and w are built once per ciphertext and a share
+ *         walks nothing (k_pairing_coop_tables2 / k_lines2s_tables2);
+ *   else  two general pairs: all a by-value call ever launches. */
+extern "C++" {
+template <class Keys>
+static int signcrypt_share_verify_run(const Keys& keys, int scheme, const void* us, const void* ws, const uint8_t* vs, const uint64_t* v_offsets, size_t n_ct,
+                                      const void* shares, const uint64_t* share_offsets, int fmt, int32_t* status) {
+  const int sig_group = keys.sig_group();
+  int rc = check_common(sig_group, scheme, fmt);
   if (rc) return rc;
-  const int sig_group = k.sig_group;
-  if ((rc = check_common(sig_group, scheme, fmt))) return rc;
   if (!v_offsets || !share_offsets) return fail(BLSGPU_E_ARG, "null offsets");
-  CTX_ACQUIRE_ON(c, k.devidx);                 // on the key set's device, without sharding
+  CTX_ACQUIRE_ON(c, keys.devidx());
   std::vector<uint64_t> voffs, soffs;
   if ((rc = read_offsets(v_offsets, n_ct, "v_offsets", voffs))) return rc;
   if ((rc = read_offsets(share_offsets, n_ct, "share_offsets", soffs))) return rc;
   const size_t n = (size_t)soffs[n_ct], total = (size_t)voffs[n_ct];
   if (n >= ((size_t)1 << 32)) return fail(BLSGPU_E_ARG, "too many shares in one call");
   if (n == 0) return 0;
-  if (!idx || !us || !ws || !shares || !status || (total && !vs)) return fail(BLSGPU_E_ARG, "null argument");
-  const size_t K = point_bytes(k.group, BLSGPU_FMT_COMPRESSED), ub = pk_size(sig_group, fmt) * n_ct, wb = sig_size(sig_group, fmt) * n_ct,
-               shb = pk_size(sig_group, fmt) * n, wtb = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n_ct, mtotal = total + K * n_ct,
-               psz = pk_size(sig_group, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sig_group, fmt);
+  if (keys.null() || !us || !ws || !shares || !status || (total && !vs)) return fail(BLSGPU_E_ARG, "null argument");
+  const size_t K = point_bytes(key_group(sig_group), BLSGPU_FMT_COMPRESSED), ub = pk_size(sig_group, fmt) * n_ct, wb = sig_size(sig_group, fmt) * n_ct,
+               shb = pk_size(sig_group, fmt) * n, wtb = sig_size(sig_group, BLSGPU_FMT_RAW_PROJ) * n_ct, mtotal = total + K * n_ct;
   std::vector<uint64_t> moffs(n_ct + 1);
   for (size_t s = 0; s <= n_ct; s++) moffs[s] = voffs[s] + K * s;
   // plan T2, from the shape alone (the knob prices the 2 n_ct walks of the row builder against the two walks a share saves)
   const size_t t2_bytes = 2 * n_ct * (size_t)SHARED_TABLE_WORDS * 4;
   const long knob = knobs().signcrypt_lines_min;
-  const bool t2_plan = sig_group == 2 && knob > 0 && n / n_ct >= (size_t)knob && pair_path_reads_rows(n) && t2_bytes <= 0xffffffffull;
+  const bool t2_plan = Keys::indexed && sig_group == 2 && knob > 0 && n / n_ct >= (size_t)knob && pair_path_reads_rows(n) && t2_bytes <= 0xffffffffull;
   const size_t t2_ws = t2_plan ? pad256(2 * 192 * n_ct) + 2 * pad256(t2_bytes) + pad256(4 * (2 * n_ct + 1)) + pad256(8 * n) : 0;
-  if ((rc = arena_reserve(c, 2 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(ub) + pad256(wb) + pad256(total) + pad256(shb) +
-                                 3 * pad256(8 * (n_ct + 1)) + pad256(mtotal) + pad256(wtb) + pad256(768 * n_ct) + pad256(4 * n) +
-                                 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + t2_ws + 256 + 8192)))
+  if ((rc = arena_reserve(c, keys.arena_bytes(n) + pad256(ub) + pad256(wb) + pad256(total) + pad256(shb) + 3 * pad256(8 * (n_ct + 1)) + pad256(mtotal) + pad256(wtb) +
+                                 pad256(768 * n_ct) + pad256(4 * n) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + t2_ws + 8192)))
     return rc;
   c->arena_off = 0;
-  const void *d_idx, *d_us, *d_ws, *d_vs, *d_sh;
+  const void *d_us, *d_ws, *d_vs, *d_sh;
   const uint64_t *d_voffs, *d_soffs, *d_moffs;
-  if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
   if ((rc = stage_in(c, us, ub, &d_us))) return rc;
   if ((rc = stage_in(c, ws, wb, &d_ws))) return rc;
   if ((rc = stage_in(c, vs, total, &d_vs))) return rc;
   if ((rc = stage_in(c, shares, shb, &d_sh))) return rc;
-  if ((rc = upload_offsets(c, voffs, &d_voffs)) || (rc = upload_offsets(c, soffs, &d_soffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return rc;
-  auto drain = [&](int r) {
-    (void)hipStreamSynchronize(c->stream);      // the uploads read voffs / soffs / moffs
-    return r;
-  };
+  if ((rc = upload_offsets(c, voffs, &d_voffs)) || (rc = upload_offsets(c, soffs, &d_soffs)) || (rc = upload_offsets(c, moffs, &d_moffs))) return drain(c, rc);
+  // from here on every way out drains: the uploads read voffs / soffs / moffs
   Carver mem{c};
-  uint32_t* d_cidx = mem.take<uint32_t>(4 * n);
-  unsigned long long* d_pre = mem.take<unsigned long long>(8 * n);
-  uint8_t* d_aff = mem.take<uint8_t>(psz * n);
-  uint8_t* d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_aff : mem.take<uint8_t>(ksz * n);
   uint8_t* d_msgs = mem.take<uint8_t>(mtotal);
   uint8_t* d_wt = mem.take<uint8_t>(wtb);
   int32_t* d_status = mem.take<int32_t>(4 * n);
   uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
   uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
-  uint32_t* d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
   uint8_t* d_caff = nullptr;
   uint32_t *d_table = nullptr, *d_scratch = nullptr, *d_tof = nullptr;
   int32_t* d_flags = nullptr;
@@ -6834,36 +6798,29 @@ int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, con
     d_flags = mem.take<int32_t>(4 * (2 * n_ct + 1));
     d_tof = mem.take<uint32_t>(8 * n);
   }
-  if (!mem.ok) return drain(fail(BLSGPU_E_HIP, "internal: arena too small"));
-  if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
-  TabledG2 key;                                    // plan ROWS: a named finite entry without rows makes every share walk
-  key.of = d_cidx;
-  if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &key.rows))) return drain(rc);
-  const size_t cnt_ = n;
-  KEYSET_GATHER(psz / 4, k.aff, 0, d_aff);
-  if (d_keys != d_aff)
-    with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_aff, d_keys); });
-  // the messages U.to_bytes() || V, one per ciphertext, and their hash, as the by-value call launches them
+  if (!mem.ok) return drain(c, fail(BLSGPU_E_HIP, "internal: arena too small"));
+  const uint8_t* d_keys;
+  TabledG2 key;                                    // plan ROWS: key.rows (a named finite entry without rows makes every share walk)
+  if ((rc = keys.stage(c, n, &d_keys, &key))) return drain(c, rc);
+  // the messages U.to_bytes() || V, one per ciphertext, and their hash: every share of a ciphertext pairs against the same W'
   with_group(sig_group, [&](auto G) {
     KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_prefix<G()>, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_us, fmt, d_voffs, d_msgs);
   });
   if (total) KL(KID_SIGNCRYPT_GATHER, k_signcrypt_hash_copy, dim3(blocks_for(total)), dim3(BLS_BLOCK), total, n_ct, (const uint8_t*)d_vs, d_voffs, K, d_msgs);
-  if ((rc = run_hash_group(c, sig_group, n_ct, d_msgs, d_moffs, scheme_dst(sig_group, scheme), d_wt))) return drain(rc);
+  if ((rc = run_hash_group(c, sig_group, n_ct, d_msgs, d_moffs, scheme_dst(sig_group, scheme), d_wt))) return drain(c, rc);
   bool t2 = t2_plan;
   if (t2) {
     // a FINITE w or W' whose walk meets h = 0 has no usable rows: the call then takes the general form for every share -- one word
     // read back decides it.  (An identity w never raises it: k_signcrypt_ct_affine.)
-    int32_t* h_any = (int32_t*)hsmall_take(c, 4);
-    if (!h_any) return drain(fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted"));
     KL(KID_SIGNCRYPT_GATHER, k_signcrypt_ct_affine, dim3(blocks_for(n_ct)), dim3(BLS_BLOCK), n_ct, (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_caff);
-    if ((rc = build_rows(c, 2 * n_ct, d_caff, d_table, d_scratch, d_flags, h_any, &t2))) return drain(rc);
+    if ((rc = build_rows(c, 2 * n_ct, d_caff, d_table, d_scratch, d_flags, &t2))) return drain(c, rc);
     if (t2) KL(KID_SIGNCRYPT_GATHER, k_signcrypt_tab_of, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, d_tof, d_tof + n);
   }
   with_group(sig_group, [&](auto G) {
-    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_pairs<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, (const uint8_t*)d_sh, (const uint8_t*)d_keys,
+    KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_pairs<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_ct, d_soffs, (const uint8_t*)d_sh, d_keys,
        (const uint8_t*)d_ws, fmt, (const uint8_t*)d_wt, d_pairs, d_status);
   });
-  PairTables t;
+  PairTables t = pairs_walked(0);
   if (key.rows && pair_path(n) == PATH_LANE_SPLIT) {
     t.shared = key;           // the records as written: the share's pair first, the key's rows as the groups' table
   } else if (key.rows) {      // plan ROWS on the one-wave path: the key's pair first, its rows as a message set's
@@ -6874,11 +6831,28 @@ int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, con
     t.both.rows = d_table;
     t.both.of = d_tof;
   }
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, t))) return drain(rc);
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, t))) return drain(c, rc);
   KL(KID_SIGNCRYPT_GATHER, k_signcrypt_share_status, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, d_status);
-  KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
+  keys.fin(c, n, d_status);
+  if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "a kernel of the share check failed to launch"));
   return status_out_and_sync(c, status, d_status, n);
+}
+}  // extern "C++"
+int blsgpu_signcrypt_share_verify_batch(int sig_group, int scheme, const void* us, const void* ws, const uint8_t* vs, const uint64_t* v_offsets,
+                                        size_t n_ct, const void* shares, const void* pk_shares, const uint64_t* share_offsets, int fmt,
+                                        int32_t* status) try {
+  const item_keys_by_value keys = {pk_shares, sig_group, fmt};
+  return signcrypt_share_verify_run(keys, scheme, us, ws, vs, v_offsets, n_ct, shares, share_offsets, fmt, status);
+}
+API_CATCH
+int blsgpu_signcrypt_share_verify_indexed_batch(int scheme, uint64_t keyset, const uint32_t* idx, const void* us, const void* ws, const uint8_t* vs,
+                                                const uint64_t* v_offsets, size_t n_ct, const void* shares, const uint64_t* share_offsets, int fmt,
+                                                int32_t* status) try {
+  KeySet k;
+  int rc = set_find(keyset, k);
+  if (rc) return rc;
+  const item_keys_indexed keys = {k, idx, fmt};
+  return signcrypt_share_verify_run(keys, scheme, us, ws, vs, v_offsets, n_ct, shares, share_offsets, fmt, status);
 }
 API_CATCH
 
@@ -7030,9 +7004,8 @@ int blsgpu_debug_tables2(int mode, const void* points, size_t m, const uint32_t*
   uint32_t* d_scratch = mem.take<uint32_t>(tb);
   int32_t* d_flags = mem.take<int32_t>(4 * (m + 1));
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  int32_t any = 0;
   bool usable = false;
-  if ((rc = build_rows(c, m, (const uint8_t*)d_pts, d_table, d_scratch, d_flags, &any, &usable))) return rc;
+  if ((rc = build_rows(c, m, (const uint8_t*)d_pts, d_table, d_scratch, d_flags, &usable))) return rc;
   if (!usable) return fail(BLSGPU_E_ARG, "a point has no usable rows");
   DebugStaged s;
   if ((rc = debug_stage(c, in, WS_PAIRS_WORDS, n, status, &s, tt.data(), 2 * n))) return rc;
@@ -7077,17 +7050,14 @@ static int msgset_apply(Ctx* c, const MsgSet& m, const uint32_t* h_pos, size_t f
   uint8_t* d_hash = mem.take<uint8_t>(hsz * count);
   uint32_t* d_pos = h_pos ? mem.take<uint32_t>(4 * count) : nullptr;
   if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  auto drain = [&](int r) {
-    (void)hipStreamSynchronize(c->stream);      // the uploads read moffs / h_pos
-    return r;
-  };
-  if (h_pos && hipMemcpyAsync(d_pos, h_pos, 4 * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) return drain(fail(BLSGPU_E_HIP, "position upload failed"));
-  if ((rc = run_hash_group(c, m.sig_group, count, (const uint8_t*)d_msgs, d_moffs, scheme_dst(m.sig_group, m.scheme), d_hash, m.sig_group == 1))) return drain(rc);
+  // the ways out through drain(c, rc): the uploads read moffs / h_pos
+  if (h_pos && hipMemcpyAsync(d_pos, h_pos, 4 * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "position upload failed"));
+  if ((rc = run_hash_group(c, m.sig_group, count, (const uint8_t*)d_msgs, d_moffs, scheme_dst(m.sig_group, m.scheme), d_hash, m.sig_group == 1))) return drain(c, rc);
   with_group(m.sig_group, [&](auto G) {
     KL(KID_MSGSET_SEAL, k_msgset_seal<G()>, dim3(blocks_for(count)), dim3(BLS_BLOCK), count, (const uint8_t*)d_hash, (const uint32_t*)d_pos, first, m.aff);
   });
   if (m.lines) set_launch_lines(c, m, d_pos, first, count, scratch.p);
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
+  if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
   SYNC_FLUSH(c);                      // before the scratch goes
   return 0;
 }
@@ -7204,23 +7174,25 @@ int blsgpu_debug_msgset_from_points(int sig_group, const void* points, size_t n,
 }
 API_CATCH
 
-// ---- the verify calls over a message set.  Launch sequence: k_msgset_check (every group's index; whether every named entry has
-// rows, one word back to the host where the plan may read rows), k_keyset_gather (the groups' stored points), [indexed:
-// k_keyset_check, k_keyset_gather of the keys], k_prepare_shared, k_msgset_mark, run_pairing2, [indexed: k_keyset_fin, k_msgset_mark].
-// No hash kernel, no k_group_affine, no k_group_lines.  keyset == 0: keys by value.
-static int msgset_verify(uint64_t msgset, const uint32_t* msg_idx, bool indexed, uint64_t keyset, const uint32_t* idx, const void* pks, const void* sigs,
-                         const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status) {
-  MsgSet m;
+// a message set, and the key set that an indexed call names next to it: the same orientation, on the same device
+static int msgset_keyset_find(uint64_t msgset, MsgSet& m, uint64_t keyset, KeySet& k) {
   int rc = set_find(msgset, m);
-  if (rc) return rc;
-  KeySet k;
-  if (indexed) {
-    if ((rc = set_find(keyset, k))) return rc;
-    if (k.sig_group != m.sig_group) return fail(BLSGPU_E_ARG, "the key set belongs to the other orientation");
-    if (k.dev != m.dev || k.devidx != m.devidx) return fail(BLSGPU_E_ARG, "the key set and the message set live on different devices");
-  }
+  if (rc || (rc = set_find(keyset, k))) return rc;
+  if (k.sig_group != m.sig_group) return fail(BLSGPU_E_ARG, "the key set belongs to the other orientation");
+  if (k.dev != m.dev || k.devidx != m.devidx) return fail(BLSGPU_E_ARG, "the key set and the message set live on different devices");
+  return 0;
+}
+// ---- the verify calls over a message set; keys: item_keys_by_value or item_keys_indexed.  Launch sequence: k_msgset_check (every
+// group's index; whether every named entry has rows, one word back to the host where the plan may read rows), k_keyset_gather (the
+// groups' stored points), [indexed, the provider's stage: k_keyset_check, k_keyset_gather of the keys], k_prepare_shared,
+// k_msgset_mark, run_pairing2, [indexed: k_keyset_fin, k_msgset_mark].  No hash kernel, no k_group_affine, no k_group_lines.
+extern "C++" {
+template <class Keys>
+static int msgset_verify(const MsgSet& m, const Keys& keys, const uint32_t* msg_idx, const void* sigs, const uint64_t* item_offsets, size_t n_groups, int fmt,
+                         int32_t* status) {
   const int sg = m.sig_group;
-  if ((rc = check_common(sg, m.scheme, fmt))) return rc;
+  int rc = check_common(sg, m.scheme, fmt);
+  if (rc) return rc;
   if (n_groups == 0) return 0;
   if (!item_offsets) return fail(BLSGPU_E_ARG, "null offsets");
   CTX_ACQUIRE_ON(c, m.devidx);
@@ -7230,22 +7202,21 @@ static int msgset_verify(uint64_t msgset, const uint32_t* msg_idx, bool indexed,
   if (n_groups >= ((uint64_t)1 << 32)) return fail(BLSGPU_E_ARG, "2^32 or more groups in one call");
   const size_t n = (size_t)ioffs[n_groups];
   if (n == 0) return 0;
-  if (!msg_idx || !sigs || !status || (indexed ? !idx : !pks)) return fail(BLSGPU_E_ARG, "null argument");
+  if (!msg_idx || !sigs || !status || keys.null()) return fail(BLSGPU_E_ARG, "null argument");
   // the plan, from the call's shape alone: the row-wide engine reads no rows; the one-wave path reads them in k_pairing_coop_rows, the
   // lane-split path in k_lines2s_shared (BLSGPU_SHARED_LINES_MIN prices a build that has already happened: it does not apply)
   const bool rows_wanted = m.lines && sg == 2 && pair_path_reads_rows(n);
-  const size_t asz = point_bytes(sg, BLSGPU_FMT_RAW_AFFINE), psz = pk_size(sg, BLSGPU_FMT_RAW_AFFINE), ksz = pk_size(sg, fmt), sgb = sig_size(sg, fmt) * n;
-  if ((rc = arena_reserve(c, 4 * pad256(4 * n) + pad256(8 * n) + pad256(psz * n) + pad256(ksz * n) + pad256(sgb) + pad256(8 * (n_groups + 1)) +
-                                 2 * pad256(4 * n_groups) + pad256(asz * n_groups) + 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 512 + 8192)))
+  const size_t asz = point_bytes(sg, BLSGPU_FMT_RAW_AFFINE), sgb = sig_size(sg, fmt) * n;
+  if ((rc = arena_reserve(c, keys.arena_bytes(n) + 3 * pad256(4 * n) + pad256(sgb) + pad256(8 * (n_groups + 1)) + 2 * pad256(4 * n_groups) + pad256(asz * n_groups) +
+                                 2 * pad256((size_t)WS_PAIRS_WORDS * 4 * n) + 256 + 8192)))
     return rc;
   c->arena_off = 0;
-  const void *d_midx, *d_idx = nullptr, *d_sigs, *d_pks = nullptr;
+  const void *d_midx, *d_sigs;
   const uint64_t* d_ioffs;
   if ((rc = stage_in(c, msg_idx, 4 * n_groups, &d_midx))) return rc;
-  if (indexed && (rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
-  if (!indexed && (rc = stage_in(c, pks, ksz * n, &d_pks))) return rc;
   if ((rc = stage_in(c, sigs, sgb, &d_sigs))) return rc;
-  if ((rc = upload_offsets(c, ioffs, &d_ioffs))) return rc;
+  if ((rc = upload_offsets(c, ioffs, &d_ioffs))) return drain(c, rc);
+  // from here on every way out drains: the upload reads ioffs
   Carver mem{c};
   uint32_t* d_cmsg = mem.take<uint32_t>(4 * n_groups);
   uint8_t* d_haff = mem.take<uint8_t>(asz * n_groups);
@@ -7255,77 +7226,58 @@ static int msgset_verify(uint64_t msgset, const uint32_t* msg_idx, bool indexed,
   uint32_t* d_pairs = mem.take<uint32_t>((size_t)WS_PAIRS_WORDS * 4 * n);
   uint32_t* d_f = mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n);
   uint32_t* d_mwalk = mem.take<uint32_t>(4);
-  uint32_t* d_cidx = nullptr;
-  unsigned long long* d_pre = nullptr;
-  uint8_t *d_kaff = nullptr, *d_keys = nullptr;
-  uint32_t* d_walk = nullptr;
-  if (indexed) {
-    d_cidx = mem.take<uint32_t>(4 * n);
-    d_pre = mem.take<unsigned long long>(8 * n);
-    d_kaff = mem.take<uint8_t>(psz * n);
-    d_keys = fmt == BLSGPU_FMT_RAW_AFFINE ? d_kaff : mem.take<uint8_t>(ksz * n);
-    d_walk = keyset_lines_wanted(k, n) ? mem.take<uint32_t>(4) : nullptr;
-  }
-  if (!mem.ok) return fail(BLSGPU_E_HIP, "internal: arena too small");
-  auto drain = [&](int r) {
-    (void)hipStreamSynchronize(c->stream);      // the upload reads ioffs
-    return r;
-  };
-  if (hipMemsetAsync(d_mwalk, 0, 4, c->stream) != hipSuccess) return drain(fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
+  if (!mem.ok) return drain(c, fail(BLSGPU_E_HIP, "internal: arena too small"));
+  if (hipMemsetAsync(d_mwalk, 0, 4, c->stream) != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
   KL(KID_MSGSET_CHECK, k_msgset_check, dim3(blocks_for(n_groups)), dim3(BLS_BLOCK), n_groups, (const uint32_t*)d_midx, (uint64_t)m.n,
      rows_wanted ? (const int32_t*)m.nolines : (const int32_t*)nullptr, d_cmsg, d_mwalk);
   const uint32_t* rows = nullptr;
   if (rows_wanted) {  // one plan per call: a named entry without usable rows makes every item walk
-    uint32_t* h_walk = (uint32_t*)hsmall_take(c, 4);
-    if (!h_walk) return drain(fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted"));
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_walk, d_mwalk, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-      return drain(fail(BLSGPU_E_HIP, "k_msgset_check failed"));
-    rows = *h_walk == 0 ? m.lines : nullptr;
+    uint32_t walk;
+    if ((rc = word_back(c, d_mwalk, &walk))) return drain(c, rc);
+    rows = walk == 0 ? m.lines : nullptr;
   }
   KL(KID_KEYSET_GATHER, k_keyset_gather, dim3(blocks_for(n_groups * (asz / 4))), dim3(BLS_BLOCK), n_groups, asz / 4, (const uint32_t*)d_cmsg, (const uint32_t*)m.aff,
      0, (uint32_t*)d_haff);
   PairTables t = pairs_walked(sg == 1 ? 2 : 0);
-  if (indexed) {
-    if ((rc = keyset_check(c, k, (const uint32_t*)d_idx, n, nullptr, n, d_cidx, d_pre, d_walk))) return drain(rc);
-    if (sg == 1) {            // (d_walk is set for such a set only: keyset_lines_wanted)
-      t.key.of = d_cidx;
-      if (d_walk && (rc = keyset_lines_decide(c, k, d_walk, &t.key.rows))) return drain(rc);
-    }
-    const size_t cnt_ = n;
-    KEYSET_GATHER(psz / 4, k.aff, 0, d_kaff);
-    if (d_keys != d_kaff)
-      with_group(k.group, [&](auto G) { KL(KID_KEYSET_GATHER, k_keyset_to_proj<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_kaff, d_keys); });
-    d_pks = d_keys;
-  }
+  const uint8_t* d_keys;
+  if ((rc = keys.stage(c, n, &d_keys, &t.key))) return drain(c, rc);      // t.key: read with fixed_g2 = 2 only
   const bool split_rows = rows && pair_path(n) == PATH_LANE_SPLIT;        // the table form of the line kernel: the signature's pair first
   with_group(sg, [&](auto G) {
-    KL(KID_PREPARE_SHARED, k_prepare_shared<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, (const uint8_t*)d_pks, (const uint8_t*)d_sigs, fmt,
+    KL(KID_PREPARE_SHARED, k_prepare_shared<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, n_groups, d_ioffs, d_keys, (const uint8_t*)d_sigs, fmt,
        (const uint8_t*)d_haff, d_pairs, d_status, split_rows ? 1 : 0, d_group);
   });
   KL(KID_MSGSET_CHECK, k_msgset_mark, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_group, (const uint32_t*)d_cmsg, d_status, d_msg_of);
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
+  if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "a message set kernel failed to launch"));
   if (rows) {
     TabledG2& role = split_rows ? t.shared : t.msg;
     role.rows = rows;
     role.of = d_msg_of;
   }
-  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, t))) return drain(rc);
-  if (indexed) {
-    KL(KID_KEYSET_FIN, k_keyset_fin, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const unsigned long long*)d_pre, d_status);
+  if ((rc = run_pairing2(c, n, d_pairs, d_f, d_status, t))) return drain(c, rc);
+  if (keys.fin(c, n, d_status)) {       // the message index's precedence once more, over what the key set had to say
     KL(KID_MSGSET_CHECK, k_msgset_mark, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint32_t*)d_group, (const uint32_t*)d_cmsg, d_status, (uint32_t*)nullptr);
-    if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
+    if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "k_keyset_fin launch failed"));
   }
   return status_out_and_sync(c, status, d_status, n);
 }
+}  // extern "C++"
 int blsgpu_verify_msgset_batch(uint64_t msgset, const uint32_t* msg_idx, const void* pks, const void* sigs, const uint64_t* item_offsets, size_t n_groups, int fmt,
                                int32_t* status) try {
-  return msgset_verify(msgset, msg_idx, false, 0, nullptr, pks, sigs, item_offsets, n_groups, fmt, status);
+  MsgSet m;
+  int rc = set_find(msgset, m);
+  if (rc) return rc;
+  const item_keys_by_value keys = {pks, m.sig_group, fmt};
+  return msgset_verify(m, keys, msg_idx, sigs, item_offsets, n_groups, fmt, status);
 }
 API_CATCH
 int blsgpu_verify_msgset_indexed_batch(uint64_t msgset, const uint32_t* msg_idx, uint64_t keyset, const uint32_t* idx, const void* sigs,
                                        const uint64_t* item_offsets, size_t n_groups, int fmt, int32_t* status) try {
-  return msgset_verify(msgset, msg_idx, true, keyset, idx, nullptr, sigs, item_offsets, n_groups, fmt, status);
+  MsgSet m;
+  KeySet k;
+  int rc = msgset_keyset_find(msgset, m, keyset, k);
+  if (rc) return rc;
+  const item_keys_indexed keys = {k, idx, fmt};
+  return msgset_verify(m, keys, msg_idx, sigs, item_offsets, n_groups, fmt, status);
 }
 API_CATCH
 
@@ -7406,10 +7358,7 @@ static int aggregate_msgset_run(Ctx* c, const MsgSet& m, const Keys& keys, const
   std::iota(bset.begin(), bset.end(), 0u);
   std::vector<uint64_t> hm, soffs;
   std::vector<uint32_t> ssid;
-  auto drain = [&](int r) {
-    (void)hipStreamSynchronize(c->stream);      // the uploads read this frame's vectors
-    return r;
-  };
+  // the ways out through drain(c, rc): the uploads read this frame's vectors
   HIPCK(hipMemcpyAsync(d_bset, bset.data(), 4 * n_sets, hipMemcpyHostToDevice, c->stream));
   HIPCK(hipMemsetAsync(d_skipped, 0, 4 * n_sets, c->stream));
   HIPCK(hipMemsetAsync(d_first, 0xff, 4 * n_sets, c->stream));
@@ -7434,14 +7383,14 @@ static int aggregate_msgset_run(Ctx* c, const MsgSet& m, const Keys& keys, const
     KL(KID_AGGM_CLASS, k_aggm_reps, dim3(blocks_for(Tz)), dim3(BLS_BLOCK), T, (const uint32_t*)d_slot, (const uint32_t*)d_tab, d_isrep);
   }
   // c. the classes numbered set after set
-  if ((rc = run_scan_u32(c, KID_AGGM_CLASS, Tz, d_isrep, d_rank, d_tiles))) return drain(rc);
+  if ((rc = run_scan_u32(c, KID_AGGM_CLASS, Tz, d_isrep, d_rank, d_tiles))) return drain(c, rc);
   if (T)
     KL(KID_AGGM_CLASS, k_aggm_number, dim3(blocks_for(T)), dim3(BLS_BLOCK), T, (const uint32_t*)d_slot, (const uint32_t*)d_tab, (const uint32_t*)d_rank,
        (const uint32_t*)d_sid, (const uint32_t*)d_cmsg, d_cid, d_csid, d_cent, d_crep, d_count);
   KL(KID_AGGM_CLASS, k_aggm_offsets, dim3(blocks_for(n_sets + 1)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_rank, d_coffs);
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_back, d_rank + T, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipMemcpyAsync(h_back + 1, d_walk, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
-    return drain(fail(BLSGPU_E_HIP, "the class kernels failed"));
+    return drain(c, fail(BLSGPU_E_HIP, "the class kernels failed"));
   const size_t C = h_back[0], M = C + n_sets;
   const uint32_t* rows = rows_wanted && h_back[1] == 0 ? m.lines : nullptr;      // one plan per call: a named entry without usable rows makes every item walk
   if (C > T) return fail(BLSGPU_E_HIP, "internal: more classes than pairs");
@@ -7474,12 +7423,12 @@ static int aggregate_msgset_run(Ctx* c, const MsgSet& m, const Keys& keys, const
        (const uint32_t*)d_skipped, (const uint32_t*)d_first, best, kp, fmt, merged ? (const uint8_t*)d_part : (const uint8_t*)nullptr, (const uint64_t*)d_so,
        (const uint8_t*)m.aff, (const uint8_t*)d_sigs, d_pairs, d_bad, d_sigid);
   });
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a class kernel failed to launch"));
+  if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "a class kernel failed to launch"));
   // f., g. one Miller value per item in rounds of at most one machine round, as aggregate_batch_run forms them
   const size_t per_round = agg_round_size(M, round);
   const size_t lanes_round = row_stride(lanes_for(per_round)), lanes_fx = row_stride(lanes_for(fx_chunk));
   if (lines_reserve(c, std::max((size_t)MILLER_ENTRIES * LINE3_WORDS_H * 4 * lanes_round, (size_t)FX_STORE_WORDS * 4 * lanes_fx)))
-    return drain(fail(BLSGPU_E_HIP, "no room for the line workspace"));
+    return drain(c, fail(BLSGPU_E_HIP, "no room for the line workspace"));
   for (size_t first = 0; first < M; first += per_round) {
     const size_t cnt = std::min(per_round, M - first), nlanes = lanes_for(cnt), lanes = row_stride(nlanes);
     const size_t cnt_rows = rows && first < C ? std::min(cnt, C - first) : 0, cnt_walk = cnt - cnt_rows, walk0 = first + cnt_rows;
@@ -7507,25 +7456,20 @@ static int aggregate_msgset_run(Ctx* c, const MsgSet& m, const Keys& keys, const
     launch_finalexp_chunk(c, n_sets, first, std::min(fx_chunk, n_sets - first), d_rec, d_stb, knobs().finalexp_seg != 0);
   KL(KID_AGG_SEG_FIN, k_agg_batch_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, o, (const uint32_t*)d_bset, best, (const uint32_t*)d_slot,
      (const uint32_t*)d_minidx, (const uint32_t*)d_first, (const uint32_t*)d_sigid, (const int32_t*)d_stb, d_status, d_aux);
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a kernel of the aggregate verify failed to launch"));
-  if ((rc = keys.fin(c, d_status, d_aux))) return drain(rc);
+  if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "a kernel of the aggregate verify failed to launch"));
+  if ((rc = keys.fin(c, d_status, d_aux))) return drain(c, rc);
   KL(KID_AGG_SEG_FIN, k_aggm_fin, dim3(blocks_for(n_sets)), dim3(BLS_BLOCK), n_sets, (const uint32_t*)d_skipped, d_status, d_aux);
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_aggm_fin failed to launch"));
-  if (aux && (rc = stage_back(c, aux, d_aux, 16 * n_sets))) return drain(rc);
-  return drain(status_out_and_sync(c, status, d_status, n_sets));
+  if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "k_aggm_fin failed to launch"));
+  if (aux && (rc = stage_back(c, aux, d_aux, 16 * n_sets))) return drain(c, rc);
+  return drain(c, status_out_and_sync(c, status, d_status, n_sets));
 }
 }  // extern "C++"
 static int aggregate_msgset_entry(uint64_t msgset, const uint32_t* msg_idx, bool indexed, uint64_t keyset, const uint32_t* idx, const void* pks,
                                   const uint64_t* set_offsets, size_t n_sets, const void* sigs, int fmt, int32_t* status, uint64_t* aux) {
   MsgSet m;
-  int rc = set_find(msgset, m);
-  if (rc) return rc;
   KeySet k;
-  if (indexed) {
-    if ((rc = set_find(keyset, k))) return rc;
-    if (k.sig_group != m.sig_group) return fail(BLSGPU_E_ARG, "the key set belongs to the other orientation");
-    if (k.dev != m.dev || k.devidx != m.devidx) return fail(BLSGPU_E_ARG, "the key set and the message set live on different devices");
-  }
+  int rc = indexed ? msgset_keyset_find(msgset, m, keyset, k) : set_find(msgset, m);
+  if (rc) return rc;
   const int sg = m.sig_group;
   if ((rc = check_common(sg, m.scheme, fmt))) return rc;
   if (!set_offsets) return fail(BLSGPU_E_ARG, "null set_offsets");
@@ -7734,15 +7678,12 @@ static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool
   const uint64_t* d_woffs = nullptr;
   if ((rc = stage_in(c, idx, 4 * n, &d_idx))) return rc;
   if ((rc = stage_in(c, us, ub, &d_us))) return rc;
-  auto drain = [&](int r) {
-    (void)hipStreamSynchronize(c->stream);      // the upload reads woffs
-    return r;
-  };
+  // the ways out through drain(c, rc): the upload reads woffs
   if (ct) {
     if ((rc = stage_in(c, vs, 32 * n, &d_vs))) return rc;
     if ((rc = stage_in(c, ws, total, &d_ws))) return rc;
     if ((rc = stage_in(c, ct_schemes, n, &d_cs))) return rc;
-    if ((rc = upload_offsets(c, woffs, &d_woffs))) return drain(rc);
+    if ((rc = upload_offsets(c, woffs, &d_woffs))) return drain(c, rc);
   }
   Carver mem{c};
   uint8_t* d_frames = ct ? (total ? mem.stage_out<uint8_t>(frames, total) : c->arena) : nullptr;
@@ -7756,10 +7697,10 @@ static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool
   uint8_t* d_u_raw = wire ? mem.take<uint8_t>(u_raw) : nullptr;
   int32_t* d_dec_u = wire ? mem.take<int32_t>(4 * n) : nullptr;
   uint32_t* d_f = split ? mem.take<uint32_t>((size_t)WS_F_WORDS * 4 * n) : nullptr;
-  if (!mem.ok) return drain(fail(BLSGPU_E_HIP, "internal: arena too small"));
+  if (!mem.ok) return drain(c, fail(BLSGPU_E_HIP, "internal: arena too small"));
   if (ct && total && d_frames != frames && hipMemsetAsync(d_frames, 0, total, c->stream) != hipSuccess)   // an item that is not opened hands back zeros
-    return drain(fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
-  if (hipMemsetAsync(d_walk, 0, 4, c->stream) != hipSuccess) return drain(fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
+    return drain(c, fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
+  if (hipMemsetAsync(d_walk, 0, 4, c->stream) != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "hipMemsetAsync failed"));
   int kfmt = fmt;
   if (wire) {
     const int legacy = fmt == BLSGPU_FMT_LEGACY;
@@ -7775,18 +7716,15 @@ static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool
   });
   const uint32_t* rows = nullptr;
   if (rows_wanted) {  // one plan per call: a named entry without usable rows makes every item walk
-    uint32_t* h_walk = (uint32_t*)hsmall_take(c, 4);
-    if (!h_walk) return drain(fail(BLSGPU_E_HIP, "internal: pinned record buffer exhausted"));
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_walk, d_walk, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-      return drain(fail(BLSGPU_E_HIP, "k_sigset_prepare failed"));
-    rows = *h_walk == 0 ? s.lines : nullptr;
+    uint32_t walk;
+    if ((rc = word_back(c, d_walk, &walk))) return drain(c, rc);
+    rows = walk == 0 ? s.lines : nullptr;
   }
   run_pairing_values(c, n, d_pairs, d_flag, d_gt, d_f, rows, d_ent, (size_t)s.n * SIGSET_ENTRY_LINE_BYTES);
   if (!ct) {
-    if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "a pairing-value kernel failed to launch"));
-    if ((rc = stage_back(c, out_gt, d_gt, (size_t)GT_BYTES * n))) return drain(rc);
-    if ((rc = stage_back(c, status, d_status, 4 * n))) return drain(rc);
+    if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "a pairing-value kernel failed to launch"));
+    if ((rc = stage_back(c, out_gt, d_gt, (size_t)GT_BYTES * n))) return drain(c, rc);
+    if ((rc = stage_back(c, status, d_status, 4 * n))) return drain(c, rc);
     SYNC_FLUSH(c);
     return 0;
   }
@@ -7794,9 +7732,9 @@ static int sigset_run(uint64_t sigset, const uint32_t* idx, const void* us, bool
     KL(KID_TIMECRYPT_OPEN, k_timecrypt_open<G()>, dim3(blocks_for(n)), dim3(BLS_BLOCK), n, (const uint8_t*)d_gt, (const uint8_t*)d_us, kfmt, (const uint8_t*)d_vs,
        (const uint8_t*)d_ws, d_woffs, d_frames, d_range, d_status);
   });
-  if (hipGetLastError() != hipSuccess) return drain(fail(BLSGPU_E_HIP, "k_timecrypt_open failed to launch"));
-  if (total && (rc = stage_back(c, frames, d_frames, total))) return drain(rc);
-  if ((rc = stage_back(c, pt_range, d_range, 16 * n))) return drain(rc);
+  if (hipGetLastError() != hipSuccess) return drain(c, fail(BLSGPU_E_HIP, "k_timecrypt_open failed to launch"));
+  if (total && (rc = stage_back(c, frames, d_frames, total))) return drain(c, rc);
+  if ((rc = stage_back(c, pt_range, d_range, 16 * n))) return drain(c, rc);
   return status_out_and_sync(c, status, d_status, n);
 }
 

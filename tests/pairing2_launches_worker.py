@@ -7,13 +7,34 @@ argv: spec.pickle, written by the parent:
      'steps': [{'name', 'keyset', 'scheme', 'idx', 'sigs', 'msgs'}              -- verify_indexed_batch
                | {'name', 'sg', 'scheme', 'groups': [(msg, pks, sigs)]}         -- verify_shared_batch
                | {'name', 'msgset', 'groups': [(msg_idx, pks, sigs)]}           -- verify_msgset_batch
-               | {'name', 'keyset', 'scheme', 'cts', 'shares'}]}                -- signcrypt_share_verify_indexed_batch"""
+               | {'name', 'keyset', 'scheme', 'cts', 'shares'}                  -- signcrypt_share_verify_indexed_batch
+               | {'name', 'door': a name of DOORS, ...}]}                       -- tests/test_gpu_item_keys_launches.py
+A step with 'door' may give {'aux': [[aux0, aux1] per set]} next to 'st' (the aggregate doors)."""
 import json
 import os
 import pickle
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def flat(rows):
+    return {'st': [s for g in rows for s in g]}
+
+
+def with_aux(rows):
+    return {'st': [s for s, _ in rows], 'aux': [list(a) for _, a in rows]}
+
+
+# door -> fn(api, key sets, message sets, step): {'st': flat statuses[, 'aux']}
+DOORS = {
+    'verify_indexed': lambda api, ks, ms, s: {'st': api.verify_indexed_batch(ks[s['keyset']], s['scheme'], s['idx'], s['sigs'], s['msgs'], fmt=s['fmt'])},
+    'verify_shared_indexed': lambda api, ks, ms, s: flat(api.verify_shared_indexed_batch(ks[s['keyset']], s['scheme'], s['groups'])),
+    'verify_msgset_indexed': lambda api, ks, ms, s: flat(api.verify_msgset_indexed_batch(ms[s['msgset']], ks[s['keyset']], s['groups'])),
+    'signcrypt_share_verify': lambda api, ks, ms, s: flat(api.signcrypt_share_verify_batch(s['sg'], s['scheme'], s['cts'], s['pairs'])),
+    'aggregate_verify_indexed': lambda api, ks, ms, s: with_aux(api.aggregate_verify_indexed_batch(ks[s['keyset']], s['scheme'], s['sets'])),
+    'aggregate_verify_msgset_indexed': lambda api, ks, ms, s: with_aux(api.aggregate_verify_msgset_indexed_batch(ms[s['msgset']], ks[s['keyset']], s['sets'])),
+}
 
 
 def main():
@@ -29,7 +50,11 @@ def main():
     out = {}
     seen = {k: v[1] for k, v in api.profile_read().items()}
     for step in spec['steps']:
-        if 'cts' in step:
+        more = {}
+        if 'door' in step:
+            more = DOORS[step['door']](api, ksets, msets, step)
+            st = more.pop('st')
+        elif 'cts' in step:
             st = [s for g in api.signcrypt_share_verify_indexed_batch(step['scheme'], ksets[step['keyset']], step['cts'], step['shares']) for s in g]
         elif 'msgset' in step:
             st = [s for g in api.verify_msgset_batch(msets[step['msgset']], step['groups']) for s in g]
@@ -38,7 +63,7 @@ def main():
         else:
             st = api.verify_indexed_batch(ksets[step['keyset']], step['scheme'], step['idx'], step['sigs'], step['msgs'])
         now = {k: v[1] for k, v in api.profile_read().items()}
-        out[step['name']] = {'st': st, 'launches': {k: now[k] - seen.get(k, 0) for k in now if now[k] != seen.get(k, 0)}}
+        out[step['name']] = dict(more, st=st, launches={k: now[k] - seen.get(k, 0) for k in now if now[k] != seen.get(k, 0)})
         seen = now
     for s in list(ksets.values()) + list(msets.values()):
         s.close()

@@ -70,18 +70,18 @@ def spec():
     return {'keysets': keysets, 'msgsets': msgsets, 'steps': steps}, want
 
 
-def measure(plan, tmp_dir, timeout=240):
-    """the steps in one worker under the plan's knobs: {step: {'launches': {kernel: count}, 'status_sha256': ..., 'st': [...]}}"""
+def measure(plan, tmp_dir, timeout=240, worker_spec=None):
+    """the steps (of this file's spec, or of worker_spec) in one worker under the plan's knobs:
+    {step: {'launches': {kernel: count}, 'status_sha256': ..., 'st': [...][, 'aux': what an aggregate door gave]}}"""
     path = os.path.join(str(tmp_dir), 'pairing2.pickle')
     with open(path, 'wb') as f:
-        pickle.dump(spec()[0], f)
+        pickle.dump(worker_spec or spec()[0], f)
     keep = {k: v for k, v in os.environ.items() if not k.startswith('BLSGPU_') or k == 'BLSGPU_LIB'}
     r = subprocess.run([sys.executable, os.path.join(util.ROOT, 'tests', 'pairing2_launches_worker.py'), path], env=dict(keep, **PLANS[plan]),
                        capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (plan, r.returncode, r.stderr[-3000:])
     got = json.loads(r.stdout.strip().splitlines()[-1])
-    return {name: {'launches': g['launches'], 'status_sha256': hashlib.sha256(struct.pack('<%di' % len(g['st']), *g['st'])).hexdigest(), 'st': g['st']}
-            for name, g in got.items()}
+    return {name: dict(g, status_sha256=hashlib.sha256(struct.pack('<%di' % len(g['st']), *g['st'])).hexdigest()) for name, g in got.items()}
 
 
 @pytest.mark.parametrize('plan', sorted(PLANS))
